@@ -9,8 +9,11 @@ One step = one trace of every ray of the batch = ONE launch of the reference's k
 (gpu_ray_tracing_pro_fullColor.py:169-177 issues num_iter = 4 of them, each starting from
 the RNG states the previous one left and adding its out-couplings to the eyebox grid).  The
 headline ``value`` times K such steps as K separate launches (``num_iter = 1`` each, SURVEY.md
-§8(d)), inputs already resident in HBM, plus the eyebox collective at N > 1.  More rates of the
-same batch ride along: ``main_job`` -- the reference's job shape, 4 chained traces issued as one
+§8(d)), inputs already resident in HBM, plus the eyebox collective at N > 1.  A plain run does
+only that: set-up, W warm-up launches, the K timed steps, the result line.  ``--dump-outputs DIR``
+also writes what the timed steps left (the eyebox grid, the RNG states, the counters; the inputs are
+seeded, so two builds given the same arguments can be compared file by file).  Everything below is
+measured only with ``--full``.  More rates of the same batch ride along: ``main_job`` -- the reference's job shape, 4 chained traces issued as one
 call (the engine fuses them into one persistent launch, bit-identical to 4 launches) --,
 ``fused`` -- all K steps in one call -- and ``long_region`` -- the headline's single launches
 over a timed region of at least LONG_STEPS steps (>= 50 ms; the driver's K = 20 gives a 5-ms region).
@@ -63,6 +66,8 @@ FUSED_EMULATE = ("C3", "C4")    # emulated_strong also times the fused shape (th
 # ~153.6 GB/s per-link figure of the node, and one RCCL gather call adds a fixed cost
 XGMI_LINK_GBPS = 76.8
 RCCL_CALL_MS = 0.03
+DUMP_BYTES = 64_000_000         # --dump-outputs: upper bound on the bytes of all files written
+DUMP_SEED = 0                   # --dump-outputs: seed of the element sample of an array over its share
 
 
 def parse(argv=None):
@@ -84,9 +89,17 @@ def parse(argv=None):
                          "or sum-reduce the whole grid")
     ap.add_argument("--emulate-ranks", type=int, default=0, metavar="N",
                     help="one GPU: time each of N ranks' shards in turn (predicted N-GPU step time)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else: the lifetimes of a trace, the evented "
+                         "pass behind the roofline, the binding record, the main_job / fused / region / long_region "
+                         "/ weak / emulated_strong records and the CPU baseline (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps left -- matrix_EB (float32), rng_states and the stats "
+                         "counters (float64) -- as DIR/<name>.npy, at most DUMP_BYTES in all (a larger array as a "
+                         "fixed seeded sample of its elements)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the main_job / fused / long_region / weak / emulated_strong records")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: skip the main_job / fused / long_region / weak / emulated_strong records")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend for N > 1 (nccl = RCCL over xGMI; gloo only to rehearse the "
                          "N > 1 path on a one-GPU box together with --one-device)")
@@ -123,6 +136,52 @@ def lifetime_histogram(per_ray) -> dict:
             "rays": int(b.size), "by_bounces": counts}
 
 
+def first_trace_lifetimes(a, scene, shard, rays, rng, eb, R, dev) -> dict:
+    """--full's first warm-up launch: one trace of the shard that also records the per-ray bounce
+    counts (lifetime_histogram) and the bounces by kind."""
+    import torch
+
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import new_stats, trace_fullcolor
+    per_ray = torch.zeros(shard.n_rays, dtype=torch.int32, device=dev)
+    kinds = None
+    if shard.n_rays:
+        g = shard.gid
+        kw = dict(gid_offset=g.offset) if g.offset is not None else dict(
+            gid_blocks=torch.as_tensor(g.block_gid, device=dev), gid_block_rays=R)
+        st0 = new_stats(dev)
+        trace_fullcolor(scene, rays, rng, eb, per_ray_bounces=per_ray, variant=a.variant, stats=st0, **kw)
+        s0 = [int(v) for v in st0.cpu()]
+        traced = shard.n_rays - s0[1]
+        kinds = {"in_coupling": traced, "interactions": s0[5], "hops_switches_exits": s0[0] - traced - s0[5],
+                 "note": "one trace's bounces by kind (wgrt_trace_stats): the in-coupling event of every ray "
+                         "(GRTF:860-904), the loop iterations with a Monte-Carlo draw (coupler interactions), and "
+                         "the iterations without one (miss hops, R3->R4 switches, terminations at GRTF:906 / "
+                         "1244-1246)"}
+    lifetimes = lifetime_histogram(per_ray)
+    if kinds is not None:
+        lifetimes["kinds"] = kinds
+    return lifetimes
+
+
+def dump_outputs(outdir: str, arrays: dict) -> dict:
+    """--dump-outputs: every array as ``outdir/<name>.npy``, DUMP_BYTES in all at the most.  The
+    arrays are taken smallest first; one larger than an even share of what is left is written as
+    a sample of its flattened elements (sorted indices drawn with DUMP_SEED, the same for every
+    run of the same shapes).  Returns name -> elements written."""
+    os.makedirs(outdir, exist_ok=True)
+    left = DUMP_BYTES - 1024 * len(arrays)   # the .npy headers
+    written = {}
+    for i, (name, arr) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].nbytes)):
+        share = left // (len(arrays) - i)
+        if arr.nbytes > share:
+            k = share // arr.itemsize
+            arr = arr.reshape(-1)[np.sort(np.random.default_rng(DUMP_SEED).integers(0, arr.size, k))]
+        np.save(os.path.join(outdir, name + ".npy"), arr)
+        left -= arr.nbytes
+        written[name] = int(arr.size)
+    return written
+
+
 def pmc_roofline(path: str, key: str, sha: str):
     """The issue-side (VALU) roofline of the trace kernel from a PMC summary of this build
     (tools/pmc_summary.py), or None when no summary matches the library hash."""
@@ -147,8 +206,7 @@ def main(argv=None):
                                                                                 hip_tracer, make_shard,
                                                                                 reduce_eyebox, replica_shard,
                                                                                 run_steps, split_calls, timed_run)
-    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import (Scene, check_stats, new_stats, reserve,
-                                                                           trace_fullcolor)
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import (Scene, check_stats, new_stats, reserve)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -208,39 +266,68 @@ def main(argv=None):
         check_stats(stats)
         return elapsed, b_total, b_local, [s.elapsed_time(e) for s, e in ev]
 
-    # warm-up: W separate launches (and one fused call, so the fused kernels are loaded too); the
-    # first one records the per-ray lifetimes and the bounce kinds of a trace
-    per_ray = torch.zeros(shard.n_rays, dtype=torch.int32, device=dev)
-    kinds = None
-    if shard.n_rays:
-        g = shard.gid
-        kw = dict(gid_offset=g.offset) if g.offset is not None else dict(
-            gid_blocks=torch.as_tensor(g.block_gid, device=dev), gid_block_rays=R)
-        st0 = new_stats(dev)
-        trace_fullcolor(scene, rays, rng, eb, per_ray_bounces=per_ray, variant=a.variant, stats=st0, **kw)
-        s0 = [int(v) for v in st0.cpu()]
-        traced = shard.n_rays - s0[1]
-        kinds = {"in_coupling": traced, "interactions": s0[5], "hops_switches_exits": s0[0] - traced - s0[5],
-                 "note": "one trace's bounces by kind (wgrt_trace_stats): the in-coupling event of every ray "
-                         "(GRTF:860-904), the loop iterations with a Monte-Carlo draw (coupler interactions), and "
-                         "the iterations without one (miss hops, R3->R4 switches, terminations at GRTF:906 / "
-                         "1244-1246)"}
-    lifetimes = lifetime_histogram(per_ray)
-    if kinds is not None:
-        lifetimes["kinds"] = kinds
-    run_steps(tracer, rays, rng, eb, shard.gid, max(a.warmup - 1, 0), 1)
-    if not a.no_extras:
+    extras_on = a.full and not a.no_extras
+    # warm-up: W separate launches; with --full the first one records the per-ray lifetimes and the
+    # bounce kinds of a trace, and one fused call follows, so the fused kernels are loaded too
+    lifetimes = None
+    if a.full:
+        lifetimes = first_trace_lifetimes(a, scene, shard, rays, rng, eb, R, dev)
+    run_steps(tracer, rays, rng, eb, shard.gid, max(a.warmup - 1, 0) if a.full else a.warmup, 1)
+    if extras_on:
         run_steps(tracer, rays, rng, eb, shard.gid, 2, 0)
     if world > 1:
         # one untimed eyebox collective: RCCL sets up a collective's connections on its first call
         # of that size class, which would otherwise land in the first timed region
         collect(eb, None)
     torch.cuda.synchronize()
-    # the headline: K separate launches with nothing else on the stream; then the same K launches
-    # again with a HIP event pair around each, for the kernel duration the roofline divides by
-    # (event records between the launches would be part of the timed steps otherwise)
+    # the headline: K separate launches with nothing else on the stream
     elapsed, bounces_total, bounces_local, _ = timed(a.steps, 1, events=False)
     value = bounces_total / elapsed
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        # what a caller of these K steps holds now: the eyebox grid (on rank 0, after the collective),
+        # this rank's RNG states (uint32, exact in float64) and the timed region's counters
+        dumped = dump_outputs(a.dump_outputs, {"matrix_EB": eb.cpu().numpy(),
+                                               "rng_states": rng.cpu().numpy().view(np.uint32).astype(np.float64),
+                                               "stats": stats.cpu().numpy().astype(np.float64)})
+    sha = lib_sha16()
+    par = (f"replicas x{world} (global ray ids offset per rank)" if weak else
+           f"fov-lambda block shards x{world} ({a.assign})")
+    if world > 1:
+        coll = "gather of own eyebox slabs" if (a.collective == "gather" and not weak) else "reduce(EB)"
+        par += (f" + RCCL {coll}" if a.dist_backend == "nccl" else
+                f" + gloo {coll}, rehearsal" + (" on one GPU" if a.one_device else ""))
+    line = {
+        "metric": w.metric(),
+        "value": round(value, 1), "unit": "ray-bounces/s", "n_gpus": world, "steps": a.steps,
+        "warmup": a.warmup, "ms_per_step": round(elapsed / a.steps * 1e3, 4), "higher_is_better": True,
+        "scaling": a.scaling, "vs_baseline": None, "dtype": "f64", "full": a.full,
+        "data": "synthetic (seeded LUT and ray origins; geometry from the couplers_coor restatement)",
+        "config": {"workload": f"{cname}: {w.name}", "nx": nx, "ny": ny, "lambdas": lambdas,
+                   "num_rays_per_FoV": R, "rays_total": w.n_rays * (world if weak else 1),
+                   "rays_rank0": shard.n_rays,
+                   "lut": f"synthetic seed {a.lut_seed} profile {w.profile}", "gap_scale": w.gap_scale,
+                   "parallelism": par, "kernel_variant": a.variant, "steps_per_launch": 1, "lib_sha16": sha,
+                   "scene_create_s": round(t_scene, 3), "lifetimes_rank0": lifetimes,
+                   "lut_staging": ("BASELINE config 3 names LUT tiles staged in LDS: built and measured "
+                                   "slower (single launch +28-37 %, DESIGN.md §5.4), so the tiles are read "
+                                   "through L1/L2 and what runs is not LDS-staged")},
+    }
+    if dumped is not None:
+        line["dumped"] = {"dir": a.dump_outputs, "elements": dumped}
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        scene.close()
+        if world > 1:
+            dist.destroy_process_group()
+
+    if not a.full:
+        return finish()
+    # --full: the same K launches again with a HIP event pair around each, for the kernel duration
+    # the roofline divides by (event records between the launches would be part of the timed steps
+    # otherwise), then every other record of the line
     _el, _bt, ev_bounces_local, call_ms = timed(a.steps, 1)
     binding = None
     if world == 1 and cname == "C3" and shard.n_rays and a.variant in (0, 7):
@@ -284,7 +371,6 @@ def main(argv=None):
         kavg_s = float(np.mean(call_ms)) / 1e3
         bpl = ev_bounces_local / len(call_ms)
         achieved = bpl * ALGO_BYTES_PER_BOUNCE / kavg_s / 1e9
-        sha = lib_sha16()
         traffic, traffic_raw, measured, traffic_note = None, None, None, "no PMC pass recorded for this library build"
         try:
             with open(a.traffic_json) as f:
@@ -327,40 +413,10 @@ def main(argv=None):
         cpu = None
         if world == 1 and not a.no_cpu_baseline:
             cpu = cpu_baseline(geom, luts, points, nx, ny, lambdas, R, a.cpu_seconds)
-        par = (f"replicas x{world} (global ray ids offset per rank)" if weak else
-               f"fov-lambda block shards x{world} ({a.assign})")
-        if world > 1:
-            coll = "gather of own eyebox slabs" if (a.collective == "gather" and not weak) else "reduce(EB)"
-            par += (f" + RCCL {coll}" if a.dist_backend == "nccl" else
-                    f" + gloo {coll}, rehearsal" + (" on one GPU" if a.one_device else ""))
-        line = {
-            "metric": w.metric(),
-            "value": round(value, 1), "unit": "ray-bounces/s", "n_gpus": world, "steps": a.steps,
-            "warmup": a.warmup, "ms_per_step": round(elapsed / a.steps * 1e3, 4), "higher_is_better": True,
-            "scaling": a.scaling, "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic (seeded LUT and ray origins; geometry from the couplers_coor restatement)",
-            "config": {"workload": f"{cname}: {w.name}", "nx": nx, "ny": ny, "lambdas": lambdas,
-                       "num_rays_per_FoV": R, "rays_total": w.n_rays * (world if weak else 1),
-                       "rays_rank0": shard.n_rays,
-                       "lut": f"synthetic seed {a.lut_seed} profile {w.profile}", "gap_scale": w.gap_scale,
-                       "parallelism": par, "kernel_variant": a.variant, "steps_per_launch": 1, "lib_sha16": sha,
-                       "scene_create_s": round(t_scene, 3), "lifetimes_rank0": lifetimes,
-                       "lut_staging": ("BASELINE config 3 names LUT tiles staged in LDS: built and measured "
-                                       "slower (single launch +28-37 %, DESIGN.md §5.4), so the tiles are read "
-                                       "through L1/L2 and what runs is not LDS-staged")},
-            "roofline": roofline,
-            "main_job": extras.get("main_job"),
-            "fused": extras.get("fused"),
-            "long_region": extras.get("long_region"),
-            "region": extras.get("region"),
-            "weak": extras.get("weak"),
-            "emulated_strong": emulated,
-            "cpu_baseline": cpu,
-        }
-        print(json.dumps(line), flush=True)
-    scene.close()
-    if world > 1:
-        dist.destroy_process_group()
+        line.update(roofline=roofline, main_job=extras.get("main_job"), fused=extras.get("fused"),
+                    long_region=extras.get("long_region"), region=extras.get("region"), weak=extras.get("weak"),
+                    emulated_strong=emulated, cpu_baseline=cpu)
+    finish()
 
 
 def region_cost(timed, call_ms, elapsed, ev_elapsed, steps):

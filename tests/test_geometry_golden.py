@@ -1,6 +1,6 @@
 """Pin couplers_coor.design_geometry to the reference geometry function (CC:122-750).
 
-``tests/golden/geometry_tables.npz`` holds the outputs of the reference's
+``tests/golden/geometry_tables_<k>.npz`` (parts of one table set) hold the outputs of the reference's
 ``couplers_coor_full_color`` run unmodified (``gen_golden.py geometry``, with a throwaway
 planar stand-in for shapely) at 3x3, 11x11, 21x21 and 100x75 FoV grids.  Every table the
 bounce kernel reads that shapely does not shape -- lut_gap, lut_TIR, eff_reg_FOV,
@@ -9,6 +9,7 @@ bit-identical.  eff_reg1 / eff_reg2 pass through shapely's LineString.simplify: 
 pinned to the stand-in's Douglas-Peucker (the same as the restatement's), not to GEOS.
 FC / OC come from shapely polygon clips and are not pinned (parity unpinned: shapely is absent).
 """
+import glob
 import os
 
 import numpy as np
@@ -16,14 +17,17 @@ import pytest
 
 from gpu_ray_tracing_for_waveguide_based_ar_display_amd.couplers_coor import CouplerGeometry, design_geometry
 
-PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "geometry_tables.npz")
+PATHS = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "geometry_tables_*.npz")))
 SIZES = [(3, 3), (11, 11), (21, 21), (100, 75)]
 
 
 @pytest.fixture(scope="module")
 def tables():
-    f = np.load(PATH, allow_pickle=False)
-    return {k: f[k] for k in f.files}
+    out = {}
+    for path in PATHS:
+        f = np.load(path, allow_pickle=False)
+        out.update({k: f[k] for k in f.files})
+    return out
 
 
 def _named(g: CouplerGeometry) -> dict:

@@ -26,6 +26,6 @@ d=$OUT/${TAG}_pmc_insts
 mkdir -p "$d"
 (cd /tmp && timeout -k 10 120 rocprofv3 --kernel-trace --output-format csv -d "$d" -o run \
    --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_INSTS_BRANCH SQ_INSTS_LDS -- \
-   python3 "$OLDPWD/bench.py" --no-cpu-baseline --no-extras --steps 10 --warmup 2 > "$d/log.txt" 2>&1)
+   python3 "$OLDPWD/bench.py" --full --no-cpu-baseline --no-extras --steps 10 --warmup 2 > "$d/log.txt" 2>&1)
 echo "pmc rc $?"
 exit 0

@@ -11,7 +11,7 @@ for n in "$@"; do
   d=$ROOT/gpurun_out/pmcab_$n/p0
   mkdir -p "$d"
   (cd /tmp && timeout -k 10 120 rocprofv3 --kernel-trace --output-format csv -d "$d" -o run --pmc $CTRS -- \
-      python3 "$ROOT/tools/with_lib.py" "$lib" "$ROOT/bench.py" --no-cpu-baseline --no-extras --steps 6 --warmup 2 > "$d/log.txt" 2>&1)
+      python3 "$ROOT/tools/with_lib.py" "$lib" "$ROOT/bench.py" --full --no-cpu-baseline --no-extras --steps 6 --warmup 2 > "$d/log.txt" 2>&1)
   rc=$?
   echo "$n rc=$rc"
   [ $rc -ne 0 ] && exit $rc

@@ -20,7 +20,7 @@ for p in "${PASSES[@]}"; do
   d=$ROOT/gpurun_out/${TAG}_pmc/p$i
   mkdir -p "$d"
   (cd /tmp && timeout -k 10 120 rocprofv3 --kernel-trace --output-format csv -d "$d" -o run --pmc $p -- \
-      python3 "$ROOT/bench.py" --no-cpu-baseline --no-extras --steps 10 --warmup 2 ${BENCH_ARGS:-} > "$d/log.txt" 2>&1)
+      python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-extras --steps 10 --warmup 2 ${BENCH_ARGS:-} > "$d/log.txt" 2>&1)
   rc=$?
   echo "pass $i rc=$rc: $p"
   if [ $rc -ne 0 ]; then exit $rc; fi

@@ -28,7 +28,7 @@ line = None
 for counter in ("FETCH_SIZE", "WRITE_SIZE"):
     d = tempfile.mkdtemp(prefix="pmc_", dir="/tmp")
     cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "run", "--pmc", counter,
-           "--", sys.executable, os.path.join(repo, "bench.py"), "--no-cpu-baseline", "--no-extras", "--steps", "5",
+           "--", sys.executable, os.path.join(repo, "bench.py"), "--full", "--no-cpu-baseline", "--no-extras", "--steps", "5",
            "--warmup", "1", "--traffic-json", "/dev/null"] + bench_args
     r = subprocess.run(cmd, cwd="/tmp", capture_output=True, text=True, timeout=600)
     if r.returncode != 0:
