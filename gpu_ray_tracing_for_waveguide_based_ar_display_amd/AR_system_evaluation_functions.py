@@ -189,11 +189,129 @@ def eye_perceive(matrix_EB, mask=None, step_y: int = 8, step_x: int = 12):
     return out
 
 
-def evaluation(matrix_EB):
-    """Drop-in for the reference's ``evaluation`` (EVAL:45-163)."""
+EB_ROWS, EB_COLS = 80, 120   # one (wavelength, FoV) slab of matrix_EB (MAIN:37)
+_dev_masks = {}
+
+
+def window_grid(ms: int = 30, step_y: int = 8, step_x: int = 12) -> tuple[int, int]:
+    """``(npy, npx)``: the eye positions an ``ms``-px pupil takes on an 80 x 120 slab at the given steps
+    (7 x 8 for the reference's 30 px at 8 / 12, EVAL:89-109)."""
+    if not 1 <= ms <= EB_ROWS or step_y < 1 or step_x < 1:
+        raise ValueError(f"need 1 <= ms <= {EB_ROWS} and steps >= 1, got ms={ms}, steps=({step_y}, {step_x})")
+    return (EB_ROWS - ms) // step_y + 1, (EB_COLS - ms) // step_x + 1
+
+
+def _square_mask(mask) -> np.ndarray:
+    m = pupil_mask() if mask is None else np.asarray(mask.cpu() if hasattr(mask, "cpu") else mask)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError(f"mask must be square, got shape {m.shape}")
+    return np.ascontiguousarray(m, dtype=np.float32)
+
+
+def _window_sums_host(eb: np.ndarray, slabs, mask: np.ndarray, step_y: int, step_x: int) -> np.ndarray:
+    """The specification of ``eyebox_window_sums`` (include/wgrt.h wgrt_eyebox_window_sums) in float64 numpy."""
+    ms = mask.shape[0]
+    npy, npx = window_grid(ms, step_y, step_x)
+    if eb.shape[-2:] != (EB_ROWS, EB_COLS):
+        raise ValueError(f"the grid's last two axes must be ({EB_ROWS}, {EB_COLS}), got {eb.shape}")
+    flat = eb.reshape(-1, EB_ROWS, EB_COLS)
+    n_slabs = flat.shape[0]
+    idx = np.arange(n_slabs, dtype=np.int64) if slabs is None else np.asarray(slabs, dtype=np.int64).reshape(-1)
+    ok = (idx >= 0) & (idx < n_slabs)
+    out = np.zeros((len(idx), 1 + npy * npx), dtype=np.float64)
+    m64 = mask.astype(np.float64)[None]
+    rows = np.nonzero(ok)[0]
+    for lo in range(0, len(rows), 256):   # 256 slabs as float64: a 20 MB temporary
+        rr = rows[lo:lo + 256]
+        part = flat[idx[rr]].astype(np.float64)
+        out[rr, 0] = part.sum(axis=(-1, -2))
+        for iy in range(npy):
+            for ix in range(npx):
+                y0, x0 = iy * step_y, ix * step_x
+                out[rr, 1 + iy * npx + ix] = (part[:, y0:y0 + ms, x0:x0 + ms] * m64).sum(axis=(-1, -2))
+    return out
+
+
+def _window_sums_device(eb, slabs, mask, step_y: int, step_x: int):
+    """``wgrt_eyebox_window_sums`` on ``eb``'s device and torch's current stream there; no host sync."""
+    import torch
+
+    from ._lib import check, load
+    from .engine import _stream_handle
+    if eb.dtype != torch.float32 or not eb.is_contiguous():
+        raise ValueError(f"a device grid must be contiguous float32, got {eb.dtype}"
+                         f"{'' if eb.is_contiguous() else ', not contiguous'}")
+    if tuple(eb.shape[-2:]) != (EB_ROWS, EB_COLS):
+        raise ValueError(f"the grid's last two axes must be ({EB_ROWS}, {EB_COLS}), got {tuple(eb.shape)}")
+    dev = eb.device
+    if mask is None:   # the reference's pupil: uploaded once per device
+        key = str(dev)
+        if key not in _dev_masks:
+            _dev_masks[key] = torch.from_numpy(pupil_mask()).to(dev)
+        m = _dev_masks[key]
+    elif isinstance(mask, torch.Tensor) and mask.device == dev:
+        m = mask.to(torch.float32).contiguous()
+    else:
+        m = torch.from_numpy(_square_mask(mask)).to(dev)
+    if m.dim() != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError(f"mask must be square, got shape {tuple(m.shape)}")
+    ms = int(m.shape[0])
+    npy, npx = window_grid(ms, step_y, step_x)
+    n_slabs = eb.numel() // (EB_ROWS * EB_COLS)
+    if slabs is None:
+        idx, n = None, n_slabs
+    else:
+        idx = torch.as_tensor(slabs, dtype=torch.int64, device=dev).reshape(-1).contiguous()
+        n = idx.numel()
+    out = torch.empty((n, 1 + npy * npx), dtype=torch.float64, device=dev)
+    check(load().wgrt_eyebox_window_sums(eb.data_ptr(), n_slabs, idx.data_ptr() if idx is not None else None, n,
+                                         m.data_ptr(), ms, int(step_y), int(step_x), out.data_ptr(),
+                                         _stream_handle(dev)), "wgrt_eyebox_window_sums")
+    return out
+
+
+def eyebox_window_sums(eb, slabs=None, mask=None, step_y: int = 8, step_x: int = 12):
+    """What anyone reads from the eyebox grid, per 80 x 120 slab: float64 ``[n, W]`` with column 0 the slab's
+    total (MAIN:186) and column ``1 + iy * npx + ix`` the sum over ``mask`` (default ``pupil_mask()``) placed at
+    ``(iy * step_y, ix * step_x)`` -- ``eye_perceive`` of the slab (EVAL:89-109); W = 57 by default.
+
+    ``eb``: ``[..., 80, 120]``, flattened to ``n_slabs`` slabs.  ``slabs``: the slab of each output row (any
+    order, repeats allowed; an index outside ``[0, n_slabs)`` gives a zero row), default every slab in order.
+    A contiguous float32 tensor on a HIP device is reduced there by ``wgrt_eyebox_window_sums`` (one pass over
+    the grid, on torch's current stream, no host sync) and a torch tensor is returned; a device tensor of
+    another dtype or layout raises ``ValueError``.  A numpy array or a host tensor takes the float64 numpy
+    statement of the same formula and returns a numpy array.  Sums are float64: an integer-valued grid (the
+    kernel adds exactly 1.0 per out-coupling, GRTF:154-165) gives the exact integers on both paths."""
+    if getattr(eb, "is_cuda", False):
+        return _window_sums_device(eb, slabs, mask, step_y, step_x)
+    if hasattr(eb, "detach"):   # a host tensor
+        eb = eb.detach().numpy()
+    if hasattr(slabs, "detach"):
+        slabs = slabs.detach().cpu().numpy()
+    return _window_sums_host(np.asarray(eb), slabs, _square_mask(mask), step_y, step_x)
+
+
+def perceive_from_window_sums(sums, shape, divisor, ms: int = 30, step_y: int = 8, step_x: int = 12) -> np.ndarray:
+    """``eye_perceive(matrix_EB / R / num_iter)`` from the window sums of the raw grid: ``sums[:, 1:] / divisor``
+    (``divisor = R * num_iter``) as float64 ``[L, NY, NX, npy, npx]``.  ``shape``: the grid's shape (its first
+    three axes ``L, NY, NX`` are used).  The host path divides every bin in float32 and sums in float32; this
+    divides the exact float64 sum once."""
+    if hasattr(sums, "detach"):
+        sums = sums.detach().cpu().numpy()
+    sums = np.asarray(sums, dtype=np.float64)
+    npy, npx = window_grid(ms, step_y, step_x)
+    nl, ny, nx = (int(v) for v in tuple(shape)[:3])
+    if sums.shape != (nl * ny * nx, 1 + npy * npx):
+        raise ValueError(f"window sums of shape {sums.shape} do not match a {(nl, ny, nx)} grid with "
+                         f"{npy} x {npx} eye positions")
+    return (sums[:, 1:] / divisor).reshape(nl, ny, nx, npy, npx)
+
+
+def evaluation_from_perceive(perceive):
+    """``evaluation`` after its first step: everything EVAL:112-163 computes from the pupil-integrated eyebox
+    efficiency ``perceive`` ``[L, NY, NX, n_epy, n_epx]`` (``eye_perceive``'s result)."""
     M_inv = np.linalg.inv(M_SENSOR)
     LAB_D65 = xyz_to_lab(XYZ_D65_ASTM / XYZ_D65_ASTM[1] * 100.0)
-    perceive = eye_perceive(matrix_EB)
     n_lambda, n_FOVy, n_FOVx, n_epy, n_epx = perceive.shape
     white = linearize_srgb(np.zeros((n_FOVy, n_FOVx, 3)) + 1.0)
     wl = (M_inv @ white.reshape(-1, 3).T).T.reshape(n_FOVy, n_FOVx, 3)[..., None, None]
@@ -222,3 +340,20 @@ def evaluation(matrix_EB):
     U_fov = U_fov / n_epx / n_epy
     U_EB = 0 if np.max(U_EB) == 0 else np.min(U_EB) / np.max(U_EB)
     return delta_e, U_fov, U_EB, output_image
+
+
+def evaluation(matrix_EB):
+    """Drop-in for the reference's ``evaluation`` (EVAL:45-163)."""
+    return evaluation_from_perceive(eye_perceive(matrix_EB))
+
+
+def evaluation_device(eb, divisor):
+    """``evaluation(eb / divisor)`` without the grid leaving the device: ``eb`` is the raw count grid
+    ``[L, NY, NX, 80, 120]`` (``divisor = R * num_iter``), reduced to its window sums where it lives
+    (``eyebox_window_sums``); only those ``[L * NY * NX, 57]`` numbers reach the host, where the colour math of
+    ``evaluation_from_perceive`` runs.  Differs from the host path only by the float32 rounding of its
+    per-bin division and summation (at most 902 * 2^-24 relative per eye position)."""
+    if len(eb.shape) != 5:
+        raise ValueError(f"expected a [L, NY, NX, 80, 120] grid, got {tuple(eb.shape)}")
+    sums = eyebox_window_sums(eb)
+    return evaluation_from_perceive(perceive_from_window_sums(sums, eb.shape, divisor))

@@ -16,7 +16,7 @@ REPO = os.path.dirname(PKG)
 LIB = os.path.join(PKG, "libwgrt.so")
 OPS_LIB = os.path.join(PKG, "_wgrt_torch.so")
 OPS_SOURCE = "wgrt_torch.cpp"
-SOURCES = ["wgrt_trace.hip", "wgrt_shadow.hip", "wgrt_scene_build.cpp"]
+SOURCES = ["wgrt_trace.hip", "wgrt_shadow.hip", "wgrt_eyebox.hip", "wgrt_scene_build.cpp"]
 HEADERS = ["wgrt_common.h", "wgrt_device.h", "wgrt_scene.h", "wgrt_scene_build.h"]
 ARCH = os.environ.get("WGRT_OFFLOAD_ARCH", "gfx950")
 

@@ -27,7 +27,8 @@ through the compiled-numba flat-offset aliasing of an out-coupling exactly on th
 ``nb x (9600 + SPILL)`` floats, 1/N of the grid, over its own xGMI link) and rank 0 assembles the
 grid; ``reduce`` is the plain sum-reduce of the whole grid (50.8 MB at 21x21).  Eyebox values are
 integer counts, so both reproduce the single-GPU grid exactly.  That is the only collective on
-the path.
+the path.  A job that wants only the efficiencies and the evaluation moves no slabs at all:
+``EyeboxReduce`` sum-reduces each rank's per-slab window sums (57 float64 per slab), again exactly.
 
 The tracer is pluggable (``trace_fn(rays, rng, eb, gid, num_iter)``, ``gid`` a ``GidMap``) so the
 same sharding / stepping / collection code runs with the HIP kernel in production (``bench.py``,
@@ -380,6 +381,70 @@ class EyeboxGather:
         return eb
 
 
+class EyeboxReduce:
+    """The evaluation-only collective: each rank reduces its own part of the grid to per-slab window sums
+    (``AR_system_evaluation_functions.eyebox_window_sums``: the slab total and the 7 x 8 pupil sums, 57
+    float64 per slab) and ONE sum-reduce of the ``[n_slabs, W]`` table brings them to rank 0, instead of the
+    gather of whole 38.4 KB slabs.
+
+    A rank reduces only the slabs it can have written: those of its own blocks and, for each of them, the
+    slab after it (the H6 top-edge spill, ``EyeboxGather``'s index sets: ``slabs[r]`` and ``spill_dst[r]``);
+    its rows go into a zeroed table.  Window sums are linear in the grid and the grid holds integer counts,
+    so every entry is an integer, exact in float64 whatever the order of the additions: rank 0's table
+    equals the window sums of the assembled grid bit for bit, spills into slabs no rank owns included.
+    A device grid is reduced by the HIP kernel; host tensors (the gloo CPU tests) by the numpy statement
+    of the same formula."""
+
+    def __init__(self, all_blocks, num_fov_x: int, num_fov_y: int, lambdas, n_lambda_scene: int, mask=None,
+                 step_y: int = 8, step_x: int = 12):
+        import torch
+        g = EyeboxGather(all_blocks, num_fov_x, num_fov_y, lambdas, n_lambda_scene)
+        self.n_slabs, self.world = g.n_slabs, g.world
+        # own slabs, then the spill targets that are not own slabs (spill_dst): no slab twice
+        self.rows = [torch.cat([g.slabs[r], g.spill_dst[r]]) for r in range(self.world)]
+        self.mask, self.step_y, self.step_x = mask, step_y, step_x
+        self._dev_rows = {}
+
+    def _rows(self, rank: int, device):
+        """Rank ``rank``'s slab list on ``device`` (host tensors here; moved once per device and cached)."""
+        key = (rank, str(device))
+        if key not in self._dev_rows:
+            self._dev_rows[key] = self.rows[rank].to(device)
+        return self._dev_rows[key]
+
+    def local(self, eb, rank: int):
+        """Rank ``rank``'s contribution: its rows' window sums scattered into a zeroed ``[n_slabs, W]`` float64
+        tensor on the grid's device."""
+        import torch
+
+        from .AR_system_evaluation_functions import eyebox_window_sums
+        rows = self._rows(rank, eb.device)
+        part = eyebox_window_sums(eb, rows, self.mask, self.step_y, self.step_x)
+        if not isinstance(part, torch.Tensor):
+            part = torch.from_numpy(part)
+        full = torch.zeros((self.n_slabs, part.shape[1]), dtype=torch.float64, device=eb.device)
+        full.index_copy_(0, rows, part)
+        return full
+
+    def __call__(self, eb, group=None, dst: int = 0):
+        """The ``[n_slabs, W]`` window sums of the whole job's grid on rank ``dst`` (this rank's own
+        contribution elsewhere)."""
+        import torch.distributed as dist
+        if _world(group) <= 1:
+            return self.local(eb, 0)
+        rank = dist.get_rank(group)
+        full = self.local(eb, rank)
+        if full.is_cuda and dist.get_backend(group) == "gloo":
+            # gloo reduces host tensors (the one-GPU rehearsal, as EyeboxGather.__call__)
+            host = full.cpu()
+            dist.reduce(host, dst=dst, op=dist.ReduceOp.SUM, group=group)
+            if rank == dst:
+                full.copy_(host)
+        else:
+            dist.reduce(full, dst=dst, op=dist.ReduceOp.SUM, group=group)
+        return full
+
+
 def trace_job(shard: Shard, build_rays_fn, trace_fn, new_eb, num_iter: int = 4, per_call: int = 1, group=None,
               collect=None):
     """Run the reference's job (``num_iter`` chained launches, MAIN:169-177) on this rank's
@@ -487,5 +552,5 @@ def shard_rays_host(points, num_fov_x, num_fov_y, lambdas, rays_per_fov, blocks,
 
 
 __all__ = ["block_range", "rank_blocks", "GidMap", "Shard", "make_shard", "replica_shard", "seeds_like", "slab_ids", "split_calls", "run_steps",
-           "reduce_eyebox", "EyeboxGather", "trace_job", "timed_run", "hip_tracer", "hip_shard_builder",
+           "reduce_eyebox", "EyeboxGather", "EyeboxReduce", "trace_job", "timed_run", "hip_tracer", "hip_shard_builder",
            "shard_rays_host", "MAX_TRACES_PER_CALL", "EB_SLAB", "SPILL"]

@@ -13,13 +13,16 @@ Same flow as the reference script, on the MI355X kernel:
    at most ``FUSE_MAX_RAYS`` rays, else as separate launches (``fuse`` overrides), timed with HIP
    events (no JIT in the timed region, unlike the reference's wall clock);
 5. efficiencies ``A = sum(EB) / N / num_iter``, ``eff_c = 3 * sum(A[lambda])`` (MAIN:186-192)
-   and ``evaluation(EB / R / num_iter)`` (MAIN:197-198);
+   and ``evaluation(EB / R / num_iter)`` (MAIN:197-198) -- on the host from the copied-back grid as the
+   reference does, or (``eyebox="device"``, ``--eyebox device``) from the per-slab window sums one device pass
+   leaves (``eyebox_window_sums``), without the grid leaving the GPU;
 6. the "Eyebox Center View.png" export (MAIN:199-203): the evaluated image at the first eye row,
    last eye column, as 8-bit RGB, rows flipped (``eyebox_center_view``, written without OpenCV).
 
 The matplotlib plots (MAIN:213-237) are visual-only and not reproduced.
 Multi-GPU: run under ``torch.distributed.run``; each rank traces an interleaved set of FoV x
-wavelength blocks and the eyebox slabs are gathered to rank 0 (``distributed.py``).
+wavelength blocks and the eyebox slabs are gathered to rank 0 (``distributed.py``); in device mode the ranks'
+window sums are sum-reduced instead (``distributed.EyeboxReduce``).
 """
 from __future__ import annotations
 
@@ -41,15 +44,30 @@ FUSE_MAX_RAYS = 4_000_000
 def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000, num_iter: int = 4,
         lambdas=(0, 1, 2), lut_dir: str | None = None, lut_seed: int = 0, lut_profile: str = "default",
         point_seed: int | None = None, evaluate: bool = True, verbose: bool = True, variant: int = 0,
-        fuse: bool | None = None, points: np.ndarray | None = None, png: str | None = None) -> dict:
+        fuse: bool | None = None, points: np.ndarray | None = None, png: str | None = None,
+        eyebox: str = "host", keep_grid: bool = False) -> dict:
     """The reference script's job on this engine; returns its printed quantities and arrays.
     ``points``: the R/2 in-coupler origins to use (default: sampled, GRTF:12-23, seeded by
-    ``point_seed``); ``png``: where to write the "Eyebox Center View" image (needs ``evaluate``)."""
+    ``point_seed``); ``png``: where to write the "Eyebox Center View" image (needs ``evaluate``).
+
+    ``eyebox``: where the grid is reduced after the trace.  ``"host"`` (the reference's flow, MAIN:186-198):
+    the whole grid is copied to the host (864 MB at the default job), summed, scaled and evaluated there, and
+    returned as ``matrix_EB``.  ``"device"``: one device pass reduces every 80 x 120 slab to its total and its
+    7 x 8 pupil sums (``eyebox_window_sums``); ``A``, ``efficiency`` and the evaluation come from that
+    ``[n_slabs, 57]`` table, several GPUs sum-reduce it (``distributed.EyeboxReduce``) instead of gathering
+    slabs, and the grid stays on the device -- ``matrix_EB`` is returned only with ``keep_grid=True``.
+    ``A`` and ``efficiency`` are bit-identical to the host mode's while a slab's count stays below 2^24 (then
+    its float32 sum is the exact integer, as is the float64 one), which always holds for
+    ``num_rays_per_FoV * num_iter < 2^24``; the evaluation divides the exact float64 window sums once where
+    the host mode divides and sums in float32 (at most 902 * 2^-24 relative per eye position)."""
+    if eyebox not in ("host", "device"):
+        raise ValueError(f"eyebox must be 'host' or 'device', got {eyebox!r}")
     import torch
     import torch.distributed as dist
 
     from .couplers_coor import design_geometry
-    from .distributed import EyeboxGather, hip_shard_builder, hip_tracer, make_shard, run_steps, split_calls
+    from .distributed import (EyeboxGather, EyeboxReduce, hip_shard_builder, hip_tracer, make_shard, run_steps,
+                              split_calls)
     from .engine import Scene, check_stats, new_stats, reserve
     from .luts import load_luts, lut_f32_mask, synthetic_luts, validate_luts
     from .rays import generate_points_in_polygon
@@ -103,18 +121,32 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
     torch.cuda.synchronize()
     kern_s = t0.elapsed_time(t1) / 1e3
     check_stats(stats)
+    t_post = time.perf_counter()   # everything below is post-processing of the traced grid
+    on_device = eyebox == "device"
+    sums = None   # device mode: the [n_slabs, 57] window sums of the whole job's grid (rank 0)
     if world > 1:
         all_blocks = [make_shard(num_FOV_x, num_FOV_y, len(lambdas), R, world, r).blocks for r in range(world)]
-        EyeboxGather(all_blocks, num_FOV_x, num_FOV_y, lambdas, scene.num_lmd, device=dev)(eb)
+        if on_device:
+            sums = EyeboxReduce(all_blocks, num_FOV_x, num_FOV_y, lambdas, scene.num_lmd)(eb)
+        if not on_device or keep_grid:
+            EyeboxGather(all_blocks, num_FOV_x, num_FOV_y, lambdas, scene.num_lmd, device=dev)(eb)
+    elif on_device:
+        from .AR_system_evaluation_functions import eyebox_window_sums
+        sums = eyebox_window_sums(eb)
     if world > 1:
         dist.all_reduce(stats)
-    matrix_EB = eb.cpu().numpy()
+    matrix_EB = eb.cpu().numpy() if not on_device or keep_grid else None
     out = dict(num_rays=num_rays, num_iter=num_iter, gpu_seconds=kern_s, bounces=int(stats[0]),
                eyebox_hits=int(stats[2]), rng_states=rng.cpu().numpy().view(np.uint32))
     if rank != 0:
         scene.close()
         return out
-    A = np.sum(matrix_EB, axis=(-2, -1)) / num_rays / num_iter
+    if on_device:
+        # slab totals are integer counts: below 2^24 the float32 cast is the value np.sum gives on the host
+        sums = sums.cpu().numpy()
+        A = sums[:, 0].reshape(scene.eb_shape()[:-2]).astype(np.float32) / num_rays / num_iter
+    else:
+        A = np.sum(matrix_EB, axis=(-2, -1)) / num_rays / num_iter
     names = {0: "Blue", 1: "Green", 2: "Red"}
     eff = {names.get(k, str(k)): float(np.sum(A[k] * 3)) for k in range(A.shape[0])}
     say("Simulation finished.")
@@ -123,10 +155,16 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
     for c in ("Red", "Green", "Blue"):
         if c in eff:
             say(f"Efficiency ({c:5s})    : {eff[c] * 100:8.3f} %")
-    out.update(matrix_EB=matrix_EB, A=A, efficiency=eff)
+    out.update(A=A, efficiency=eff)
+    if matrix_EB is not None:
+        out["matrix_EB"] = matrix_EB
     if evaluate:
-        from .AR_system_evaluation_functions import evaluation
-        delta_e, U_fov, U_EB, output_image = evaluation(matrix_EB / R / num_iter)
+        from .AR_system_evaluation_functions import evaluation, evaluation_from_perceive, perceive_from_window_sums
+        if on_device:
+            delta_e, U_fov, U_EB, output_image = evaluation_from_perceive(
+                perceive_from_window_sums(sums, scene.eb_shape(), R * num_iter))
+        else:
+            delta_e, U_fov, U_EB, output_image = evaluation(matrix_EB / R / num_iter)
         out.update(delta_e=float(delta_e), U_fov=float(U_fov), U_EB=float(U_EB), output_image=output_image)
         out["center_view"] = eyebox_center_view(output_image)
         if png:
@@ -135,6 +173,8 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
         say(f"Color dispersion      : {delta_e:8.2f}")
         say(f"FoV uniformity        : {U_fov * 100:8.2f} %")
         say(f"Eyebox uniformity     : {U_EB * 100:8.2f} %")
+    out["post_seconds"] = time.perf_counter() - t_post
+    say(f"Post-processing time  : {out['post_seconds']:.4f} s  (eyebox reduced on the {eyebox})")
     scene.close()
     return out
 
@@ -198,6 +238,9 @@ def main(argv=None):
     ap.add_argument("--fuse", choices=["auto", "yes", "no"], default="auto",
                     help="num_iter chained traces as one fused launch (auto: when a GPU traces <= 4M rays)")
     ap.add_argument("--no-fuse", action="store_true", help="same as --fuse no")
+    ap.add_argument("--eyebox", choices=["host", "device"], default="host",
+                    help="where the eyebox grid is reduced after the trace: host (the reference's flow: the whole "
+                         "grid is copied back) or device (per-slab pupil sums on the GPU; the grid stays there)")
     ap.add_argument("--json", default=None, help="write scalar results here")
     ap.add_argument("--png", default="Eyebox Center View.png",
                     help="the eyebox-center image (MAIN:199-203); empty string: do not write it")
@@ -211,7 +254,7 @@ def main(argv=None):
     res = run(a.num_fov_x, a.num_fov_y, a.rays_per_fov, a.num_iter, lut_dir=a.lut_dir, lut_seed=a.lut_seed,
               lut_profile=a.lut_profile, point_seed=a.point_seed, evaluate=not a.no_eval,
               fuse=False if a.no_fuse else {"auto": None, "yes": True, "no": False}[a.fuse],
-              png=a.png or None)
+              png=a.png or None, eyebox=a.eyebox)
     if a.json and (not dist.is_initialized() or dist.get_rank() == 0):
         keep = {k: v for k, v in res.items() if isinstance(v, (int, float, dict, str))}
         with open(a.json, "w") as f:

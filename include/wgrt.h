@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define WGRT_ABI_VERSION 7
+#define WGRT_ABI_VERSION 8
 
 typedef enum {
     WGRT_OK = 0,
@@ -293,6 +293,22 @@ wgrt_status wgrt_eyebox_pack(const float *eb, int64_t n_slabs, const int64_t *sl
                              const float *spill_mask, int64_t n, int64_t nb, float *payload, void *stream);
 wgrt_status wgrt_eyebox_assemble(float *eb, int64_t n_slabs, const float *recv, int32_t world, int64_t nb,
                                  const int64_t *dst, const int64_t *spill_dst, void *stream);
+
+/* ABI 8.  Per-slab reduction of the eyebox grid (replaces the host passes of MAIN:186-198 / EVAL:66-109).
+ * For row j < n, slab s = slabs ? slabs[j] : j of eb [n_slabs, 80, 120]:
+ *   out[j * W + 0]                 = sum of the slab
+ *   out[j * W + 1 + iy * npx + ix] = sum over (r, c) in [0, ms)^2 of mask[r * ms + c] * eb[s, iy*step_y + r, ix*step_x + c]
+ * with npy = (80 - ms) / step_y + 1, npx = (120 - ms) / step_x + 1, W = 1 + npy * npx
+ * (ms = 30, steps 8 / 12: npy = 7, npx = 8, W = 57 -- the reference's eye positions).
+ * Accumulated in float64 in a fixed order (no float atomics): the same input gives the same bits on every
+ * run, and an integer-valued grid gives the exact integers.  Rows whose s is outside [0, n_slabs) are
+ * zero-filled.  eb (16-B aligned), slabs (int64, or NULL), mask (float32 [ms * ms]) and out (float64 [n * W])
+ * are DEVICE pointers; asynchronous on stream, on the stream's device (as wgrt_eyebox_pack).  1 <= ms <= 80,
+ * step_y, step_x >= 1, n <= 2^31 - 1, else WGRT_ERR_INVALID_ARGUMENT.  n == 0 is WGRT_OK without a launch.
+ * Not part of the reference. */
+wgrt_status wgrt_eyebox_window_sums(const float *eb, int64_t n_slabs, const int64_t *slabs, int64_t n,
+                                    const float *mask, int32_t ms, int32_t step_y, int32_t step_x,
+                                    double *out, void *stream);
 
 /* Polygon membership of n points (DEVICE xy[n, 2]) through the scene's locator:
  * bit k of out_mask[i] = is_inside_or_on_edge(point i, polygon k) with polygon order
