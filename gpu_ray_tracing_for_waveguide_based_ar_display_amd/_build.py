@@ -16,8 +16,8 @@ REPO = os.path.dirname(PKG)
 LIB = os.path.join(PKG, "libwgrt.so")
 OPS_LIB = os.path.join(PKG, "_wgrt_torch.so")
 OPS_SOURCE = "wgrt_torch.cpp"
-SOURCES = ["wgrt_trace.hip", "wgrt_shadow.hip", "wgrt_eyebox.hip", "wgrt_scene_build.cpp"]
-HEADERS = ["wgrt_common.h", "wgrt_device.h", "wgrt_scene.h", "wgrt_scene_build.h"]
+SOURCES = ["wgrt_trace.hip", "wgrt_scene.hip", "wgrt_rays.hip", "wgrt_shadow.hip", "wgrt_eyebox.hip",
+           "wgrt_scene_build.cpp"]
 ARCH = os.environ.get("WGRT_OFFLOAD_ARCH", "gfx950")
 
 # -ffp-contract=off: the reference never fuses a*b+c (Python float semantics); keeping
@@ -43,8 +43,10 @@ def _stale() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [os.path.join(REPO, "include", h)
-                                                                   for h in ("wgrt.h", "wgrt_debug.h")]
+    # everything in csrc/ but the operator library's source, so that a new header cannot be forgotten
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)
+            if f.endswith((".h", ".hip", ".cpp")) and f != OPS_SOURCE]
+    deps += [os.path.join(REPO, "include", h) for h in ("wgrt.h", "wgrt_debug.h")]
     deps.append(os.path.abspath(__file__))
     return any(os.path.getmtime(d) > t for d in deps)
 

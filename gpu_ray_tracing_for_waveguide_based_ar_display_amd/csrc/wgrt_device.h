@@ -230,13 +230,12 @@ __device__ __forceinline__ typename Loc::Word locate_w(const Loc &L, double x, d
 
 // The exact test of an EDGE class.  Kp: the launch's kernarg handle -- the locator's array pointers
 // are then read from the kernarg segment (not held in SGPRs across the Jones loop); NULL: from L.
+// Every reader takes the handle as an argument, so the test is also correct as a real call (a noinline
+// build ran the parity tests green); inlined, it keeps the wave loop free of a call's
+// register cost.
 template <class Loc>
-#ifdef WGRT_EDGE_NOINLINE
-__device__ __attribute__((noinline))   // A/B and contract check: the exact tests as a real call
-#else
-__device__ __forceinline__
-#endif
-bool in_poly_w(const Loc &L, typename Loc::Word w, int k, double x, double y, const KArgs *Kp = nullptr) {
+__device__ __forceinline__ bool in_poly_w(const Loc &L, typename Loc::Word w, int k, double x, double y,
+                                          const KArgs *Kp = nullptr) {
     const unsigned cls = (unsigned)(w >> (2 * k)) & 3u;
     if (__builtin_expect(cls != 2u, 1)) return cls == 1u;   // IN / OUT; EDGE cells are rare (0.34 % of C3 lane-passes)
     const int cy = (int)floor((y - L.y0) * L.inv_h);   // an EDGE cell is inside the grid
@@ -917,14 +916,9 @@ __device__ __forceinline__ double4 block_cw(const double *B, bool entry, double 
 // The efficiencies from the single-precision Hermitian forms (the estimate every decision starts
 // with).  cw = {cosA_0, cosA_1, cosA_2, Wsum}.
 __device__ __forceinline__ void estimate32(JDecision &d, const double *B, const JRay &r, bool three, double inv,
-                                           double f01, double inv_n_g, const double4 &cw, SegAcc *sg = nullptr,
-                                           float4 *h01 = nullptr) {
+                                           double f01, double inv_n_g, const double4 &cw, SegAcc *sg = nullptr) {
     const float4 *H = (const float4 *)(B + kJBlockHerm);
     const float4 h0 = H[0], h1 = H[1];
-    if (h01) {
-        h01[0] = h0;
-        h01[1] = h1;
-    }
     SEG_IWAITVM(sg);   // (the third branch's form is loaded after the mark: its wait counts in s[3])
     SEG_IMARK_DEP(sg, 2, h0.x + h1.x);
     const float er = (float)r.er, ei = (float)r.ei, mr = (float)r.mr, mi = (float)r.mi;
@@ -969,11 +963,7 @@ __device__ __forceinline__ void estimate64(JDecision &d, const double *B, const 
 // at the 1e5-bounce cap, which the bound's margin covers (§2.4).  It lives in the AMP instantiations of
 // the trace kernel, which a launch runs when its scene has such a block (wgrt_scene::nonunitary_blocks):
 // on scaled-unitary LUTs the kernel carries none of it (compiled into every launch it cost 2-4 %).
-// WGRT_AMPLIFY=0 never selects them (the round-5 bound, proven for scaled-unitary matrices only).
-#ifndef WGRT_AMPLIFY
-#define WGRT_AMPLIFY 1
-#endif
-constexpr bool kAmplify = WGRT_AMPLIFY != 0;
+// Without the step the bound is round 5's, proven for scaled-unitary matrices only.
 
 // |det M|^2 = det H, bounded from above from the tile's single-precision H = M^H M: the float products
 // are exact in double and the float entries carry 2^-24 relative rounding, so det H lies within
@@ -1116,9 +1106,6 @@ __device__ __forceinline__ int interact(const TraceArgs &A, const KArgs &K, cons
 // The EDGE classes a lane's loop iteration consults -- eff_reg1's, the region's slices' up to the
 // first IN one, eff_reg2's in R3 -- replaced by the exact predicate's verdict (IN 1 / OUT 0) through
 // the 128-B band records (in_poly_w).  Rare: 0.34 % of C3 lane-passes meet an EDGE cell.
-#ifndef WGRT_EDGE_WAIT
-#define WGRT_EDGE_WAIT 1
-#endif
 template <class Loc>
 __device__ __forceinline__ typename Loc::Word resolve_edges(const KArgs &K, const Loc &loc, typename Loc::Word w,
                                                             int region, int first, int count, double x, double y) {
@@ -1177,9 +1164,7 @@ __device__ __forceinline__ int advance(const TraceArgs &A, const KArgs &K, const
         // exact test that leaves some in flight would otherwise make the wait insertion assume them pending
         // on every path after this rare one, and wait for every load in flight before the interaction's
         // line-0 loads -- the pass's miss-hop gathers among them
-#if WGRT_EDGE_WAIT
         __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
-#endif
         f = (c >> (2 * first)) & gmask;
         in = f & kLow;
         cand = in | ((f >> 1) & kLow);

@@ -1,4 +1,6 @@
-// wgrt_eyebox.hip -- per-slab reduction of the eyebox grid (wgrt_eyebox_window_sums, include/wgrt.h).
+// wgrt_eyebox.hip -- the eyebox grid's own kernels (include/wgrt.h wgrt_eyebox_*): the per-slab
+// reduction (wgrt_eyebox_window_sums) and, at the end of the file, the slab collection of the
+// strong-scaling gather (wgrt_eyebox_pack / wgrt_eyebox_assemble).
 //
 // What the driver reads from an 80 x 120 slab of matrix_EB is its total (MAIN:186-192) and the sums
 // over a 30-px pupil mask at every 8th / 12th bin (eye_perceive, EVAL:66-109): 1 + 7 x 8 numbers out
@@ -22,7 +24,7 @@
 #include <string>
 
 #include "../../include/wgrt.h"
-#include "wgrt_scene.h"
+#include "wgrt_host.h"
 
 using namespace wgrt;
 
@@ -167,16 +169,108 @@ extern "C" wgrt_status wgrt_eyebox_window_sums(const float *eb, int64_t n_slabs,
     if (n > INT32_MAX) return fail(WGRT_ERR_INVALID_ARGUMENT, "at most 2^31 - 1 rows per call");
     const int npy = (kEbRows - ms) / step_y + 1, npx = (kEbCols - ms) / step_x + 1;
     int sdev = 0;
-    if (hipError_t e = stream_device(stream, &sdev); e != hipSuccess)
-        return fail(WGRT_ERR_HIP, std::string("stream device: ") + hipGetErrorString(e));
-    DeviceScope dev_scope(sdev);
-    if (dev_scope.error() != hipSuccess)
-        return fail(WGRT_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(dev_scope.error()));
+    HIP_TRY(stream_device(stream, &sdev));
+    DEVICE_SCOPE(dev_scope, sdev);
     // 38.4 KB + the mask: 42 KB at ms = 30 (three workgroups per CU), 64 KB at ms = 80 (two)
     const size_t lds = (size_t)(WGRT_EB_SLAB + ms * ms + 2 * kLdsPad) * sizeof(float);
     hipLaunchKernelGGL(eyebox_window_sums_kernel, dim3((unsigned)n), dim3(kThreads), lds, (hipStream_t)stream, eb,
                        n_slabs, slabs, mask, (int)ms, (int)step_y, (int)step_x, npy, npx, out);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess)
-        return fail(WGRT_ERR_HIP, std::string("eyebox_window_sums launch: ") + hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return WGRT_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Eyebox collection of the strong-scaling gather (wgrt_eyebox_pack / wgrt_eyebox_assemble): row copies
+// of whole 80 x 120 slabs as 16-B loads / stores, one workgroup per (row, 1/kSlabParts of the slab).
+// The spill rows (121 floats) move as dwords.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int kSlabParts = 3;   // 800 float4 per workgroup: 256 threads x 3-4
+
+inline int64_t eb_spill_floats(int64_t nb) { return (nb * WGRT_EB_SPILL + 3) / 4 * 4; }
+
+__global__ __launch_bounds__(256) void eyebox_pack_kernel(const float *eb, int64_t n_slabs, const int64_t *slabs,
+                                                          const int64_t *next, const float *mask, int64_t n, int64_t nb,
+                                                          float *payload) {
+    const int64_t j = blockIdx.y;
+    if (j >= n) return;
+    const int64_t s = slabs[j];
+    if (s < 0 || s >= n_slabs) return;
+    const float4 *src = (const float4 *)(eb + s * WGRT_EB_SLAB);
+    float4 *out = (float4 *)(payload + j * WGRT_EB_SLAB);
+    const int lo = (int)blockIdx.x * (kSlabF4 / kSlabParts), hi = lo + kSlabF4 / kSlabParts;
+    for (int c = lo + threadIdx.x; c < hi; c += blockDim.x) out[c] = src[c];
+    if (blockIdx.x == 0 && threadIdx.x < WGRT_EB_SPILL) {
+        const int64_t t = next[j];
+        const float v = (t >= 0 && t < n_slabs) ? eb[t * WGRT_EB_SLAB + threadIdx.x] * mask[j] : 0.0f;
+        payload[nb * WGRT_EB_SLAB + j * WGRT_EB_SPILL + threadIdx.x] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void eyebox_copy_kernel(float *eb, int64_t n_slabs, const float *recv, int64_t nb,
+                                                          int64_t plen, const int64_t *dst) {
+    const int64_t row = blockIdx.y;   // r * nb + j
+    const int64_t s = dst[row];
+    if (s < 0 || s >= n_slabs) return;
+    const int64_t r = row / nb, j = row % nb;
+    const float4 *src = (const float4 *)(recv + r * plen + j * WGRT_EB_SLAB);
+    float4 *out = (float4 *)(eb + s * WGRT_EB_SLAB);
+    const int lo = (int)blockIdx.x * (kSlabF4 / kSlabParts), hi = lo + kSlabF4 / kSlabParts;
+    for (int c = lo + threadIdx.x; c < hi; c += blockDim.x) out[c] = src[c];
+}
+
+__global__ __launch_bounds__(128) void eyebox_spill_kernel(float *eb, int64_t n_slabs, const float *recv, int64_t nb,
+                                                           int64_t plen, const int64_t *spill_dst) {
+    const int64_t row = blockIdx.x;
+    const int64_t s = spill_dst[row];
+    if (s < 0 || s >= n_slabs || threadIdx.x >= WGRT_EB_SPILL) return;
+    const int64_t r = row / nb, j = row % nb;
+    // one spill row per target slab (slab s's spill comes only from slab s - 1): no atomics needed
+    eb[s * WGRT_EB_SLAB + threadIdx.x] += recv[r * plen + nb * WGRT_EB_SLAB + j * WGRT_EB_SPILL + threadIdx.x];
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t wgrt_eyebox_payload_floats(int64_t nb) { return nb < 0 ? -1 : nb * WGRT_EB_SLAB + eb_spill_floats(nb); }
+
+wgrt_status wgrt_eyebox_pack(const float *eb, int64_t n_slabs, const int64_t *slabs, const int64_t *next,
+                             const float *spill_mask, int64_t n, int64_t nb, float *payload, void *stream) {
+    if (n < 0 || nb < n || n_slabs < 0) return fail(WGRT_ERR_INVALID_ARGUMENT, "need 0 <= n <= nb and n_slabs >= 0");
+    if (n == 0) return WGRT_OK;
+    if (!eb || !slabs || !next || !spill_mask || !payload) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (((uintptr_t)eb | (uintptr_t)payload) & 15) return fail(WGRT_ERR_INVALID_ARGUMENT, "eb / payload must be 16-B aligned");
+    if (n > 65535) return fail(WGRT_ERR_INVALID_ARGUMENT, "at most 65535 slabs per rank");
+    int sdev = 0;
+    HIP_TRY(stream_device(stream, &sdev));
+    DEVICE_SCOPE(dev_scope, sdev);
+    hipLaunchKernelGGL(eyebox_pack_kernel, dim3(kSlabParts, (unsigned)n), dim3(256), 0, (hipStream_t)stream, eb,
+                       n_slabs, slabs, next, spill_mask, n, nb, payload);
+    HIP_TRY(hipGetLastError());
+    return WGRT_OK;
+}
+
+wgrt_status wgrt_eyebox_assemble(float *eb, int64_t n_slabs, const float *recv, int32_t world, int64_t nb,
+                                 const int64_t *dst, const int64_t *spill_dst, void *stream) {
+    if (world < 0 || nb < 0 || n_slabs < 0) return fail(WGRT_ERR_INVALID_ARGUMENT, "negative world / nb / n_slabs");
+    const int64_t rows = (int64_t)world * nb;
+    if (rows == 0) return WGRT_OK;
+    if (!eb || !recv || !dst || !spill_dst) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (((uintptr_t)eb | (uintptr_t)recv) & 15) return fail(WGRT_ERR_INVALID_ARGUMENT, "eb / recv must be 16-B aligned");
+    if (rows > 65535) return fail(WGRT_ERR_INVALID_ARGUMENT, "at most 65535 payload rows");
+    int sdev = 0;
+    HIP_TRY(stream_device(stream, &sdev));
+    DEVICE_SCOPE(dev_scope, sdev);
+    const int64_t plen = wgrt_eyebox_payload_floats(nb);
+    hipLaunchKernelGGL(eyebox_copy_kernel, dim3(kSlabParts, (unsigned)rows), dim3(256), 0, (hipStream_t)stream, eb,
+                       n_slabs, recv, nb, plen, dst);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(eyebox_spill_kernel, dim3((unsigned)rows), dim3(128), 0, (hipStream_t)stream, eb, n_slabs, recv,
+                       nb, plen, spill_dst);
+    HIP_TRY(hipGetLastError());
+    return WGRT_OK;
+}
+
+}  // extern "C"

@@ -160,7 +160,7 @@ __device__ void shadow_trace(const TraceArgs &A, const Loc &loc, int64_t i, Shad
             const double f01 = entry ? A.n_g : 1.0;
             const double nb = (double)bounces * 0.01;
             const double en2 = fma(jr.er, jr.er, fma(jr.ei, jr.ei, fma(jr.mr, jr.mr, jr.mi * jr.mi)));
-            const double grow = kAmplify ? fma(nb * nb, growth, 1.0) * (double)jr.amp : fma(nb * nb, growth, 1.0);
+            const double grow = fma(nb * nb, growth, 1.0) * (double)jr.amp;
             const double base = grow * fabs(inv) * fmax(en2, 1.0);
             const double c_ref[3] = {e0, e0 + e1, e0 + e1 + e2};
             // how much of each bound the arithmetic uses against the reference's thresholds
@@ -200,7 +200,7 @@ __device__ void shadow_trace(const TraceArgs &A, const Loc &loc, int64_t i, Shad
                 const JField f = jones(load_rec(JB + kJBlockRec + 8 * b), jr);
                 const double n2 = norm2(f);
                 const double rn = rsq_nr(n2);
-                if (kAmplify && amp_blk) {   // the product lane's amplification step (wgrt_device.h interact)
+                if (amp_blk) {   // the product lane's amplification step (wgrt_device.h interact)
                     const float4 hb = ((const float4 *)(JB + kJBlockHerm))[b];
                     float pa, nmin;
                     amp_prepare(hb, en2, A.cert_tol * grow, pa, nmin);
@@ -378,12 +378,9 @@ extern "C" wgrt_status wgrt_debug_shadow(const wgrt_scene *s, const wgrt_rays *r
     A.cert_tol = kCertTol;   // the bounds the product lane uses by default
     A.cert_tol32 = std::max(kCertTol32, A.cert_tol);
     S.out = stats;
-    DeviceScope dev_scope(s->device);   // launched on the scene's device; the caller's is restored
-    if (dev_scope.error() != hipSuccess)
-        return fail(WGRT_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(dev_scope.error()));
+    DEVICE_SCOPE(dev_scope, s->device);   // launched on the scene's device; the caller's is restored
     const int64_t blocks = std::min<int64_t>((n_rays + 255) / 256, 16384);
     hipLaunchKernelGGL(shadow_kernel<Locator>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, S, A.loc);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(WGRT_ERR_HIP, std::string("shadow_kernel: ") + hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return WGRT_OK;
 }

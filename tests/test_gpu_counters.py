@@ -110,9 +110,9 @@ def test_interaction_counts_with_replays(dev, oracle_runs, name, num_iter):
 
 def test_every_ray_replayed(dev, oracle_runs):
     """Bounds so wide that no decision is certified: every traced ray is abandoned at its in-coupling
-    event and re-traced by the kernel behind the launch (replay_kernel for a single launch: more rays
-    than its threads, so its grid-stride loop runs).  Results, counters and per-ray bounces equal the
-    oracle's."""
+    event and re-traced by the launch itself (a single launch: replay_tail in the trace kernel's last
+    workgroup, with more rays than its 256 threads, so its stride loop runs).  Results, counters and
+    per-ray bounces equal the oracle's."""
     c, want = oracle_runs("C2")
     got = _run(c, dev, 7, debug=dict(cert_tol=1e3, cert_tol32=1e3))
     st = got[0]["stats"]

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Register / scratch / occupancy summary of the kernels of one build of wgrt_trace.hip
-# (hipcc -Rpass-analysis=kernel-resource-usage).  Extra hipcc flags (e.g. -DWGRT_EDGE_NOINLINE) pass through.
+# (hipcc -Rpass-analysis=kernel-resource-usage).  Extra hipcc flags (e.g. -DWGRT_INKERNEL_REPLAY=0) pass through.
 #   tools/kres.sh [-Dmacro ...]
 cd "$(dirname "$0")/.." || exit 1
 /opt/rocm/bin/hipcc -O3 -std=c++17 -ffp-contract=off -fno-fast-math -mllvm -disable-machine-licm --offload-arch=gfx950 \
