@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import types
 
 import numpy as np
 
@@ -68,6 +69,8 @@ class TraceStats(ctypes.Structure):
 
 
 STATS_LEN = len(TraceStats._fields_)   # int64 words of a wgrt_trace_stats (torch stats tensors)
+# ... and their indices by name: STAT.bounces, STAT.eyebox_hits, ... (tests/test_capi.py pins the layout to the header)
+STAT = types.SimpleNamespace(**{name: i for i, (name, _) in enumerate(TraceStats._fields_)})
 
 
 class DebugOpts(ctypes.Structure):

@@ -1,0 +1,227 @@
+// wgrt_args.h -- what every kernel of a launch is handed: the device-side scene view (LocatorT), the
+// launch arguments (TraceArgs) and the handle that re-reads them from the kernarg segment (KArgs), the
+// codes and the counter record (Counters) shared by both lanes of the per-ray state machine.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/wgrt.h"
+#include "wgrt_common.h"
+#include "wgrt_scene_build.h"
+
+namespace wgrt {
+
+// s_waitcnt vmcnt(0) with expcnt / lgkmcnt left at their maxima, in the gfx9 simm16 encoding (vmcnt bits
+// 3:0 and 15:14, expcnt 6:4 = 7, lgkmcnt 11:8 = 15): through __builtin_amdgcn_s_waitcnt, so the compiler's
+// wait insertion knows that every vector-memory access issued before it has completed
+constexpr int kWaitVmcnt0 = 0x0F70;
+
+// ----------------------------------------------------------------------------
+// device-side scene view
+// ----------------------------------------------------------------------------
+// The exact polygon locator (wgrt_scene_build.cpp).  CellT = uint64_t cell words (up to 32
+// polygons), uint32_t (up to 16 polygons: half the grid's cache footprint).
+template <class CellT>
+struct LocatorT {
+    using Word = CellT;
+    const CellT *cells;
+    const double *verts;
+    const int32_t *poly_off;
+    const int32_t *row_off;
+    const int32_t *row_edges;
+    double x0, y0, inv_h;
+    int ncx, ncy;
+    const double *bands;    // 128-B band records (LocatorHost::bands); NULL: CSR lists only
+};
+using Locator = LocatorT<uint64_t>;
+
+struct TraceArgs {
+    const float *x, *y, *m, *n, *l, *te, *tm, *dph;
+    uint32_t *rng;
+    float *eb;
+    wgrt_trace_stats *stats;
+    uint32_t *per_ray;
+    int64_t n_rays, gid_offset;
+    const double *tiles;
+    Locator loc;
+    int tile_d, nfc, noc, nx, ny, nl;
+    double n_g, inv_n_g;
+    double threshold;   // ener * efficiency > threshold guard of R2..R5: 0 full colour, 1e-15 single lambda
+    const int32_t *order;   // Jones-vector variants: issue order of the 64-ray chunks (NULL: ascending)
+    const double *jtiles;   // Jones-vector tiles (wgrt_common.h kJ*)
+    int jtile_d;
+    // Jones-vector variants: out-couplings appended as (position, tile index) and binned into
+    // matrix_EB by the epilogue kernel after the launch
+    double2 *q_xy;
+    uint32_t *q_i;
+    unsigned long long *q_count;
+    double cert_tol;   // Jones-vector variants: base of the double-precision certification bound
+    double cert_tol32; // ... and of the single-precision estimate's bound
+    unsigned long long *replay_count;   // Jones-vector variants: abandoned rays (local indices)
+    uint32_t *replay_list;
+    // Jones-vector variants: per-workgroup counter partials (a Counters record in a kPartWords slot) of
+    // the trace kernel, summed into *stats by the epilogue -- no contended atomics on the stats
+    unsigned long long *part;
+    int n_trace_waves;                  // partial slots of the trace kernel (one per workgroup)
+    unsigned long long *heads0;         // this launch's counter set (kScratchCtr words)
+    unsigned long long *other_ctr;      // the next launch's counter set, zeroed by this launch's epilogue
+    uint32_t *full_list;                // out-coupling queue blocks the trace waves filled (block numbers); with the
+                                        // in-kernel epilogue: per block, the link to the block its wave filled before
+    unsigned long long *full_count;
+    unsigned long long *epi_acc;        // in-kernel epilogue: the launch's totals (a Counters record) ...
+    unsigned long long *epi_done;       // ... and the count of trace workgroups that have added theirs
+    unsigned long long *timeline;       // debug: per-wave timeline (wgrt_debug_opts), timeline kernels only
+    int64_t timeline_waves;
+    // fused launches (variants 7 / 9, n_iter > 1): n_iter chained traces of every ray in one
+    // launch; rng64[i] = (state << 32) | iter_tag(iter_epoch, traces completed, broken)
+    int n_iter;
+    uint64_t *rng64;
+    uint32_t iter_epoch;
+    unsigned long long handoff_wait_ticks;   // fused: s_memrealtime ticks a lane may wait for a hand-off ...
+    uint32_t handoff_min_passes;             // ... once its wave has also run this many passes waiting
+    // global ray ids of an interleaved shard (wgrt_launch_opts.gid_blocks): NULL = gid_offset + i
+    const int64_t *gid_blocks;
+    int64_t gid_block_rays;
+};
+
+// TraceArgs fields re-read from the kernarg segment where they are used (a volatile scalar load,
+// a scalar-cache hit) instead of being held in SGPRs for the whole kernel: the Jones loop keeps
+// only its per-pass operands in SGPRs; the ray columns and the rare-path pointers (refill,
+// retire, replay, out-coupling) are fetched when those run.
+//
+// KArgs is the handle those reads go through: the base of the kernarg segment as the KERNEL BODY
+// saw it.  Only kernel_kargs<Kernel>() makes one, and it refuses to compile unless Kernel's first
+// parameter is a TraceArgs (which then lies at offset 0 of the segment).  A function that reads a
+// field takes the handle as a parameter, so it reads the right segment whether or not the
+// compiler inlines it; __builtin_amdgcn_kernarg_segment_ptr() evaluated inside a called function
+// instead reads whatever the caller's registers hold (round 4's out-of-line EDGE build faulted
+// with hipErrorIllegalAddress that way).
+typedef const char __attribute__((address_space(4))) KSeg;
+
+template <class F>
+struct first_param;
+template <class A0, class... R>
+struct first_param<void(A0, R...)> {
+    using type = A0;
+};
+template <class X, class Y>
+struct same_type {
+    static constexpr bool value = false;
+};
+template <class X>
+struct same_type<X, X> {
+    static constexpr bool value = true;
+};
+
+class KArgs {
+    KSeg *base_;
+    __device__ explicit KArgs(KSeg *b) : base_(b) {}
+    template <class Kernel>
+    friend __device__ KArgs kernel_kargs();
+
+public:
+    template <class T>
+    __device__ __forceinline__ T get(size_t off) const {
+        return *(volatile const T __attribute__((address_space(4))) *)(base_ + off);
+    }
+    // the whole TraceArgs, for a rare path that hands it to code written against the struct (the replay)
+    __device__ __forceinline__ TraceArgs args() const {
+        return *(const TraceArgs *)base_;
+    }
+};
+
+// Call in the body of the __global__ function Kernel itself: kernel_kargs<decltype(my_kernel<...>)>().
+template <class Kernel>
+__device__ __forceinline__ KArgs kernel_kargs() {
+    static_assert(same_type<typename first_param<Kernel>::type, TraceArgs>::value,
+                  "KArgs reads TraceArgs fields at their offsets in the kernarg segment: the kernel's first "
+                  "parameter must be the TraceArgs");
+    return KArgs((KSeg *)__builtin_amdgcn_kernarg_segment_ptr());
+}
+
+// A TraceArgs field through the handle K in scope.
+#define KA(f) K.template get<decltype(TraceArgs::f)>(offsetof(TraceArgs, f))
+// the same for the locator's exact-test arrays (TraceArgs::loc holds them for every variant)
+#define KLOCP(Kp, f) (Kp)->template get<decltype(Locator::f)>(offsetof(TraceArgs, loc) + offsetof(Locator, f))
+#define KLOC(f) KLOCP(&K, f)
+
+// Global id of local ray i (wgrt_launch_opts.gid_blocks): only the zero-state RNG fix-up reads it.
+__device__ __forceinline__ int64_t ray_gid(const TraceArgs &A, int64_t i) {
+    return A.gid_blocks ? A.gid_blocks[i / A.gid_block_rays] + i % A.gid_block_rays : A.gid_offset + i;
+}
+// The same from the kernarg segment.
+__device__ __forceinline__ int64_t ray_gid_ka(const KArgs &K, int64_t i) {
+    const int64_t *gb = KA(gid_blocks);
+    if (gb) {
+        const int64_t r = KA(gid_block_rays);
+        return gb[i / r] + i % r;
+    }
+    return KA(gid_offset) + i;
+}
+
+// What a lane's step returns besides a block index / region (the Jones-vector lane adds two, wgrt_jones_lane.h).
+enum : int { kDie = -1, kTransit = -2 };
+constexpr int kChunk = 64;   // rays per work-queue chunk of the Jones-vector variants (chunk_order unit)
+
+__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// The counters a kernel accumulates: one 64-bit word per wgrt_trace_stats field, in the struct's order, so
+// word k of a record adds to word k of *stats.  Every site that sums, parks or publishes counters goes
+// through this record; a word a kernel never touches stays a compile-time zero and costs nothing up to
+// the first trip through memory.
+enum Ctr : int { kCtrBounces, kCtrBadRays, kCtrHits, kCtrReplayed, kCtrGiveups, kCtrInter, kCtrLibm, kCtrWords };
+static_assert(sizeof(wgrt_trace_stats) == kCtrWords * sizeof(uint64_t) &&
+                  offsetof(wgrt_trace_stats, bounces) == 8 * kCtrBounces &&
+                  offsetof(wgrt_trace_stats, bad_rays) == 8 * kCtrBadRays &&
+                  offsetof(wgrt_trace_stats, eyebox_hits) == 8 * kCtrHits &&
+                  offsetof(wgrt_trace_stats, replayed) == 8 * kCtrReplayed &&
+                  offsetof(wgrt_trace_stats, handoff_giveups) == 8 * kCtrGiveups &&
+                  offsetof(wgrt_trace_stats, interactions) == 8 * kCtrInter &&
+                  offsetof(wgrt_trace_stats, libm_rays) == 8 * kCtrLibm,
+              "Ctr names the words of wgrt_trace_stats: a new field gets its index here");
+constexpr int kPartWords = (kCtrWords + 7) / 8 * 8;   // a trace workgroup's partial slot: whole 64-B lines
+
+struct Counters {
+    unsigned long long w[kCtrWords] = {};
+
+    // every lane's record -> its wave's sums (in every lane)
+    __device__ __forceinline__ void wave_reduce() {
+        for (int k = 0; k < kCtrWords; ++k) w[k] = wave_sum(w[k]);
+    }
+    // ... -> the 256-thread workgroup's sums through one LDS array: valid in thread 0 only
+    __device__ __forceinline__ void block_reduce(unsigned long long (&red)[4][kCtrWords]) {
+        wave_reduce();
+        if ((threadIdx.x & 63) == 0)
+            for (int k = 0; k < kCtrWords; ++k) red[threadIdx.x >> 6][k] = w[k];
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int k = 0; k < kCtrWords; ++k) w[k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
+    }
+    // the non-zero words added to kCtrWords words of memory, *stats or a launch's totals (the atomics commute)
+    __device__ __forceinline__ void add_to(unsigned long long *dst) const {
+        for (int k = 0; k < kCtrWords; ++k)
+            if (w[k]) atomicAdd(dst + k, w[k]);
+    }
+    // (st != NULL is the caller's test, made with its own condition: folded in here it cost the single-launch
+    // kernels a VGPR across the wave loop, profiles/untangle_kernel_identity.md)
+    __device__ __forceinline__ void add_to(wgrt_trace_stats *st) const { add_to((unsigned long long *)st); }
+    // parked in / added from a partial slot that only this workgroup writes and a later kernel reads
+    __device__ __forceinline__ void store(unsigned long long *slot) const {
+        for (int k = 0; k < kCtrWords; ++k) slot[k] = w[k];
+    }
+    __device__ __forceinline__ void add_from(const unsigned long long *slot) {
+        for (int k = 0; k < kCtrWords; ++k) w[k] += slot[k];
+    }
+    // totals other workgroups of this kernel added with agent-scope atomics
+    __device__ __forceinline__ void load_agent(const unsigned long long *acc) {
+        for (int k = 0; k < kCtrWords; ++k) w[k] = __hip_atomic_load(acc + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+
+}  // namespace wgrt

@@ -1,0 +1,358 @@
+// wgrt_exact_lane.h -- the exact lane of the reference's per-ray state machine
+// (GPU_ray_tracing_functions.py = GRTF:833-1246): the reference's float64
+// arithmetic in its expression order.  Variant 1, the replays and the certification shadow run it.
+#pragma once
+
+#include "wgrt_args.h"
+#include "wgrt_locator.h"
+
+namespace wgrt {
+
+// E_field_cal (GRTF:132-152).  rec = (p, q, r, s) complex in the reference call's argument
+// order: Ete' = p*te_in + r*tm_in, Etm' = q*te_in + s*tm_in.  The multiplications by 0.0 are
+// Python's real->complex promotions; they are kept so signed zeros propagate exactly.
+struct Field {
+    double te_re, te_im, tm_re, tm_im;
+};
+
+__device__ __forceinline__ Field efield(double Ete, double Etm, double cd, double sd, const double *rec) {
+    const double pr = rec[0], pi = rec[1], qr = rec[2], qi = rec[3];
+    const double rr = rec[4], ri = rec[5], sr = rec[6], si = rec[7];
+    const double ti_re = cd * Etm - sd * 0.0, ti_im = cd * 0.0 + sd * Etm;
+    const double a_re = pr * Ete - pi * 0.0, a_im = pr * 0.0 + pi * Ete;
+    const double b_re = rr * ti_re - ri * ti_im, b_im = rr * ti_im + ri * ti_re;
+    const double c_re = qr * Ete - qi * 0.0, c_im = qr * 0.0 + qi * Ete;
+    const double d_re = sr * ti_re - si * ti_im, d_im = sr * ti_im + si * ti_re;
+    return Field{a_re + b_re, a_im + b_im, c_re + d_re, c_im + d_im};
+}
+
+// |Ete'|^2 + |Etm'|^2 of efield() without the "* 0.0" promotion terms: for finite inputs
+// (LUTs are checked at scene creation, ray state stays finite) those terms only change the
+// sign of zero components, so every component has the same magnitude as efield()'s and the
+// sum of squares is identical.  Used for the branch estimates only.
+__device__ __forceinline__ double efield_sq(double Ete, double Etm, double cd, double sd, const double *rec) {
+    const double pr = rec[0], pi = rec[1], qr = rec[2], qi = rec[3];
+    const double rr = rec[4], ri = rec[5], sr = rec[6], si = rec[7];
+    const double ti_re = cd * Etm, ti_im = sd * Etm;
+    const double a_re = pr * Ete + (rr * ti_re - ri * ti_im), a_im = pi * Ete + (rr * ti_im + ri * ti_re);
+    const double c_re = qr * Ete + (sr * ti_re - si * ti_im), c_im = qi * Ete + (sr * ti_im + si * ti_re);
+    return (a_re * a_re + a_im * a_im) + (c_re * c_re + c_im * c_im);
+}
+
+// The exact lane carries the ray's delta_phase as the reference does (GRTF:857): a taken branch
+// sets it to E_field_cal's wrapped phase difference plus lut_TIR (GRTF:145-150, 877, 926, ...), a
+// miss hop adds 2 lut_TIR without a wrap (GRTF:1052, 1108, 1178), and every E_field_cal takes
+// cos / sin of the accumulated, unwrapped value (GRTF:135).  The rounding of that accumulation is
+// part of the reference's result: with lut_TIR near +-pi and runs of hundreds of hops the phase
+// reaches thousands of radians, and a rotation carried as a product of hop phasors instead (round
+// 4's lane) drifted from it far enough to change decisions (the adversarial_lossless LUTs of
+// tests/test_gpu_certification.py: 33 of 96,768 rays).  This lane differs from the reference only by
+// the device's cos / sin / atan2 against glibc's (ulps of the result).
+struct Ray {
+    double x, y, te, tm, cos_t, ener;
+    double dph;   // delta_phase (GRTF:857), unwrapped as the reference carries it
+    uint32_t s;
+    int region;
+};
+
+// One ray in flight on a lane.
+struct Lane {
+    Ray r;
+    const double *T;   // this ray's (lambda, m, n) tile
+    int64_t i;         // local ray index
+    int l, m, n;
+    uint32_t bounces;  // 1 in-coupling event + loop iterations (GRTF:905)
+    bool hit;          // accumulated into matrix_EB
+    bool libm;         // a guard product ener * e_k fell below 2^-1000 (wgrt_trace_stats.libm_rays)
+};
+
+// Load ray i (GRTF:846-859).  Returns false (and leaves the lane empty) for a ray whose
+// FoV / wavelength indices fall outside the scene.
+__device__ __forceinline__ bool lane_load(const TraceArgs &A, int64_t i, Lane &L) {
+    const int64_t ld = i;
+    const int m = (int)A.m[ld], n = (int)A.n[ld], l = A.l ? (int)A.l[ld] : 0;
+    if (!(m >= 0 && m < A.nx && n >= 0 && n < A.ny && l >= 0 && l < A.nl)) return false;
+    L.i = i;
+    L.l = l;
+    L.m = m;
+    L.n = n;
+    L.T = A.tiles + (int64_t)((l * A.nx + m) * A.ny + n) * A.tile_d;
+    L.r.x = (double)A.x[ld];
+    L.r.y = (double)A.y[ld];
+    L.r.te = (double)A.te[ld];
+    L.r.tm = (double)A.tm[ld];
+    L.r.dph = (double)A.dph[ld];
+    L.r.cos_t = 1.0;
+    L.r.ener = 1.0;
+    L.r.s = A.rng[ld];
+    L.r.region = 0;
+    L.bounces = 1;
+    L.hit = false;
+    L.libm = false;
+    return true;
+}
+
+// A coupler interaction: `blk` of the lane's tile, `kind` 0 in-coupler states (entry event,
+// R0, R1), 1 R2, 2 R3, 3 R4, 4 R5.  Evaluates every branch's efficiency (GRTF:860-869,
+// 909-918, ..., 1186-1200), draws, and applies the chosen branch.  Returns the next region
+// or kDie.  Only the chosen branch's phase (two atan2) is evaluated; its field is recomputed
+// by the same operations rather than kept in registers for every branch.
+template <class Loc>
+__device__ __forceinline__ int interact(const TraceArgs &A, const Loc &loc, Lane &L, int blk, int kind,
+                                        bool entry) {
+    Ray &r = L.r;
+    const double *T = L.T;
+    const double *B = T + kTileHeader + kBlock * blk;
+    // phase = complex(math.cos(delta), math.sin(delta)) (GRTF:135), once for every E_field_cal call of
+    // this interaction (they all take the same delta)
+    const double cd = cos(r.dph), sd = sin(r.dph);
+    const bool three = kind >= 3;
+    const bool thr = kind >= 1;  // the ener > threshold guard exists only in R2..R5
+    const double denom = entry ? T[kTileCosIc1] : r.cos_t;
+    const double u = rng_draw_lazy(r.s, [&]() { return ray_gid(A, L.i); });
+
+    // Decide the branch.  The reference compares u with cumulative branch efficiencies
+    // e_k = (hypot(Ete')^2 + hypot(Etm')^2) * cosA_k / cos(theta) [* or / n_g].  Here the
+    // comparisons are first made with cheap estimates (squared moduli instead of the
+    // correctly rounded hypot, one reciprocal instead of three divisions), whose relative
+    // error is below 1e-14; a decision is accepted only when every threshold it depends on
+    // is farther than 1e-12 (relative) from u and no product can underflow, which makes it
+    // provably the reference's decision.  Otherwise -- about once in 1e12 draws -- the lane
+    // recomputes every e_k exactly as the reference does.  The chosen branch's magnitudes
+    // and efficiency are always computed exactly.
+    // one branch at a time (a rolled loop keeps the register peak down)
+    double q[3] = {0.0, 0.0, 0.0};
+    const int nbr = three ? 3 : 2;
+#pragma unroll 1
+    for (int k = 0; k < nbr; ++k) {
+        const double v = efield_sq(r.te, r.tm, cd, sd, B + kBlockRec + 8 * k);
+        q[0] = k == 0 ? v : q[0];
+        q[1] = k == 1 ? v : q[1];
+        q[2] = k == 2 ? v : q[2];
+    }
+    // 1 / denom to ~1e-16 relative (estimates only): hardware reciprocal + two Newton steps
+    double inv = __builtin_amdgcn_rcp(denom);
+    inv = fma(inv, fma(-denom, inv, 1.0), inv);
+    inv = fma(inv, fma(-denom, inv, 1.0), inv);
+    double a0 = q[0] * B[0] * inv, a1 = q[1] * B[1] * inv;
+    if (entry) {
+        a0 *= A.n_g;
+        a1 *= A.n_g;
+    }
+    const double a2 = three ? q[2] * B[2] * inv * A.inv_n_g : 0.0;
+    const double c0 = a0, c1 = a0 + a1, c2 = c1 + a2;
+    const double scale = fabs(a0) + fabs(a1) + fabs(a2);   // bounds every partial sum
+    const double tol = 1e-12 * scale;
+    const bool tiny = thr && !(r.ener > 1e-200 && (a0 == 0.0 || a0 > 1e-100) && (a1 == 0.0 || a1 > 1e-100) &&
+                               (!three || a2 == 0.0 || a2 > 1e-100));
+    // ener * e_k > threshold (GRTF:606 single-lambda: 1e-15; GRTF:1020 full colour: 0).  With
+    // threshold 0 and no underflow it is e_k > 0, i.e. a_k > 0; otherwise the estimate
+    // ener * a_k must clear the threshold by a relative margin far above its error.
+    const double t = A.threshold;
+    const double p0 = r.ener * a0, p1 = r.ener * a1, p2 = r.ener * a2;
+    const double tmar = 1e-12 * t;
+    const bool tsure = !thr || t == 0.0 ||
+                       (fabs(p0 - t) > tmar && fabs(p1 - t) > tmar && (!three || fabs(p2 - t) > tmar));
+    const bool pass0 = !thr || (t == 0.0 ? a0 > 0.0 : p0 > t);
+    const bool pass1 = !thr || (t == 0.0 ? a1 > 0.0 : p1 > t);
+    const bool pass2 = t == 0.0 ? a2 > 0.0 : p2 > t;
+    const bool sure = scale > 1e-290 && !tiny && tsure && fabs(u - c0) > tol && fabs(u - c1) > tol &&
+                      (!three || fabs(u - c2) > tol);
+    int b;
+    if (sure) {
+        if (u <= c0 && pass0) b = 0;
+        else if (u <= c1 && pass1) b = 1;
+        else if (three && u <= c2 && pass2) b = 2;
+        else return kDie;
+    } else {
+        double te[3], tm[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            te[k] = tm[k] = 0.0;
+            if (k < 2 || three) {
+                const Field f = efield(r.te, r.tm, cd, sd, B + kBlockRec + 8 * k);
+                te[k] = hypot_cr(f.te_re, f.te_im);
+                tm[k] = hypot_cr(f.tm_re, f.tm_im);
+            }
+        }
+        double e0 = (te[0] * te[0] + tm[0] * tm[0]) * B[0] / denom;
+        double e1 = (te[1] * te[1] + tm[1] * tm[1]) * B[1] / denom;
+        if (entry) {
+            e0 = e0 * A.n_g;
+            e1 = e1 * A.n_g;
+        }
+        double e2 = 0.0;
+        if (three) e2 = (te[2] * te[2] + tm[2] * tm[2]) * B[2] / denom / A.n_g;
+        // the ener-underflow regime: a guard product ener * e_k (GRTF:1020, 1073, 1136,
+        // ...) of a nonzero efficiency below 2^-1000, next to the subnormal range, where whether it rounds
+        // to zero -- and so the decision -- hangs on the last bits of the libm's cos / sin / atan2.  The
+        // certain path above never gets here with such a product (it needs ener > 1e-200 and every
+        // nonzero a_k > 1e-100), so checking this path sees every one.
+        if (thr)
+            L.libm |= ((e0 > 0.0) & (r.ener * e0 < 0x1p-1000)) | ((e1 > 0.0) & (r.ener * e1 < 0x1p-1000)) |
+                      (three & (e2 > 0.0) & (r.ener * e2 < 0x1p-1000));
+        if (u <= e0 && (!thr || r.ener * e0 > t)) b = 0;
+        else if (u <= e0 + e1 && (!thr || r.ener * e1 > t)) b = 1;
+        else if (three && u <= e0 + e1 + e2 && r.ener * e2 > t) b = 2;
+        else return kDie;
+    }
+
+    if (b == 2) {  // out-coupling (GRTF:1162-1171, 1231-1240)
+        if (inside_or_on_edge(r.x, r.y, T + kTileEbRect, 4)) {
+            const double xmin = T[kTileEbRange], xmax = T[kTileEbRange + 1];
+            const double ymin = T[kTileEbRange + 2], ymax = T[kTileEbRange + 3];
+            const double dx = (xmax - xmin) / kEbNx, dy = (ymax - ymin) / kEbNy;
+            int64_t ix = (int64_t)floor((r.x - xmin) / dx);
+            int64_t iy = (int64_t)floor((r.y - ymin) / dy);
+            // compiled-numba addressing (GRTF:164): a negative index wraps once, an index
+            // equal to the axis length aliases into the next row; guarded to the buffer
+            if (ix < 0) ix += kEbNx;
+            if (iy < 0) iy += kEbNy;
+            const int64_t off = ((((int64_t)L.l * A.ny + L.n) * A.nx + L.m) * kEbNy + iy) * kEbNx + ix;
+            const int64_t total = (int64_t)A.nl * A.ny * A.nx * kEbNy * kEbNx;
+            if (off >= 0 && off < total) {
+                unsafeAtomicAdd(A.eb + off, 1.0f);
+                L.hit = true;
+            }
+        }
+        return kDie;
+    }
+    const Field f = efield(r.te, r.tm, cd, sd, B + kBlockRec + 8 * b);
+    const double cte = hypot_cr(f.te_re, f.te_im);
+    const double ctm = hypot_cr(f.tm_re, f.tm_im);
+    double e = (cte * cte + ctm * ctm) * B[b] / denom;   // exact e_b (GRTF:868-869, 917-918, ...)
+    if (entry) e = e * A.n_g;
+    // take the branch (GRTF:872-882 and every branch body after it)
+    const double norm = sqrt(cte * cte + ctm * ctm);
+    // E_field_cal's output phase (GRTF:145-150): 0 for a component below 1e-20, wrapped difference
+    const double pte = cte >= 1e-20 ? atan2(f.te_im, f.te_re) : 0.0;
+    const double ptm = ctm >= 1e-20 ? atan2(f.tm_im, f.tm_re) : 0.0;
+    int tir, gap;
+    if (kind == 0) { tir = b == 0 ? 0 : 2; gap = b == 0 ? 0 : 4; }
+    else if (kind <= 2) { tir = b == 0 ? 0 : 1; gap = b == 0 ? 0 : 2; }
+    else { tir = b == 0 ? 1 : 3; gap = b == 0 ? 2 : 6; }
+    r.cos_t = B[b];
+    r.te = cte / norm;
+    r.tm = ctm / norm;
+    r.dph = wrap_pi(ptm - pte) + T[kTileTir + tir];   // delta_phase = delta_phase_b + lut_TIR[...] (GRTF:877, ...)
+    r.x += T[kTileGap + gap];
+    r.y += T[kTileGap + gap + 1];
+    r.ener = r.ener * e;
+    if (kind == 0) {
+        const bool in_ic = in_poly(loc, locate(loc, r.x, r.y), kPolyIC, r.x, r.y);
+        if (b == 0) return in_ic ? 0 : 2;
+        return in_ic ? 1 : kDie;
+    }
+    if (kind <= 2) return b == 0 ? 2 : 3;
+    return b == 0 ? 4 : 5;
+}
+
+// Run a ray through the loop iterations that need no Monte-Carlo interaction -- hops that
+// miss every coupler slice (GRTF:1049-1052, 1102-1108, 1175-1178) and the R3 -> R4 switch
+// -- until the next interaction is due.  Returns that interaction's block index, or kDie
+// when the ray terminated (left eff_reg1 at GRTF:906, R5 miss at GRTF:1244-1246, or
+// range(1e5) exhausted).  Each iteration counts one bounce.
+template <class Loc>
+__device__ __forceinline__ int advance(const TraceArgs &A, const Loc &loc, Lane &L, int &kind) {
+    Ray &r = L.r;
+    const double *T = L.T;
+    // A miss hop's step is fixed by the region: R2 moves by gap[0:2] and adds 2*TIR[0],
+    // R3 and R4 move by gap[2:4] and add 2*TIR[1] (R5 misses die).  Fetch it once.
+    const int g = (r.region == 2) ? 0 : 2;
+    const double gx = T[kTileGap + g], gy = T[kTileGap + g + 1];
+    const double tir2 = 2 * T[kTileTir + g / 2];   // 2*lut_TIR[...] (exact doubling)
+    for (;;) {
+        if (L.bounces > (uint32_t)kMaxLoop) return kDie;
+        ++L.bounces;
+        const Cell c = locate(loc, r.x, r.y);
+        if (!in_poly(loc, c, kPolyEff1, r.x, r.y)) return kDie;
+        const int region = r.region;
+        if (region <= 1) {
+            kind = 0;
+            return 1 + region;
+        }
+        int s;
+        if (region <= 3) {
+            s = first_slice(loc, c, kPolyFC0, A.nfc, r.x, r.y);
+            if (s >= 0) {
+                kind = region - 1;
+                return 3 + (region - 2) * A.nfc + s;
+            }
+            if (region == 3 && !in_poly(loc, c, kPolyEff2, r.x, r.y)) {
+                r.region = 4;   // GRTF:1103-1104: switch to the out-coupler state without moving
+                continue;
+            }
+        } else {
+            s = first_slice(loc, c, kPolyFC0 + A.nfc, A.noc, r.x, r.y);
+            if (s >= 0) {
+                kind = region - 1;
+                return 3 + 2 * A.nfc + (region - 4) * A.noc + s;
+            }
+            if (region == 5) return kDie;
+        }
+        r.x += gx;
+        r.y += gy;
+        r.dph += tir2;   // delta_phase += 2*lut_TIR[...] (GRTF:1052, 1108, 1178)
+    }
+}
+
+// Eyebox accumulation of an out-coupling (GRTF:1162-1171, 1231-1240): the per-FoV
+// eyebox rectangle test, the bin, and the atomic; compiled-numba addressing as in interact().
+__device__ __forceinline__ bool eyebox_add(const TraceArgs &A, int l, int m, int n, double x, double y) {
+    const double *T = A.tiles + (int64_t)((l * A.nx + m) * A.ny + n) * A.tile_d;
+    if (!inside_or_on_edge(x, y, T + kTileEbRect, 4)) return false;
+    const double xmin = T[kTileEbRange], xmax = T[kTileEbRange + 1];
+    const double ymin = T[kTileEbRange + 2], ymax = T[kTileEbRange + 3];
+    const double dx = (xmax - xmin) / kEbNx, dy = (ymax - ymin) / kEbNy;
+    int64_t ix = (int64_t)floor((x - xmin) / dx);
+    int64_t iy = (int64_t)floor((y - ymin) / dy);
+    if (ix < 0) ix += kEbNx;
+    if (iy < 0) iy += kEbNy;
+    const int64_t off = ((((int64_t)l * A.ny + n) * A.nx + m) * kEbNy + iy) * kEbNx + ix;
+    const int64_t total = (int64_t)A.nl * A.ny * A.nx * kEbNy * kEbNx;
+    if (off < 0 || off >= total) return false;
+    unsafeAtomicAdd(A.eb + off, 1.0f);
+    return true;
+}
+
+template <class LaneT>
+__device__ __forceinline__ void lane_retire(const TraceArgs &A, const LaneT &L) {
+    A.rng[L.i] = L.r.s;
+    if (A.per_ray) A.per_ray[L.i] = L.bounces;
+}
+
+// Per-wave reduction of the ray counters, then one 64-bit atomic per non-zero counter per wave.
+__device__ __forceinline__ void add_stats(wgrt_trace_stats *stats, Counters c) {
+    c.wave_reduce();
+    if ((threadIdx.x & 63) == 0 && stats) c.add_to(stats);
+}
+
+// Trace ray i to termination with the reference arithmetic (variant 1's lane; replays), counted in c.  With
+// s_io, the trace starts from *s_io instead of rng_states[i] and leaves its final state there
+// (rng_states untouched).
+__device__ __forceinline__ void trace_one(const TraceArgs &A, int64_t i, Counters &c, uint32_t *s_io = nullptr) {
+    Lane L;
+    if (!lane_load(A, i, L)) {
+        ++c.w[kCtrBadRays];
+        return;
+    }
+    if (s_io) L.r.s = *s_io;
+    int blk = 0, kind = 0;
+    bool entry = true;
+    for (;;) {
+        const int next = interact(A, A.loc, L, blk, kind, entry);
+        if (next < 0) break;
+        L.r.region = next;
+        entry = false;
+        blk = advance(A, A.loc, L, kind);
+        if (blk < 0) break;
+        ++c.w[kCtrInter];   // the interactions after the in-coupling event
+    }
+    if (s_io) *s_io = L.r.s;
+    else lane_retire(A, L);
+    c.w[kCtrBounces] += L.bounces;
+    c.w[kCtrHits] += L.hit;
+    c.w[kCtrLibm] += L.libm ? 1u : 0u;
+}
+
+}  // namespace wgrt

@@ -212,7 +212,7 @@ WGRT_HD void pack_tile(const PackView &v, int64_t g, double *T, double *J) {
             h[3] = (float)((pr * ri - pi * rr) + (qr * si - qi * sr));   // Im(conj(p) r + conj(q) s)
             if (k < 2) {
                 // kappa^2 = s1^2 / s2^2 of H (s1^2 - s2^2 = sqrt((h11 - h22)^2 + 4 |h12|^2), no cancellation):
-                // not scaled-unitary once kappa^2 > 1 + 1e-6 (the Jones lane's amplification step, wgrt_device.h)
+                // not scaled-unitary once kappa^2 > 1 + 1e-6 (the Jones lane's amplification step, wgrt_jones_lane.h)
                 const double h11 = (pr * pr + pi * pi) + (qr * qr + qi * qi), h22 = (rr * rr + ri * ri) + (sr * sr + si * si);
                 const double g_re = (pr * rr + pi * ri) + (qr * sr + qi * si), g_im = (pr * ri - pi * rr) + (qr * si - qi * sr);
                 const double dif = sqrt((h11 - h22) * (h11 - h22) + 4.0 * (g_re * g_re + g_im * g_im));

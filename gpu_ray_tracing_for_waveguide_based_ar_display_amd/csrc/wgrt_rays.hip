@@ -6,7 +6,7 @@
 #include <string>
 
 #include "../../include/wgrt.h"
-#include "wgrt_device.h"
+#include "wgrt_common.h"
 #include "wgrt_host.h"
 
 using namespace wgrt;

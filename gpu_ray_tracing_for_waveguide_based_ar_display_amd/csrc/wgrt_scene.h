@@ -8,7 +8,7 @@
 #include <mutex>
 #include <string>
 
-#include "wgrt_device.h"
+#include "wgrt_args.h"
 #include "wgrt_host.h"
 
 struct wgrt_scene {
@@ -31,7 +31,7 @@ struct wgrt_scene {
     int jones_grid[2][2][2] = {};   // resident 256-thread workgroups: [64-bit cells][fused][single wavelength]
     int jones_tl_grid[2] = {};      // ... of the debug timeline instantiations (32-bit cells): [fused]
     int64_t nonunitary_blocks = 0;  // Jones blocks whose branch matrices are not scaled-unitary (their launches
-                                    // run the AMP instantiations: wgrt_device.h, the amplification step)
+                                    // run the AMP instantiations: wgrt_jones_lane.h, the amplification step)
     // Jones-vector launches: per-stream launch scratch (launches on one stream are ordered, so
     // they may share it; launches on different streams never do)
     struct Scratch {

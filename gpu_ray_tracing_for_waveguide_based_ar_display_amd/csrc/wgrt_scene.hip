@@ -13,7 +13,7 @@
 #include "../../include/wgrt.h"
 #include "../../include/wgrt_debug.h"
 #include "wgrt_common.h"
-#include "wgrt_device.h"
+#include "wgrt_locator.h"
 #include "wgrt_scene.h"
 #include "wgrt_scene_build.h"
 

@@ -2,7 +2,7 @@
 // wgrt_debug_shadow, include/wgrt.h).
 //
 // The Jones-vector kernels (variants 7 / 9) take a Monte-Carlo decision only when the draw lies
-// farther than a bound `tol` from every branch threshold (wgrt_device.h, "Jones-vector path").
+// farther than a bound `tol` from every branch threshold (wgrt_jones_lane.h, "Jones-vector path").
 // This kernel measures how much of that bound the arithmetic actually uses.  One lane per ray
 // traces the ray with the reference's own arithmetic, literally (GPU_ray_tracing_functions.py =
 // GRTF):
@@ -34,7 +34,8 @@
 #include "../../include/wgrt.h"
 #include "../../include/wgrt_debug.h"
 #include "wgrt_common.h"
-#include "wgrt_device.h"
+#include "wgrt_exact_lane.h"
+#include "wgrt_jones_lane.h"
 #include "wgrt_scene.h"
 
 using namespace wgrt;
@@ -79,7 +80,7 @@ struct RefField {
 
 __device__ __forceinline__ RefField ref_efield(double Ete, double Etm, double dph, const double *rec) {
     const double cd = cos(dph), sd = sin(dph);
-    const Field f = efield(Ete, Etm, cd, sd, rec);   // Python-promotion complex products (wgrt_device.h)
+    const Field f = efield(Ete, Etm, cd, sd, rec);   // Python-promotion complex products (wgrt_exact_lane.h)
     RefField o;
     o.te = hypot_cr(f.te_re, f.te_im);
     o.tm = hypot_cr(f.tm_re, f.tm_im);
@@ -143,7 +144,7 @@ __device__ void shadow_trace(const TraceArgs &A, const Loc &loc, int64_t i, Shad
         else if (three && u <= e0 + e1 + e2 && ener * e2 > t) b = 2;
         else b = -1;
 
-        // ---- the product lane's view of the same decision (wgrt_device.h Jones interact) ----
+        // ---- the product lane's view of the same decision (wgrt_jones_lane.h interact) ----
         {
             const double2 hp = *(const double2 *)(J + kJHop + (region == 2 ? 0 : 2));
             for (uint32_t h = 0; h < hops; ++h) {
@@ -200,7 +201,7 @@ __device__ void shadow_trace(const TraceArgs &A, const Loc &loc, int64_t i, Shad
                 const JField f = jones(load_rec(JB + kJBlockRec + 8 * b), jr);
                 const double n2 = norm2(f);
                 const double rn = rsq_nr(n2);
-                if (amp_blk) {   // the product lane's amplification step (wgrt_device.h interact)
+                if (amp_blk) {   // the product lane's amplification step (wgrt_jones_lane.h interact)
                     const float4 hb = ((const float4 *)(JB + kJBlockHerm))[b];
                     float pa, nmin;
                     amp_prepare(hb, en2, A.cert_tol * grow, pa, nmin);

@@ -40,6 +40,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+from ._lib import STAT
+
 MAX_TRACES_PER_CALL = 255   # wgrt_launch_opts.num_iter
 EB_SLAB = 80 * 120          # one (wavelength, FoV) slab of matrix_EB (MAIN:37)
 SPILL = 121                 # floats of the next slab an edge out-coupling can alias into (ix <= 120 at iy 80)
@@ -467,7 +469,7 @@ def timed_run(trace_fn, rays, rng, eb, gid: GidMap, steps: int, per_call: int, s
               group=None, collect=None):
     """bench.py's timed region on one rank: barrier + ``sync()``, ``steps`` chained traces of the
     shard (``run_steps``), the eyebox collective to rank 0 (``collect``, default the reduce),
-    ``sync()`` + barrier.  ``stats[0]`` (the device bounce counter, zeroed here) is what the
+    ``sync()`` + barrier.  ``stats[STAT.bounces]`` (the device bounce counter, zeroed here) is what the
     tracer adds to.  Returns ``(elapsed, bounces, bounces_local)``: the wall time MAX over ranks,
     the bounce total SUM over ranks, this rank's own bounces.  The two small all-reduces run on
     ``stats``'s device (RCCL on the GPU box, gloo in the CPU tests)."""
@@ -489,7 +491,7 @@ def timed_run(trace_fn, rays, rng, eb, gid: GidMap, steps: int, per_call: int, s
     if multi:
         dist.barrier(group)
     elapsed = time.perf_counter() - t0
-    local = int(stats[0].item())
+    local = int(stats[STAT.bounces].item())
     t = torch.tensor([elapsed], dtype=torch.float64, device=stats.device)
     b = torch.tensor([local], dtype=torch.int64, device=stats.device)
     if multi:

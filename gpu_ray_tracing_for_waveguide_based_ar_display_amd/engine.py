@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import STATS_LEN, DebugOpts, Rays, Scene, TraceStats, WgrtError, check, load, ops
+from ._lib import STAT, STATS_LEN, DebugOpts, Rays, Scene, TraceStats, WgrtError, check, load, ops
 
 RAY_COLUMNS = ("x", "y", "gap_x", "gap_y", "pol", "azi", "m", "n", "lmd_num", "te", "tm", "delta_phase")
 READ_COLUMNS = ("x", "y", "m", "n", "lmd_num", "te", "tm", "delta_phase")
@@ -91,11 +91,11 @@ def check_stats(stats: torch.Tensor) -> None:
     (``wgrt_trace_stats.libm_rays``, ABI 7): their paths depend on the libm's last bits, so they may
     differ from a CPU run of the reference.  Synchronises on ``stats``."""
     st = stats.cpu()
-    g = int(st[4])
+    g = int(st[STAT.handoff_giveups])
     if g:
         raise WgrtError(f"{g} fused-launch traces gave up waiting for their ray's previous trace "
                         "(hand-off failure; results of this call are invalid)")
-    lm = int(st[6]) if st.numel() > 6 else 0
+    lm = int(st[STAT.libm_rays]) if st.numel() > STAT.libm_rays else 0
     if lm:
         import warnings
         from .luts import EnerUnderflowWarning
@@ -366,6 +366,6 @@ def selftest_math(a: torch.Tensor, b: torch.Tensor, stream=None) -> torch.Tensor
     return out
 
 
-__all__ = ["Scene", "WgrtError", "TraceStats", "STATS_LEN", "new_stats", "check_stats", "block_runs",
+__all__ = ["Scene", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
            "trace_fullcolor", "trace_single", "init_rays", "schedule_by_lifetime",
            "rays_to_device", "classify_points", "shadow", "selftest_math", "RAY_COLUMNS", "_lib"]

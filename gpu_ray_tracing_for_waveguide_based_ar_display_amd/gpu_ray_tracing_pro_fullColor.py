@@ -68,7 +68,7 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
     from .couplers_coor import design_geometry
     from .distributed import (EyeboxGather, EyeboxReduce, hip_shard_builder, hip_tracer, make_shard, run_steps,
                               split_calls)
-    from .engine import Scene, check_stats, new_stats, reserve
+    from .engine import STAT, Scene, check_stats, new_stats, reserve
     from .luts import load_luts, lut_f32_mask, synthetic_luts, validate_luts
     from .rays import generate_points_in_polygon
 
@@ -136,8 +136,8 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
     if world > 1:
         dist.all_reduce(stats)
     matrix_EB = eb.cpu().numpy() if not on_device or keep_grid else None
-    out = dict(num_rays=num_rays, num_iter=num_iter, gpu_seconds=kern_s, bounces=int(stats[0]),
-               eyebox_hits=int(stats[2]), rng_states=rng.cpu().numpy().view(np.uint32))
+    out = dict(num_rays=num_rays, num_iter=num_iter, gpu_seconds=kern_s, bounces=int(stats[STAT.bounces]),
+               eyebox_hits=int(stats[STAT.eyebox_hits]), rng_states=rng.cpu().numpy().view(np.uint32))
     if rank != 0:
         scene.close()
         return out

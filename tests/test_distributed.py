@@ -16,6 +16,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from gpu_ray_tracing_for_waveguide_based_ar_display_amd._lib import STAT
 from gpu_ray_tracing_for_waveguide_based_ar_display_amd.distributed import (EB_SLAB, SPILL, EyeboxGather, GidMap,
                                                                             block_range, make_shard, rank_blocks,
                                                                             replica_shard, shard_rays_host, slab_ids,
@@ -42,7 +43,7 @@ def _inputs():
 
 def _oracle_tracer(geom, luts, stats=None):
     """trace_fn of distributed.run_steps on the CPU oracle (one call per run of consecutive blocks
-    of the shard's GidMap); adds its bounces to stats[0] like the HIP tracer's device counter."""
+    of the shard's GidMap); adds its bounces to stats[STAT.bounces] like the HIP tracer's device counter."""
     from oracle import OracleScene
     sc = OracleScene.from_geometry(geom, luts)
 
@@ -56,7 +57,7 @@ def _oracle_tracer(geom, luts, stats=None):
                 b, _ = sc.trace(part, r, eb, gid_offset=g, threads=1)
                 rng[lo:hi] = r
                 if stats is not None:
-                    stats[0] += b
+                    stats[STAT.bounces] += b
     return fn
 
 

@@ -20,7 +20,7 @@ sys.path.insert(0, os.environ["REPO"])
 import torch
 from gpu_ray_tracing_for_waveguide_based_ar_display_amd.configs import CONFIGS, build_inputs
 from gpu_ray_tracing_for_waveguide_based_ar_display_amd.distributed import hip_shard_builder, make_shard
-from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import Scene, trace_fullcolor, reserve, new_stats
+from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import STAT, Scene, trace_fullcolor, reserve, new_stats
 import dataclasses
 w = CONFIGS[os.environ["AB_CONFIG"]]
 if os.environ.get("AB_PROFILE"):
@@ -66,13 +66,13 @@ st.zero_()
 for k in range(nl):
     ev[k][0].record(); trace_fullcolor(sc, rays, rng, eb, stats=st, chunk_order=order, **lk); ev[k][1].record()
 torch.cuda.synchronize()
-b1 = int(st[0]) / nl
+b1 = int(st[STAT.bounces]) / nl
 st.zero_()
 ev[nl][0].record(); trace_fullcolor(sc, rays, rng, eb, stats=st, num_iter=nf); ev[nl][1].record()
 torch.cuda.synchronize()
 single = [ev[k][0].elapsed_time(ev[k][1]) for k in range(nl)]
 print(json.dumps({"single_ms": float(np.median(single)), "fused_ms_per_step": ev[nl][0].elapsed_time(ev[nl][1]) / nf,
-                  "bounces_per_launch": b1, "fused_bounces": int(st[0])}))
+                  "bounces_per_launch": b1, "fused_bounces": int(st[STAT.bounces])}))
 '''
 
 

@@ -27,7 +27,7 @@ def main():
 
     from gpu_ray_tracing_for_waveguide_based_ar_display_amd.configs import CONFIGS, build_inputs
     from gpu_ray_tracing_for_waveguide_based_ar_display_amd.distributed import hip_shard_builder, make_shard
-    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import Scene, new_stats, trace_fullcolor
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import STAT, Scene, new_stats, trace_fullcolor
     w = CONFIGS[a.config]
     nx, ny, lam, R = w.nx, w.ny, list(w.lambdas), w.R
     dev = torch.device("cuda", 0)
@@ -51,7 +51,7 @@ def main():
                 e.record()
             torch.cuda.synchronize()
             ms = float(np.median([s.elapsed_time(e) for s, e in ev])) / a.num_iter
-            b = int(st[0]) / a.launches / a.num_iter
+            b = int(st[STAT.bounces]) / a.launches / a.num_iter
             print(json.dumps({"config": a.config, "workgroups": wg, "chunk_rays": ch, "num_iter": a.num_iter,
                               "ms_per_trace": round(ms, 4),
                               "bounces_per_trace": b, "ray_bounces_per_s": round(b / ms * 1e3, 1)}), flush=True)

@@ -7,7 +7,7 @@ then, on the GPU:
     python tools/with_lib.py exp_libs/seg/libwgrt.so tools/segments.py --out profiles/r06_pass_segments.json
 
 For each workload (C3 whole batch, rank 0's interleaved eighth of C3, C2) it runs the timeline
-instantiation of the trace kernel with the segment stamps (wgrt_device.h SegAcc): per wave, the shader
+instantiation of the trace kernel with the segment stamps (wgrt_seg.h SegAcc): per wave, the shader
 cycles of every launch-tail pass split into
     advance | retire + ballots | line-0 round trip | estimate + decision | taken loads round trip |
     field update | rest of the pass (in-coupler test, outcome, out-coupling queue)
