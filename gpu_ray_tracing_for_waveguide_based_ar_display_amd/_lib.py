@@ -26,7 +26,8 @@ EXPORTED = ("wgrt_scene_create", "wgrt_scene_create_ex", "wgrt_scene_destroy", "
             "wgrt_locator_classify_host", "wgrt_selftest_math", "wgrt_status_string", "wgrt_last_error",
             "wgrt_abi_version", "wgrt_eyebox_payload_floats", "wgrt_eyebox_pack", "wgrt_eyebox_assemble",
             "wgrt_eyebox_window_sums")
-EXPORTED_DEBUG = ("wgrt_debug_shadow", "wgrt_debug_scene_copy")
+EXPORTED_DEBUG = ("wgrt_debug_shadow", "wgrt_debug_scene_copy", "wgrt_debug_set_auto_order",
+                  "wgrt_debug_get_auto_order", "wgrt_debug_get_tile_tail", "wgrt_debug_order_host")
 
 
 class WgrtError(RuntimeError):
@@ -201,6 +202,15 @@ def load():
                                     _vp, _vp, _vp]
     L.wgrt_debug_scene_copy.restype = st
     L.wgrt_debug_scene_copy.argtypes = [_vp, ctypes.c_int, _vp, ctypes.c_int64]
+    if hasattr(L, "wgrt_debug_set_auto_order"):   # the automatic issue order's hooks (absent from earlier builds)
+        L.wgrt_debug_set_auto_order.restype = st
+        L.wgrt_debug_set_auto_order.argtypes = [ctypes.c_int]
+        L.wgrt_debug_get_auto_order.restype = st
+        L.wgrt_debug_get_auto_order.argtypes = [_vp, _vp, _vp, ctypes.c_int64]
+        L.wgrt_debug_get_tile_tail.restype = st
+        L.wgrt_debug_get_tile_tail.argtypes = [_vp, _vp, ctypes.c_int64]
+        L.wgrt_debug_order_host.restype = st
+        L.wgrt_debug_order_host.argtypes = [_vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp]
     L.wgrt_status_string.restype = ctypes.c_char_p
     L.wgrt_status_string.argtypes = [ctypes.c_int]
     L.wgrt_last_error.restype = ctypes.c_char_p

@@ -30,8 +30,15 @@ struct wgrt_scene {
     int64_t edge_cells = 0;        // locator cells with an EDGE class
     int jones_grid[2][2][2] = {};   // resident 256-thread workgroups: [64-bit cells][fused][single wavelength]
     int jones_tl_grid[2] = {};      // ... of the debug timeline instantiations (32-bit cells): [fused]
+    int jones_learn_grid[2] = {};   // ... of the learning instantiations (full colour, single trace): [64-bit cells]
     int64_t nonunitary_blocks = 0;  // Jones blocks whose branch matrices are not scaled-unitary (their launches
                                     // run the AMP instantiations: wgrt_jones_lane.h, the amplification step)
+    // The automatic issue order's statistic (wgrt_order.h): per (wavelength, FoV) tile, the traces of the
+    // learning launches that took more than kLongBounces bounces.  learned_rays / learn_gen (the rays those
+    // launches traced, and how many there were) change under scratch_mu.
+    uint32_t *d_tile_tail = nullptr;
+    int64_t learned_rays = 0;
+    uint32_t learn_gen = 0;
     // Jones-vector launches: per-stream launch scratch (launches on one stream are ordered, so
     // they may share it; launches on different streams never do)
     struct Scratch {
@@ -51,6 +58,13 @@ struct wgrt_scene {
         uint64_t *rng64 = nullptr;           // fused launches: per-ray {state, tag} granules
         uint32_t iter_epoch = 0;             // < 2^23 (iter_tag)
         int64_t cap64 = 0;
+        // the automatic issue order: the permutation, the sort's other buffer and the chunks' class keys
+        // (order_cap chunks each), and what the permutation was built from
+        int32_t *order = nullptr;
+        int64_t order_cap = 0;
+        int64_t order_rays = -1;             // -1: none built
+        const float *order_m = nullptr, *order_n = nullptr, *order_l = nullptr;
+        uint32_t order_gen = 0;
     };
     std::mutex scratch_mu;
     std::map<void *, Scratch> scratch;
@@ -60,7 +74,7 @@ namespace wgrt {
 
 // What scene creation and destruction need from the trace unit (wgrt_trace.hip), the one place that
 // instantiates the trace kernels and knows the launch scratch:
-// the resident grid of every trace kernel instantiation (jones_grid / jones_tl_grid) from the occupancy queries ...
+// the resident grid of every trace kernel instantiation (jones_grid / jones_tl_grid / jones_learn_grid) from the occupancy queries ...
 wgrt_status query_trace_grids(wgrt_scene *s);
 // ... and the release of one stream's launch scratch (the scene's device is current)
 void free_scratch(wgrt_scene::Scratch &sc);

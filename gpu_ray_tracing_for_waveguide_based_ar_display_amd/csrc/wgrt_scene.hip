@@ -308,6 +308,12 @@ wgrt_status wgrt_scene_create_ex(const wgrt_scene_desc *desc, int device, const 
         if (e != hipSuccess) return bail(fail(WGRT_ERR_HIP, std::string("nonunitary_kernel: ") + hipGetErrorString(e)));
         s->nonunitary_blocks = (int64_t)nu;
     }
+    {   // the automatic issue order's tile table starts empty (wgrt_scene.h)
+        const size_t nt = (size_t)s->nl * s->nx * s->ny;
+        if ((st = alloc_n(nt, &s->d_tile_tail)) != WGRT_OK) return bail(st);
+        const hipError_t e = hipMemset(s->d_tile_tail, 0, std::max<size_t>(nt, 1) * sizeof(uint32_t));
+        if (e != hipSuccess) return bail(fail(WGRT_ERR_HIP, std::string("hipMemset(tile_tail): ") + hipGetErrorString(e)));
+    }
     if ((st = query_trace_grids(s)) != WGRT_OK) return bail(st);
     s->loc_host = host.loc;
     s->loc_host.cells.clear();
@@ -324,7 +330,8 @@ wgrt_status wgrt_scene_destroy(wgrt_scene *s) {
     if (!s) return WGRT_OK;
     DeviceScope dev_scope(s->device);
     for (void *p : {(void *)s->d_tiles, (void *)s->d_jtiles, (void *)s->d_cells, (void *)s->d_cells32, (void *)s->d_verts,
-                    (void *)s->d_poly_off, (void *)s->d_row_off, (void *)s->d_row_edges, (void *)s->d_bands})
+                    (void *)s->d_poly_off, (void *)s->d_row_off, (void *)s->d_row_edges, (void *)s->d_bands,
+                    (void *)s->d_tile_tail})
         (void)hipFree(p);
     for (auto &kv : s->scratch) free_scratch(kv.second);
     delete s;

@@ -22,16 +22,19 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <initializer_list>
 #include <mutex>
 #include <string>
+#include <vector>
 
 #include "../../include/wgrt.h"
 #include "../../include/wgrt_debug.h"
 #include "wgrt_common.h"
 #include "wgrt_exact_lane.h"
 #include "wgrt_jones_lane.h"
+#include "wgrt_order.h"
 #include "wgrt_scene.h"
 
 using namespace wgrt;
@@ -292,7 +295,16 @@ __device__ __forceinline__ void finish_single(const KArgs &K, Counters c) {
 // to n_iter launches: each ray's traces run in order from the same states; eyebox adds commute.
 // TL: the debug wave timeline (wgrt_debug_opts.timeline); the product instantiations have TL = false
 // and contain none of its code.
-template <bool FUSED, bool SINGLE, bool TL, bool AMP, class Loc>
+// LEARN: the learning launches of the automatic issue order (single traces; wgrt_order.h): a trace that ends
+// after more than kLongBounces bounces counts into its tile's slot of the scene's tile_tail, the learning
+// kernel's fifth parameter, read from the kernarg segment where it is used (kLearnTailOff).  A ray the launch
+// abandons to the replay is not counted (none in practice).  Off in the product instantiations, which
+// contain none of it (a sixth parameter of this function moved an instruction of their prologue).
+template <class Loc>
+constexpr size_t kLearnTailOff = sizeof(TraceArgs) + sizeof(Loc) + sizeof(unsigned long long *) + 8;
+static_assert(sizeof(TraceArgs) % 8 == 0 && sizeof(Locator) % 8 == 0 && sizeof(LocatorT<uint32_t>) % 8 == 0,
+              "kLearnTailOff: the kernel parameters lie back to back, the int padded to 8 bytes");
+template <bool FUSED, bool SINGLE, bool TL, bool AMP, bool LEARN, class Loc>
 __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, const Loc &loc, unsigned long long *heads,
                                           int chunk) {
     // Single launches (!FUSED) do their epilogue in this kernel (above), and retire a finished trace at one
@@ -431,6 +443,8 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             uint32_t *const pr = KA(per_ray);
             if (!FUSED && pr) pr[L.i] = L.bounces;
         }
+        if (LEARN && L.bounces > kLongBounces)   // result unused: no return, no wait
+            atomicAdd(K.template get<uint32_t *>(kLearnTailOff<Loc>) + L.tix, 1u);
         active = false;
     };
 
@@ -762,7 +776,7 @@ __global__ __launch_bounds__(256) void replay_kernel(TraceArgs A) {
 template <class CellT, bool FUSED, bool SINGLE, bool AMP>
 __global__ WGRT_JONES_BOUNDS void trace_jones_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
                                                      int chunk) {
-    jones_body<FUSED, SINGLE, false, AMP>(
+    jones_body<FUSED, SINGLE, false, AMP, false>(
         A, kernel_kargs<decltype(trace_jones_kernel<CellT, FUSED, SINGLE, AMP>)>(), loc, counter, chunk);
 }
 
@@ -771,8 +785,76 @@ __global__ WGRT_JONES_BOUNDS void trace_jones_kernel(TraceArgs A, LocatorT<CellT
 template <class CellT, bool FUSED, bool SINGLE>
 __global__ WGRT_JONES_BOUNDS void trace_jones_tl_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
                                                         int chunk) {
-    jones_body<FUSED, SINGLE, true, false>(A, kernel_kargs<decltype(trace_jones_tl_kernel<CellT, FUSED, SINGLE>)>(),
-                                           loc, counter, chunk);
+    jones_body<FUSED, SINGLE, true, false, false>(A, kernel_kargs<decltype(trace_jones_tl_kernel<CellT, FUSED, SINGLE>)>(),
+                                                  loc, counter, chunk);
+}
+
+// The same loop counting each tile's long traces into the scene's tile_tail (the automatic issue order's
+// learning launches: full colour, single trace, scaled-unitary LUTs): again a separate instantiation.
+template <class CellT>
+__global__ WGRT_JONES_BOUNDS void trace_jones_learn_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
+                                                           int chunk, uint32_t *tail) {
+    jones_body<false, false, false, false, true>(A, kernel_kargs<decltype(trace_jones_learn_kernel<CellT>)>(), loc,
+                                                 counter, chunk);
+}
+
+// The automatic issue order of a batch (wgrt_order.h), built by one workgroup: the class key of every
+// 64-ray chunk from its first ray's tile (m, n, lmd_num columns; an index out of range: the lowest class)
+// and the scene's tile_tail, then the stable two-pass sort of the chunks by key.  keys, tmp and order hold
+// n_chunks entries each; whatever tile_tail and the columns hold, order comes out a permutation, since both
+// passes sort the keys stored by the first step.
+__global__ __launch_bounds__(kOrderThreads) void order_kernel(const float *m, const float *n, const float *l,
+                                                              int64_t n_rays, int nx, int ny, int nl,
+                                                              const uint32_t *tail, uint32_t *keys, int32_t *tmp,
+                                                              int32_t *order) {
+    __shared__ uint32_t hist[kOrderDigits * kOrderThreads];
+    __shared__ uint32_t part[kOrderThreads];
+    const int t = threadIdx.x;
+    const int64_t n_chunks = (n_rays + kChunk - 1) / kChunk;
+    // the table's largest count
+    uint32_t mx = 0;
+    for (int64_t k = t; k < (int64_t)nl * nx * ny; k += kOrderThreads) mx = tail[k] > mx ? tail[k] : mx;
+    part[t] = mx;
+    __syncthreads();
+    for (int w = kOrderThreads / 2; w > 0; w >>= 1) {
+        if (t < w) part[t] = part[t + w] > part[t] ? part[t + w] : part[t];
+        __syncthreads();
+    }
+    mx = part[0];
+    __syncthreads();
+    for (int64_t c = t; c < n_chunks; c += kOrderThreads) {
+        const int64_t i = c * kChunk;
+        const int fm = (int)m[i], fn = (int)n[i], fl = l ? (int)l[i] : 0;
+        const bool ok = fm >= 0 && fm < nx && fn >= 0 && fn < ny && fl >= 0 && fl < nl;
+        keys[c] = order_key(ok ? tail[(fl * nx + fm) * ny + fn] : 0u, mx);
+    }
+    __syncthreads();
+    for (int pass = 0; pass < kOrderPasses; ++pass) {
+        const int32_t *const src = tmp;                       // pass 1 reads what pass 0 placed
+        int32_t *const dst = pass == kOrderPasses - 1 ? order : tmp;
+        order_count(t, pass, n_chunks, keys, src, hist);
+        __syncthreads();
+        // exclusive prefix sum of hist in index order: thread t owns entries [t * kOrderDigits, ...)
+        uint32_t sum = 0;
+        for (int k = 0; k < kOrderDigits; ++k) sum += hist[t * kOrderDigits + k];
+        part[t] = sum;
+        __syncthreads();
+        for (int w = 1; w < kOrderThreads; w <<= 1) {
+            const uint32_t add = t >= w ? part[t - w] : 0u;
+            __syncthreads();
+            part[t] += add;
+            __syncthreads();
+        }
+        uint32_t run = part[t] - sum;
+        for (int k = 0; k < kOrderDigits; ++k) {
+            const uint32_t h = hist[t * kOrderDigits + k];
+            hist[t * kOrderDigits + k] = run;
+            run += h;
+        }
+        __syncthreads();
+        order_place(t, pass, n_chunks, keys, src, hist, dst);
+        __syncthreads();
+    }
 }
 
 // Every trace kernel instantiation, stated once: the Jones kernels by [64-bit cells][fused][single
@@ -795,6 +877,8 @@ const void *const kJonesKernels[2][2][2][2] = {
        (const void *)trace_jones_kernel<uint64_t, true, false, true>},
       {(const void *)trace_jones_kernel<uint64_t, true, true, false>,
        (const void *)trace_jones_kernel<uint64_t, true, true, true>}}}};
+const void *const kLearnKernels[2] = {(const void *)trace_jones_learn_kernel<uint32_t>,
+                                      (const void *)trace_jones_learn_kernel<uint64_t>};
 const void *const kTimelineKernels[2] = {(const void *)trace_jones_tl_kernel<uint32_t, false, false>,
                                          (const void *)trace_jones_tl_kernel<uint32_t, true, false>};
 
@@ -822,12 +906,13 @@ wgrt_status query_trace_grids(wgrt_scene *s) {
                 s->jones_grid[c][f][g] = std::min(plain, amp);
             }
     for (int f = 0; f < 2; ++f) HIP_TRY(grid_of(kTimelineKernels[f], s->jones_tl_grid[f]));
+    for (int c = 0; c < 2; ++c) HIP_TRY(grid_of(kLearnKernels[c], s->jones_learn_grid[c]));
     return WGRT_OK;
 }
 
 void free_scratch(wgrt_scene::Scratch &sc) {
     for (void *p : {(void *)sc.ctr, (void *)sc.list, (void *)sc.q_xy, (void *)sc.q_i, (void *)sc.full, (void *)sc.rng64,
-                    (void *)sc.part})
+                    (void *)sc.part, (void *)sc.order})
         (void)hipFree(p);
 }
 
@@ -903,6 +988,13 @@ wgrt_status ensure_scratch(wgrt_scene *ms, void *stream, int64_t n_rays, int num
         return h;
     });
     if (e != WGRT_OK) return e;
+    // the automatic issue order's three arrays (order, the sort's other buffer, class keys); new ones hold no order
+    const int64_t chunks = (n_rays + kChunk - 1) / kChunk;
+    e = grow(sc->order_cap, chunks, {(void **)&sc->order}, [&] {
+        sc->order_rays = -1;
+        return hipMalloc((void **)&sc->order, (size_t)chunks * 3 * sizeof(int32_t));
+    });
+    if (e != WGRT_OK) return e;
     if (num_iter > 1) {   // the granules of a fused launch; new ones start a new epoch count
         e = grow(sc->cap64, n_rays, {(void **)&sc->rng64}, [&] {
             sc->iter_epoch = 0;
@@ -943,7 +1035,62 @@ struct LaunchCfg {
     const wgrt_debug_opts *dbg = nullptr;
     double grid_k = 0.0;   // wgrt_launch_opts.grid_sqrt_k (0: kGridSqrtK; < 0: the resident grid)
     bool timeline = false; // set by validate_launch: the debug wave timeline is asked for
+    bool learn = false;    // set by plan_auto_order: this launch runs the learning instantiation ...
+    bool auto_order = false;   // ... and / or is issued in the automatic order, built from the tile table as
+    uint32_t order_gen = 0;    // it stood after this many learning launches
 };
+
+// wgrt_debug_set_auto_order: the automatic issue order (and its learning launches) on / off, process-wide.
+std::atomic<int> g_auto_order{1};
+
+// The automatic issue order (wgrt_order.h) applies to full-colour single traces on scaled-unitary LUTs whose
+// caller gave no chunk_order; single-wavelength scenes and scenes that need the amplification step keep the
+// natural order (no learning instantiation is built for them).  While the scene has seen fewer than
+// kLearnRaysPerTile rays per tile, the launch learns (not a timeline launch: that kernel is another
+// instantiation); once a learning launch has run, launches of whole 64-ray chunks are issued in the order
+// built from the table.
+void plan_auto_order(wgrt_scene *ms, int64_t n_rays, int item, LaunchCfg &c) {
+    if (!g_auto_order.load(std::memory_order_relaxed) || c.variant == 1 || c.num_iter > 1 || c.single || c.chunk_order ||
+        ms->nonunitary_blocks)
+        return;
+    std::lock_guard<std::mutex> lk(ms->scratch_mu);
+    const bool learning = ms->learned_rays < kLearnRaysPerTile * (int64_t)ms->nl * ms->nx * ms->ny;
+    // While the scene still learns (a batch of few rays per tile: a shard), the order is rebuilt after 1, 2,
+    // 4, ... learning launches only, not after each: order_kernel is one workgroup (0.24 ms for C3's 21,168
+    // chunks), about a launch's time at every size.
+    c.order_gen = ms->learn_gen;
+    if (learning)
+        while (c.order_gen & (c.order_gen - 1)) c.order_gen &= c.order_gen - 1;
+    c.auto_order = ms->learn_gen > 0 && item == kChunk;
+    if (!c.timeline && learning) {
+        c.learn = true;
+        ms->learned_rays += n_rays;
+        ++ms->learn_gen;
+    }
+}
+
+// The stream's automatic order for this launch: the cached one if it was built for the same batch layout
+// (ray count, the three index columns) and the same state of the tile table, else built now, on the
+// launch's stream, ahead of the trace kernel.
+wgrt_status auto_order(wgrt_scene *ms, wgrt_scene::Scratch *sc, const TraceArgs &A, const LaunchCfg &c, hipStream_t st,
+                       const int32_t **out) {
+    std::lock_guard<std::mutex> lk(ms->scratch_mu);
+    if (sc->order_rays != A.n_rays || sc->order_m != A.m || sc->order_n != A.n || sc->order_l != A.l ||
+        sc->order_gen != c.order_gen) {
+        const int64_t chunks = (A.n_rays + kChunk - 1) / kChunk;
+        sc->order_rays = -1;
+        hipLaunchKernelGGL(order_kernel, dim3(1), dim3(kOrderThreads), 0, st, A.m, A.n, A.l, A.n_rays, A.nx, A.ny, A.nl,
+                           (const uint32_t *)ms->d_tile_tail, (uint32_t *)(sc->order + 2 * chunks), sc->order + chunks,
+                           sc->order);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(WGRT_ERR_HIP, std::string("order_kernel: ") + hipGetErrorString(e));
+        sc->order_rays = A.n_rays;
+        sc->order_m = A.m, sc->order_n = A.n, sc->order_l = A.l;
+        sc->order_gen = c.order_gen;
+    }
+    *out = sc->order;
+    return WGRT_OK;
+}
 
 // Single traces: ceil(kGridSqrtK * sqrt(work items)) workgroups (wgrt_launch_opts.grid_sqrt_k).
 constexpr double kGridSqrtK = 6.5;
@@ -1045,6 +1192,7 @@ TraceArgs fill_args(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, 
 int64_t launch_grid(const wgrt_scene *s, int64_t n_rays, int64_t item, const LaunchCfg &c) {
     int64_t grid = c.workgroups > 0 ? c.workgroups
                    : c.timeline     ? s->jones_tl_grid[c.num_iter > 1]
+                   : c.learn        ? s->jones_learn_grid[c.variant == 9]
                                     : s->jones_grid[c.variant == 9][c.num_iter > 1][c.single];
     // a workgroup's 4 waves need 4 work items to all have work (debug chunk_rays: smaller items)
     const int64_t useful = (n_rays + 4 * item - 1) / (4 * item);
@@ -1103,6 +1251,13 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
     A.full_list = sc->full;
     A.part = sc->part;
     A.n_trace_waves = (int)grid;   // one partial slot per trace workgroup
+    if (c.auto_order) {
+        const wgrt_status e = auto_order(ms, sc, A, c, st, &A.order);
+        if (e != WGRT_OK) {
+            mark_dirty(ms, sc);
+            return e;
+        }
+    }
     // chunk_order is given in 64-ray chunks; a staged chunk is one ray per lane
     int jchunk = A.order ? kChunk : item;
     // the timeline kernels and variant 7 read 32-bit cell words; the amplification step only for scenes that
@@ -1110,8 +1265,10 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
     LocatorT<uint32_t> l32{};
     if (c.variant != 9) l32 = make_locator32(s);
     const void *const kernel = c.timeline ? kTimelineKernels[num_iter > 1]
+                               : c.learn  ? kLearnKernels[c.variant == 9]
                                           : kJonesKernels[c.variant == 9][num_iter > 1][c.single][s->nonunitary_blocks != 0];
-    void *args[] = {&A, c.variant == 9 ? (void *)&A.loc : (void *)&l32, &ctr, &jchunk};
+    uint32_t *tail = ms->d_tile_tail;   // the learning kernels' last parameter (the others take four)
+    void *args[] = {&A, c.variant == 9 ? (void *)&A.loc : (void *)&l32, &ctr, &jchunk, &tail};
     (void)hipLaunchKernel(kernel, dim3((unsigned)grid), dim3(256), args, 0, st);
     hipError_t e = hipGetLastError();   // (and clears it, as after every launch here)
     if (e == hipSuccess && dbg && dbg->fail_after_trace) {
@@ -1155,6 +1312,7 @@ wgrt_status trace_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_r
     TraceArgs A = fill_args(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, c);
     // a work item: a 64-ray chunk, or the debug option's smaller one
     const int item = (c.dbg && c.dbg->chunk_rays > 0) ? std::min(c.dbg->chunk_rays, 64) : kChunk;
+    plan_auto_order(const_cast<wgrt_scene *>(s), n_rays, item, c);
     return dispatch(s, A, launch_grid(s, n_rays, item, c), item, stream, c);
 }
 
@@ -1228,6 +1386,64 @@ wgrt_status wgrt_trace_single(const wgrt_scene *s, const wgrt_rays *rays, int64_
                               uint32_t *per_ray_bounces, void *stream) {
     return trace_launch(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream,
                         cfg_of(0, 0, true));
+}
+
+wgrt_status wgrt_debug_set_auto_order(int on) {
+    g_auto_order.store(on != 0, std::memory_order_relaxed);
+    return WGRT_OK;
+}
+
+wgrt_status wgrt_debug_get_auto_order(const wgrt_scene *s, void *stream, int32_t *out, int64_t n) {
+    if (!s || (n > 0 && !out)) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL scene / out");
+    wgrt_scene *ms = const_cast<wgrt_scene *>(s);
+    DEVICE_SCOPE(dev_scope, s->device);
+    std::lock_guard<std::mutex> lk(ms->scratch_mu);
+    const auto it = ms->scratch.find(stream);
+    if (it == ms->scratch.end() || it->second.order_rays < 0)
+        return fail(WGRT_ERR_INVALID_ARGUMENT, "no automatic order has been built on this stream");
+    if (n != (it->second.order_rays + kChunk - 1) / kChunk)
+        return fail(WGRT_ERR_INVALID_ARGUMENT, "n must be the order's " +
+                                                   std::to_string((it->second.order_rays + kChunk - 1) / kChunk) + " chunks");
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    HIP_TRY(hipMemcpy(out, it->second.order, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return WGRT_OK;
+}
+
+wgrt_status wgrt_debug_get_tile_tail(const wgrt_scene *s, uint32_t *out, int64_t n) {
+    if (!s || !out) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL scene / out");
+    if (n != (int64_t)s->nl * s->nx * s->ny) return fail(WGRT_ERR_INVALID_ARGUMENT, "n must be num_lmd * nx * ny");
+    DEVICE_SCOPE(dev_scope, s->device);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, s->d_tile_tail, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return WGRT_OK;
+}
+
+wgrt_status wgrt_debug_order_host(const uint32_t *tile_tail, int64_t n_tiles, const int32_t *chunk_tile, int64_t n_chunks,
+                                  int32_t *order) {
+    if (n_tiles < 0 || n_chunks < 0 || n_chunks > 0x7fffffffll || (n_tiles > 0 && !tile_tail) ||
+        (n_chunks > 0 && (!chunk_tile || !order)))
+        return fail(WGRT_ERR_INVALID_ARGUMENT, "bad tile table / chunk list");
+    uint32_t mx = 0;
+    for (int64_t k = 0; k < n_tiles; ++k) mx = std::max(mx, tile_tail[k]);
+    std::vector<uint32_t> keys((size_t)n_chunks), hist((size_t)kOrderDigits * kOrderThreads);
+    std::vector<int32_t> tmp((size_t)n_chunks);
+    for (int64_t c = 0; c < n_chunks; ++c) {
+        const bool ok = chunk_tile[c] >= 0 && chunk_tile[c] < n_tiles;
+        keys[c] = order_key(ok ? tile_tail[chunk_tile[c]] : 0u, mx);
+    }
+    // the device kernel's passes, its threads one after the other
+    for (int pass = 0; pass < kOrderPasses; ++pass) {
+        int32_t *const dst = pass == kOrderPasses - 1 ? order : tmp.data();
+        for (int t = 0; t < kOrderThreads; ++t) order_count(t, pass, n_chunks, keys.data(), tmp.data(), hist.data());
+        uint32_t run = 0;
+        for (uint32_t &h : hist) {
+            const uint32_t v = h;
+            h = run;
+            run += v;
+        }
+        for (int t = 0; t < kOrderThreads; ++t) order_place(t, pass, n_chunks, keys.data(), tmp.data(), hist.data(), dst);
+    }
+    return WGRT_OK;
 }
 
 }  // extern "C"

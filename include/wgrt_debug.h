@@ -81,6 +81,25 @@ wgrt_status wgrt_debug_shadow(const wgrt_scene *scene, const wgrt_rays *rays, in
  * Jones-vector tiles (doubles, tiles * tile / jtile doubles; wgrt_scene_info). */
 wgrt_status wgrt_debug_scene_copy(const wgrt_scene *scene, int which, void *dst, int64_t bytes);
 
+/* The automatic issue order of single full-colour traces (csrc/wgrt_order.h): a scene counts, per
+ * (wavelength, FoV) tile, the traces of its first launches that took more than 24 bounces (until it has
+ * seen 1024 rays per tile), and later launches without a chunk_order issue their 64-ray chunks in
+ * descending classes of that count.  A scheduling hint: results do not depend on it.  This switch is the
+ * one piece of process-wide state here (for A/B timing and tests): 0 turns learning and ordering off, so
+ * every launch runs as if the scene had no table; default 1. */
+wgrt_status wgrt_debug_set_auto_order(int on);
+/* Copies the order the stream's last automatically ordered launch used to host memory (n must be its
+ * ceil(n_rays / 64) chunks); WGRT_ERR_INVALID_ARGUMENT when the stream has built none.  Waits for the stream. */
+wgrt_status wgrt_debug_get_auto_order(const wgrt_scene *scene, void *stream, int32_t *out, int64_t n);
+/* Copies the scene's tile table (uint32 counts, n = num_lmd * nx * ny, index (lambda * nx + m) * ny + n)
+ * to host memory.  Waits for the device. */
+wgrt_status wgrt_debug_get_tile_tail(const wgrt_scene *scene, uint32_t *out, int64_t n);
+/* The order kernel's arithmetic on the host (no device): the issue order of n_chunks chunks, chunk c
+ * belonging to tile chunk_tile[c] (out of [0, n_tiles): no tile, the lowest class), from the table
+ * tile_tail[n_tiles]. */
+wgrt_status wgrt_debug_order_host(const uint32_t *tile_tail, int64_t n_tiles, const int32_t *chunk_tile,
+                                  int64_t n_chunks, int32_t *order);
+
 #ifdef __cplusplus
 }
 #endif

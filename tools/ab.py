@@ -53,6 +53,12 @@ if os.environ.get("AB_ORDER"):   # lifetime-ordered chunk issue from one earlier
     key = ((rays["lmd_num"].to(torch.int64) * nx + rays["m"].to(torch.int64)) * ny + rays["n"].to(torch.int64))
     if os.environ["AB_ORDER"] == "seg":
         order = schedule_by_lifetime(pb, key, nx * ny * 3)
+    elif os.environ["AB_ORDER"].startswith("tail"):   # tail<N>[c<K>]: tiles by their rays with > N bounces, K classes
+        thr, _, ncls = os.environ["AB_ORDER"][4:].partition("c")
+        tail = torch.zeros(nx * ny * 3, device=dev).index_add_(0, key, (pb > int(thr)).float())
+        if ncls:
+            tail = torch.floor(tail * int(ncls) / (tail.max() + 1))
+        order = torch.argsort(-tail[key[::CHUNK]], stable=True).to(torch.int32)
     else:
         tot = torch.zeros(nx * ny * 3, device=dev).index_add_(0, key, pb.float())
         cnt = torch.zeros(nx * ny * 3, device=dev).index_add_(0, key, torch.ones_like(pb, dtype=torch.float32))
@@ -89,8 +95,9 @@ def main():
     res = {n: [] for n in a.names}
     for r in range(a.rounds):
         for n in a.names:
-            # NAME[:seg|:glob][@scene_opt=v,...][+launch_opt=v,...]: the build ("tree" = the in-tree
-            # library), optionally with lifetime-ordered chunk issue, scene options (e.g. coarse_shift=-1)
+            # NAME[:seg|:glob|:tail<N>[c<K>]][@scene_opt=v,...][+launch_opt=v,...]: the build ("tree" = the
+            # in-tree library), optionally with chunk issue ordered by the tiles' mean lifetime (seg, glob) or
+            # by their count of rays with more than N bounces (in K classes), scene options (e.g. coarse_shift=-1)
             # and launch options (e.g. grid_sqrt_k=4.5)
             n0, _, lopts = n.partition("+")
             n0, _, sopts = n0.partition("@")
