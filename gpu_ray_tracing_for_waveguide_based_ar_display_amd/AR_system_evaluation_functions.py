@@ -347,13 +347,104 @@ def evaluation(matrix_EB):
     return evaluation_from_perceive(eye_perceive(matrix_EB))
 
 
-def evaluation_device(eb, divisor):
+_ev_consts = None
+_ev_workspaces = {}   # (device, bytes) -> uint8 tensor, reused by every later call of that size
+
+
+def _evaluate_consts():
+    """``wl = inv(M_SENSOR) . white`` and ``LAB_D65`` as ``evaluation_from_perceive`` computes them (the
+    linearised pure-white image is (1, 1, 1) at every FoV), float64 ``[3]`` each."""
+    global _ev_consts
+    if _ev_consts is None:
+        white = linearize_srgb(np.zeros((1, 3)) + 1.0)
+        wl = (np.linalg.inv(M_SENSOR) @ white.T).T[0]
+        lab = xyz_to_lab(XYZ_D65_ASTM / XYZ_D65_ASTM[1] * 100.0)
+        _ev_consts = (np.ascontiguousarray(wl, dtype=np.float64), np.ascontiguousarray(lab, dtype=np.float64))
+    return _ev_consts
+
+
+def evaluation_from_window_sums(sums, shape, divisor, ms: int = 30, step_y: int = 8, step_x: int = 12,
+                                image="all"):
+    """``evaluation_from_perceive(perceive_from_window_sums(sums, shape, divisor, ...))`` by the library's
+    restatement of the same colour math (csrc/wgrt_colour.h): ``(delta_e, U_fov, U_EB, output_image)``.
+
+    ``sums``: the ``[3 * NY * NX, 1 + npy * npx]`` float64 table of ``eyebox_window_sums``.  A tensor on a HIP
+    device is evaluated there (``wgrt_eyebox_evaluate``, on torch's current stream; the workspace is cached
+    per device and size, so calls of one size on different streams of a device must not overlap) and one small copy brings the scalars back -- and the image only when asked; a numpy
+    array or a host tensor goes through the host replica of the same kernels (``wgrt_eyebox_evaluate_host``).
+    ``image``: ``"all"`` gives ``output_image`` float64 ``[NY, NX, 3, npy, npx]`` as ``evaluation`` does,
+    ``"center"`` only the position MAIN:199-203 exports (``i = 0``, ``j = npx - 1``) as ``[NY, NX, 3]``, ``None``
+    no image (``output_image`` is ``None``).  The colour math needs the three wavelengths: ``L != 3`` raises
+    ``ValueError``."""
+    import ctypes
+
+    from ._lib import check, load
+    if image not in ("all", "center", None):
+        raise ValueError(f"image must be 'all', 'center' or None, got {image!r}")
+    npy, npx = window_grid(ms, step_y, step_x)
+    nl, ny, nx = (int(v) for v in tuple(shape)[:3])
+    if nl != 3:
+        raise ValueError(f"the colour evaluation needs 3 wavelengths, got L = {nl}")
+    n_fov, n_pos = ny * nx, npy * npx
+    if tuple(sums.shape) != (nl * n_fov, 1 + n_pos):
+        raise ValueError(f"window sums of shape {tuple(sums.shape)} do not match a {(nl, ny, nx)} grid with "
+                         f"{npy} x {npx} eye positions")
+    L = load()
+    wl, lab = _evaluate_consts()
+    vp = ctypes.c_void_p
+    image_pos = -1 if image == "all" else npx - 1
+    image_shape = None if image is None else ((n_fov, 3, n_pos) if image == "all" else (n_fov, 3))
+    ws_bytes = int(L.wgrt_eyebox_evaluate_workspace_bytes(n_fov, n_pos))
+    if ws_bytes < 0:
+        raise ValueError(f"a table of {n_fov} FoVs x {n_pos} eye positions is beyond wgrt_eyebox_evaluate's limits")
+    if getattr(sums, "is_cuda", False):
+        import torch
+
+        from .engine import _stream_handle
+        if sums.dtype != torch.float64 or not sums.is_contiguous():
+            raise ValueError("a device table must be contiguous float64")
+        dev = sums.device
+        key = (str(dev), ws_bytes)
+        if key not in _ev_workspaces:
+            _ev_workspaces[key] = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = _ev_workspaces[key]
+        out = torch.empty(3 + n_pos, dtype=torch.float64, device=dev)
+        img = None if image is None else torch.empty(image_shape, dtype=torch.float32, device=dev)
+        check(L.wgrt_eyebox_evaluate(sums.data_ptr(), n_fov, n_pos, float(divisor), wl.ctypes.data_as(vp),
+                                     lab.ctypes.data_as(vp), out.data_ptr(),
+                                     img.data_ptr() if img is not None else None, image_pos, ws.data_ptr(),
+                                     _stream_handle(dev)), "wgrt_eyebox_evaluate")
+        out = out.cpu().numpy()
+        img = None if img is None else img.cpu().numpy()
+    else:
+        if hasattr(sums, "detach"):
+            sums = sums.detach().numpy()
+        sums = np.ascontiguousarray(sums, dtype=np.float64)
+        ws = np.empty(ws_bytes // 8, dtype=np.float64)
+        out = np.empty(3 + n_pos, dtype=np.float64)
+        img = None if image is None else np.empty(image_shape, dtype=np.float32)
+        check(L.wgrt_eyebox_evaluate_host(sums.ctypes.data_as(vp), n_fov, n_pos, float(divisor),
+                                          wl.ctypes.data_as(vp), lab.ctypes.data_as(vp), out.ctypes.data_as(vp),
+                                          img.ctypes.data_as(vp) if img is not None else None, image_pos,
+                                          ws.ctypes.data_as(vp)), "wgrt_eyebox_evaluate_host")
+    if img is not None:
+        img = img.astype(np.float64).reshape((ny, nx, 3, npy, npx) if image == "all" else (ny, nx, 3))
+    return float(out[0]), float(out[1]), float(out[2]), img
+
+
+def evaluation_device(eb, divisor, evaluate_on: str = "host"):
     """``evaluation(eb / divisor)`` without the grid leaving the device: ``eb`` is the raw count grid
     ``[L, NY, NX, 80, 120]`` (``divisor = R * num_iter``), reduced to its window sums where it lives
-    (``eyebox_window_sums``); only those ``[L * NY * NX, 57]`` numbers reach the host, where the colour math of
-    ``evaluation_from_perceive`` runs.  Differs from the host path only by the float32 rounding of its
-    per-bin division and summation (at most 902 * 2^-24 relative per eye position)."""
+    (``eyebox_window_sums``).  ``evaluate_on="host"``: only those ``[L * NY * NX, 57]`` numbers reach the host,
+    where the colour math of ``evaluation_from_perceive`` runs; ``"device"``: the table stays on the device
+    too and ``evaluation_from_window_sums`` evaluates it there, on the same stream.  Differs from the host path
+    only by the float32 rounding of its per-bin division and summation (at most 902 * 2^-24 relative per eye
+    position)."""
+    if evaluate_on not in ("host", "device"):
+        raise ValueError(f"evaluate_on must be 'host' or 'device', got {evaluate_on!r}")
     if len(eb.shape) != 5:
         raise ValueError(f"expected a [L, NY, NX, 80, 120] grid, got {tuple(eb.shape)}")
     sums = eyebox_window_sums(eb)
+    if evaluate_on == "device":
+        return evaluation_from_window_sums(sums, eb.shape, divisor)
     return evaluation_from_perceive(perceive_from_window_sums(sums, eb.shape, divisor))

@@ -18,14 +18,15 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libwgrt.so")   # the in-tree build, the only one the product binds
 OPS_PATH = os.path.join(PKG, "_wgrt_torch.so")   # the torch operator library (csrc/wgrt_torch.cpp)
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 # include/wgrt.h (the drop-in boundary) and include/wgrt_debug.h (test / profiling hooks)
 EXPORTED = ("wgrt_scene_create", "wgrt_scene_create_ex", "wgrt_scene_destroy", "wgrt_scene_get_info",
             "wgrt_trace_fullcolor", "wgrt_trace_fullcolor_ex", "wgrt_trace_single", "wgrt_trace_single_ex",
             "wgrt_trace_opts", "wgrt_scene_reserve", "wgrt_rays_init", "wgrt_scene_classify",
             "wgrt_locator_classify_host", "wgrt_selftest_math", "wgrt_status_string", "wgrt_last_error",
             "wgrt_abi_version", "wgrt_eyebox_payload_floats", "wgrt_eyebox_pack", "wgrt_eyebox_assemble",
-            "wgrt_eyebox_window_sums")
+            "wgrt_eyebox_window_sums", "wgrt_eyebox_evaluate_workspace_bytes", "wgrt_eyebox_evaluate",
+            "wgrt_eyebox_evaluate_host")
 EXPORTED_DEBUG = ("wgrt_debug_shadow", "wgrt_debug_scene_copy", "wgrt_debug_set_auto_order",
                   "wgrt_debug_get_auto_order", "wgrt_debug_get_tile_tail", "wgrt_debug_order_host")
 
@@ -196,6 +197,14 @@ def load():
         L.wgrt_eyebox_window_sums.restype = st
         L.wgrt_eyebox_window_sums.argtypes = [_vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, ctypes.c_int32,
                                               ctypes.c_int32, ctypes.c_int32, _vp, _vp]
+    if abi >= 9:   # the evaluation of the window-sum table (ABI 9)
+        L.wgrt_eyebox_evaluate_workspace_bytes.restype = ctypes.c_int64
+        L.wgrt_eyebox_evaluate_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
+        ev = [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp]
+        L.wgrt_eyebox_evaluate.restype = st
+        L.wgrt_eyebox_evaluate.argtypes = ev + [_vp]
+        L.wgrt_eyebox_evaluate_host.restype = st
+        L.wgrt_eyebox_evaluate_host.argtypes = ev
     # test / profiling hooks (include/wgrt_debug.h)
     L.wgrt_debug_shadow.restype = st
     L.wgrt_debug_shadow.argtypes = [_vp, ctypes.POINTER(Rays), ctypes.c_int64, ctypes.c_int64, ctypes.c_int, _vp,

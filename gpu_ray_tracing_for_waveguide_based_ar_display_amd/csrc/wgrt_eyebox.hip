@@ -1,6 +1,7 @@
 // wgrt_eyebox.hip -- the eyebox grid's own kernels (include/wgrt.h wgrt_eyebox_*): the per-slab
-// reduction (wgrt_eyebox_window_sums) and, at the end of the file, the slab collection of the
-// strong-scaling gather (wgrt_eyebox_pack / wgrt_eyebox_assemble).
+// reduction (wgrt_eyebox_window_sums), the slab collection of the strong-scaling gather
+// (wgrt_eyebox_pack / wgrt_eyebox_assemble) and, at the end of the file, the evaluation of the
+// reduction's table (wgrt_eyebox_evaluate: colour metrics and images).
 //
 // What the driver reads from an 80 x 120 slab of matrix_EB is its total (MAIN:186-192) and the sums
 // over a 30-px pupil mask at every 8th / 12th bin (eye_perceive, EVAL:66-109): 1 + 7 x 8 numbers out
@@ -24,6 +25,7 @@
 #include <string>
 
 #include "../../include/wgrt.h"
+#include "wgrt_colour.h"
 #include "wgrt_host.h"
 
 using namespace wgrt;
@@ -269,6 +271,201 @@ wgrt_status wgrt_eyebox_assemble(float *eb, int64_t n_slabs, const float *recv, 
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(eyebox_spill_kernel, dim3((unsigned)rows), dim3(128), 0, (hipStream_t)stream, eb, n_slabs, recv,
                        nb, plen, spill_dst);
+    HIP_TRY(hipGetLastError());
+    return WGRT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// Evaluation of the window-sum table (wgrt_eyebox_evaluate; EVAL:112-163 on the device).  The pixel math is
+// wgrt_colour.h's; here are the three passes around it:
+//   1. ev_pixels_kernel: a workgroup owns kEvTileFov FoVs x kEvPosChunk eye positions.  Lane k of the tile
+//      takes pixel (k / pw, k % pw), so consecutive lanes read consecutive doubles of a table row (the rows
+//      of a tile are contiguous but for column 0) in each of the three wavelength blocks.  The pixel's
+//      delta E, Y and float32 V go to LDS, and lane p < pw then adds its position's column over the tile's
+//      FoVs in FoV order: one partial record per (tile, position);
+//   2. ev_fold_kernel: one workgroup of kEvFoldGroups waves.  Wave g folds its contiguous share of the tiles
+//      in tile order, lane = position; wave 0 then folds the groups in group order, applies EVAL:150-163
+//      per position, and its lane 0 takes the totals over the positions in position order;
+//   3. ev_image_kernel / ev_image_one_kernel: the image side again from the table, normalised by the
+//      position's maximum V from pass 2 (recomputing three pow per pixel is cheaper than a 15 MB HSV buffer).
+// No atomics, every sum in an order fixed by (n_fov, n_pos): two runs give the same bits.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int kEvThreads = 256;
+constexpr int kEvSlots = kEvTileFov * kEvPosChunk;
+static_assert(kEvPosChunk == 64, "a position chunk is one wave of the column pass and of the fold");
+
+struct EvTile {
+    int64_t f0;
+    int p0, nf, pw;
+};
+
+__device__ __forceinline__ EvTile ev_tile(int64_t n_fov, int64_t n_pos) {
+    EvTile t;
+    t.f0 = (int64_t)blockIdx.x * kEvTileFov;
+    t.p0 = (int)blockIdx.y * kEvPosChunk;
+    t.nf = (int)(n_fov - t.f0 < kEvTileFov ? n_fov - t.f0 : kEvTileFov);
+    t.pw = (int)(n_pos - t.p0 < kEvPosChunk ? n_pos - t.p0 : kEvPosChunk);
+    return t;
+}
+
+// the pixel (FoV f, position p) of the table: its three window sums -> px
+__device__ __forceinline__ void ev_load_px(const double *sums, int64_t n_fov, int64_t n_pos, int64_t f, int64_t p,
+                                           double divisor, const EvConsts &k, double px[3]) {
+    const int64_t W = 1 + n_pos, block = n_fov * W, i = f * W + 1 + p;
+    ev_px(sums[i], sums[block + i], sums[2 * block + i], divisor, k, px);
+}
+
+__global__ __launch_bounds__(kEvThreads) void ev_pixels_kernel(const double *sums, int64_t n_fov, int64_t n_pos,
+                                                               double divisor, EvConsts k, EvWorkspace ws) {
+    __shared__ double s_de[kEvSlots], s_y[kEvSlots];
+    __shared__ float s_v[kEvSlots];
+    const EvTile t = ev_tile(n_fov, n_pos);
+    for (int q = threadIdx.x; q < t.nf * t.pw; q += kEvThreads) {
+        const int fl = q / t.pw, pl = q - fl * t.pw;
+        double px[3], Y, de;
+        float h, s, v;
+        ev_load_px(sums, n_fov, n_pos, t.f0 + fl, t.p0 + pl, divisor, k, px);
+        ev_colour(px, k, Y, de);
+        ev_hsv(px, h, s, v);
+        s_de[fl * kEvPosChunk + pl] = de;
+        s_y[fl * kEvPosChunk + pl] = Y;
+        s_v[fl * kEvPosChunk + pl] = v;
+    }
+    __syncthreads();
+    const int pl = threadIdx.x;
+    if (pl < t.pw) {
+        EvRecord r = ev_record_empty();
+        for (int fl = 0; fl < t.nf; ++fl)
+            ev_record_pixel(r, s_de[fl * kEvPosChunk + pl], s_y[fl * kEvPosChunk + pl], s_v[fl * kEvPosChunk + pl]);
+        const int64_t at = (int64_t)blockIdx.x * n_pos + t.p0 + pl;
+        ws.de_sum[at] = r.de_sum;
+        ws.y_min[at] = r.y_min;
+        ws.y_max[at] = r.y_max;
+        ws.y_sum[at] = r.y_sum;
+        ws.dark[at] = r.dark;
+        ws.v_max[at] = r.v_max;
+    }
+}
+
+__global__ __launch_bounds__(kEvFoldGroups * 64) void ev_fold_kernel(int64_t n_fov, int64_t n_pos, EvWorkspace ws,
+                                                                     double *out) {
+    __shared__ EvRecord s_rec[kEvFoldGroups][64];
+    const int g = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t n_tiles = ev_tiles(n_fov);
+    const int64_t per = (n_tiles + kEvFoldGroups - 1) / kEvFoldGroups;
+    const int64_t lo = g * per, hi = lo + per < n_tiles ? lo + per : n_tiles;
+    for (int64_t p0 = 0; p0 < n_pos; p0 += 64) {   // the same trip count in every lane
+        const int64_t p = p0 + lane;
+        EvRecord r = ev_record_empty();
+        if (p < n_pos)
+#pragma unroll 4   // 24 loads in flight; a deeper unroll spills at the 128 VGPRs of a 1024-thread workgroup
+            for (int64_t tile = lo; tile < hi; ++tile) {
+                const int64_t at = tile * n_pos + p;
+                EvRecord o;
+                o.de_sum = ws.de_sum[at];
+                o.y_min = ws.y_min[at];
+                o.y_max = ws.y_max[at];
+                o.y_sum = ws.y_sum[at];
+                o.dark = ws.dark[at];
+                o.v_max = ws.v_max[at];
+                ev_record_add(r, o);
+            }
+        s_rec[g][lane] = r;
+        __syncthreads();
+        if (g == 0 && p < n_pos) {
+#pragma unroll 3
+            for (int gg = 1; gg < kEvFoldGroups; ++gg) ev_record_add(r, s_rec[gg][lane]);
+            double de_mean, ufov, ueb;
+            ev_position(r, n_fov, de_mean, ufov, ueb);
+            ws.pos_de[p] = de_mean;
+            ws.pos_ufov[p] = ufov;
+            ws.max_v[p] = r.v_max;
+            out[3 + p] = ueb;
+        }
+        __syncthreads();
+    }
+    // the per-position values were written by this workgroup's wave 0, before the barrier above
+    if (threadIdx.x == 0) {
+        double o3[3];
+        ev_totals(ws.pos_de, ws.pos_ufov, out + 3, n_pos, o3);
+        out[0] = o3[0];
+        out[1] = o3[1];
+        out[2] = o3[2];
+    }
+}
+
+// image [n_fov, 3, n_pos]: the same tiling as pass 1, a wave's stores run along the position axis
+__global__ __launch_bounds__(kEvThreads) void ev_image_kernel(const double *sums, int64_t n_fov, int64_t n_pos,
+                                                              double divisor, EvConsts k, const float *max_v,
+                                                              float *image) {
+    const EvTile t = ev_tile(n_fov, n_pos);
+    for (int q = threadIdx.x; q < t.nf * t.pw; q += kEvThreads) {
+        const int fl = q / t.pw, pl = q - fl * t.pw;
+        const int64_t f = t.f0 + fl, p = t.p0 + pl;
+        double px[3];
+        float h, s, v, rgb[3];
+        ev_load_px(sums, n_fov, n_pos, f, p, divisor, k, px);
+        ev_hsv(px, h, s, v);
+        ev_image_rgb(h, s, v, max_v[p], rgb);
+        image[(f * 3 + 0) * n_pos + p] = rgb[0];
+        image[(f * 3 + 1) * n_pos + p] = rgb[1];
+        image[(f * 3 + 2) * n_pos + p] = rgb[2];
+    }
+}
+
+// image [n_fov, 3] of the one position p: a lane per FoV
+__global__ __launch_bounds__(kEvThreads) void ev_image_one_kernel(const double *sums, int64_t n_fov, int64_t n_pos,
+                                                                  double divisor, EvConsts k, const float *max_v,
+                                                                  int64_t p, float *image) {
+    const int64_t f = (int64_t)blockIdx.x * kEvThreads + threadIdx.x;
+    if (f >= n_fov) return;
+    double px[3];
+    float h, s, v, rgb[3];
+    ev_load_px(sums, n_fov, n_pos, f, p, divisor, k, px);
+    ev_hsv(px, h, s, v);
+    ev_image_rgb(h, s, v, max_v[p], rgb);
+    image[f * 3 + 0] = rgb[0];
+    image[f * 3 + 1] = rgb[1];
+    image[f * 3 + 2] = rgb[2];
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t wgrt_eyebox_evaluate_workspace_bytes(int64_t n_fov, int64_t n_pos) {
+    return ev_shape_error(n_fov, n_pos) ? -1 : ev_workspace_bytes(n_fov, n_pos);
+}
+
+wgrt_status wgrt_eyebox_evaluate(const double *sums, int64_t n_fov, int64_t n_pos, double divisor, const double *wl,
+                                 const double *lab_d65, double *out, float *image, int64_t image_pos,
+                                 void *workspace, void *stream) {
+    if (const char *why = ev_args_error(sums, n_fov, n_pos, divisor, wl, lab_d65, out, image, image_pos, workspace))
+        return fail(WGRT_ERR_INVALID_ARGUMENT, why);
+    int sdev = 0;
+    HIP_TRY(stream_device(stream, &sdev));
+    DEVICE_SCOPE(dev_scope, sdev);
+    EvConsts k;
+    for (int c = 0; c < 3; ++c) k.wl[c] = wl[c], k.lab_d65[c] = lab_d65[c];
+    const EvWorkspace ws = ev_workspace(workspace, n_fov, n_pos);
+    const dim3 tiles((unsigned)ev_tiles(n_fov), (unsigned)((n_pos + kEvPosChunk - 1) / kEvPosChunk));
+    hipLaunchKernelGGL(ev_pixels_kernel, tiles, dim3(kEvThreads), 0, (hipStream_t)stream, sums, n_fov, n_pos, divisor,
+                       k, ws);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ev_fold_kernel, dim3(1), dim3(kEvFoldGroups * 64), 0, (hipStream_t)stream, n_fov, n_pos, ws,
+                       out);
+    HIP_TRY(hipGetLastError());
+    if (image && image_pos < 0)
+        hipLaunchKernelGGL(ev_image_kernel, tiles, dim3(kEvThreads), 0, (hipStream_t)stream, sums, n_fov, n_pos,
+                           divisor, k, ws.max_v, image);
+    else if (image)
+        hipLaunchKernelGGL(ev_image_one_kernel, dim3((unsigned)((n_fov + kEvThreads - 1) / kEvThreads)),
+                           dim3(kEvThreads), 0, (hipStream_t)stream, sums, n_fov, n_pos, divisor, k, ws.max_v,
+                           image_pos, image);
     HIP_TRY(hipGetLastError());
     return WGRT_OK;
 }

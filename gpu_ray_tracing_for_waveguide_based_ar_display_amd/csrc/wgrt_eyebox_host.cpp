@@ -1,0 +1,104 @@
+// wgrt_eyebox_host.cpp -- wgrt_eyebox_evaluate_host: the host replica of wgrt_eyebox_evaluate (test hook, needs
+// no GPU).  The pixel function is the one the kernels compile (wgrt_colour.h) and every sum is taken in the
+// kernels' order: a position's column over a tile's FoVs in FoV order, the tiles in kEvFoldGroups contiguous
+// groups in tile order, the groups in group order, the totals in position order.  What differs from the
+// device is the libm behind pow / cbrt / hypot / atan2 / sin / cos / exp, and nothing else.
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "../../include/wgrt.h"
+#include "wgrt_colour.h"
+
+namespace wgrt {
+wgrt_status fail(wgrt_status s, const std::string &msg);   // wgrt_rays.hip, beside wgrt_last_error
+}
+
+using namespace wgrt;
+
+namespace {
+
+void px_at(const double *sums, int64_t n_fov, int64_t n_pos, int64_t f, int64_t p, double divisor, const EvConsts &k,
+           double px[3]) {
+    const int64_t W = 1 + n_pos, block = n_fov * W, i = f * W + 1 + p;
+    ev_px(sums[i], sums[block + i], sums[2 * block + i], divisor, k, px);
+}
+
+}  // namespace
+
+extern "C" wgrt_status wgrt_eyebox_evaluate_host(const double *sums, int64_t n_fov, int64_t n_pos, double divisor,
+                                                 const double *wl, const double *lab_d65, double *out, float *image,
+                                                 int64_t image_pos, void *workspace) {
+    if (const char *why = ev_args_error(sums, n_fov, n_pos, divisor, wl, lab_d65, out, image, image_pos, workspace))
+        return fail(WGRT_ERR_INVALID_ARGUMENT, why);
+    EvConsts k;
+    for (int c = 0; c < 3; ++c) k.wl[c] = wl[c], k.lab_d65[c] = lab_d65[c];
+    const EvWorkspace ws = ev_workspace(workspace, n_fov, n_pos);
+    const int64_t n_tiles = ev_tiles(n_fov);
+    // pass 1: one partial record per (tile, position)
+    for (int64_t tile = 0; tile < n_tiles; ++tile) {
+        const int64_t f0 = tile * kEvTileFov, f1 = f0 + kEvTileFov < n_fov ? f0 + kEvTileFov : n_fov;
+        for (int64_t p = 0; p < n_pos; ++p) {
+            EvRecord r = ev_record_empty();
+            for (int64_t f = f0; f < f1; ++f) {
+                double px[3], Y, de;
+                float h, s, v;
+                px_at(sums, n_fov, n_pos, f, p, divisor, k, px);
+                ev_colour(px, k, Y, de);
+                ev_hsv(px, h, s, v);
+                ev_record_pixel(r, de, Y, v);
+            }
+            const int64_t at = tile * n_pos + p;
+            ws.de_sum[at] = r.de_sum;
+            ws.y_min[at] = r.y_min;
+            ws.y_max[at] = r.y_max;
+            ws.y_sum[at] = r.y_sum;
+            ws.dark[at] = r.dark;
+            ws.v_max[at] = r.v_max;
+        }
+    }
+    // pass 2: the fold
+    const int64_t per = (n_tiles + kEvFoldGroups - 1) / kEvFoldGroups;
+    for (int64_t p = 0; p < n_pos; ++p) {
+        EvRecord r = ev_record_empty();
+        for (int g = 0; g < kEvFoldGroups; ++g) {
+            const int64_t lo = g * per, hi = lo + per < n_tiles ? lo + per : n_tiles;
+            EvRecord q = ev_record_empty();
+            for (int64_t tile = lo; tile < hi; ++tile) {
+                const int64_t at = tile * n_pos + p;
+                EvRecord o;
+                o.de_sum = ws.de_sum[at];
+                o.y_min = ws.y_min[at];
+                o.y_max = ws.y_max[at];
+                o.y_sum = ws.y_sum[at];
+                o.dark = ws.dark[at];
+                o.v_max = ws.v_max[at];
+                ev_record_add(q, o);
+            }
+            if (g == 0) r = q;
+            else ev_record_add(r, q);
+        }
+        double de_mean, ufov, ueb;
+        ev_position(r, n_fov, de_mean, ufov, ueb);
+        ws.pos_de[p] = de_mean;
+        ws.pos_ufov[p] = ufov;
+        ws.max_v[p] = r.v_max;
+        out[3 + p] = ueb;
+    }
+    ev_totals(ws.pos_de, ws.pos_ufov, out + 3, n_pos, out);
+    // pass 3: the image
+    if (!image) return WGRT_OK;
+    for (int64_t f = 0; f < n_fov; ++f)
+        for (int64_t p = image_pos < 0 ? 0 : image_pos; p < (image_pos < 0 ? n_pos : image_pos + 1); ++p) {
+            double px[3];
+            float h, s, v, rgb[3];
+            px_at(sums, n_fov, n_pos, f, p, divisor, k, px);
+            ev_hsv(px, h, s, v);
+            ev_image_rgb(h, s, v, ws.max_v[p], rgb);
+            for (int c = 0; c < 3; ++c) {
+                if (image_pos < 0) image[(f * 3 + c) * n_pos + p] = rgb[c];
+                else image[f * 3 + c] = rgb[c];
+            }
+        }
+    return WGRT_OK;
+}

@@ -15,7 +15,8 @@ Same flow as the reference script, on the MI355X kernel:
 5. efficiencies ``A = sum(EB) / N / num_iter``, ``eff_c = 3 * sum(A[lambda])`` (MAIN:186-192)
    and ``evaluation(EB / R / num_iter)`` (MAIN:197-198) -- on the host from the copied-back grid as the
    reference does, or (``eyebox="device"``, ``--eyebox device``) from the per-slab window sums one device pass
-   leaves (``eyebox_window_sums``), without the grid leaving the GPU;
+   leaves (``eyebox_window_sums``), without the grid leaving the GPU; with ``evaluate_on="device"``
+   (``--evaluate device``) the table stays there too and the colour math runs in ``wgrt_eyebox_evaluate``;
 6. the "Eyebox Center View.png" export (MAIN:199-203): the evaluated image at the first eye row,
    last eye column, as 8-bit RGB, rows flipped (``eyebox_center_view``, written without OpenCV).
 
@@ -45,7 +46,8 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
         lambdas=(0, 1, 2), lut_dir: str | None = None, lut_seed: int = 0, lut_profile: str = "default",
         point_seed: int | None = None, evaluate: bool = True, verbose: bool = True, variant: int = 0,
         fuse: bool | None = None, points: np.ndarray | None = None, png: str | None = None,
-        eyebox: str = "host", keep_grid: bool = False) -> dict:
+        eyebox: str = "host", keep_grid: bool = False, evaluate_on: str = "host",
+        keep_image: bool = False) -> dict:
     """The reference script's job on this engine; returns its printed quantities and arrays.
     ``points``: the R/2 in-coupler origins to use (default: sampled, GRTF:12-23, seeded by
     ``point_seed``); ``png``: where to write the "Eyebox Center View" image (needs ``evaluate``).
@@ -59,9 +61,19 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
     ``A`` and ``efficiency`` are bit-identical to the host mode's while a slab's count stays below 2^24 (then
     its float32 sum is the exact integer, as is the float64 one), which always holds for
     ``num_rays_per_FoV * num_iter < 2^24``; the evaluation divides the exact float64 window sums once where
-    the host mode divides and sums in float32 (at most 902 * 2^-24 relative per eye position)."""
+    the host mode divides and sums in float32 (at most 902 * 2^-24 relative per eye position).
+
+    ``evaluate_on``: where the colour math of the evaluation runs.  ``"host"``: ``evaluation_from_perceive`` in
+    numpy.  ``"device"`` (needs ``eyebox="device"``): the window-sum table (rank 0's, after ``EyeboxReduce``,
+    on several GPUs) is evaluated where it lives (``evaluation_from_window_sums``); only the three figures and
+    the centre image come back, ``center_view`` and the PNG are built from that image, and ``output_image``
+    (every eye position's image) is returned only with ``keep_image=True``."""
     if eyebox not in ("host", "device"):
         raise ValueError(f"eyebox must be 'host' or 'device', got {eyebox!r}")
+    if evaluate_on not in ("host", "device"):
+        raise ValueError(f"evaluate_on must be 'host' or 'device', got {evaluate_on!r}")
+    if evaluate_on == "device" and eyebox != "device":
+        raise ValueError("evaluate_on='device' evaluates the on-device window sums: it needs eyebox='device'")
     import torch
     import torch.distributed as dist
 
@@ -143,8 +155,10 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
         return out
     if on_device:
         # slab totals are integer counts: below 2^24 the float32 cast is the value np.sum gives on the host
-        sums = sums.cpu().numpy()
-        A = sums[:, 0].reshape(scene.eb_shape()[:-2]).astype(np.float32) / num_rays / num_iter
+        sums_dev = sums
+        sums = sums[:, 0].cpu().numpy() if evaluate_on == "device" else sums.cpu().numpy()
+        totals = sums if sums.ndim == 1 else sums[:, 0]
+        A = totals.reshape(scene.eb_shape()[:-2]).astype(np.float32) / num_rays / num_iter
     else:
         A = np.sum(matrix_EB, axis=(-2, -1)) / num_rays / num_iter
     names = {0: "Blue", 1: "Green", 2: "Red"}
@@ -159,14 +173,24 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
     if matrix_EB is not None:
         out["matrix_EB"] = matrix_EB
     if evaluate:
-        from .AR_system_evaluation_functions import evaluation, evaluation_from_perceive, perceive_from_window_sums
-        if on_device:
-            delta_e, U_fov, U_EB, output_image = evaluation_from_perceive(
-                perceive_from_window_sums(sums, scene.eb_shape(), R * num_iter))
+        from .AR_system_evaluation_functions import (evaluation, evaluation_from_perceive,
+                                                     evaluation_from_window_sums, perceive_from_window_sums)
+        if evaluate_on == "device":
+            delta_e, U_fov, U_EB, image = evaluation_from_window_sums(
+                sums_dev, scene.eb_shape(), R * num_iter, image="all" if keep_image else "center")
+            center = image[:, :, :, 0, image.shape[4] - 1] if keep_image else image
+            out.update(delta_e=float(delta_e), U_fov=float(U_fov), U_EB=float(U_EB))
+            if keep_image:
+                out["output_image"] = image
+            out["center_view"] = center_view_u8(center)
         else:
-            delta_e, U_fov, U_EB, output_image = evaluation(matrix_EB / R / num_iter)
-        out.update(delta_e=float(delta_e), U_fov=float(U_fov), U_EB=float(U_EB), output_image=output_image)
-        out["center_view"] = eyebox_center_view(output_image)
+            if on_device:
+                delta_e, U_fov, U_EB, output_image = evaluation_from_perceive(
+                    perceive_from_window_sums(sums, scene.eb_shape(), R * num_iter))
+            else:
+                delta_e, U_fov, U_EB, output_image = evaluation(matrix_EB / R / num_iter)
+            out.update(delta_e=float(delta_e), U_fov=float(U_fov), U_EB=float(U_EB), output_image=output_image)
+            out["center_view"] = eyebox_center_view(output_image)
         if png:
             write_png(png, out["center_view"])
             say(f"Wrote {png}")
@@ -184,7 +208,12 @@ def eyebox_center_view(output_image: np.ndarray) -> np.ndarray:
     column) as uint8 (``* 255`` then truncation), rows flipped -- uint8 RGB [n_FOVy, n_FOVx, 3].  (The
     reference converts it to BGR for cv2.imwrite, which stores the RGB image in the PNG.)"""
     n_epx = output_image.shape[4]
-    return np.ascontiguousarray(np.flipud((output_image[:, :, :, 0, n_epx - 1] * 255).astype(np.uint8)))
+    return center_view_u8(output_image[:, :, :, 0, n_epx - 1])
+
+
+def center_view_u8(center: np.ndarray) -> np.ndarray:
+    """One eye position's image ``[n_FOVy, n_FOVx, 3]`` as ``eyebox_center_view`` exports it."""
+    return np.ascontiguousarray(np.flipud((center * 255).astype(np.uint8)))
 
 
 def write_png(path: str, rgb: np.ndarray) -> None:
@@ -241,6 +270,9 @@ def main(argv=None):
     ap.add_argument("--eyebox", choices=["host", "device"], default="host",
                     help="where the eyebox grid is reduced after the trace: host (the reference's flow: the whole "
                          "grid is copied back) or device (per-slab pupil sums on the GPU; the grid stays there)")
+    ap.add_argument("--evaluate", choices=["host", "device"], default="host",
+                    help="where the evaluation's colour math runs: host (numpy) or device (wgrt_eyebox_evaluate on "
+                         "the window-sum table; needs --eyebox device)")
     ap.add_argument("--json", default=None, help="write scalar results here")
     ap.add_argument("--png", default="Eyebox Center View.png",
                     help="the eyebox-center image (MAIN:199-203); empty string: do not write it")
@@ -254,7 +286,7 @@ def main(argv=None):
     res = run(a.num_fov_x, a.num_fov_y, a.rays_per_fov, a.num_iter, lut_dir=a.lut_dir, lut_seed=a.lut_seed,
               lut_profile=a.lut_profile, point_seed=a.point_seed, evaluate=not a.no_eval,
               fuse=False if a.no_fuse else {"auto": None, "yes": True, "no": False}[a.fuse],
-              png=a.png or None, eyebox=a.eyebox)
+              png=a.png or None, eyebox=a.eyebox, evaluate_on=a.evaluate)
     if a.json and (not dist.is_initialized() or dist.get_rank() == 0):
         keep = {k: v for k, v in res.items() if isinstance(v, (int, float, dict, str))}
         with open(a.json, "w") as f:

@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define WGRT_ABI_VERSION 8
+#define WGRT_ABI_VERSION 9
 
 typedef enum {
     WGRT_OK = 0,
@@ -309,6 +309,39 @@ wgrt_status wgrt_eyebox_assemble(float *eb, int64_t n_slabs, const float *recv, 
 wgrt_status wgrt_eyebox_window_sums(const float *eb, int64_t n_slabs, const int64_t *slabs, int64_t n,
                                     const float *mask, int32_t ms, int32_t step_y, int32_t step_x,
                                     double *out, void *stream);
+
+/* ABI 9.  Evaluation of the window-sum table on the device (replaces the host colour math of EVAL:112-163):
+ * the three merit figures and, optionally, the evaluated image, from what wgrt_eyebox_window_sums wrote.
+ *   sums     float64 [3 * n_fov, 1 + n_pos], rows ordered (lambda, FoV) -- the whole three-wavelength grid's
+ *            table; column 0 (the slab total) is ignored;
+ *   divisor  perceive = sum / divisor (R * num_iter, MAIN:197); finite and > 0;
+ *   wl       HOST float64 [3]: inv(M_SENSOR) . (1, 1, 1), the per-wavelength weights of the white image
+ *            (EVAL:47-52, 112-118); lab_d65: HOST float64 [3], the CIELAB reference white (EVAL:53-57);
+ *   out      float64 [3 + n_pos]: delta_e, U_fov, U_EB (EVAL:160-163), then U_EB[i, j] of every eye position
+ *            before the final min / max (0 for a position with a dark pixel, EVAL:150-157);
+ *   image    float32, or NULL for none.  image_pos = -1: every position, [n_fov, 3, n_pos] (the reference's
+ *            output_image [NY, NX, 3, npy, npx]); image_pos = p >= 0: position p alone, [n_fov, 3];
+ *   workspace  wgrt_eyebox_evaluate_workspace_bytes(n_fov, n_pos) bytes (-1 for a shape the call rejects),
+ *            8-B aligned, overwritten.
+ * Each pixel (FoV, position) is evaluated as AR_system_evaluation_functions.evaluation_from_perceive does, operation
+ * by operation (csrc/wgrt_colour.h): float64 colour side, float32 HSV normalisation.  No float atomics; every sum
+ * is taken in an order fixed by (n_fov, n_pos), so the same input gives the same bits on every run.  sums, out,
+ * image and workspace are DEVICE pointers; the call allocates nothing and is asynchronous on stream, on the
+ * stream's device (as wgrt_eyebox_window_sums, whose table may be fed on the same stream without a sync).
+ * n_fov >= 1, 1 <= n_pos <= 2^20, 3 * n_fov * (1 + n_pos) <= 2^31 - 1 (the index arithmetic's limit: a 17 GB
+ * table), -1 <= image_pos < n_pos, sums / out / workspace 8-B and image 4-B aligned, else
+ * WGRT_ERR_INVALID_ARGUMENT.  Not part of the reference. */
+int64_t wgrt_eyebox_evaluate_workspace_bytes(int64_t n_fov, int64_t n_pos);
+wgrt_status wgrt_eyebox_evaluate(const double *sums, int64_t n_fov, int64_t n_pos, double divisor, const double *wl,
+                                 const double *lab_d65, double *out, float *image, int64_t image_pos,
+                                 void *workspace, void *stream);
+
+/* Host-only replica of wgrt_eyebox_evaluate (no GPU needed; test hook): the same arguments with HOST pointers,
+ * the same pixel function and the same order of every sum, on the CPU.  Differs from the device only by the
+ * host libm's last places in pow / cbrt / hypot / atan2 / sin / cos / exp. */
+wgrt_status wgrt_eyebox_evaluate_host(const double *sums, int64_t n_fov, int64_t n_pos, double divisor,
+                                      const double *wl, const double *lab_d65, double *out, float *image,
+                                      int64_t image_pos, void *workspace);
 
 /* Polygon membership of n points (DEVICE xy[n, 2]) through the scene's locator:
  * bit k of out_mask[i] = is_inside_or_on_edge(point i, polygon k) with polygon order

@@ -1,0 +1,308 @@
+"""``wgrt_eyebox_evaluate`` (csrc/wgrt_eyebox.hip) on the GPU against its host replica
+(``wgrt_eyebox_evaluate_host``: the same pixel function and summation order, tests/test_eyebox_evaluate.py)
+and against numpy's ``evaluation_from_perceive``, on the tables of tests/_evaluate_cases.py; then determinism,
+the memory around its three outputs, chaining behind ``wgrt_eyebox_window_sums`` on one stream, the driver's
+``evaluate_on="device"`` mode and the multi-rank flow (all ranks on cuda:0 over gloo, as
+tests/test_gpu_eyebox_reduce.py).
+
+Tolerances as on the CPU: 1e-12 relative for the scalars and the per-position ``U_EB`` (exactly 0 where the
+reference is), 2^-20 absolute for the image; device and replica differ only by the last places of the device
+libm."""
+import ctypes
+import os
+import socket
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+from gpu_ray_tracing_for_waveguide_based_ar_display_amd import AR_system_evaluation_functions as E  # noqa: E402
+from tests import _evaluate_cases as C  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+INVALID_ARGUMENT = 1   # WGRT_ERR_INVALID_ARGUMENT (include/wgrt.h)
+PAD = 64               # guard words on either side of every output
+
+
+def _dev():
+    if not torch.cuda.is_available():
+        pytest.skip("no HIP device")
+    return torch.device("cuda", 0)
+
+
+def _lib():
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd import _lib
+    return _lib.load()
+
+
+def _host_raw(table, n_fov, n_pos, image_pos):
+    """The host replica's ``(out, image)``; ``image_pos=None``: no image."""
+    L = _lib()
+    vp = ctypes.c_void_p
+    wl, lab = E._evaluate_consts()
+    ws = np.empty(int(L.wgrt_eyebox_evaluate_workspace_bytes(n_fov, n_pos)) // 8)
+    out = np.empty(3 + n_pos)
+    img = None if image_pos is None else np.empty((n_fov, 3, n_pos) if image_pos < 0 else (n_fov, 3), np.float32)
+    assert L.wgrt_eyebox_evaluate_host(table.ctypes.data_as(vp), n_fov, n_pos, C.DIVISOR, wl.ctypes.data_as(vp),
+                                       lab.ctypes.data_as(vp), out.ctypes.data_as(vp),
+                                       img.ctypes.data_as(vp) if img is not None else None,
+                                       -1 if image_pos is None else image_pos, ws.ctypes.data_as(vp)) == 0
+    return out, img
+
+
+def _dev_raw(table_dev, n_fov, n_pos, image_pos, divisor=C.DIVISOR, expect=0):
+    """The raw device call with ``out``, ``image`` and the workspace each between ``PAD`` guard words, which must
+    come back untouched: ``(out, image)`` on the host (``image_pos=None``: image = NULL)."""
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import _stream_handle
+    L = _lib()
+    dev = table_dev.device
+    vp = ctypes.c_void_p
+    wl, lab = E._evaluate_consts()
+    n_img = 0 if image_pos is None else (n_fov * 3 * n_pos if image_pos < 0 else n_fov * 3)
+    ws_words = max(int(L.wgrt_eyebox_evaluate_workspace_bytes(n_fov, n_pos)), 8) // 8
+    out = torch.full((PAD + 3 + n_pos + PAD,), -7.25, dtype=torch.float64, device=dev)
+    img = torch.full((PAD + n_img + PAD,), -7.25, dtype=torch.float32, device=dev)
+    ws = torch.full((PAD + ws_words + PAD,), -7.25, dtype=torch.float64, device=dev)
+    st = L.wgrt_eyebox_evaluate(table_dev.data_ptr(), n_fov, n_pos, divisor, wl.ctypes.data_as(vp),
+                                lab.ctypes.data_as(vp), out.data_ptr() + 8 * PAD,
+                                img.data_ptr() + 4 * PAD if image_pos is not None else None,
+                                -1 if image_pos is None else image_pos, ws.data_ptr() + 8 * PAD, _stream_handle(dev))
+    assert st == expect, L.wgrt_last_error()
+    torch.cuda.synchronize()
+    o, i, w = out.cpu().numpy(), img.cpu().numpy(), ws.cpu().numpy()
+    for name, a, n in (("out", o, 3 + n_pos), ("image", i, n_img), ("workspace", w, ws_words)):
+        assert (a[:PAD] == -7.25).all() and (a[PAD + n:] == -7.25).all(), f"{name}: guard words overwritten"
+    if expect != 0:
+        assert (o == -7.25).all() and (i == -7.25).all() and (w == -7.25).all()   # nothing was launched
+        return None, None
+    image = None if image_pos is None else i[PAD:PAD + n_img].reshape((n_fov, 3, n_pos) if image_pos < 0 else (n_fov, 3))
+    return o[PAD:PAD + 3 + n_pos], image
+
+
+WORST = dict(scalar_vs_host=0.0, scalar_vs_numpy=0.0, image_vs_host=0.0, image_vs_numpy=0.0, differ_host=0,
+             differ_numpy=0, elements=0)
+
+
+def _rel(got, want):
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    nz = want != 0
+    return float(np.max(np.abs(got[nz] - want[nz]) / np.abs(want[nz]))) if nz.any() else 0.0
+
+
+@pytest.mark.parametrize("case", C.CASES, ids=C.case_id)
+def test_device_equals_replica_and_numpy(case):
+    dev = _dev()
+    table, shape, kw, want, ueb = C.reference(case)
+    ny, nx, n_pos = shape[1], shape[2], case[2]
+    n_fov = ny * nx
+    d = torch.tensor(table, device=dev)   # the reference table is read-only
+    out, img = _dev_raw(d, n_fov, n_pos, -1)
+    h_out, h_img = _host_raw(table, n_fov, n_pos, -1)
+    cid = C.case_id(case)
+    C.close(out, h_out, f"{cid} out vs replica")
+    C.close(out[:3], np.array([float(v) for v in want[:3]]), f"{cid} scalars vs numpy")
+    C.close(out[3:], ueb, f"{cid} U_EB[i, j] vs numpy")
+    npy, npx = E.window_grid(**kw)
+    as_host = img.astype(np.float64).reshape(ny, nx, 3, npy, npx)
+    dh, nh = C.image_close(img, h_img, f"{cid} vs replica")
+    dn, nn = C.image_close(as_host, want[3], f"{cid} vs numpy")
+    WORST.update(scalar_vs_host=max(WORST["scalar_vs_host"], _rel(out, h_out)),
+                 scalar_vs_numpy=max(WORST["scalar_vs_numpy"], _rel(out[:3], want[:3]), _rel(out[3:], ueb)),
+                 image_vs_host=max(WORST["image_vs_host"], dh), image_vs_numpy=max(WORST["image_vs_numpy"], dn),
+                 differ_host=WORST["differ_host"] + nh, differ_numpy=WORST["differ_numpy"] + nn,
+                 elements=WORST["elements"] + img.size)
+    print("worst so far:", WORST)
+    # the Python layer on a device tensor: the same figures, the image in the host's layout
+    got = E.evaluation_from_window_sums(d, shape, C.DIVISOR, image="all", **kw)
+    assert got[:3] == tuple(float(v) for v in out[:3])
+    np.testing.assert_array_equal(got[3], as_host)
+
+
+@pytest.mark.parametrize("case", [(5, 7, 56, "dark"), (21, 21, 77, "lit"), (1, 1, 1, "dark"), (9, 7, 1, "lit")],
+                         ids=C.case_id)
+def test_deterministic_and_image_forms_within_bounds(case):
+    """Two runs give identical bytes; the one-position image is the full image's slice bit for bit; without an
+    image the scalars are the same bits; the guard words around ``out``, ``image`` and the workspace survive
+    every form (checked inside ``_dev_raw``)."""
+    dev = _dev()
+    table, shape, kw, want, ueb = C.reference(case)
+    n_fov, n_pos = shape[1] * shape[2], case[2]
+    d = torch.tensor(table, device=dev)   # the reference table is read-only
+    out, img = _dev_raw(d, n_fov, n_pos, -1)
+    out2, img2 = _dev_raw(d, n_fov, n_pos, -1)
+    assert out.tobytes() == out2.tobytes() and img.tobytes() == img2.tobytes()
+    for p in sorted({0, n_pos // 2, n_pos - 1}):
+        out_p, img_p = _dev_raw(d, n_fov, n_pos, p)
+        assert out_p.tobytes() == out.tobytes()
+        assert img_p.tobytes() == np.ascontiguousarray(img[:, :, p]).tobytes()
+    out_n, _ = _dev_raw(d, n_fov, n_pos, None)
+    assert out_n.tobytes() == out.tobytes()
+    npy, npx = E.window_grid(**kw)
+    centre = E.evaluation_from_window_sums(d, shape, C.DIVISOR, image="center", **kw)
+    np.testing.assert_array_equal(centre[3], img[:, :, npx - 1].astype(np.float64).reshape(shape[1], shape[2], 3))
+    assert E.evaluation_from_window_sums(d, shape, C.DIVISOR, image=None, **kw)[3] is None
+
+
+def test_argument_validation_launches_nothing():
+    dev = _dev()
+    table, shape, kw, _, _ = C.reference((4, 5, 56, "lit"))
+    d = torch.tensor(table, device=dev)   # the reference table is read-only
+    for n_fov, n_pos, divisor, image_pos in [(0, 56, 1.0, -1), (20, 0, 1.0, -1), (20, 56, 0.0, -1),
+                                             (20, 56, float("nan"), -1), (20, 56, float("inf"), -1),
+                                             (20, 56, 1.0, 56), (20, 56, 1.0, -2)]:
+        _dev_raw(d, n_fov, n_pos, image_pos, divisor=divisor, expect=INVALID_ARGUMENT)
+    L = _lib()
+    wl, lab = E._evaluate_consts()
+    vp = ctypes.c_void_p
+    out = torch.zeros(3 + 56, dtype=torch.float64, device=dev)
+    ws = torch.zeros(int(L.wgrt_eyebox_evaluate_workspace_bytes(20, 56)) // 8, dtype=torch.float64, device=dev)
+    assert L.wgrt_eyebox_evaluate(None, 20, 56, 1.0, wl.ctypes.data_as(vp), lab.ctypes.data_as(vp), out.data_ptr(),
+                                  None, -1, ws.data_ptr(), None) == INVALID_ARGUMENT
+    assert L.wgrt_eyebox_evaluate(d.data_ptr(), 20, 56, 1.0, wl.ctypes.data_as(vp), lab.ctypes.data_as(vp),
+                                  out.data_ptr(), None, -1, None, None) == INVALID_ARGUMENT
+    with pytest.raises(ValueError):   # the Python layer refuses a device table the kernel cannot take
+        E.evaluation_from_window_sums(d.float(), shape, C.DIVISOR)
+    with pytest.raises(ValueError):
+        E.evaluation_from_window_sums(d[:40], (2, 4, 5, 80, 120), C.DIVISOR)
+
+
+def test_chained_behind_window_sums_and_current_device():
+    """The table fed straight from ``eyebox_window_sums`` of a device grid, on the same stream with no sync
+    between the two calls, against the table round-tripped through the host; on a side stream, so that a call
+    on the wrong stream would race.  The calling thread's current device is left as it was."""
+    dev = _dev()
+    rng = np.random.default_rng(11)
+    shape = (3, 6, 7, 80, 120)
+    eb = torch.from_numpy(rng.poisson(1.5, size=shape).astype(np.float32)).to(dev)
+    before = torch.cuda.current_device()
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        sums = E.eyebox_window_sums(eb)
+        chained = E.evaluation_from_window_sums(sums, shape, 9000.0)
+    side.synchronize()
+    assert torch.cuda.current_device() == before
+    table = sums.cpu().numpy()
+    torch.cuda.synchronize()
+    again = E.evaluation_from_window_sums(torch.from_numpy(table).to(dev), shape, 9000.0)
+    assert chained[:3] == again[:3] and chained[3].tobytes() == again[3].tobytes()
+    assert C.hue_branch_margin(E.perceive_from_window_sums(table, shape, 9000.0)) > 1e-6
+    host = E.evaluation_from_window_sums(table, shape, 9000.0)
+    for name, g, w in zip(("delta_e", "U_fov", "U_EB"), chained[:3], host[:3]):
+        C.close(g, w, f"chained {name}")
+    C.image_close(chained[3], host[3], "chained")
+    # evaluation_device: the grid -> the figures without the table leaving the device
+    via = E.evaluation_device(eb, 9000.0, evaluate_on="device")
+    assert via[:3] == again[:3] and via[3].tobytes() == again[3].tobytes()
+
+
+# --- the driver -------------------------------------------------------------------------------------------
+
+NX, NY, LAMBDAS, R, STEPS = 5, 4, [0, 1, 2], 256, 2
+
+
+def _inputs():
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.couplers_coor import design_geometry
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.luts import synthetic_luts
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.rays import generate_points_in_polygon
+    geom = design_geometry(NX, NY)
+    luts = synthetic_luts(geom, seed=3, profile="deep")
+    pts = generate_points_in_polygon(geom.IC, R // 2, rng=np.random.default_rng(6))
+    return geom, luts, pts
+
+
+def test_driver_evaluate_on_device(tmp_path):
+    _dev()
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.gpu_ray_tracing_pro_fullColor import read_png, run
+    _, _, pts = _inputs()   # the same in-coupler origins in every run
+    kw = dict(lut_seed=3, lut_profile="deep", points=pts, verbose=False, eyebox="device")
+    host = run(NX, NY, R, STEPS, evaluate_on="host", keep_grid=True, **kw)
+    png = str(tmp_path / "centre.png")
+    dev = run(NX, NY, R, STEPS, evaluate_on="device", png=png, **kw)
+    assert dev["A"].dtype == host["A"].dtype and dev["A"].tobytes() == host["A"].tobytes()
+    assert dev["efficiency"] == host["efficiency"]
+    np.testing.assert_array_equal(dev["rng_states"], host["rng_states"])
+    table = E.eyebox_window_sums(host["matrix_EB"])
+    assert C.hue_branch_margin(E.perceive_from_window_sums(table, host["matrix_EB"].shape, R * STEPS)) > 1e-6
+    for key in ("delta_e", "U_fov", "U_EB"):
+        C.close(dev[key], host[key], f"driver {key}")
+    assert "output_image" not in dev and "matrix_EB" not in dev
+    assert dev["center_view"].shape == host["center_view"].shape and dev["center_view"].dtype == np.uint8
+    # the * 255 truncation may flip at a boundary: one 8-bit level per channel
+    step = np.abs(dev["center_view"].astype(np.int16) - host["center_view"].astype(np.int16))
+    print(f"center_view: {int(np.count_nonzero(step))} of {step.size} channels differ, max {int(step.max())}")
+    assert step.max() <= 1
+    np.testing.assert_array_equal(read_png(png), dev["center_view"])
+    kept = run(NX, NY, R, STEPS, evaluate_on="device", keep_image=True, **kw)
+    assert kept["output_image"].shape == host["output_image"].shape
+    C.image_close(kept["output_image"], host["output_image"], "driver output_image")
+    assert (kept["delta_e"], kept["U_fov"], kept["U_EB"]) == (dev["delta_e"], dev["U_fov"], dev["U_EB"])
+    np.testing.assert_array_equal(kept["center_view"], dev["center_view"])
+    with pytest.raises(ValueError):
+        run(NX, NY, R, STEPS, **dict(kw, eyebox="host", evaluate_on="device"))
+    with pytest.raises(ValueError):
+        run(NX, NY, R, STEPS, evaluate_on="gpu", **kw)
+
+
+# --- multi-rank: every rank traces its shard on cuda:0, the window sums are sum-reduced over gloo and rank 0
+# --- evaluates its table on the device ------------------------------------------------------------------------
+
+def _free_port():
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
+def _traced(world, rank, reduce_with=None):
+    """Rank ``rank``'s shard traced on cuda:0 and reduced to the job's window sums (``world = 1``: in process)."""
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.distributed import (hip_shard_builder, hip_tracer,
+                                                                                make_shard, run_steps)
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import Scene, check_stats, new_stats
+    dev = torch.device("cuda", 0)
+    geom, luts, pts = _inputs()
+    scene = Scene.from_geometry(geom, luts)
+    shard = make_shard(NX, NY, len(LAMBDAS), R, world, rank)
+    rays, rng = hip_shard_builder(pts, NX, NY, LAMBDAS, R, dev)(shard)
+    eb = torch.zeros(scene.eb_shape(), dtype=torch.float32, device=dev)
+    stats = new_stats(dev)
+    run_steps(hip_tracer(scene, 0, stats), rays, rng, eb, shard.gid, STEPS, 1)
+    sums = reduce_with(eb) if reduce_with is not None else E.eyebox_window_sums(eb)
+    shape = scene.eb_shape()
+    got = E.evaluation_from_window_sums(sums, shape, R * STEPS, image="center") if rank == 0 else None
+    torch.cuda.synchronize()
+    check_stats(stats)
+    scene.close()
+    return sums, got
+
+
+def _worker(rank, world, port, outdir):
+    import torch.distributed as dist
+
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.distributed import EyeboxReduce, rank_blocks
+
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    torch.cuda.set_device(torch.device("cuda", 0))
+    nb = NX * NY * len(LAMBDAS)
+    reduce = EyeboxReduce([rank_blocks(nb, world, r, "interleaved", len(LAMBDAS)) for r in range(world)],
+                          NX, NY, LAMBDAS, len(LAMBDAS))
+    sums, got = _traced(world, rank, reduce)
+    if rank == 0:
+        assert sums.is_cuda
+        np.savez(os.path.join(outdir, "rank0.npz"), sums=sums.cpu().numpy(), scalars=np.array(got[:3]), image=got[3])
+    dist.destroy_process_group()
+
+
+def test_two_ranks_equal_single_process(tmp_path):
+    """The reduced table is bit-identical to the single-process one, so rank 0's device scalars and centre image
+    equal the single-process device results bit for bit."""
+    _dev()
+    import torch.multiprocessing as mp
+    mp.start_processes(_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True, start_method="spawn")
+    got = np.load(tmp_path / "rank0.npz")
+    sums, want = _traced(1, 0)
+    assert got["sums"].tobytes() == sums.cpu().numpy().tobytes() and got["sums"][:, 0].sum() > 0
+    assert got["scalars"].tobytes() == np.array(want[:3]).tobytes()
+    assert got["image"].shape == (NY, NX, 3) and got["image"].tobytes() == want[3].tobytes()

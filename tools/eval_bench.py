@@ -10,12 +10,18 @@ On a synthetic integer-valued grid at 2 % occupancy, filled on the device, at th
   (d) host_post     wall time of the driver's host mode after the trace: eb.cpu(), the slab sums, the scaling
                     and evaluation() (MAIN:186-198);
       device_post   the same quantities in device mode: (a), its 57 doubles per slab copied back, and
-                    evaluation_from_perceive.
+                    evaluation_from_perceive;
+      device_eval_post  the same in device mode with --evaluate device: (a), (e) with the centre image, and the
+                    slab totals, three figures and centre image copied back;
+  (e) evaluate      wgrt_eyebox_evaluate on the table of (a) (evaluation_from_window_sums' device path, through
+                    the raw call so that no copy is timed): with the full image, the centre image, no image;
+      host_colour_s wall time of the host colour math (e) replaces, evaluation_from_perceive on the copied-back
+                    table, in this process.
 
-(a)-(c): HIP events around each of --repeats calls after --warmup calls, all in this process; median, min
+(a)-(c), (e): HIP events around each of --repeats calls after --warmup calls, all in this process; median, min
 and max in ms.  (d): wall clock around --post-repeats runs (seconds each; the host evaluation of the default
-grid takes several seconds).  The kernel's result is compared with (b)'s once per shape (integer counts:
-equal after the cast to float32).
+grid takes several seconds).  The kernel's result is compared with (b)'s once per shape (integer counts: equal
+after the cast to float32), (e)'s with the host colour math.
 
     python tools/eval_bench.py --out profiles/eval_bench.jsonl
 """
@@ -65,6 +71,34 @@ def event_times(fn, warmup, repeats):
     return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
 
 
+def raw_evaluate(E, sums, shape, divisor):
+    """``form -> callable`` launching wgrt_eyebox_evaluate on the device table ``sums`` into buffers allocated
+    here once (what evaluation_from_window_sums does, without its copies back), and the buffers."""
+    import ctypes
+
+    import torch
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd._lib import check, load
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import _stream_handle
+    L = load()
+    dev = sums.device
+    npy, npx = E.window_grid()
+    n_fov, n_pos = shape[1] * shape[2], npy * npx
+    wl, lab = E._evaluate_consts()
+    vp = ctypes.c_void_p
+    ws = torch.empty(int(L.wgrt_eyebox_evaluate_workspace_bytes(n_fov, n_pos)), dtype=torch.uint8, device=dev)
+    out = torch.empty(3 + n_pos, dtype=torch.float64, device=dev)
+    img = {"all": torch.empty((n_fov, 3, n_pos), dtype=torch.float32, device=dev),
+           "center": torch.empty((n_fov, 3), dtype=torch.float32, device=dev), "none": None}
+    pos = {"all": -1, "center": npx - 1, "none": -1}
+
+    def call(form):
+        check(L.wgrt_eyebox_evaluate(sums.data_ptr(), n_fov, n_pos, float(divisor), wl.ctypes.data_as(vp),
+                                     lab.ctypes.data_as(vp), out.data_ptr(),
+                                     img[form].data_ptr() if img[form] is not None else None, pos[form],
+                                     ws.data_ptr(), _stream_handle(dev)), "wgrt_eyebox_evaluate")
+    return call, out, img, ws
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--shapes", nargs="+", default=["default", "C3"], choices=sorted(SHAPES))
@@ -102,7 +136,14 @@ def main(argv=None):
         rec["window_sums_over_sum_floor"] = round(rec["window_sums"]["median_ms"] / rec["sum_floor"]["median_ms"], 3)
         rec["window_sums_GBps"] = round(rec["grid_bytes"] / rec["window_sums"]["median_ms"] / 1e6, 1)
         rec["sum_floor_GBps"] = round(rec["grid_bytes"] / rec["sum_floor"]["median_ms"] / 1e6, 1)
-        host, d2h, device = [], [], []
+        # (e): the evaluation of the table on the device
+        call, ev_out, ev_img, ev_ws = raw_evaluate(E, sums, shape, R * K)
+        rec["table_bytes"] = sums.numel() * 8
+        rec["image_bytes"] = ev_img["all"].numel() * 4
+        rec["workspace_bytes"] = ev_ws.numel()
+        for form in ("all", "center", "none"):
+            rec[f"evaluate_{form}"] = event_times(lambda: call(form), a.warmup, a.repeats)
+        host, d2h, device, device_eval, colour = [], [], [], [], []
         for _ in range(a.post_repeats):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -116,13 +157,29 @@ def main(argv=None):
             t0 = time.perf_counter()
             s = E.eyebox_window_sums(eb).cpu().numpy()
             A_d = s[:, 0].reshape(shape).astype(np.float32) / num_rays / K
+            t1 = time.perf_counter()
             ev_d = E.evaluation_from_perceive(E.perceive_from_window_sums(s, shape, R * K))
             device.append(time.perf_counter() - t0)
+            colour.append(time.perf_counter() - t1)
+            t0 = time.perf_counter()
+            sd = E.eyebox_window_sums(eb)
+            A_e = sd[:, 0].cpu().numpy().reshape(shape).astype(np.float32) / num_rays / K
+            ev_e = E.evaluation_from_window_sums(sd, shape + (80, 120), R * K, image="center")
+            device_eval.append(time.perf_counter() - t0)
         rec["A_bit_identical"] = bool(A.tobytes() == A_d.tobytes())
         rec["evaluation_diff"] = [float(ev_d[k] - ev[k]) for k in range(3)]
         rec["host_post_s"] = [round(v, 4) for v in host]
         rec["host_post_d2h_s"] = [round(v, 4) for v in d2h]
         rec["device_post_s"] = [round(v, 4) for v in device]
+        rec["host_colour_s"] = [round(v, 4) for v in colour]
+        rec["device_eval_post_s"] = [round(v, 4) for v in device_eval]
+        rec["device_eval_A_bit_identical"] = bool(A_e.tobytes() == A_d.tobytes())
+        rec["device_eval_rel_diff"] = [float(abs(ev_e[k] - ev_d[k]) / abs(ev_d[k])) if ev_d[k] else float(abs(ev_e[k]))
+                                       for k in range(3)]
+        n_epx = ev_d[3].shape[4]
+        rec["device_eval_center_max_diff"] = float(np.max(np.abs(ev_e[3] - ev_d[3][:, :, :, 0, n_epx - 1])))
+        rec["host_colour_over_evaluate_center"] = round(
+            statistics.median(colour) * 1e3 / rec["evaluate_center"]["median_ms"], 1)
         line = json.dumps(rec)
         print(line, flush=True)
         if a.out:
