@@ -1,6 +1,12 @@
 // wgrt_exact_lane.h -- the exact lane of the reference's per-ray state machine
 // (GPU_ray_tracing_functions.py = GRTF:833-1246): the reference's float64
-// arithmetic in its expression order.  Variant 1, the replays and the certification shadow run it.
+// arithmetic in its expression order, stated once.  Who runs what:
+//   trace_one     variant 1 (trace_grid_kernel) and every replay (replay_tail, epilogue_kernel; wgrt_trace.hip):
+//                 lane_load, then interact / advance in turn, lane_retire;
+//   lane_load, take_branch, advance, lane_retire
+//                 the certification shadow too (wgrt_shadow.hip), around its own literal all-branches decision:
+//                 what it certifies the product lane against is this file's arithmetic, not a copy of it;
+//   eyebox_add    interact's out-coupling and the Jones kernels' out-coupling queue (bin_entry, wgrt_trace.hip).
 #pragma once
 
 #include "wgrt_args.h"
@@ -69,27 +75,79 @@ struct Lane {
 // Load ray i (GRTF:846-859).  Returns false (and leaves the lane empty) for a ray whose
 // FoV / wavelength indices fall outside the scene.
 __device__ __forceinline__ bool lane_load(const TraceArgs &A, int64_t i, Lane &L) {
-    const int64_t ld = i;
-    const int m = (int)A.m[ld], n = (int)A.n[ld], l = A.l ? (int)A.l[ld] : 0;
+    const int m = (int)A.m[i], n = (int)A.n[i], l = A.l ? (int)A.l[i] : 0;
     if (!(m >= 0 && m < A.nx && n >= 0 && n < A.ny && l >= 0 && l < A.nl)) return false;
     L.i = i;
     L.l = l;
     L.m = m;
     L.n = n;
     L.T = A.tiles + (int64_t)((l * A.nx + m) * A.ny + n) * A.tile_d;
-    L.r.x = (double)A.x[ld];
-    L.r.y = (double)A.y[ld];
-    L.r.te = (double)A.te[ld];
-    L.r.tm = (double)A.tm[ld];
-    L.r.dph = (double)A.dph[ld];
+    L.r.x = (double)A.x[i];
+    L.r.y = (double)A.y[i];
+    L.r.te = (double)A.te[i];
+    L.r.tm = (double)A.tm[i];
+    L.r.dph = (double)A.dph[i];
     L.r.cos_t = 1.0;
     L.r.ener = 1.0;
-    L.r.s = A.rng[ld];
+    L.r.s = A.rng[i];
     L.r.region = 0;
     L.bounces = 1;
     L.hit = false;
     L.libm = false;
     return true;
+}
+
+// Eyebox accumulation of an out-coupling (GRTF:1162-1171, 1231-1240) of a ray of tile T = (l, m, n) at (x, y):
+// the per-FoV eyebox rectangle test, the bin, and the atomic.  Returns whether the grid was added to.
+__device__ __forceinline__ bool eyebox_add(const TraceArgs &A, const double *T, int l, int m, int n, double x,
+                                           double y) {
+    if (!inside_or_on_edge(x, y, T + kTileEbRect, 4)) return false;
+    const double xmin = T[kTileEbRange], xmax = T[kTileEbRange + 1];
+    const double ymin = T[kTileEbRange + 2], ymax = T[kTileEbRange + 3];
+    const double dx = (xmax - xmin) / kEbNx, dy = (ymax - ymin) / kEbNy;
+    int64_t ix = (int64_t)floor((x - xmin) / dx);
+    int64_t iy = (int64_t)floor((y - ymin) / dy);
+    // compiled-numba addressing (GRTF:164): a negative index wraps once, an index
+    // equal to the axis length aliases into the next row; guarded to the buffer
+    if (ix < 0) ix += kEbNx;
+    if (iy < 0) iy += kEbNy;
+    const int64_t off = ((((int64_t)l * A.ny + n) * A.nx + m) * kEbNy + iy) * kEbNx + ix;
+    const int64_t total = (int64_t)A.nl * A.ny * A.nx * kEbNy * kEbNx;
+    if (off >= 0 && off < total) {
+        unsafeAtomicAdd(A.eb + off, 1.0f);
+        return true;
+    }
+    return false;
+}
+
+// Take branch b (0 or 1) of block B in state `kind` (GRTF:872-882 and every branch body after it): cte / ctm are
+// the branch's exact magnitudes (correctly rounded hypot of E_field_cal's components), dphi its wrapped phase
+// difference (GRTF:145-150) and e its exact efficiency.  Returns the next region, or kDie for a ray that the
+// in-coupler's second branch carries out of the in-coupler.
+template <class Loc>
+__device__ __forceinline__ int take_branch(const Loc &loc, Lane &L, const double *B, int b, int kind, double cte,
+                                           double ctm, double dphi, double e) {
+    Ray &r = L.r;
+    const double *T = L.T;
+    const double norm = sqrt(cte * cte + ctm * ctm);
+    int tir, gap;
+    if (kind == 0) { tir = b == 0 ? 0 : 2; gap = b == 0 ? 0 : 4; }
+    else if (kind <= 2) { tir = b == 0 ? 0 : 1; gap = b == 0 ? 0 : 2; }
+    else { tir = b == 0 ? 1 : 3; gap = b == 0 ? 2 : 6; }
+    r.cos_t = B[b];
+    r.te = cte / norm;
+    r.tm = ctm / norm;
+    r.dph = dphi + T[kTileTir + tir];   // delta_phase = delta_phase_b + lut_TIR[...] (GRTF:877, ...)
+    r.x += T[kTileGap + gap];
+    r.y += T[kTileGap + gap + 1];
+    r.ener = r.ener * e;
+    if (kind == 0) {
+        const bool in_ic = in_poly(loc, locate(loc, r.x, r.y), kPolyIC, r.x, r.y);
+        if (b == 0) return in_ic ? 0 : 2;
+        return in_ic ? 1 : kDie;
+    }
+    if (kind <= 2) return b == 0 ? 2 : 3;
+    return b == 0 ? 4 : 5;
 }
 
 // A coupler interaction: `blk` of the lane's tile, `kind` 0 in-coupler states (entry event,
@@ -198,23 +256,7 @@ __device__ __forceinline__ int interact(const TraceArgs &A, const Loc &loc, Lane
     }
 
     if (b == 2) {  // out-coupling (GRTF:1162-1171, 1231-1240)
-        if (inside_or_on_edge(r.x, r.y, T + kTileEbRect, 4)) {
-            const double xmin = T[kTileEbRange], xmax = T[kTileEbRange + 1];
-            const double ymin = T[kTileEbRange + 2], ymax = T[kTileEbRange + 3];
-            const double dx = (xmax - xmin) / kEbNx, dy = (ymax - ymin) / kEbNy;
-            int64_t ix = (int64_t)floor((r.x - xmin) / dx);
-            int64_t iy = (int64_t)floor((r.y - ymin) / dy);
-            // compiled-numba addressing (GRTF:164): a negative index wraps once, an index
-            // equal to the axis length aliases into the next row; guarded to the buffer
-            if (ix < 0) ix += kEbNx;
-            if (iy < 0) iy += kEbNy;
-            const int64_t off = ((((int64_t)L.l * A.ny + L.n) * A.nx + L.m) * kEbNy + iy) * kEbNx + ix;
-            const int64_t total = (int64_t)A.nl * A.ny * A.nx * kEbNy * kEbNx;
-            if (off >= 0 && off < total) {
-                unsafeAtomicAdd(A.eb + off, 1.0f);
-                L.hit = true;
-            }
-        }
+        if (eyebox_add(A, T, L.l, L.m, L.n, r.x, r.y)) L.hit = true;
         return kDie;
     }
     const Field f = efield(r.te, r.tm, cd, sd, B + kBlockRec + 8 * b);
@@ -222,38 +264,22 @@ __device__ __forceinline__ int interact(const TraceArgs &A, const Loc &loc, Lane
     const double ctm = hypot_cr(f.tm_re, f.tm_im);
     double e = (cte * cte + ctm * ctm) * B[b] / denom;   // exact e_b (GRTF:868-869, 917-918, ...)
     if (entry) e = e * A.n_g;
-    // take the branch (GRTF:872-882 and every branch body after it)
-    const double norm = sqrt(cte * cte + ctm * ctm);
     // E_field_cal's output phase (GRTF:145-150): 0 for a component below 1e-20, wrapped difference
     const double pte = cte >= 1e-20 ? atan2(f.te_im, f.te_re) : 0.0;
     const double ptm = ctm >= 1e-20 ? atan2(f.tm_im, f.tm_re) : 0.0;
-    int tir, gap;
-    if (kind == 0) { tir = b == 0 ? 0 : 2; gap = b == 0 ? 0 : 4; }
-    else if (kind <= 2) { tir = b == 0 ? 0 : 1; gap = b == 0 ? 0 : 2; }
-    else { tir = b == 0 ? 1 : 3; gap = b == 0 ? 2 : 6; }
-    r.cos_t = B[b];
-    r.te = cte / norm;
-    r.tm = ctm / norm;
-    r.dph = wrap_pi(ptm - pte) + T[kTileTir + tir];   // delta_phase = delta_phase_b + lut_TIR[...] (GRTF:877, ...)
-    r.x += T[kTileGap + gap];
-    r.y += T[kTileGap + gap + 1];
-    r.ener = r.ener * e;
-    if (kind == 0) {
-        const bool in_ic = in_poly(loc, locate(loc, r.x, r.y), kPolyIC, r.x, r.y);
-        if (b == 0) return in_ic ? 0 : 2;
-        return in_ic ? 1 : kDie;
-    }
-    if (kind <= 2) return b == 0 ? 2 : 3;
-    return b == 0 ? 4 : 5;
+    return take_branch(loc, L, B, b, kind, cte, ctm, wrap_pi(ptm - pte), e);
 }
 
 // Run a ray through the loop iterations that need no Monte-Carlo interaction -- hops that
 // miss every coupler slice (GRTF:1049-1052, 1102-1108, 1175-1178) and the R3 -> R4 switch
 // -- until the next interaction is due.  Returns that interaction's block index, or kDie
 // when the ray terminated (left eff_reg1 at GRTF:906, R5 miss at GRTF:1244-1246, or
-// range(1e5) exhausted).  Each iteration counts one bounce.
+// range(1e5) exhausted).  Each iteration counts one bounce.  With `hops`, the miss hops made are added to it
+// (the certification shadow turns its Jones state by as many hop phasors; everything is inlined, so the
+// other callers pay nothing for it).
 template <class Loc>
-__device__ __forceinline__ int advance(const TraceArgs &A, const Loc &loc, Lane &L, int &kind) {
+__device__ __forceinline__ int advance(const TraceArgs &A, const Loc &loc, Lane &L, int &kind,
+                                       uint32_t *hops = nullptr) {
     Ray &r = L.r;
     const double *T = L.T;
     // A miss hop's step is fixed by the region: R2 moves by gap[0:2] and adds 2*TIR[0],
@@ -293,26 +319,8 @@ __device__ __forceinline__ int advance(const TraceArgs &A, const Loc &loc, Lane 
         r.x += gx;
         r.y += gy;
         r.dph += tir2;   // delta_phase += 2*lut_TIR[...] (GRTF:1052, 1108, 1178)
+        if (hops) ++*hops;
     }
-}
-
-// Eyebox accumulation of an out-coupling (GRTF:1162-1171, 1231-1240): the per-FoV
-// eyebox rectangle test, the bin, and the atomic; compiled-numba addressing as in interact().
-__device__ __forceinline__ bool eyebox_add(const TraceArgs &A, int l, int m, int n, double x, double y) {
-    const double *T = A.tiles + (int64_t)((l * A.nx + m) * A.ny + n) * A.tile_d;
-    if (!inside_or_on_edge(x, y, T + kTileEbRect, 4)) return false;
-    const double xmin = T[kTileEbRange], xmax = T[kTileEbRange + 1];
-    const double ymin = T[kTileEbRange + 2], ymax = T[kTileEbRange + 3];
-    const double dx = (xmax - xmin) / kEbNx, dy = (ymax - ymin) / kEbNy;
-    int64_t ix = (int64_t)floor((x - xmin) / dx);
-    int64_t iy = (int64_t)floor((y - ymin) / dy);
-    if (ix < 0) ix += kEbNx;
-    if (iy < 0) iy += kEbNy;
-    const int64_t off = ((((int64_t)l * A.ny + n) * A.nx + m) * kEbNy + iy) * kEbNx + ix;
-    const int64_t total = (int64_t)A.nl * A.ny * A.nx * kEbNy * kEbNx;
-    if (off < 0 || off >= total) return false;
-    unsafeAtomicAdd(A.eb + off, 1.0f);
-    return true;
 }
 
 template <class LaneT>

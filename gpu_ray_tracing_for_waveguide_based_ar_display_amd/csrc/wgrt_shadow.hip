@@ -25,7 +25,14 @@
 // the product lane would leave uncertain (replayed), and "silent flips": decisions the product
 // lane would certify although they differ from the reference's -- which must never happen.  The ray always
 // follows the reference's decision, so its final RNG state and bounce count are the reference's
-// (tests compare them with the CPU oracle).
+// (tests compare them with the CPU oracle and with variant 1).
+//
+// Who runs what: the decision (every branch's ref_efield, the draw, the comparison) and the product lane's
+// view of it are this file's, literal on purpose where the exact lane's interact() estimates first.  The ray
+// load, the taken branch's body, the walk to the next interaction and the retire are the exact lane's own
+// lane_load / take_branch / advance / lane_retire (wgrt_exact_lane.h), the functions variant 1 and every
+// replay run, so what the shadow certifies against is that arithmetic.  wgrt_debug_shadow takes its
+// arguments from the launch path's scene_ray_args and NULL-column check (wgrt_launch_args.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -36,7 +43,7 @@
 #include "wgrt_common.h"
 #include "wgrt_exact_lane.h"
 #include "wgrt_jones_lane.h"
-#include "wgrt_scene.h"
+#include "wgrt_launch_args.h"
 
 using namespace wgrt;
 
@@ -90,34 +97,29 @@ __device__ __forceinline__ RefField ref_efield(double Ete, double Etm, double dp
     return o;
 }
 
+// One ray on the exact lane (wgrt_exact_lane.h: lane_load, take_branch, advance, lane_retire -- the functions
+// variant 1 and the replays run), around the shadow's own decision: every branch's literal E_field_cal, and the
+// product lane's view of the same draw.
 template <class Loc>
 __device__ void shadow_trace(const TraceArgs &A, const Loc &loc, int64_t i, ShadowAcc &acc) {
-    // ---- load (GRTF:842-859) ----
-    const int m = (int)A.m[i], n = (int)A.n[i], l = A.l ? (int)A.l[i] : 0;
-    if (!(m >= 0 && m < A.nx && n >= 0 && n < A.ny && l >= 0 && l < A.nl)) return;
-    const int64_t g = (int64_t)((l * A.nx + m) * A.ny + n);
-    const double *T = A.tiles + g * A.tile_d;     // exact tile (reference arithmetic)
-    const double *J = A.jtiles + g * A.jtile_d;   // Jones tile (product lane)
-    const int64_t gid = A.gid_offset + i;
-    double x = (double)A.x[i], y = (double)A.y[i];
-    double Ete = (double)A.te[i], Etm = (double)A.tm[i], dph = (double)A.dph[i];
-    double cos_th = 1.0, ener = 1.0;
-    uint32_t s = A.rng[i];
-    uint32_t bounces = 1;
-    int region = 0;
+    Lane L;
+    if (!lane_load(A, i, L)) return;
+    Ray &r = L.r;
+    const double *T = L.T;                                                                    // exact tile
+    const double *J = A.jtiles + (int64_t)((L.l * A.nx + L.m) * A.ny + L.n) * A.jtile_d;   // Jones tile
     // Jones-vector state (te_in = Ete, tm_in = phase * Etm, GRTF:136-138)
     JRay jr{};
     {
         double sd = 0.0, cd = 1.0;
-        if (A.dph[i] != 0.0f) sincos(dph, &sd, &cd);
-        jr.er = Ete;
+        if (A.dph[i] != 0.0f) sincos(r.dph, &sd, &cd);
+        jr.er = r.te;
         jr.ei = 0.0;
-        jr.mr = cd * Etm;
-        jr.mi = sd * Etm;
+        jr.mr = cd * r.tm;
+        jr.mi = sd * r.tm;
         jr.amp = 1.0f;
     }
     double jener = 1.0, eerr = 0.0;
-    uint32_t hops = 0;
+    uint32_t hops = 0;   // miss hops since the last interaction (advance)
     const double t = A.threshold;
     int blk = 0, kind = 0;
     bool entry = true;
@@ -126,10 +128,10 @@ __device__ void shadow_trace(const TraceArgs &A, const Loc &loc, int64_t i, Shad
         const double *B = T + kTileHeader + kBlock * blk;
         const double *JB = J + kJHeader + kJBlock * blk;
         const bool three = kind >= 3, thr = kind >= 1;
-        const double denom = entry ? T[kTileCosIc1] : cos_th;
+        const double denom = entry ? T[kTileCosIc1] : r.cos_t;
         RefField E[3];
         E[2] = RefField{0.0, 0.0, 0.0};
-        for (int k = 0; k < (three ? 3 : 2); ++k) E[k] = ref_efield(Ete, Etm, dph, B + kBlockRec + 8 * k);
+        for (int k = 0; k < (three ? 3 : 2); ++k) E[k] = ref_efield(r.te, r.tm, r.dph, B + kBlockRec + 8 * k);
         double e0 = (E[0].te * E[0].te + E[0].tm * E[0].tm) * B[0] / denom;
         double e1 = (E[1].te * E[1].te + E[1].tm * E[1].tm) * B[1] / denom;
         if (entry) {
@@ -137,16 +139,16 @@ __device__ void shadow_trace(const TraceArgs &A, const Loc &loc, int64_t i, Shad
             e1 = e1 * A.n_g;
         }
         const double e2 = three ? (E[2].te * E[2].te + E[2].tm * E[2].tm) * B[2] / denom / A.n_g : 0.0;
-        const double u = rng_draw(s, gid);
+        const double u = rng_draw_lazy(r.s, [&]() { return ray_gid(A, L.i); });   // interact()'s draw
         int b;   // the reference's decision: 0, 1, 2 (out-coupling) or -1 (dies)
-        if (u <= e0 && (!thr || ener * e0 > t)) b = 0;
-        else if (u <= e0 + e1 && (!thr || ener * e1 > t)) b = 1;
-        else if (three && u <= e0 + e1 + e2 && ener * e2 > t) b = 2;
+        if (u <= e0 && (!thr || r.ener * e0 > t)) b = 0;
+        else if (u <= e0 + e1 && (!thr || r.ener * e1 > t)) b = 1;
+        else if (three && u <= e0 + e1 + e2 && r.ener * e2 > t) b = 2;
         else b = -1;
 
         // ---- the product lane's view of the same decision (wgrt_jones_lane.h interact) ----
         {
-            const double2 hp = *(const double2 *)(J + kJHop + (region == 2 ? 0 : 2));
+            const double2 hp = *(const double2 *)(J + kJHop + (r.region == 2 ? 0 : 2));
             for (uint32_t h = 0; h < hops; ++h) {
                 const double mr = jr.mr;
                 jr.mr = fma(mr, hp.x, -jr.mi * hp.y);
@@ -156,10 +158,10 @@ __device__ void shadow_trace(const TraceArgs &A, const Loc &loc, int64_t i, Shad
             double growth, cos_ic1;
             bool amp_blk;
             const double4 cw = block_cw(JB, entry, growth, cos_ic1, amp_blk);
-            const double jden = entry ? cos_ic1 : cos_th;
+            const double jden = entry ? cos_ic1 : r.cos_t;
             const double inv = rcp_nr(jden);
             const double f01 = entry ? A.n_g : 1.0;
-            const double nb = (double)bounces * 0.01;
+            const double nb = (double)L.bounces * 0.01;
             const double en2 = fma(jr.er, jr.er, fma(jr.ei, jr.ei, fma(jr.mr, jr.mr, jr.mi * jr.mi)));
             const double grow = fma(nb * nb, growth, 1.0) * (double)jr.amp;
             const double base = grow * fabs(inv) * fmax(en2, 1.0);
@@ -180,7 +182,7 @@ __device__ void shadow_trace(const TraceArgs &A, const Loc &loc, int64_t i, Shad
             jones_decide(d64, u, A.cert_tol * base, JB, cw.w, three, thr, t, jener, eerr);
             const double r32 = ratio(d32, A.cert_tol32 * base), r64 = ratio(d64, A.cert_tol * base);
             if (thr && t != 0.0) {   // the ener guard's tracked relative error against the reference's ener
-                const double er = fabs(jener / ener - 1.0) / (eerr + 1e-15);
+                const double er = fabs(jener / r.ener - 1.0) / (eerr + 1e-15);
                 acc.max_ener = fmax(acc.max_ener, er);
             }
             // the product lane's decision: the single-precision one, else the double-precision one
@@ -192,7 +194,7 @@ __device__ void shadow_trace(const TraceArgs &A, const Loc &loc, int64_t i, Shad
             else if (bj != b) ++acc.flips;
             acc.max_ratio = fmax(acc.max_ratio, r64);
             acc.max_ratio32 = fmax(acc.max_ratio32, r32);
-            const int db = depth_bucket(bounces);
+            const int db = depth_bucket(L.bounces);
             acc.max_depth[db] = fmax(acc.max_depth[db], r32);
             ++acc.n_depth[db];
             ++acc.hist[hist_bucket(r32)];
@@ -220,77 +222,15 @@ __device__ void shadow_trace(const TraceArgs &A, const Loc &loc, int64_t i, Shad
             }
         }
         if (b < 0 || b == 2) break;   // dies, or out-couples (GRTF:1162-1171, 1231-1240): the trace ends
-
-        // ---- take branch b (GRTF:872-882 and every branch body after it) ----
-        int tir, gap;
-        if (kind == 0) { tir = b == 0 ? 0 : 2; gap = b == 0 ? 0 : 4; }
-        else if (kind <= 2) { tir = b == 0 ? 0 : 1; gap = b == 0 ? 0 : 2; }
-        else { tir = b == 0 ? 1 : 3; gap = b == 0 ? 2 : 6; }
-        const RefField &Eb = E[b];
-        cos_th = B[b];
-        const double norm = sqrt(Eb.te * Eb.te + Eb.tm * Eb.tm);
-        Ete = Eb.te / norm;
-        Etm = Eb.tm / norm;
-        dph = Eb.dphi + T[kTileTir + tir];
-        x += T[kTileGap + gap];
-        y += T[kTileGap + gap + 1];
-        ener *= b == 0 ? e0 : e1;
-        int next;
-        if (kind == 0) {
-            const bool in_ic = in_poly(loc, locate(loc, x, y), kPolyIC, x, y);
-            next = b == 0 ? (in_ic ? 0 : 2) : (in_ic ? 1 : kDie);
-        } else if (kind <= 2) {
-            next = b == 0 ? 2 : 3;
-        } else {
-            next = b == 0 ? 4 : 5;
-        }
+        const int next = take_branch(loc, L, B, b, kind, E[b].te, E[b].tm, E[b].dphi, b == 0 ? e0 : e1);
         if (next < 0) break;
-        region = next;
+        r.region = next;
         entry = false;
-
-        // ---- loop iterations up to the next interaction (GRTF:905-1246) ----
-        const int hg = region == 2 ? 0 : 2;   // miss hop: gap[0:2] + 2 TIR[0] in R2, gap[2:4] + 2 TIR[1] in R3 / R4
-        blk = -1;
-        for (;;) {
-            if (bounces > (uint32_t)kMaxLoop) break;
-            ++bounces;
-            const Cell c = locate(loc, x, y);
-            if (!in_poly(loc, c, kPolyEff1, x, y)) break;
-            if (region <= 1) {
-                kind = 0;
-                blk = 1 + region;
-                break;
-            }
-            if (region <= 3) {
-                const int sl = first_slice(loc, c, kPolyFC0, A.nfc, x, y);
-                if (sl >= 0) {
-                    kind = region - 1;
-                    blk = 3 + (region - 2) * A.nfc + sl;
-                    break;
-                }
-                if (region == 3 && !in_poly(loc, c, kPolyEff2, x, y)) {
-                    region = 4;   // GRTF:1103-1104
-                    continue;
-                }
-            } else {
-                const int sl = first_slice(loc, c, kPolyFC0 + A.nfc, A.noc, x, y);
-                if (sl >= 0) {
-                    kind = region - 1;
-                    blk = 3 + 2 * A.nfc + (region - 4) * A.noc + sl;
-                    break;
-                }
-                if (region == 5) break;   // GRTF:1244-1246
-            }
-            x += T[kTileGap + hg];
-            y += T[kTileGap + hg + 1];
-            dph += 2 * T[kTileTir + hg / 2];
-            ++hops;
-        }
+        blk = advance(A, loc, L, kind, &hops);   // the loop iterations up to the next interaction
         if (blk < 0) break;
     }
-    A.rng[i] = s;
-    if (A.per_ray) A.per_ray[i] = bounces;
-    acc.bounces += bounces;
+    lane_retire(A, L);
+    acc.bounces += L.bounces;
 }
 
 __device__ __forceinline__ double wave_max(double v) {
@@ -346,38 +286,15 @@ extern "C" wgrt_status wgrt_debug_shadow(const wgrt_scene *s, const wgrt_rays *r
     if (single && s->nl != 1)
         return fail(WGRT_ERR_INVALID_ARGUMENT, "single-wavelength shadow needs a scene built with num_lmd == 1");
     if (n_rays == 0) return WGRT_OK;
-    if (!rays->x || !rays->y || !rays->m || !rays->n || (!single && !rays->lmd_num) || !rays->te || !rays->tm ||
-        !rays->delta_phase || !rng_states)
+    if (!ray_columns_present(rays, single != 0) || !rng_states)
         return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL ray column / rng_states");
     ShadowArgs S{};
     TraceArgs &A = S.A;
-    A.x = rays->x;
-    A.y = rays->y;
-    A.m = rays->m;
-    A.n = rays->n;
-    A.l = single ? nullptr : rays->lmd_num;
-    A.te = rays->te;
-    A.tm = rays->tm;
-    A.dph = rays->delta_phase;
+    A = scene_ray_args(s, rays, single != 0);   // with the bounds the product lane uses by default
     A.rng = rng_states;
     A.per_ray = per_ray_bounces;
     A.n_rays = n_rays;
     A.gid_offset = gid_offset;
-    A.tiles = s->d_tiles;
-    A.jtiles = s->d_jtiles;
-    A.tile_d = s->tile_d;
-    A.jtile_d = s->jtile_d;
-    A.loc = make_locator(s);
-    A.nfc = s->nfc;
-    A.noc = s->noc;
-    A.nx = s->nx;
-    A.ny = s->ny;
-    A.nl = s->nl;
-    A.n_g = s->n_g;
-    A.inv_n_g = 1.0 / s->n_g;
-    A.threshold = single ? 1e-15 : 0.0;
-    A.cert_tol = kCertTol;   // the bounds the product lane uses by default
-    A.cert_tol32 = std::max(kCertTol32, A.cert_tol);
     S.out = stats;
     DEVICE_SCOPE(dev_scope, s->device);   // launched on the scene's device; the caller's is restored
     const int64_t blocks = std::min<int64_t>((n_rays + 255) / 256, 16384);

@@ -11,9 +11,11 @@
 // and one set of 64-bit stats atomics per wave.
 //
 // Two lanes implement the reference's per-ray state machine (R0..R5):
-//   * the exact lane (variant 1, the replay kernel, the diagnostic shadow): the reference's
-//     float64 arithmetic in its expression order (E_field_cal with correctly rounded hypot,
-//     GRTF:132-152), compiled with -ffp-contract=off;
+//   * the exact lane (wgrt_exact_lane.h, the one statement of it): the reference's float64 arithmetic in
+//     its expression order (E_field_cal with correctly rounded hypot, GRTF:132-152), compiled with
+//     -ffp-contract=off.  trace_one runs it here for variant 1 (trace_grid_kernel) and the replays
+//     (replay_tail, epilogue_kernel), and bin_entry bins the out-coupling queue through its eyebox_add;
+//     the certification shadow (wgrt_shadow.hip) runs the same functions around its own decision;
 //   * the Jones-vector lane (variants 7 / 9, the product path): the same decisions from the
 //     field carried as a complex Jones vector, each certified against a bound on the
 //     difference to the exact arithmetic; an uncertain decision abandons the ray, which the
@@ -34,8 +36,8 @@
 #include "wgrt_common.h"
 #include "wgrt_exact_lane.h"
 #include "wgrt_jones_lane.h"
+#include "wgrt_launch_args.h"
 #include "wgrt_order.h"
-#include "wgrt_scene.h"
 
 using namespace wgrt;
 
@@ -111,7 +113,7 @@ static_assert(kQBlock >= 1 && kQBlock <= 64, "a queue block is binned by one lan
 __device__ __forceinline__ bool bin_entry(const TraceArgs &A, uint32_t g, int nx, int ny, double x, double y) {
     const int n = (int)(g % (uint32_t)ny), m = (int)(g / (uint32_t)ny % (uint32_t)nx);
     const int l = (int)(g / ((uint32_t)ny * (uint32_t)nx));
-    return eyebox_add(A, l, m, n, x, y);
+    return eyebox_add(A, A.tiles + (int64_t)((l * A.nx + m) * A.ny + n) * A.tile_d, l, m, n, x, y);
 }
 
 __global__ __launch_bounds__(256) void epilogue_kernel(TraceArgs A) {
@@ -1120,8 +1122,7 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
                 (dbg->timeline && dbg->timeline_waves < 0)))
         return fail(WGRT_ERR_INVALID_ARGUMENT, "bad wgrt_debug_opts");
     if (n_rays == 0) return WGRT_OK;
-    if (!rays->x || !rays->y || !rays->m || !rays->n || (!single && !rays->lmd_num) || !rays->te || !rays->tm ||
-        !rays->delta_phase || !rng_states || !matrix_EB)
+    if (!ray_columns_present(rays, single) || !rng_states || !matrix_EB)
         return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL ray column / rng_states / matrix_EB");
     if (c.variant == 7 && !s->d_cells32) return fail(WGRT_ERR_UNSUPPORTED, "variant 7 needs <= 16 polygons");
     if (c.variant >= 7 && n_rays > 0xffffffffll)
@@ -1139,25 +1140,14 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
     return WGRT_OK;
 }
 
-// Step 2: the launch arguments that come from the scene, the rays and the options (the launch scratch's
-// are added once it is sized: dispatch).  single: the single-wavelength kernel process_rays_kernel_pro
-// (GRTF:419-831) -- no lmd_num column, wavelength 0 of a one-wavelength scene, threshold 1e-15; otherwise
-// process_rays_kernel_pro_fullColor (GRTF:833-1246), threshold 0.  The two kernels differ in nothing else.
+// Step 2: the launch arguments: the scene's and the rays' (scene_ray_args, wgrt_launch_args.h) and the
+// options' (the launch scratch's are added once it is sized: dispatch).
 TraceArgs fill_args(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
                     uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats, uint32_t *per_ray_bounces,
                     const LaunchCfg &c) {
     const wgrt_debug_opts *dbg = c.dbg;
-    TraceArgs A{};
-    A.x = rays->x;
-    A.y = rays->y;
-    A.m = rays->m;
-    A.n = rays->n;
-    A.l = c.single ? nullptr : rays->lmd_num;
-    A.threshold = c.single ? 1e-15 : 0.0;
+    TraceArgs A = scene_ray_args(s, rays, c.single);
     A.order = c.chunk_order;   // a permutation of the 64-ray chunks (trusted device data)
-    A.te = rays->te;
-    A.tm = rays->tm;
-    A.dph = rays->delta_phase;
     A.rng = rng_states;
     A.eb = matrix_EB;
     A.stats = stats;
@@ -1166,23 +1156,11 @@ TraceArgs fill_args(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, 
     A.gid_offset = gid_offset;
     A.gid_blocks = c.gid_blocks;
     A.gid_block_rays = c.gid_blocks ? c.gid_block_rays : 1;
-    A.tiles = s->d_tiles;
-    A.loc = make_locator(s);
-    A.tile_d = s->tile_d;
-    A.nfc = s->nfc;
-    A.noc = s->noc;
-    A.nx = s->nx;
-    A.ny = s->ny;
-    A.nl = s->nl;
-    A.n_g = s->n_g;
-    A.inv_n_g = 1.0 / s->n_g;
-    A.cert_tol = (dbg && dbg->cert_tol > 0.0) ? dbg->cert_tol : kCertTol;
-    // raising the double bound raises this one too
-    A.cert_tol32 = std::max((dbg && dbg->cert_tol32 > 0.0) ? dbg->cert_tol32 : kCertTol32, A.cert_tol);
+    if (dbg && dbg->cert_tol > 0.0) A.cert_tol = dbg->cert_tol;
+    if (dbg && dbg->cert_tol32 > 0.0) A.cert_tol32 = dbg->cert_tol32;
+    A.cert_tol32 = std::max(A.cert_tol32, A.cert_tol);   // raising the double bound raises this one too
     A.timeline = c.timeline ? dbg->timeline : nullptr;
     A.timeline_waves = c.timeline ? dbg->timeline_waves : 0;
-    A.jtiles = s->d_jtiles;
-    A.jtile_d = s->jtile_d;
     A.n_iter = 1;
     return A;
 }

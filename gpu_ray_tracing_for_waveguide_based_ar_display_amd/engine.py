@@ -150,10 +150,9 @@ def _debug_opts(debug: dict | None):
     return d
 
 
-def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
-           workgroups, single, chunk_order=None, num_iter=1, gid_blocks=None, gid_block_rays=0, debug=None,
-           grid_sqrt_k=0.0):
-    device = torch.device("cuda", scene.device)
+def _read_columns(rays, rng_states, n_rays, single, device):
+    """The columns a launch reads (READ_COLUMNS, no ``lmd_num`` for a single-wavelength scene), validated
+    together with ``rng_states`` and the ray count: ``(cols, N)``.  ``_trace`` and ``shadow`` share it."""
     x = rays["x"]
     N = x.numel() if n_rays is None else int(n_rays)
     if N < 0 or N > x.numel():
@@ -168,6 +167,15 @@ def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ra
     if rng_states.dtype not in (torch.int32, torch.uint32):
         raise TypeError(f"rng_states must be uint32 (or an int32 view), got {rng_states.dtype}")
     _as_dev(rng_states, rng_states.dtype, "rng_states", device, x.numel())
+    return cols, N
+
+
+def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
+           workgroups, single, chunk_order=None, num_iter=1, gid_blocks=None, gid_block_rays=0, debug=None,
+           grid_sqrt_k=0.0):
+    device = torch.device("cuda", scene.device)
+    cols, N = _read_columns(rays, rng_states, n_rays, single, device)
+    x = cols["x"]
     _as_dev(matrix_EB, torch.float32, "matrix_EB", device)
     if tuple(matrix_EB.shape) != scene.eb_shape():
         raise ValueError(f"matrix_EB shape {tuple(matrix_EB.shape)} != {scene.eb_shape()}")
@@ -331,12 +339,8 @@ def shadow(scene: Scene, rays: dict, rng_states: torch.Tensor, gid_offset: int =
     ``rng_states`` / ``per_ray_bounces`` are updated as one exact launch would.  Synchronous;
     returns the statistics as a dict (``max_ratio``, ``silent_flips``, ``uncertain``, ...)."""
     device = torch.device("cuda", scene.device)
-    x = rays["x"]
-    N = x.numel() if n_rays is None else int(n_rays)
     single = scene.single_lambda
-    cols = {k: _as_dev(rays[k], torch.float32, k, device, x.numel()) for k in READ_COLUMNS
-            if not (single and k == "lmd_num")}
-    _as_dev(rng_states, rng_states.dtype, "rng_states", device, x.numel())
+    cols, N = _read_columns(rays, rng_states, n_rays, single, device)
     r = Rays(**{k: ctypes.c_void_p(v.data_ptr()) for k, v in cols.items()})
     nbytes = ctypes.sizeof(_lib.ShadowStats)
     buf = torch.zeros(nbytes // 8, dtype=torch.int64, device=device)
