@@ -23,12 +23,12 @@ sum-reduce of the grid (the north star's single RCCL reduce of the eyebox over x
 Collective.  Each rank writes only the eyebox slabs ``EB[l, n, m]`` of its own blocks, plus --
 through the compiled-numba flat-offset aliasing of an out-coupling exactly on the eyebox edge
 (GRTF:154-165) -- the first ``SPILL`` floats of the slab after one of its own.
-``collect_eyebox`` gathers exactly those bytes to rank 0 (``gather``: each rank sends
-``nb x (9600 + SPILL)`` floats, 1/N of the grid, over its own xGMI link) and rank 0 assembles the
-grid; ``reduce`` is the plain sum-reduce of the whole grid (50.8 MB at 21x21).  Eyebox values are
-integer counts, so both reproduce the single-GPU grid exactly.  That is the only collective on
-the path.  A job that wants only the efficiencies and the evaluation moves no slabs at all:
-``EyeboxReduce`` sum-reduces each rank's per-slab window sums (57 float64 per slab), again exactly.
+``EyeboxGather`` gathers exactly those bytes to rank 0 (each rank sends ``nb x (9600 + SPILL)`` floats,
+1/N of the grid, over its own xGMI link) and rank 0 assembles the grid; ``reduce_eyebox`` is the plain
+sum-reduce of the whole grid (50.8 MB at 21x21).  Eyebox values are integer counts, so both reproduce the
+single-GPU grid exactly.  That is the only collective on the path.  A job that wants only the efficiencies
+and the evaluation moves no slabs at all: ``EyeboxReduce`` sum-reduces each rank's per-slab window sums (57
+float64 per slab), again exactly.  All three take their slab indices from one ``SlabPlan``.
 
 The tracer is pluggable (``trace_fn(rays, rng, eb, gid, num_iter)``, ``gid`` a ``GidMap``) so the
 same sharding / stepping / collection code runs with the HIP kernel in production (``bench.py``,
@@ -37,10 +37,11 @@ the reference-flow driver) and with the CPU oracle in the multi-process CPU test
 from __future__ import annotations
 
 from dataclasses import dataclass, field
+from types import SimpleNamespace
 
 import numpy as np
 
-from ._lib import STAT
+from ._lib import STAT, check, load
 
 MAX_TRACES_PER_CALL = 255   # wgrt_launch_opts.num_iter
 EB_SLAB = 80 * 120          # one (wavelength, FoV) slab of matrix_EB (MAIN:37)
@@ -207,85 +208,96 @@ def _world(group):
     return dist.get_world_size(group) if dist.is_initialized() else 1
 
 
+def _operands(group, *tensors, scratch: bool = False):
+    """What a collective is handed for ``tensors``: the tensors themselves, except under gloo (the CPU tests, the
+    one-GPU rehearsals), which moves host tensors only and whose reduce leaves partial sums in the other ranks'
+    operands: there a device tensor goes as a host copy and a host tensor the collective may overwrite
+    (``scratch``) as a clone.  The caller copies a result back where it was handed a copy."""
+    import torch.distributed as dist
+    if dist.get_backend(group) != "gloo":
+        return tensors
+    return tuple(t.cpu() if t.is_cuda else t.clone() if scratch else t for t in tensors)
+
+
 def reduce_eyebox(eb, group=None, dst: int = 0):
-    """Sum-reduce the eyebox grid to ``dst`` (exact: integer counts in float32 < 2**24)."""
+    """Sum-reduce the eyebox grid (or ``EyeboxReduce``'s table) to rank ``dst``, in place there; every other rank's
+    tensor stays as it was.  Exact: integer counts, in float32 below 2**24."""
     import torch.distributed as dist
     if _world(group) > 1:
-        if getattr(eb, "is_cuda", False) and dist.get_backend(group) == "gloo":
-            # gloo reduces device tensors only as an all-reduce (the bench's one-GPU rehearsal)
-            dist.all_reduce(eb, op=dist.ReduceOp.SUM, group=group)
-        else:
-            dist.reduce(eb, dst=dst, op=dist.ReduceOp.SUM, group=group)
+        at_dst = dist.get_rank(group) == dst
+        buf, = _operands(group, eb, scratch=not at_dst)
+        dist.reduce(buf, dst=dst, op=dist.ReduceOp.SUM, group=group)
+        if at_dst and buf is not eb:
+            eb.copy_(buf)
     return eb
+
+
+class SlabPlan:
+    """One block assignment's index sets (``all_blocks[r]``: global block ids of rank r), computed once in numpy.
+
+    Two per rank r: ``slabs[r]``, the eyebox slab of each of its blocks in block order (not ascending), and
+    ``spill[r]``, whether that slab's spill must travel -- it lands in slab s + 1 and moves unless s + 1 is the
+    rank's own slab (then it is in that slab's copy already) or past the grid (dropped, as the kernel's guard
+    drops it).  The rest follows from them: ``nxt`` (where a row's spill is read, clamped to the grid),
+    ``spill_rows`` / ``spill_dst`` (the payload rows with a spill, the slabs they add to), ``rows`` (every slab
+    the rank can have written: its own, then the spill targets that are not, no slab twice), ``unowned`` (slabs
+    of no rank), and ``wgrt_eyebox_assemble``'s flat row maps: payload row j of rank r goes to slab
+    ``dst_rows[r * nb + j]`` and its spill adds to ``spill_dst_rows[r * nb + j]``, -1 for none."""
+
+    def __init__(self, all_blocks, num_fov_x: int, num_fov_y: int, lambdas, n_lambda_scene: int):
+        n = self.n_slabs = n_lambda_scene * num_fov_y * num_fov_x
+        self.world = len(all_blocks)
+        self.slabs = [slab_ids(b, num_fov_x, num_fov_y, lambdas) for b in all_blocks]
+        self.spill = [~np.isin(s + 1, s) & (s + 1 < n) for s in self.slabs]
+        self.counts = [len(s) for s in self.slabs]
+        self.nb = max(self.counts)
+        self.has_spill = [bool(m.any()) for m in self.spill]
+        self.nxt = [np.minimum(s + 1, n - 1) for s in self.slabs]
+        self.spill_rows = [np.nonzero(m)[0] for m in self.spill]
+        self.spill_dst = [s[m] + 1 for s, m in zip(self.slabs, self.spill)]
+        self.rows = [np.concatenate([s, d]) for s, d in zip(self.slabs, self.spill_dst)]
+        self.unowned = np.setdiff1d(np.arange(n), np.concatenate(self.slabs))
+        dst = np.full((2, self.world, self.nb), -1, dtype=np.int64)
+        for r, s in enumerate(self.slabs):
+            dst[0, r, :len(s)] = s
+            dst[1, r, self.spill_rows[r]] = self.spill_dst[r]
+        self.dst_rows, self.spill_dst_rows = dst[0].reshape(-1), dst[1].reshape(-1)
+        self.tensors = {}
+
+    def on(self, device):
+        """The plan as tensors on ``device`` (int64; ``spill`` as the float32 factor the pack multiplies by),
+        uploaded on first use and kept in ``tensors``: the indices live where the grid they index lives."""
+        import torch
+        key = str(device)
+        if key not in self.tensors:
+            t = lambda a, dt=torch.int64: torch.as_tensor(a, dtype=dt, device=device)
+            per_rank = ("slabs", "nxt", "spill_rows", "spill_dst", "rows")
+            self.tensors[key] = SimpleNamespace(
+                spill=[t(m, torch.float32) for m in self.spill], unowned=t(self.unowned), dst_rows=t(self.dst_rows),
+                spill_dst_rows=t(self.spill_dst_rows), **{k: [t(a) for a in getattr(self, k)] for k in per_rank})
+        return self.tensors[key]
 
 
 class EyeboxGather:
     """Gather of each rank's own eyebox slabs (+ their spill) to rank 0, and the assembly there.
 
-    ``all_blocks[r]``: global block ids of rank r (every rank knows the whole assignment, so
-    the message sizes and placements need no exchange).  A rank's payload is one flat buffer,
-    ``[nb x 9600 slab floats | nb x SPILL spill floats, padded to 4]`` (include/wgrt.h
-    wgrt_eyebox_*), padded to the largest shard (the collective needs equal sizes).  The send buffer
-    and rank 0's receive buffer are allocated once (first call per device and dtype) and reused;
-    every index is precomputed on the host here, so a call makes no host round trip before the
-    collective.  On a HIP device the pack and the assembly are the library's row-copy kernels
-    (``wgrt_eyebox_pack`` / ``wgrt_eyebox_assemble``: one launch each, 16-B loads and stores, each
-    owned slab written once from the rank that traced it); host tensors (the gloo CPU tests) take the
-    same steps as torch gathers and scatters.  Slabs no rank owns are zeroed, spills added last."""
+    Every rank knows the whole assignment (``SlabPlan``), so the message sizes and placements need no exchange.
+    A rank's payload is one flat buffer, ``[nb x 9600 slab floats | nb x SPILL spill floats, padded to 4]``
+    (include/wgrt.h wgrt_eyebox_*), padded to the largest shard (the collective needs equal sizes).  The send
+    buffer and rank 0's receive buffer are allocated once (first call per device and dtype) and reused, and the
+    plan's tensors are uploaded once per device (``device=``: up front), so a call makes no host round trip before
+    the collective.  On a HIP device a contiguous float32 grid is packed and assembled by the library's row-copy
+    kernels (``wgrt_eyebox_pack`` / ``wgrt_eyebox_assemble``: one launch each, 16-B loads and stores, each owned
+    slab written once from the rank that traced it); any other tensor takes the same steps as torch gathers and
+    scatters on its own device.  Slabs no rank owns are zeroed, spills added last."""
 
     def __init__(self, all_blocks, num_fov_x: int, num_fov_y: int, lambdas, n_lambda_scene: int, device=None):
-        import torch
-        self.n_slabs = n_lambda_scene * num_fov_y * num_fov_x
-        self.world = len(all_blocks)
-        self.nb = max(len(b) for b in all_blocks)
-        self.spill_len = (self.nb * SPILL + 3) // 4 * 4
-        self.payload_len = self.nb * EB_SLAB + self.spill_len
-        self.device = device
-        t = lambda a, dt=torch.int64: torch.as_tensor(np.asarray(a), dtype=dt, device=device)
-        self.slabs, self.nxt, self.spill_mask, self.spill_rows, self.spill_dst = [], [], [], [], []
-        self.has_spill, self.counts = [], []
-        owned = np.zeros(self.n_slabs, dtype=bool)
-        for b in all_blocks:
-            s = slab_ids(b, num_fov_x, num_fov_y, lambdas)
-            own = set(s.tolist())
-            owned[s] = True
-            # the spill of slab s lands in s + 1; it must travel unless s + 1 is this rank's own
-            # slab (then it is already in that slab's copy) or past the grid (dropped, as the
-            # kernel's guard drops it)
-            sp = np.array([(v + 1) not in own and v + 1 < self.n_slabs for v in s.tolist()], dtype=bool)
-            self.counts.append(len(s))
-            self.slabs.append(t(s))
-            self.nxt.append(t(np.minimum(s + 1, self.n_slabs - 1)))
-            self.spill_mask.append(t(sp, torch.float32))
-            self.spill_rows.append(t(np.nonzero(sp)[0]))
-            self.spill_dst.append(t(s[sp] + 1))
-            self.has_spill.append(bool(sp.any()))
-        self.unowned = t(np.nonzero(~owned)[0])
-        self.any_unowned = bool((~owned).any())
-        # the assembly's row maps (wgrt_eyebox_assemble): payload row j of rank r -> its slab and the slab
-        # its spill row adds to, -1 for padding rows and rows without a spill to move
-        dst = np.full((self.world, self.nb), -1, dtype=np.int64)
-        sdst = np.full((self.world, self.nb), -1, dtype=np.int64)
-        for r, b in enumerate(all_blocks):
-            sl = slab_ids(b, num_fov_x, num_fov_y, lambdas)
-            dst[r, :len(sl)] = sl
-            sp = self.spill_mask[r].cpu().numpy() > 0
-            sdst[r, :len(sl)][sp] = sl[sp] + 1
-        self.dst_rows, self.spill_dst_rows = t(dst.reshape(-1)), t(sdst.reshape(-1))
+        p = self.plan = SlabPlan(all_blocks, num_fov_x, num_fov_y, lambdas, n_lambda_scene)
+        self.n_slabs, self.world, self.nb, self.counts, self.has_spill = p.n_slabs, p.world, p.nb, p.counts, p.has_spill
+        self.payload_len = self.nb * EB_SLAB + (self.nb * SPILL + 3) // 4 * 4
         self._bufs = {}
-        self._dev_idx = {}
-
-    def _idx(self, device):
-        """The index tensors on ``device`` (moved once per device and cached): the HIP kernels take their
-        raw pointers, so they must live on the grid's own device whatever ``device=`` the gather was
-        built with."""
-        key = str(device)
-        if key not in self._dev_idx:
-            mv = lambda v: v.to(device)
-            self._dev_idx[key] = dict(slabs=[mv(v) for v in self.slabs], nxt=[mv(v) for v in self.nxt],
-                                      spill_mask=[mv(v) for v in self.spill_mask], dst_rows=mv(self.dst_rows),
-                                      spill_dst_rows=mv(self.spill_dst_rows), unowned=mv(self.unowned))
-        return self._dev_idx[key]
+        if device is not None:
+            p.on(device)
 
     def buffers(self, device, dtype, dst: bool):
         """(send, recv): the payload buffer and, on the gathering rank, the [world, payload] receive
@@ -304,115 +316,92 @@ class EyeboxGather:
 
     @staticmethod
     def _hip(t) -> bool:
-        return getattr(t, "is_cuda", False) and t.dtype.is_floating_point and t.element_size() == 4
+        return t.is_cuda and t.dtype.is_floating_point and t.element_size() == 4 and t.is_contiguous()
+
+    @staticmethod
+    def _kernel(name: str, eb, *args) -> None:
+        """The library's row-copy kernel ``name`` on grid ``eb``, on torch's current stream of its device."""
+        from .engine import _stream_handle
+        check(getattr(load(), name)(eb.data_ptr(), *args, _stream_handle(eb.device)), name)
 
     def pack(self, eb, rank: int, out=None):
         """Rank ``rank``'s payload, into ``out`` (the collective passes its reused send buffer) or a new
-        zeroed buffer."""
+        zeroed buffer.  ``eb`` may have any layout."""
         import torch
-        flat = eb.reshape(self.n_slabs, EB_SLAB)
         buf = out if out is not None else torch.zeros(self.payload_len, dtype=eb.dtype, device=eb.device)
         n = self.counts[rank]
-        if self._hip(eb) and eb.is_contiguous():
-            from ._lib import check, load
-            from .engine import _stream_handle
+        ix = self.plan.on(eb.device)
+        if self._hip(eb):
             if buf.device != eb.device or not buf.is_contiguous() or buf.numel() < self.payload_len:
                 raise ValueError("EyeboxGather.pack: out must be a contiguous payload buffer on the grid's device")
-            ix = self._idx(eb.device)
-            check(load().wgrt_eyebox_pack(eb.data_ptr(), self.n_slabs, ix["slabs"][rank].data_ptr(),
-                                          ix["nxt"][rank].data_ptr(), ix["spill_mask"][rank].data_ptr(), n, self.nb,
-                                          buf.data_ptr(), _stream_handle(eb.device)), "wgrt_eyebox_pack")
+            self._kernel("wgrt_eyebox_pack", eb, self.n_slabs, ix.slabs[rank].data_ptr(), ix.nxt[rank].data_ptr(),
+                         ix.spill[rank].data_ptr(), n, self.nb, buf.data_ptr())
             return buf
+        flat = eb.reshape(self.n_slabs, EB_SLAB)
         main, spill = self._views(buf)
-        torch.index_select(flat, 0, self.slabs[rank], out=main[:n])
+        torch.index_select(flat, 0, ix.slabs[rank], out=main[:n])
         if self.has_spill[rank]:
-            torch.index_select(flat[:, :SPILL], 0, self.nxt[rank], out=spill[:n])
-            spill[:n].mul_(self.spill_mask[rank].to(eb.dtype)[:, None])
+            torch.index_select(flat[:, :SPILL], 0, ix.nxt[rank], out=spill[:n])
+            spill[:n].mul_(ix.spill[rank].to(eb.dtype)[:, None])
         return buf
 
     def assemble(self, eb, parts) -> None:
-        """Rank 0: rebuild the whole grid in ``eb`` from every rank's payload (``parts[r]``: rank r's
-        flat payload; on a HIP device ``parts`` may be the [world, payload] receive buffer itself)."""
-        flat = eb.reshape(self.n_slabs, EB_SLAB)
-        ix = self._idx(eb.device)
-        if self.any_unowned:
-            flat.index_fill_(0, ix["unowned"], 0)
-        recv = parts if hasattr(parts, "shape") else None
-        if self._hip(eb) and eb.is_contiguous():
-            import torch
-            if recv is None or not recv.is_contiguous():
-                recv = torch.stack(list(parts)) if not hasattr(parts, "shape") else parts.contiguous()
-            if recv.device != eb.device:
-                recv = recv.to(eb.device)
-            from ._lib import check, load
-            from .engine import _stream_handle
-            check(load().wgrt_eyebox_assemble(eb.data_ptr(), self.n_slabs, recv.data_ptr(), self.world, self.nb,
-                                              ix["dst_rows"].data_ptr(), ix["spill_dst_rows"].data_ptr(),
-                                              _stream_handle(eb.device)), "wgrt_eyebox_assemble")
+        """Rank 0: rebuild the whole grid in ``eb`` (contiguous: it is written in place) from every rank's
+        payload (``parts[r]``: rank r's flat payload; ``parts`` may be the [world, payload] receive buffer)."""
+        import torch
+        if not eb.is_contiguous():
+            raise ValueError("EyeboxGather.assemble: the grid must be contiguous (it is written in place)")
+        flat = eb.view(self.n_slabs, EB_SLAB)
+        ix = self.plan.on(eb.device)
+        if len(self.plan.unowned):
+            flat.index_fill_(0, ix.unowned, 0)
+        if self._hip(eb):
+            recv = parts if hasattr(parts, "shape") else torch.stack(list(parts))
+            recv = recv if recv.device == eb.device and recv.is_contiguous() else recv.to(eb.device).contiguous()
+            self._kernel("wgrt_eyebox_assemble", eb, self.n_slabs, recv.data_ptr(), self.world, self.nb,
+                         ix.dst_rows.data_ptr(), ix.spill_dst_rows.data_ptr())
             return
-        parts = [recv[r] for r in range(self.world)] if recv is not None else parts
-        for r, p in enumerate(parts):
-            n = self.counts[r]
-            if n:
-                flat.index_copy_(0, self.slabs[r], self._views(p)[0][:n])
-        head = flat[:, :SPILL]
-        for r, p in enumerate(parts):
-            if self.has_spill[r]:
-                head.index_add_(0, self.spill_dst[r], self._views(p)[1].index_select(0, self.spill_rows[r]))
+        views = [self._views(parts[r]) for r in range(self.world)]
+        for r, (main, _) in enumerate(views):
+            flat.index_copy_(0, ix.slabs[r], main[:self.counts[r]])
+        for r, (_, spill) in enumerate(views):   # an empty index set adds nothing
+            flat[:, :SPILL].index_add_(0, ix.spill_dst[r], spill.index_select(0, ix.spill_rows[r]))
 
     def __call__(self, eb, group=None, dst: int = 0):
         import torch.distributed as dist
         if _world(group) <= 1:
             return eb
         rank = dist.get_rank(group)
-        on_gloo_dev = getattr(eb, "is_cuda", False) and dist.get_backend(group) == "gloo"
         send, recv = self.buffers(eb.device, eb.dtype, rank == dst)
-        payload = self.pack(eb, rank, out=send)
-        if on_gloo_dev:
-            # gloo gathers host tensors (the bench's one-GPU rehearsal)
-            payload = payload.cpu()
-            parts = [recv[r].cpu() for r in range(self.world)] if rank == dst else None
-        else:
-            parts = [recv[r] for r in range(self.world)] if rank == dst else None
-        dist.gather(payload, gather_list=parts, dst=dst, group=group)
+        payload, = _operands(group, self.pack(eb, rank, out=send))
+        rows = recv.unbind(0) if rank == dst else ()
+        parts = _operands(group, *rows)
+        dist.gather(payload, gather_list=list(parts) if rank == dst else None, dst=dst, group=group)
         if rank == dst:
-            if on_gloo_dev:
-                for r in range(self.world):
-                    recv[r].copy_(parts[r])
+            for row, part in zip(rows, parts):
+                if part is not row:
+                    row.copy_(part)
             self.assemble(eb, recv)
         return eb
 
 
 class EyeboxReduce:
     """The evaluation-only collective: each rank reduces its own part of the grid to per-slab window sums
-    (``AR_system_evaluation_functions.eyebox_window_sums``: the slab total and the 7 x 8 pupil sums, 57
-    float64 per slab) and ONE sum-reduce of the ``[n_slabs, W]`` table brings them to rank 0, instead of the
-    gather of whole 38.4 KB slabs.
+    (``AR_system_evaluation_functions.eyebox_window_sums``: the slab total and the 7 x 8 pupil sums, 57 float64 per
+    slab) and ONE sum-reduce of the ``[n_slabs, W]`` table brings them to rank 0, instead of whole 38.4 KB slabs.
 
-    A rank reduces only the slabs it can have written: those of its own blocks and, for each of them, the
-    slab after it (the H6 top-edge spill, ``EyeboxGather``'s index sets: ``slabs[r]`` and ``spill_dst[r]``);
-    its rows go into a zeroed table.  Window sums are linear in the grid and the grid holds integer counts,
-    so every entry is an integer, exact in float64 whatever the order of the additions: rank 0's table
-    equals the window sums of the assembled grid bit for bit, spills into slabs no rank owns included.
-    A device grid is reduced by the HIP kernel; host tensors (the gloo CPU tests) by the numpy statement
-    of the same formula."""
+    A rank reduces only the slabs it can have written (``SlabPlan.rows``: its own blocks' and, for the H6 top-edge
+    spill, the slab after each), into a zeroed table.  Window sums are linear in the grid and the grid holds
+    integer counts, so every entry is an integer, exact in float64 whatever the order of the additions: rank 0's
+    table equals the window sums of the assembled grid bit for bit, spills into slabs no rank owns included.  A
+    device grid is reduced by the HIP kernel; host tensors by the numpy statement of the same formula."""
 
     def __init__(self, all_blocks, num_fov_x: int, num_fov_y: int, lambdas, n_lambda_scene: int, mask=None,
                  step_y: int = 8, step_x: int = 12):
-        import torch
-        g = EyeboxGather(all_blocks, num_fov_x, num_fov_y, lambdas, n_lambda_scene)
-        self.n_slabs, self.world = g.n_slabs, g.world
-        # own slabs, then the spill targets that are not own slabs (spill_dst): no slab twice
-        self.rows = [torch.cat([g.slabs[r], g.spill_dst[r]]) for r in range(self.world)]
+        self.plan = SlabPlan(all_blocks, num_fov_x, num_fov_y, lambdas, n_lambda_scene)
+        self.n_slabs, self.world = self.plan.n_slabs, self.plan.world
+        self.rows = self.plan.on("cpu").rows
         self.mask, self.step_y, self.step_x = mask, step_y, step_x
-        self._dev_rows = {}
-
-    def _rows(self, rank: int, device):
-        """Rank ``rank``'s slab list on ``device`` (host tensors here; moved once per device and cached)."""
-        key = (rank, str(device))
-        if key not in self._dev_rows:
-            self._dev_rows[key] = self.rows[rank].to(device)
-        return self._dev_rows[key]
 
     def local(self, eb, rank: int):
         """Rank ``rank``'s contribution: its rows' window sums scattered into a zeroed ``[n_slabs, W]`` float64
@@ -420,31 +409,15 @@ class EyeboxReduce:
         import torch
 
         from .AR_system_evaluation_functions import eyebox_window_sums
-        rows = self._rows(rank, eb.device)
-        part = eyebox_window_sums(eb, rows, self.mask, self.step_y, self.step_x)
-        if not isinstance(part, torch.Tensor):
-            part = torch.from_numpy(part)
+        rows = self.plan.on(eb.device).rows[rank]
+        part = torch.as_tensor(eyebox_window_sums(eb, rows, self.mask, self.step_y, self.step_x))
         full = torch.zeros((self.n_slabs, part.shape[1]), dtype=torch.float64, device=eb.device)
-        full.index_copy_(0, rows, part)
-        return full
+        return full.index_copy_(0, rows, part)
 
     def __call__(self, eb, group=None, dst: int = 0):
-        """The ``[n_slabs, W]`` window sums of the whole job's grid on rank ``dst`` (this rank's own
-        contribution elsewhere)."""
+        """Rank ``dst``: the ``[n_slabs, W]`` window sums of the whole job's grid (elsewhere: this rank's own part)."""
         import torch.distributed as dist
-        if _world(group) <= 1:
-            return self.local(eb, 0)
-        rank = dist.get_rank(group)
-        full = self.local(eb, rank)
-        if full.is_cuda and dist.get_backend(group) == "gloo":
-            # gloo reduces host tensors (the one-GPU rehearsal, as EyeboxGather.__call__)
-            host = full.cpu()
-            dist.reduce(host, dst=dst, op=dist.ReduceOp.SUM, group=group)
-            if rank == dst:
-                full.copy_(host)
-        else:
-            dist.reduce(full, dst=dst, op=dist.ReduceOp.SUM, group=group)
-        return full
+        return reduce_eyebox(self.local(eb, dist.get_rank(group) if _world(group) > 1 else 0), group, dst)
 
 
 def trace_job(shard: Shard, build_rays_fn, trace_fn, new_eb, num_iter: int = 4, per_call: int = 1, group=None,
@@ -501,19 +474,16 @@ def timed_run(trace_fn, rays, rng, eb, gid: GidMap, steps: int, per_call: int, s
 
 
 def hip_tracer(scene, variant: int = 0, stats=None):
-    """trace_fn for ``run_steps`` / ``trace_job`` using the HIP kernel (torch device tensors);
-    ``stats`` (int64[STATS_LEN] device tensor) is added to by every call.  A shard of several
-    block ranges passes its global ids as ``gid_blocks``, uploaded once per map and device and kept
-    on the GidMap itself (``GidMap.device_blocks``: released with the map, no tracer-side cache)."""
+    """trace_fn for ``run_steps`` / ``trace_job`` using the HIP kernel (torch device tensors); ``stats``
+    (int64[STATS_LEN] device tensor) is added to by every call.  A shard of several block ranges passes its global
+    ids as ``gid_blocks``, uploaded once per map and device and kept on the map (``GidMap.device_blocks``)."""
     from .engine import trace_fullcolor
 
     def fn(rays, rng, eb, gid: GidMap, num_iter=1):
         off = gid.offset
-        if off is not None:
-            trace_fullcolor(scene, rays, rng, eb, gid_offset=off, stats=stats, variant=variant, num_iter=num_iter)
-            return
-        trace_fullcolor(scene, rays, rng, eb, stats=stats, variant=variant, num_iter=num_iter,
-                        gid_blocks=gid.device_blocks(rng.device), gid_block_rays=gid.rays_per_block)
+        ids = dict(gid_offset=off) if off is not None else dict(gid_blocks=gid.device_blocks(rng.device),
+                                                                gid_block_rays=gid.rays_per_block)
+        trace_fullcolor(scene, rays, rng, eb, stats=stats, variant=variant, num_iter=num_iter, **ids)
     return fn
 
 
@@ -555,4 +525,4 @@ def shard_rays_host(points, num_fov_x, num_fov_y, lambdas, rays_per_fov, blocks,
 
 __all__ = ["block_range", "rank_blocks", "GidMap", "Shard", "make_shard", "replica_shard", "seeds_like", "slab_ids", "split_calls", "run_steps",
            "reduce_eyebox", "EyeboxGather", "EyeboxReduce", "trace_job", "timed_run", "hip_tracer", "hip_shard_builder",
-           "shard_rays_host", "MAX_TRACES_PER_CALL", "EB_SLAB", "SPILL"]
+           "shard_rays_host", "SlabPlan", "MAX_TRACES_PER_CALL", "EB_SLAB", "SPILL"]

@@ -28,9 +28,11 @@ window sums are sum-reduced instead (``distributed.EyeboxReduce``).
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import time
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -68,139 +70,166 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
     on several GPUs) is evaluated where it lives (``evaluation_from_window_sums``); only the three figures and
     the centre image come back, ``center_view`` and the PNG are built from that image, and ``output_image``
     (every eye position's image) is returned only with ``keep_image=True``."""
-    if eyebox not in ("host", "device"):
-        raise ValueError(f"eyebox must be 'host' or 'device', got {eyebox!r}")
-    if evaluate_on not in ("host", "device"):
-        raise ValueError(f"evaluate_on must be 'host' or 'device', got {evaluate_on!r}")
+    for name, where in (("eyebox", eyebox), ("evaluate_on", evaluate_on)):
+        if where not in ("host", "device"):
+            raise ValueError(f"{name} must be 'host' or 'device', got {where!r}")
     if evaluate_on == "device" and eyebox != "device":
         raise ValueError("evaluate_on='device' evaluates the on-device window sums: it needs eyebox='device'")
+    from .engine import STAT
+    with _set_up(num_FOV_x, num_FOV_y, int(num_rays_per_FoV), num_iter, lambdas, lut_dir, lut_seed, lut_profile,
+                 point_seed, points, verbose) as job:   # closes the scene on every way out
+        kern_s = _trace(job, variant, fuse)
+        t_post = time.perf_counter()   # everything below is post-processing of the traced grid
+        grid, table, stats = _collect(job, eyebox == "device", keep_grid)
+        out = dict(num_rays=job.num_rays, num_iter=num_iter, gpu_seconds=kern_s, bounces=int(stats[STAT.bounces]),
+                   eyebox_hits=int(stats[STAT.eyebox_hits]), rng_states=job.rng.cpu().numpy().view(np.uint32))
+        if job.rank != 0:
+            return out
+        _report(job, out, grid, table)
+        if evaluate:
+            _evaluate(job, out, grid, table, evaluate_on, keep_image, png)
+        out["post_seconds"] = time.perf_counter() - t_post
+        job.say(f"Post-processing time  : {out['post_seconds']:.4f} s  (eyebox reduced on the {eyebox})")
+        return out
+
+
+@contextlib.contextmanager
+def _set_up(nx, ny, R, num_iter, lambdas, lut_dir, lut_seed, lut_profile, point_seed, points, verbose):
+    """Steps 1-3: geometry, LUTs, the scene, the origins (rank 0's on every rank), every rank's shard and this
+    rank's rays, as the record the later stages read; the scene is closed when the ``with`` block ends."""
     import torch
     import torch.distributed as dist
 
     from .couplers_coor import design_geometry
-    from .distributed import (EyeboxGather, EyeboxReduce, hip_shard_builder, hip_tracer, make_shard, run_steps,
-                              split_calls)
-    from .engine import STAT, Scene, check_stats, new_stats, reserve
+    from .distributed import hip_shard_builder, make_shard
+    from .engine import Scene, new_stats
     from .luts import load_luts, lut_f32_mask, synthetic_luts, validate_luts
     from .rays import generate_points_in_polygon
 
-    world = dist.get_world_size() if dist.is_initialized() else 1
-    rank = dist.get_rank() if dist.is_initialized() else 0
+    world, rank = (dist.get_world_size(), dist.get_rank()) if dist.is_initialized() else (1, 0)
     dev = torch.device("cuda", torch.cuda.current_device())
     say = (lambda *a: print(*a, flush=True)) if (verbose and rank == 0) else (lambda *a: None)
 
     say("=" * 60 + "\nInitializing system components ...\n" + "=" * 60)
-    geom = design_geometry(num_FOV_x, num_FOV_y)
+    geom = design_geometry(nx, ny)
     f32_angles = 0
     if lut_dir:
         raw = load_luts(lut_dir)
         f32_angles = lut_f32_mask(raw)   # complex64 files: float32 cosines, as the compiled reference
-        luts = validate_luts(raw, len(geom.lmd), num_FOV_x, num_FOV_y, geom.num_fc_slices, geom.num_oc_slices)
+        luts = validate_luts(raw, len(geom.lmd), nx, ny, geom.num_fc_slices, geom.num_oc_slices)
     else:
         luts = synthetic_luts(geom, seed=lut_seed, profile=lut_profile)
-    scene = Scene.from_geometry(geom, luts, device=dev.index, lut_f32_angles=f32_angles)
-    R = int(num_rays_per_FoV)
-    rng_pts = np.random.default_rng(point_seed) if point_seed is not None else None
-    if points is None:
-        points = generate_points_in_polygon(geom.IC, R // 2, rng=rng_pts)
-    points = np.ascontiguousarray(points, dtype=np.float64)
-    if world > 1:  # every rank must use the same origins
-        t = torch.from_numpy(np.ascontiguousarray(points)).to(dev)
-        dist.broadcast(t, src=0)
-        points = t.cpu().numpy()
-    shard = make_shard(num_FOV_x, num_FOV_y, len(lambdas), R, world, rank)
-    # ray columns and RNG seeds built on the device (MAIN:59-158 without the host arrays:
-    # 48 B x N of host memory and its upload at the reference's 100 x 75 x 3 x 5000 default)
-    rays, rng = hip_shard_builder(points, num_FOV_x, num_FOV_y, lambdas, R, dev)(shard)
-    eb = torch.zeros(scene.eb_shape(), dtype=torch.float32, device=dev)
-    stats = new_stats(dev)
-    num_rays = num_FOV_x * num_FOV_y * len(lambdas) * R
-    say(f"Initialization complete: {num_rays:,} rays, {world} GPU(s)\n" + "=" * 60 + "\nSTART GPU RAY TRACING\n" + "=" * 60)
+    with contextlib.closing(Scene.from_geometry(geom, luts, device=dev.index, lut_f32_angles=f32_angles)) as scene:
+        if points is None:
+            points = generate_points_in_polygon(geom.IC, R // 2,
+                                                rng=None if point_seed is None else np.random.default_rng(point_seed))
+        points = np.ascontiguousarray(points, dtype=np.float64)
+        if world > 1:  # every rank must use the same origins
+            t = torch.from_numpy(points).to(dev)
+            dist.broadcast(t, src=0)
+            points = t.cpu().numpy()
+        shards = [make_shard(nx, ny, len(lambdas), R, world, r) for r in range(world)]
+        # ray columns and RNG seeds built on the device (MAIN:59-158 without the host arrays:
+        # 48 B x N of host memory and its upload at the reference's 100 x 75 x 3 x 5000 default)
+        rays, rng = hip_shard_builder(points, nx, ny, lambdas, R, dev)(shards[rank])
+        eb = torch.zeros(scene.eb_shape(), dtype=torch.float32, device=dev)
+        num_rays = nx * ny * len(lambdas) * R
+        say(f"Initialization complete: {num_rays:,} rays, {world} GPU(s)\n" + "=" * 60 + "\nSTART GPU RAY TRACING\n" + "=" * 60)
+        yield SimpleNamespace(nx=nx, ny=ny, R=R, num_iter=num_iter, lambdas=lambdas, world=world, rank=rank, dev=dev,
+                              say=say, scene=scene, shards=shards, shard=shards[rank], rays=rays, rng=rng, eb=eb,
+                              stats=new_stats(dev), num_rays=num_rays)
 
-    # the num_iter chained launches of MAIN:169-177; fuse: as one call (wgrt_launch_opts.num_iter,
-    # one persistent launch for the Jones-vector variants), with results identical to num_iter calls
-    if fuse is None:
-        fuse = shard.n_rays <= FUSE_MAX_RAYS
-    per_call = 0 if fuse else 1
-    calls = split_calls(num_iter, per_call)
-    if shard.n_rays and calls:
-        reserve(scene, shard.n_rays, max(calls))
+
+def _trace(job, variant, fuse) -> float:
+    """Step 4, the num_iter chained launches of MAIN:169-177; fuse: as one call (wgrt_launch_opts.num_iter, one
+    persistent launch for the Jones-vector variants), with identical results.  Returns their seconds by HIP events."""
+    import torch
+
+    from .distributed import hip_tracer, run_steps, split_calls
+    from .engine import check_stats, reserve
+    n_rays = job.shard.n_rays
+    per_call = 0 if (n_rays <= FUSE_MAX_RAYS if fuse is None else fuse) else 1
+    calls = split_calls(job.num_iter, per_call)
+    if n_rays and calls:
+        reserve(job.scene, n_rays, max(calls))
     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0.record()
-    if shard.n_rays:
-        run_steps(hip_tracer(scene, variant, stats), rays, rng, eb, shard.gid, num_iter, per_call)
+    if n_rays:
+        run_steps(hip_tracer(job.scene, variant, job.stats), job.rays, job.rng, job.eb, job.shard.gid, job.num_iter,
+                  per_call)
     t1.record()
     torch.cuda.synchronize()
-    kern_s = t0.elapsed_time(t1) / 1e3
-    check_stats(stats)
-    t_post = time.perf_counter()   # everything below is post-processing of the traced grid
-    on_device = eyebox == "device"
-    sums = None   # device mode: the [n_slabs, 57] window sums of the whole job's grid (rank 0)
-    if world > 1:
-        all_blocks = [make_shard(num_FOV_x, num_FOV_y, len(lambdas), R, world, r).blocks for r in range(world)]
+    check_stats(job.stats)
+    return t0.elapsed_time(t1) / 1e3
+
+
+def _collect(job, on_device: bool, keep_grid: bool):
+    """The ranks' results brought together, ``(grid, table, stats)``: the whole job's eyebox grid on the host
+    (rank 0, in host mode or with ``keep_grid``; else None), device mode's ``[n_slabs, 57]`` window sums of that
+    grid as a device tensor (rank 0's is the job's; else None), and the job's counters on the host."""
+    import torch.distributed as dist
+
+    from .AR_system_evaluation_functions import eyebox_window_sums
+    from .distributed import EyeboxGather, EyeboxReduce
+    want_grid = not on_device or keep_grid
+    table = None
+    if job.world > 1:
+        plan = ([s.blocks for s in job.shards], job.nx, job.ny, job.lambdas, job.scene.num_lmd)
         if on_device:
-            sums = EyeboxReduce(all_blocks, num_FOV_x, num_FOV_y, lambdas, scene.num_lmd)(eb)
-        if not on_device or keep_grid:
-            EyeboxGather(all_blocks, num_FOV_x, num_FOV_y, lambdas, scene.num_lmd, device=dev)(eb)
+            table = EyeboxReduce(*plan)(job.eb)
+        if want_grid:
+            EyeboxGather(*plan, device=job.dev)(job.eb)
+        dist.all_reduce(job.stats)
     elif on_device:
-        from .AR_system_evaluation_functions import eyebox_window_sums
-        sums = eyebox_window_sums(eb)
-    if world > 1:
-        dist.all_reduce(stats)
-    matrix_EB = eb.cpu().numpy() if not on_device or keep_grid else None
-    out = dict(num_rays=num_rays, num_iter=num_iter, gpu_seconds=kern_s, bounces=int(stats[STAT.bounces]),
-               eyebox_hits=int(stats[STAT.eyebox_hits]), rng_states=rng.cpu().numpy().view(np.uint32))
-    if rank != 0:
-        scene.close()
-        return out
-    if on_device:
-        # slab totals are integer counts: below 2^24 the float32 cast is the value np.sum gives on the host
-        sums_dev = sums
-        sums = sums[:, 0].cpu().numpy() if evaluate_on == "device" else sums.cpu().numpy()
-        totals = sums if sums.ndim == 1 else sums[:, 0]
-        A = totals.reshape(scene.eb_shape()[:-2]).astype(np.float32) / num_rays / num_iter
+        table = eyebox_window_sums(job.eb)
+    return job.eb.cpu().numpy() if want_grid and job.rank == 0 else None, table, job.stats.cpu().numpy()
+
+
+def _report(job, out: dict, grid, table) -> None:
+    """Step 5's efficiencies, into ``out`` and printed: ``A`` from the host grid, or from the table's slab totals
+    -- integer counts: below 2^24 the float32 cast is the value np.sum gives on the host."""
+    num_rays, num_iter, kern_s = job.num_rays, job.num_iter, out["gpu_seconds"]
+    if table is not None:
+        A = table[:, 0].cpu().numpy().reshape(job.scene.eb_shape()[:-2]).astype(np.float32) / num_rays / num_iter
     else:
-        A = np.sum(matrix_EB, axis=(-2, -1)) / num_rays / num_iter
+        A = np.sum(grid, axis=(-2, -1)) / num_rays / num_iter
     names = {0: "Blue", 1: "Green", 2: "Red"}
     eff = {names.get(k, str(k)): float(np.sum(A[k] * 3)) for k in range(A.shape[0])}
-    say("Simulation finished.")
-    say(f"Number of rays traced : {num_rays * num_iter:,}")
-    say(f"GPU calculation time  : {kern_s:.4f} s  ({out['bounces'] / max(kern_s, 1e-12):.3e} ray-bounces/s)")
+    job.say("Simulation finished.")
+    job.say(f"Number of rays traced : {num_rays * num_iter:,}")
+    job.say(f"GPU calculation time  : {kern_s:.4f} s  ({out['bounces'] / max(kern_s, 1e-12):.3e} ray-bounces/s)")
     for c in ("Red", "Green", "Blue"):
         if c in eff:
-            say(f"Efficiency ({c:5s})    : {eff[c] * 100:8.3f} %")
+            job.say(f"Efficiency ({c:5s})    : {eff[c] * 100:8.3f} %")
     out.update(A=A, efficiency=eff)
-    if matrix_EB is not None:
-        out["matrix_EB"] = matrix_EB
-    if evaluate:
-        from .AR_system_evaluation_functions import (evaluation, evaluation_from_perceive,
-                                                     evaluation_from_window_sums, perceive_from_window_sums)
-        if evaluate_on == "device":
-            delta_e, U_fov, U_EB, image = evaluation_from_window_sums(
-                sums_dev, scene.eb_shape(), R * num_iter, image="all" if keep_image else "center")
-            center = image[:, :, :, 0, image.shape[4] - 1] if keep_image else image
-            out.update(delta_e=float(delta_e), U_fov=float(U_fov), U_EB=float(U_EB))
-            if keep_image:
-                out["output_image"] = image
-            out["center_view"] = center_view_u8(center)
-        else:
-            if on_device:
-                delta_e, U_fov, U_EB, output_image = evaluation_from_perceive(
-                    perceive_from_window_sums(sums, scene.eb_shape(), R * num_iter))
-            else:
-                delta_e, U_fov, U_EB, output_image = evaluation(matrix_EB / R / num_iter)
-            out.update(delta_e=float(delta_e), U_fov=float(U_fov), U_EB=float(U_EB), output_image=output_image)
-            out["center_view"] = eyebox_center_view(output_image)
-        if png:
-            write_png(png, out["center_view"])
-            say(f"Wrote {png}")
-        say(f"Color dispersion      : {delta_e:8.2f}")
-        say(f"FoV uniformity        : {U_fov * 100:8.2f} %")
-        say(f"Eyebox uniformity     : {U_EB * 100:8.2f} %")
-    out["post_seconds"] = time.perf_counter() - t_post
-    say(f"Post-processing time  : {out['post_seconds']:.4f} s  (eyebox reduced on the {eyebox})")
-    scene.close()
-    return out
+    if grid is not None:
+        out["matrix_EB"] = grid
+
+
+def _evaluate(job, out: dict, grid, table, evaluate_on: str, keep_image: bool, png) -> None:
+    """Steps 5-6, into ``out`` and printed: the evaluation -- of the table where it lives, of the table's host
+    copy, or of the host grid (MAIN:197-198) -- then the centre view and its PNG."""
+    from .AR_system_evaluation_functions import (evaluation, evaluation_from_perceive, evaluation_from_window_sums,
+                                                 perceive_from_window_sums)
+    shape, divisor = job.scene.eb_shape(), job.R * job.num_iter
+    whole = evaluate_on == "host" or keep_image   # ``image``: every eye position's, else the centre one alone
+    if evaluate_on == "device":
+        *figures, image = evaluation_from_window_sums(table, shape, divisor, image="all" if whole else "center")
+    elif table is not None:
+        *figures, image = evaluation_from_perceive(perceive_from_window_sums(table.cpu().numpy(), shape, divisor))
+    else:
+        *figures, image = evaluation(grid / job.R / job.num_iter)
+    delta_e, U_fov, U_EB = (float(v) for v in figures)
+    out.update(delta_e=delta_e, U_fov=U_fov, U_EB=U_EB)
+    if whole:
+        out["output_image"] = image
+    out["center_view"] = eyebox_center_view(image) if whole else center_view_u8(image)
+    if png:
+        write_png(png, out["center_view"])
+        job.say(f"Wrote {png}")
+    job.say(f"Color dispersion      : {delta_e:8.2f}")
+    job.say(f"FoV uniformity        : {U_fov * 100:8.2f} %")
+    job.say(f"Eyebox uniformity     : {U_EB * 100:8.2f} %")
 
 
 def eyebox_center_view(output_image: np.ndarray) -> np.ndarray:

@@ -3,17 +3,15 @@ tests/test_gpu_eyebox_reduce.py): ``eyebox_window_sums`` in float64 numpy, the s
 ``eye_perceive``, how the exact float64 window sums relate to the float32 host flow of the driver
 (MAIN:197-198), and ``distributed.EyeboxReduce`` over gloo at world size 2 and 3."""
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from gpu_ray_tracing_for_waveguide_based_ar_display_amd import AR_system_evaluation_functions as E
 from gpu_ray_tracing_for_waveguide_based_ar_display_amd.distributed import (EB_SLAB, SPILL, EyeboxGather, EyeboxReduce,
                                                                             rank_blocks, slab_ids)
+from tests import _dist
 
 SHAPE = (3, 2, 4, 80, 120)
 
@@ -119,12 +117,6 @@ def test_device_spec_against_float32_host_flow(grid):
 
 # --- EyeboxReduce over gloo (host tensors: the numpy path, so this covers the index logic) ----------------
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 def _rank_grid(rank, blocks, nx, ny, lambdas, scene_l):
     """A synthetic integer grid as rank ``rank`` could have written it: nonzero only in its own slabs and
     in the first SPILL floats of the slab after each of them."""
@@ -138,9 +130,7 @@ def _rank_grid(rank, blocks, nx, ny, lambdas, scene_l):
     return eb
 
 
-def _reduce_worker(rank, world, port, outdir, nx, ny, lambdas, scene_l):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _reduce_worker(rank, world, outdir, nx, ny, lambdas, scene_l):
     blocks = [rank_blocks(nx * ny * len(lambdas), world, r, "interleaved", len(lambdas)) for r in range(world)]
     eb = torch.from_numpy(_rank_grid(rank, blocks, nx, ny, lambdas, scene_l))
     sums = EyeboxReduce(blocks, nx, ny, lambdas, scene_l)(eb)
@@ -148,14 +138,12 @@ def _reduce_worker(rank, world, port, outdir, nx, ny, lambdas, scene_l):
     if rank == 0:
         np.save(os.path.join(outdir, "sums.npy"), sums.numpy())
         np.save(os.path.join(outdir, "grid.npy"), grid.numpy())
-    dist.destroy_process_group()
 
 
 @pytest.mark.parametrize("nx,ny,lambdas,scene_l,world", [(4, 3, [0, 1, 2], 3, 2), (4, 3, [0, 1, 2], 3, 3),
                                                          (11, 11, [1], 3, 3)])
 def test_eyebox_reduce_equals_window_sums_of_gathered_grid(tmp_path, nx, ny, lambdas, scene_l, world):
-    mp.start_processes(_reduce_worker, args=(world, _free_port(), str(tmp_path), nx, ny, lambdas, scene_l),
-                       nprocs=world, join=True, start_method="spawn")
+    _dist.spawn(_reduce_worker, world, str(tmp_path), nx, ny, lambdas, scene_l)
     sums, grid = np.load(tmp_path / "sums.npy"), np.load(tmp_path / "grid.npy")
     assert sums.dtype == np.float64 and sums.shape == (scene_l * ny * nx, 57)
     np.testing.assert_array_equal(sums, E.eyebox_window_sums(grid))

@@ -11,44 +11,29 @@ sum-reduce) must equal the oracle's trace of the tiled batch.  RCCL itself needs
 its first run is the driver's 8-GPU bench.
 """
 import os
-import socket
 
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
+from tests import _dist  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 NX, NY, LAMBDAS, R, STEPS = 5, 4, [0, 1, 2], 256, 2
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 def _inputs():
-    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.couplers_coor import design_geometry
-    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.luts import synthetic_luts
-    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.rays import generate_points_in_polygon
-    geom = design_geometry(NX, NY)
-    luts = synthetic_luts(geom, seed=3, profile="deep")
-    pts = generate_points_in_polygon(geom.IC, R // 2, rng=np.random.default_rng(6))
-    return geom, luts, pts
+    return _dist.small_job(NX, NY, R, lut_seed=3, point_seed=6, lut_profile="deep")
 
 
-def _worker(rank, world, port, outdir, mode):
-    import torch.distributed as dist
-
+def _worker(rank, world, outdir, mode):
     from gpu_ray_tracing_for_waveguide_based_ar_display_amd.distributed import (EyeboxGather, hip_shard_builder,
                                                                                 hip_tracer, make_shard,
                                                                                 rank_blocks, replica_shard, timed_run)
     from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import Scene, check_stats, new_stats
 
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     geom, luts, pts = _inputs()
@@ -73,7 +58,6 @@ def _worker(rank, world, port, outdir, mode):
     if rank == 0:
         np.save(os.path.join(outdir, "eb.npy"), eb.cpu().numpy())
     scene.close()
-    dist.destroy_process_group()
 
 
 def _oracle(copies=1):
@@ -95,11 +79,9 @@ def _oracle(copies=1):
 
 
 def _run(tmp_path, world, mode):
-    import torch.multiprocessing as mp
     if not torch.cuda.is_available():
         pytest.skip("no HIP device")
-    mp.start_processes(_worker, args=(world, _free_port(), str(tmp_path), mode), nprocs=world, join=True,
-                       start_method="spawn")
+    _dist.spawn(_worker, world, str(tmp_path), mode)
     return [np.load(tmp_path / f"res{r}.npy") for r in range(world)]
 
 
@@ -173,9 +155,9 @@ def test_eyebox_gather_built_on_host_used_on_device():
     dev = torch.device("cuda", 0)
     nx, ny, lambdas, world = 9, 7, [0, 1, 2], 3
     blocks = [rank_blocks(nx * ny * 3, world, r, "interleaved", 3) for r in range(world)]
-    g = EyeboxGather(blocks, nx, ny, lambdas, 3)          # no device=: host index tensors
+    g = EyeboxGather(blocks, nx, ny, lambdas, 3)          # no device=: no index tensor uploaded yet
     ref = EyeboxGather(blocks, nx, ny, lambdas, 3)
-    assert g.slabs[0].device.type == "cpu"
+    assert not g.plan.tensors
     rng = np.random.default_rng(11)
     shape = (3, ny, nx, 80, 120)
     ebs = [rng.integers(0, 5, size=shape).astype(np.float32) for _ in range(world)]

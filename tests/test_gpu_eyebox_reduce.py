@@ -5,10 +5,8 @@ kernel in every rank (all ranks on cuda:0 over gloo, as tests/test_gpu_distribut
 
 Counts are integers, so every comparison of an integer-valued grid is bit for bit; only the test on
 non-integer input has a tolerance (the summation order differs)."""
-import ctypes
 import functools
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -16,6 +14,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from gpu_ray_tracing_for_waveguide_based_ar_display_amd import AR_system_evaluation_functions as E  # noqa: E402
+from tests import _dist  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -188,13 +187,7 @@ NX, NY, LAMBDAS, R, STEPS = 5, 4, [0, 1, 2], 256, 2
 
 
 def _inputs():
-    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.couplers_coor import design_geometry
-    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.luts import synthetic_luts
-    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.rays import generate_points_in_polygon
-    geom = design_geometry(NX, NY)
-    luts = synthetic_luts(geom, seed=3, profile="deep")
-    pts = generate_points_in_polygon(geom.IC, R // 2, rng=np.random.default_rng(6))
-    return geom, luts, pts
+    return _dist.small_job(NX, NY, R, lut_seed=3, point_seed=6, lut_profile="deep")
 
 
 def test_driver_device_mode_equals_host_mode():
@@ -220,42 +213,22 @@ def test_driver_device_mode_equals_host_mode():
 
 # --- multi-rank: every rank traces its shard on cuda:0 and the window sums are sum-reduced over gloo --------
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
+def _worker(rank, world, outdir):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.distributed import EyeboxReduce, rank_blocks
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.gpu_ray_tracing_pro_fullColor import _set_up, _trace
 
-
-def _worker(rank, world, port, outdir):
-    import torch.distributed as dist
-
-    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.distributed import (EyeboxReduce, hip_shard_builder,
-                                                                                hip_tracer, make_shard, rank_blocks,
-                                                                                run_steps)
-    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import Scene, check_stats, new_stats
-
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    dev = torch.device("cuda", 0)
-    torch.cuda.set_device(dev)
-    geom, luts, pts = _inputs()
-    scene = Scene.from_geometry(geom, luts)
+    torch.cuda.set_device(torch.device("cuda", 0))
     nb = NX * NY * len(LAMBDAS)
-    shard = make_shard(NX, NY, len(LAMBDAS), R, world, rank)
     reduce = EyeboxReduce([rank_blocks(nb, world, r, "interleaved", len(LAMBDAS)) for r in range(world)],
                           NX, NY, LAMBDAS, len(LAMBDAS))
-    rays, rng = hip_shard_builder(pts, NX, NY, LAMBDAS, R, dev)(shard)
-    eb = torch.zeros(scene.eb_shape(), dtype=torch.float32, device=dev)
-    stats = new_stats(dev)
-    run_steps(hip_tracer(scene, 0, stats), rays, rng, eb, shard.gid, STEPS, 1)
-    sums = reduce(eb)
-    torch.cuda.synchronize()
-    check_stats(stats)
+    # the driver's own set-up and trace stages: this rank's shard, STEPS separate launches, counters checked
+    with _set_up(NX, NY, R, STEPS, LAMBDAS, None, 3, "deep", None, _inputs()[2], False) as job:
+        _trace(job, 0, False)
+        sums = reduce(job.eb)
+        torch.cuda.synchronize()
     if rank == 0:
         assert sums.is_cuda
         np.save(os.path.join(outdir, "sums.npy"), sums.cpu().numpy())
-    scene.close()
-    dist.destroy_process_group()
 
 
 @functools.lru_cache(maxsize=None)
@@ -276,9 +249,7 @@ def _oracle_sums():
 @pytest.mark.parametrize("world", [2, 3])
 def test_sharded_reduce_equals_oracle_window_sums(tmp_path, world):
     _dev()
-    import torch.multiprocessing as mp
-    mp.start_processes(_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True,
-                       start_method="spawn")
+    _dist.spawn(_worker, world, str(tmp_path))
     got = np.load(tmp_path / "sums.npy")
     assert got.dtype == np.float64 and got.shape == (3 * NY * NX, 57)
     np.testing.assert_array_equal(got, _oracle_sums())

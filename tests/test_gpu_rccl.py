@@ -8,29 +8,25 @@ it pins the call shapes, dtypes and buffers RCCL is given, not the transfer spee
 Tolerance: exact (the assembled grid equals the traced one bit for bit)."""
 import json
 import os
-import socket
 import subprocess
 import sys
 
 import pytest
 
 torch = pytest.importorskip("torch")
+
+from tests import _dist  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def test_rccl_collectives_of_the_strong_scaling_path():
     if not torch.cuda.is_available():
         pytest.skip("no HIP device")
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1",
-               MASTER_PORT=str(_free_port()))
+               MASTER_PORT=str(_dist.free_port()))
     p = subprocess.run([sys.executable, os.path.join(REPO, "tools", "rccl_probe.py")], env=env, cwd=REPO,
                        capture_output=True, text=True, timeout=100)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
