@@ -291,6 +291,31 @@ def eyebox_window_sums(eb, slabs=None, mask=None, step_y: int = 8, step_x: int =
     return _window_sums_host(np.asarray(eb), slabs, _square_mask(mask), step_y, step_x)
 
 
+def check_window_plan(mask=None, step_y: int = 8, step_x: int = 12) -> None:
+    """The argument check of the trace's window-table sink (``wgrt_window_plan_validate``; needs no GPU):
+    raises ``WgrtError`` with the reason unless 1 <= ms <= 80, the steps are >= 1 and every tap of ``mask`` is
+    exactly 0 or 1 (the sink adds exactly 1.0 per tap; ``eyebox_window_sums`` serves any other mask from a grid)."""
+    from ._lib import check, load
+    m = _square_mask(mask)
+    check(load().wgrt_window_plan_validate(m.ctypes.data, int(m.shape[0]), int(step_y), int(step_x)),
+          "wgrt_window_plan_validate")
+
+
+def window_table_from_offsets(offsets, n_slabs: int, mask=None, step_y: int = 8, step_x: int = 12) -> np.ndarray:
+    """The table the trace's window-table sink leaves for out-couplings at the flat grid ``offsets`` (int64; those
+    outside ``[0, n_slabs * 9600)`` are dropped as the grid's guard drops them): float64 ``[n_slabs, W]``, on the
+    host through the membership code the kernels compile (``wgrt_window_table_host``; needs no GPU).  Equal to
+    ``eyebox_window_sums`` of the grid with one count per offset."""
+    from ._lib import check, load
+    m = _square_mask(mask)
+    npy, npx = window_grid(int(m.shape[0]), step_y, step_x)
+    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    out = np.zeros((int(n_slabs), 1 + npy * npx), dtype=np.float64)
+    check(load().wgrt_window_table_host(m.ctypes.data, int(m.shape[0]), int(step_y), int(step_x), off.ctypes.data,
+                                        off.size, int(n_slabs), out.ctypes.data), "wgrt_window_table_host")
+    return out
+
+
 def perceive_from_window_sums(sums, shape, divisor, ms: int = 30, step_y: int = 8, step_x: int = 12) -> np.ndarray:
     """``eye_perceive(matrix_EB / R / num_iter)`` from the window sums of the raw grid: ``sums[:, 1:] / divisor``
     (``divisor = R * num_iter``) as float64 ``[L, NY, NX, npy, npx]``.  ``shape``: the grid's shape (its first

@@ -26,7 +26,8 @@ EXPORTED = ("wgrt_scene_create", "wgrt_scene_create_ex", "wgrt_scene_destroy", "
             "wgrt_locator_classify_host", "wgrt_selftest_math", "wgrt_status_string", "wgrt_last_error",
             "wgrt_abi_version", "wgrt_eyebox_payload_floats", "wgrt_eyebox_pack", "wgrt_eyebox_assemble",
             "wgrt_eyebox_window_sums", "wgrt_eyebox_evaluate_workspace_bytes", "wgrt_eyebox_evaluate",
-            "wgrt_eyebox_evaluate_host")
+            "wgrt_eyebox_evaluate_host", "wgrt_window_plan_create", "wgrt_window_plan_destroy",
+            "wgrt_window_plan_width", "wgrt_trace_windows", "wgrt_window_plan_validate", "wgrt_window_table_host")
 EXPORTED_DEBUG = ("wgrt_debug_shadow", "wgrt_debug_scene_copy", "wgrt_debug_set_auto_order",
                   "wgrt_debug_get_auto_order", "wgrt_debug_get_tile_tail", "wgrt_debug_order_host")
 
@@ -205,6 +206,21 @@ def load():
         L.wgrt_eyebox_evaluate.argtypes = ev + [_vp]
         L.wgrt_eyebox_evaluate_host.restype = st
         L.wgrt_eyebox_evaluate_host.argtypes = ev
+    if hasattr(L, "wgrt_trace_windows"):   # the window-table sink: new symbols within ABI 9, bound by name
+        L.wgrt_window_plan_create.restype = st
+        L.wgrt_window_plan_create.argtypes = [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int,
+                                              ctypes.POINTER(_vp)]
+        L.wgrt_window_plan_destroy.restype = st
+        L.wgrt_window_plan_destroy.argtypes = [_vp]
+        L.wgrt_window_plan_width.restype = ctypes.c_int64
+        L.wgrt_window_plan_width.argtypes = [_vp]
+        L.wgrt_trace_windows.restype = st
+        L.wgrt_trace_windows.argtypes = L.wgrt_trace_opts.argtypes + [_vp, _vp]
+        L.wgrt_window_plan_validate.restype = st
+        L.wgrt_window_plan_validate.argtypes = [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+        L.wgrt_window_table_host.restype = st
+        L.wgrt_window_table_host.argtypes = [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int64,
+                                             ctypes.c_int64, _vp]
     # test / profiling hooks (include/wgrt_debug.h)
     L.wgrt_debug_shadow.restype = st
     L.wgrt_debug_shadow.argtypes = [_vp, ctypes.POINTER(Rays), ctypes.c_int64, ctypes.c_int64, ctypes.c_int, _vp,

@@ -14,6 +14,8 @@
 
 namespace wgrt {
 
+struct WindowPlanView;   // wgrt_window.h
+
 // s_waitcnt vmcnt(0) with expcnt / lgkmcnt left at their maxima, in the gfx9 simm16 encoding (vmcnt bits
 // 3:0 and 15:14, expcnt 6:4 = 7, lgkmcnt 11:8 = 15): through __builtin_amdgcn_s_waitcnt, so the compiler's
 // wait insertion knows that every vector-memory access issued before it has completed
@@ -85,6 +87,11 @@ struct TraceArgs {
     // global ray ids of an interleaved shard (wgrt_launch_opts.gid_blocks): NULL = gid_offset + i
     const int64_t *gid_blocks;
     int64_t gid_block_rays;
+    // the window-table sink (wgrt_trace_windows; wgrt_window.h): with win_table, every out-coupling also
+    // counts into table [n_slabs, W] under the plan *win; eb may then be NULL.  Last, so that every other
+    // field keeps its place in the kernarg segment.
+    double *win_table;
+    const WindowPlanView *win;
 };
 
 // TraceArgs fields re-read from the kernarg segment where they are used (a volatile scalar load,

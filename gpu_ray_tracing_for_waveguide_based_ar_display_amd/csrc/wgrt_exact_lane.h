@@ -11,6 +11,7 @@
 
 #include "wgrt_args.h"
 #include "wgrt_locator.h"
+#include "wgrt_window.h"
 
 namespace wgrt {
 
@@ -98,7 +99,8 @@ __device__ __forceinline__ bool lane_load(const TraceArgs &A, int64_t i, Lane &L
 }
 
 // Eyebox accumulation of an out-coupling (GRTF:1162-1171, 1231-1240) of a ray of tile T = (l, m, n) at (x, y):
-// the per-FoV eyebox rectangle test, the bin, and the atomic.  Returns whether the grid was added to.
+// the per-FoV eyebox rectangle test, the bin, and the atomic -- into the grid, into the pupil-window table of
+// wgrt_trace_windows, or both (wave-uniform: they are launch arguments).  Returns whether the bin was added to.
 __device__ __forceinline__ bool eyebox_add(const TraceArgs &A, const double *T, int l, int m, int n, double x,
                                            double y) {
     if (!inside_or_on_edge(x, y, T + kTileEbRect, 4)) return false;
@@ -114,7 +116,11 @@ __device__ __forceinline__ bool eyebox_add(const TraceArgs &A, const double *T, 
     const int64_t off = ((((int64_t)l * A.ny + n) * A.nx + m) * kEbNy + iy) * kEbNx + ix;
     const int64_t total = (int64_t)A.nl * A.ny * A.nx * kEbNy * kEbNx;
     if (off >= 0 && off < total) {
-        unsafeAtomicAdd(A.eb + off, 1.0f);
+        if (A.eb) unsafeAtomicAdd(A.eb + off, 1.0f);
+        if (A.win_table) {
+            double *const table = A.win_table;
+            window_visit(*A.win, off, [table](int64_t k) { unsafeAtomicAdd(table + k, 1.0); });
+        }
         return true;
     }
     return false;

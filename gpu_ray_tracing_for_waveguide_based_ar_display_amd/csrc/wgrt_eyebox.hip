@@ -27,6 +27,7 @@
 #include "../../include/wgrt.h"
 #include "wgrt_colour.h"
 #include "wgrt_host.h"
+#include "wgrt_window.h"
 
 using namespace wgrt;
 
@@ -180,6 +181,41 @@ extern "C" wgrt_status wgrt_eyebox_window_sums(const float *eb, int64_t n_slabs,
     HIP_TRY(hipGetLastError());
     return WGRT_OK;
 }
+
+// The plan of the trace's window-table sink (wgrt_trace_windows; the sink itself is eyebox_add,
+// wgrt_exact_lane.h): the mask as one bit per tap and the window grid (wgrt_window.h), copied to the device once.
+extern "C" wgrt_status wgrt_window_plan_create(const float *mask, int32_t ms, int32_t step_y, int32_t step_x,
+                                               int device, wgrt_window_plan **out) {
+    if (!out) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL out");
+    *out = nullptr;
+    wgrt_window_plan *p = new wgrt_window_plan;
+    if (const char *why = window_plan_view(mask, ms, step_y, step_x, p->host)) {
+        delete p;
+        return fail(WGRT_ERR_INVALID_ARGUMENT, why);
+    }
+    p->device = device;
+    DeviceScope scope(device);
+    hipError_t e = scope.error();
+    if (e == hipSuccess) e = hipMalloc((void **)&p->d_view, sizeof(WindowPlanView));
+    if (e == hipSuccess) e = hipMemcpy(p->d_view, &p->host, sizeof(WindowPlanView), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(p->d_view);
+        delete p;
+        return malloc_status(e, "wgrt_window_plan_create");
+    }
+    *out = p;
+    return WGRT_OK;
+}
+
+extern "C" wgrt_status wgrt_window_plan_destroy(wgrt_window_plan *plan) {
+    if (!plan) return WGRT_OK;
+    DEVICE_SCOPE(dev_scope, plan->device);
+    (void)hipFree(plan->d_view);
+    delete plan;
+    return WGRT_OK;
+}
+
+extern "C" int64_t wgrt_window_plan_width(const wgrt_window_plan *plan) { return plan ? plan->host.W : -1; }
 
 // ---------------------------------------------------------------------------------------------
 // Eyebox collection of the strong-scaling gather (wgrt_eyebox_pack / wgrt_eyebox_assemble): row copies

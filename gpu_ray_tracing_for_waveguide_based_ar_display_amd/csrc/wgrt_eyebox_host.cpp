@@ -1,5 +1,6 @@
-// wgrt_eyebox_host.cpp -- wgrt_eyebox_evaluate_host: the host replica of wgrt_eyebox_evaluate (test hook, needs
-// no GPU).  The pixel function is the one the kernels compile (wgrt_colour.h) and every sum is taken in the
+// wgrt_eyebox_host.cpp -- the eyebox's host-only test hooks (no GPU needed): wgrt_eyebox_evaluate_host and, at the
+// end of the file, the window-table sink's (wgrt_window_plan_validate, wgrt_window_table_host).
+// wgrt_eyebox_evaluate_host is the host replica of wgrt_eyebox_evaluate.  The pixel function is the one the kernels compile (wgrt_colour.h) and every sum is taken in the
 // kernels' order: a position's column over a tile's FoVs in FoV order, the tiles in kEvFoldGroups contiguous
 // groups in tile order, the groups in group order, the totals in position order.  What differs from the
 // device is the libm behind pow / cbrt / hypot / atan2 / sin / cos / exp, and nothing else.
@@ -9,6 +10,7 @@
 
 #include "../../include/wgrt.h"
 #include "wgrt_colour.h"
+#include "wgrt_window.h"
 
 namespace wgrt {
 wgrt_status fail(wgrt_status s, const std::string &msg);   // wgrt_rays.hip, beside wgrt_last_error
@@ -100,5 +102,25 @@ extern "C" wgrt_status wgrt_eyebox_evaluate_host(const double *sums, int64_t n_f
                 else image[f * 3 + c] = rgb[c];
             }
         }
+    return WGRT_OK;
+}
+
+// The window-table sink on the host (test hooks): the plan check of wgrt_window_plan_create, and the table a
+// list of hits leaves, through the membership code the trace kernels compile (wgrt_window.h).
+extern "C" wgrt_status wgrt_window_plan_validate(const float *mask, int32_t ms, int32_t step_y, int32_t step_x) {
+    WindowPlanView v;
+    if (const char *why = window_plan_view(mask, ms, step_y, step_x, v)) return fail(WGRT_ERR_INVALID_ARGUMENT, why);
+    return WGRT_OK;
+}
+
+extern "C" wgrt_status wgrt_window_table_host(const float *mask, int32_t ms, int32_t step_y, int32_t step_x,
+                                              const int64_t *offsets, int64_t n, int64_t n_slabs, double *table) {
+    WindowPlanView v;
+    if (const char *why = window_plan_view(mask, ms, step_y, step_x, v)) return fail(WGRT_ERR_INVALID_ARGUMENT, why);
+    if (n < 0 || n_slabs < 0) return fail(WGRT_ERR_INVALID_ARGUMENT, "need n >= 0 and n_slabs >= 0");
+    if (n > 0 && (!offsets || (n_slabs > 0 && !table))) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL argument");
+    const int64_t total = n_slabs * kEbSlabCells;
+    for (int64_t k = 0; k < n; ++k)
+        if (offsets[k] >= 0 && offsets[k] < total) window_visit(v, offsets[k], [table](int64_t e) { table[e] += 1.0; });
     return WGRT_OK;
 }

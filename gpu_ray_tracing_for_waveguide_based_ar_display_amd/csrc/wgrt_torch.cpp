@@ -1,4 +1,5 @@
-// wgrt_torch.cpp -- the bounce kernel as a PyTorch-ROCm operator: torch.ops.wgrt.trace.
+// wgrt_torch.cpp -- the bounce kernel as PyTorch-ROCm operators: torch.ops.wgrt.trace and, with the pupil-window
+// table as a second sink (wgrt_trace_windows), torch.ops.wgrt.trace_windows.
 //
 // The launch path the Python layer takes for torch tensors (engine.trace_fullcolor / trace_single):
 // one call of process_rays_kernel_pro_fullColor[blocks, tpb](...) or process_rays_kernel_pro[...]
@@ -13,10 +14,15 @@
 // Python layer loaded it (RTLD_GLOBAL, _lib.load) -- the in-tree build or the one WGRT_LIB names,
 // so the operator and the ctypes entry points always share one library and one set of scenes.  The
 // extension is linked with -z now, so loading it without libwgrt fails at load time, not mid-call.
+// The window sink's entry points arrived within ABI 9 and are looked up by name at the first trace_windows
+// call (as _lib.load binds them), so the operator library still loads over an earlier ABI-9 build of libwgrt
+// (tools/with_lib.py), where trace keeps working and trace_windows raises.
 #include <torch/library.h>
 
 #include <ATen/core/Tensor.h>
 #include <c10/core/DeviceGuard.h>
+
+#include <dlfcn.h>
 
 #include <cstdint>
 #include <optional>
@@ -53,12 +59,29 @@ void *u32(const Tensor &t, const char *name, const Ctx &c, int64_t need) {
     return t.data_ptr();
 }
 
-int64_t trace(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
-              const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
-              Tensor rng_states, Tensor matrix_EB, std::optional<Tensor> stats, std::optional<Tensor> per_ray_bounces,
-              int64_t n_rays, int64_t gid_offset, int64_t stream, int64_t kernel, int64_t variant, int64_t workgroups,
-              const std::optional<Tensor> &chunk_order, int64_t num_iter, const std::optional<Tensor> &gid_blocks,
-              int64_t gid_block_rays, int64_t debug, double grid_sqrt_k) {
+// wgrt_trace_windows / wgrt_window_plan_width of the loaded libwgrt.so (global scope), or an error.
+struct WindowAbi {
+    decltype(&wgrt_trace_windows) trace;
+    decltype(&wgrt_window_plan_width) width;
+};
+const WindowAbi &window_abi() {
+    static const WindowAbi abi{reinterpret_cast<decltype(&wgrt_trace_windows)>(dlsym(RTLD_DEFAULT, "wgrt_trace_windows")),
+                               reinterpret_cast<decltype(&wgrt_window_plan_width)>(
+                                   dlsym(RTLD_DEFAULT, "wgrt_window_plan_width"))};
+    TORCH_CHECK(abi.trace && abi.width, "wgrt.trace_windows: the loaded libwgrt.so has no wgrt_trace_windows (a build "
+                                        "from before the window-table sink)");
+    return abi;
+}
+
+// Both operators: trace (the grid alone: plan 0, no table) and trace_windows (the grid, the window table of
+// plan `plan` -- a wgrt_window_plan handle -- or both).
+int64_t trace_impl(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
+                   const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
+                   Tensor rng_states, std::optional<Tensor> matrix_EB, std::optional<Tensor> stats,
+                   std::optional<Tensor> per_ray_bounces, int64_t n_rays, int64_t gid_offset, int64_t stream,
+                   int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
+                   int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
+                   double grid_sqrt_k, int64_t plan, std::optional<Tensor> table) {
     const wgrt_scene *s = reinterpret_cast<const wgrt_scene *>(static_cast<uintptr_t>(scene));
     TORCH_CHECK(s != nullptr, "wgrt.trace: NULL scene");
     wgrt_scene_info info{};
@@ -85,11 +108,27 @@ int64_t trace(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, 
     r.delta_phase = column(delta_phase, "delta_phase", c);
 
     uint32_t *rng = static_cast<uint32_t *>(u32(rng_states, "rng_states", c, c.rays));
-    on_device(matrix_EB, "matrix_EB", c);
-    TORCH_CHECK(matrix_EB.scalar_type() == at::kFloat, "wgrt.trace: matrix_EB must be float32");
-    const int64_t eb_want = (int64_t)info.tiles * 80 * 120;   // [L,] NY, NX, 80, 120
-    TORCH_CHECK(matrix_EB.numel() == eb_want, "wgrt.trace: matrix_EB holds ", matrix_EB.numel(),
-                " floats, the scene's grid has ", eb_want);
+    TORCH_CHECK(matrix_EB.has_value() || table.has_value(), "wgrt.trace: needs matrix_EB, a window table, or both");
+    float *eb = nullptr;
+    if (matrix_EB) {
+        on_device(*matrix_EB, "matrix_EB", c);
+        TORCH_CHECK(matrix_EB->scalar_type() == at::kFloat, "wgrt.trace: matrix_EB must be float32");
+        const int64_t eb_want = (int64_t)info.tiles * 80 * 120;   // [L,] NY, NX, 80, 120
+        TORCH_CHECK(matrix_EB->numel() == eb_want, "wgrt.trace: matrix_EB holds ", matrix_EB->numel(),
+                    " floats, the scene's grid has ", eb_want);
+        eb = matrix_EB->data_ptr<float>();
+    }
+    const wgrt_window_plan *wp = reinterpret_cast<const wgrt_window_plan *>(static_cast<uintptr_t>(plan));
+    double *tab = nullptr;
+    if (table) {
+        const int64_t W = window_abi().width(wp);
+        TORCH_CHECK(W > 0, "wgrt.trace: a window table needs its plan");
+        on_device(*table, "table", c);
+        TORCH_CHECK(table->scalar_type() == at::kDouble, "wgrt.trace: table must be float64");
+        TORCH_CHECK(table->dim() == 2 && table->size(0) == info.tiles && table->size(1) == W,
+                    "wgrt.trace: table must have shape [", info.tiles, ", ", W, "], got ", table->sizes());
+        tab = table->data_ptr<double>();
+    }
     wgrt_trace_stats *stp = nullptr;
     if (stats) {
         on_device(*stats, "stats", c);
@@ -125,8 +164,20 @@ int64_t trace(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, 
     // test / profiling hooks: the address of a wgrt_debug_opts record the caller keeps alive (0: none)
     o.debug = reinterpret_cast<const wgrt_debug_opts *>(static_cast<uintptr_t>(debug));
     o.grid_sqrt_k = grid_sqrt_k;
-    return wgrt_trace_opts(s, &r, n_rays, gid_offset, rng, matrix_EB.data_ptr<float>(), stp, per,
-                           reinterpret_cast<void *>(static_cast<uintptr_t>(stream)), &o);
+    void *const hip_stream = reinterpret_cast<void *>(static_cast<uintptr_t>(stream));
+    if (!tab) return wgrt_trace_opts(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o);
+    return window_abi().trace(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o, wp, tab);
+}
+
+int64_t trace(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
+              const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
+              Tensor rng_states, Tensor matrix_EB, std::optional<Tensor> stats, std::optional<Tensor> per_ray_bounces,
+              int64_t n_rays, int64_t gid_offset, int64_t stream, int64_t kernel, int64_t variant, int64_t workgroups,
+              const std::optional<Tensor> &chunk_order, int64_t num_iter, const std::optional<Tensor> &gid_blocks,
+              int64_t gid_block_rays, int64_t debug, double grid_sqrt_k) {
+    return trace_impl(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats, per_ray_bounces,
+                      n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
+                      gid_block_rays, debug, grid_sqrt_k, 0, std::nullopt);
 }
 
 }  // namespace
@@ -138,4 +189,12 @@ TORCH_LIBRARY(wgrt, m) {
           "int workgroups, Tensor? chunk_order, int num_iter, Tensor? gid_blocks, int gid_block_rays, int debug, "
           "float grid_sqrt_k) -> int",
           &trace);
+    // the same launch with the window table as a second sink (wgrt_trace_windows): matrix_EB optional, plan a
+    // wgrt_window_plan handle, table float64 [tiles, W]
+    m.def("trace_windows(int scene, Tensor x, Tensor y, Tensor m, Tensor n, Tensor? lmd_num, Tensor te, Tensor tm, "
+          "Tensor delta_phase, Tensor(a!) rng_states, Tensor(b!)? matrix_EB, Tensor(c!)? stats, "
+          "Tensor(d!)? per_ray_bounces, int n_rays, int gid_offset, int stream, int kernel, int variant, "
+          "int workgroups, Tensor? chunk_order, int num_iter, Tensor? gid_blocks, int gid_block_rays, int debug, "
+          "float grid_sqrt_k, int plan, Tensor(e!)? table) -> int",
+          &trace_impl);
 }

@@ -1040,6 +1040,9 @@ struct LaunchCfg {
     bool learn = false;    // set by plan_auto_order: this launch runs the learning instantiation ...
     bool auto_order = false;   // ... and / or is issued in the automatic order, built from the tile table as
     uint32_t order_gen = 0;    // it stood after this many learning launches
+    // wgrt_trace_windows: the window table the out-couplings count into and its plan's device view (NULL: none)
+    double *win_table = nullptr;
+    const WindowPlanView *win = nullptr;
 };
 
 // wgrt_debug_set_auto_order: the automatic issue order (and its learning launches) on / off, process-wide.
@@ -1122,7 +1125,8 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
                 (dbg->timeline && dbg->timeline_waves < 0)))
         return fail(WGRT_ERR_INVALID_ARGUMENT, "bad wgrt_debug_opts");
     if (n_rays == 0) return WGRT_OK;
-    if (!ray_columns_present(rays, single) || !rng_states || !matrix_EB)
+    // (with a window table, wgrt_trace_windows, the grid is optional)
+    if (!ray_columns_present(rays, single) || !rng_states || (!matrix_EB && !c.win_table))
         return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL ray column / rng_states / matrix_EB");
     if (c.variant == 7 && !s->d_cells32) return fail(WGRT_ERR_UNSUPPORTED, "variant 7 needs <= 16 polygons");
     if (c.variant >= 7 && n_rays > 0xffffffffll)
@@ -1150,6 +1154,8 @@ TraceArgs fill_args(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, 
     A.order = c.chunk_order;   // a permutation of the 64-ray chunks (trusted device data)
     A.rng = rng_states;
     A.eb = matrix_EB;
+    A.win_table = c.win_table;
+    A.win = c.win;
     A.stats = stats;
     A.per_ray = per_ray_bounces;
     A.n_rays = n_rays;
@@ -1335,9 +1341,10 @@ wgrt_status wgrt_trace_fullcolor(const wgrt_scene *s, const wgrt_rays *rays, int
                         cfg_of(0, 0, false));
 }
 
-wgrt_status wgrt_trace_opts(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
-                            uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats,
-                            uint32_t *per_ray_bounces, void *stream, const wgrt_launch_opts *opts) {
+wgrt_status wgrt_trace_windows(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
+                               uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats,
+                               uint32_t *per_ray_bounces, void *stream, const wgrt_launch_opts *opts,
+                               const wgrt_window_plan *plan, double *table) {
     if (!opts) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL opts");
     if (opts->kernel != 0 && opts->kernel != 1) return fail(WGRT_ERR_INVALID_ARGUMENT, "kernel must be 0 or 1");
     LaunchCfg c = cfg_of(opts->variant, opts->workgroups, opts->kernel == 1);
@@ -1349,7 +1356,23 @@ wgrt_status wgrt_trace_opts(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
     c.dbg = opts->debug;
     c.grid_k = opts->grid_sqrt_k;
     if (!(c.grid_k == c.grid_k)) return fail(WGRT_ERR_INVALID_ARGUMENT, "grid_sqrt_k is NaN");
+    if (table) {   // (without a table the call is wgrt_trace_opts, and the plan is not looked at)
+        if (!plan) return fail(WGRT_ERR_INVALID_ARGUMENT, "a window table needs its wgrt_window_plan");
+        if (s && plan->device != s->device)
+            return fail(WGRT_ERR_INVALID_ARGUMENT, "the window plan lives on device " + std::to_string(plan->device) +
+                                                       ", the scene on device " + std::to_string(s->device));
+        if ((uintptr_t)table & 7) return fail(WGRT_ERR_INVALID_ARGUMENT, "table must be 8-B aligned");
+        c.win_table = table;
+        c.win = plan->d_view;
+    }
     return trace_launch(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, c);
+}
+
+wgrt_status wgrt_trace_opts(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
+                            uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats,
+                            uint32_t *per_ray_bounces, void *stream, const wgrt_launch_opts *opts) {
+    return wgrt_trace_windows(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, opts,
+                              nullptr, nullptr);
 }
 
 wgrt_status wgrt_trace_single_ex(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,

@@ -191,7 +191,8 @@ def run_steps(trace_fn, rays, rng, eb, gid: GidMap, steps: int, per_call: int = 
     """The reference's loop of chained launches (MAIN:169-177) over one shard: ``steps`` traces
     of every ray, each starting from the RNG states the previous one left, issued as calls of
     at most ``per_call`` traces (``trace_fn(..., num_iter=k)``; a fused call gives the results
-    of k separate ones).  ``hook(j, "start" | "end")`` brackets call j (HIP events in bench.py).
+    of k separate ones).  ``eb`` is handed to ``trace_fn`` as it is: None for a tracer that carries the
+    window-table sink alone (``hip_tracer(windows=...)``).  ``hook(j, "start" | "end")`` brackets call j (HIP events in bench.py).
     Returns the traces per call."""
     calls = split_calls(steps, per_call)
     for j, k in enumerate(calls):
@@ -473,17 +474,22 @@ def timed_run(trace_fn, rays, rng, eb, gid: GidMap, steps: int, per_call: int, s
     return float(t.item()), int(b.item()), local
 
 
-def hip_tracer(scene, variant: int = 0, stats=None):
+def hip_tracer(scene, variant: int = 0, stats=None, windows=None):
     """trace_fn for ``run_steps`` / ``trace_job`` using the HIP kernel (torch device tensors); ``stats``
     (int64[STATS_LEN] device tensor) is added to by every call.  A shard of several block ranges passes its global
-    ids as ``gid_blocks``, uploaded once per map and device and kept on the map (``GidMap.device_blocks``)."""
+    ids as ``gid_blocks``, uploaded once per map and device and kept on the map (``GidMap.device_blocks``).
+
+    ``windows=(plan, table)``: every call also counts its out-couplings into the pupil-window table
+    (``engine.trace_fullcolor(windows=...)``), and ``eb`` may be None -- a grid-free job.  Every rank's table is
+    the full ``[n_slabs, W]`` with its top-edge spills already in the slabs they alias into, so the collective
+    of such a job is ``reduce_eyebox(table)``, one sum-reduce: no slab list, no scatter."""
     from .engine import trace_fullcolor
 
     def fn(rays, rng, eb, gid: GidMap, num_iter=1):
         off = gid.offset
         ids = dict(gid_offset=off) if off is not None else dict(gid_blocks=gid.device_blocks(rng.device),
                                                                 gid_block_rays=gid.rays_per_block)
-        trace_fullcolor(scene, rays, rng, eb, stats=stats, variant=variant, num_iter=num_iter, **ids)
+        trace_fullcolor(scene, rays, rng, eb, stats=stats, variant=variant, num_iter=num_iter, windows=windows, **ids)
     return fn
 
 

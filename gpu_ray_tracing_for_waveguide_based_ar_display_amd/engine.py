@@ -48,12 +48,12 @@ def rays_to_device(rays: dict, device="cuda") -> dict:
             for k in RAY_COLUMNS if k in rays}
 
 
-def trace_fullcolor(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_EB: torch.Tensor,
+def trace_fullcolor(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_EB: torch.Tensor | None,
                     gid_offset: int = 0, n_rays: int | None = None, stats: torch.Tensor | None = None,
                     per_ray_bounces: torch.Tensor | None = None, stream=None, variant: int = VARIANT_AUTO,
                     workgroups: int = 0, chunk_order: torch.Tensor | None = None, num_iter: int = 1,
                     gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
-                    grid_sqrt_k: float = 0.0) -> None:
+                    grid_sqrt_k: float = 0.0, windows=None) -> None:
     """Asynchronous launch on ``stream`` (default: torch's current stream).
 
     rays: dict of device float32 tensors keyed like the reference columns
@@ -70,13 +70,16 @@ def trace_fullcolor(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_E
     ``gid_block_rays`` rays; ``gid_offset`` must then be 0).  debug: ``wgrt_debug_opts`` fields
     (cert_tol, cert_tol32, chunk_rays, timeline (uint64 device tensor), fail_after_trace,
     handoff_wait_ticks) -- test / profiling hooks.  grid_sqrt_k: the single-trace grid rule
-    (``wgrt_launch_opts.grid_sqrt_k``; 0 the default, < 0 the resident grid).
+    (``wgrt_launch_opts.grid_sqrt_k``; 0 the default, < 0 the resident grid).  windows: ``(plan, table)``, a
+    ``WindowPlan`` and a float64 ``[n_slabs, plan.W]`` device tensor (``plan.new_table(scene)``) that every
+    out-coupling is also counted into (``wgrt_trace_windows``: the table equals ``eyebox_window_sums`` of the grid
+    the same trace leaves); ``matrix_EB`` may then be None, and no grid is written.
     """
     if scene.single_lambda:
         raise ValueError("trace_fullcolor needs a full-colour scene; use trace_single for a single-wavelength one")
     _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single=False, chunk_order=chunk_order, num_iter=num_iter, gid_blocks=gid_blocks,
-           gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k)
+           gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows)
 
 
 def new_stats(device) -> torch.Tensor:
@@ -114,21 +117,65 @@ def reserve(scene: Scene, n_rays: int, num_iter: int = 1, stream=None) -> None:
                                     ctypes.c_void_p(_stream_handle(device, stream))), "wgrt_scene_reserve")
 
 
-def trace_single(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_EB: torch.Tensor,
+def trace_single(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_EB: torch.Tensor | None,
                  gid_offset: int = 0, n_rays: int | None = None, stats: torch.Tensor | None = None,
                  per_ray_bounces: torch.Tensor | None = None, stream=None, variant: int = VARIANT_AUTO,
                  workgroups: int = 0, chunk_order: torch.Tensor | None = None, num_iter: int = 1,
                  gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
-                 grid_sqrt_k: float = 0.0) -> None:
+                 grid_sqrt_k: float = 0.0, windows=None) -> None:
     """One launch of the single-wavelength kernel (``process_rays_kernel_pro``, GRTF:419-831)
     through ``wgrt_trace_single_ex``: no ``lmd_num`` column (ignored if present),
     matrix_EB [NY, NX, 80, 120], branch guard ener * efficiency > 1e-15.  The scene must be
-    a single-wavelength one (``Scene.from_geometry(..., wavelength=l)`` or 3-D LUTs)."""
+    a single-wavelength one (``Scene.from_geometry(..., wavelength=l)`` or 3-D LUTs).  ``windows``: as
+    ``trace_fullcolor``."""
     if not scene.single_lambda:
         raise ValueError("trace_single needs a single-wavelength scene (Scene.from_geometry(..., wavelength=l))")
     _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single=True, chunk_order=chunk_order, num_iter=num_iter, gid_blocks=gid_blocks,
-           gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k)
+           gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows)
+
+
+class WindowPlan:
+    """The plan of the trace's window-table sink (``wgrt_window_plan``): a binary pupil ``mask`` (default
+    ``pupil_mask()``) and the eye-position steps (8 / 12), uploaded to ``device`` once.  ``W = 1 + npy * npx``
+    is the table's width (57 by default); ``new_table(scene)`` a zeroed float64 ``[n_slabs, W]`` table on the
+    scene's device, in the layout of ``eyebox_window_sums``.  A mask with a tap other than 0 or 1 raises
+    (``eyebox_window_sums`` serves it from a grid)."""
+
+    def __init__(self, mask=None, step_y: int = 8, step_x: int = 12, device: int = 0):
+        from .AR_system_evaluation_functions import _square_mask
+        self.mask = _square_mask(mask)
+        self.ms, self.step_y, self.step_x, self.device = int(self.mask.shape[0]), int(step_y), int(step_x), int(device)
+        self._h = None
+        L = load()
+        h = ctypes.c_void_p()
+        check(L.wgrt_window_plan_create(self.mask.ctypes.data, self.ms, self.step_y, self.step_x, self.device,
+                                        ctypes.byref(h)), "wgrt_window_plan_create")
+        self._h = h
+        self.W = int(L.wgrt_window_plan_width(h))
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise WgrtError("window plan destroyed")
+        return self._h
+
+    def new_table(self, scene: Scene) -> torch.Tensor:
+        if scene.device != self.device:
+            raise ValueError(f"the plan is on device {self.device}, the scene on device {scene.device}")
+        n_slabs = scene.num_lmd * scene.ny * scene.nx
+        return torch.zeros((n_slabs, self.W), dtype=torch.float64, device=torch.device("cuda", scene.device))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            load().wgrt_window_plan_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _debug_opts(debug: dict | None):
@@ -172,13 +219,22 @@ def _read_columns(rays, rng_states, n_rays, single, device):
 
 def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single, chunk_order=None, num_iter=1, gid_blocks=None, gid_block_rays=0, debug=None,
-           grid_sqrt_k=0.0):
+           grid_sqrt_k=0.0, windows=None):
     device = torch.device("cuda", scene.device)
     cols, N = _read_columns(rays, rng_states, n_rays, single, device)
     x = cols["x"]
-    _as_dev(matrix_EB, torch.float32, "matrix_EB", device)
-    if tuple(matrix_EB.shape) != scene.eb_shape():
-        raise ValueError(f"matrix_EB shape {tuple(matrix_EB.shape)} != {scene.eb_shape()}")
+    if matrix_EB is None and windows is None:
+        raise ValueError("matrix_EB=None needs windows=(plan, table)")
+    if matrix_EB is not None:
+        _as_dev(matrix_EB, torch.float32, "matrix_EB", device)
+        if tuple(matrix_EB.shape) != scene.eb_shape():
+            raise ValueError(f"matrix_EB shape {tuple(matrix_EB.shape)} != {scene.eb_shape()}")
+    if windows is not None:
+        plan, table = windows
+        _as_dev(table, torch.float64, "windows table", device)
+        want = (scene.num_lmd * scene.ny * scene.nx, plan.W)
+        if tuple(table.shape) != want:
+            raise ValueError(f"windows table shape {tuple(table.shape)} != {want}")
     if stats is not None:
         _as_dev(stats, torch.int64, "stats", device, STATS_LEN)
     if per_ray_bounces is not None:
@@ -193,13 +249,18 @@ def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ra
             raise ValueError("gid_blocks needs gid_block_rays >= 1")
         _as_dev(gid_blocks, torch.int64, "gid_blocks", device, (N + gid_block_rays - 1) // gid_block_rays if N else None)
     dbg = _debug_opts(debug)
-    # the launch: torch.ops.wgrt.trace (csrc/wgrt_torch.cpp) -> wgrt_trace_opts on the caller's stream
-    status = ops().trace(scene.handle.value, cols["x"], cols["y"], cols["m"], cols["n"], cols.get("lmd_num"),
-                         cols["te"], cols["tm"], cols["delta_phase"], rng_states, matrix_EB, stats, per_ray_bounces,
-                         N, int(gid_offset), _stream_handle(device, stream), 1 if single else 0, int(variant),
-                         int(workgroups), chunk_order, int(num_iter), gid_blocks,
-                         int(gid_block_rays) if gid_blocks is not None else 0,
-                         ctypes.addressof(dbg) if dbg is not None else 0, float(grid_sqrt_k))
+    # the launch: torch.ops.wgrt.trace (csrc/wgrt_torch.cpp) -> wgrt_trace_opts on the caller's stream; with a
+    # window table torch.ops.wgrt.trace_windows -> wgrt_trace_windows
+    args = (scene.handle.value, cols["x"], cols["y"], cols["m"], cols["n"], cols.get("lmd_num"),
+            cols["te"], cols["tm"], cols["delta_phase"], rng_states, matrix_EB, stats, per_ray_bounces,
+            N, int(gid_offset), _stream_handle(device, stream), 1 if single else 0, int(variant),
+            int(workgroups), chunk_order, int(num_iter), gid_blocks,
+            int(gid_block_rays) if gid_blocks is not None else 0,
+            ctypes.addressof(dbg) if dbg is not None else 0, float(grid_sqrt_k))
+    if windows is None:
+        status = ops().trace(*args)
+    else:
+        status = ops().trace_windows(*args, plan.handle.value, table)
     check(status, "wgrt_trace_single" if single else "wgrt_trace_fullcolor")
 
 
@@ -370,6 +431,6 @@ def selftest_math(a: torch.Tensor, b: torch.Tensor, stream=None) -> torch.Tensor
     return out
 
 
-__all__ = ["Scene", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
+__all__ = ["Scene", "WindowPlan", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
            "trace_fullcolor", "trace_single", "init_rays", "schedule_by_lifetime",
            "rays_to_device", "classify_points", "shadow", "selftest_math", "RAY_COLUMNS", "_lib"]

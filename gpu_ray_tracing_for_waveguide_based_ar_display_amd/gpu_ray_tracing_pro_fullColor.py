@@ -16,14 +16,16 @@ Same flow as the reference script, on the MI355X kernel:
    and ``evaluation(EB / R / num_iter)`` (MAIN:197-198) -- on the host from the copied-back grid as the
    reference does, or (``eyebox="device"``, ``--eyebox device``) from the per-slab window sums one device pass
    leaves (``eyebox_window_sums``), without the grid leaving the GPU; with ``evaluate_on="device"``
-   (``--evaluate device``) the table stays there too and the colour math runs in ``wgrt_eyebox_evaluate``;
+   (``--evaluate device``) the table stays there too and the colour math runs in ``wgrt_eyebox_evaluate``; or
+   (``eyebox="windows"``, ``--eyebox windows``) from the same table counted by the trace itself
+   (``wgrt_trace_windows``), with no grid allocated at all;
 6. the "Eyebox Center View.png" export (MAIN:199-203): the evaluated image at the first eye row,
    last eye column, as 8-bit RGB, rows flipped (``eyebox_center_view``, written without OpenCV).
 
 The matplotlib plots (MAIN:213-237) are visual-only and not reproduced.
 Multi-GPU: run under ``torch.distributed.run``; each rank traces an interleaved set of FoV x
 wavelength blocks and the eyebox slabs are gathered to rank 0 (``distributed.py``); in device mode the ranks'
-window sums are sum-reduced instead (``distributed.EyeboxReduce``).
+window sums are sum-reduced instead (``distributed.EyeboxReduce``; in windows mode the ranks' tables as they are).
 """
 from __future__ import annotations
 
@@ -65,22 +67,31 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
     ``num_rays_per_FoV * num_iter < 2^24``; the evaluation divides the exact float64 window sums once where
     the host mode divides and sums in float32 (at most 902 * 2^-24 relative per eye position).
 
+    ``"windows"``: the trace counts every out-coupling straight into that table (``engine.WindowPlan``,
+    ``wgrt_trace_windows``): no grid is allocated, zeroed, scattered into or read back (864 MB at the default job
+    against the table's 10 MB), several GPUs sum-reduce their tables as they are, and everything after the trace
+    is device mode's, fed the same table bit for bit.  There is no grid to keep: ``keep_grid=True`` raises.
+
     ``evaluate_on``: where the colour math of the evaluation runs.  ``"host"``: ``evaluation_from_perceive`` in
-    numpy.  ``"device"`` (needs ``eyebox="device"``): the window-sum table (rank 0's, after ``EyeboxReduce``,
-    on several GPUs) is evaluated where it lives (``evaluation_from_window_sums``); only the three figures and
+    numpy.  ``"device"`` (needs ``eyebox="device"`` or ``"windows"``): the window-sum table (rank 0's, after the
+    reduce, on several GPUs) is evaluated where it lives (``evaluation_from_window_sums``); only the three figures and
     the centre image come back, ``center_view`` and the PNG are built from that image, and ``output_image``
     (every eye position's image) is returned only with ``keep_image=True``."""
-    for name, where in (("eyebox", eyebox), ("evaluate_on", evaluate_on)):
-        if where not in ("host", "device"):
-            raise ValueError(f"{name} must be 'host' or 'device', got {where!r}")
-    if evaluate_on == "device" and eyebox != "device":
-        raise ValueError("evaluate_on='device' evaluates the on-device window sums: it needs eyebox='device'")
+    if eyebox not in ("host", "device", "windows"):
+        raise ValueError(f"eyebox must be 'host', 'device' or 'windows', got {eyebox!r}")
+    if evaluate_on not in ("host", "device"):
+        raise ValueError(f"evaluate_on must be 'host' or 'device', got {evaluate_on!r}")
+    if evaluate_on == "device" and eyebox == "host":
+        raise ValueError("evaluate_on='device' evaluates the on-device window sums: it needs eyebox='device' "
+                         "or 'windows'")
+    if eyebox == "windows" and keep_grid:
+        raise ValueError("eyebox='windows' traces without a grid: there is none to keep (keep_grid=True)")
     from .engine import STAT
     with _set_up(num_FOV_x, num_FOV_y, int(num_rays_per_FoV), num_iter, lambdas, lut_dir, lut_seed, lut_profile,
-                 point_seed, points, verbose) as job:   # closes the scene on every way out
+                 point_seed, points, verbose, eyebox == "windows") as job:   # closes the scene on every way out
         kern_s = _trace(job, variant, fuse)
         t_post = time.perf_counter()   # everything below is post-processing of the traced grid
-        grid, table, stats = _collect(job, eyebox == "device", keep_grid)
+        grid, table, stats = _collect(job, eyebox != "host", keep_grid)
         out = dict(num_rays=job.num_rays, num_iter=num_iter, gpu_seconds=kern_s, bounces=int(stats[STAT.bounces]),
                    eyebox_hits=int(stats[STAT.eyebox_hits]), rng_states=job.rng.cpu().numpy().view(np.uint32))
         if job.rank != 0:
@@ -89,20 +100,23 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
         if evaluate:
             _evaluate(job, out, grid, table, evaluate_on, keep_image, png)
         out["post_seconds"] = time.perf_counter() - t_post
-        job.say(f"Post-processing time  : {out['post_seconds']:.4f} s  (eyebox reduced on the {eyebox})")
+        job.say(f"Post-processing time  : {out['post_seconds']:.4f} s  (eyebox reduced "
+                f"{'by the trace' if eyebox == 'windows' else 'on the ' + eyebox})")
         return out
 
 
 @contextlib.contextmanager
-def _set_up(nx, ny, R, num_iter, lambdas, lut_dir, lut_seed, lut_profile, point_seed, points, verbose):
+def _set_up(nx, ny, R, num_iter, lambdas, lut_dir, lut_seed, lut_profile, point_seed, points, verbose,
+            windows: bool = False):
     """Steps 1-3: geometry, LUTs, the scene, the origins (rank 0's on every rank), every rank's shard and this
-    rank's rays, as the record the later stages read; the scene is closed when the ``with`` block ends."""
+    rank's rays, as the record the later stages read; the scene is closed when the ``with`` block ends.
+    ``windows``: a zeroed window table (``job.windows = (plan, table)``) instead of the grid (``job.eb`` None)."""
     import torch
     import torch.distributed as dist
 
     from .couplers_coor import design_geometry
     from .distributed import hip_shard_builder, make_shard
-    from .engine import Scene, new_stats
+    from .engine import Scene, WindowPlan, new_stats
     from .luts import load_luts, lut_f32_mask, synthetic_luts, validate_luts
     from .rays import generate_points_in_polygon
 
@@ -132,12 +146,18 @@ def _set_up(nx, ny, R, num_iter, lambdas, lut_dir, lut_seed, lut_profile, point_
         # ray columns and RNG seeds built on the device (MAIN:59-158 without the host arrays:
         # 48 B x N of host memory and its upload at the reference's 100 x 75 x 3 x 5000 default)
         rays, rng = hip_shard_builder(points, nx, ny, lambdas, R, dev)(shards[rank])
-        eb = torch.zeros(scene.eb_shape(), dtype=torch.float32, device=dev)
+        eb = None if windows else torch.zeros(scene.eb_shape(), dtype=torch.float32, device=dev)
+        plan = WindowPlan(device=dev.index) if windows else None
         num_rays = nx * ny * len(lambdas) * R
         say(f"Initialization complete: {num_rays:,} rays, {world} GPU(s)\n" + "=" * 60 + "\nSTART GPU RAY TRACING\n" + "=" * 60)
-        yield SimpleNamespace(nx=nx, ny=ny, R=R, num_iter=num_iter, lambdas=lambdas, world=world, rank=rank, dev=dev,
-                              say=say, scene=scene, shards=shards, shard=shards[rank], rays=rays, rng=rng, eb=eb,
-                              stats=new_stats(dev), num_rays=num_rays)
+        try:
+            yield SimpleNamespace(nx=nx, ny=ny, R=R, num_iter=num_iter, lambdas=lambdas, world=world, rank=rank,
+                                  dev=dev, say=say, scene=scene, shards=shards, shard=shards[rank], rays=rays, rng=rng,
+                                  eb=eb, windows=(plan, plan.new_table(scene)) if windows else None,
+                                  stats=new_stats(dev), num_rays=num_rays)
+        finally:
+            if plan is not None:
+                plan.close()
 
 
 def _trace(job, variant, fuse) -> float:
@@ -155,8 +175,8 @@ def _trace(job, variant, fuse) -> float:
     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0.record()
     if n_rays:
-        run_steps(hip_tracer(job.scene, variant, job.stats), job.rays, job.rng, job.eb, job.shard.gid, job.num_iter,
-                  per_call)
+        run_steps(hip_tracer(job.scene, variant, job.stats, job.windows), job.rays, job.rng, job.eb, job.shard.gid,
+                  job.num_iter, per_call)
     t1.record()
     torch.cuda.synchronize()
     check_stats(job.stats)
@@ -170,7 +190,12 @@ def _collect(job, on_device: bool, keep_grid: bool):
     import torch.distributed as dist
 
     from .AR_system_evaluation_functions import eyebox_window_sums
-    from .distributed import EyeboxGather, EyeboxReduce
+    from .distributed import EyeboxGather, EyeboxReduce, reduce_eyebox
+    if job.windows is not None:
+        table = reduce_eyebox(job.windows[1])
+        if job.world > 1:
+            dist.all_reduce(job.stats)
+        return None, table, job.stats.cpu().numpy()
     want_grid = not on_device or keep_grid
     table = None
     if job.world > 1:
@@ -296,12 +321,13 @@ def main(argv=None):
     ap.add_argument("--fuse", choices=["auto", "yes", "no"], default="auto",
                     help="num_iter chained traces as one fused launch (auto: when a GPU traces <= 4M rays)")
     ap.add_argument("--no-fuse", action="store_true", help="same as --fuse no")
-    ap.add_argument("--eyebox", choices=["host", "device"], default="host",
+    ap.add_argument("--eyebox", choices=["host", "device", "windows"], default="host",
                     help="where the eyebox grid is reduced after the trace: host (the reference's flow: the whole "
-                         "grid is copied back) or device (per-slab pupil sums on the GPU; the grid stays there)")
+                         "grid is copied back), device (per-slab pupil sums on the GPU; the grid stays there) or "
+                         "windows (the trace counts into the pupil-sum table itself; no grid is allocated)")
     ap.add_argument("--evaluate", choices=["host", "device"], default="host",
                     help="where the evaluation's colour math runs: host (numpy) or device (wgrt_eyebox_evaluate on "
-                         "the window-sum table; needs --eyebox device)")
+                         "the window-sum table; needs --eyebox device or windows)")
     ap.add_argument("--json", default=None, help="write scalar results here")
     ap.add_argument("--png", default="Eyebox Center View.png",
                     help="the eyebox-center image (MAIN:199-203); empty string: do not write it")

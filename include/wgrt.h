@@ -343,6 +343,50 @@ wgrt_status wgrt_eyebox_evaluate_host(const double *sums, int64_t n_fov, int64_t
                                       const double *wl, const double *lab_d65, double *out, float *image,
                                       int64_t image_pos, void *workspace);
 
+/* The window-table sink (new symbols within ABI 9: no existing struct or signature changed, so
+ * WGRT_ABI_VERSION stays 9; a caller finds out whether a library has them by looking the symbols up).
+ *
+ * What anyone reads from an 80 x 120 slab of matrix_EB is its total and its pupil-window sums, the
+ * [n_slabs, W] table of wgrt_eyebox_window_sums.  wgrt_trace_windows counts every out-coupling straight into
+ * that table, so a job that only evaluates never allocates the grid (38.4 KB per slab against 8 W bytes).
+ * An out-coupling into flat grid offset off -- computed as for the grid, aliasing included (GRTF:164): the
+ * negative-index wrap, ix == 120 into the next row, iy == 80 into the next slab, dropped outside the
+ * buffer -- lies in slab s = off / 9600, row r = off % 9600 / 120, column c = off % 120, and adds 1 to
+ * table[s, 0] and to table[s, 1 + wy * npx + wx] of every window (wy, wx) with wy * step_y <= r <
+ * wy * step_y + ms, wx * step_x <= c < wx * step_x + ms and the tap mask[r - wy * step_y, c - wx * step_x]
+ * set (npy, npx, W as in wgrt_eyebox_window_sums).  The counts are integers and the window sums linear in
+ * the grid, so the table a trace leaves equals wgrt_eyebox_window_sums of the grid the same trace would have
+ * left, bit for bit, and feeds wgrt_eyebox_evaluate unchanged.
+ *
+ * A plan is the mask and the steps, on one device.  mask is a HOST float32 [ms * ms]; 1 <= ms <= 80, steps
+ * >= 1, and every tap exactly 0.0f or 1.0f (the sink adds exactly 1.0 per tap, so the sums are exact integers
+ * in any order; wgrt_eyebox_window_sums keeps serving other masks from a grid), else
+ * WGRT_ERR_INVALID_ARGUMENT with the reason in wgrt_last_error.  The device holds the mask as one bit per tap. */
+typedef struct wgrt_window_plan wgrt_window_plan;   /* opaque, device-resident */
+wgrt_status wgrt_window_plan_create(const float *mask, int32_t ms, int32_t step_y, int32_t step_x, int device,
+                                    wgrt_window_plan **out);
+wgrt_status wgrt_window_plan_destroy(wgrt_window_plan *plan);
+int64_t wgrt_window_plan_width(const wgrt_window_plan *plan);   /* W = 1 + npy * npx; -1 for NULL */
+
+/* wgrt_trace_opts with the window table as a second sink.  table: DEVICE float64 [n_slabs, W], n_slabs =
+ * num_lmd * ny * nx slabs in matrix_EB's order, accumulated into by f64 atomic adds and never zeroed; plan: a
+ * plan on the scene's device.  matrix_EB may be NULL (the table alone); with both, the same hits are written
+ * to both.  table == NULL: exactly wgrt_trace_opts (matrix_EB required, plan ignored).  Every kernel,
+ * variant and option of wgrt_trace_opts; wgrt_trace_stats.eyebox_hits counts the same hits; the call
+ * allocates nothing more and is asynchronous on stream.  Not part of the reference. */
+wgrt_status wgrt_trace_windows(const wgrt_scene *scene, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
+                               uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats,
+                               uint32_t *per_ray_bounces, void *stream, const wgrt_launch_opts *opts,
+                               const wgrt_window_plan *plan, double *table);
+
+/* Host-only (no GPU needed; test hooks) through the same membership code (csrc/wgrt_window.h):
+ * _validate is wgrt_window_plan_create's argument check alone; _table_host ADDS the n hits at flat grid
+ * offsets offsets[n] (HOST int64; those outside [0, n_slabs * 9600) are dropped, as the grid's guard drops
+ * them) to the HOST table [n_slabs, W]. */
+wgrt_status wgrt_window_plan_validate(const float *mask, int32_t ms, int32_t step_y, int32_t step_x);
+wgrt_status wgrt_window_table_host(const float *mask, int32_t ms, int32_t step_y, int32_t step_x,
+                                   const int64_t *offsets, int64_t n, int64_t n_slabs, double *table);
+
 /* Polygon membership of n points (DEVICE xy[n, 2]) through the scene's locator:
  * bit k of out_mask[i] = is_inside_or_on_edge(point i, polygon k) with polygon order
  * 0 eff_reg1, 1 eff_reg2, 2 IC, 3.. FC slices, then OC slices (GRTF:63-71).  Bit 63 is set
