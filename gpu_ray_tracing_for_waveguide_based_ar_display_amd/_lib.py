@@ -27,9 +27,11 @@ EXPORTED = ("wgrt_scene_create", "wgrt_scene_create_ex", "wgrt_scene_destroy", "
             "wgrt_abi_version", "wgrt_eyebox_payload_floats", "wgrt_eyebox_pack", "wgrt_eyebox_assemble",
             "wgrt_eyebox_window_sums", "wgrt_eyebox_evaluate_workspace_bytes", "wgrt_eyebox_evaluate",
             "wgrt_eyebox_evaluate_host", "wgrt_window_plan_create", "wgrt_window_plan_destroy",
-            "wgrt_window_plan_width", "wgrt_trace_windows", "wgrt_window_plan_validate", "wgrt_window_table_host")
+            "wgrt_window_plan_width", "wgrt_trace_windows", "wgrt_window_plan_validate", "wgrt_window_table_host",
+            "wgrt_chain_begin", "wgrt_chain_step", "wgrt_chain_end")
 EXPORTED_DEBUG = ("wgrt_debug_shadow", "wgrt_debug_scene_copy", "wgrt_debug_set_auto_order",
-                  "wgrt_debug_get_auto_order", "wgrt_debug_get_tile_tail", "wgrt_debug_order_host")
+                  "wgrt_debug_get_auto_order", "wgrt_debug_get_tile_tail", "wgrt_debug_order_host",
+                  "wgrt_debug_chain_plan", "wgrt_debug_chain_set_serial")
 
 
 class WgrtError(RuntimeError):
@@ -103,6 +105,26 @@ class ShadowStats(ctypes.Structure):
                 ("max_ratio32", ctypes.c_double),
                 ("max_ratio_by_depth", ctypes.c_double * 6), ("decisions_by_depth", ctypes.c_uint64 * 6),
                 ("ratio_hist", ctypes.c_uint64 * 20), ("max_ener_ratio", ctypes.c_double), ("max_amp", ctypes.c_double)]
+
+
+class ChainPlan(ctypes.Structure):
+    """``wgrt_chain_plan`` (include/wgrt_debug.h): where a chain's next step goes."""
+    _fields_ = [("chained", ctypes.c_int), ("side", ctypes.c_int), ("join", ctypes.c_int), ("seed", ctypes.c_int),
+                ("clear", ctypes.c_int), ("wait_serial", ctypes.c_uint32), ("publish_serial", ctypes.c_uint32),
+                ("serial_after", ctypes.c_uint32), ("in_segment_after", ctypes.c_int64)]
+
+
+# wgrt_debug_chain_plan's flags and the largest tag serial (include/wgrt_debug.h)
+CHAIN_LEARNS, CHAIN_VARIANT1, CHAIN_SINGLE, CHAIN_FUSED, CHAIN_DEBUG, CHAIN_CAPTURE, CHAIN_FULL = 1, 2, 4, 8, 16, 32, 64
+CHAIN_SERIAL_MAX = 0x7ffffffe
+
+
+def chain_plan(in_segment: int, serial: int, flags: int = 0) -> dict:
+    """``wgrt_debug_chain_plan``: the host logic of ``wgrt_chain_step`` (no GPU needed)."""
+    p = ChainPlan()
+    check(load().wgrt_debug_chain_plan(int(in_segment), int(serial), int(flags), ctypes.byref(p)),
+          "wgrt_debug_chain_plan")
+    return {f: int(getattr(p, f)) for f, _ in ChainPlan._fields_}
 
 
 class SceneInfo(ctypes.Structure):
@@ -236,6 +258,18 @@ def load():
         L.wgrt_debug_get_tile_tail.argtypes = [_vp, _vp, ctypes.c_int64]
         L.wgrt_debug_order_host.restype = st
         L.wgrt_debug_order_host.argtypes = [_vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp]
+    if hasattr(L, "wgrt_chain_begin"):   # chained single launches: new symbols within ABI 9, bound by name
+        L.wgrt_chain_begin.restype = st
+        L.wgrt_chain_begin.argtypes = [_vp, ctypes.POINTER(Rays), ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, ctypes.POINTER(_vp)]
+        L.wgrt_chain_step.restype = st
+        L.wgrt_chain_step.argtypes = [_vp]
+        L.wgrt_chain_end.restype = st
+        L.wgrt_chain_end.argtypes = [_vp]
+        L.wgrt_debug_chain_plan.restype = st
+        L.wgrt_debug_chain_plan.argtypes = [ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ChainPlan)]
+        L.wgrt_debug_chain_set_serial.restype = st
+        L.wgrt_debug_chain_set_serial.argtypes = [_vp, _vp, ctypes.c_uint32]
     L.wgrt_status_string.restype = ctypes.c_char_p
     L.wgrt_status_string.argtypes = [ctypes.c_int]
     L.wgrt_last_error.restype = ctypes.c_char_p

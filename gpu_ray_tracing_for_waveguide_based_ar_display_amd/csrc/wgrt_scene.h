@@ -31,6 +31,8 @@ struct wgrt_scene {
     int jones_grid[2][2][2] = {};   // resident 256-thread workgroups: [64-bit cells][fused][single wavelength]
     int jones_tl_grid[2] = {};      // ... of the debug timeline instantiations (32-bit cells): [fused]
     int jones_learn_grid[2] = {};   // ... of the learning instantiations (full colour, single trace): [64-bit cells]
+    int jones_chain_grid[2] = {};   // ... the most a chained step may use (wgrt_chain_*): [64-bit cells], half the
+                                    // resident grid less a margin (query_trace_grids)
     int64_t nonunitary_blocks = 0;  // Jones blocks whose branch matrices are not scaled-unitary (their launches
                                     // run the AMP instantiations: wgrt_jones_lane.h, the amplification step)
     // The automatic issue order's statistic (wgrt_order.h): per (wavelength, FoV) tile, the traces of the
@@ -65,6 +67,17 @@ struct wgrt_scene {
         int64_t order_rays = -1;             // -1: none built
         const float *order_m = nullptr, *order_n = nullptr, *order_l = nullptr;
         uint32_t order_gen = 0;
+        // chained single launches (wgrt_chain_*, caller's stream S = this scratch's key): the library-owned
+        // side stream T (hipStreamNonBlocking; its launch scratch is the map's entry for T), the events of a
+        // segment's two ends, and the per-ray {state, tag} granules both sides hand over through -- the one
+        // thing the two sides share.  chain_serial: the last tag serial handed out (chain_tag, wgrt_trace.hip);
+        // it only grows while the granule array lives, so a stale granule never matches.
+        hipStream_t chain_side = nullptr;
+        hipEvent_t chain_ev_begin = nullptr, chain_ev_join = nullptr;
+        uint64_t *chain_gran = nullptr;
+        int64_t chain_cap = 0;
+        uint32_t chain_serial = 0;
+        bool chain_open = false;             // a wgrt_chain is between begin and end on this stream
     };
     std::mutex scratch_mu;
     std::map<void *, Scratch> scratch;

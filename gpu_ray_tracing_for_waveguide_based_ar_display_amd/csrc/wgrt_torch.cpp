@@ -16,7 +16,8 @@
 // extension is linked with -z now, so loading it without libwgrt fails at load time, not mid-call.
 // The window sink's entry points arrived within ABI 9 and are looked up by name at the first trace_windows
 // call (as _lib.load binds them), so the operator library still loads over an earlier ABI-9 build of libwgrt
-// (tools/with_lib.py), where trace keeps working and trace_windows raises.
+// (tools/with_lib.py), where trace keeps working and trace_windows raises.  The same holds for the chained launches'
+// entry points (wgrt_chain_*; torch.ops.wgrt.chain_begin / chain_step / chain_end, engine.TraceChain).
 #include <torch/library.h>
 
 #include <ATen/core/Tensor.h>
@@ -73,15 +74,31 @@ const WindowAbi &window_abi() {
     return abi;
 }
 
-// Both operators: trace (the grid alone: plan 0, no table) and trace_windows (the grid, the window table of
-// plan `plan` -- a wgrt_window_plan handle -- or both).
-int64_t trace_impl(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
+// The chain's entry points (wgrt_chain_*), new within ABI 9 as well: looked up at the first chain_begin.
+struct ChainAbi {
+    decltype(&wgrt_chain_begin) begin;
+    decltype(&wgrt_chain_step) step;
+    decltype(&wgrt_chain_end) end;
+};
+const ChainAbi &chain_abi() {
+    static const ChainAbi abi{reinterpret_cast<decltype(&wgrt_chain_begin)>(dlsym(RTLD_DEFAULT, "wgrt_chain_begin")),
+                              reinterpret_cast<decltype(&wgrt_chain_step)>(dlsym(RTLD_DEFAULT, "wgrt_chain_step")),
+                              reinterpret_cast<decltype(&wgrt_chain_end)>(dlsym(RTLD_DEFAULT, "wgrt_chain_end"))};
+    TORCH_CHECK(abi.begin && abi.step && abi.end, "wgrt.chain_begin: the loaded libwgrt.so has no wgrt_chain_begin (a "
+                                                  "build from before the chained launches)");
+    return abi;
+}
+
+// All three launching operators: trace (the grid alone: plan 0, no table), trace_windows (the grid, the window
+// table of plan `plan` -- a wgrt_window_plan handle -- or both) and, with `chain`, chain_begin: the same checks and
+// records handed to wgrt_chain_begin, which launches nothing and leaves the chain's handle in *chain.
+int64_t trace_core(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
                    const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
                    Tensor rng_states, std::optional<Tensor> matrix_EB, std::optional<Tensor> stats,
                    std::optional<Tensor> per_ray_bounces, int64_t n_rays, int64_t gid_offset, int64_t stream,
                    int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
                    int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
-                   double grid_sqrt_k, int64_t plan, std::optional<Tensor> table) {
+                   double grid_sqrt_k, int64_t plan, std::optional<Tensor> table, wgrt_chain **chain) {
     const wgrt_scene *s = reinterpret_cast<const wgrt_scene *>(static_cast<uintptr_t>(scene));
     TORCH_CHECK(s != nullptr, "wgrt.trace: NULL scene");
     wgrt_scene_info info{};
@@ -165,8 +182,47 @@ int64_t trace_impl(int64_t scene, const Tensor &x, const Tensor &y, const Tensor
     o.debug = reinterpret_cast<const wgrt_debug_opts *>(static_cast<uintptr_t>(debug));
     o.grid_sqrt_k = grid_sqrt_k;
     void *const hip_stream = reinterpret_cast<void *>(static_cast<uintptr_t>(stream));
+    if (chain) {
+        TORCH_CHECK(!per, "wgrt.chain_begin: a chain takes no per_ray_bounces");
+        return chain_abi().begin(s, &r, n_rays, gid_offset, rng, eb, stp, hip_stream, &o, tab ? wp : nullptr, tab, chain);
+    }
     if (!tab) return wgrt_trace_opts(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o);
     return window_abi().trace(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o, wp, tab);
+}
+
+int64_t trace_impl(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
+                   const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
+                   Tensor rng_states, std::optional<Tensor> matrix_EB, std::optional<Tensor> stats,
+                   std::optional<Tensor> per_ray_bounces, int64_t n_rays, int64_t gid_offset, int64_t stream,
+                   int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
+                   int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
+                   double grid_sqrt_k, int64_t plan, std::optional<Tensor> table) {
+    return trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats, per_ray_bounces,
+                      n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
+                      gid_block_rays, debug, grid_sqrt_k, plan, table, nullptr);
+}
+
+// chain_begin: trace_windows' arguments -> the chain's handle (a user-space address: positive), or the negated
+// wgrt_status of a failure (wgrt_last_error has the detail).  The
+// Python layer keeps every tensor alive until chain_end (engine.TraceChain).
+int64_t chain_begin(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
+                    const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
+                    Tensor rng_states, std::optional<Tensor> matrix_EB, std::optional<Tensor> stats,
+                    std::optional<Tensor> per_ray_bounces, int64_t n_rays, int64_t gid_offset, int64_t stream,
+                    int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
+                    int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
+                    double grid_sqrt_k, int64_t plan, std::optional<Tensor> table) {
+    wgrt_chain *ch = nullptr;
+    const int64_t st = trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats,
+                                  per_ray_bounces, n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order,
+                                  num_iter, gid_blocks, gid_block_rays, debug, grid_sqrt_k, plan, table, &ch);
+    return st == WGRT_OK ? static_cast<int64_t>(reinterpret_cast<uintptr_t>(ch)) : -st;
+}
+int64_t chain_step(int64_t chain) {
+    return chain_abi().step(reinterpret_cast<wgrt_chain *>(static_cast<uintptr_t>(chain)));
+}
+int64_t chain_end(int64_t chain) {
+    return chain_abi().end(reinterpret_cast<wgrt_chain *>(static_cast<uintptr_t>(chain)));
 }
 
 int64_t trace(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
@@ -197,4 +253,13 @@ TORCH_LIBRARY(wgrt, m) {
           "int workgroups, Tensor? chunk_order, int num_iter, Tensor? gid_blocks, int gid_block_rays, int debug, "
           "float grid_sqrt_k, int plan, Tensor(e!)? table) -> int",
           &trace_impl);
+    // a chain of single launches (wgrt_chain_*): begin takes trace_windows' arguments and returns the handle
+    m.def("chain_begin(int scene, Tensor x, Tensor y, Tensor m, Tensor n, Tensor? lmd_num, Tensor te, Tensor tm, "
+          "Tensor delta_phase, Tensor(a!) rng_states, Tensor(b!)? matrix_EB, Tensor(c!)? stats, "
+          "Tensor(d!)? per_ray_bounces, int n_rays, int gid_offset, int stream, int kernel, int variant, "
+          "int workgroups, Tensor? chunk_order, int num_iter, Tensor? gid_blocks, int gid_block_rays, int debug, "
+          "float grid_sqrt_k, int plan, Tensor(e!)? table) -> int",
+          &chain_begin);
+    m.def("chain_step(int chain) -> int", &chain_step);
+    m.def("chain_end(int chain) -> int", &chain_end);
 }

@@ -204,6 +204,13 @@ __device__ __forceinline__ uint32_t iter_tag(uint32_t epoch, uint32_t k, bool br
     return (epoch << 9) | (broken ? 0x100u : 0u) | k;
 }
 
+// Tag of a chain's per-ray granule (wgrt_chain_*): the serial of the step (or the segment's seed)
+// that published the state, and whether the ray's hand-off was given up (the mark every later step passes on).
+// The serial only grows while the granule array lives, so what an earlier segment left never matches.
+__device__ __host__ __forceinline__ uint32_t chain_tag(uint32_t serial, bool broken) {
+    return (serial << 1) | (broken ? 1u : 0u);
+}
+
 // Single launches re-trace their abandoned rays inside the trace kernel (the workgroup that counts
 // itself done last: replay_tail), so no replay kernel follows the launch: -0.2 to -1.6 % per single
 // launch.  WGRT_INKERNEL_REPLAY=0 builds the round-5 design (replay_kernel behind it).
@@ -239,6 +246,25 @@ __device__ __forceinline__ void replay_tail(const KArgs &K, unsigned long long n
     if (threadIdx.x == 0) c.w[kCtrReplayed] = nr;
     if ((threadIdx.x & 63) == 0 && R.stats) c.add_to(R.stats);
 }
+// The same for a chained step: the abandoned ray's start state is what the previous step published (its granule
+// still holds it: only this step's trace of the ray writes it next), and its end is published like a retire's,
+// for the next step's waiters.
+__device__ __forceinline__ void replay_tail_chain(const KArgs &K, unsigned long long nr) {
+    const TraceArgs R = K.args();
+    const uint32_t *const list = KA(replay_list);
+    Counters c;
+    for (unsigned long long k = threadIdx.x; k < nr; k += blockDim.x) {
+        const int64_t i = (int64_t)__hip_atomic_load(list + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        uint64_t was = __hip_atomic_load(R.rng64 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        uint32_t st = (uint32_t)(was >> 32);
+        trace_one(R, i, c, &st);
+        __hip_atomic_compare_exchange_strong(R.rng64 + i, &was, ((uint64_t)st << 32) | chain_tag(R.iter_epoch, false),
+                                             __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    c.wave_reduce();
+    if (threadIdx.x == 0) c.w[kCtrReplayed] = nr;
+    if ((threadIdx.x & 63) == 0 && R.stats) c.add_to(R.stats);
+}
 #endif
 
 // The two ends of a Jones-vector launch, given every lane's counters (by value: by reference the fused
@@ -254,6 +280,7 @@ __device__ __forceinline__ void finish_fused(const KArgs &K, Counters c) {
 // each per workgroup: not contended), waits for them, and counts the workgroup done; the workgroup that
 // counts last reads the totals at agent scope, adds them to *stats, zeroes the next launch's counter set
 // (every other workgroup has left this one's) and replays.
+template <bool CHAIN>
 __device__ __forceinline__ void finish_single(const KArgs &K, Counters c) {
     __shared__ unsigned long long red[4][kCtrWords];
     __shared__ int last_wg;
@@ -281,7 +308,10 @@ __device__ __forceinline__ void finish_single(const KArgs &K, Counters c) {
     // the reference arithmetic -- no replay kernel behind the launch.  Every list entry was stored at
     // agent scope and waited for by its lane before that lane's workgroup counted itself done.
     const unsigned long long nr = __hip_atomic_load(KA(replay_count), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (__builtin_expect(nr != 0ull, 0)) replay_tail(K, nr);
+    if (__builtin_expect(nr != 0ull, 0)) {
+        if (CHAIN) replay_tail_chain(K, nr);
+        else replay_tail(K, nr);
+    }
 #endif
 }
 
@@ -306,7 +336,14 @@ template <class Loc>
 constexpr size_t kLearnTailOff = sizeof(TraceArgs) + sizeof(Loc) + sizeof(unsigned long long *) + 8;
 static_assert(sizeof(TraceArgs) % 8 == 0 && sizeof(Locator) % 8 == 0 && sizeof(LocatorT<uint32_t>) % 8 == 0,
               "kLearnTailOff: the kernel parameters lie back to back, the int padded to 8 bytes");
-template <bool FUSED, bool SINGLE, bool TL, bool AMP, bool LEARN, class Loc>
+// CHAIN: a step of a chain of single launches (wgrt_chain_*; full colour): the single-launch path, but the
+// ray's start state comes from its granule A.rng64[i] once its tag says that the previous step's trace of the ray
+// has ended (serial A.iter_epoch - 1; the lane waits in place otherwise, as in a fused launch, polling with
+// agent-scope loads, bounded by A.handoff_wait_ticks / handoff_min_passes), and a trace's end publishes
+// {state, serial A.iter_epoch} there instead of writing rng_states.  The previous step runs in another kernel, on
+// another hardware queue, at the same time.  Its operands are read from the kernarg segment where they are used.
+// Off in the product instantiations, which contain none of it.
+template <bool FUSED, bool SINGLE, bool TL, bool AMP, bool LEARN, bool CHAIN, class Loc>
 __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, const Loc &loc, unsigned long long *heads,
                                           int chunk) {
     // Single launches (!FUSED) do their epilogue in this kernel (above), and retire a finished trace at one
@@ -389,7 +426,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
         const bool in_cur = oc < 64u;
         const bool ok = lane_load_staged(sbufs + (in_cur ? sb : sb ^ 1) * (kStageCols * 64),
                                          (int)(in_cur ? oc : L.i - sbase_prev), L.i, L,
-                                         (FUSED && L.k > 0) ? KA(rng64) + L.i : nullptr, &w);
+                                         (CHAIN || (FUSED && L.k > 0)) ? KA(rng64) + L.i : nullptr, &w);
         waiting = false;
         active = false;
         if (__builtin_expect(!ok, 0)) {
@@ -402,6 +439,24 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
                 L.r.s = (uint32_t)(w >> 32);
             } else if ((tag >> 8) == ((A.iter_epoch << 1) | 1u)) {
                 return;   // abandoned in an earlier iteration: the replay kernel finishes it
+            } else {
+                waiting = true;
+                wait_t0 = __builtin_amdgcn_s_memrealtime();
+                wait_passes = 0;
+                return;
+            }
+        }
+        if (CHAIN) {
+            const uint32_t tag = (uint32_t)w, ser = KA(iter_epoch);
+            if (tag == chain_tag(ser - 1u, false)) {
+                L.r.s = (uint32_t)(w >> 32);
+            } else if (tag == chain_tag(ser - 1u, true)) {
+                // given up in an earlier step: the mark goes on to the next step -- unless that step's waiter has
+                // already given up too and left its own, newer mark (a compare-and-swap whose result is not used)
+                uint64_t was = w;
+                __hip_atomic_compare_exchange_strong(KA(rng64) + L.i, &was, (uint64_t)chain_tag(ser, true),
+                                                     __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                return;
             } else {
                 waiting = true;
                 wait_t0 = __builtin_amdgcn_s_memrealtime();
@@ -440,6 +495,13 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
                 // store costs the ray's next waiter one more bound before it gives up too
                 __hip_atomic_store(KA(rng64) + L.i, hand, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
+        } else if (CHAIN) {
+            // the granule still holds what this trace started from, unless the next step's waiter has given up
+            // and marked the ray meanwhile: the mark then stays (the fused hand-off's rule, above)
+            const uint32_t ser = KA(iter_epoch);
+            uint64_t was = ((uint64_t)L.s0 << 32) | chain_tag(ser - 1u, false);
+            __hip_atomic_compare_exchange_strong(KA(rng64) + L.i, &was, ((uint64_t)L.r.s << 32) | chain_tag(ser, false),
+                                                 __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else {
             KA(rng)[L.i] = L.r.s;
             uint32_t *const pr = KA(per_ray);
@@ -578,6 +640,35 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
                 }
             }
         }
+        if (CHAIN && waiting) {
+            // the same poll across the kernel boundary: the previous step's trace of the ray publishes the granule
+            const uint64_t w = __hip_atomic_load(KA(rng64) + L.i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint32_t tag = (uint32_t)w, ser = KA(iter_epoch);
+            if (tag == chain_tag(ser - 1u, false)) {
+                L.r.s = (uint32_t)(w >> 32);
+                L.s0 = L.r.s;
+                waiting = false;
+                active = true;
+                blk = 0;
+                kind = 0;
+                entry = true;
+            } else if (tag == chain_tag(ser - 1u, true)) {
+                uint64_t was = w;   // (as in start(): a newer mark stays)
+                __hip_atomic_compare_exchange_strong(KA(rng64) + L.i, &was, (uint64_t)chain_tag(ser, true),
+                                                     __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                waiting = false;
+            } else if ((++wait_passes > KA(handoff_min_passes)) &
+                       (__builtin_amdgcn_s_memrealtime() - wait_t0 > KA(handoff_wait_ticks))) {
+                // never arrived: the ray is marked for the next step at once (only if the granule still holds the
+                // value just polled), so every later step passes the mark on instead of waiting out the bound
+                uint64_t seen = w;
+                if (__hip_atomic_compare_exchange_strong(KA(rng64) + L.i, &seen, (uint64_t)chain_tag(ser, true),
+                                                         __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+                    waiting = false;
+                    ++tot_giveup;
+                }
+            }
+        }
         uint64_t need = __ballot(!active && !waiting);
         // fused launches refill in batches of kFusedRefill free lanes (or when the wave is empty):
         // a refill's column loads are one round trip the whole wave waits for, and in a fused
@@ -658,7 +749,11 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
         if (__ballot(active || waiting) == 0ull) break;   // queue exhausted, nothing in flight
         // single-trace launches: once the queue has run dry, the wave's remaining rays finish in
         // the tail loop below
-        if (!FUSED && exhausted) break;
+        // (a chained step stays here while a lane still waits for its ray: the tail loop does not poll)
+        if (!FUSED && exhausted && !(CHAIN && __ballot(waiting) != 0ull)) break;
+        // a wave with nothing but waiting lanes leaves the issue slots to the waves that work (the guide's
+        // polling-cost row): about 0.3 us between polls
+        if (CHAIN && __ballot(active) == 0ull) __builtin_amdgcn_s_sleep(10);
         interact_pass(nullptr);
     }
     if (!FUSED && __ballot(active) != 0ull) {
@@ -747,7 +842,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
     c.w[kCtrGiveups] = tot_giveup;
     c.w[kCtrInter] = tot_int;
     if (FUSED) finish_fused(K, c);
-    else finish_single(K, c);
+    else finish_single<CHAIN>(K, c);
 }
 
 #if !WGRT_INKERNEL_REPLAY
@@ -773,12 +868,14 @@ __global__ __launch_bounds__(256) void replay_kernel(TraceArgs A) {
 // At 96 VGPRs (5 waves) the full-colour single-trace kernel spills 88 B per lane and runs 36 %
 // slower than at 4.
 #define WGRT_JONES_BOUNDS __launch_bounds__(256, 4)
+constexpr int kJonesWavesPerSimd = 4;   // = workgroups of 256 threads per CU
+constexpr int kChainMargin = 8;         // workgroups two chained grids leave free: one per XCD (query_trace_grids)
 // AMP: with the amplification step of the certification bound (wgrt_jones_lane.h; scenes with a block whose
 // branch matrices are not scaled-unitary)
 template <class CellT, bool FUSED, bool SINGLE, bool AMP>
 __global__ WGRT_JONES_BOUNDS void trace_jones_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
                                                      int chunk) {
-    jones_body<FUSED, SINGLE, false, AMP, false>(
+    jones_body<FUSED, SINGLE, false, AMP, false, false>(
         A, kernel_kargs<decltype(trace_jones_kernel<CellT, FUSED, SINGLE, AMP>)>(), loc, counter, chunk);
 }
 
@@ -787,7 +884,7 @@ __global__ WGRT_JONES_BOUNDS void trace_jones_kernel(TraceArgs A, LocatorT<CellT
 template <class CellT, bool FUSED, bool SINGLE>
 __global__ WGRT_JONES_BOUNDS void trace_jones_tl_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
                                                         int chunk) {
-    jones_body<FUSED, SINGLE, true, false, false>(A, kernel_kargs<decltype(trace_jones_tl_kernel<CellT, FUSED, SINGLE>)>(),
+    jones_body<FUSED, SINGLE, true, false, false, false>(A, kernel_kargs<decltype(trace_jones_tl_kernel<CellT, FUSED, SINGLE>)>(),
                                                   loc, counter, chunk);
 }
 
@@ -796,8 +893,31 @@ __global__ WGRT_JONES_BOUNDS void trace_jones_tl_kernel(TraceArgs A, LocatorT<Ce
 template <class CellT>
 __global__ WGRT_JONES_BOUNDS void trace_jones_learn_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
                                                            int chunk, uint32_t *tail) {
-    jones_body<false, false, false, false, true>(A, kernel_kargs<decltype(trace_jones_learn_kernel<CellT>)>(), loc,
+    jones_body<false, false, false, false, true, false>(A, kernel_kargs<decltype(trace_jones_learn_kernel<CellT>)>(), loc,
                                                  counter, chunk);
+}
+
+// The single-launch loop as a step of a chain (wgrt_chain_*): full colour, no learning, no timeline.
+template <class CellT, bool AMP>
+__global__ WGRT_JONES_BOUNDS void trace_jones_chain_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
+                                                           int chunk) {
+    jones_body<false, false, false, AMP, false, true>(A, kernel_kargs<decltype(trace_jones_chain_kernel<CellT, AMP>)>(),
+                                                      loc, counter, chunk);
+}
+
+// The two ends of a chain's segment, on the caller's stream: every ray's state into its granule under the
+// segment's seed tag before the first step, and back to rng_states after the last -- where the tag is the last
+// step's, so a ray no step traced (a bad ray) or whose hand-off was given up keeps what rng_states holds.
+__global__ __launch_bounds__(256) void chain_seed_kernel(const uint32_t *rng, uint64_t *gran, int64_t n, uint32_t tag) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) gran[i] = ((uint64_t)rng[i] << 32) | tag;
+}
+__global__ __launch_bounds__(256) void chain_finalize_kernel(uint32_t *rng, const uint64_t *gran, int64_t n,
+                                                             uint32_t tag) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t w = gran[i];
+    if ((uint32_t)w == tag) rng[i] = (uint32_t)(w >> 32);
 }
 
 // The automatic issue order of a batch (wgrt_order.h), built by one workgroup: the class key of every
@@ -881,6 +1001,9 @@ const void *const kJonesKernels[2][2][2][2] = {
        (const void *)trace_jones_kernel<uint64_t, true, true, true>}}}};
 const void *const kLearnKernels[2] = {(const void *)trace_jones_learn_kernel<uint32_t>,
                                       (const void *)trace_jones_learn_kernel<uint64_t>};
+const void *const kChainKernels[2][2] = {   // [64-bit cells][AMP]
+    {(const void *)trace_jones_chain_kernel<uint32_t, false>, (const void *)trace_jones_chain_kernel<uint32_t, true>},
+    {(const void *)trace_jones_chain_kernel<uint64_t, false>, (const void *)trace_jones_chain_kernel<uint64_t, true>}};
 const void *const kTimelineKernels[2] = {(const void *)trace_jones_tl_kernel<uint32_t, false, false>,
                                          (const void *)trace_jones_tl_kernel<uint32_t, true, false>};
 
@@ -909,13 +1032,37 @@ wgrt_status query_trace_grids(wgrt_scene *s) {
             }
     for (int f = 0; f < 2; ++f) HIP_TRY(grid_of(kTimelineKernels[f], s->jones_tl_grid[f]));
     for (int c = 0; c < 2; ++c) HIP_TRY(grid_of(kLearnKernels[c], s->jones_learn_grid[c]));
+    // A chained step's waves spin on rays that only the previous step's launch can finish, so that launch must
+    // always be able to get workgroups resident while this one is.  Two steps are in flight at a time (stream order
+    // on each side), so a chained grid is at most half of what the chip holds, less kChainMargin workgroups (one per
+    // XCD) between the two: both launches of a pair are then resident whole, whatever the dispatch order.  Half
+    // is also the fastest grid measured (C3: 0.181 ms per step at 510 workgroups against 0.204 at the plain
+    // launch's 946 and 0.200 at 379): the next step's bulk then runs beside the whole drain, not
+    // only in the workgroup slots the drain has already given back.  The occupancy query may be one block per CU
+    // high for kernels of 97-112 SGPRs (these have 98-100), so the figure is also held to the 4 waves per SIMD of
+    // WGRT_JONES_BOUNDS, which is what the guide's min(API, 8, floor(800 / (ceil(sgpr / 16) * 16 + 16))) = min(API,
+    // 8, 6) comes to once the VGPR budget (126 <= 128: 4 waves) is counted: 4 x 256 CUs = 1,024 resident
+    // workgroups, (1,024 - 8) / 2 = 508 per chained step.
+    for (int c = 0; c < 2; ++c) {
+        int per_cu = 0;
+        for (int a = 0; a < 2; ++a) {
+            int k = 0;
+            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&k, kChainKernels[c][a], 256, 0));
+            per_cu = a == 0 ? k : std::min(per_cu, k);
+        }
+        s->jones_chain_grid[c] =
+            std::max(1, (cus * std::min(std::max(1, per_cu), kJonesWavesPerSimd) - kChainMargin) / 2);
+    }
     return WGRT_OK;
 }
 
 void free_scratch(wgrt_scene::Scratch &sc) {
     for (void *p : {(void *)sc.ctr, (void *)sc.list, (void *)sc.q_xy, (void *)sc.q_i, (void *)sc.full, (void *)sc.rng64,
-                    (void *)sc.part, (void *)sc.order})
+                    (void *)sc.part, (void *)sc.order, (void *)sc.chain_gran})
         (void)hipFree(p);
+    if (sc.chain_ev_begin) (void)hipEventDestroy(sc.chain_ev_begin);
+    if (sc.chain_ev_join) (void)hipEventDestroy(sc.chain_ev_join);
+    if (sc.chain_side) (void)hipStreamDestroy(sc.chain_side);
 }
 
 }  // namespace wgrt
@@ -1043,6 +1190,9 @@ struct LaunchCfg {
     // wgrt_trace_windows: the window table the out-couplings count into and its plan's device view (NULL: none)
     double *win_table = nullptr;
     const WindowPlanView *win = nullptr;
+    // a chained step (wgrt_chain_step): the chain's granules and the tag serial this step publishes (0: not chained)
+    uint64_t *chain_gran = nullptr;
+    uint32_t chain_serial = 0;
 };
 
 // wgrt_debug_set_auto_order: the automatic issue order (and its learning launches) on / off, process-wide.
@@ -1054,12 +1204,25 @@ std::atomic<int> g_auto_order{1};
 // kLearnRaysPerTile rays per tile, the launch learns (not a timeline launch: that kernel is another
 // instantiation); once a learning launch has run, launches of whole 64-ray chunks are issued in the order
 // built from the table.
-void plan_auto_order(wgrt_scene *ms, int64_t n_rays, int item, LaunchCfg &c) {
-    if (!g_auto_order.load(std::memory_order_relaxed) || c.variant == 1 || c.num_iter > 1 || c.single || c.chunk_order ||
-        ms->nonunitary_blocks)
-        return;
+bool auto_order_applies(const wgrt_scene *ms, const LaunchCfg &c) {
+    return g_auto_order.load(std::memory_order_relaxed) && c.variant != 1 && c.num_iter <= 1 && !c.single &&
+           !c.chunk_order && !ms->nonunitary_blocks;
+}
+bool still_learning(const wgrt_scene *ms) {   // (under scratch_mu)
+    return ms->learned_rays < kLearnRaysPerTile * (int64_t)ms->nl * ms->nx * ms->ny;
+}
+// Would a plain launch of this configuration learn now?  Such a step of a chain runs as one: the table has one
+// writer at a time, and no chained instantiation learns.
+bool would_learn(wgrt_scene *ms, const LaunchCfg &c) {
+    if (!auto_order_applies(ms, c) || c.timeline) return false;
     std::lock_guard<std::mutex> lk(ms->scratch_mu);
-    const bool learning = ms->learned_rays < kLearnRaysPerTile * (int64_t)ms->nl * ms->nx * ms->ny;
+    return still_learning(ms);
+}
+
+void plan_auto_order(wgrt_scene *ms, int64_t n_rays, int item, LaunchCfg &c) {
+    if (!auto_order_applies(ms, c)) return;
+    std::lock_guard<std::mutex> lk(ms->scratch_mu);
+    const bool learning = !c.chain_serial && still_learning(ms);
     // While the scene still learns (a batch of few rays per tile: a shard), the order is rebuilt after 1, 2,
     // 4, ... learning launches only, not after each: order_kernel is one workgroup (0.24 ms for C3's 21,168
     // chunks), about a launch's time at every size.
@@ -1175,6 +1338,7 @@ TraceArgs fill_args(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, 
 // grid, fewer for a single trace (grid_sqrt_k), never more than have work; c.workgroups overrides.
 int64_t launch_grid(const wgrt_scene *s, int64_t n_rays, int64_t item, const LaunchCfg &c) {
     int64_t grid = c.workgroups > 0 ? c.workgroups
+                   : c.chain_serial ? s->jones_chain_grid[c.variant == 9]
                    : c.timeline     ? s->jones_tl_grid[c.num_iter > 1]
                    : c.learn        ? s->jones_learn_grid[c.variant == 9]
                                     : s->jones_grid[c.variant == 9][c.num_iter > 1][c.single];
@@ -1192,6 +1356,8 @@ int64_t launch_grid(const wgrt_scene *s, int64_t n_rays, int64_t item, const Lau
         const int64_t want = std::max<int64_t>(1, (int64_t)std::ceil(K * std::sqrt((double)items)));
         if (grid > want) grid = want;
     }
+    // (a chained step never fills the chip, whoever chose its grid: query_trace_grids)
+    if (c.chain_serial) grid = std::min<int64_t>(grid, s->jones_chain_grid[c.variant == 9]);
     return std::min(grid, useful);
 }
 
@@ -1227,6 +1393,12 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
         // a debug bound (fault-injection tests) gives up on the clock alone
         A.handoff_min_passes = (dbg && dbg->handoff_wait_ticks) ? 0u : kHandoffMinPasses;
     }
+    if (c.chain_serial) {   // the fused hand-off's operands, across the kernel boundary (jones_body, CHAIN)
+        A.rng64 = c.chain_gran;
+        A.iter_epoch = c.chain_serial;
+        A.handoff_wait_ticks = (dbg && dbg->handoff_wait_ticks) ? dbg->handoff_wait_ticks : kHandoffTicksPerIter * 2ull;
+        A.handoff_min_passes = (dbg && dbg->handoff_wait_ticks) ? 0u : kHandoffMinPasses;
+    }
     unsigned long long *ctr = sc->ctr + (size_t)parity * kScratchCtr;
     set_counter_slots(A, ctr, sc->ctr + (size_t)(parity ^ 1u) * kScratchCtr);
     A.replay_list = sc->list;
@@ -1248,7 +1420,8 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
     // need it (wgrt_jones_lane.h, "Amplification")
     LocatorT<uint32_t> l32{};
     if (c.variant != 9) l32 = make_locator32(s);
-    const void *const kernel = c.timeline ? kTimelineKernels[num_iter > 1]
+    const void *const kernel = c.chain_serial ? kChainKernels[c.variant == 9][s->nonunitary_blocks != 0]
+                               : c.timeline ? kTimelineKernels[num_iter > 1]
                                : c.learn  ? kLearnKernels[c.variant == 9]
                                           : kJonesKernels[c.variant == 9][num_iter > 1][c.single][s->nonunitary_blocks != 0];
     uint32_t *tail = ms->d_tile_tail;   // the learning kernels' last parameter (the others take four)
@@ -1308,6 +1481,207 @@ LaunchCfg cfg_of(int variant, int workgroups, bool single) {
     return c;
 }
 
+// wgrt_launch_opts (and the window sink's plan and table) as a launch configuration.
+wgrt_status cfg_of_opts(const wgrt_scene *s, const wgrt_launch_opts *opts, const wgrt_window_plan *plan, double *table,
+                        LaunchCfg &c) {
+    if (!opts) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL opts");
+    if (opts->kernel != 0 && opts->kernel != 1) return fail(WGRT_ERR_INVALID_ARGUMENT, "kernel must be 0 or 1");
+    c = cfg_of(opts->variant, opts->workgroups, opts->kernel == 1);
+    c.chunk_order = opts->chunk_order;
+    c.n_chunk_order = opts->n_chunk_order;
+    c.num_iter = opts->num_iter;
+    c.gid_blocks = opts->gid_blocks;
+    c.gid_block_rays = opts->gid_block_rays;
+    c.dbg = opts->debug;
+    c.grid_k = opts->grid_sqrt_k;
+    if (!(c.grid_k == c.grid_k)) return fail(WGRT_ERR_INVALID_ARGUMENT, "grid_sqrt_k is NaN");
+    if (table) {   // (without a table the call is wgrt_trace_opts, and the plan is not looked at)
+        if (!plan) return fail(WGRT_ERR_INVALID_ARGUMENT, "a window table needs its wgrt_window_plan");
+        if (s && plan->device != s->device)
+            return fail(WGRT_ERR_INVALID_ARGUMENT, "the window plan lives on device " + std::to_string(plan->device) +
+                                                       ", the scene on device " + std::to_string(s->device));
+        if ((uintptr_t)table & 7) return fail(WGRT_ERR_INVALID_ARGUMENT, "table must be 8-B aligned");
+        c.win_table = table;
+        c.win = plan->d_view;
+    }
+    return WGRT_OK;
+}
+
+// Where a chain's next step goes (wgrt_debug_chain_plan states the rule; no device).
+wgrt_chain_plan chain_plan(int64_t seg, uint32_t ser, uint32_t flags) {
+    wgrt_chain_plan p{};
+    if (flags) {
+        p.join = seg >= 0;
+        p.serial_after = ser;
+        p.in_segment_after = -1;
+        return p;
+    }
+    p.chained = 1;
+    if (seg >= 0 && ser >= WGRT_CHAIN_SERIAL_MAX) {   // the tag serial has run out: close the segment, start afresh
+        p.join = 1;
+        seg = -1;
+    }
+    if (seg < 0) {
+        if (ser >= WGRT_CHAIN_SERIAL_MAX - 1u) {   // the seed and the step each take a serial
+            p.clear = 1;
+            ser = 0;
+        }
+        p.seed = 1;
+        ++ser;
+        seg = 0;
+    }
+    p.wait_serial = ser;
+    p.publish_serial = ser + 1u;
+    p.side = (int)(seg & 1);
+    p.serial_after = ser + 1u;
+    p.in_segment_after = seg + 1;
+    return p;
+}
+
+}  // namespace
+
+// A chain between wgrt_chain_begin and wgrt_chain_end: the copied arguments of its launches and where it stands.
+struct wgrt_chain {
+    wgrt_scene *s = nullptr;
+    wgrt_rays rays{};
+    int64_t n_rays = 0, gid_offset = 0;
+    uint32_t *rng = nullptr;
+    float *eb = nullptr;
+    wgrt_trace_stats *stats = nullptr;
+    void *stream = nullptr;
+    LaunchCfg cfg;
+    wgrt_debug_opts dbg{};
+    uint32_t flags = 0;                  // WGRT_CHAIN_*: what keeps every step of this chain a plain launch
+    wgrt_scene::Scratch *sc = nullptr;   // the caller's stream's scratch: side stream, events, granules, serial
+    int64_t in_segment = -1;             // chained steps issued since the open segment's seed (-1: none open)
+    bool failed = false;                 // a step failed: the later ones are refused
+    bool prepared = false;               // begin made the side stream and sized the granules and both scratches
+};
+
+namespace {
+
+// begin: the side stream, the events and the granules of the caller's stream (cached in its scratch), and both
+// sides' launch scratch at this batch's size -- whatever synchronises happens here, not in a step.
+wgrt_status chain_prepare(wgrt_chain *ch) {
+    wgrt_scene *ms = ch->s;
+    hipStream_t S = (hipStream_t)ch->stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(S, &cap));
+    if (cap != hipStreamCaptureStatusNone) ch->flags |= WGRT_CHAIN_CAPTURE;
+    wgrt_scene::Scratch *sc = nullptr;
+    hipStream_t side = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ms->scratch_mu);
+        sc = &ms->scratch[ch->stream];
+        if (sc->chain_open) return fail(WGRT_ERR_INVALID_ARGUMENT, "a chain is already open on this stream");
+        if (!ch->flags) {
+            if (!sc->chain_side) HIP_TRY(hipStreamCreateWithFlags(&sc->chain_side, hipStreamNonBlocking));
+            if (!sc->chain_ev_begin) HIP_TRY(hipEventCreateWithFlags(&sc->chain_ev_begin, hipEventDisableTiming));
+            if (!sc->chain_ev_join) HIP_TRY(hipEventCreateWithFlags(&sc->chain_ev_join, hipEventDisableTiming));
+            side = sc->chain_side;
+            if (sc->chain_cap < ch->n_rays) {   // new granules: all-zero words match no tag, and the serial restarts
+                HIP_TRY(hipStreamSynchronize(S));
+                HIP_TRY(hipStreamSynchronize(side));
+                (void)hipFree(sc->chain_gran);
+                sc->chain_gran = nullptr;
+                sc->chain_cap = 0;
+                hipError_t h = hipMalloc((void **)&sc->chain_gran, (size_t)ch->n_rays * sizeof(uint64_t));
+                if (h == hipSuccess) h = hipMemset(sc->chain_gran, 0, (size_t)ch->n_rays * sizeof(uint64_t));
+                const wgrt_status e = malloc_status(h, "hipMalloc(chain granules)");
+                if (e != WGRT_OK) return e;
+                sc->chain_cap = ch->n_rays;
+                sc->chain_serial = 0;
+            }
+        }
+    }
+    if (side) {
+        // the largest grid a step of this chain can be launched on: chained, plain, or plain and learning
+        const int item = (ch->cfg.dbg && ch->cfg.dbg->chunk_rays > 0) ? std::min(ch->cfg.dbg->chunk_rays, 64) : kChunk;
+        LaunchCfg chained = ch->cfg, learning = ch->cfg;
+        chained.chain_serial = 1;
+        learning.learn = true;
+        int64_t grid = 1;
+        for (const LaunchCfg *k : {&ch->cfg, &chained, &learning})
+            grid = std::max(grid, launch_grid(ms, ch->n_rays, item, *k));
+        for (void *st : {ch->stream, (void *)side}) {
+            wgrt_scene::Scratch *tmp = nullptr;
+            const wgrt_status e = ensure_scratch(ms, st, ch->n_rays, 1, grid, &tmp);
+            if (e != WGRT_OK) return e;
+        }
+    }
+    std::lock_guard<std::mutex> lk(ms->scratch_mu);
+    sc->chain_open = true;
+    ch->sc = sc;
+    ch->prepared = side != nullptr;
+    return WGRT_OK;
+}
+
+// Close the open segment: the caller's stream waits for the side stream's last step, then rng_states takes the
+// last step's states from the granules (chain_finalize_kernel) -- ordered after every step by the streams, not by
+// timing.
+wgrt_status chain_join(wgrt_chain *ch) {
+    if (ch->in_segment < 0) return WGRT_OK;
+    hipStream_t S = (hipStream_t)ch->stream;
+    wgrt_scene::Scratch *sc = ch->sc;
+    const int64_t steps = ch->in_segment;
+    ch->in_segment = -1;
+    if (steps >= 2) {
+        HIP_TRY(hipEventRecord(sc->chain_ev_join, sc->chain_side));
+        HIP_TRY(hipStreamWaitEvent(S, sc->chain_ev_join, 0));
+    }
+    if (ch->failed) return WGRT_OK;
+    hipLaunchKernelGGL(chain_finalize_kernel, dim3((unsigned)((ch->n_rays + 255) / 256)), dim3(256), 0, S, ch->rng,
+                       (const uint64_t *)sc->chain_gran, ch->n_rays, chain_tag(sc->chain_serial, false));
+    HIP_TRY(hipGetLastError());
+    return WGRT_OK;
+}
+
+wgrt_status chain_step(wgrt_chain *ch) {
+    if (ch->failed) return fail(WGRT_ERR_INVALID_ARGUMENT, "an earlier step of this chain failed");
+    wgrt_scene *ms = ch->s;
+    hipStream_t S = (hipStream_t)ch->stream;
+    wgrt_scene::Scratch *sc = ch->sc;
+    if (ch->in_segment < 0) {
+        // no segment open: the next chained step would fork to the side stream, which a capture that has begun
+        // on S since begin must not see (one query per segment, none per step of an open one)
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        HIP_TRY(hipStreamIsCapturing(S, &cap));
+        ch->flags = cap != hipStreamCaptureStatusNone ? (ch->flags | WGRT_CHAIN_CAPTURE) : (ch->flags & ~WGRT_CHAIN_CAPTURE);
+    }
+    // (a chain whose begin found a reason to stay serial, a capture among them, sized nothing: it stays serial)
+    const uint32_t flags = ch->flags | (!ch->prepared ? WGRT_CHAIN_CAPTURE : 0u) |
+                           (would_learn(ms, ch->cfg) ? WGRT_CHAIN_LEARNS : 0u);
+    const wgrt_chain_plan p = chain_plan(ch->in_segment, sc->chain_serial, flags);
+    wgrt_status e = WGRT_OK;
+    if (p.join) e = chain_join(ch);
+    if (e == WGRT_OK && !p.chained)
+        e = trace_launch(ms, &ch->rays, ch->n_rays, ch->gid_offset, ch->rng, ch->eb, ch->stats, nullptr, ch->stream, ch->cfg);
+    if (e == WGRT_OK && p.chained) {
+        auto hip = [](hipError_t h, const char *what) {
+            return h == hipSuccess ? WGRT_OK : fail(WGRT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(h));
+        };
+        if (p.clear) e = hip(hipMemsetAsync(sc->chain_gran, 0, (size_t)sc->chain_cap * sizeof(uint64_t), S), "hipMemsetAsync");
+        if (e == WGRT_OK && p.seed) {
+            hipLaunchKernelGGL(chain_seed_kernel, dim3((unsigned)((ch->n_rays + 255) / 256)), dim3(256), 0, S,
+                               (const uint32_t *)ch->rng, sc->chain_gran, ch->n_rays, chain_tag(p.wait_serial, false));
+            e = hip(hipGetLastError(), "chain_seed_kernel");
+            if (e == WGRT_OK) e = hip(hipEventRecord(sc->chain_ev_begin, S), "hipEventRecord");
+            if (e == WGRT_OK) e = hip(hipStreamWaitEvent(sc->chain_side, sc->chain_ev_begin, 0), "hipStreamWaitEvent");
+        }
+        if (e == WGRT_OK) {
+            sc->chain_serial = p.serial_after;
+            ch->in_segment = p.in_segment_after;
+            LaunchCfg c = ch->cfg;
+            c.chain_gran = sc->chain_gran;
+            c.chain_serial = p.publish_serial;
+            e = trace_launch(ms, &ch->rays, ch->n_rays, ch->gid_offset, ch->rng, ch->eb, ch->stats, nullptr,
+                             p.side ? (void *)sc->chain_side : ch->stream, c);
+        }
+    }
+    if (e != WGRT_OK) ch->failed = true;
+    return e;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1345,27 +1719,96 @@ wgrt_status wgrt_trace_windows(const wgrt_scene *s, const wgrt_rays *rays, int64
                                uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats,
                                uint32_t *per_ray_bounces, void *stream, const wgrt_launch_opts *opts,
                                const wgrt_window_plan *plan, double *table) {
-    if (!opts) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL opts");
-    if (opts->kernel != 0 && opts->kernel != 1) return fail(WGRT_ERR_INVALID_ARGUMENT, "kernel must be 0 or 1");
-    LaunchCfg c = cfg_of(opts->variant, opts->workgroups, opts->kernel == 1);
-    c.chunk_order = opts->chunk_order;
-    c.n_chunk_order = opts->n_chunk_order;
-    c.num_iter = opts->num_iter;
-    c.gid_blocks = opts->gid_blocks;
-    c.gid_block_rays = opts->gid_block_rays;
-    c.dbg = opts->debug;
-    c.grid_k = opts->grid_sqrt_k;
-    if (!(c.grid_k == c.grid_k)) return fail(WGRT_ERR_INVALID_ARGUMENT, "grid_sqrt_k is NaN");
-    if (table) {   // (without a table the call is wgrt_trace_opts, and the plan is not looked at)
-        if (!plan) return fail(WGRT_ERR_INVALID_ARGUMENT, "a window table needs its wgrt_window_plan");
-        if (s && plan->device != s->device)
-            return fail(WGRT_ERR_INVALID_ARGUMENT, "the window plan lives on device " + std::to_string(plan->device) +
-                                                       ", the scene on device " + std::to_string(s->device));
-        if ((uintptr_t)table & 7) return fail(WGRT_ERR_INVALID_ARGUMENT, "table must be 8-B aligned");
-        c.win_table = table;
-        c.win = plan->d_view;
-    }
+    LaunchCfg c;
+    const wgrt_status e = cfg_of_opts(s, opts, plan, table, c);
+    if (e != WGRT_OK) return e;
     return trace_launch(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, c);
+}
+
+wgrt_status wgrt_chain_begin(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
+                             uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats, void *stream,
+                             const wgrt_launch_opts *opts, const wgrt_window_plan *plan, double *table,
+                             wgrt_chain **out) {
+    if (!out) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL out");
+    *out = nullptr;
+    if (!s || !rays) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL scene / rays");
+    if (n_rays < 0 || gid_offset < 0) return fail(WGRT_ERR_INVALID_ARGUMENT, "negative n_rays / gid_offset");
+    LaunchCfg c;
+    wgrt_status e = cfg_of_opts(s, opts, plan, table, c);
+    if (e != WGRT_OK) return e;
+    DEVICE_SCOPE(dev_scope, s->device);
+    e = validate_launch(s, rays, n_rays, gid_offset, rng_states, matrix_EB, nullptr, c);
+    if (e != WGRT_OK) return e;
+    wgrt_chain *ch = new wgrt_chain;
+    ch->s = const_cast<wgrt_scene *>(s);
+    ch->rays = *rays;
+    ch->n_rays = n_rays;
+    ch->gid_offset = gid_offset;
+    ch->rng = rng_states;
+    ch->eb = matrix_EB;
+    ch->stats = stats;
+    ch->stream = stream;
+    ch->cfg = c;   // (validated: the variant resolved, num_iter clamped)
+    if (c.dbg) {
+        ch->dbg = *c.dbg;
+        ch->cfg.dbg = &ch->dbg;
+    }
+    ch->flags = (c.variant == 1 ? WGRT_CHAIN_VARIANT1 : 0u) | (c.single ? WGRT_CHAIN_SINGLE : 0u) |
+                (c.num_iter > 1 ? WGRT_CHAIN_FUSED : 0u) | ((c.chunk_order || c.timeline) ? WGRT_CHAIN_DEBUG : 0u);
+    // A launch whose own grid is the kernel's resident grid fills the chip alone: two of them in flight crowd each
+    // other's drain and gain nothing (C4: +6.6 % per step chained), so such a batch stays serial.
+    // Chained are the batches the sqrt(items) grid rule (or the caller) gives fewer workgroups.
+    if (!ch->flags && n_rays) {
+        const int item = (c.dbg && c.dbg->chunk_rays > 0) ? std::min(c.dbg->chunk_rays, 64) : kChunk;
+        if (launch_grid(s, n_rays, item, c) >= s->jones_grid[c.variant == 9][0][0]) ch->flags |= WGRT_CHAIN_FULL;
+    }
+    e = n_rays ? chain_prepare(ch) : WGRT_OK;
+    if (e != WGRT_OK) {
+        delete ch;
+        return e;
+    }
+    *out = ch;
+    return WGRT_OK;
+}
+
+wgrt_status wgrt_chain_step(wgrt_chain *ch) {
+    if (!ch) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL chain");
+    if (ch->n_rays == 0) return WGRT_OK;
+    DEVICE_SCOPE(dev_scope, ch->s->device);
+    return chain_step(ch);
+}
+
+wgrt_status wgrt_chain_end(wgrt_chain *ch) {
+    if (!ch) return WGRT_OK;
+    wgrt_status e = WGRT_OK;
+    if (ch->sc) {
+        DeviceScope dev_scope(ch->s->device);
+        e = chain_join(ch);
+        std::lock_guard<std::mutex> lk(ch->s->scratch_mu);
+        ch->sc->chain_open = false;
+    }
+    delete ch;
+    return e;
+}
+
+wgrt_status wgrt_debug_chain_plan(int64_t in_segment, uint32_t serial, uint32_t flags, wgrt_chain_plan *out) {
+    if (!out || in_segment < -1 || serial > WGRT_CHAIN_SERIAL_MAX)
+        return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL out / bad in_segment / serial");
+    *out = chain_plan(in_segment, serial, flags);
+    return WGRT_OK;
+}
+
+wgrt_status wgrt_debug_chain_set_serial(const wgrt_scene *s, void *stream, uint32_t serial) {
+    if (!s || serial > WGRT_CHAIN_SERIAL_MAX) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL scene / serial out of range");
+    wgrt_scene *ms = const_cast<wgrt_scene *>(s);
+    DEVICE_SCOPE(dev_scope, s->device);
+    std::lock_guard<std::mutex> lk(ms->scratch_mu);
+    wgrt_scene::Scratch &sc = ms->scratch[stream];
+    if (sc.chain_open) return fail(WGRT_ERR_INVALID_ARGUMENT, "a chain is open on this stream");
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    if (sc.chain_gran) HIP_TRY(hipMemset(sc.chain_gran, 0, (size_t)sc.chain_cap * sizeof(uint64_t)));
+    sc.chain_serial = serial;
+    return WGRT_OK;
 }
 
 wgrt_status wgrt_trace_opts(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,

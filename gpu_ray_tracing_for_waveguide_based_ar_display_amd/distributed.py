@@ -193,8 +193,18 @@ def run_steps(trace_fn, rays, rng, eb, gid: GidMap, steps: int, per_call: int = 
     at most ``per_call`` traces (``trace_fn(..., num_iter=k)``; a fused call gives the results
     of k separate ones).  ``eb`` is handed to ``trace_fn`` as it is: None for a tracer that carries the
     window-table sink alone (``hip_tracer(windows=...)``).  ``hook(j, "start" | "end")`` brackets call j (HIP events in bench.py).
+    Separate launches (``per_call == 1``, more than one step, no hook) of a tracer that offers ``chain`` are issued
+    as one: still one kernel launch per trace, the same results, consecutive launches overlapping.
     Returns the traces per call."""
     calls = split_calls(steps, per_call)
+    chain = getattr(trace_fn, "chain", None)
+    if chain is not None and per_call == 1 and steps > 1 and hook is None:
+        # separate launches all the same, issued as a chain: consecutive launches overlap across two hardware
+        # queues (engine.TraceChain).  With a hook the calls stay plain launches: it brackets each one on the stream
+        with chain(rays, rng, eb, gid) as ch:
+            for _ in calls:
+                ch.step()
+        return calls
     for j, k in enumerate(calls):
         if hook is not None:
             hook(j, "start")
@@ -482,14 +492,25 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None):
     ``windows=(plan, table)``: every call also counts its out-couplings into the pupil-window table
     (``engine.trace_fullcolor(windows=...)``), and ``eb`` may be None -- a grid-free job.  Every rank's table is
     the full ``[n_slabs, W]`` with its top-edge spills already in the slabs they alias into, so the collective
-    of such a job is ``reduce_eyebox(table)``, one sum-reduce: no slab list, no scatter."""
-    from .engine import trace_fullcolor
+    of such a job is ``reduce_eyebox(table)``, one sum-reduce: no slab list, no scatter.
+
+    ``fn.chain(rays, rng, eb, gid)`` returns an ``engine.TraceChain`` over the same arguments: a context whose
+    ``step()`` is one such call with ``num_iter = 1``."""
+    from .engine import TraceChain, trace_fullcolor
+
+    def ids_of(rng, gid: GidMap):
+        off = gid.offset
+        return dict(gid_offset=off) if off is not None else dict(gid_blocks=gid.device_blocks(rng.device),
+                                                                 gid_block_rays=gid.rays_per_block)
 
     def fn(rays, rng, eb, gid: GidMap, num_iter=1):
-        off = gid.offset
-        ids = dict(gid_offset=off) if off is not None else dict(gid_blocks=gid.device_blocks(rng.device),
-                                                                gid_block_rays=gid.rays_per_block)
-        trace_fullcolor(scene, rays, rng, eb, stats=stats, variant=variant, num_iter=num_iter, windows=windows, **ids)
+        trace_fullcolor(scene, rays, rng, eb, stats=stats, variant=variant, num_iter=num_iter, windows=windows,
+                        **ids_of(rng, gid))
+
+    def chain(rays, rng, eb, gid: GidMap):
+        """The same launches as a chain (``run_steps`` uses it for separate launches without a hook)."""
+        return TraceChain(scene, rays, rng, eb, stats=stats, variant=variant, windows=windows, **ids_of(rng, gid))
+    fn.chain = chain
     return fn
 
 

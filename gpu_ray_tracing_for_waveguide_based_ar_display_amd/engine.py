@@ -219,7 +219,7 @@ def _read_columns(rays, rng_states, n_rays, single, device):
 
 def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single, chunk_order=None, num_iter=1, gid_blocks=None, gid_block_rays=0, debug=None,
-           grid_sqrt_k=0.0, windows=None):
+           grid_sqrt_k=0.0, windows=None, chain=False):
     device = torch.device("cuda", scene.device)
     cols, N = _read_columns(rays, rng_states, n_rays, single, device)
     x = cols["x"]
@@ -257,11 +257,81 @@ def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ra
             int(workgroups), chunk_order, int(num_iter), gid_blocks,
             int(gid_block_rays) if gid_blocks is not None else 0,
             ctypes.addressof(dbg) if dbg is not None else 0, float(grid_sqrt_k))
+    if chain:
+        # torch.ops.wgrt.chain_begin -> wgrt_chain_begin: nothing is launched; the handle, and everything the
+        # chain's launches will read or write (the side stream uses memory torch's allocator accounts to the
+        # caller's stream, so the tensors must outlive the chain: TraceChain holds them until end)
+        h = ops().chain_begin(*args, plan.handle.value if windows is not None else 0,
+                              table if windows is not None else None)
+        if h <= 0:   # the negated wgrt_status of the failure
+            check(-h, "wgrt_chain_begin")
+        return h, (args, dbg, windows)
     if windows is None:
         status = ops().trace(*args)
     else:
         status = ops().trace_windows(*args, plan.handle.value, table)
     check(status, "wgrt_trace_single" if single else "wgrt_trace_fullcolor")
+
+
+class TraceChain:
+    """A chain of single traces of one batch (``wgrt_chain_begin`` / ``_step`` / ``_end``): each ``step()`` is one
+    launch (``num_iter = 1``) and the chain leaves exactly what as many ``trace_fullcolor`` calls leave --
+    ``rng_states``, ``matrix_EB`` / window table and ``stats``, bit for bit -- but consecutive launches run on two
+    hardware queues, so one launch's drain is covered by the next one's bulk (DESIGN.md §4.3).  A context manager::
+
+        with TraceChain(scene, rays, rng, eb, stats=stats) as ch:
+            for _ in range(k):
+                ch.step()
+
+    Takes ``trace_fullcolor``'s arguments (no ``per_ray_bounces``).  Between ``__enter__`` and ``__exit__`` nothing
+    else may touch ``rng_states``, ``matrix_EB``, the window table or ``stats`` on the stream; after ``__exit__``
+    the stream is ordered after every step.  The chain holds references to every tensor until it ends, and
+    ``__exit__`` always ends it, also on an exception.  Steps that cannot be chained (the scene's learning
+    launches, variant 1, ``chunk_order``, a debug timeline, a stream under capture) run as plain launches."""
+
+    def __init__(self, scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_EB: torch.Tensor | None,
+                 gid_offset: int = 0, n_rays: int | None = None, stats: torch.Tensor | None = None, stream=None,
+                 variant: int = VARIANT_AUTO, workgroups: int = 0, chunk_order: torch.Tensor | None = None,
+                 gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
+                 grid_sqrt_k: float = 0.0, windows=None):
+        if scene.single_lambda:
+            raise ValueError("TraceChain needs a full-colour scene")
+        self._h = 0
+        self._step = ops().chain_step
+        self._h, self._keep = _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, None, stream,
+                                     variant, workgroups, single=False, chunk_order=chunk_order, gid_blocks=gid_blocks,
+                                     gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k,
+                                     windows=windows, chain=True)
+        self.steps = 0
+
+    def step(self) -> None:
+        if not self._h:
+            raise WgrtError("the chain has ended")
+        status = self._step(self._h)
+        if status:
+            check(status, "wgrt_chain_step")
+        self.steps += 1
+
+    def end(self) -> None:
+        h, self._h = self._h, 0
+        if h:
+            try:
+                check(ops().chain_end(h), "wgrt_chain_end")
+            finally:
+                self._keep = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.end()
+        return False
+
+    def __del__(self):
+        try:
+            self.end()
+        except Exception:
+            pass
 
 
 def timeline_summary(buf, percentiles: bool = True) -> dict:
@@ -431,6 +501,6 @@ def selftest_math(a: torch.Tensor, b: torch.Tensor, stream=None) -> torch.Tensor
     return out
 
 
-__all__ = ["Scene", "WindowPlan", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
+__all__ = ["Scene", "WindowPlan", "TraceChain", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
            "trace_fullcolor", "trace_single", "init_rays", "schedule_by_lifetime",
            "rays_to_device", "classify_points", "shadow", "selftest_math", "RAY_COLUMNS", "_lib"]

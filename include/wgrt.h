@@ -379,6 +379,34 @@ wgrt_status wgrt_trace_windows(const wgrt_scene *scene, const wgrt_rays *rays, i
                                uint32_t *per_ray_bounces, void *stream, const wgrt_launch_opts *opts,
                                const wgrt_window_plan *plan, double *table);
 
+/* Chained single launches (new symbols within ABI 9, looked up by name).  A chain is a run of single traces
+ * (num_iter = 1 each) of one batch, every trace starting from the RNG states the previous one left -- what the
+ * same number of wgrt_trace_windows calls would compute, bit for bit (rng_states, matrix_EB / table, stats) --
+ * issued so that one launch's drain overlaps the next launch's bulk: the steps alternate between the caller's
+ * stream and one library-owned non-blocking side stream, and step k + 1 takes ray i's state from the granule
+ * step k's trace of ray i published (the fused launches' per-ray hand-off, across the kernel boundary).
+ *   begin  takes the arguments of wgrt_trace_windows (no per_ray_bounces; plan / table may be NULL), copies
+ *          them (opts and its debug record included; the device buffers must stay alive until end) and sizes
+ *          both sides' launch scratch, so that no step allocates or synchronises;
+ *   step   enqueues one trace: its own kernel launch, with the arguments a plain launch would get;
+ *   end    joins the side stream into the caller's, leaves rng_states at the last step's states and frees the
+ *          chain.  After it returns, `stream` is ordered after every step, as if they had been plain launches.
+ * Between begin and end the caller enqueues nothing on `stream` that touches rng_states, matrix_EB, the table
+ * or stats, starts no other chain or trace of the scene on it, and begins no graph capture on it while steps are
+ * in flight (a chain looks at the stream's capture state at begin and whenever it opens a segment).  Steps that cannot be chained run as plain
+ * launches on `stream`, after a join: a launch that still learns the scene's tile table, variant 1, a
+ * single-wavelength scene, num_iter > 1, chunk_order, a debug timeline, a stream under capture, and a batch so
+ * large that one launch's grid is the kernel's resident grid (it fills the chip alone: nothing to overlap)
+ * (wgrt_debug_chain_plan states the rule).  wgrt_trace_stats.handoff_giveups counts hand-offs given up
+ * (a bug: the results of the chain are then invalid), as for fused launches. */
+typedef struct wgrt_chain wgrt_chain;
+wgrt_status wgrt_chain_begin(const wgrt_scene *scene, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
+                             uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats, void *stream,
+                             const wgrt_launch_opts *opts, const wgrt_window_plan *plan, double *table,
+                             wgrt_chain **out);
+wgrt_status wgrt_chain_step(wgrt_chain *chain);
+wgrt_status wgrt_chain_end(wgrt_chain *chain);
+
 /* Host-only (no GPU needed; test hooks) through the same membership code (csrc/wgrt_window.h):
  * _validate is wgrt_window_plan_create's argument check alone; _table_host ADDS the n hits at flat grid
  * offsets offsets[n] (HOST int64; those outside [0, n_slabs * 9600) are dropped, as the grid's guard drops

@@ -100,6 +100,37 @@ wgrt_status wgrt_debug_get_tile_tail(const wgrt_scene *scene, uint32_t *out, int
 wgrt_status wgrt_debug_order_host(const uint32_t *tile_tail, int64_t n_tiles, const int32_t *chunk_tile,
                                   int64_t n_chunks, int32_t *order);
 
+/* The host logic of a chain (wgrt_chain_step; no device): where the next step goes, given what the step is
+ * (flags) and where the chain stands (in_segment: chained steps issued since the segment opened, -1 when no
+ * segment is open; serial: the last granule tag serial handed out).  Any flag makes the step a plain launch
+ * on the caller's stream, behind a join when a segment is open.  A chained step opens a segment when none is
+ * open (seed: rng_states -> granules on the caller's stream, the side stream made to wait for it) and closes
+ * and reopens it when the tag serial would run out (WGRT_CHAIN_SERIAL_MAX); step k of a segment goes to the
+ * caller's stream for even k and to the side stream for odd k, waits for the tag serial - 1 and publishes
+ * serial. */
+#define WGRT_CHAIN_LEARNS 1u      /* the launch would still learn the scene's tile table */
+#define WGRT_CHAIN_VARIANT1 2u    /* variant 1, or auto on more than 2^32 - 1 rays */
+#define WGRT_CHAIN_SINGLE 4u      /* the single-wavelength kernel */
+#define WGRT_CHAIN_FUSED 8u       /* num_iter > 1 */
+#define WGRT_CHAIN_DEBUG 16u      /* chunk_order or a debug timeline */
+#define WGRT_CHAIN_CAPTURE 32u    /* the caller's stream is under graph capture */
+#define WGRT_CHAIN_FULL 64u       /* the launch's own grid is the kernel's resident grid: it fills the chip alone */
+#define WGRT_CHAIN_SERIAL_MAX 0x7ffffffeu
+typedef struct {
+    int chained;        /* 1: the chained kernel; 0: a plain launch on the caller's stream */
+    int side;           /* 0: the caller's stream, 1: the side stream */
+    int join;           /* 1: the open segment is closed first (side stream joined, finalize) */
+    int seed;           /* 1: a segment is opened first (after the join, if any) */
+    int clear;          /* 1: the granules are cleared and the serial restarts before the seed */
+    uint32_t wait_serial, publish_serial;   /* chained: the tag it takes states from, the tag it publishes */
+    uint32_t serial_after;                  /* the chain's serial after the step */
+    int64_t in_segment_after;               /* ... and its in_segment */
+} wgrt_chain_plan;
+wgrt_status wgrt_debug_chain_plan(int64_t in_segment, uint32_t serial, uint32_t flags, wgrt_chain_plan *out);
+/* Sets the tag serial of the stream's granules (clearing them), so that a test reaches WGRT_CHAIN_SERIAL_MAX
+ * within a few steps.  No chain may be open on the stream.  Waits for the stream. */
+wgrt_status wgrt_debug_chain_set_serial(const wgrt_scene *scene, void *stream, uint32_t serial);
+
 #ifdef __cplusplus
 }
 #endif
