@@ -28,7 +28,8 @@ EXPORTED = ("wgrt_scene_create", "wgrt_scene_create_ex", "wgrt_scene_destroy", "
             "wgrt_eyebox_window_sums", "wgrt_eyebox_evaluate_workspace_bytes", "wgrt_eyebox_evaluate",
             "wgrt_eyebox_evaluate_host", "wgrt_window_plan_create", "wgrt_window_plan_destroy",
             "wgrt_window_plan_width", "wgrt_trace_windows", "wgrt_window_plan_validate", "wgrt_window_table_host",
-            "wgrt_chain_begin", "wgrt_chain_step", "wgrt_chain_end")
+            "wgrt_chain_begin", "wgrt_chain_step", "wgrt_chain_end", "wgrt_trace_fate", "wgrt_fate_census",
+            "wgrt_fate_census_host", "wgrt_fate_col", "wgrt_fate_cols", "wgrt_fate_reason_name")
 EXPORTED_DEBUG = ("wgrt_debug_shadow", "wgrt_debug_scene_copy", "wgrt_debug_set_auto_order",
                   "wgrt_debug_get_auto_order", "wgrt_debug_get_tile_tail", "wgrt_debug_order_host",
                   "wgrt_debug_chain_plan", "wgrt_debug_chain_set_serial")
@@ -270,6 +271,20 @@ def load():
         L.wgrt_debug_chain_plan.argtypes = [ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ChainPlan)]
         L.wgrt_debug_chain_set_serial.restype = st
         L.wgrt_debug_chain_set_serial.argtypes = [_vp, _vp, ctypes.c_uint32]
+    if hasattr(L, "wgrt_trace_fate"):   # per-ray fates and their census: new symbols within ABI 9, bound by name
+        L.wgrt_trace_fate.restype = st
+        L.wgrt_trace_fate.argtypes = L.wgrt_trace_opts.argtypes + [_vp, _vp, _vp]
+        cen = [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp]
+        L.wgrt_fate_census.restype = st
+        L.wgrt_fate_census.argtypes = cen + [_vp]
+        L.wgrt_fate_census_host.restype = st
+        L.wgrt_fate_census_host.argtypes = cen
+        L.wgrt_fate_col.restype = ctypes.c_int32
+        L.wgrt_fate_col.argtypes = [ctypes.c_int]
+        L.wgrt_fate_cols.restype = ctypes.c_int32
+        L.wgrt_fate_cols.argtypes = []
+        L.wgrt_fate_reason_name.restype = ctypes.c_char_p
+        L.wgrt_fate_reason_name.argtypes = [ctypes.c_int]
     L.wgrt_status_string.restype = ctypes.c_char_p
     L.wgrt_status_string.argtypes = [ctypes.c_int]
     L.wgrt_last_error.restype = ctypes.c_char_p

@@ -92,6 +92,10 @@ struct TraceArgs {
     // field keeps its place in the kernarg segment.
     double *win_table;
     const WindowPlanView *win;
+    // per-ray fate codes (wgrt_trace_fate; wgrt_fate.h): with fate, the lane that ends ray i's trace stores its
+    // code in fate[i] (0 for a ray that is not traced).  NULL: nothing is stored.  Single launches only; the
+    // Jones-vector lane stores it in its FATE instantiations.  Last again, for the same reason.
+    uint8_t *fate;
 };
 
 // TraceArgs fields re-read from the kernarg segment where they are used (a volatile scalar load,

@@ -6,10 +6,16 @@
 //   lane_load, take_branch, advance, lane_retire
 //                 the certification shadow too (wgrt_shadow.hip), around its own literal all-branches decision:
 //                 what it certifies the product lane against is this file's arithmetic, not a copy of it;
-//   eyebox_add    interact's out-coupling and the Jones kernels' out-coupling queue (bin_entry, wgrt_trace.hip).
+//   eyebox_add    the Jones kernels' out-coupling queue (bin_entry, wgrt_trace.hip); interact's out-coupling runs
+//                 its two halves, eyebox_inside (the rectangle test: also the fate's reason 3 / 4, and what the
+//                 Jones lane's FATE instantiations call) and eyebox_bin.
+// FATE (a template parameter of interact, advance, lane_retire and trace_one; off by default): every place a trace
+// ends sets the lane's fate code (wgrt_fate.h) and lane_retire stores it beside per_ray.  Without it the lane is
+// the code it was before fates existed -- the replays inlined into the Jones kernels keep their registers.
 #pragma once
 
 #include "wgrt_args.h"
+#include "wgrt_fate.h"
 #include "wgrt_locator.h"
 #include "wgrt_window.h"
 
@@ -71,6 +77,7 @@ struct Lane {
     uint32_t bounces;  // 1 in-coupling event + loop iterations (GRTF:905)
     bool hit;          // accumulated into matrix_EB
     bool libm;         // a guard product ener * e_k fell below 2^-1000 (wgrt_trace_stats.libm_rays)
+    uint8_t why;       // fate code (wgrt_fate.h), set where the trace ends
 };
 
 // Load ray i (GRTF:846-859).  Returns false (and leaves the lane empty) for a ray whose
@@ -95,15 +102,20 @@ __device__ __forceinline__ bool lane_load(const TraceArgs &A, int64_t i, Lane &L
     L.bounces = 1;
     L.hit = false;
     L.libm = false;
+    L.why = 0;
     return true;
 }
 
 // Eyebox accumulation of an out-coupling (GRTF:1162-1171, 1231-1240) of a ray of tile T = (l, m, n) at (x, y):
-// the per-FoV eyebox rectangle test, the bin, and the atomic -- into the grid, into the pupil-window table of
-// wgrt_trace_windows, or both (wave-uniform: they are launch arguments).  Returns whether the bin was added to.
-__device__ __forceinline__ bool eyebox_add(const TraceArgs &A, const double *T, int l, int m, int n, double x,
+// the per-FoV eyebox rectangle test (eyebox_inside: the one statement of it), then the bin and the atomic
+// (eyebox_bin) -- into the grid, into the pupil-window table of wgrt_trace_windows, or both (wave-uniform: they
+// are launch arguments).  eyebox_bin / eyebox_add return whether the bin was added to.
+__device__ __forceinline__ bool eyebox_inside(const double *T, double x, double y) {
+    return inside_or_on_edge(x, y, T + kTileEbRect, 4);
+}
+
+__device__ __forceinline__ bool eyebox_bin(const TraceArgs &A, const double *T, int l, int m, int n, double x,
                                            double y) {
-    if (!inside_or_on_edge(x, y, T + kTileEbRect, 4)) return false;
     const double xmin = T[kTileEbRange], xmax = T[kTileEbRange + 1];
     const double ymin = T[kTileEbRange + 2], ymax = T[kTileEbRange + 3];
     const double dx = (xmax - xmin) / kEbNx, dy = (ymax - ymin) / kEbNy;
@@ -124,6 +136,11 @@ __device__ __forceinline__ bool eyebox_add(const TraceArgs &A, const double *T, 
         return true;
     }
     return false;
+}
+
+__device__ __forceinline__ bool eyebox_add(const TraceArgs &A, const double *T, int l, int m, int n, double x,
+                                           double y) {
+    return eyebox_inside(T, x, y) && eyebox_bin(A, T, l, m, n, x, y);
 }
 
 // Take branch b (0 or 1) of block B in state `kind` (GRTF:872-882 and every branch body after it): cte / ctm are
@@ -150,7 +167,7 @@ __device__ __forceinline__ int take_branch(const Loc &loc, Lane &L, const double
     if (kind == 0) {
         const bool in_ic = in_poly(loc, locate(loc, r.x, r.y), kPolyIC, r.x, r.y);
         if (b == 0) return in_ic ? 0 : 2;
-        return in_ic ? 1 : kDie;
+        return in_ic ? 1 : kDie;   // (interact sets the fate: reason 6)
     }
     if (kind <= 2) return b == 0 ? 2 : 3;
     return b == 0 ? 4 : 5;
@@ -159,9 +176,10 @@ __device__ __forceinline__ int take_branch(const Loc &loc, Lane &L, const double
 // A coupler interaction: `blk` of the lane's tile, `kind` 0 in-coupler states (entry event,
 // R0, R1), 1 R2, 2 R3, 3 R4, 4 R5.  Evaluates every branch's efficiency (GRTF:860-869,
 // 909-918, ..., 1186-1200), draws, and applies the chosen branch.  Returns the next region
-// or kDie.  Only the chosen branch's phase (two atan2) is evaluated; its field is recomputed
+// or kDie (FATE: with the lane's fate set; its region is the state the ray is in, 9 at the entry).
+// Only the chosen branch's phase (two atan2) is evaluated; its field is recomputed
 // by the same operations rather than kept in registers for every branch.
-template <class Loc>
+template <bool FATE = false, class Loc>
 __device__ __forceinline__ int interact(const TraceArgs &A, const Loc &loc, Lane &L, int blk, int kind,
                                         bool entry) {
     Ray &r = L.r;
@@ -174,6 +192,7 @@ __device__ __forceinline__ int interact(const TraceArgs &A, const Loc &loc, Lane
     const bool thr = kind >= 1;  // the ener > threshold guard exists only in R2..R5
     const double denom = entry ? T[kTileCosIc1] : r.cos_t;
     const double u = rng_draw_lazy(r.s, [&]() { return ray_gid(A, L.i); });
+    const int freg = entry ? kFateEntry : r.region;   // (FATE only)
 
     // Decide the branch.  The reference compares u with cumulative branch efficiencies
     // e_k = (hypot(Ete')^2 + hypot(Etm')^2) * cosA_k / cos(theta) [* or / n_g].  Here the
@@ -227,7 +246,10 @@ __device__ __forceinline__ int interact(const TraceArgs &A, const Loc &loc, Lane
         if (u <= c0 && pass0) b = 0;
         else if (u <= c1 && pass1) b = 1;
         else if (three && u <= c2 && pass2) b = 2;
-        else return kDie;
+        else {
+            if (FATE) L.why = fate_code(freg, kFateLost);
+            return kDie;
+        }
     } else {
         double te[3], tm[3];
 #pragma unroll
@@ -258,11 +280,20 @@ __device__ __forceinline__ int interact(const TraceArgs &A, const Loc &loc, Lane
         if (u <= e0 && (!thr || r.ener * e0 > t)) b = 0;
         else if (u <= e0 + e1 && (!thr || r.ener * e1 > t)) b = 1;
         else if (three && u <= e0 + e1 + e2 && r.ener * e2 > t) b = 2;
-        else return kDie;
+        else {
+            if (FATE) L.why = fate_code(freg, kFateLost);
+            return kDie;
+        }
     }
 
     if (b == 2) {  // out-coupling (GRTF:1162-1171, 1231-1240)
-        if (eyebox_add(A, T, L.l, L.m, L.n, r.x, r.y)) L.hit = true;
+        if (FATE) {
+            const bool in = eyebox_inside(T, r.x, r.y);
+            if (in && eyebox_bin(A, T, L.l, L.m, L.n, r.x, r.y)) L.hit = true;
+            L.why = fate_code(freg, in ? kFateEyebox : kFateBeside);
+        } else if (eyebox_add(A, T, L.l, L.m, L.n, r.x, r.y)) {
+            L.hit = true;
+        }
         return kDie;
     }
     const Field f = efield(r.te, r.tm, cd, sd, B + kBlockRec + 8 * b);
@@ -273,17 +304,20 @@ __device__ __forceinline__ int interact(const TraceArgs &A, const Loc &loc, Lane
     // E_field_cal's output phase (GRTF:145-150): 0 for a component below 1e-20, wrapped difference
     const double pte = cte >= 1e-20 ? atan2(f.te_im, f.te_re) : 0.0;
     const double ptm = ctm >= 1e-20 ? atan2(f.tm_im, f.tm_re) : 0.0;
-    return take_branch(loc, L, B, b, kind, cte, ctm, wrap_pi(ptm - pte), e);
+    const int next = take_branch(loc, L, B, b, kind, cte, ctm, wrap_pi(ptm - pte), e);
+    if (FATE && next == kDie) L.why = fate_code(freg, kFateLeftIc);
+    return next;
 }
 
 // Run a ray through the loop iterations that need no Monte-Carlo interaction -- hops that
 // miss every coupler slice (GRTF:1049-1052, 1102-1108, 1175-1178) and the R3 -> R4 switch
 // -- until the next interaction is due.  Returns that interaction's block index, or kDie
 // when the ray terminated (left eff_reg1 at GRTF:906, R5 miss at GRTF:1244-1246, or
-// range(1e5) exhausted).  Each iteration counts one bounce.  With `hops`, the miss hops made are added to it
+// range(1e5) exhausted; FATE: the lane's fate is set, reason 1, 5 or 7 in the region the ray is in).
+// Each iteration counts one bounce.  With `hops`, the miss hops made are added to it
 // (the certification shadow turns its Jones state by as many hop phasors; everything is inlined, so the
 // other callers pay nothing for it).
-template <class Loc>
+template <bool FATE = false, class Loc>
 __device__ __forceinline__ int advance(const TraceArgs &A, const Loc &loc, Lane &L, int &kind,
                                        uint32_t *hops = nullptr) {
     Ray &r = L.r;
@@ -294,10 +328,16 @@ __device__ __forceinline__ int advance(const TraceArgs &A, const Loc &loc, Lane 
     const double gx = T[kTileGap + g], gy = T[kTileGap + g + 1];
     const double tir2 = 2 * T[kTileTir + g / 2];   // 2*lut_TIR[...] (exact doubling)
     for (;;) {
-        if (L.bounces > (uint32_t)kMaxLoop) return kDie;
+        if (L.bounces > (uint32_t)kMaxLoop) {
+            if (FATE) L.why = fate_code(r.region, kFateBounceCap);
+            return kDie;
+        }
         ++L.bounces;
         const Cell c = locate(loc, r.x, r.y);
-        if (!in_poly(loc, c, kPolyEff1, r.x, r.y)) return kDie;
+        if (!in_poly(loc, c, kPolyEff1, r.x, r.y)) {
+            if (FATE) L.why = fate_code(r.region, kFateLeftEff1);
+            return kDie;
+        }
         const int region = r.region;
         if (region <= 1) {
             kind = 0;
@@ -320,7 +360,10 @@ __device__ __forceinline__ int advance(const TraceArgs &A, const Loc &loc, Lane 
                 kind = region - 1;
                 return 3 + 2 * A.nfc + (region - 4) * A.noc + s;
             }
-            if (region == 5) return kDie;
+            if (region == 5) {
+                if (FATE) L.why = fate_code(5, kFateOcMiss);
+                return kDie;
+            }
         }
         r.x += gx;
         r.y += gy;
@@ -329,10 +372,11 @@ __device__ __forceinline__ int advance(const TraceArgs &A, const Loc &loc, Lane 
     }
 }
 
-template <class LaneT>
+template <bool FATE = false, class LaneT>
 __device__ __forceinline__ void lane_retire(const TraceArgs &A, const LaneT &L) {
     A.rng[L.i] = L.r.s;
     if (A.per_ray) A.per_ray[L.i] = L.bounces;
+    if (FATE) A.fate[L.i] = L.why;   // (a FATE kernel is launched with the buffer)
 }
 
 // Per-wave reduction of the ray counters, then one 64-bit atomic per non-zero counter per wave.
@@ -344,26 +388,28 @@ __device__ __forceinline__ void add_stats(wgrt_trace_stats *stats, Counters c) {
 // Trace ray i to termination with the reference arithmetic (variant 1's lane; replays), counted in c.  With
 // s_io, the trace starts from *s_io instead of rng_states[i] and leaves its final state there
 // (rng_states untouched).
+template <bool FATE = false>
 __device__ __forceinline__ void trace_one(const TraceArgs &A, int64_t i, Counters &c, uint32_t *s_io = nullptr) {
     Lane L;
     if (!lane_load(A, i, L)) {
         ++c.w[kCtrBadRays];
+        if (FATE) A.fate[i] = 0;   // no trace (wgrt_fate.h)
         return;
     }
     if (s_io) L.r.s = *s_io;
     int blk = 0, kind = 0;
     bool entry = true;
     for (;;) {
-        const int next = interact(A, A.loc, L, blk, kind, entry);
+        const int next = interact<FATE>(A, A.loc, L, blk, kind, entry);
         if (next < 0) break;
         L.r.region = next;
         entry = false;
-        blk = advance(A, A.loc, L, kind);
+        blk = advance<FATE>(A, A.loc, L, kind);
         if (blk < 0) break;
         ++c.w[kCtrInter];   // the interactions after the in-coupling event
     }
     if (s_io) *s_io = L.r.s;
-    else lane_retire(A, L);
+    else lane_retire<FATE>(A, L);
     c.w[kCtrBounces] += L.bounces;
     c.w[kCtrHits] += L.hit;
     c.w[kCtrLibm] += L.libm ? 1u : 0u;

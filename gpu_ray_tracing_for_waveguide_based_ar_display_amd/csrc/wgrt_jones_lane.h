@@ -63,7 +63,9 @@ struct JLane {
     uint64_t pf;             // locator cell word of (x, y), loaded a step ahead
 };
 
-enum : int { kUncertain = -3, kOut = -4 };
+// (kDieIc: what a FATE instantiation's interact returns instead of kDie where the in-coupler's second order leaves
+// the in-coupler -- fate reason 6, wgrt_fate.h; every other die of interact is reason 2)
+enum : int { kUncertain = -3, kOut = -4, kDieIc = -5 };
 
 // Default bases of the certification bounds (wgrt_debug_opts overrides them per call): the
 // double-precision evaluation's, and the single-precision estimate's -- 8e-6 covers the rounding
@@ -358,7 +360,9 @@ __device__ __forceinline__ float amp_step(float amp, float pa, float nmin, doubl
 // abandoned.  The taken branch's field is always computed in double precision from its
 // double-precision matrix (loaded after the decision), so the carried Jones vector and ener
 // are the same values the all-double evaluation gives.
-template <bool SINGLE, bool AMP, class Loc>
+// FATE (the fate-storing instantiations, wgrt_trace_fate): the one die that is not a Monte-Carlo loss returns
+// kDieIc, so the caller can tell fate reason 6 from 2; nothing else differs.
+template <bool SINGLE, bool AMP, bool FATE, class Loc>
 __device__ __forceinline__ int interact(const TraceArgs &A, const KArgs &K, const Loc &loc, JLane &L, int blk,
                                         int kind, bool entry, SegAcc *sg = nullptr) {
     JRay &r = L.r;
@@ -451,7 +455,7 @@ __device__ __forceinline__ int interact(const TraceArgs &A, const KArgs &K, cons
     if (kind == 0) {
         const bool in_ic = in_poly_w(loc, (typename Loc::Word)L.pf, kPolyIC, r.x, r.y, &K);
         if (ba) return in_ic ? 0 : 2;
-        return in_ic ? 1 : kDie;
+        return in_ic ? 1 : (FATE ? kDieIc : kDie);
     }
     if (kind <= 2) return ba ? 2 : 3;
     return ba ? 4 : 5;
@@ -493,8 +497,11 @@ __device__ __forceinline__ int low_bit(uint64_t v) { return __builtin_ctzll(v); 
 // evaluation per lane -- and only lanes whose outcome hinges on an EDGE class take the (rare)
 // exact path first: the earlier nested per-slice tests cost every wave-pass the exec-mask
 // bookkeeping of every slice's exact test (SALU per bounce).
-template <class Loc>
-__device__ __forceinline__ int advance(const TraceArgs &A, const KArgs &K, const Loc &loc, JLane &L, int &kind) {
+// FATE: a trace this iteration ends leaves its fate code in *why (wgrt_fate.h), one more select: the cap before
+// eff_reg1 before the R5 miss, the oracle's order (its loop ends before the next eff_reg1 test).
+template <bool FATE = false, class Loc>
+__device__ __forceinline__ int advance(const TraceArgs &A, const KArgs &K, const Loc &loc, JLane &L, int &kind,
+                                       uint32_t *why = nullptr) {
     using W = typename Loc::Word;
     constexpr int kBits = 8 * (int)sizeof(W);
     constexpr W kLow = (W)0x5555555555555555ull;
@@ -552,6 +559,7 @@ __device__ __forceinline__ int advance(const TraceArgs &A, const KArgs &K, const
     }
     const int step = hit ? blkbase + sl : kTransit;
     const int next = ic ? 1 + region : step;
+    if (FATE) *why = die ? (uint32_t)(10 * region + (over ? 7 : !eff1 ? 1 : 5)) : *why;
     return die ? kDie : next;
 }
 

@@ -17,7 +17,8 @@
 // The window sink's entry points arrived within ABI 9 and are looked up by name at the first trace_windows
 // call (as _lib.load binds them), so the operator library still loads over an earlier ABI-9 build of libwgrt
 // (tools/with_lib.py), where trace keeps working and trace_windows raises.  The same holds for the chained launches'
-// entry points (wgrt_chain_*; torch.ops.wgrt.chain_begin / chain_step / chain_end, engine.TraceChain).
+// entry points (wgrt_chain_*; torch.ops.wgrt.chain_begin / chain_step / chain_end, engine.TraceChain) and for
+// wgrt_trace_fate (torch.ops.wgrt.trace_fate: the launch that also stores every ray's fate code).
 #include <torch/library.h>
 
 #include <ATen/core/Tensor.h>
@@ -89,6 +90,13 @@ const ChainAbi &chain_abi() {
     return abi;
 }
 
+// wgrt_trace_fate (per-ray fate codes), new within ABI 9 too: looked up at the first trace_fate call.
+decltype(&wgrt_trace_fate) fate_abi() {
+    static const auto fn = reinterpret_cast<decltype(&wgrt_trace_fate)>(dlsym(RTLD_DEFAULT, "wgrt_trace_fate"));
+    TORCH_CHECK(fn, "wgrt.trace_fate: the loaded libwgrt.so has no wgrt_trace_fate (a build from before the ray fates)");
+    return fn;
+}
+
 // All three launching operators: trace (the grid alone: plan 0, no table), trace_windows (the grid, the window
 // table of plan `plan` -- a wgrt_window_plan handle -- or both) and, with `chain`, chain_begin: the same checks and
 // records handed to wgrt_chain_begin, which launches nothing and leaves the chain's handle in *chain.
@@ -98,7 +106,8 @@ int64_t trace_core(int64_t scene, const Tensor &x, const Tensor &y, const Tensor
                    std::optional<Tensor> per_ray_bounces, int64_t n_rays, int64_t gid_offset, int64_t stream,
                    int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
                    int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
-                   double grid_sqrt_k, int64_t plan, std::optional<Tensor> table, wgrt_chain **chain) {
+                   double grid_sqrt_k, int64_t plan, std::optional<Tensor> table, wgrt_chain **chain,
+                   std::optional<Tensor> fate = std::nullopt) {
     const wgrt_scene *s = reinterpret_cast<const wgrt_scene *>(static_cast<uintptr_t>(scene));
     TORCH_CHECK(s != nullptr, "wgrt.trace: NULL scene");
     wgrt_scene_info info{};
@@ -186,6 +195,13 @@ int64_t trace_core(int64_t scene, const Tensor &x, const Tensor &y, const Tensor
         TORCH_CHECK(!per, "wgrt.chain_begin: a chain takes no per_ray_bounces");
         return chain_abi().begin(s, &r, n_rays, gid_offset, rng, eb, stp, hip_stream, &o, tab ? wp : nullptr, tab, chain);
     }
+    if (fate) {   // trace_fate: one uint8 per ray of the batch, written by the lane that ends the ray's trace
+        on_device(*fate, "fate", c);
+        TORCH_CHECK(fate->scalar_type() == at::kByte, "wgrt.trace_fate: fate must be uint8");
+        TORCH_CHECK(fate->numel() == c.rays, "wgrt.trace_fate: fate holds ", fate->numel(), " entries, the batch has ", c.rays);
+        return fate_abi()(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o, tab ? wp : nullptr, tab,
+                          static_cast<uint8_t *>(fate->data_ptr()));
+    }
     if (!tab) return wgrt_trace_opts(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o);
     return window_abi().trace(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o, wp, tab);
 }
@@ -200,6 +216,19 @@ int64_t trace_impl(int64_t scene, const Tensor &x, const Tensor &y, const Tensor
     return trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats, per_ray_bounces,
                       n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
                       gid_block_rays, debug, grid_sqrt_k, plan, table, nullptr);
+}
+
+// trace_fate: trace_windows' arguments and the fate buffer (wgrt_trace_fate).
+int64_t trace_fate(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
+                   const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
+                   Tensor rng_states, std::optional<Tensor> matrix_EB, std::optional<Tensor> stats,
+                   std::optional<Tensor> per_ray_bounces, int64_t n_rays, int64_t gid_offset, int64_t stream,
+                   int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
+                   int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
+                   double grid_sqrt_k, int64_t plan, std::optional<Tensor> table, Tensor fate) {
+    return trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats, per_ray_bounces,
+                      n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
+                      gid_block_rays, debug, grid_sqrt_k, plan, table, nullptr, fate);
 }
 
 // chain_begin: trace_windows' arguments -> the chain's handle (a user-space address: positive), or the negated
@@ -260,6 +289,13 @@ TORCH_LIBRARY(wgrt, m) {
           "int workgroups, Tensor? chunk_order, int num_iter, Tensor? gid_blocks, int gid_block_rays, int debug, "
           "float grid_sqrt_k, int plan, Tensor(e!)? table) -> int",
           &chain_begin);
+    // the same launch storing every ray's fate code (wgrt_trace_fate): fate uint8 [rays]
+    m.def("trace_fate(int scene, Tensor x, Tensor y, Tensor m, Tensor n, Tensor? lmd_num, Tensor te, Tensor tm, "
+          "Tensor delta_phase, Tensor(a!) rng_states, Tensor(b!)? matrix_EB, Tensor(c!)? stats, "
+          "Tensor(d!)? per_ray_bounces, int n_rays, int gid_offset, int stream, int kernel, int variant, "
+          "int workgroups, Tensor? chunk_order, int num_iter, Tensor? gid_blocks, int gid_block_rays, int debug, "
+          "float grid_sqrt_k, int plan, Tensor(e!)? table, Tensor(f!) fate) -> int",
+          &trace_fate);
     m.def("chain_step(int chain) -> int", &chain_step);
     m.def("chain_end(int chain) -> int", &chain_end);
 }

@@ -51,6 +51,14 @@ __global__ __launch_bounds__(256) void trace_grid_kernel(TraceArgs A) {
     add_stats(A.stats, c);
 }
 
+// The same storing every ray's fate code (wgrt_trace_fate with variant 1; wgrt_fate.h).
+__global__ __launch_bounds__(256) void trace_grid_fate_kernel(TraceArgs A) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    Counters c;
+    if (i < A.n_rays) trace_one<true>(A, i, c);
+    add_stats(A.stats, c);
+}
+
 // A counter set of the Jones-vector variants' launch scratch, each slot on its own 128-B line: the kHeads
 // work-queue heads, then the replay count, the out-coupling queue and full-block counts, and a single
 // launch's epilogue totals (a Counters record) and done count.
@@ -236,12 +244,13 @@ __device__ __forceinline__ void record_abandoned(const KArgs &K, uint32_t i) {
 // reference-arithmetic lane (trace_one) over the replay list, its TraceArgs read from the kernarg segment
 // here, so nothing of it is live across the wave loop.  Inlined: as a real call it gave the wave loop 128
 // VGPRs and scratch (above).
+template <bool FATE>
 __device__ __forceinline__ void replay_tail(const KArgs &K, unsigned long long nr) {
     const TraceArgs R = K.args();
     const uint32_t *const list = KA(replay_list);
     Counters c;
     for (unsigned long long k = threadIdx.x; k < nr; k += blockDim.x)
-        trace_one(R, (int64_t)__hip_atomic_load(list + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), c);
+        trace_one<FATE>(R, (int64_t)__hip_atomic_load(list + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), c);
     c.wave_reduce();
     if (threadIdx.x == 0) c.w[kCtrReplayed] = nr;
     if ((threadIdx.x & 63) == 0 && R.stats) c.add_to(R.stats);
@@ -280,7 +289,7 @@ __device__ __forceinline__ void finish_fused(const KArgs &K, Counters c) {
 // each per workgroup: not contended), waits for them, and counts the workgroup done; the workgroup that
 // counts last reads the totals at agent scope, adds them to *stats, zeroes the next launch's counter set
 // (every other workgroup has left this one's) and replays.
-template <bool CHAIN>
+template <bool CHAIN, bool FATE>
 __device__ __forceinline__ void finish_single(const KArgs &K, Counters c) {
     __shared__ unsigned long long red[4][kCtrWords];
     __shared__ int last_wg;
@@ -310,7 +319,7 @@ __device__ __forceinline__ void finish_single(const KArgs &K, Counters c) {
     const unsigned long long nr = __hip_atomic_load(KA(replay_count), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (__builtin_expect(nr != 0ull, 0)) {
         if (CHAIN) replay_tail_chain(K, nr);
-        else replay_tail(K, nr);
+        else replay_tail<FATE>(K, nr);
     }
 #endif
 }
@@ -343,7 +352,12 @@ static_assert(sizeof(TraceArgs) % 8 == 0 && sizeof(Locator) % 8 == 0 && sizeof(L
 // {state, serial A.iter_epoch} there instead of writing rng_states.  The previous step runs in another kernel, on
 // another hardware queue, at the same time.  Its operands are read from the kernarg segment where they are used.
 // Off in the product instantiations, which contain none of it.
-template <bool FUSED, bool SINGLE, bool TL, bool AMP, bool LEARN, bool CHAIN, class Loc>
+// FATE: a single launch that stores every ray's fate code (wgrt_trace_fate; wgrt_fate.h): the lane carries the
+// code from the place its trace ends (advance's select; interact's kDie / kDieIc / kOut, an out-coupling's reason
+// from eyebox_inside, the bin step's own predicate, on the ~2 % of rays that out-couple) to the retire site, which
+// stores the byte with rng[L.i]; a bad ray stores 0; an abandoned ray stores nothing (its replay on the exact lane
+// does).  Off everywhere else: no register, no store.
+template <bool FUSED, bool SINGLE, bool TL, bool AMP, bool LEARN, bool CHAIN, bool FATE, class Loc>
 __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, const Loc &loc, unsigned long long *heads,
                                           int chunk) {
     // Single launches (!FUSED) do their epilogue in this kernel (above), and retire a finished trace at one
@@ -384,6 +398,9 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
     unsigned long long qbase = 0;      // this wave's block of out-coupling slots ...
     int qfill = kQBlock;               // ... and how many of them are used (none reserved yet)
     bool qblk = false;                 // a block has been reserved
+    uint32_t fate = 0;                 // FATE: the fate code of the trace that ended on this lane, until its retire
+    static_assert(!FATE || (!FUSED && !CHAIN && !LEARN && !TL && WGRT_INKERNEL_REPLAY),
+                  "fates are stored by plain single launches whose replay runs in the kernel (replay_tail<FATE>)");
 
     // head x's items: stripes of kStripe consecutive chunks, stripe s on head s % 8, iteration-
     // major.  Every die gets a mix of all FoVs and wavelengths -- ray lifetimes differ by tile,
@@ -431,6 +448,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
         active = false;
         if (__builtin_expect(!ok, 0)) {
             ++tot_bad;
+            if (FATE) KA(fate)[L.i] = 0;   // no trace
             return;
         }
         if (FUSED && L.k > 0) {
@@ -506,6 +524,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             KA(rng)[L.i] = L.r.s;
             uint32_t *const pr = KA(per_ray);
             if (!FUSED && pr) pr[L.i] = L.bounces;
+            if (FATE) KA(fate)[L.i] = (uint8_t)fate;
         }
         if (LEARN && L.bounces > kLongBounces)   // result unused: no return, no wait
             atomicAdd(K.template get<uint32_t *>(kLearnTailOff<Loc>) + L.tix, 1u);
@@ -589,8 +608,14 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
         bool out = false;
         if (active && blk >= 0) {
             L.inter += entry ? 0u : 1u;
-            const int next = interact<SINGLE, AMP>(A, K, loc, L, blk, kind, entry, sg);
+            const int next = interact<SINGLE, AMP, FATE>(A, K, loc, L, blk, kind, entry, sg);
             out = next == kOut;
+            if (FATE && next < 0 && next != kUncertain) {
+                int reason = next == kDieIc ? kFateLeftIc : kFateLost;
+                if (out)
+                    reason = eyebox_inside(KA(tiles) + (int64_t)L.tix * KA(tile_d), L.r.x, L.r.y) ? kFateEyebox : kFateBeside;
+                fate = fate_code(entry ? kFateEntry : L.r.region, reason);
+            }
             outcome(next);
         }
         SEG_TMARK(sg, 5, L.r.er);
@@ -601,7 +626,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
     for (;;) {
         __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
         if (active) {
-            blk = advance(A, K, loc, L, kind);
+            blk = advance<FATE>(A, K, loc, L, kind, &fate);
             entry = false;
             if (!FUSED) fin |= blk == kDie;
             else if (blk == kDie) retire();
@@ -782,7 +807,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             }
 #endif
             if (!first && active) {
-                blk = advance(A, K, loc, L, kind);
+                blk = advance<FATE>(A, K, loc, L, kind, &fate);
                 entry = false;
                 fin |= blk == kDie;
             }
@@ -842,7 +867,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
     c.w[kCtrGiveups] = tot_giveup;
     c.w[kCtrInter] = tot_int;
     if (FUSED) finish_fused(K, c);
-    else finish_single<CHAIN>(K, c);
+    else finish_single<CHAIN, FATE>(K, c);
 }
 
 #if !WGRT_INKERNEL_REPLAY
@@ -875,7 +900,7 @@ constexpr int kChainMargin = 8;         // workgroups two chained grids leave fr
 template <class CellT, bool FUSED, bool SINGLE, bool AMP>
 __global__ WGRT_JONES_BOUNDS void trace_jones_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
                                                      int chunk) {
-    jones_body<FUSED, SINGLE, false, AMP, false, false>(
+    jones_body<FUSED, SINGLE, false, AMP, false, false, false>(
         A, kernel_kargs<decltype(trace_jones_kernel<CellT, FUSED, SINGLE, AMP>)>(), loc, counter, chunk);
 }
 
@@ -884,7 +909,7 @@ __global__ WGRT_JONES_BOUNDS void trace_jones_kernel(TraceArgs A, LocatorT<CellT
 template <class CellT, bool FUSED, bool SINGLE>
 __global__ WGRT_JONES_BOUNDS void trace_jones_tl_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
                                                         int chunk) {
-    jones_body<FUSED, SINGLE, true, false, false, false>(A, kernel_kargs<decltype(trace_jones_tl_kernel<CellT, FUSED, SINGLE>)>(),
+    jones_body<FUSED, SINGLE, true, false, false, false, false>(A, kernel_kargs<decltype(trace_jones_tl_kernel<CellT, FUSED, SINGLE>)>(),
                                                   loc, counter, chunk);
 }
 
@@ -893,7 +918,7 @@ __global__ WGRT_JONES_BOUNDS void trace_jones_tl_kernel(TraceArgs A, LocatorT<Ce
 template <class CellT>
 __global__ WGRT_JONES_BOUNDS void trace_jones_learn_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
                                                            int chunk, uint32_t *tail) {
-    jones_body<false, false, false, false, true, false>(A, kernel_kargs<decltype(trace_jones_learn_kernel<CellT>)>(), loc,
+    jones_body<false, false, false, false, true, false, false>(A, kernel_kargs<decltype(trace_jones_learn_kernel<CellT>)>(), loc,
                                                  counter, chunk);
 }
 
@@ -901,8 +926,18 @@ __global__ WGRT_JONES_BOUNDS void trace_jones_learn_kernel(TraceArgs A, LocatorT
 template <class CellT, bool AMP>
 __global__ WGRT_JONES_BOUNDS void trace_jones_chain_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
                                                            int chunk) {
-    jones_body<false, false, false, AMP, false, true>(A, kernel_kargs<decltype(trace_jones_chain_kernel<CellT, AMP>)>(),
+    jones_body<false, false, false, AMP, false, true, false>(A, kernel_kargs<decltype(trace_jones_chain_kernel<CellT, AMP>)>(),
                                                       loc, counter, chunk);
+}
+
+// The single-launch loop storing every ray's fate code (wgrt_trace_fate): both cell widths, full colour and
+// single wavelength, with and without the amplification step; no learning, timeline or chained twin (the launch
+// plan routes a fate launch around those: validate_launch, plan_auto_order).
+template <class CellT, bool SINGLE, bool AMP>
+__global__ WGRT_JONES_BOUNDS void trace_jones_fate_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
+                                                          int chunk) {
+    jones_body<false, SINGLE, false, AMP, false, false, true>(
+        A, kernel_kargs<decltype(trace_jones_fate_kernel<CellT, SINGLE, AMP>)>(), loc, counter, chunk);
 }
 
 // The two ends of a chain's segment, on the caller's stream: every ray's state into its granule under the
@@ -981,7 +1016,8 @@ __global__ __launch_bounds__(kOrderThreads) void order_kernel(const float *m, co
 
 // Every trace kernel instantiation, stated once: the Jones kernels by [64-bit cells][fused][single
 // wavelength][AMP], the debug timeline kernels (32-bit cells, full colour, no AMP) by [fused].  The occupancy
-// queries loop over the table and the launch indexes it, so a kernel cannot be in one and not the other.
+// queries loop over the table and the launch indexes it, so a kernel cannot be in one and not the other.  The
+// fate-storing kernels (wgrt_trace_fate) by [64-bit cells][single wavelength][AMP]: single launches only.
 const void *const kJonesKernels[2][2][2][2] = {
     {{{(const void *)trace_jones_kernel<uint32_t, false, false, false>,
        (const void *)trace_jones_kernel<uint32_t, false, false, true>},
@@ -1004,6 +1040,11 @@ const void *const kLearnKernels[2] = {(const void *)trace_jones_learn_kernel<uin
 const void *const kChainKernels[2][2] = {   // [64-bit cells][AMP]
     {(const void *)trace_jones_chain_kernel<uint32_t, false>, (const void *)trace_jones_chain_kernel<uint32_t, true>},
     {(const void *)trace_jones_chain_kernel<uint64_t, false>, (const void *)trace_jones_chain_kernel<uint64_t, true>}};
+const void *const kFateKernels[2][2][2] = {   // [64-bit cells][single wavelength][AMP]
+    {{(const void *)trace_jones_fate_kernel<uint32_t, false, false>, (const void *)trace_jones_fate_kernel<uint32_t, false, true>},
+     {(const void *)trace_jones_fate_kernel<uint32_t, true, false>, (const void *)trace_jones_fate_kernel<uint32_t, true, true>}},
+    {{(const void *)trace_jones_fate_kernel<uint64_t, false, false>, (const void *)trace_jones_fate_kernel<uint64_t, false, true>},
+     {(const void *)trace_jones_fate_kernel<uint64_t, true, false>, (const void *)trace_jones_fate_kernel<uint64_t, true, true>}}};
 const void *const kTimelineKernels[2] = {(const void *)trace_jones_tl_kernel<uint32_t, false, false>,
                                          (const void *)trace_jones_tl_kernel<uint32_t, true, false>};
 
@@ -1030,6 +1071,14 @@ wgrt_status query_trace_grids(wgrt_scene *s) {
                 HIP_TRY(grid_of(kJonesKernels[c][f][g][1], amp));
                 s->jones_grid[c][f][g] = std::min(plain, amp);
             }
+    // the fate instantiations: never more workgroups than the plain launch of the same kind gets
+    for (int c = 0; c < 2; ++c)
+        for (int g = 0; g < 2; ++g) {
+            int plain = 0, amp = 0;
+            HIP_TRY(grid_of(kFateKernels[c][g][0], plain));
+            HIP_TRY(grid_of(kFateKernels[c][g][1], amp));
+            s->jones_fate_grid[c][g] = std::min(s->jones_grid[c][0][g], std::min(plain, amp));
+        }
     for (int f = 0; f < 2; ++f) HIP_TRY(grid_of(kTimelineKernels[f], s->jones_tl_grid[f]));
     for (int c = 0; c < 2; ++c) HIP_TRY(grid_of(kLearnKernels[c], s->jones_learn_grid[c]));
     // A chained step's waves spin on rays that only the previous step's launch can finish, so that launch must
@@ -1193,6 +1242,10 @@ struct LaunchCfg {
     // a chained step (wgrt_chain_step): the chain's granules and the tag serial this step publishes (0: not chained)
     uint64_t *chain_gran = nullptr;
     uint32_t chain_serial = 0;
+    // wgrt_trace_fate: the per-ray fate codes (NULL: none).  A fate launch is a single launch (validate_launch),
+    // never learns the tile table (plan_auto_order: no learning instantiation stores fates; the scene learns from
+    // its next plain launch instead) and takes no debug timeline (validate_launch refuses it).
+    uint8_t *fate = nullptr;
 };
 
 // wgrt_debug_set_auto_order: the automatic issue order (and its learning launches) on / off, process-wide.
@@ -1230,7 +1283,7 @@ void plan_auto_order(wgrt_scene *ms, int64_t n_rays, int item, LaunchCfg &c) {
     if (learning)
         while (c.order_gen & (c.order_gen - 1)) c.order_gen &= c.order_gen - 1;
     c.auto_order = ms->learn_gen > 0 && item == kChunk;
-    if (!c.timeline && learning) {
+    if (!c.timeline && learning && !c.fate) {   // (a fate launch does not learn: LaunchCfg::fate)
         c.learn = true;
         ms->learned_rays += n_rays;
         ++ms->learn_gen;
@@ -1280,6 +1333,9 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
     if (c.num_iter > 255) return fail(WGRT_ERR_INVALID_ARGUMENT, "num_iter must be <= 255");
     if (c.num_iter > 1 && (per_ray_bounces || c.chunk_order))
         return fail(WGRT_ERR_INVALID_ARGUMENT, "num_iter > 1 takes no per_ray_bounces / chunk_order");
+    if (c.num_iter > 1 && c.fate)
+        return fail(WGRT_ERR_INVALID_ARGUMENT, "num_iter > 1 takes no fate: a fused launch's retire sites publish hand-off "
+                                               "granules, not per-trace results (trace the iterations one call each)");
     if (c.chunk_order && c.variant == 1)
         return fail(WGRT_ERR_INVALID_ARGUMENT, "chunk_order needs variant 0, 7 or 9");
     if (c.gid_blocks && (c.gid_block_rays < 1 || gid_offset != 0))
@@ -1301,6 +1357,8 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
     if (c.timeline && s->nonunitary_blocks)
         return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline is built without the amplification step: scaled-unitary "
                                           "LUTs only");
+    if (c.timeline && c.fate)
+        return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel stores no fates: trace with fate or with the timeline");
     // (a chained variant-1 call, num_iter > 1, has no chunk_order: rejected above)
     if (c.chunk_order && c.n_chunk_order != (n_rays + kChunk - 1) / kChunk)
         return fail(WGRT_ERR_INVALID_ARGUMENT, "chunk_order must list ceil(n_rays / 64) chunks");
@@ -1321,6 +1379,7 @@ TraceArgs fill_args(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, 
     A.win = c.win;
     A.stats = stats;
     A.per_ray = per_ray_bounces;
+    A.fate = c.fate;
     A.n_rays = n_rays;
     A.gid_offset = gid_offset;
     A.gid_blocks = c.gid_blocks;
@@ -1340,6 +1399,7 @@ int64_t launch_grid(const wgrt_scene *s, int64_t n_rays, int64_t item, const Lau
     int64_t grid = c.workgroups > 0 ? c.workgroups
                    : c.chain_serial ? s->jones_chain_grid[c.variant == 9]
                    : c.timeline     ? s->jones_tl_grid[c.num_iter > 1]
+                   : c.fate         ? s->jones_fate_grid[c.variant == 9][c.single]
                    : c.learn        ? s->jones_learn_grid[c.variant == 9]
                                     : s->jones_grid[c.variant == 9][c.num_iter > 1][c.single];
     // a workgroup's 4 waves need 4 work items to all have work (debug chunk_rays: smaller items)
@@ -1372,7 +1432,8 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
     if (c.variant == 1) {
         const int64_t blocks = (A.n_rays + 255) / 256;
         if (blocks > 0x7fffffff) return fail(WGRT_ERR_INVALID_ARGUMENT, "too many rays for one launch");
-        hipLaunchKernelGGL(trace_grid_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
+        if (c.fate) hipLaunchKernelGGL(trace_grid_fate_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
+        else hipLaunchKernelGGL(trace_grid_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
         HIP_TRY(hipGetLastError());
         return WGRT_OK;
     }
@@ -1422,6 +1483,7 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
     if (c.variant != 9) l32 = make_locator32(s);
     const void *const kernel = c.chain_serial ? kChainKernels[c.variant == 9][s->nonunitary_blocks != 0]
                                : c.timeline ? kTimelineKernels[num_iter > 1]
+                               : c.fate   ? kFateKernels[c.variant == 9][c.single][s->nonunitary_blocks != 0]
                                : c.learn  ? kLearnKernels[c.variant == 9]
                                           : kJonesKernels[c.variant == 9][num_iter > 1][c.single][s->nonunitary_blocks != 0];
     uint32_t *tail = ms->d_tile_tail;   // the learning kernels' last parameter (the others take four)
@@ -1722,6 +1784,17 @@ wgrt_status wgrt_trace_windows(const wgrt_scene *s, const wgrt_rays *rays, int64
     LaunchCfg c;
     const wgrt_status e = cfg_of_opts(s, opts, plan, table, c);
     if (e != WGRT_OK) return e;
+    return trace_launch(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, c);
+}
+
+wgrt_status wgrt_trace_fate(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
+                            uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats, uint32_t *per_ray_bounces,
+                            void *stream, const wgrt_launch_opts *opts, const wgrt_window_plan *plan, double *table,
+                            uint8_t *fate) {
+    LaunchCfg c;
+    const wgrt_status e = cfg_of_opts(s, opts, plan, table, c);
+    if (e != WGRT_OK) return e;
+    c.fate = fate;
     return trace_launch(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, c);
 }
 

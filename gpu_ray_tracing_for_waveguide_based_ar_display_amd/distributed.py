@@ -484,7 +484,7 @@ def timed_run(trace_fn, rays, rng, eb, gid: GidMap, steps: int, per_call: int, s
     return float(t.item()), int(b.item()), local
 
 
-def hip_tracer(scene, variant: int = 0, stats=None, windows=None):
+def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None):
     """trace_fn for ``run_steps`` / ``trace_job`` using the HIP kernel (torch device tensors); ``stats``
     (int64[STATS_LEN] device tensor) is added to by every call.  A shard of several block ranges passes its global
     ids as ``gid_blocks``, uploaded once per map and device and kept on the map (``GidMap.device_blocks``).
@@ -495,7 +495,11 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None):
     of such a job is ``reduce_eyebox(table)``, one sum-reduce: no slab list, no scatter.
 
     ``fn.chain(rays, rng, eb, gid)`` returns an ``engine.TraceChain`` over the same arguments: a context whose
-    ``step()`` is one such call with ``num_iter = 1``."""
+    ``step()`` is one such call with ``num_iter = 1``.
+
+    ``fate``: a uint8 device tensor every call stores the rays' fate codes in (``engine.trace_fullcolor(fate=...)``:
+    single launches only, so ``num_iter`` must stay 1); such a tracer offers no ``chain`` (a chain takes no fates),
+    so ``run_steps`` issues its launches plain, and a ``hook`` can census the buffer after each."""
     from .engine import TraceChain, trace_fullcolor
 
     def ids_of(rng, gid: GidMap):
@@ -505,12 +509,13 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None):
 
     def fn(rays, rng, eb, gid: GidMap, num_iter=1):
         trace_fullcolor(scene, rays, rng, eb, stats=stats, variant=variant, num_iter=num_iter, windows=windows,
-                        **ids_of(rng, gid))
+                        fate=fate, **ids_of(rng, gid))
 
     def chain(rays, rng, eb, gid: GidMap):
         """The same launches as a chain (``run_steps`` uses it for separate launches without a hook)."""
         return TraceChain(scene, rays, rng, eb, stats=stats, variant=variant, windows=windows, **ids_of(rng, gid))
-    fn.chain = chain
+    if fate is None:
+        fn.chain = chain
     return fn
 
 

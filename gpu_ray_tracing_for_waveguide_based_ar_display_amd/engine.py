@@ -53,7 +53,7 @@ def trace_fullcolor(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_E
                     per_ray_bounces: torch.Tensor | None = None, stream=None, variant: int = VARIANT_AUTO,
                     workgroups: int = 0, chunk_order: torch.Tensor | None = None, num_iter: int = 1,
                     gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
-                    grid_sqrt_k: float = 0.0, windows=None) -> None:
+                    grid_sqrt_k: float = 0.0, windows=None, fate: torch.Tensor | None = None) -> None:
     """Asynchronous launch on ``stream`` (default: torch's current stream).
 
     rays: dict of device float32 tensors keyed like the reference columns
@@ -73,13 +73,16 @@ def trace_fullcolor(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_E
     (``wgrt_launch_opts.grid_sqrt_k``; 0 the default, < 0 the resident grid).  windows: ``(plan, table)``, a
     ``WindowPlan`` and a float64 ``[n_slabs, plan.W]`` device tensor (``plan.new_table(scene)``) that every
     out-coupling is also counted into (``wgrt_trace_windows``: the table equals ``eyebox_window_sums`` of the grid
-    the same trace leaves); ``matrix_EB`` may then be None, and no grid is written.
+    the same trace leaves); ``matrix_EB`` may then be None, and no grid is written.  fate: a uint8 device tensor
+    of one byte per ray of the batch that takes every traced ray's fate code (``wgrt_trace_fate``; ``FATE_CODES``,
+    0 for a ray that was skipped); single launches only (``num_iter > 1`` raises), and nothing else the launch
+    leaves changes.
     """
     if scene.single_lambda:
         raise ValueError("trace_fullcolor needs a full-colour scene; use trace_single for a single-wavelength one")
     _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single=False, chunk_order=chunk_order, num_iter=num_iter, gid_blocks=gid_blocks,
-           gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows)
+           gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows, fate=fate)
 
 
 def new_stats(device) -> torch.Tensor:
@@ -122,17 +125,17 @@ def trace_single(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_EB: 
                  per_ray_bounces: torch.Tensor | None = None, stream=None, variant: int = VARIANT_AUTO,
                  workgroups: int = 0, chunk_order: torch.Tensor | None = None, num_iter: int = 1,
                  gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
-                 grid_sqrt_k: float = 0.0, windows=None) -> None:
+                 grid_sqrt_k: float = 0.0, windows=None, fate: torch.Tensor | None = None) -> None:
     """One launch of the single-wavelength kernel (``process_rays_kernel_pro``, GRTF:419-831)
     through ``wgrt_trace_single_ex``: no ``lmd_num`` column (ignored if present),
     matrix_EB [NY, NX, 80, 120], branch guard ener * efficiency > 1e-15.  The scene must be
-    a single-wavelength one (``Scene.from_geometry(..., wavelength=l)`` or 3-D LUTs).  ``windows``: as
+    a single-wavelength one (``Scene.from_geometry(..., wavelength=l)`` or 3-D LUTs).  ``windows``, ``fate``: as
     ``trace_fullcolor``."""
     if not scene.single_lambda:
         raise ValueError("trace_single needs a single-wavelength scene (Scene.from_geometry(..., wavelength=l))")
     _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single=True, chunk_order=chunk_order, num_iter=num_iter, gid_blocks=gid_blocks,
-           gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows)
+           gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows, fate=fate)
 
 
 class WindowPlan:
@@ -219,7 +222,7 @@ def _read_columns(rays, rng_states, n_rays, single, device):
 
 def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single, chunk_order=None, num_iter=1, gid_blocks=None, gid_block_rays=0, debug=None,
-           grid_sqrt_k=0.0, windows=None, chain=False):
+           grid_sqrt_k=0.0, windows=None, chain=False, fate=None):
     device = torch.device("cuda", scene.device)
     cols, N = _read_columns(rays, rng_states, n_rays, single, device)
     x = cols["x"]
@@ -241,6 +244,10 @@ def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ra
         if per_ray_bounces.dtype not in (torch.int32, torch.uint32):
             raise TypeError("per_ray_bounces must be uint32 / int32")
         _as_dev(per_ray_bounces, per_ray_bounces.dtype, "per_ray_bounces", device, x.numel())
+    if fate is not None:
+        _as_dev(fate, torch.uint8, "fate", device, x.numel())
+        if int(num_iter) > 1:
+            raise ValueError("fate needs num_iter == 1: a fused launch stores no per-trace fates")
     n_chunks = (N + CHUNK - 1) // CHUNK
     if chunk_order is not None:
         _as_dev(chunk_order, torch.int32, "chunk_order", device, n_chunks)
@@ -266,7 +273,10 @@ def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ra
         if h <= 0:   # the negated wgrt_status of the failure
             check(-h, "wgrt_chain_begin")
         return h, (args, dbg, windows)
-    if windows is None:
+    if fate is not None:   # torch.ops.wgrt.trace_fate -> wgrt_trace_fate (plan 0, no table: the grid alone)
+        status = ops().trace_fate(*args, plan.handle.value if windows is not None else 0,
+                                  table if windows is not None else None, fate)
+    elif windows is None:
         status = ops().trace(*args)
     else:
         status = ops().trace_windows(*args, plan.handle.value, table)
@@ -332,6 +342,116 @@ class TraceChain:
             self.end()
         except Exception:
             pass
+
+
+# ---- where every ray ends: fate codes, their census and the loss budget (csrc/wgrt_fate.h states the code) ----
+# The classes of ``loss_budget``: every fate code belongs to exactly one (reason, regions; the entry is region 9).
+FATE_CLASSES = (("in_coupling_loss", 2, (9,)), ("left_in_coupler", 6, (9, 0, 1)), ("left_plate", 1, (0, 1, 2, 3, 4, 5)),
+                ("lost_ic", 2, (0, 1)), ("lost_fc", 2, (2, 3)), ("lost_oc", 2, (4, 5)), ("eyebox", 3, (4, 5)),
+                ("beside_eyebox", 4, (4, 5)), ("oc_miss", 5, (5,)), ("bounce_cap", 7, (0, 1, 2, 3, 4, 5)))
+
+
+def fate_col(code: int) -> int:
+    """Column of fate code ``code`` in a census row (``wgrt_fate_col``); raises for a code no trace can end with."""
+    c = int(load().wgrt_fate_col(int(code)))
+    if c < 0:
+        raise ValueError(f"{code} is not a fate code")
+    return c
+
+
+def _fate_constant(name: str):
+    L = load()
+    if name == "FATE_COLS":
+        return int(L.wgrt_fate_cols())
+    if name == "FATE_REASONS":
+        return {r: L.wgrt_fate_reason_name(r).decode() for r in range(1, 8)}
+    return tuple(c for c in range(256) if L.wgrt_fate_col(c) >= 0)   # FATE_CODES
+
+
+def __getattr__(name: str):
+    # FATE_COLS, FATE_REASONS ({reason: name}) and FATE_CODES (the codes a trace can end with) come from the
+    # library, so they are read when first used (importing this module needs no built library)
+    if name in ("FATE_COLS", "FATE_REASONS", "FATE_CODES"):
+        v = _fate_constant(name)
+        globals()[name] = v
+        return v
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def fate_census(scene: Scene, rays: dict, fate: torch.Tensor, table: torch.Tensor | None = None,
+                stream=None) -> torch.Tensor:
+    """Count the fate codes a trace left (``trace_*(fate=...)``) per tile (``wgrt_fate_census``): ray i with code c
+    adds 1 to ``table[(l * ny + n) * nx + m, fate_col(c)]``, an int64 ``[n_slabs, FATE_COLS]`` device tensor in
+    ``matrix_EB``'s slab order that is accumulated into when given (a zeroed one is made otherwise) and returned.
+    ``rays``: the batch's ``m``, ``n`` (and, full colour, ``lmd_num``) columns.  Asynchronous on ``stream``."""
+    device = torch.device("cuda", scene.device)
+    fate = _as_dev(fate, torch.uint8, "fate", device)
+    n = fate.numel()
+    cols = {k: _as_dev(rays[k], torch.float32, k, device) for k in ("m", "n") + (() if scene.single_lambda else ("lmd_num",))}
+    for k, v in cols.items():
+        if v.numel() < n:
+            raise ValueError(f"ray column {k!r} has {v.numel()} rays, fate has {n}")
+    L = load()
+    shape = (scene.num_lmd * scene.ny * scene.nx, int(L.wgrt_fate_cols()))
+    if table is None:
+        table = torch.zeros(shape, dtype=torch.int64, device=device)
+    else:
+        _as_dev(table, torch.int64, "table", device)
+        if tuple(table.shape) != shape:
+            raise ValueError(f"table shape {tuple(table.shape)} != {shape}")
+    lmd = cols.get("lmd_num")
+    check(L.wgrt_fate_census(ctypes.c_void_p(fate.data_ptr()), ctypes.c_void_p(cols["m"].data_ptr()),
+                             ctypes.c_void_p(cols["n"].data_ptr()),
+                             ctypes.c_void_p(lmd.data_ptr()) if lmd is not None else None, n, scene.nx, scene.ny,
+                             scene.num_lmd, ctypes.c_void_p(table.data_ptr()),
+                             ctypes.c_void_p(_stream_handle(device, stream))), "wgrt_fate_census")
+    return table
+
+
+def fate_census_host(fate, m, n, lmd_num, nx: int, ny: int, num_lmd: int, table=None) -> np.ndarray:
+    """The census on the host (``wgrt_fate_census_host``; numpy arrays, no GPU needed): the same validity rule,
+    tile index and column function as the device's.  ``lmd_num=None``: wavelength 0.  Adds into ``table`` (int64
+    ``[num_lmd * ny * nx, FATE_COLS]``, C-contiguous) when given."""
+    L = load()
+    fate = np.ascontiguousarray(fate, dtype=np.uint8)
+    cols = [np.ascontiguousarray(c, dtype=np.float32) if c is not None else None for c in (m, n, lmd_num)]
+    if any(c is not None and c.shape[0] < fate.shape[0] for c in cols):
+        raise ValueError("a tile index column is shorter than fate")
+    if table is None:
+        table = np.zeros((num_lmd * ny * nx, int(L.wgrt_fate_cols())), dtype=np.int64)
+    elif table.dtype != np.int64 or not table.flags.c_contiguous:
+        raise ValueError("table must be a C-contiguous int64 array")
+    check(L.wgrt_fate_census_host(fate.ctypes.data, cols[0].ctypes.data, cols[1].ctypes.data,
+                                  cols[2].ctypes.data if cols[2] is not None else None, fate.shape[0], int(nx), int(ny),
+                                  int(num_lmd), table.ctypes.data), "wgrt_fate_census_host")
+    return table
+
+
+def loss_budget(census, scene) -> dict:
+    """The loss budget of a fate census (``fate_census``; a device tensor or a numpy array ``[n_slabs, FATE_COLS]``;
+    ``scene``: anything with ``num_lmd``, ``nx``, ``ny``): where the traced rays ended, per wavelength and in total,
+    in the classes of ``FATE_CLASSES`` -- ``in_coupling_loss`` (code 92: lost at the in-coupler's first diffraction),
+    ``left_in_coupler`` (96, 06, 16: the second order walked out of the in-coupler), ``left_plate`` (reason 1),
+    ``lost_ic`` / ``lost_fc`` / ``lost_oc`` (reason 2 in the in-coupler, fold-grating and out-coupler states),
+    ``eyebox`` (reason 3), ``beside_eyebox`` (reason 4), ``oc_miss`` (55) and ``bounce_cap`` (reason 7).  Returns
+    ``{"per_wavelength": [{"rays", "counts", "fractions"}, ...], "total": {...}, "eyebox": int64 [num_lmd, ny, nx]}``:
+    ``counts`` are the integer class counts (they sum to ``rays``, the rays counted), ``fractions`` their shares of
+    ``rays`` (summing to 1 up to the rounding of ten float64 quotients; all 0 when no ray was counted), and ``eyebox``
+    the reason-3 count of every tile: the rays of that FoV and wavelength that reached its eyebox."""
+    c = census.cpu().numpy() if isinstance(census, torch.Tensor) else np.asarray(census)
+    nl, ny, nx = int(scene.num_lmd), int(scene.ny), int(scene.nx)
+    c = c.reshape(nl, ny, nx, -1).astype(np.int64)
+    cols = {name: [fate_col(10 * region + reason) for region in regions] for name, reason, regions in FATE_CLASSES}
+
+    def entry(rows):   # rows: [..., FATE_COLS] -> one budget record
+        tot = rows.reshape(-1, rows.shape[-1]).sum(axis=0)
+        counts = {name: int(tot[k].sum()) for name, k in cols.items()}
+        rays = int(tot.sum())
+        assert rays == sum(counts.values()), "a census column outside every class"
+        return {"rays": rays, "counts": counts,
+                "fractions": {name: (v / rays if rays else 0.0) for name, v in counts.items()}}
+    return {"per_wavelength": [entry(c[l]) for l in range(nl)], "total": entry(c),
+            "eyebox": c[..., cols["eyebox"]].sum(axis=-1)}
 
 
 def timeline_summary(buf, percentiles: bool = True) -> dict:
@@ -501,6 +621,6 @@ def selftest_math(a: torch.Tensor, b: torch.Tensor, stream=None) -> torch.Tensor
     return out
 
 
-__all__ = ["Scene", "WindowPlan", "TraceChain", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
+__all__ = ["Scene", "WindowPlan", "TraceChain", "fate_census", "fate_census_host", "fate_col", "loss_budget", "FATE_CLASSES", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
            "trace_fullcolor", "trace_single", "init_rays", "schedule_by_lifetime",
            "rays_to_device", "classify_points", "shadow", "selftest_math", "RAY_COLUMNS", "_lib"]

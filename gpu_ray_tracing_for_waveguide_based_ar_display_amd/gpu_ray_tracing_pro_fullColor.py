@@ -19,6 +19,8 @@ Same flow as the reference script, on the MI355X kernel:
    (``--evaluate device``) the table stays there too and the colour math runs in ``wgrt_eyebox_evaluate``; or
    (``eyebox="windows"``, ``--eyebox windows``) from the same table counted by the trace itself
    (``wgrt_trace_windows``), with no grid allocated at all;
+   with ``budget=True`` (``--budget``) every launch also stores each ray's fate code, a census counts them per
+   tile, and the loss budget -- where the rays that did not reach the eyebox went -- is printed per wavelength;
 6. the "Eyebox Center View.png" export (MAIN:199-203): the evaluated image at the first eye row,
    last eye column, as 8-bit RGB, rows flipped (``eyebox_center_view``, written without OpenCV).
 
@@ -51,7 +53,7 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
         point_seed: int | None = None, evaluate: bool = True, verbose: bool = True, variant: int = 0,
         fuse: bool | None = None, points: np.ndarray | None = None, png: str | None = None,
         eyebox: str = "host", keep_grid: bool = False, evaluate_on: str = "host",
-        keep_image: bool = False) -> dict:
+        keep_image: bool = False, budget: bool = False) -> dict:
     """The reference script's job on this engine; returns its printed quantities and arrays.
     ``points``: the R/2 in-coupler origins to use (default: sampled, GRTF:12-23, seeded by
     ``point_seed``); ``png``: where to write the "Eyebox Center View" image (needs ``evaluate``).
@@ -76,7 +78,15 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
     numpy.  ``"device"`` (needs ``eyebox="device"`` or ``"windows"``): the window-sum table (rank 0's, after the
     reduce, on several GPUs) is evaluated where it lives (``evaluation_from_window_sums``); only the three figures and
     the centre image come back, ``center_view`` and the PNG are built from that image, and ``output_image``
-    (every eye position's image) is returned only with ``keep_image=True``."""
+    (every eye position's image) is returned only with ``keep_image=True``.
+
+    ``budget``: also report where every ray ended.  The ``num_iter`` traces then go as plain single launches
+    (neither fused nor chained: only a single launch stores fates), each storing the rays' fate codes in one
+    reused buffer of a byte per ray (``engine.trace_fullcolor(fate=...)``) and followed by ``engine.fate_census``
+    into one ``[n_slabs, 56]`` table; several GPUs census their shards and sum-reduce the tables to rank 0.  Returned
+    as ``fate_census`` (the int64 table) and ``loss_budget`` (``engine.loss_budget``) and printed per wavelength
+    after the efficiencies.  Works with every ``eyebox`` mode; everything else returned is bit-identical to
+    ``budget=False`` (separate launches give the fused call's results)."""
     if eyebox not in ("host", "device", "windows"):
         raise ValueError(f"eyebox must be 'host', 'device' or 'windows', got {eyebox!r}")
     if evaluate_on not in ("host", "device"):
@@ -88,15 +98,18 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
         raise ValueError("eyebox='windows' traces without a grid: there is none to keep (keep_grid=True)")
     from .engine import STAT
     with _set_up(num_FOV_x, num_FOV_y, int(num_rays_per_FoV), num_iter, lambdas, lut_dir, lut_seed, lut_profile,
-                 point_seed, points, verbose, eyebox == "windows") as job:   # closes the scene on every way out
+                 point_seed, points, verbose, eyebox == "windows", budget) as job:   # closes the scene on every way out
         kern_s = _trace(job, variant, fuse)
         t_post = time.perf_counter()   # everything below is post-processing of the traced grid
         grid, table, stats = _collect(job, eyebox != "host", keep_grid)
         out = dict(num_rays=job.num_rays, num_iter=num_iter, gpu_seconds=kern_s, bounces=int(stats[STAT.bounces]),
                    eyebox_hits=int(stats[STAT.eyebox_hits]), rng_states=job.rng.cpu().numpy().view(np.uint32))
+        census = _census(job)
         if job.rank != 0:
             return out
         _report(job, out, grid, table)
+        if census is not None:
+            _report_budget(job, out, census)
         if evaluate:
             _evaluate(job, out, grid, table, evaluate_on, keep_image, png)
         out["post_seconds"] = time.perf_counter() - t_post
@@ -107,16 +120,19 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
 
 @contextlib.contextmanager
 def _set_up(nx, ny, R, num_iter, lambdas, lut_dir, lut_seed, lut_profile, point_seed, points, verbose,
-            windows: bool = False):
+            windows: bool = False, budget: bool = False):
     """Steps 1-3: geometry, LUTs, the scene, the origins (rank 0's on every rank), every rank's shard and this
     rank's rays, as the record the later stages read; the scene is closed when the ``with`` block ends.
-    ``windows``: a zeroed window table (``job.windows = (plan, table)``) instead of the grid (``job.eb`` None)."""
+    ``windows``: a zeroed window table (``job.windows = (plan, table)``) instead of the grid (``job.eb`` None).
+    ``budget``: a fate buffer of a byte per ray of the shard and a zeroed census table (``job.fate``, ``job.census``)."""
     import torch
     import torch.distributed as dist
 
     from .couplers_coor import design_geometry
     from .distributed import hip_shard_builder, make_shard
     from .engine import Scene, WindowPlan, new_stats
+    if budget:
+        from .engine import FATE_COLS
     from .luts import load_luts, lut_f32_mask, synthetic_luts, validate_luts
     from .rays import generate_points_in_polygon
 
@@ -149,12 +165,14 @@ def _set_up(nx, ny, R, num_iter, lambdas, lut_dir, lut_seed, lut_profile, point_
         eb = None if windows else torch.zeros(scene.eb_shape(), dtype=torch.float32, device=dev)
         plan = WindowPlan(device=dev.index) if windows else None
         num_rays = nx * ny * len(lambdas) * R
+        fate = torch.zeros(rng.numel(), dtype=torch.uint8, device=dev) if budget else None
+        census = (torch.zeros((scene.num_lmd * ny * nx, FATE_COLS), dtype=torch.int64, device=dev) if budget else None)
         say(f"Initialization complete: {num_rays:,} rays, {world} GPU(s)\n" + "=" * 60 + "\nSTART GPU RAY TRACING\n" + "=" * 60)
         try:
             yield SimpleNamespace(nx=nx, ny=ny, R=R, num_iter=num_iter, lambdas=lambdas, world=world, rank=rank,
                                   dev=dev, say=say, scene=scene, shards=shards, shard=shards[rank], rays=rays, rng=rng,
                                   eb=eb, windows=(plan, plan.new_table(scene)) if windows else None,
-                                  stats=new_stats(dev), num_rays=num_rays)
+                                  stats=new_stats(dev), num_rays=num_rays, fate=fate, census=census)
         finally:
             if plan is not None:
                 plan.close()
@@ -162,21 +180,26 @@ def _set_up(nx, ny, R, num_iter, lambdas, lut_dir, lut_seed, lut_profile, point_
 
 def _trace(job, variant, fuse) -> float:
     """Step 4, the num_iter chained launches of MAIN:169-177; fuse: as one call (wgrt_launch_opts.num_iter, one
-    persistent launch for the Jones-vector variants), with identical results.  Returns their seconds by HIP events."""
+    persistent launch for the Jones-vector variants), with identical results.  With the job's fate buffer
+    (``budget``): plain single launches, each followed by its census.  Returns their seconds by HIP events."""
     import torch
 
     from .distributed import hip_tracer, run_steps, split_calls
-    from .engine import check_stats, reserve
+    from .engine import check_stats, fate_census, reserve
     n_rays = job.shard.n_rays
     per_call = 0 if (n_rays <= FUSE_MAX_RAYS if fuse is None else fuse) else 1
+    hook = None
+    if job.fate is not None:   # the budget: a launch's fates are counted before the next launch overwrites them
+        per_call = 1
+        hook = lambda j, when: when == "end" and fate_census(job.scene, job.rays, job.fate, table=job.census)
     calls = split_calls(job.num_iter, per_call)
     if n_rays and calls:
         reserve(job.scene, n_rays, max(calls))
     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0.record()
     if n_rays:
-        run_steps(hip_tracer(job.scene, variant, job.stats, job.windows), job.rays, job.rng, job.eb, job.shard.gid,
-                  job.num_iter, per_call)
+        run_steps(hip_tracer(job.scene, variant, job.stats, job.windows, fate=job.fate), job.rays, job.rng, job.eb,
+                  job.shard.gid, job.num_iter, per_call, hook=hook)
     t1.record()
     torch.cuda.synchronize()
     check_stats(job.stats)
@@ -208,6 +231,28 @@ def _collect(job, on_device: bool, keep_grid: bool):
     elif on_device:
         table = eyebox_window_sums(job.eb)
     return job.eb.cpu().numpy() if want_grid and job.rank == 0 else None, table, job.stats.cpu().numpy()
+
+
+def _census(job):
+    """The job's fate census on rank 0 (``budget``; else None): every rank's table of its shard, sum-reduced -- one
+    reduce of an int64 table through ``distributed._operands``, as the window tables go."""
+    if job.census is None:
+        return None
+    from .distributed import reduce_eyebox
+    return reduce_eyebox(job.census)
+
+
+def _report_budget(job, out: dict, census) -> None:
+    """The loss budget into ``out`` and printed per wavelength (``engine.loss_budget``)."""
+    from .engine import FATE_CLASSES, loss_budget
+    out["fate_census"] = census.cpu().numpy()
+    out["loss_budget"] = b = loss_budget(out["fate_census"], job.scene)
+    names = {0: "Blue", 1: "Green", 2: "Red"}
+    job.say("Loss budget (share of the traced rays)")
+    job.say("  " + " " * 18 + "".join(f"{names.get(k, str(k)):>10s}" for k in range(len(b["per_wavelength"]))) + f"{'all':>10s}")
+    for name, _, _ in FATE_CLASSES:
+        row = [w["fractions"][name] for w in b["per_wavelength"]] + [b["total"]["fractions"][name]]
+        job.say(f"  {name:18s}" + "".join(f"{v * 100:9.3f}%" for v in row))
 
 
 def _report(job, out: dict, grid, table) -> None:
@@ -328,6 +373,9 @@ def main(argv=None):
     ap.add_argument("--evaluate", choices=["host", "device"], default="host",
                     help="where the evaluation's colour math runs: host (numpy) or device (wgrt_eyebox_evaluate on "
                          "the window-sum table; needs --eyebox device or windows)")
+    ap.add_argument("--budget", action="store_true",
+                    help="also report where every ray ended: per-ray fates, their per-tile census and the loss budget "
+                         "per wavelength (the traces then run as plain single launches)")
     ap.add_argument("--json", default=None, help="write scalar results here")
     ap.add_argument("--png", default="Eyebox Center View.png",
                     help="the eyebox-center image (MAIN:199-203); empty string: do not write it")
@@ -341,7 +389,7 @@ def main(argv=None):
     res = run(a.num_fov_x, a.num_fov_y, a.rays_per_fov, a.num_iter, lut_dir=a.lut_dir, lut_seed=a.lut_seed,
               lut_profile=a.lut_profile, point_seed=a.point_seed, evaluate=not a.no_eval,
               fuse=False if a.no_fuse else {"auto": None, "yes": True, "no": False}[a.fuse],
-              png=a.png or None, eyebox=a.eyebox, evaluate_on=a.evaluate)
+              png=a.png or None, eyebox=a.eyebox, evaluate_on=a.evaluate, budget=a.budget)
     if a.json and (not dist.is_initialized() or dist.get_rank() == 0):
         keep = {k: v for k, v in res.items() if isinstance(v, (int, float, dict, str))}
         with open(a.json, "w") as f:

@@ -407,6 +407,51 @@ wgrt_status wgrt_chain_begin(const wgrt_scene *scene, const wgrt_rays *rays, int
 wgrt_status wgrt_chain_step(wgrt_chain *chain);
 wgrt_status wgrt_chain_end(wgrt_chain *chain);
 
+/* Where every ray ends: per-ray fates and the per-tile census (new symbols within ABI 9, looked up by name).
+ *
+ * A ray's fate is the code 10 * region + reason of the place its trace ended (csrc/wgrt_fate.h states it once;
+ * it is the CPU oracle's code): region the state R0..R5 the ray was in, 9 for the in-coupling event; reason
+ *   1 left eff_reg1 (left the plate)      2 Monte-Carlo loss (the draw took no branch)
+ *   3 out-coupled inside the FoV's eyebox rectangle   4 out-coupled outside it
+ *   5 missed every out-coupler slice in R5            6 the in-coupler's second order left the in-coupler
+ *   7 ran out of bounces (range(100000) exhausted).
+ * 27 codes can occur: 92 96; 01 02 06 07; 11 12 16 17; 21 22 27; 31 32 37; 41 42 43 44 47; 51 52 53 54 55 57.
+ * 0 means "not traced" (an m / n / lmd_num outside the scene).  An out-coupling whose aliased grid offset is
+ * dropped (GRTF:164) is still reason 3, so per tile the reason-3 count is the number of rays of THAT tile that
+ * reached its eyebox, while matrix_EB counts a hit in the slab its aliased offset falls into.
+ *
+ * wgrt_trace_fate is wgrt_trace_windows plus fate, a DEVICE uint8 [n_rays]: after the launch fate[i], i < n_rays,
+ * has been written exactly once, by whichever lane finished ray i's trace (the Jones-vector lane, or the exact
+ * lane for variant 1 and for a replayed ray); both give the same code.  fate == NULL is exactly
+ * wgrt_trace_windows.  matrix_EB, rng_states, the window table and stats come out bit-identical with and without
+ * fate.  fate != NULL with opts->num_iter > 1 is WGRT_ERR_INVALID_ARGUMENT (a fused launch's retire sites
+ * publish hand-off granules; trace the iterations one call each), and wgrt_chain_begin takes no fates.  What a
+ * fate launch routes around: it runs the fate-storing kernel instantiation, which has no learning and no timeline
+ * twin, so a fate launch never learns the scene's tile table (the automatic issue order learns from the next plain
+ * launch instead; results do not depend on the order), and fate with wgrt_debug_opts.timeline is
+ * WGRT_ERR_UNSUPPORTED.  A launch without fate runs the kernels it ran before this entry point existed. */
+#define WGRT_FATE_COLS 56      /* column = 8 * min(code / 10, 6) + code % 10; column 0 reserved */
+wgrt_status wgrt_trace_fate(const wgrt_scene *scene, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
+                            uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats,
+                            uint32_t *per_ray_bounces, void *stream, const wgrt_launch_opts *opts,
+                            const wgrt_window_plan *plan, double *table, uint8_t *fate);
+
+/* The census: ray i with valid code c and tile s = (l * ny + n) * nx + m (matrix_EB's slab order; m, n, lmd_num
+ * the batch's DEVICE columns, lmd_num == NULL: l = 0) adds 1 to table[s, column(c)], table a DEVICE int64
+ * [num_lmd * ny * nx, WGRT_FATE_COLS] that is ADDED to and never zeroed.  A ray is counted nowhere if its code is
+ * 0 or none of the codes above, or if its tile lies outside the scene; nothing outside the table is touched.
+ * Integer atomics: the table is the same on every run and for any ray order.  Asynchronous on stream, allocates
+ * nothing; n_rays == 0 is WGRT_OK without a launch. */
+wgrt_status wgrt_fate_census(const uint8_t *fate, const float *m, const float *n, const float *lmd_num,
+                             int64_t n_rays, int32_t nx, int32_t ny, int32_t num_lmd, int64_t *table, void *stream);
+/* Host-only twins (no GPU needed): the same census over HOST pointers through the same validity rule and column
+ * function; the column of a code (-1 for a code that is not one of the 27); a reason's name (1..7, else NULL). */
+wgrt_status wgrt_fate_census_host(const uint8_t *fate, const float *m, const float *n, const float *lmd_num,
+                                  int64_t n_rays, int32_t nx, int32_t ny, int32_t num_lmd, int64_t *table);
+int32_t wgrt_fate_col(int code);
+int32_t wgrt_fate_cols(void);   /* WGRT_FATE_COLS of the library */
+const char *wgrt_fate_reason_name(int reason);
+
 /* Host-only (no GPU needed; test hooks) through the same membership code (csrc/wgrt_window.h):
  * _validate is wgrt_window_plan_create's argument check alone; _table_host ADDS the n hits at flat grid
  * offsets offsets[n] (HOST int64; those outside [0, n_slabs * 9600) are dropped, as the grid's guard drops
