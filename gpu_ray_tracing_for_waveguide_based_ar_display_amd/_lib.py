@@ -23,7 +23,7 @@ ABI_VERSION = 9
 EXPORTED = ("wgrt_scene_create", "wgrt_scene_create_ex", "wgrt_scene_destroy", "wgrt_scene_get_info",
             "wgrt_trace_fullcolor", "wgrt_trace_fullcolor_ex", "wgrt_trace_single", "wgrt_trace_single_ex",
             "wgrt_trace_opts", "wgrt_scene_reserve", "wgrt_rays_init", "wgrt_scene_classify",
-            "wgrt_locator_classify_host", "wgrt_selftest_math", "wgrt_status_string", "wgrt_last_error",
+            "wgrt_locator_classify_host", "wgrt_locator_palette_host", "wgrt_selftest_math", "wgrt_status_string", "wgrt_last_error",
             "wgrt_abi_version", "wgrt_eyebox_payload_floats", "wgrt_eyebox_pack", "wgrt_eyebox_assemble",
             "wgrt_eyebox_window_sums", "wgrt_eyebox_evaluate_workspace_bytes", "wgrt_eyebox_evaluate",
             "wgrt_eyebox_evaluate_host", "wgrt_window_plan_create", "wgrt_window_plan_destroy",
@@ -32,7 +32,8 @@ EXPORTED = ("wgrt_scene_create", "wgrt_scene_create_ex", "wgrt_scene_destroy", "
             "wgrt_fate_census_host", "wgrt_fate_col", "wgrt_fate_cols", "wgrt_fate_reason_name")
 EXPORTED_DEBUG = ("wgrt_debug_shadow", "wgrt_debug_scene_copy", "wgrt_debug_set_auto_order",
                   "wgrt_debug_get_auto_order", "wgrt_debug_get_tile_tail", "wgrt_debug_order_host",
-                  "wgrt_debug_chain_plan", "wgrt_debug_chain_set_serial")
+                  "wgrt_debug_chain_plan", "wgrt_debug_chain_set_serial", "wgrt_debug_set_byte_locator",
+                  "wgrt_debug_set_palette_cap", "wgrt_debug_scene_palette")
 
 
 class WgrtError(RuntimeError):
@@ -285,6 +286,17 @@ def load():
         L.wgrt_fate_cols.argtypes = []
         L.wgrt_fate_reason_name.restype = ctypes.c_char_p
         L.wgrt_fate_reason_name.argtypes = [ctypes.c_int]
+    if hasattr(L, "wgrt_locator_palette_host"):   # the byte locator's hooks: new symbols within ABI 9, bound by name
+        L.wgrt_locator_palette_host.restype = st
+        L.wgrt_locator_palette_host.argtypes = [ctypes.POINTER(SceneDesc), ctypes.c_double, _i64, _i64, _d,
+                                                ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _vp, _vp, _vp,
+                                                ctypes.c_int64]
+        L.wgrt_debug_set_byte_locator.restype = st
+        L.wgrt_debug_set_byte_locator.argtypes = [ctypes.c_int]
+        L.wgrt_debug_set_palette_cap.restype = st
+        L.wgrt_debug_set_palette_cap.argtypes = [ctypes.c_int]
+        L.wgrt_debug_scene_palette.restype = st
+        L.wgrt_debug_scene_palette.argtypes = [_vp] + [ctypes.POINTER(ctypes.c_int)] * 3
     L.wgrt_status_string.restype = ctypes.c_char_p
     L.wgrt_status_string.argtypes = [ctypes.c_int]
     L.wgrt_last_error.restype = ctypes.c_char_p
@@ -442,16 +454,29 @@ class Scene:
 
     def debug_copy(self, which: str) -> np.ndarray:
         """Host copy of a device structure (wgrt_debug_scene_copy): "cells" (uint64 [ncy, ncx]),
-        "tiles" / "jtiles" (float64 [tiles, doubles per tile])."""
+        "tiles" / "jtiles" (float64 [tiles, doubles per tile]), "cells8" / "palette" (the byte locator's byte grid,
+        uint8 [ncy, ncx], and its 256 palette words; a scene without a byte grid raises)."""
         inf = self.info()
         if which == "cells":
             out = np.empty((inf["grid_cells_y"], inf["grid_cells_x"]), np.uint64)
+        elif which == "cells8":
+            out = np.empty((inf["grid_cells_y"], inf["grid_cells_x"]), np.uint8)
+        elif which == "palette":
+            out = np.empty(256, np.uint64)
         else:
             per = inf["tile_bytes" if which == "tiles" else "jtile_bytes"] // 8
             out = np.empty((inf["tiles"], per), np.float64)
-        k = {"cells": 0, "tiles": 1, "jtiles": 2}[which]
+        k = {"cells": 0, "tiles": 1, "jtiles": 2, "cells8": 3, "palette": 4}[which]
         check(load().wgrt_debug_scene_copy(self.handle, k, out.ctypes.data, out.nbytes), "wgrt_debug_scene_copy")
         return out
+
+    def palette_info(self) -> dict:
+        """``wgrt_debug_scene_palette``: the grid's distinct cell words, whether the scene has a byte grid, and
+        whether its Jones-vector launches run the byte locator now."""
+        n, g, a = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        check(load().wgrt_debug_scene_palette(self.handle, ctypes.byref(n), ctypes.byref(g), ctypes.byref(a)),
+              "wgrt_debug_scene_palette")
+        return {"distinct_words": n.value, "byte_grid": bool(g.value), "active": bool(a.value)}
 
     def eb_shape(self):
         if self.single_lambda:   # process_rays_kernel_pro's matrix_EB [NY, NX, 80, 120]
@@ -486,3 +511,43 @@ def locator_classify_host(geom, luts, xy: np.ndarray, cell_mm: float = 0.125) ->
           "wgrt_locator_classify_host")
     return out
 
+
+
+def set_byte_locator(on: bool) -> None:
+    """``wgrt_debug_set_byte_locator``: the Jones-vector lane's byte locator on / off, process-wide (A/B, tests)."""
+    check(load().wgrt_debug_set_byte_locator(1 if on else 0), "wgrt_debug_set_byte_locator")
+
+
+def set_palette_cap(cap: int = 256) -> None:
+    """``wgrt_debug_set_palette_cap``: scenes created from now on get a byte grid only with at most ``cap``
+    distinct cell words (tests force the word-form fallback with a small cap)."""
+    check(load().wgrt_debug_set_palette_cap(int(cap)), "wgrt_debug_set_palette_cap")
+
+
+def locator_palette_host(geom, luts, cell_mm: float = 0.125, tables: bool = True) -> dict:
+    """Host build of the byte locator's tables (``wgrt_locator_palette_host``; needs no GPU): ``count`` distinct
+    cell words, ``cells`` (uint64 [ncy, ncx]) and, when the descriptor gets a byte grid, ``palette`` (uint64
+    [256]) and ``cells8`` (uint8 [ncy, ncx]); else both None; ``x0, y0, h``: the grid's origin and cell size.  ``tables=False``: the count and grid size only."""
+    L = load()
+    desc, keep, _ = make_desc(geom.IC, geom.FC, geom.FC_offset, geom.OC, geom.OC_offset, geom.n_g,
+                              geom.eff_reg1, geom.eff_reg2, geom.eff_reg_FOV, geom.eff_reg_FOV_range,
+                              luts["lut_ic1"], luts["lut_ic2"], luts["lut_ic3"], luts["lut_fc1"],
+                              luts["lut_fc2"], luts["lut_oc1"], luts["lut_oc2"], geom.lut_TIR, geom.lut_gap)
+    ncx, ncy, cnt, has = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int(), ctypes.c_int()
+    grid = (ctypes.c_double * 3)()
+    call = lambda *bufs: check(L.wgrt_locator_palette_host(ctypes.byref(desc), float(cell_mm), ctypes.byref(ncx),
+                                                           ctypes.byref(ncy), grid, ctypes.byref(cnt), ctypes.byref(has), *bufs),
+                               "wgrt_locator_palette_host")
+    call(None, None, None, 0)
+    out = {"count": cnt.value, "byte_grid": bool(has.value), "ncx": ncx.value, "ncy": ncy.value, "x0": grid[0],
+           "y0": grid[1], "h": grid[2], "cells": None,
+           "palette": None, "cells8": None}
+    if not tables:
+        return out
+    shape = (ncy.value, ncx.value)
+    pal, c8, cells = np.zeros(256, np.uint64), np.zeros(shape, np.uint8), np.zeros(shape, np.uint64)
+    call(pal.ctypes.data_as(_vp), c8.ctypes.data_as(_vp), cells.ctypes.data_as(_vp), cells.size)
+    out["cells"] = cells
+    if has.value:
+        out["palette"], out["cells8"] = pal, c8
+    return out

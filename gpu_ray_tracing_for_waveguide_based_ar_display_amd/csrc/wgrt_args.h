@@ -29,6 +29,8 @@ constexpr int kWaitVmcnt0 = 0x0F70;
 template <class CellT>
 struct LocatorT {
     using Word = CellT;
+    using Cell = CellT;   // what the grid holds and a lane prefetches (JLane::pf)
+    static constexpr bool kByte = false;
     const CellT *cells;
     const double *verts;
     const int32_t *poly_off;
@@ -39,6 +41,28 @@ struct LocatorT {
     const double *bands;    // 128-B band records (LocatorHost::bands); NULL: CSR lists only
 };
 using Locator = LocatorT<uint64_t>;
+
+// The byte form of the locator (the Jones-vector lane only; wgrt_scene_build.h build_palette_host): the grid
+// holds each cell's index into the palette of the scene's distinct cell words (88 on the design geometry), a
+// quarter of the 32-bit grid's cache footprint at the same cell size and the same index arithmetic.  A lane
+// prefetches the byte (JLane::pb) and decodes the word from the workgroup's LDS copy of the palette where it
+// is consumed; everything downstream sees the word a LocatorT<CellT> would have loaded.  The fields the exact
+// test reads keep LocatorT's names.
+template <class CellT>
+struct ByteLocatorT {
+    using Word = CellT;
+    using Cell = uint8_t;
+    static constexpr bool kByte = true;
+    const uint8_t *cells;
+    const double *verts;
+    const int32_t *poly_off;
+    const int32_t *row_off;
+    const int32_t *row_edges;
+    double x0, y0, inv_h;
+    int ncx, ncy;
+    const double *bands;
+    const CellT *palette;   // kPaletteMax words, ascending, zero past the scene's count
+};
 
 struct TraceArgs {
     const float *x, *y, *m, *n, *l, *te, *tm, *dph;

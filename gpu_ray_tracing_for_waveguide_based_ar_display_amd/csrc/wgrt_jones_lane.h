@@ -61,7 +61,38 @@ struct JLane {
     uint32_t k;              // fused launches: the iteration (chained launch) this trace belongs to
     uint32_t s0;             // RNG state at the start of this trace (fused launches: replay point)
     uint64_t pf;             // locator cell word of (x, y), loaded a step ahead
+    uint32_t pb;             // byte locator: the cell's palette index instead (pf unused; one register for variant 9 too)
 };
+
+// The workgroup's LDS copy of the byte locator's palette (ByteLocatorT): filled once at kernel start
+// (fill_palette: 256 threads, one entry each, one barrier), read where a prefetched cell is consumed.
+template <class Loc>
+__device__ __forceinline__ typename Loc::Word *lds_palette() {
+    __shared__ typename Loc::Word pal[kPaletteMax];
+    return pal;
+}
+
+template <class Loc>
+__device__ __forceinline__ void fill_palette(const Loc &loc) {
+    if constexpr (Loc::kByte) {
+        lds_palette<Loc>()[threadIdx.x & (kPaletteMax - 1)] = loc.palette[threadIdx.x & (kPaletteMax - 1)];
+        __syncthreads();
+    }
+}
+
+// The cell of the lane's (new) position, issued a step ahead of its use: the word, or the byte form's index ...
+template <class Loc>
+__device__ __forceinline__ void prefetch_cell(const Loc &loc, JLane &L) {
+    if constexpr (Loc::kByte) L.pb = locate_c(loc, L.r.x, L.r.y);
+    else L.pf = locate_c(loc, L.r.x, L.r.y);
+}
+
+// ... and its cell word where it is consumed (byte form: one LDS read after the prefetch has landed).
+template <class Loc>
+__device__ __forceinline__ typename Loc::Word prefetched_word(const JLane &L) {
+    if constexpr (Loc::kByte) return lds_palette<Loc>()[L.pb];
+    else return (typename Loc::Word)L.pf;
+}
 
 // (kDieIc: what a FATE instantiation's interact returns instead of kDie where the in-coupler's second order leaves
 // the in-coupler -- fate reason 6, wgrt_fate.h; every other die of interact is reason 2)
@@ -411,7 +442,7 @@ __device__ __forceinline__ int interact(const TraceArgs &A, const KArgs &K, cons
     const double2 mv = ba ? mva : mvb;
     r.x = r.x + mv.x;
     r.y = r.y + mv.y;
-    L.pf = locate_c(loc, r.x, r.y);
+    prefetch_cell(loc, L);
     // the phase step of the new region's miss hops (R2: 2 lut_TIR[0]; R3, R4: 2 lut_TIR[1]; the
     // in-coupler states and R5 never hop), loaded with the taken branch's matrix
     const double2 hop = *(const double2 *)(T + kJHop + ((kind == 0 || (kind <= 2 && ba)) ? 0 : 2));
@@ -453,7 +484,7 @@ __device__ __forceinline__ int interact(const TraceArgs &A, const KArgs &K, cons
     r.hi = hop.y;
     SEG_IMARK_DEP(sg, 5, r.er + r.ei + r.mr + r.mi + r.ener);
     if (kind == 0) {
-        const bool in_ic = in_poly_w(loc, (typename Loc::Word)L.pf, kPolyIC, r.x, r.y, &K);
+        const bool in_ic = in_poly_w(loc, prefetched_word<Loc>(L), kPolyIC, r.x, r.y, &K);
         if (ba) return in_ic ? 0 : 2;
         return in_ic ? 1 : (FATE ? kDieIc : kDie);
     }
@@ -507,7 +538,7 @@ __device__ __forceinline__ int advance(const TraceArgs &A, const KArgs &K, const
     constexpr W kLow = (W)0x5555555555555555ull;
     constexpr W kTop = (W)1 << (kBits - 1);
     JRay &r = L.r;
-    W c = (W)L.pf;
+    W c = prefetched_word<Loc>(L);
     const int region = r.region;
     const int nfc = A.nfc, noc = A.noc;
     // the coupler slices this region scans (GRTF:1002-1005, 1112-1115) and its blocks
@@ -555,7 +586,7 @@ __device__ __forceinline__ int advance(const TraceArgs &A, const KArgs &K, const
         const double mr = r.mr;
         r.mr = fma(mr, r.hr, -r.mi * r.hi);
         r.mi = fma(mr, r.hi, r.mi * r.hr);
-        L.pf = locate_c(loc, r.x, r.y);   // read by the next pass
+        prefetch_cell(loc, L);   // read by the next pass
     }
     const int step = hit ? blkbase + sl : kTransit;
     const int next = ic ? 1 + region : step;

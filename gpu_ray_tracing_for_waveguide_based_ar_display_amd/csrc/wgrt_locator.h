@@ -111,9 +111,10 @@ __device__ __forceinline__ bool in_poly_w(const Loc &L, typename Loc::Word w, in
 }
 
 // Cell word of (x, y): the grid has a border of all-OUT cells, so clamping is exact for points
-// outside it (and for NaN, which converts to 0).
+// outside it (and for NaN, which converts to 0).  The byte form (ByteLocatorT) loads the cell's palette index
+// with the same clamp and the same index.
 template <class Loc>
-__device__ __forceinline__ typename Loc::Word locate_c(const Loc &L, double x, double y) {
+__device__ __forceinline__ typename Loc::Cell locate_c(const Loc &L, double x, double y) {
     int ix = (int)((x - L.x0) * L.inv_h), iy = (int)((y - L.y0) * L.inv_h);
     ix = min(max(ix, 0), L.ncx - 1);
     iy = min(max(iy, 0), L.ncy - 1);

@@ -20,6 +20,14 @@ struct wgrt_scene {
     int jtile_d = 0;
     uint64_t *d_cells = nullptr;
     uint32_t *d_cells32 = nullptr;   // 32-bit copy of the cell words (npoly <= 16), else NULL
+    // The byte locator (wgrt_args.h ByteLocatorT): the scene's distinct cell words ascending (zero past palette_count;
+    // kPaletteSlots entries, of which the kernels read the first kPaletteMax, and their 32-bit copy for npoly <= 16) and each cell's palette index.  All NULL when the
+    // grid holds more distinct words than the palette (or the debug cap at creation) allows: such a scene runs the
+    // word-form kernels.  palette_count: the distinct words, saturating at kPaletteSlots.
+    uint64_t *d_palette = nullptr;
+    uint32_t *d_palette32 = nullptr;
+    uint8_t *d_cells8 = nullptr;
+    int palette_count = 0;
     double *d_verts = nullptr;
     int32_t *d_poly_off = nullptr;
     int32_t *d_row_off = nullptr;
@@ -28,12 +36,13 @@ struct wgrt_scene {
     wgrt::LocatorHost loc_host;  // grid parameters (cells / verts vectors released after upload)
     int64_t tiles = 0;
     int64_t edge_cells = 0;        // locator cells with an EDGE class
-    int jones_grid[2][2][2] = {};   // resident 256-thread workgroups: [64-bit cells][fused][single wavelength]
-    int jones_tl_grid[2] = {};      // ... of the debug timeline instantiations (32-bit cells): [fused]
-    int jones_fate_grid[2][2] = {}; // ... of the fate-storing instantiations (wgrt_trace_fate): [64-bit cells][single wavelength]
-    int jones_learn_grid[2] = {};   // ... of the learning instantiations (full colour, single trace): [64-bit cells]
-    int jones_chain_grid[2] = {};   // ... the most a chained step may use (wgrt_chain_*): [64-bit cells], half the
-                                    // resident grid less a margin (query_trace_grids)
+    // resident 256-thread workgroups, each [byte locator] first: the word-form and the byte-form instantiations
+    int jones_grid[2][2][2][2] = {};   // [64-bit cells][fused][single wavelength]
+    int jones_tl_grid[2][2] = {};      // ... of the debug timeline instantiations (32-bit cells): [fused]
+    int jones_fate_grid[2][2][2] = {}; // ... of the fate-storing instantiations (wgrt_trace_fate): [64-bit cells][single wavelength]
+    int jones_learn_grid[2][2] = {};   // ... of the learning instantiations (full colour, single trace): [64-bit cells]
+    int jones_chain_grid[2][2] = {};   // ... the most a chained step may use (wgrt_chain_*): [64-bit cells], half the
+                                       // resident grid less a margin (query_trace_grids)
     int64_t nonunitary_blocks = 0;  // Jones blocks whose branch matrices are not scaled-unitary (their launches
                                     // run the AMP instantiations: wgrt_jones_lane.h, the amplification step)
     // The automatic issue order's statistic (wgrt_order.h): per (wavelength, FoV) tile, the traces of the
@@ -106,6 +115,20 @@ inline Locator make_locator(const wgrt_scene *s) {
     L.inv_h = s->loc_host.inv_h;
     L.ncx = s->loc_host.ncx;
     L.ncy = s->loc_host.ncy;
+    return L;
+}
+
+template <class CellT>
+inline ByteLocatorT<CellT> make_byte_locator(const wgrt_scene *s, const Locator &g, const CellT *palette) {
+    ByteLocatorT<CellT> L;
+    L.cells = s->d_cells8;
+    L.palette = palette;
+    L.verts = g.verts;
+    L.poly_off = g.poly_off;
+    L.row_off = g.row_off;
+    L.row_edges = g.row_edges;
+    L.bands = g.bands;
+    L.x0 = g.x0, L.y0 = g.y0, L.inv_h = g.inv_h, L.ncx = g.ncx, L.ncy = g.ncy;
     return L;
 }
 

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <initializer_list>
 #include <string>
@@ -110,6 +111,74 @@ __global__ __launch_bounds__(256) void classify_cells_kernel(const double *verts
     if ((threadIdx.x & 63) == 0 && edges) atomicAdd(edge_cells, (unsigned long long)edges);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The byte locator's palette and byte grid on the device (wgrt_scene_build.h build_palette_host is the host
+// build's; both are pure functions of the word grid, so the two builds agree byte for byte).
+// ---------------------------------------------------------------------------------------------
+constexpr unsigned long long kPalEmpty = ~0ull;   // no cell word: class 3 does not exist
+
+// The distinct cell words into an open-addressing table of kPaletteSlots slots.  Only a cell whose word differs
+// from its left neighbour's inserts (the first of a run; every distinct word starts at least one run), and an
+// insert first looks: the atomics are as many as there are distinct words, give or take a race.  A word that finds
+// the table full sets *overflow.
+__global__ __launch_bounds__(256) void palette_collect_kernel(const uint64_t *cells, int64_t n, unsigned long long *table,
+                                                              int *overflow) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    const unsigned long long w = cells[c];
+    if (c > 0 && cells[c - 1] == w) return;
+    unsigned h = (unsigned)((w * 0x9E3779B97F4A7C15ull) >> 40) & (kPaletteSlots - 1);
+    for (int probe = 0; probe < kPaletteSlots; ++probe, h = (h + 1) & (kPaletteSlots - 1)) {
+        unsigned long long cur = __hip_atomic_load(table + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == kPalEmpty) cur = atomicCAS(table + h, kPalEmpty, w);
+        if (cur == kPalEmpty || cur == w) return;
+    }
+    atomicOr(overflow, 1);
+}
+
+// One workgroup: the table's words by rank (strictly ascending; zero past the count) and their count.
+__global__ __launch_bounds__(1024) void palette_sort_kernel(const unsigned long long *table, uint64_t *palette,
+                                                            uint32_t *palette32, int *count) {
+    __shared__ unsigned long long key[kPaletteSlots];
+    __shared__ int total;
+    if (threadIdx.x == 0) total = 0;
+    for (int k = threadIdx.x; k < kPaletteSlots; k += blockDim.x) {
+        key[k] = table[k];
+        palette[k] = 0;
+    }
+    for (int k = threadIdx.x; k < kPaletteMax; k += blockDim.x) palette32[k] = 0;
+    __syncthreads();
+    for (int k = threadIdx.x; k < kPaletteSlots; k += blockDim.x) {
+        const unsigned long long w = key[k];
+        if (w == kPalEmpty) continue;
+        int rank = 0;
+        for (int j = 0; j < kPaletteSlots; ++j) rank += key[j] < w;   // (the empty marker is the largest value)
+        palette[rank] = w;
+        if (rank < kPaletteMax) palette32[rank] = (uint32_t)w;
+        atomicAdd(&total, 1);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) *count = total;
+}
+
+// Each cell's palette index: a binary search of the (at most kPaletteMax) palette words held in LDS.
+__global__ __launch_bounds__(256) void cells8_kernel(const uint64_t *cells, int64_t n, const uint64_t *palette, int count,
+                                                     uint8_t *cells8) {
+    __shared__ uint64_t pal[kPaletteMax];
+    pal[threadIdx.x] = threadIdx.x < count ? palette[threadIdx.x] : ~0ull;
+    __syncthreads();
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    const uint64_t w = cells[c];
+    int lo = 0;
+    for (int step = kPaletteMax / 2; step > 0; step >>= 1) lo += pal[lo + step - 1] < w ? step : 0;
+    cells8[c] = (uint8_t)lo;
+}
+
+// wgrt_debug_set_palette_cap: the most distinct cell words a scene created from now on may have and still get a
+// byte grid (tests force the fallback with it; at most kPaletteMax, the default).
+std::atomic<int> g_palette_cap{kPaletteMax};
+
 // Blocks of the Jones tiles flagged non-scaled-unitary (the sign bit of their float Wsum, wgrt_pack.h):
 // counted once per scene, to pick the trace kernel instantiation (AMP) for its launches.
 __global__ __launch_bounds__(256) void nonunitary_kernel(const double *jtiles, int64_t ntiles, int jd, int nblk,
@@ -152,6 +221,62 @@ wgrt_status upload_n(const T *src, size_t n, T **dst) {
 template <class T>
 wgrt_status upload(const std::vector<T> &v, T **dst) {
     return upload_n(v.data(), v.size(), dst);
+}
+
+// The scene's palette and byte grid from its cell words: on the host from the host build's words (host_cells), else
+// on the device from d_cells.  More distinct words than the cap: the scene keeps only the count.
+wgrt_status build_byte_grid(wgrt_scene *s, size_t ncells, const std::vector<uint64_t> *host_cells) {
+    const int cap = std::min(g_palette_cap.load(std::memory_order_relaxed), kPaletteMax);
+    wgrt_status st;
+    if (host_cells) {
+        std::vector<uint64_t> pal;
+        std::vector<uint8_t> c8;
+        s->palette_count = build_palette_host(*host_cells, cap, pal, c8);
+        if (s->palette_count > cap) return WGRT_OK;
+        pal.resize(kPaletteSlots, 0ull);
+        std::vector<uint32_t> pal32(pal.begin(), pal.begin() + kPaletteMax);
+        if ((st = upload(pal, &s->d_palette)) != WGRT_OK || (st = upload(c8, &s->d_cells8)) != WGRT_OK ||
+            (s->npoly <= 16 && (st = upload(pal32, &s->d_palette32)) != WGRT_OK))
+            return st;
+        return WGRT_OK;
+    }
+    unsigned long long *table = nullptr;
+    int *flags = nullptr;   // [0] the table overflowed, [1] the count
+    uint32_t *pal32 = nullptr;
+    auto done = [&](wgrt_status e) {
+        (void)hipFree(table);
+        (void)hipFree(flags);
+        (void)hipFree(pal32);
+        return e;
+    };
+    if ((st = alloc_n((size_t)kPaletteSlots, &table)) != WGRT_OK || (st = alloc_n(2, &flags)) != WGRT_OK ||
+        (st = alloc_n((size_t)kPaletteMax, &pal32)) != WGRT_OK || (st = alloc_n((size_t)kPaletteSlots, &s->d_palette)) != WGRT_OK)
+        return done(st);
+    auto hip = [&](hipError_t e) { return e == hipSuccess ? WGRT_OK : fail(WGRT_ERR_HIP, std::string("byte grid: ") + hipGetErrorString(e)); };
+    if ((st = hip(hipMemset(table, 0xff, kPaletteSlots * sizeof(unsigned long long)))) != WGRT_OK ||
+        (st = hip(hipMemset(flags, 0, 2 * sizeof(int)))) != WGRT_OK)
+        return done(st);
+    hipLaunchKernelGGL(palette_collect_kernel, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, 0, s->d_cells,
+                       (int64_t)ncells, table, flags);
+    hipLaunchKernelGGL(palette_sort_kernel, dim3(1), dim3(1024), 0, 0, table, s->d_palette, pal32, flags + 1);
+    int h[2] = {0, 0};
+    if ((st = hip(hipGetLastError())) != WGRT_OK || (st = hip(hipMemcpy(h, flags, sizeof(h), hipMemcpyDeviceToHost))) != WGRT_OK)
+        return done(st);
+    s->palette_count = h[0] ? kPaletteSlots : h[1];
+    if (s->palette_count > cap) {
+        (void)hipFree(s->d_palette);
+        s->d_palette = nullptr;
+        return done(WGRT_OK);
+    }
+    if ((st = alloc_n(ncells, &s->d_cells8)) != WGRT_OK) return done(st);
+    hipLaunchKernelGGL(cells8_kernel, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, 0, s->d_cells, (int64_t)ncells,
+                       s->d_palette, s->palette_count, s->d_cells8);
+    if ((st = hip(hipGetLastError())) != WGRT_OK || (st = hip(hipDeviceSynchronize())) != WGRT_OK) return done(st);
+    if (s->npoly <= 16) {
+        s->d_palette32 = pal32;
+        pal32 = nullptr;
+    }
+    return done(WGRT_OK);
 }
 
 }  // namespace
@@ -291,6 +416,7 @@ wgrt_status wgrt_scene_create_ex(const wgrt_scene_desc *desc, int device, const 
         }
         s->edge_cells = (int64_t)ec;
     }
+    if ((st = build_byte_grid(s, ncells, host_build ? &host.loc.cells : nullptr)) != WGRT_OK) return bail(st);
     {   // the scene's non-scaled-unitary blocks (the trace kernel instantiation its launches run)
         const int nblk = 3 + 2 * s->nfc + 2 * s->noc;
         const int64_t nt = (int64_t)s->nl * s->nx * s->ny;
@@ -329,7 +455,8 @@ wgrt_status wgrt_scene_create_ex(const wgrt_scene_desc *desc, int device, const 
 wgrt_status wgrt_scene_destroy(wgrt_scene *s) {
     if (!s) return WGRT_OK;
     DeviceScope dev_scope(s->device);
-    for (void *p : {(void *)s->d_tiles, (void *)s->d_jtiles, (void *)s->d_cells, (void *)s->d_cells32, (void *)s->d_verts,
+    for (void *p : {(void *)s->d_tiles, (void *)s->d_jtiles, (void *)s->d_cells, (void *)s->d_cells32, (void *)s->d_palette, (void *)s->d_palette32,
+                    (void *)s->d_cells8, (void *)s->d_verts,
                     (void *)s->d_poly_off, (void *)s->d_row_off, (void *)s->d_row_edges, (void *)s->d_bands,
                     (void *)s->d_tile_tail})
         (void)hipFree(p);
@@ -410,6 +537,45 @@ wgrt_status wgrt_locator_classify_host(const wgrt_scene_desc *desc, double cell_
     return WGRT_OK;
 }
 
+wgrt_status wgrt_locator_palette_host(const wgrt_scene_desc *desc, double cell_mm, int64_t *ncx, int64_t *ncy,
+                                      double *grid, int *distinct_words, int *byte_grid, uint64_t *palette, uint8_t *cells8,
+                                      uint64_t *cells, int64_t n_cells) {
+    if (!desc) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!(cell_mm > 0.0)) return fail(WGRT_ERR_INVALID_ARGUMENT, "cell_mm must be > 0");
+    SceneHost host;
+    try {
+        build_scene_host(*desc, cell_mm, host, true, false);
+    } catch (const std::exception &e) {
+        return fail(WGRT_ERR_INVALID_ARGUMENT, e.what());
+    }
+    const int64_t n = (int64_t)host.loc.ncx * host.loc.ncy;
+    if (ncx) *ncx = host.loc.ncx;
+    if (ncy) *ncy = host.loc.ncy;
+    if (grid) grid[0] = host.loc.x0, grid[1] = host.loc.y0, grid[2] = host.loc.h;
+    if ((cells8 || cells) && n_cells != n)
+        return fail(WGRT_ERR_INVALID_ARGUMENT, "n_cells must be the grid's " + std::to_string(n) + " cells");
+    const int cap = std::min(g_palette_cap.load(std::memory_order_relaxed), kPaletteMax);
+    std::vector<uint64_t> pal;
+    std::vector<uint8_t> c8;
+    const int count = build_palette_host(host.loc.cells, cap, pal, c8);
+    if (distinct_words) *distinct_words = count;
+    if (byte_grid) *byte_grid = count <= cap;
+    if (cells) std::copy(host.loc.cells.begin(), host.loc.cells.end(), cells);
+    if (count > cap) return WGRT_OK;   // no byte grid: palette / cells8 are left as they were
+    if (palette) {
+        std::fill(palette, palette + kPaletteMax, 0ull);
+        std::copy(pal.begin(), pal.end(), palette);
+    }
+    if (cells8) std::copy(c8.begin(), c8.end(), cells8);
+    return WGRT_OK;
+}
+
+wgrt_status wgrt_debug_set_palette_cap(int cap) {
+    if (cap < 0) return fail(WGRT_ERR_INVALID_ARGUMENT, "cap must be >= 0");
+    g_palette_cap.store(std::min(cap, kPaletteMax), std::memory_order_relaxed);
+    return WGRT_OK;
+}
+
 wgrt_status wgrt_debug_scene_copy(const wgrt_scene *s, int which, void *dst, int64_t bytes) {
     if (!s || !dst) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL scene / dst");
     const size_t ncells = (size_t)s->loc_host.ncx * s->loc_host.ncy;
@@ -419,8 +585,11 @@ wgrt_status wgrt_debug_scene_copy(const wgrt_scene *s, int which, void *dst, int
         case 0: src = s->d_cells, n = ncells * sizeof(uint64_t); break;
         case 1: src = s->d_tiles, n = (size_t)s->tiles * s->tile_d * sizeof(double); break;
         case 2: src = s->d_jtiles, n = (size_t)s->tiles * s->jtile_d * sizeof(double); break;
-        default: return fail(WGRT_ERR_INVALID_ARGUMENT, "which: 0 cells, 1 tiles, 2 jtiles");
+        case 3: src = s->d_cells8, n = ncells; break;
+        case 4: src = s->d_palette, n = (size_t)kPaletteMax * sizeof(uint64_t); break;
+        default: return fail(WGRT_ERR_INVALID_ARGUMENT, "which: 0 cells, 1 tiles, 2 jtiles, 3 byte grid, 4 palette");
     }
+    if (!src) return fail(WGRT_ERR_UNSUPPORTED, "the scene has no byte grid (wgrt_debug_scene_palette)");
     if (bytes != (int64_t)n) return fail(WGRT_ERR_INVALID_ARGUMENT, "bytes must be " + std::to_string(n));
     DEVICE_SCOPE(dev_scope, s->device);
     HIP_TRY(hipMemcpy(dst, src, n, hipMemcpyDeviceToHost));

@@ -218,6 +218,41 @@ void build_locator(const std::vector<const double *> &polys, const std::vector<i
     classify_cells_host(polys, nverts, out);
 }
 
+int build_palette_host(const std::vector<uint64_t> &cells, int cap, std::vector<uint64_t> &palette,
+                       std::vector<uint8_t> &cells8) {
+    palette.clear();
+    cells8.clear();
+    // the distinct words, kept sorted; neighbouring cells mostly share their word, so the last one is tried first
+    std::vector<uint64_t> pal;
+    bool have = false;
+    uint64_t last = 0;
+    for (const uint64_t w : cells) {
+        if (have && w == last) continue;
+        have = true;
+        last = w;
+        const auto it = std::lower_bound(pal.begin(), pal.end(), w);
+        if (it != pal.end() && *it == w) continue;
+        if ((int)pal.size() >= kPaletteSlots) return kPaletteSlots;   // saturated
+        pal.insert(it, w);
+    }
+    const int count = (int)pal.size();
+    if (count > std::min(cap, kPaletteMax)) return count;
+    cells8.resize(cells.size());
+    size_t idx = 0;
+    have = false;
+    for (size_t c = 0; c < cells.size(); ++c) {
+        const uint64_t w = cells[c];
+        if (!have || w != last) {
+            idx = (size_t)(std::lower_bound(pal.begin(), pal.end(), w) - pal.begin());
+            have = true;
+            last = w;
+        }
+        cells8[c] = (uint8_t)idx;
+    }
+    palette = std::move(pal);
+    return count;
+}
+
 PackView pack_view(const wgrt_scene_desc &d, const double *trig) {
     PackView v;
     v.ic1 = d.lut_ic1, v.ic2 = d.lut_ic2, v.ic3 = d.lut_ic3;

@@ -47,6 +47,15 @@ void classify_cells_host(const std::vector<const double *> &polys, const std::ve
                          LocatorHost &out);
 void build_locator(const std::vector<const double *> &polys, const std::vector<int64_t> &nverts,
                    double cell_mm, LocatorHost &out);
+// The byte form of the cell grid (the Jones-vector lane's byte locator): the palette -- the grid's distinct cell
+// words, ascending, so that it and the byte grid are pure functions of the word grid -- and each cell's palette
+// index.  A scene has a byte grid when it has at most `cap` <= kPaletteMax distinct words; the count is exact up
+// to kPaletteSlots (the device build's table), which it saturates at.
+constexpr int kPaletteMax = 256;
+constexpr int kPaletteSlots = 2048;
+// returns the distinct-word count; palette / cells8 are filled only when it is <= cap (else left empty)
+int build_palette_host(const std::vector<uint64_t> &cells, int cap, std::vector<uint64_t> &palette,
+                       std::vector<uint8_t> &cells8);
 PackView pack_view(const wgrt_scene_desc &d, const double *trig);
 // lut_f32_angles: wgrt_scene_opts bit mask of complex64 tables (cosf of their float32 angles)
 void build_trig(const wgrt_scene_desc &d, std::vector<double> &trig, int lut_f32_angles = 0);

@@ -343,7 +343,8 @@ __device__ __forceinline__ void finish_single(const KArgs &K, Counters c) {
 // contain none of it (a sixth parameter of this function moved an instruction of their prologue).
 template <class Loc>
 constexpr size_t kLearnTailOff = sizeof(TraceArgs) + sizeof(Loc) + sizeof(unsigned long long *) + 8;
-static_assert(sizeof(TraceArgs) % 8 == 0 && sizeof(Locator) % 8 == 0 && sizeof(LocatorT<uint32_t>) % 8 == 0,
+static_assert(sizeof(TraceArgs) % 8 == 0 && sizeof(Locator) % 8 == 0 && sizeof(LocatorT<uint32_t>) % 8 == 0 &&
+                  sizeof(ByteLocatorT<uint64_t>) % 8 == 0 && sizeof(ByteLocatorT<uint32_t>) % 8 == 0,
               "kLearnTailOff: the kernel parameters lie back to back, the int padded to 8 bytes");
 // CHAIN: a step of a chain of single launches (wgrt_chain_*; full colour): the single-launch path, but the
 // ray's start state comes from its granule A.rng64[i] once its tag says that the previous step's trace of the ray
@@ -357,6 +358,8 @@ static_assert(sizeof(TraceArgs) % 8 == 0 && sizeof(Locator) % 8 == 0 && sizeof(L
 // from eyebox_inside, the bin step's own predicate, on the ~2 % of rays that out-couple) to the retire site, which
 // stores the byte with rng[L.i]; a bad ray stores 0; an abandoned ray stores nothing (its replay on the exact lane
 // does).  Off everywhere else: no register, no store.
+// Loc: the locator's form, a template axis of every instantiation: LocatorT<CellT> gathers cell words,
+// ByteLocatorT<CellT> a scene's byte grid (wgrt_args.h; the workgroup copies the palette into LDS first).
 template <bool FUSED, bool SINGLE, bool TL, bool AMP, bool LEARN, bool CHAIN, bool FATE, class Loc>
 __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, const Loc &loc, unsigned long long *heads,
                                           int chunk) {
@@ -364,6 +367,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
     // place per pass, right after advance(): the rays that ended in the previous pass's interaction (fin)
     // and those advance() ends.  Fused launches retire at once: their hand-off would wait a pass.
     bool fin = false;
+    fill_palette(loc);   // byte locator: the palette into LDS, one barrier (nothing for the word form)
     const int lane = threadIdx.x & 63;
     const int64_t n_chunks = (A.n_rays + chunk - 1) / chunk;
     const int64_t n_iter = FUSED ? A.n_iter : 1;
@@ -940,6 +944,44 @@ __global__ WGRT_JONES_BOUNDS void trace_jones_fate_kernel(TraceArgs A, LocatorT<
         A, kernel_kargs<decltype(trace_jones_fate_kernel<CellT, SINGLE, AMP>)>(), loc, counter, chunk);
 }
 
+// The same kernels over the byte locator (ByteLocatorT<CellT>: the scene's byte grid and palette), under names
+// of their own: the word forms above stay as they are, for scenes without a byte grid and for the A/B
+// (wgrt_debug_set_byte_locator).
+template <class CellT, bool FUSED, bool SINGLE, bool AMP>
+__global__ WGRT_JONES_BOUNDS void trace_jones_b_kernel(TraceArgs A, ByteLocatorT<CellT> loc, unsigned long long *counter,
+                                                       int chunk) {
+    jones_body<FUSED, SINGLE, false, AMP, false, false, false>(
+        A, kernel_kargs<decltype(trace_jones_b_kernel<CellT, FUSED, SINGLE, AMP>)>(), loc, counter, chunk);
+}
+
+template <class CellT, bool FUSED, bool SINGLE>
+__global__ WGRT_JONES_BOUNDS void trace_jones_b_tl_kernel(TraceArgs A, ByteLocatorT<CellT> loc, unsigned long long *counter,
+                                                          int chunk) {
+    jones_body<FUSED, SINGLE, true, false, false, false, false>(
+        A, kernel_kargs<decltype(trace_jones_b_tl_kernel<CellT, FUSED, SINGLE>)>(), loc, counter, chunk);
+}
+
+template <class CellT>
+__global__ WGRT_JONES_BOUNDS void trace_jones_b_learn_kernel(TraceArgs A, ByteLocatorT<CellT> loc,
+                                                             unsigned long long *counter, int chunk, uint32_t *tail) {
+    jones_body<false, false, false, false, true, false, false>(
+        A, kernel_kargs<decltype(trace_jones_b_learn_kernel<CellT>)>(), loc, counter, chunk);
+}
+
+template <class CellT, bool AMP>
+__global__ WGRT_JONES_BOUNDS void trace_jones_b_chain_kernel(TraceArgs A, ByteLocatorT<CellT> loc,
+                                                             unsigned long long *counter, int chunk) {
+    jones_body<false, false, false, AMP, false, true, false>(
+        A, kernel_kargs<decltype(trace_jones_b_chain_kernel<CellT, AMP>)>(), loc, counter, chunk);
+}
+
+template <class CellT, bool SINGLE, bool AMP>
+__global__ WGRT_JONES_BOUNDS void trace_jones_b_fate_kernel(TraceArgs A, ByteLocatorT<CellT> loc,
+                                                            unsigned long long *counter, int chunk) {
+    jones_body<false, SINGLE, false, AMP, false, false, true>(
+        A, kernel_kargs<decltype(trace_jones_b_fate_kernel<CellT, SINGLE, AMP>)>(), loc, counter, chunk);
+}
+
 // The two ends of a chain's segment, on the caller's stream: every ray's state into its granule under the
 // segment's seed tag before the first step, and back to rng_states after the last -- where the tag is the last
 // step's, so a ray no step traced (a bad ray) or whose hand-off was given up keeps what rng_states holds.
@@ -1014,39 +1056,33 @@ __global__ __launch_bounds__(kOrderThreads) void order_kernel(const float *m, co
     }
 }
 
-// Every trace kernel instantiation, stated once: the Jones kernels by [64-bit cells][fused][single
-// wavelength][AMP], the debug timeline kernels (32-bit cells, full colour, no AMP) by [fused].  The occupancy
-// queries loop over the table and the launch indexes it, so a kernel cannot be in one and not the other.  The
-// fate-storing kernels (wgrt_trace_fate) by [64-bit cells][single wavelength][AMP]: single launches only.
-const void *const kJonesKernels[2][2][2][2] = {
-    {{{(const void *)trace_jones_kernel<uint32_t, false, false, false>,
-       (const void *)trace_jones_kernel<uint32_t, false, false, true>},
-      {(const void *)trace_jones_kernel<uint32_t, false, true, false>,
-       (const void *)trace_jones_kernel<uint32_t, false, true, true>}},
-     {{(const void *)trace_jones_kernel<uint32_t, true, false, false>,
-       (const void *)trace_jones_kernel<uint32_t, true, false, true>},
-      {(const void *)trace_jones_kernel<uint32_t, true, true, false>,
-       (const void *)trace_jones_kernel<uint32_t, true, true, true>}}},
-    {{{(const void *)trace_jones_kernel<uint64_t, false, false, false>,
-       (const void *)trace_jones_kernel<uint64_t, false, false, true>},
-      {(const void *)trace_jones_kernel<uint64_t, false, true, false>,
-       (const void *)trace_jones_kernel<uint64_t, false, true, true>}},
-     {{(const void *)trace_jones_kernel<uint64_t, true, false, false>,
-       (const void *)trace_jones_kernel<uint64_t, true, false, true>},
-      {(const void *)trace_jones_kernel<uint64_t, true, true, false>,
-       (const void *)trace_jones_kernel<uint64_t, true, true, true>}}}};
-const void *const kLearnKernels[2] = {(const void *)trace_jones_learn_kernel<uint32_t>,
-                                      (const void *)trace_jones_learn_kernel<uint64_t>};
-const void *const kChainKernels[2][2] = {   // [64-bit cells][AMP]
-    {(const void *)trace_jones_chain_kernel<uint32_t, false>, (const void *)trace_jones_chain_kernel<uint32_t, true>},
-    {(const void *)trace_jones_chain_kernel<uint64_t, false>, (const void *)trace_jones_chain_kernel<uint64_t, true>}};
-const void *const kFateKernels[2][2][2] = {   // [64-bit cells][single wavelength][AMP]
-    {{(const void *)trace_jones_fate_kernel<uint32_t, false, false>, (const void *)trace_jones_fate_kernel<uint32_t, false, true>},
-     {(const void *)trace_jones_fate_kernel<uint32_t, true, false>, (const void *)trace_jones_fate_kernel<uint32_t, true, true>}},
-    {{(const void *)trace_jones_fate_kernel<uint64_t, false, false>, (const void *)trace_jones_fate_kernel<uint64_t, false, true>},
-     {(const void *)trace_jones_fate_kernel<uint64_t, true, false>, (const void *)trace_jones_fate_kernel<uint64_t, true, true>}}};
-const void *const kTimelineKernels[2] = {(const void *)trace_jones_tl_kernel<uint32_t, false, false>,
-                                         (const void *)trace_jones_tl_kernel<uint32_t, true, false>};
+// Every trace kernel instantiation, stated once: the Jones kernels by [byte locator][64-bit cells][fused][single
+// wavelength][AMP], the debug timeline kernels (32-bit cells, full colour, no AMP) by [byte locator][fused].  The
+// occupancy queries loop over the tables and the launch indexes them, so a kernel cannot be in one and not the
+// other.  The fate-storing kernels (wgrt_trace_fate) by [byte locator][64-bit cells][single wavelength][AMP]: single
+// launches only.  (WGRT_K2 / WGRT_K4: kernel K's instantiations over two / the last two of its bool parameters.)
+#define WGRT_K2(K, C, ...) {(const void *)K<C, ##__VA_ARGS__, false>, (const void *)K<C, ##__VA_ARGS__, true>}
+#define WGRT_K4(K, C, ...) {WGRT_K2(K, C, ##__VA_ARGS__, false), WGRT_K2(K, C, ##__VA_ARGS__, true)}
+#define WGRT_K8(K, C) {WGRT_K4(K, C, false), WGRT_K4(K, C, true)}
+const void *const kJonesKernels[2][2][2][2][2] = {
+    {WGRT_K8(trace_jones_kernel, uint32_t), WGRT_K8(trace_jones_kernel, uint64_t)},
+    {WGRT_K8(trace_jones_b_kernel, uint32_t), WGRT_K8(trace_jones_b_kernel, uint64_t)}};
+const void *const kLearnKernels[2][2] = {   // [byte locator][64-bit cells]
+    {(const void *)trace_jones_learn_kernel<uint32_t>, (const void *)trace_jones_learn_kernel<uint64_t>},
+    {(const void *)trace_jones_b_learn_kernel<uint32_t>, (const void *)trace_jones_b_learn_kernel<uint64_t>}};
+const void *const kChainKernels[2][2][2] = {   // [byte locator][64-bit cells][AMP]
+    {WGRT_K2(trace_jones_chain_kernel, uint32_t), WGRT_K2(trace_jones_chain_kernel, uint64_t)},
+    {WGRT_K2(trace_jones_b_chain_kernel, uint32_t), WGRT_K2(trace_jones_b_chain_kernel, uint64_t)}};
+const void *const kFateKernels[2][2][2][2] = {   // [byte locator][64-bit cells][single wavelength][AMP]
+    {WGRT_K4(trace_jones_fate_kernel, uint32_t), WGRT_K4(trace_jones_fate_kernel, uint64_t)},
+    {WGRT_K4(trace_jones_b_fate_kernel, uint32_t), WGRT_K4(trace_jones_b_fate_kernel, uint64_t)}};
+const void *const kTimelineKernels[2][2] = {   // [byte locator][fused]
+    {(const void *)trace_jones_tl_kernel<uint32_t, false, false>, (const void *)trace_jones_tl_kernel<uint32_t, true, false>},
+    {(const void *)trace_jones_b_tl_kernel<uint32_t, false, false>,
+     (const void *)trace_jones_b_tl_kernel<uint32_t, true, false>}};
+#undef WGRT_K8
+#undef WGRT_K4
+#undef WGRT_K2
 
 }  // namespace
 
@@ -1063,24 +1099,27 @@ wgrt_status query_trace_grids(wgrt_scene *s) {
         out = std::max(1, cus * std::max(1, per_cu));
         return e;
     };
-    for (int c = 0; c < 2; ++c)
-        for (int f = 0; f < 2; ++f)
+    // (each locator form from its own instantiations: a launch takes the grid of the kernel it runs)
+    for (int b = 0; b < 2; ++b) {
+        for (int c = 0; c < 2; ++c)
+            for (int f = 0; f < 2; ++f)
+                for (int g = 0; g < 2; ++g) {
+                    int plain = 0, amp = 0;
+                    HIP_TRY(grid_of(kJonesKernels[b][c][f][g][0], plain));
+                    HIP_TRY(grid_of(kJonesKernels[b][c][f][g][1], amp));
+                    s->jones_grid[b][c][f][g] = std::min(plain, amp);
+                }
+        // the fate instantiations: never more workgroups than the plain launch of the same kind gets
+        for (int c = 0; c < 2; ++c)
             for (int g = 0; g < 2; ++g) {
                 int plain = 0, amp = 0;
-                HIP_TRY(grid_of(kJonesKernels[c][f][g][0], plain));
-                HIP_TRY(grid_of(kJonesKernels[c][f][g][1], amp));
-                s->jones_grid[c][f][g] = std::min(plain, amp);
+                HIP_TRY(grid_of(kFateKernels[b][c][g][0], plain));
+                HIP_TRY(grid_of(kFateKernels[b][c][g][1], amp));
+                s->jones_fate_grid[b][c][g] = std::min(s->jones_grid[b][c][0][g], std::min(plain, amp));
             }
-    // the fate instantiations: never more workgroups than the plain launch of the same kind gets
-    for (int c = 0; c < 2; ++c)
-        for (int g = 0; g < 2; ++g) {
-            int plain = 0, amp = 0;
-            HIP_TRY(grid_of(kFateKernels[c][g][0], plain));
-            HIP_TRY(grid_of(kFateKernels[c][g][1], amp));
-            s->jones_fate_grid[c][g] = std::min(s->jones_grid[c][0][g], std::min(plain, amp));
-        }
-    for (int f = 0; f < 2; ++f) HIP_TRY(grid_of(kTimelineKernels[f], s->jones_tl_grid[f]));
-    for (int c = 0; c < 2; ++c) HIP_TRY(grid_of(kLearnKernels[c], s->jones_learn_grid[c]));
+        for (int f = 0; f < 2; ++f) HIP_TRY(grid_of(kTimelineKernels[b][f], s->jones_tl_grid[b][f]));
+        for (int c = 0; c < 2; ++c) HIP_TRY(grid_of(kLearnKernels[b][c], s->jones_learn_grid[b][c]));
+    }
     // A chained step's waves spin on rays that only the previous step's launch can finish, so that launch must
     // always be able to get workgroups resident while this one is.  Two steps are in flight at a time (stream order
     // on each side), so a chained grid is at most half of what the chip holds, less kChainMargin workgroups (one per
@@ -1092,16 +1131,17 @@ wgrt_status query_trace_grids(wgrt_scene *s) {
     // WGRT_JONES_BOUNDS, which is what the guide's min(API, 8, floor(800 / (ceil(sgpr / 16) * 16 + 16))) = min(API,
     // 8, 6) comes to once the VGPR budget (126 <= 128: 4 waves) is counted: 4 x 256 CUs = 1,024 resident
     // workgroups, (1,024 - 8) / 2 = 508 per chained step.
-    for (int c = 0; c < 2; ++c) {
-        int per_cu = 0;
-        for (int a = 0; a < 2; ++a) {
-            int k = 0;
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&k, kChainKernels[c][a], 256, 0));
-            per_cu = a == 0 ? k : std::min(per_cu, k);
+    for (int b = 0; b < 2; ++b)
+        for (int c = 0; c < 2; ++c) {
+            int per_cu = 0;
+            for (int a = 0; a < 2; ++a) {
+                int k = 0;
+                HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&k, kChainKernels[b][c][a], 256, 0));
+                per_cu = a == 0 ? k : std::min(per_cu, k);
+            }
+            s->jones_chain_grid[b][c] =
+                std::max(1, (cus * std::min(std::max(1, per_cu), kJonesWavesPerSimd) - kChainMargin) / 2);
         }
-        s->jones_chain_grid[c] =
-            std::max(1, (cus * std::min(std::max(1, per_cu), kJonesWavesPerSimd) - kChainMargin) / 2);
-    }
     return WGRT_OK;
 }
 
@@ -1246,7 +1286,17 @@ struct LaunchCfg {
     // never learns the tile table (plan_auto_order: no learning instantiation stores fates; the scene learns from
     // its next plain launch instead) and takes no debug timeline (validate_launch refuses it).
     uint8_t *fate = nullptr;
+    // set by validate_launch: the launch runs the byte-locator instantiation (byte_locator_applies)
+    bool byte = false;
 };
+
+// wgrt_debug_set_byte_locator: the byte locator on / off, process-wide (the same-binary A/B; default on).  A
+// launch runs the byte form when the switch is on and its scene has a byte grid (at most kPaletteMax distinct cell
+// words, and no more than the debug cap at its creation); variant 7 also needs the 32-bit palette.
+std::atomic<int> g_byte_locator{1};
+bool byte_locator_applies(const wgrt_scene *s, int variant) {
+    return g_byte_locator.load(std::memory_order_relaxed) && s->d_cells8 && (variant == 9 || (variant == 7 && s->d_palette32));
+}
 
 // wgrt_debug_set_auto_order: the automatic issue order (and its learning launches) on / off, process-wide.
 std::atomic<int> g_auto_order{1};
@@ -1351,6 +1401,7 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
     if (c.variant >= 7 && n_rays > 0xffffffffll)
         return fail(WGRT_ERR_UNSUPPORTED, "variants 7 / 9 index at most 2^32 - 1 rays per launch");
     if (c.variant == 0) c.variant = n_rays > 0xffffffffll ? 1 : (s->d_cells32 ? 7 : 9);   // auto
+    c.byte = byte_locator_applies(s, c.variant);
     c.timeline = dbg && dbg->timeline && dbg->timeline_waves > 0;
     if (c.timeline && (c.variant != 7 || single))
         return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline is built for the full-colour 32-bit-cell kernel only");
@@ -1397,11 +1448,11 @@ TraceArgs fill_args(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, 
 // grid, fewer for a single trace (grid_sqrt_k), never more than have work; c.workgroups overrides.
 int64_t launch_grid(const wgrt_scene *s, int64_t n_rays, int64_t item, const LaunchCfg &c) {
     int64_t grid = c.workgroups > 0 ? c.workgroups
-                   : c.chain_serial ? s->jones_chain_grid[c.variant == 9]
-                   : c.timeline     ? s->jones_tl_grid[c.num_iter > 1]
-                   : c.fate         ? s->jones_fate_grid[c.variant == 9][c.single]
-                   : c.learn        ? s->jones_learn_grid[c.variant == 9]
-                                    : s->jones_grid[c.variant == 9][c.num_iter > 1][c.single];
+                   : c.chain_serial ? s->jones_chain_grid[c.byte][c.variant == 9]
+                   : c.timeline     ? s->jones_tl_grid[c.byte][c.num_iter > 1]
+                   : c.fate         ? s->jones_fate_grid[c.byte][c.variant == 9][c.single]
+                   : c.learn        ? s->jones_learn_grid[c.byte][c.variant == 9]
+                                    : s->jones_grid[c.byte][c.variant == 9][c.num_iter > 1][c.single];
     // a workgroup's 4 waves need 4 work items to all have work (debug chunk_rays: smaller items)
     const int64_t useful = (n_rays + 4 * item - 1) / (4 * item);
     if (c.workgroups <= 0 && c.num_iter <= 1 && c.grid_k >= 0.0) {
@@ -1417,7 +1468,7 @@ int64_t launch_grid(const wgrt_scene *s, int64_t n_rays, int64_t item, const Lau
         if (grid > want) grid = want;
     }
     // (a chained step never fills the chip, whoever chose its grid: query_trace_grids)
-    if (c.chain_serial) grid = std::min<int64_t>(grid, s->jones_chain_grid[c.variant == 9]);
+    if (c.chain_serial) grid = std::min<int64_t>(grid, s->jones_chain_grid[c.byte][c.variant == 9]);
     return std::min(grid, useful);
 }
 
@@ -1479,15 +1530,23 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
     int jchunk = A.order ? kChunk : item;
     // the timeline kernels and variant 7 read 32-bit cell words; the amplification step only for scenes that
     // need it (wgrt_jones_lane.h, "Amplification")
+    // ... and the byte locator where the launch runs it (LaunchCfg::byte): the same view with the byte grid and the
+    // palette of the kernel's word width
     LocatorT<uint32_t> l32{};
+    ByteLocatorT<uint32_t> b32{};
+    ByteLocatorT<uint64_t> b64{};
     if (c.variant != 9) l32 = make_locator32(s);
-    const void *const kernel = c.chain_serial ? kChainKernels[c.variant == 9][s->nonunitary_blocks != 0]
-                               : c.timeline ? kTimelineKernels[num_iter > 1]
-                               : c.fate   ? kFateKernels[c.variant == 9][c.single][s->nonunitary_blocks != 0]
-                               : c.learn  ? kLearnKernels[c.variant == 9]
-                                          : kJonesKernels[c.variant == 9][num_iter > 1][c.single][s->nonunitary_blocks != 0];
+    if (c.byte && c.variant != 9) b32 = make_byte_locator(s, A.loc, s->d_palette32);
+    if (c.byte && c.variant == 9) b64 = make_byte_locator(s, A.loc, s->d_palette);
+    const bool amp = s->nonunitary_blocks != 0, wide = c.variant == 9;
+    const void *const kernel = c.chain_serial ? kChainKernels[c.byte][wide][amp]
+                               : c.timeline ? kTimelineKernels[c.byte][num_iter > 1]
+                               : c.fate   ? kFateKernels[c.byte][wide][c.single][amp]
+                               : c.learn  ? kLearnKernels[c.byte][wide]
+                                          : kJonesKernels[c.byte][wide][num_iter > 1][c.single][amp];
     uint32_t *tail = ms->d_tile_tail;   // the learning kernels' last parameter (the others take four)
-    void *args[] = {&A, c.variant == 9 ? (void *)&A.loc : (void *)&l32, &ctr, &jchunk, &tail};
+    void *const locp = c.byte ? (wide ? (void *)&b64 : (void *)&b32) : (wide ? (void *)&A.loc : (void *)&l32);
+    void *args[] = {&A, locp, &ctr, &jchunk, &tail};
     (void)hipLaunchKernel(kernel, dim3((unsigned)grid), dim3(256), args, 0, st);
     hipError_t e = hipGetLastError();   // (and clears it, as after every launch here)
     if (e == hipSuccess && dbg && dbg->fail_after_trace) {
@@ -1754,9 +1813,10 @@ wgrt_status wgrt_scene_reserve(const wgrt_scene *s, int64_t n_rays, int num_iter
     if (n_rays == 0) return WGRT_OK;
     DEVICE_SCOPE(dev_scope, s->device);
     int64_t grid = 0;
-    for (int c = 0; c < 2; ++c)
-        for (int f = 0; f < 2; ++f)
-            for (int g = 0; g < 2; ++g) grid = std::max<int64_t>(grid, s->jones_grid[c][f][g]);
+    for (int b = 0; b < 2; ++b)
+        for (int c = 0; c < 2; ++c)
+            for (int f = 0; f < 2; ++f)
+                for (int g = 0; g < 2; ++g) grid = std::max<int64_t>(grid, s->jones_grid[b][c][f][g]);
     wgrt_scene::Scratch *sc = nullptr;
     return ensure_scratch(const_cast<wgrt_scene *>(s), stream, n_rays, std::max(num_iter, 1),
                           std::min<int64_t>(grid, (n_rays + 255) / 256), &sc);
@@ -1833,7 +1893,7 @@ wgrt_status wgrt_chain_begin(const wgrt_scene *s, const wgrt_rays *rays, int64_t
     // Chained are the batches the sqrt(items) grid rule (or the caller) gives fewer workgroups.
     if (!ch->flags && n_rays) {
         const int item = (c.dbg && c.dbg->chunk_rays > 0) ? std::min(c.dbg->chunk_rays, 64) : kChunk;
-        if (launch_grid(s, n_rays, item, c) >= s->jones_grid[c.variant == 9][0][0]) ch->flags |= WGRT_CHAIN_FULL;
+        if (launch_grid(s, n_rays, item, c) >= s->jones_grid[c.byte][c.variant == 9][0][0]) ch->flags |= WGRT_CHAIN_FULL;
     }
     e = n_rays ? chain_prepare(ch) : WGRT_OK;
     if (e != WGRT_OK) {
@@ -1907,6 +1967,19 @@ wgrt_status wgrt_trace_single(const wgrt_scene *s, const wgrt_rays *rays, int64_
 
 wgrt_status wgrt_debug_set_auto_order(int on) {
     g_auto_order.store(on != 0, std::memory_order_relaxed);
+    return WGRT_OK;
+}
+
+wgrt_status wgrt_debug_set_byte_locator(int on) {
+    g_byte_locator.store(on != 0, std::memory_order_relaxed);
+    return WGRT_OK;
+}
+
+wgrt_status wgrt_debug_scene_palette(const wgrt_scene *s, int *distinct_words, int *byte_grid, int *active) {
+    if (!s) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL scene");
+    if (distinct_words) *distinct_words = s->palette_count;
+    if (byte_grid) *byte_grid = s->d_cells8 != nullptr;
+    if (active) *active = byte_locator_applies(s, s->d_cells32 ? 7 : 9);
     return WGRT_OK;
 }
 

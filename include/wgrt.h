@@ -473,6 +473,19 @@ wgrt_status wgrt_scene_classify(const wgrt_scene *scene, const double *xy, int64
 wgrt_status wgrt_locator_classify_host(const wgrt_scene_desc *desc, double cell_mm, const double *xy, int64_t n,
                                        uint64_t *out_mask);
 
+/* Host-only build of the byte locator's tables (no GPU needed; test hook; a new symbol within ABI 9, looked up
+ * by name): the locator grid of cell size cell_mm (ncx x ncy cells; grid[3]: the origin x0, y0 and the cell
+ * size in use, so that cell (ix, iy) covers [x0 + ix h, x0 + (ix + 1) h) x [y0 + iy h, ...)), the count of its distinct cell words
+ * (saturating at 2048), and -- when that count is at most 256 and at most the debug cap
+ * (wgrt_debug_set_palette_cap), i.e. when a scene of this descriptor gets a byte grid -- the palette (256
+ * words: the distinct words strictly ascending, zero past the count) and the byte grid (each cell's palette
+ * index); byte_grid says whether.  cells: the word grid itself.  Every output may be NULL; cells8 / cells hold n_cells = ncx * ncy
+ * entries (call once with both NULL to learn the size).  Without a byte grid, palette and cells8 are not
+ * written. */
+wgrt_status wgrt_locator_palette_host(const wgrt_scene_desc *desc, double cell_mm, int64_t *ncx, int64_t *ncy,
+                                      double *grid, int *distinct_words, int *byte_grid, uint64_t *palette, uint8_t *cells8,
+                                      uint64_t *cells, int64_t n_cells);
+
 /* The test / profiling hooks (certification shadow, scene copies, wave timeline, launch
  * overrides) are declared in include/wgrt_debug.h. */
 

@@ -78,7 +78,9 @@ wgrt_status wgrt_debug_shadow(const wgrt_scene *scene, const wgrt_rays *rays, in
 
 /* Copies one of a scene's device structures to host memory dst (bytes must equal its size):
  * which = 0 the locator cell words (uint64, ncx * ncy), 1 the exact lane's tiles, 2 the
- * Jones-vector tiles (doubles, tiles * tile / jtile doubles; wgrt_scene_info). */
+ * Jones-vector tiles (doubles, tiles * tile / jtile doubles; wgrt_scene_info), 3 the byte locator's
+ * byte grid (uint8, ncx * ncy), 4 its palette (uint64, 256); 3 and 4 are WGRT_ERR_UNSUPPORTED for a scene
+ * without a byte grid. */
 wgrt_status wgrt_debug_scene_copy(const wgrt_scene *scene, int which, void *dst, int64_t bytes);
 
 /* The automatic issue order of single full-colour traces (csrc/wgrt_order.h): a scene counts, per
@@ -88,6 +90,18 @@ wgrt_status wgrt_debug_scene_copy(const wgrt_scene *scene, int which, void *dst,
  * one piece of process-wide state here (for A/B timing and tests): 0 turns learning and ordering off, so
  * every launch runs as if the scene had no table; default 1. */
 wgrt_status wgrt_debug_set_auto_order(int on);
+/* The byte locator of the Jones-vector lane (csrc/wgrt_args.h ByteLocatorT): a scene whose locator grid holds
+ * at most 256 distinct cell words also keeps a byte per cell (its index into the palette of those words), and
+ * its Jones-vector launches gather that byte instead of the 4- or 8-byte word.  Results do not depend on it.
+ * Process-wide, like the switch above, for the same-binary A/B and the tests: 0 makes every launch run the
+ * word-form kernels; default 1. */
+wgrt_status wgrt_debug_set_byte_locator(int on);
+/* The most distinct cell words a scene created from now on may have and still get a byte grid (0 .. 256,
+ * larger values mean 256; default 256): a test forces the word-form fallback with it. */
+wgrt_status wgrt_debug_set_palette_cap(int cap);
+/* A scene's distinct cell words (saturating at 2048), whether it has a byte grid, and whether its launches
+ * run the byte locator now (byte grid and switch).  Each output may be NULL. */
+wgrt_status wgrt_debug_scene_palette(const wgrt_scene *scene, int *distinct_words, int *byte_grid, int *active);
 /* Copies the order the stream's last automatically ordered launch used to host memory (n must be its
  * ceil(n_rays / 64) chunks); WGRT_ERR_INVALID_ARGUMENT when the stream has built none.  Waits for the stream. */
 wgrt_status wgrt_debug_get_auto_order(const wgrt_scene *scene, void *stream, int32_t *out, int64_t n);

@@ -6,7 +6,10 @@ With --merge PMC_JSON the issue-side roofline of this build is also recorded the
   valu_busy_frac = SQ_ACTIVE_INST_VALU x 4 / (GRBM_GUI_ACTIVE / 8 x 1024 SIMDs)   (quad-cycles;
                    GRBM_GUI_ACTIVE is summed over the 8 XCDs, MI355X_MICROARCH.md),
   lanes_active_per_valu = SQ_THREAD_CYCLES_VALU / (64 x SQ_ACTIVE_INST_VALU),
-  valu / salu / vmem wave-instructions per bounce.
+  valu / salu / vmem wave-instructions per bounce,
+  L2 requests (TCC_HIT_sum + TCC_MISS_sum), L2 misses and FETCH_SIZE / WRITE_SIZE bytes per bounce.
+A scene with a byte grid runs the byte-locator form of the kernel the bench line names (trace_jones_b_* with the
+same template arguments, csrc/wgrt_trace.hip): either name matches.
 Usage: python tools/pmc_summary.py gpurun_out/<TAG>_pmc [OUT_JSON] [--merge profiles/pmc.json]"""
 import csv
 import glob
@@ -19,6 +22,12 @@ merge = sys.argv[sys.argv.index("--merge") + 1] if "--merge" in sys.argv else No
 if merge:
     args.remove(merge)
 root = args[0]
+
+
+def is_trace_kernel(kname, name):
+    return kname in name or kname.replace("trace_jones_", "trace_jones_b_") in name
+
+
 res, bpl, kname, line, durs = {}, None, None, None, []
 for d in sorted(glob.glob(os.path.join(root, "p*"))):
     log = open(os.path.join(d, "log.txt")).read().splitlines()
@@ -31,7 +40,7 @@ for d in sorted(glob.glob(os.path.join(root, "p*"))):
     per = {}
     for f in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
-            if kname not in row["Kernel_Name"]:
+            if not is_trace_kernel(kname, row["Kernel_Name"]):
                 continue
             per.setdefault(row["Counter_Name"], {}).setdefault(row["Dispatch_Id"], 0.0)
             per[row["Counter_Name"]][row["Dispatch_Id"]] += float(row["Counter_Value"])
@@ -40,7 +49,7 @@ for d in sorted(glob.glob(os.path.join(root, "p*"))):
     # the trace kernel's own durations in this pass (kernel trace): the clock estimate's denominator
     for f in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
-            if kname in row["Kernel_Name"]:
+            if is_trace_kernel(kname, row["Kernel_Name"]):
                 durs.append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) * 1e-9)
 out = {"kernel": kname, "bounces_per_launch": bpl, "counters_per_dispatch": res}
 g = res.get
@@ -54,6 +63,12 @@ if g("SQ_ACTIVE_INST_VALU"):
     out["lanes_active_per_valu"] = g("SQ_THREAD_CYCLES_VALU", 0) / (64 * g("SQ_ACTIVE_INST_VALU"))
 if g("TCC_HIT_sum") is not None and g("TCC_MISS_sum") is not None:
     out["l2_hit_rate"] = g("TCC_HIT_sum") / max(g("TCC_HIT_sum") + g("TCC_MISS_sum"), 1)
+    if bpl:
+        out["l2_requests_per_bounce"] = (g("TCC_HIT_sum") + g("TCC_MISS_sum")) / bpl
+        out["l2_misses_per_bounce"] = g("TCC_MISS_sum") / bpl
+for c in ("FETCH_SIZE", "WRITE_SIZE"):   # KiB (tools/pmc_traffic.py)
+    if bpl and g(c) is not None:
+        out[c.lower() + "_bytes_per_bounce"] = g(c) * 1024 / bpl
 if g("SQ_ACTIVE_INST_VALU") and g("GRBM_GUI_ACTIVE"):
     out["valu_busy_frac"] = 4 * g("SQ_ACTIVE_INST_VALU") / (g("GRBM_GUI_ACTIVE") / 8 * 1024)
 if durs:

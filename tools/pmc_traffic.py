@@ -39,7 +39,9 @@ for counter in ("FETCH_SIZE", "WRITE_SIZE"):
     vals = {}
     for f in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
-            if kname in row["Kernel_Name"] and row["Counter_Name"] == counter:
+            # (the kernel the bench line names, or its byte-locator form: tools/pmc_summary.py)
+            if (kname in row["Kernel_Name"] or kname.replace("trace_jones_", "trace_jones_b_") in row["Kernel_Name"]) \
+                    and row["Counter_Name"] == counter:
                 vals[row["Dispatch_Id"]] = vals.get(row["Dispatch_Id"], 0.0) + float(row["Counter_Value"])
     res[counter] = sum(vals.values()) / max(len(vals), 1)
     res[counter + "_dispatches"] = len(vals)
