@@ -457,6 +457,84 @@ def evaluation_from_window_sums(sums, shape, divisor, ms: int = 30, step_y: int 
     return float(out[0]), float(out[1]), float(out[2]), img
 
 
+# ---- Monte-Carlo error bars from replica window tables (engine.trace_*(replicas=B), engine.fold_replicas) ----
+def jackknife_se(loo) -> np.ndarray:
+    """The delete-a-group jackknife standard error of a statistic from its ``B`` leave-one-out values ``loo``
+    ``[B, ...]``: ``sqrt((B - 1) / B * sum_b (loo_b - mean_b loo)^2)``, over the first axis."""
+    loo = np.asarray(loo, dtype=np.float64)
+    B = loo.shape[0]
+    if B < 2:
+        raise ValueError("the jackknife needs at least two leave-one-out values")
+    d = loo - loo.mean(axis=0)
+    return np.sqrt((B - 1) / B * np.sum(d * d, axis=0))
+
+
+def _replica_tables(reps_table, shape):
+    """``reps_table`` checked against the grid ``shape``: ``(B, (L, NY, NX))``."""
+    nl, ny, nx = (int(v) for v in tuple(shape)[:3])
+    if len(reps_table.shape) != 3 or reps_table.shape[0] < 2 or reps_table.shape[1] != nl * ny * nx:
+        raise ValueError(f"replica tables of shape {tuple(reps_table.shape)} do not match [B >= 2, {nl * ny * nx}, W]")
+    return int(reps_table.shape[0]), (nl, ny, nx)
+
+
+def evaluation_error_bars(reps_table, shape, divisor, evaluate_on: str = "host", ms: int = 30, step_y: int = 8,
+                          step_x: int = 12, image="all") -> dict:
+    """The evaluation of a job traced into ``B`` replica window tables, with jackknife error bars.
+
+    ``reps_table``: ``[B, n_slabs, W]`` (a device tensor or a numpy array), replica ``b`` counted from the rays whose
+    global id is ``b`` mod ``B``; ``shape``: the grid's shape (``L, NY, NX`` are used); ``divisor``: ``R * num_iter``, as
+    for the one table.  The replicas are folded (``engine.fold_replicas``) into their sum -- the table a plain
+    windows trace leaves, bit for bit -- and the ``B`` leave-one-out tables, each of ``(B - 1) / B`` of the rays and so
+    evaluated with ``divisor * (B - 1) / B``.  Every row goes through ``evaluation_from_window_sums``, the library's one
+    statement of the colour math: ``evaluate_on="device"`` where the tables live (a device tensor; ``wgrt_eyebox_evaluate``),
+    ``"host"`` on their host copy (``wgrt_eyebox_evaluate_host``, no GPU needed), so row 0's figures are, bit for bit,
+    what ``evaluation_from_window_sums`` gives for the summed table there.  (``evaluation_from_perceive``, numpy's
+    restatement, differs from both in the last place; the jackknife does not see that.)  Only row 0's image is made
+    (``image`` as ``evaluation_from_window_sums``).
+
+    Returns ``delta_e``, ``U_fov``, ``U_EB`` (row 0's: what the one table gives), ``delta_e_se``, ``U_fov_se``,
+    ``U_EB_se`` (``jackknife_se`` of the leave-one-out values), ``jackknife`` (those values, ``[B, 3]``), ``image`` and
+    ``table`` (row 0).  The efficiencies are means over rays, for which the delete-a-group jackknife is the textbook
+    estimator (``efficiency_error_bars`` gives the same number directly); ``delta_e`` is a smooth function of such
+    means almost everywhere, for which it is a reasonable one.  ``U_fov`` and ``U_EB`` are min / max ratios: for such
+    non-smooth statistics the jackknife is known to be unreliable, and their ``_se`` is an indication of scale only.
+    With ``B | R / 2`` every tile gives every replica the same number of rays from disjoint subsets of the shared
+    origins, which is what makes the replicas exchangeable (``run(error_bars=B)`` requires it)."""
+    from .engine import fold_replicas
+    if evaluate_on not in ("host", "device"):
+        raise ValueError(f"evaluate_on must be 'host' or 'device', got {evaluate_on!r}")
+    B, _ = _replica_tables(reps_table, shape)
+    loo_div = divisor * (B - 1) / B
+    if evaluate_on == "device":
+        if not getattr(reps_table, "is_cuda", False):
+            raise ValueError("evaluate_on='device' needs the replica tables as a device tensor")
+        rows = fold_replicas(reps_table)
+    else:
+        rows = fold_replicas(reps_table.detach().cpu().numpy() if hasattr(reps_table, "detach") else reps_table)
+    ev = lambda t, d, im: evaluation_from_window_sums(t, shape, d, ms, step_y, step_x, image=im)
+    delta_e, U_fov, U_EB, img = ev(rows[0], divisor, image)
+    loo = np.array([[float(v) for v in ev(rows[1 + b], loo_div, None)[:3]] for b in range(B)], dtype=np.float64)
+    se = jackknife_se(loo)
+    return dict(delta_e=float(delta_e), U_fov=float(U_fov), U_EB=float(U_EB), delta_e_se=float(se[0]),
+                U_fov_se=float(se[1]), U_EB_se=float(se[2]), jackknife=loo, image=img, table=rows[0])
+
+
+def efficiency_error_bars(reps_table, shape, num_rays, num_iter) -> dict:
+    """Standard errors of the efficiencies from the replica tables ``[B, n_slabs, W]``: replica ``b`` alone estimates
+    ``A_b = B * table[b, :, 0] / num_rays / num_iter`` (it holds a ``B``-th of the rays), so the mean of the ``A_b`` is
+    the job's ``A`` and ``A_se = std(A_b, ddof=1) / sqrt(B)``, ``[L, NY, NX]``; the same for each wavelength's
+    ``3 * sum(A)``: ``efficiency_se`` ``[L]``.  Also returns the replica values (``A_reps`` ``[B, L, NY, NX]``,
+    ``efficiency_reps`` ``[B, L]``).  Equal to ``jackknife_se`` of the leave-one-out efficiencies: for a mean the two
+    are the same number."""
+    B, (nl, ny, nx) = _replica_tables(reps_table, shape)
+    tot = reps_table[:, :, 0]
+    tot = tot.detach().cpu().numpy() if hasattr(tot, "detach") else np.asarray(tot)
+    A = (B * tot.astype(np.float64) / num_rays / num_iter).reshape(B, nl, ny, nx)
+    eff = 3.0 * A.sum(axis=(2, 3))
+    return dict(A_se=A.std(axis=0, ddof=1) / np.sqrt(B), efficiency_se=eff.std(axis=0, ddof=1) / np.sqrt(B),
+                A_reps=A, efficiency_reps=eff)
+
+
 def evaluation_device(eb, divisor, evaluate_on: str = "host"):
     """``evaluation(eb / divisor)`` without the grid leaving the device: ``eb`` is the raw count grid
     ``[L, NY, NX, 80, 120]`` (``divisor = R * num_iter``), reduced to its window sums where it lives

@@ -29,7 +29,8 @@ EXPORTED = ("wgrt_scene_create", "wgrt_scene_create_ex", "wgrt_scene_destroy", "
             "wgrt_eyebox_evaluate_host", "wgrt_window_plan_create", "wgrt_window_plan_destroy",
             "wgrt_window_plan_width", "wgrt_trace_windows", "wgrt_window_plan_validate", "wgrt_window_table_host",
             "wgrt_chain_begin", "wgrt_chain_step", "wgrt_chain_end", "wgrt_trace_fate", "wgrt_fate_census",
-            "wgrt_fate_census_host", "wgrt_fate_col", "wgrt_fate_cols", "wgrt_fate_reason_name")
+            "wgrt_fate_census_host", "wgrt_fate_col", "wgrt_fate_cols", "wgrt_fate_reason_name", "wgrt_trace_replicas",
+            "wgrt_window_replicas_fold", "wgrt_window_replicas_fold_host")
 EXPORTED_DEBUG = ("wgrt_debug_shadow", "wgrt_debug_scene_copy", "wgrt_debug_set_auto_order",
                   "wgrt_debug_get_auto_order", "wgrt_debug_get_tile_tail", "wgrt_debug_order_host",
                   "wgrt_debug_chain_plan", "wgrt_debug_chain_set_serial", "wgrt_debug_set_byte_locator",
@@ -286,6 +287,13 @@ def load():
         L.wgrt_fate_cols.argtypes = []
         L.wgrt_fate_reason_name.restype = ctypes.c_char_p
         L.wgrt_fate_reason_name.argtypes = [ctypes.c_int]
+    if hasattr(L, "wgrt_trace_replicas"):   # replica window tables and their fold: new symbols within ABI 9, by name
+        L.wgrt_trace_replicas.restype = st
+        L.wgrt_trace_replicas.argtypes = L.wgrt_trace_opts.argtypes + [_vp, _vp, ctypes.c_int]
+        L.wgrt_window_replicas_fold.restype = st
+        L.wgrt_window_replicas_fold.argtypes = [_vp, ctypes.c_int32, ctypes.c_int64, _vp, _vp]
+        L.wgrt_window_replicas_fold_host.restype = st
+        L.wgrt_window_replicas_fold_host.argtypes = [_vp, ctypes.c_int32, ctypes.c_int64, _vp]
     if hasattr(L, "wgrt_locator_palette_host"):   # the byte locator's hooks: new symbols within ABI 9, bound by name
         L.wgrt_locator_palette_host.restype = st
         L.wgrt_locator_palette_host.argtypes = [ctypes.POINTER(SceneDesc), ctypes.c_double, _i64, _i64, _d,

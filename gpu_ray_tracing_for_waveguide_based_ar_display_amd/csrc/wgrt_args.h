@@ -120,7 +120,23 @@ struct TraceArgs {
     // code in fate[i] (0 for a ray that is not traced).  NULL: nothing is stored.  Single launches only; the
     // Jones-vector lane stores it in its FATE instantiations.  Last again, for the same reason.
     uint8_t *fate;
+    // replica window tables (wgrt_trace_replicas): with win_reps >= 2, win_table is [win_reps, n_slabs, W] and an
+    // out-coupling of the ray with global id g counts into copy g % win_reps, win_rep_stride = n_slabs * W entries
+    // apart.  0: one table.  The exact lane reads them where it bins (eyebox_bin); the Jones-vector lane carries
+    // the replica in its out-coupling queue entry (the REPS instantiations).  Single launches only.  Last again.
+    int64_t win_rep_stride;
+    int32_t win_reps;
+    int32_t pad_reps_;
 };
+
+// The replica of global ray id g >= 0 among reps (2 .. 64) copies: g % reps from 32-bit remainders (the 64-bit
+// one is a long routine; this runs where a ray out-couples).
+__device__ __forceinline__ uint32_t replica_of(int64_t g, uint32_t reps) {
+    const uint32_t hi = (uint32_t)((uint64_t)g >> 32) % reps, lo = (uint32_t)g % reps;
+    const uint32_t two32 = (0xffffffffu % reps + 1u) % reps;   // 2^32 % reps
+    return (hi * two32 + lo) % reps;                           // (< 64 * 64 + 64)
+}
+constexpr int kRepShift = 24;   // a REPS queue entry: tile index | replica << kRepShift (scenes below 2^24 tiles)
 
 // TraceArgs fields re-read from the kernarg segment where they are used (a volatile scalar load,
 // a scalar-cache hit) instead of being held in SGPRs for the whole kernel: the Jones loop keeps

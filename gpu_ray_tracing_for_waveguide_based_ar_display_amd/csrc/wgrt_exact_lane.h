@@ -114,8 +114,11 @@ __device__ __forceinline__ bool eyebox_inside(const double *T, double x, double 
     return inside_or_on_edge(x, y, T + kTileEbRect, 4);
 }
 
+// rep() gives the ray's replica (wgrt_trace_replicas): called only where a launch with replica tables bins into
+// them, so a launch without pays one wave-uniform test inside the table branch.
+template <class RepF>
 __device__ __forceinline__ bool eyebox_bin(const TraceArgs &A, const double *T, int l, int m, int n, double x,
-                                           double y) {
+                                           double y, RepF rep) {
     const double xmin = T[kTileEbRange], xmax = T[kTileEbRange + 1];
     const double ymin = T[kTileEbRange + 2], ymax = T[kTileEbRange + 3];
     const double dx = (xmax - xmin) / kEbNx, dy = (ymax - ymin) / kEbNy;
@@ -130,7 +133,8 @@ __device__ __forceinline__ bool eyebox_bin(const TraceArgs &A, const double *T, 
     if (off >= 0 && off < total) {
         if (A.eb) unsafeAtomicAdd(A.eb + off, 1.0f);
         if (A.win_table) {
-            double *const table = A.win_table;
+            double *table = A.win_table;
+            if (A.win_reps) table += (int64_t)rep() * A.win_rep_stride;
             window_visit(*A.win, off, [table](int64_t k) { unsafeAtomicAdd(table + k, 1.0); });
         }
         return true;
@@ -138,9 +142,10 @@ __device__ __forceinline__ bool eyebox_bin(const TraceArgs &A, const double *T, 
     return false;
 }
 
+template <class RepF>
 __device__ __forceinline__ bool eyebox_add(const TraceArgs &A, const double *T, int l, int m, int n, double x,
-                                           double y) {
-    return eyebox_inside(T, x, y) && eyebox_bin(A, T, l, m, n, x, y);
+                                           double y, RepF rep) {
+    return eyebox_inside(T, x, y) && eyebox_bin(A, T, l, m, n, x, y, rep);
 }
 
 // Take branch b (0 or 1) of block B in state `kind` (GRTF:872-882 and every branch body after it): cte / ctm are
@@ -287,11 +292,13 @@ __device__ __forceinline__ int interact(const TraceArgs &A, const Loc &loc, Lane
     }
 
     if (b == 2) {  // out-coupling (GRTF:1162-1171, 1231-1240)
+        // (the replica is the global id's, as the RNG fix-up's id above)
+        const auto rep = [&]() { return replica_of(ray_gid(A, L.i), (uint32_t)A.win_reps); };
         if (FATE) {
             const bool in = eyebox_inside(T, r.x, r.y);
-            if (in && eyebox_bin(A, T, L.l, L.m, L.n, r.x, r.y)) L.hit = true;
+            if (in && eyebox_bin(A, T, L.l, L.m, L.n, r.x, r.y, rep)) L.hit = true;
             L.why = fate_code(freg, in ? kFateEyebox : kFateBeside);
-        } else if (eyebox_add(A, T, L.l, L.m, L.n, r.x, r.y)) {
+        } else if (eyebox_add(A, T, L.l, L.m, L.n, r.x, r.y, rep)) {
             L.hit = true;
         }
         return kDie;

@@ -217,6 +217,57 @@ extern "C" wgrt_status wgrt_window_plan_destroy(wgrt_window_plan *plan) {
 
 extern "C" int64_t wgrt_window_plan_width(const wgrt_window_plan *plan) { return plan ? plan->host.W : -1; }
 
+// The fold of the replica window tables (wgrt_trace_replicas; include/wgrt.h): out[0] = the sum of the B tables
+// in ascending b, out[1 + b] = out[0] - reps[b].  A stream of B x n doubles read twice (the second pass out of the
+// L2) and (1 + B) x n written: one thread per V entries, V = 2 (16-B accesses) when every row starts 16-B aligned,
+// else 1.  No atomics and one order of the additions, the host twin's (wgrt_eyebox_host.cpp).
+namespace {
+
+template <int V>
+__global__ __launch_bounds__(256) void replicas_fold_kernel(const double *reps, int B, int64_t n, double *out) {
+    const int64_t k = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+    if (k >= n) return;   // (V == 2 only with n even: k + 1 < n)
+    double s[V];
+    for (int v = 0; v < V; ++v) s[v] = 0.0;
+    for (int b = 0; b < B; ++b) {
+        double r[V];
+        if (V == 2) *(double2 *)r = *(const double2 *)(reps + (int64_t)b * n + k);
+        else r[0] = reps[(int64_t)b * n + k];
+        for (int v = 0; v < V; ++v) s[v] += r[v];
+    }
+    if (V == 2) *(double2 *)(out + k) = *(const double2 *)s;
+    else out[k] = s[0];
+    for (int b = 0; b < B; ++b) {
+        double r[V];
+        if (V == 2) *(double2 *)r = *(const double2 *)(reps + (int64_t)b * n + k);
+        else r[0] = reps[(int64_t)b * n + k];
+        for (int v = 0; v < V; ++v) r[v] = s[v] - r[v];
+        if (V == 2) *(double2 *)(out + (int64_t)(1 + b) * n + k) = *(const double2 *)r;
+        else out[(int64_t)(1 + b) * n + k] = r[0];
+    }
+}
+
+}  // namespace
+
+extern "C" wgrt_status wgrt_window_replicas_fold(const double *reps, int32_t B, int64_t n, double *out, void *stream) {
+    if (B < 2 || B > WGRT_MAX_REPLICAS)
+        return fail(WGRT_ERR_INVALID_ARGUMENT, "need 2 <= B <= " + std::to_string(WGRT_MAX_REPLICAS));
+    if (n < 0) return fail(WGRT_ERR_INVALID_ARGUMENT, "need n >= 0");
+    if (n == 0) return WGRT_OK;
+    if (!reps || !out) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (((uintptr_t)reps | (uintptr_t)out) & 7) return fail(WGRT_ERR_INVALID_ARGUMENT, "reps and out must be 8-B aligned");
+    const bool vec = n % 2 == 0 && !(((uintptr_t)reps | (uintptr_t)out) & 15);
+    const int64_t threads = vec ? n / 2 : n, blocks = (threads + 255) / 256;
+    if (blocks > INT32_MAX) return fail(WGRT_ERR_INVALID_ARGUMENT, "n too large for one launch");
+    int sdev = 0;
+    HIP_TRY(stream_device(stream, &sdev));
+    DEVICE_SCOPE(dev_scope, sdev);
+    if (vec) hipLaunchKernelGGL(replicas_fold_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, reps, (int)B, n, out);
+    else hipLaunchKernelGGL(replicas_fold_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, reps, (int)B, n, out);
+    HIP_TRY(hipGetLastError());
+    return WGRT_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Eyebox collection of the strong-scaling gather (wgrt_eyebox_pack / wgrt_eyebox_assemble): row copies
 // of whole 80 x 120 slabs as 16-B loads / stores, one workgroup per (row, 1/kSlabParts of the slab).

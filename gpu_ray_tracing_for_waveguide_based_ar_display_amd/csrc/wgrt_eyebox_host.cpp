@@ -124,3 +124,19 @@ extern "C" wgrt_status wgrt_window_table_host(const float *mask, int32_t ms, int
         if (offsets[k] >= 0 && offsets[k] < total) window_visit(v, offsets[k], [table](int64_t e) { table[e] += 1.0; });
     return WGRT_OK;
 }
+
+// The fold of the replica window tables over HOST pointers: wgrt_window_replicas_fold's additions in its order.
+extern "C" wgrt_status wgrt_window_replicas_fold_host(const double *reps, int32_t B, int64_t n, double *out) {
+    if (B < 2 || B > WGRT_MAX_REPLICAS)
+        return wgrt::fail(WGRT_ERR_INVALID_ARGUMENT, "need 2 <= B <= " + std::to_string(WGRT_MAX_REPLICAS));
+    if (n < 0) return wgrt::fail(WGRT_ERR_INVALID_ARGUMENT, "need n >= 0");
+    if (n == 0) return WGRT_OK;
+    if (!reps || !out) return wgrt::fail(WGRT_ERR_INVALID_ARGUMENT, "NULL argument");
+    for (int64_t k = 0; k < n; ++k) {
+        double s = 0.0;
+        for (int b = 0; b < B; ++b) s += reps[(int64_t)b * n + k];
+        out[k] = s;
+        for (int b = 0; b < B; ++b) out[(int64_t)(1 + b) * n + k] = s - reps[(int64_t)b * n + k];
+    }
+    return WGRT_OK;
+}

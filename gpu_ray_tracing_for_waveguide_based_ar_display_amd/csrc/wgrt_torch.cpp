@@ -18,7 +18,8 @@
 // call (as _lib.load binds them), so the operator library still loads over an earlier ABI-9 build of libwgrt
 // (tools/with_lib.py), where trace keeps working and trace_windows raises.  The same holds for the chained launches'
 // entry points (wgrt_chain_*; torch.ops.wgrt.chain_begin / chain_step / chain_end, engine.TraceChain) and for
-// wgrt_trace_fate (torch.ops.wgrt.trace_fate: the launch that also stores every ray's fate code).
+// wgrt_trace_fate (torch.ops.wgrt.trace_fate: the launch that also stores every ray's fate code) and wgrt_trace_replicas
+// (torch.ops.wgrt.trace_replicas: the launch into replica window tables).
 #include <torch/library.h>
 
 #include <ATen/core/Tensor.h>
@@ -26,6 +27,7 @@
 
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <optional>
 
@@ -97,6 +99,14 @@ decltype(&wgrt_trace_fate) fate_abi() {
     return fn;
 }
 
+// wgrt_trace_replicas (replica window tables), new within ABI 9 too: looked up at the first trace_replicas call.
+decltype(&wgrt_trace_replicas) replicas_abi() {
+    static const auto fn = reinterpret_cast<decltype(&wgrt_trace_replicas)>(dlsym(RTLD_DEFAULT, "wgrt_trace_replicas"));
+    TORCH_CHECK(fn, "wgrt.trace_replicas: the loaded libwgrt.so has no wgrt_trace_replicas (a build from before the "
+                    "replica tables)");
+    return fn;
+}
+
 // All three launching operators: trace (the grid alone: plan 0, no table), trace_windows (the grid, the window
 // table of plan `plan` -- a wgrt_window_plan handle -- or both) and, with `chain`, chain_begin: the same checks and
 // records handed to wgrt_chain_begin, which launches nothing and leaves the chain's handle in *chain.
@@ -107,7 +117,7 @@ int64_t trace_core(int64_t scene, const Tensor &x, const Tensor &y, const Tensor
                    int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
                    int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
                    double grid_sqrt_k, int64_t plan, std::optional<Tensor> table, wgrt_chain **chain,
-                   std::optional<Tensor> fate = std::nullopt) {
+                   std::optional<Tensor> fate = std::nullopt, int64_t replicas = 0) {
     const wgrt_scene *s = reinterpret_cast<const wgrt_scene *>(static_cast<uintptr_t>(scene));
     TORCH_CHECK(s != nullptr, "wgrt.trace: NULL scene");
     wgrt_scene_info info{};
@@ -151,8 +161,14 @@ int64_t trace_core(int64_t scene, const Tensor &x, const Tensor &y, const Tensor
         TORCH_CHECK(W > 0, "wgrt.trace: a window table needs its plan");
         on_device(*table, "table", c);
         TORCH_CHECK(table->scalar_type() == at::kDouble, "wgrt.trace: table must be float64");
-        TORCH_CHECK(table->dim() == 2 && table->size(0) == info.tiles && table->size(1) == W,
-                    "wgrt.trace: table must have shape [", info.tiles, ", ", W, "], got ", table->sizes());
+        if (replicas >= 2) {   // trace_replicas: one table per replica (the library checks the count's range)
+            TORCH_CHECK(table->dim() == 3 && table->size(0) == replicas && table->size(1) == info.tiles && table->size(2) == W,
+                        "wgrt.trace_replicas: table must have shape [", replicas, ", ", info.tiles, ", ", W, "], got ",
+                        table->sizes());
+        } else {
+            TORCH_CHECK(table->dim() == 2 && table->size(0) == info.tiles && table->size(1) == W,
+                        "wgrt.trace: table must have shape [", info.tiles, ", ", W, "], got ", table->sizes());
+        }
         tab = table->data_ptr<double>();
     }
     wgrt_trace_stats *stp = nullptr;
@@ -195,6 +211,11 @@ int64_t trace_core(int64_t scene, const Tensor &x, const Tensor &y, const Tensor
         TORCH_CHECK(!per, "wgrt.chain_begin: a chain takes no per_ray_bounces");
         return chain_abi().begin(s, &r, n_rays, gid_offset, rng, eb, stp, hip_stream, &o, tab ? wp : nullptr, tab, chain);
     }
+    if (replicas != 0) {   // trace_replicas (0: the call is trace_windows, below)
+        TORCH_CHECK(!fate, "wgrt.trace_replicas: takes no fate");
+        return replicas_abi()(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o, tab ? wp : nullptr, tab,
+                              static_cast<int>(std::max<int64_t>(-1, std::min<int64_t>(replicas, 1 << 20))));
+    }
     if (fate) {   // trace_fate: one uint8 per ray of the batch, written by the lane that ends the ray's trace
         on_device(*fate, "fate", c);
         TORCH_CHECK(fate->scalar_type() == at::kByte, "wgrt.trace_fate: fate must be uint8");
@@ -229,6 +250,20 @@ int64_t trace_fate(int64_t scene, const Tensor &x, const Tensor &y, const Tensor
     return trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats, per_ray_bounces,
                       n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
                       gid_block_rays, debug, grid_sqrt_k, plan, table, nullptr, fate);
+}
+
+// trace_replicas: trace_windows' arguments and the replica count (wgrt_trace_replicas): table float64
+// [replicas, tiles, W] for replicas >= 2.
+int64_t trace_replicas(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
+                       const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
+                       Tensor rng_states, std::optional<Tensor> matrix_EB, std::optional<Tensor> stats,
+                       std::optional<Tensor> per_ray_bounces, int64_t n_rays, int64_t gid_offset, int64_t stream,
+                       int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
+                       int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
+                       double grid_sqrt_k, int64_t plan, std::optional<Tensor> table, int64_t replicas) {
+    return trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats, per_ray_bounces,
+                      n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
+                      gid_block_rays, debug, grid_sqrt_k, plan, table, nullptr, std::nullopt, replicas);
 }
 
 // chain_begin: trace_windows' arguments -> the chain's handle (a user-space address: positive), or the negated
@@ -296,6 +331,13 @@ TORCH_LIBRARY(wgrt, m) {
           "int workgroups, Tensor? chunk_order, int num_iter, Tensor? gid_blocks, int gid_block_rays, int debug, "
           "float grid_sqrt_k, int plan, Tensor(e!)? table, Tensor(f!) fate) -> int",
           &trace_fate);
+    // the same launch into replica window tables (wgrt_trace_replicas): table float64 [replicas, tiles, W]
+    m.def("trace_replicas(int scene, Tensor x, Tensor y, Tensor m, Tensor n, Tensor? lmd_num, Tensor te, Tensor tm, "
+          "Tensor delta_phase, Tensor(a!) rng_states, Tensor(b!)? matrix_EB, Tensor(c!)? stats, "
+          "Tensor(d!)? per_ray_bounces, int n_rays, int gid_offset, int stream, int kernel, int variant, "
+          "int workgroups, Tensor? chunk_order, int num_iter, Tensor? gid_blocks, int gid_block_rays, int debug, "
+          "float grid_sqrt_k, int plan, Tensor(e!)? table, int replicas) -> int",
+          &trace_replicas);
     m.def("chain_step(int chain) -> int", &chain_step);
     m.def("chain_end(int chain) -> int", &chain_end);
 }

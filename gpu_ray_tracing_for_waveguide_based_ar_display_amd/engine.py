@@ -53,7 +53,7 @@ def trace_fullcolor(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_E
                     per_ray_bounces: torch.Tensor | None = None, stream=None, variant: int = VARIANT_AUTO,
                     workgroups: int = 0, chunk_order: torch.Tensor | None = None, num_iter: int = 1,
                     gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
-                    grid_sqrt_k: float = 0.0, windows=None, fate: torch.Tensor | None = None) -> None:
+                    grid_sqrt_k: float = 0.0, windows=None, fate: torch.Tensor | None = None, replicas: int = 0) -> None:
     """Asynchronous launch on ``stream`` (default: torch's current stream).
 
     rays: dict of device float32 tensors keyed like the reference columns
@@ -76,13 +76,18 @@ def trace_fullcolor(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_E
     the same trace leaves); ``matrix_EB`` may then be None, and no grid is written.  fate: a uint8 device tensor
     of one byte per ray of the batch that takes every traced ray's fate code (``wgrt_trace_fate``; ``FATE_CODES``,
     0 for a ray that was skipped); single launches only (``num_iter > 1`` raises), and nothing else the launch
-    leaves changes.
+    leaves changes.  replicas: ``B``, with ``windows=(plan, table)`` and ``table`` the float64 ``[B, n_slabs, plan.W]``
+    tensor of ``plan.new_table(scene, replicas=B)``: an out-coupling of the ray with global id ``g`` counts into
+    ``table[g % B]`` (``wgrt_trace_replicas``; 2 <= B <= 64), so ``table.sum(0)`` is the table a plain windows trace
+    leaves, bit for bit, and ``fold_replicas`` / ``evaluation_error_bars`` turn the copies into jackknife error
+    bars; single launches only, not together with ``fate``; 0 or 1: no replicas.
     """
     if scene.single_lambda:
         raise ValueError("trace_fullcolor needs a full-colour scene; use trace_single for a single-wavelength one")
     _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single=False, chunk_order=chunk_order, num_iter=num_iter, gid_blocks=gid_blocks,
-           gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows, fate=fate)
+           gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows, fate=fate,
+           replicas=replicas)
 
 
 def new_stats(device) -> torch.Tensor:
@@ -125,24 +130,39 @@ def trace_single(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_EB: 
                  per_ray_bounces: torch.Tensor | None = None, stream=None, variant: int = VARIANT_AUTO,
                  workgroups: int = 0, chunk_order: torch.Tensor | None = None, num_iter: int = 1,
                  gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
-                 grid_sqrt_k: float = 0.0, windows=None, fate: torch.Tensor | None = None) -> None:
+                 grid_sqrt_k: float = 0.0, windows=None, fate: torch.Tensor | None = None, replicas: int = 0) -> None:
     """One launch of the single-wavelength kernel (``process_rays_kernel_pro``, GRTF:419-831)
     through ``wgrt_trace_single_ex``: no ``lmd_num`` column (ignored if present),
     matrix_EB [NY, NX, 80, 120], branch guard ener * efficiency > 1e-15.  The scene must be
-    a single-wavelength one (``Scene.from_geometry(..., wavelength=l)`` or 3-D LUTs).  ``windows``, ``fate``: as
-    ``trace_fullcolor``."""
+    a single-wavelength one (``Scene.from_geometry(..., wavelength=l)`` or 3-D LUTs).  ``windows``, ``fate``,
+    ``replicas``: as ``trace_fullcolor``."""
     if not scene.single_lambda:
         raise ValueError("trace_single needs a single-wavelength scene (Scene.from_geometry(..., wavelength=l))")
     _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single=True, chunk_order=chunk_order, num_iter=num_iter, gid_blocks=gid_blocks,
-           gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows, fate=fate)
+           gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows, fate=fate,
+           replicas=replicas)
+
+
+MAX_REPLICAS = 64   # WGRT_MAX_REPLICAS (include/wgrt.h)
+
+
+def _replica_count(replicas) -> int:
+    """``replicas`` as the count of replica tables: 0 for none (0, 1 or None), else 2 .. MAX_REPLICAS."""
+    B = int(replicas or 0)
+    if B in (0, 1):
+        return 0
+    if not 2 <= B <= MAX_REPLICAS:
+        raise ValueError(f"replicas must be 0, 1 or 2 .. {MAX_REPLICAS}, got {B}")
+    return B
 
 
 class WindowPlan:
     """The plan of the trace's window-table sink (``wgrt_window_plan``): a binary pupil ``mask`` (default
     ``pupil_mask()``) and the eye-position steps (8 / 12), uploaded to ``device`` once.  ``W = 1 + npy * npx``
     is the table's width (57 by default); ``new_table(scene)`` a zeroed float64 ``[n_slabs, W]`` table on the
-    scene's device, in the layout of ``eyebox_window_sums``.  A mask with a tap other than 0 or 1 raises
+    scene's device, in the layout of ``eyebox_window_sums``; ``new_table(scene, replicas=B)`` the zeroed
+    ``[B, n_slabs, W]`` replica tables of ``trace_*(replicas=B)``.  A mask with a tap other than 0 or 1 raises
     (``eyebox_window_sums`` serves it from a grid)."""
 
     def __init__(self, mask=None, step_y: int = 8, step_x: int = 12, device: int = 0):
@@ -163,11 +183,13 @@ class WindowPlan:
             raise WgrtError("window plan destroyed")
         return self._h
 
-    def new_table(self, scene: Scene) -> torch.Tensor:
+    def new_table(self, scene: Scene, replicas: int = 0) -> torch.Tensor:
         if scene.device != self.device:
             raise ValueError(f"the plan is on device {self.device}, the scene on device {scene.device}")
         n_slabs = scene.num_lmd * scene.ny * scene.nx
-        return torch.zeros((n_slabs, self.W), dtype=torch.float64, device=torch.device("cuda", scene.device))
+        B = _replica_count(replicas)
+        return torch.zeros(((B,) if B else ()) + (n_slabs, self.W), dtype=torch.float64,
+                           device=torch.device("cuda", scene.device))
 
     def close(self):
         if getattr(self, "_h", None) is not None:
@@ -222,8 +244,9 @@ def _read_columns(rays, rng_states, n_rays, single, device):
 
 def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single, chunk_order=None, num_iter=1, gid_blocks=None, gid_block_rays=0, debug=None,
-           grid_sqrt_k=0.0, windows=None, chain=False, fate=None):
+           grid_sqrt_k=0.0, windows=None, chain=False, fate=None, replicas=0):
     device = torch.device("cuda", scene.device)
+    B = _replica_count(replicas)
     cols, N = _read_columns(rays, rng_states, n_rays, single, device)
     x = cols["x"]
     if matrix_EB is None and windows is None:
@@ -235,7 +258,7 @@ def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ra
     if windows is not None:
         plan, table = windows
         _as_dev(table, torch.float64, "windows table", device)
-        want = (scene.num_lmd * scene.ny * scene.nx, plan.W)
+        want = ((B,) if B else ()) + (scene.num_lmd * scene.ny * scene.nx, plan.W)
         if tuple(table.shape) != want:
             raise ValueError(f"windows table shape {tuple(table.shape)} != {want}")
     if stats is not None:
@@ -248,6 +271,15 @@ def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ra
         _as_dev(fate, torch.uint8, "fate", device, x.numel())
         if int(num_iter) > 1:
             raise ValueError("fate needs num_iter == 1: a fused launch stores no per-trace fates")
+    if B:
+        if windows is None:
+            raise ValueError("replicas need windows=(plan, table): a grid has no replicas")
+        if int(num_iter) > 1:
+            raise ValueError("replicas need num_iter == 1: replica tables are filled by single launches")
+        if fate is not None:
+            raise ValueError("a launch stores fates or fills replica tables, not both")
+        if chain:
+            raise ValueError("a chain takes no replicas")
     n_chunks = (N + CHUNK - 1) // CHUNK
     if chunk_order is not None:
         _as_dev(chunk_order, torch.int32, "chunk_order", device, n_chunks)
@@ -276,6 +308,8 @@ def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ra
     if fate is not None:   # torch.ops.wgrt.trace_fate -> wgrt_trace_fate (plan 0, no table: the grid alone)
         status = ops().trace_fate(*args, plan.handle.value if windows is not None else 0,
                                   table if windows is not None else None, fate)
+    elif windows is not None and int(replicas or 0):   # torch.ops.wgrt.trace_replicas -> wgrt_trace_replicas (1: one table)
+        status = ops().trace_replicas(*args, plan.handle.value, table, B or 1)
     elif windows is None:
         status = ops().trace(*args)
     else:
@@ -303,9 +337,11 @@ class TraceChain:
                  gid_offset: int = 0, n_rays: int | None = None, stats: torch.Tensor | None = None, stream=None,
                  variant: int = VARIANT_AUTO, workgroups: int = 0, chunk_order: torch.Tensor | None = None,
                  gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
-                 grid_sqrt_k: float = 0.0, windows=None):
+                 grid_sqrt_k: float = 0.0, windows=None, replicas: int = 0):
         if scene.single_lambda:
             raise ValueError("TraceChain needs a full-colour scene")
+        if _replica_count(replicas):
+            raise ValueError("a chain takes no replicas: trace replica tables with single launches")
         self._h = 0
         self._step = ops().chain_step
         self._h, self._keep = _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, None, stream,
@@ -342,6 +378,35 @@ class TraceChain:
             self.end()
         except Exception:
             pass
+
+
+def fold_replicas(table, stream=None):
+    """The fold of replica window tables ``[B, n_slabs, W]`` (``trace_*(replicas=B)``): ``[1 + B, n_slabs, W]`` whose row
+    0 is the sum of the replicas in ascending order -- the table a plain windows trace leaves -- and whose row
+    ``1 + b`` is row 0 less replica ``b``, the leave-one-out tables of the jackknife.  A device tensor is folded on
+    the device (``wgrt_window_replicas_fold``, asynchronous on ``stream``), a numpy array on the host
+    (``wgrt_window_replicas_fold_host``, no GPU needed); both give the same bits."""
+    L = load()
+    if isinstance(table, torch.Tensor):
+        if table.dtype != torch.float64 or table.dim() != 3 or not table.is_contiguous():
+            raise ValueError("replica tables must be a contiguous float64 [B, n_slabs, W] tensor")
+        B = _replica_count(table.shape[0])
+        if not B:
+            raise ValueError(f"need 2 .. {MAX_REPLICAS} replicas, got {table.shape[0]}")
+        out = torch.empty((1 + B,) + tuple(table.shape[1:]), dtype=torch.float64, device=table.device)
+        with torch.cuda.device(table.device):
+            check(L.wgrt_window_replicas_fold(ctypes.c_void_p(table.data_ptr()), B, table[0].numel(),
+                                              ctypes.c_void_p(out.data_ptr()),
+                                              ctypes.c_void_p(_stream_handle(table.device, stream))),
+                  "wgrt_window_replicas_fold")
+        return out
+    t = np.ascontiguousarray(table, dtype=np.float64)
+    if t.ndim != 3:
+        raise ValueError("replica tables must have shape [B, n_slabs, W]")
+    out = np.empty((1 + t.shape[0],) + t.shape[1:], dtype=np.float64)
+    check(L.wgrt_window_replicas_fold_host(t.ctypes.data, t.shape[0], t[0].size, out.ctypes.data),
+          "wgrt_window_replicas_fold_host")
+    return out
 
 
 # ---- where every ray ends: fate codes, their census and the loss budget (csrc/wgrt_fate.h states the code) ----
@@ -621,6 +686,6 @@ def selftest_math(a: torch.Tensor, b: torch.Tensor, stream=None) -> torch.Tensor
     return out
 
 
-__all__ = ["Scene", "WindowPlan", "TraceChain", "fate_census", "fate_census_host", "fate_col", "loss_budget", "FATE_CLASSES", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
+__all__ = ["Scene", "WindowPlan", "TraceChain", "fold_replicas", "MAX_REPLICAS", "fate_census", "fate_census_host", "fate_col", "loss_budget", "FATE_CLASSES", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
            "trace_fullcolor", "trace_single", "init_rays", "schedule_by_lifetime",
            "rays_to_device", "classify_points", "shadow", "selftest_math", "RAY_COLUMNS", "_lib"]

@@ -21,6 +21,8 @@ Same flow as the reference script, on the MI355X kernel:
    (``wgrt_trace_windows``), with no grid allocated at all;
    with ``budget=True`` (``--budget``) every launch also stores each ray's fate code, a census counts them per
    tile, and the loss budget -- where the rays that did not reach the eyebox went -- is printed per wavelength;
+   with ``error_bars=B`` (``--error-bars B``, windows mode) the trace counts into ``B`` replica tables by ray id and
+   every printed figure carries a jackknife standard error;
 6. the "Eyebox Center View.png" export (MAIN:199-203): the evaluated image at the first eye row,
    last eye column, as 8-bit RGB, rows flipped (``eyebox_center_view``, written without OpenCV).
 
@@ -53,7 +55,7 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
         point_seed: int | None = None, evaluate: bool = True, verbose: bool = True, variant: int = 0,
         fuse: bool | None = None, points: np.ndarray | None = None, png: str | None = None,
         eyebox: str = "host", keep_grid: bool = False, evaluate_on: str = "host",
-        keep_image: bool = False, budget: bool = False) -> dict:
+        keep_image: bool = False, budget: bool = False, error_bars: int = 0) -> dict:
     """The reference script's job on this engine; returns its printed quantities and arrays.
     ``points``: the R/2 in-coupler origins to use (default: sampled, GRTF:12-23, seeded by
     ``point_seed``); ``png``: where to write the "Eyebox Center View" image (needs ``evaluate``).
@@ -86,7 +88,35 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
     into one ``[n_slabs, 56]`` table; several GPUs census their shards and sum-reduce the tables to rank 0.  Returned
     as ``fate_census`` (the int64 table) and ``loss_budget`` (``engine.loss_budget``) and printed per wavelength
     after the efficiencies.  Works with every ``eyebox`` mode; everything else returned is bit-identical to
-    ``budget=False`` (separate launches give the fused call's results)."""
+    ``budget=False`` (separate launches give the fused call's results).
+
+    ``error_bars``: ``B`` (2 .. 64; 0: none): Monte-Carlo standard errors of everything printed, from one job.  The
+    trace counts the out-couplings of the ray with global id ``g`` into copy ``g % B`` of the window table
+    (``engine.trace_fullcolor(replicas=B)``), the copies are folded into their sum and the ``B`` leave-one-out tables
+    (``engine.fold_replicas``), and the metrics are jackknifed over them (``evaluation_error_bars``,
+    ``efficiency_error_bars``).  A grid has no replicas, so it needs ``eyebox="windows"``; and it needs ``B | R / 2``:
+    the TE ray and the TM ray of one origin then fall into the same replica, and every tile gives every replica the
+    same number of rays, drawn from disjoint subsets of the ``R / 2`` origins all tiles share -- rays are not
+    independent across tiles, and replicas by origin carry that dependence into the error bar.  Anything else raises
+    ``ValueError`` before any GPU work, as does ``budget=True`` with it.  The traces go as plain single launches (only
+    a single launch fills replica tables).  The result gains ``efficiency_se`` (per colour), ``A_se``, ``delta_e_se``,
+    ``U_fov_se``, ``U_EB_se`` and ``jackknife`` (the leave-one-out figures ``[B, 3]``), and ``+-`` is printed beside each
+    figure; everything returned before is bit-identical with and without it.  ``U_fov`` and ``U_EB`` are min / max
+    ratios, for which the jackknife is an indication only.  Memory: 10.3 MB per replica at the default job (22,500
+    slabs x 57 x 8 B), 205 MB at ``B = 20``, against the grid's 864 MB."""
+    error_bars = int(error_bars or 0)
+    if error_bars:
+        if not 2 <= error_bars <= 64:
+            raise ValueError(f"error_bars must be 0 or 2 .. 64 replicas, got {error_bars}")
+        if eyebox != "windows":
+            raise ValueError("error_bars counts into replica window tables: it needs eyebox='windows' (a grid has no "
+                             "replicas)")
+        if budget:
+            raise ValueError("error_bars and budget=True exclude each other: a launch stores fates or fills replica "
+                             "tables, not both")
+        if int(num_rays_per_FoV) % 2 or (int(num_rays_per_FoV) // 2) % error_bars:
+            raise ValueError(f"error_bars={error_bars} must divide num_rays_per_FoV / 2 = {int(num_rays_per_FoV) / 2:g}: the "
+                             "replicas are then disjoint subsets of the origins every tile shares")
     if eyebox not in ("host", "device", "windows"):
         raise ValueError(f"eyebox must be 'host', 'device' or 'windows', got {eyebox!r}")
     if evaluate_on not in ("host", "device"):
@@ -98,20 +128,24 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
         raise ValueError("eyebox='windows' traces without a grid: there is none to keep (keep_grid=True)")
     from .engine import STAT
     with _set_up(num_FOV_x, num_FOV_y, int(num_rays_per_FoV), num_iter, lambdas, lut_dir, lut_seed, lut_profile,
-                 point_seed, points, verbose, eyebox == "windows", budget) as job:   # closes the scene on every way out
+                 point_seed, points, verbose, eyebox == "windows", budget, error_bars) as job:   # closes the scene on every way out
         kern_s = _trace(job, variant, fuse)
         t_post = time.perf_counter()   # everything below is post-processing of the traced grid
         grid, table, stats = _collect(job, eyebox != "host", keep_grid)
+        reps = None
+        if job.replicas and job.rank == 0:   # the replica tables -> their sum (the one table, bit for bit) + leave-one-outs
+            from .engine import fold_replicas
+            reps, table = table, fold_replicas(table)[0]
         out = dict(num_rays=job.num_rays, num_iter=num_iter, gpu_seconds=kern_s, bounces=int(stats[STAT.bounces]),
                    eyebox_hits=int(stats[STAT.eyebox_hits]), rng_states=job.rng.cpu().numpy().view(np.uint32))
         census = _census(job)
         if job.rank != 0:
             return out
-        _report(job, out, grid, table)
+        _report(job, out, grid, table, reps)
         if census is not None:
             _report_budget(job, out, census)
         if evaluate:
-            _evaluate(job, out, grid, table, evaluate_on, keep_image, png)
+            _evaluate(job, out, grid, table, evaluate_on, keep_image, png, reps)
         out["post_seconds"] = time.perf_counter() - t_post
         job.say(f"Post-processing time  : {out['post_seconds']:.4f} s  (eyebox reduced "
                 f"{'by the trace' if eyebox == 'windows' else 'on the ' + eyebox})")
@@ -120,11 +154,12 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
 
 @contextlib.contextmanager
 def _set_up(nx, ny, R, num_iter, lambdas, lut_dir, lut_seed, lut_profile, point_seed, points, verbose,
-            windows: bool = False, budget: bool = False):
+            windows: bool = False, budget: bool = False, replicas: int = 0):
     """Steps 1-3: geometry, LUTs, the scene, the origins (rank 0's on every rank), every rank's shard and this
     rank's rays, as the record the later stages read; the scene is closed when the ``with`` block ends.
     ``windows``: a zeroed window table (``job.windows = (plan, table)``) instead of the grid (``job.eb`` None).
-    ``budget``: a fate buffer of a byte per ray of the shard and a zeroed census table (``job.fate``, ``job.census``)."""
+    ``budget``: a fate buffer of a byte per ray of the shard and a zeroed census table (``job.fate``, ``job.census``).
+    ``replicas``: the table is the zeroed ``[replicas, n_slabs, W]`` replica tables (``job.replicas``)."""
     import torch
     import torch.distributed as dist
 
@@ -171,8 +206,9 @@ def _set_up(nx, ny, R, num_iter, lambdas, lut_dir, lut_seed, lut_profile, point_
         try:
             yield SimpleNamespace(nx=nx, ny=ny, R=R, num_iter=num_iter, lambdas=lambdas, world=world, rank=rank,
                                   dev=dev, say=say, scene=scene, shards=shards, shard=shards[rank], rays=rays, rng=rng,
-                                  eb=eb, windows=(plan, plan.new_table(scene)) if windows else None,
-                                  stats=new_stats(dev), num_rays=num_rays, fate=fate, census=census)
+                                  eb=eb, windows=(plan, plan.new_table(scene, replicas=replicas)) if windows else None,
+                                  stats=new_stats(dev), num_rays=num_rays, fate=fate, census=census,
+                                  replicas=replicas)
         finally:
             if plan is not None:
                 plan.close()
@@ -181,7 +217,8 @@ def _set_up(nx, ny, R, num_iter, lambdas, lut_dir, lut_seed, lut_profile, point_
 def _trace(job, variant, fuse) -> float:
     """Step 4, the num_iter chained launches of MAIN:169-177; fuse: as one call (wgrt_launch_opts.num_iter, one
     persistent launch for the Jones-vector variants), with identical results.  With the job's fate buffer
-    (``budget``): plain single launches, each followed by its census.  Returns their seconds by HIP events."""
+    (``budget``): plain single launches, each followed by its census; with replica tables (``error_bars``): plain
+    single launches too.  Returns their seconds by HIP events."""
     import torch
 
     from .distributed import hip_tracer, run_steps, split_calls
@@ -192,13 +229,15 @@ def _trace(job, variant, fuse) -> float:
     if job.fate is not None:   # the budget: a launch's fates are counted before the next launch overwrites them
         per_call = 1
         hook = lambda j, when: when == "end" and fate_census(job.scene, job.rays, job.fate, table=job.census)
+    if job.replicas:   # only a single launch fills replica tables; the tracer offers no chain
+        per_call = 1
     calls = split_calls(job.num_iter, per_call)
     if n_rays and calls:
         reserve(job.scene, n_rays, max(calls))
     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0.record()
     if n_rays:
-        run_steps(hip_tracer(job.scene, variant, job.stats, job.windows, fate=job.fate), job.rays, job.rng, job.eb,
+        run_steps(hip_tracer(job.scene, variant, job.stats, job.windows, fate=job.fate, replicas=job.replicas), job.rays, job.rng, job.eb,
                   job.shard.gid, job.num_iter, per_call, hook=hook)
     t1.record()
     torch.cuda.synchronize()
@@ -209,7 +248,8 @@ def _trace(job, variant, fuse) -> float:
 def _collect(job, on_device: bool, keep_grid: bool):
     """The ranks' results brought together, ``(grid, table, stats)``: the whole job's eyebox grid on the host
     (rank 0, in host mode or with ``keep_grid``; else None), device mode's ``[n_slabs, 57]`` window sums of that
-    grid as a device tensor (rank 0's is the job's; else None), and the job's counters on the host."""
+    grid as a device tensor (rank 0's is the job's; else None), and the job's counters on the host.  With replica
+    tables the table is all of them, ``[B, n_slabs, 57]``: replicas are by global ray id, so the ranks' tables add."""
     import torch.distributed as dist
 
     from .AR_system_evaluation_functions import eyebox_window_sums
@@ -255,9 +295,10 @@ def _report_budget(job, out: dict, census) -> None:
         job.say(f"  {name:18s}" + "".join(f"{v * 100:9.3f}%" for v in row))
 
 
-def _report(job, out: dict, grid, table) -> None:
+def _report(job, out: dict, grid, table, reps=None) -> None:
     """Step 5's efficiencies, into ``out`` and printed: ``A`` from the host grid, or from the table's slab totals
-    -- integer counts: below 2^24 the float32 cast is the value np.sum gives on the host."""
+    -- integer counts: below 2^24 the float32 cast is the value np.sum gives on the host.  ``reps``: the replica
+    tables ``table`` is the sum of: their standard errors (``efficiency_error_bars``) too."""
     num_rays, num_iter, kern_s = job.num_rays, job.num_iter, out["gpu_seconds"]
     if table is not None:
         A = table[:, 0].cpu().numpy().reshape(job.scene.eb_shape()[:-2]).astype(np.float32) / num_rays / num_iter
@@ -265,24 +306,36 @@ def _report(job, out: dict, grid, table) -> None:
         A = np.sum(grid, axis=(-2, -1)) / num_rays / num_iter
     names = {0: "Blue", 1: "Green", 2: "Red"}
     eff = {names.get(k, str(k)): float(np.sum(A[k] * 3)) for k in range(A.shape[0])}
+    eff_se = None
+    if reps is not None:
+        from .AR_system_evaluation_functions import efficiency_error_bars
+        bars = efficiency_error_bars(reps, job.scene.eb_shape(), num_rays, num_iter)
+        eff_se = {names.get(k, str(k)): float(v) for k, v in enumerate(bars["efficiency_se"])}
+        out.update(A_se=bars["A_se"], efficiency_se=eff_se)
     job.say("Simulation finished.")
     job.say(f"Number of rays traced : {num_rays * num_iter:,}")
     job.say(f"GPU calculation time  : {kern_s:.4f} s  ({out['bounces'] / max(kern_s, 1e-12):.3e} ray-bounces/s)")
     for c in ("Red", "Green", "Blue"):
         if c in eff:
-            job.say(f"Efficiency ({c:5s})    : {eff[c] * 100:8.3f} %")
+            job.say(f"Efficiency ({c:5s})    : {eff[c] * 100:8.3f} %" +
+                    (f"  +- {eff_se[c] * 100:.3f}" if eff_se is not None else ""))
     out.update(A=A, efficiency=eff)
     if grid is not None:
         out["matrix_EB"] = grid
 
 
-def _evaluate(job, out: dict, grid, table, evaluate_on: str, keep_image: bool, png) -> None:
+def _evaluate(job, out: dict, grid, table, evaluate_on: str, keep_image: bool, png, reps=None) -> None:
     """Steps 5-6, into ``out`` and printed: the evaluation -- of the table where it lives, of the table's host
-    copy, or of the host grid (MAIN:197-198) -- then the centre view and its PNG."""
-    from .AR_system_evaluation_functions import (evaluation, evaluation_from_perceive, evaluation_from_window_sums,
-                                                 perceive_from_window_sums)
+    copy, or of the host grid (MAIN:197-198) -- then the centre view and its PNG.  ``reps``: the replica tables
+    ``table`` is the sum of: the leave-one-out tables are evaluated as well and jackknifed (``evaluation_error_bars``)."""
+    from .AR_system_evaluation_functions import (evaluation, evaluation_error_bars, evaluation_from_perceive,
+                                                 evaluation_from_window_sums, perceive_from_window_sums)
     shape, divisor = job.scene.eb_shape(), job.R * job.num_iter
     whole = evaluate_on == "host" or keep_image   # ``image``: every eye position's, else the centre one alone
+    se = None
+    if reps is not None:   # the figures themselves come from ``table`` below, exactly as without error bars
+        se = evaluation_error_bars(reps, shape, divisor, evaluate_on, image=None)
+        out.update(delta_e_se=se["delta_e_se"], U_fov_se=se["U_fov_se"], U_EB_se=se["U_EB_se"], jackknife=se["jackknife"])
     if evaluate_on == "device":
         *figures, image = evaluation_from_window_sums(table, shape, divisor, image="all" if whole else "center")
     elif table is not None:
@@ -297,9 +350,10 @@ def _evaluate(job, out: dict, grid, table, evaluate_on: str, keep_image: bool, p
     if png:
         write_png(png, out["center_view"])
         job.say(f"Wrote {png}")
-    job.say(f"Color dispersion      : {delta_e:8.2f}")
-    job.say(f"FoV uniformity        : {U_fov * 100:8.2f} %")
-    job.say(f"Eyebox uniformity     : {U_EB * 100:8.2f} %")
+    pm = (lambda k, scale: f"  +- {se[k] * scale:.2f}") if se is not None else (lambda k, scale: "")
+    job.say(f"Color dispersion      : {delta_e:8.2f}" + pm("delta_e_se", 1))
+    job.say(f"FoV uniformity        : {U_fov * 100:8.2f} %" + pm("U_fov_se", 100))
+    job.say(f"Eyebox uniformity     : {U_EB * 100:8.2f} %" + pm("U_EB_se", 100))
 
 
 def eyebox_center_view(output_image: np.ndarray) -> np.ndarray:
@@ -376,6 +430,9 @@ def main(argv=None):
     ap.add_argument("--budget", action="store_true",
                     help="also report where every ray ended: per-ray fates, their per-tile census and the loss budget "
                          "per wavelength (the traces then run as plain single launches)")
+    ap.add_argument("--error-bars", type=int, default=0, metavar="B",
+                    help="Monte-Carlo standard errors of every printed figure from B replica window tables filled by ray "
+                         "id and jackknifed (needs --eyebox windows and B dividing rays-per-fov / 2)")
     ap.add_argument("--json", default=None, help="write scalar results here")
     ap.add_argument("--png", default="Eyebox Center View.png",
                     help="the eyebox-center image (MAIN:199-203); empty string: do not write it")
@@ -389,7 +446,7 @@ def main(argv=None):
     res = run(a.num_fov_x, a.num_fov_y, a.rays_per_fov, a.num_iter, lut_dir=a.lut_dir, lut_seed=a.lut_seed,
               lut_profile=a.lut_profile, point_seed=a.point_seed, evaluate=not a.no_eval,
               fuse=False if a.no_fuse else {"auto": None, "yes": True, "no": False}[a.fuse],
-              png=a.png or None, eyebox=a.eyebox, evaluate_on=a.evaluate, budget=a.budget)
+              png=a.png or None, eyebox=a.eyebox, evaluate_on=a.evaluate, budget=a.budget, error_bars=a.error_bars)
     if a.json and (not dist.is_initialized() or dist.get_rank() == 0):
         keep = {k: v for k, v in res.items() if isinstance(v, (int, float, dict, str))}
         with open(a.json, "w") as f:

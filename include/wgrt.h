@@ -452,6 +452,44 @@ int32_t wgrt_fate_col(int code);
 int32_t wgrt_fate_cols(void);   /* WGRT_FATE_COLS of the library */
 const char *wgrt_fate_reason_name(int reason);
 
+/* Monte-Carlo error bars: replica window tables and their fold (new symbols within ABI 9, looked up by name).
+ *
+ * wgrt_trace_replicas is wgrt_trace_windows plus replicas = B: table becomes a DEVICE float64 [B, n_slabs, W]
+ * (B copies of the table of wgrt_trace_windows, one after the other), ADDED to and never zeroed, and an
+ * out-coupling of the ray with global id g -- gid_offset + i, or the id opts->gid_blocks gives ray i -- counts into
+ * copy g % B, through the membership rule above: the slab still comes from the aliased offset, and an offset
+ * outside the buffer is still dropped.  The counts are integers, so the B copies add up, bit for bit, to the table
+ * wgrt_trace_windows leaves; with matrix_EB also given the grid gets the same hits as ever; rng_states and stats
+ * do not depend on replicas.  Because the replica is the global id's, the tables of the shards of one batch add up
+ * to the whole batch's tables.
+ *   replicas 0 or 1     exactly wgrt_trace_windows (table [n_slabs, W], or NULL);
+ *   2 <= replicas <= WGRT_MAX_REPLICAS   table required, else WGRT_ERR_INVALID_ARGUMENT;
+ *   anything else       WGRT_ERR_INVALID_ARGUMENT.
+ * A replica launch is a single launch, as a fate launch is: opts->num_iter > 1 is WGRT_ERR_INVALID_ARGUMENT (trace
+ * the iterations one call each), wgrt_chain_begin takes no replicas, and there is no entry point that takes both
+ * replicas and fates.  It runs kernel instantiations of its own (variants 7 / 9), which have no learning and no
+ * timeline twin: a replica launch never learns the scene's tile table (the next plain launch does; results do not
+ * depend on the order), and replicas with wgrt_debug_opts.timeline is WGRT_ERR_UNSUPPORTED.  Those kernels carry
+ * the replica in the top byte of their out-coupling queue entry, so variants 7 / 9 refuse a scene of 2^24 tiles or
+ * more with WGRT_ERR_UNSUPPORTED (variant 1 has no such limit).  The call allocates nothing and is asynchronous on
+ * stream.  A launch without replicas runs the kernels it ran before this entry point existed. */
+#define WGRT_MAX_REPLICAS 64
+wgrt_status wgrt_trace_replicas(const wgrt_scene *scene, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
+                                uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats,
+                                uint32_t *per_ray_bounces, void *stream, const wgrt_launch_opts *opts,
+                                const wgrt_window_plan *plan, double *table, int replicas);
+
+/* The fold: from reps, DEVICE float64 [B, n] (n = n_slabs * W entries per replica), out, DEVICE float64
+ * [1 + B, n]:  out[0] = sum over b of reps[b], added in ascending b from 0.0;  out[1 + b] = out[0] - reps[b], the
+ * leave-one-out tables of the delete-a-group jackknife.  One thread per entry pair, a fixed order and no atomics:
+ * the same input gives the same bits, and integer counts come out as exact integers.  Every row of out is a table
+ * wgrt_eyebox_evaluate takes unchanged: row 0 with the divisor rays-per-tile * launches, a leave-one-out row with
+ * that times (B - 1) / B.  2 <= B <= WGRT_MAX_REPLICAS and n >= 0, else WGRT_ERR_INVALID_ARGUMENT; n == 0 is
+ * WGRT_OK without a launch; reps and out must not overlap.  Asynchronous on stream, allocates nothing.  The _host
+ * twin is the same loop over HOST pointers (no GPU needed). */
+wgrt_status wgrt_window_replicas_fold(const double *reps, int32_t B, int64_t n, double *out, void *stream);
+wgrt_status wgrt_window_replicas_fold_host(const double *reps, int32_t B, int64_t n, double *out);
+
 /* Host-only (no GPU needed; test hooks) through the same membership code (csrc/wgrt_window.h):
  * _validate is wgrt_window_plan_create's argument check alone; _table_host ADDS the n hits at flat grid
  * offsets offsets[n] (HOST int64; those outside [0, n_slabs * 9600) are dropped, as the grid's guard drops

@@ -1,0 +1,453 @@
+"""Replica window tables on the GPU (``wgrt_trace_replicas`` through ``torch.ops.wgrt.trace_replicas``), their fold
+(``wgrt_window_replicas_fold``) and the driver's ``run(error_bars=B)``.
+
+The expected replica tables come from the CPU oracle: rays are independent and their state travels in
+``rng_states``, so replica ``b`` of a batch whose global ids start at 0 is what the sub-batch ``rays[b::B]``,
+``rng[b::B]`` leaves -- ``eyebox_window_sums`` of the grid ``OracleScene.trace`` fills from it.
+
+Tolerance: none; every comparison is of bytes."""
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+from gpu_ray_tracing_for_waveguide_based_ar_display_amd import AR_system_evaluation_functions as E  # noqa: E402
+from gpu_ray_tracing_for_waveguide_based_ar_display_amd import _lib  # noqa: E402
+from gpu_ray_tracing_for_waveguide_based_ar_display_amd._lib import STAT  # noqa: E402
+from tests._fixtures import GoldenCase  # noqa: E402
+from tests.test_gpu_parity import _config  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+FIXTURES = ["c1_rgb", "h6_edge_rgb", "s1_532"]
+# the oracle's hits per replica (B = 4, four launches): no replica is empty
+HITS4 = {"c1_rgb": [41, 35, 40, 40], "h6_edge_rgb": [37, 22, 29, 29], "s1_532": [9, 6, 11, 7]}
+_C2S = dict(nx=11, ny=11, lambdas=[1], R=64)             # 7,744 rays: more than replay_tail's 256 threads
+_SMALL = dict(nx=5, ny=4, lambdas=[0, 1, 2], R=100)      # 6,000 rays
+_SMALL_AMP = dict(_SMALL, profile="adversarial_polarizing", seed=3)
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("no HIP device")
+    return torch.device("cuda", 0)
+
+
+@pytest.fixture(autouse=True)
+def _switches():
+    yield
+    _lib.set_byte_locator(True)
+
+
+_cases, _oracle = {}, {}
+
+
+def _case(name):
+    if name not in _cases:
+        _cases[name] = GoldenCase(name) if name in FIXTURES else _config(**{"c2s": _C2S, "small": _SMALL,
+                                                                           "small_amp": _SMALL_AMP}[name])
+    return _cases[name]
+
+
+def oracle_replicas(name, B, launches):
+    """(tables [B, n_slabs, 57], rng after, grid) of case ``name`` from the oracle, replica b from rays b::B.
+    Computed once per (case, B, launches) and shared."""
+    key = (name, B, launches)
+    if key not in _oracle:
+        from oracle import OracleScene
+        c = _case(name)
+        sc = OracleScene.from_geometry(c.geom, c.luts, wavelength=getattr(c, "wavelength", None))
+        rng_after = np.empty(c.N, np.uint32)
+        tables, total = [], np.zeros(c.eb_shape(), np.float32)
+        for b in range(B):
+            rays = {k: np.ascontiguousarray(v[b::B]) for k, v in c.rays.items()}
+            rng = np.ascontiguousarray(c.fresh_rng()[b::B])
+            eb = np.zeros(c.eb_shape(), np.float32)
+            for _ in range(launches):
+                sc.trace(rays, rng, eb)
+            rng_after[b::B] = rng
+            tables.append(E.eyebox_window_sums(eb))
+            total += eb
+        t = np.stack(tables)
+        t.setflags(write=False)
+        _oracle[key] = (t, rng_after, total)
+    return _oracle[key]
+
+
+def _trace(c, dev, B, launches=1, variant=0, grid=False, rays=None, rng=None, table=None, scene=None, plan=None, **kw):
+    """``launches`` single launches into ``[B, n_slabs, 57]`` replica tables (``B`` 0: the one table):
+    (table, grid or None, rng states, stats) on the host."""
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import (Scene, WindowPlan, new_stats, rays_to_device,
+                                                                           trace_fullcolor, trace_single)
+    wl = getattr(c, "wavelength", None)
+    own = scene is None
+    if own:
+        scene = Scene.from_geometry(c.geom, c.luts, wavelength=wl)
+        plan = WindowPlan()
+    trace = trace_single if wl is not None else trace_fullcolor
+    if table is None:
+        table = plan.new_table(scene, replicas=B)
+    rays = rays_to_device(c.rays, dev) if rays is None else rays
+    rng = torch.from_numpy(c.fresh_rng().view(np.int32)).to(dev) if rng is None else rng
+    eb = torch.zeros(c.eb_shape(), dtype=torch.float32, device=dev) if grid else None
+    stats = new_stats(dev)
+    for _ in range(launches):
+        trace(scene, rays, rng, eb, stats=stats, variant=variant, windows=(plan, table), replicas=B, **kw)
+    torch.cuda.synchronize()
+    out = (table.cpu().numpy(), eb.cpu().numpy() if grid else None, rng.cpu().numpy().view(np.uint32).copy(),
+           stats.cpu().numpy().copy())
+    if own:
+        plan.close()
+        scene.close()
+    return out
+
+
+# 1. the fixtures, every variant, four separate launches --------------------------------------------------------
+
+@pytest.mark.parametrize("variant", [1, 7, 9])
+@pytest.mark.parametrize("name", FIXTURES)
+def test_fixtures_equal_the_oracles_replicas(dev, name, variant):
+    c = _case(name)
+    want, _, _ = oracle_replicas(name, 4, 4)
+    table, _, rng, stats = _trace(c, dev, 4, launches=4, variant=variant)
+    assert table.shape == (4, want.shape[1], 57) and table.dtype == np.float64
+    for b in range(4):
+        assert table[b].tobytes() == want[b].tobytes(), f"replica {b}"
+        assert table[b, :, 0].sum() == HITS4[name][b] > 0
+    assert table.sum(0).tobytes() == E.eyebox_window_sums(c.eb_expected(4)).tobytes()
+    np.testing.assert_array_equal(rng, c.f["rng_after4"])
+    # the counters of a plain windows trace
+    _, _, rng0, stats0 = _trace(c, dev, 0, launches=4, variant=variant)
+    np.testing.assert_array_equal(stats, stats0)
+    np.testing.assert_array_equal(rng, rng0)
+    assert int(stats[STAT.eyebox_hits]) == sum(HITS4[name]) and int(stats[STAT.bad_rays]) == 0
+
+
+@pytest.mark.parametrize("variant", [1, 7])
+def test_the_grid_beside_the_replicas(dev, variant):
+    c = _case("c1_rgb")
+    want, _, _ = oracle_replicas("c1_rgb", 4, 4)
+    table, eb, rng, _ = _trace(c, dev, 4, launches=4, variant=variant, grid=True)
+    np.testing.assert_array_equal(eb, c.eb_expected(4))
+    assert table.tobytes() == want.tobytes()
+    np.testing.assert_array_equal(rng, c.f["rng_after4"])
+
+
+# 2. the replica is the global id's ------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("variant", [1, 7])
+def test_replica_of_the_global_id_not_the_local_index(dev, variant):
+    """c1_rgb split at ray 37 (37 % 4 != 0): rays [0, 37) with gid_offset 0, then [37, N) with gid_offset 37, into
+    one table -- the single call's table.  A sink that took the local index would shift the second part's replicas."""
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import Scene, WindowPlan, rays_to_device
+    c = _case("c1_rgb")
+    want, rng_want, _ = oracle_replicas("c1_rgb", 4, 1)
+    scene, plan = Scene.from_geometry(c.geom, c.luts), WindowPlan()
+    table = plan.new_table(scene, replicas=4)
+    full = rays_to_device(c.rays, dev)
+    rng_all = torch.from_numpy(c.fresh_rng().view(np.int32)).to(dev)
+    got_rng = []
+    for lo, hi in ((0, 37), (37, c.N)):
+        rays = {k: v[lo:hi].contiguous() for k, v in full.items()}
+        rng = rng_all[lo:hi].contiguous()
+        _, _, r, _ = _trace(c, dev, 4, variant=variant, rays=rays, rng=rng, table=table, scene=scene, plan=plan,
+                            gid_offset=lo)
+        got_rng.append(r)
+    got = table.cpu().numpy()
+    plan.close()
+    scene.close()
+    assert got.tobytes() == want.tobytes()
+    np.testing.assert_array_equal(np.concatenate(got_rng), rng_want)
+    np.testing.assert_array_equal(rng_want, c.f["rng_after1"])
+    assert all(got[b, :, 0].sum() > 0 for b in range(4))
+
+
+def test_two_gid_blocks_shards_add_up(dev):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.distributed import make_shard
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import init_rays
+    c = _case("c1_rgb")
+    want, _, _ = oracle_replicas("c1_rgb", 4, 1)
+    parts = []
+    for r in range(2):
+        shard = make_shard(c.nx, c.ny, len(c.lambdas), c.R, 2, r)
+        rays, rng = init_rays(c.f["points"], c.nx, c.ny, c.lambdas, c.R, block_list=shard.blocks, device=dev)
+        gb = torch.from_numpy(shard.gid.block_gid).to(dev)
+        t, _, _, _ = _trace(c, dev, 4, variant=7, rays=rays, rng=rng, n_rays=rng.numel(), gid_blocks=gb,
+                            gid_block_rays=c.R)
+        assert t.sum() > 0
+        parts.append(t)
+    assert (parts[0] + parts[1]).tobytes() == want.tobytes()
+
+
+# 3. / 4. the exact lane in replay_tail; small work items ----------------------------------------------------------
+
+def test_forced_replay(dev):
+    """No decision certified (as test_gpu_window_sink.test_forced_replay): every hit is binned by replay_tail's exact
+    lane, which reads the replica count from the launch arguments."""
+    c = _case("c2s")
+    want, rng_want, _ = oracle_replicas("c2s", 8, 1)
+    hits = [int(want[b, :, 0].sum()) for b in range(8)]
+    assert hits == [15, 24, 15, 19, 13, 22, 12, 17]
+    table, _, rng, stats = _trace(c, dev, 8, variant=7, debug=dict(cert_tol=1e3, cert_tol32=1e3))
+    traced = c.N - int(stats[STAT.bad_rays])
+    assert int(stats[STAT.replayed]) == traced > 256
+    np.testing.assert_array_equal(rng, rng_want)
+    assert table.tobytes() == want.tobytes()
+    assert int(stats[STAT.eyebox_hits]) == sum(hits)
+
+
+def test_small_work_items(dev):
+    """chunk_rays 13 on two workgroups: waves fill and chain several queue blocks whose entries carry mixed replicas."""
+    c = _case("small")
+    want, rng_want, _ = oracle_replicas("small", 10, 1)
+    hits = [int(want[b, :, 0].sum()) for b in range(10)]
+    assert min(hits) >= 6 and max(hits) <= 23
+    table, _, rng, stats = _trace(c, dev, 10, variant=7, workgroups=2, debug=dict(chunk_rays=13))
+    np.testing.assert_array_equal(rng, rng_want)
+    assert table.tobytes() == want.tobytes()
+    assert int(stats[STAT.eyebox_hits]) == sum(hits)
+
+
+# 5. both locator forms; the AMP instantiation ---------------------------------------------------------------------
+
+@pytest.mark.parametrize("variant", [7, 9])
+def test_byte_and_word_locator(dev, variant):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import Scene
+    c = _case("small")
+    want, rng_want, _ = oracle_replicas("small", 10, 1)
+    sc = Scene.from_geometry(c.geom, c.luts)
+    assert sc.palette_info()["byte_grid"]   # (the scene has a byte grid: the default runs the byte form)
+    sc.close()
+    got = {}
+    for byte in (True, False):
+        _lib.set_byte_locator(byte)
+        got[byte] = _trace(c, dev, 10, variant=variant)
+    _lib.set_byte_locator(True)
+    assert got[True][0].tobytes() == got[False][0].tobytes() == want.tobytes()
+    np.testing.assert_array_equal(got[True][2], got[False][2])
+    np.testing.assert_array_equal(got[True][2], rng_want)
+    np.testing.assert_array_equal(got[True][3], got[False][3])
+
+
+def test_amp_profile(dev):
+    """Non-unitary LUTs: the launch runs the REPS + AMP kernel.  This profile rarely reaches the eyebox (9 hits in 32
+    launches of the 6,000 rays, in 5 of the 10 replicas), hence the 32 launches."""
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import Scene
+    c = _case("small_amp")
+    sc = Scene.from_geometry(c.geom, c.luts)
+    assert sc.info()["nonunitary_blocks"] > 0
+    sc.close()
+    want, rng_want, _ = oracle_replicas("small_amp", 10, 32)
+    hits = [int(want[b, :, 0].sum()) for b in range(10)]
+    assert sum(hits) == 9 and sum(h > 0 for h in hits) == 5
+    table, _, rng, stats = _trace(c, dev, 10, launches=32, variant=7)
+    np.testing.assert_array_equal(rng, rng_want)
+    assert table.tobytes() == want.tobytes()
+    assert int(stats[STAT.eyebox_hits]) == 9
+
+
+# 6. argument errors -------------------------------------------------------------------------------------------------
+
+def test_argument_errors(dev):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import (Scene, TraceChain, WindowPlan, rays_to_device,
+                                                                           trace_fullcolor)
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd._lib import WgrtError, ops
+    c = _case("c1_rgb")
+    scene, plan = Scene.from_geometry(c.geom, c.luts), WindowPlan()
+    rays = rays_to_device(c.rays, dev)
+    rng = torch.from_numpy(c.fresh_rng().view(np.int32)).to(dev)
+    before = rng.clone()
+    good = plan.new_table(scene, replicas=4)
+    assert good.shape == (4, 27, 57) and good.dtype == torch.float64 and not good.any()
+    go = lambda **kw: trace_fullcolor(scene, rays, rng, None, variant=7, **kw)
+    with pytest.raises(ValueError, match="num_iter"):
+        go(windows=(plan, good), replicas=4, num_iter=2)
+    with pytest.raises(ValueError, match="fate"):
+        go(windows=(plan, good), replicas=4, fate=torch.zeros(c.N, dtype=torch.uint8, device=dev))
+    with pytest.raises(ValueError, match="replicas"):
+        go(windows=(plan, torch.zeros((65, 27, 57), dtype=torch.float64, device=dev)), replicas=65)
+    with pytest.raises(ValueError, match="shape"):
+        go(windows=(plan, good[:3]), replicas=4)
+    with pytest.raises(ValueError, match="shape"):
+        go(windows=(plan, good[0]), replicas=4)
+    with pytest.raises(TypeError):
+        go(windows=(plan, good.to(torch.float32)), replicas=4)
+    with pytest.raises(ValueError, match="is on"):
+        go(windows=(plan, good.cpu()), replicas=4)
+    with pytest.raises(ValueError, match="windows"):
+        trace_fullcolor(scene, rays, rng, torch.zeros(c.eb_shape(), dtype=torch.float32, device=dev), replicas=4)
+    with pytest.raises(ValueError, match="chain"):
+        TraceChain(scene, rays, rng, None, windows=(plan, good), replicas=4)
+    with pytest.raises(ValueError, match="replicas"):
+        plan.new_table(scene, replicas=65)
+
+    # the operator and the C entry point themselves
+    def op(table, B, num_iter=1, debug=0):
+        return ops().trace_replicas(scene.handle.value, rays["x"], rays["y"], rays["m"], rays["n"], rays["lmd_num"],
+                                    rays["te"], rays["tm"], rays["delta_phase"], rng, None, None, None, c.N, 0, 0, 0, 7,
+                                    0, None, num_iter, None, 0, debug, 0.0, plan.handle.value, table, B)
+    with pytest.raises(RuntimeError, match="shape"):
+        op(good[:3], 4)
+    with pytest.raises(RuntimeError, match="float64"):
+        op(good.to(torch.float32), 4)
+    with pytest.raises(RuntimeError, match="must be on"):
+        op(good.cpu(), 4)
+    assert op(good, 4, num_iter=2) == 1                                                    # WGRT_ERR_INVALID_ARGUMENT
+    assert op(torch.zeros((65, 27, 57), dtype=torch.float64, device=dev), 65) == 1
+    assert op(plan.new_table(scene), -2) == 1
+    with pytest.raises(WgrtError, match="invalid argument"):
+        _lib.check(op(good, 4, num_iter=2), "wgrt_trace_replicas")
+    torch.cuda.synchronize()
+    assert torch.equal(rng, before) and not good.any()   # nothing was launched
+    plan.close()
+    scene.close()
+
+
+@pytest.mark.parametrize("variant", [1, 7])
+def test_one_replica_is_trace_windows(dev, variant):
+    c = _case("c1_rgb")
+    one = _trace(c, dev, 1, variant=variant)      # replicas=1, an [n_slabs, W] table: through wgrt_trace_replicas
+    plain = _trace(c, dev, 0, variant=variant)    # trace_windows
+    assert one[0].shape == (27, 57) and one[0].tobytes() == plain[0].tobytes()
+    assert one[0].tobytes() == E.eyebox_window_sums(c.eb_expected(1)).tobytes()
+    np.testing.assert_array_equal(one[2], plain[2])
+    np.testing.assert_array_equal(one[3], plain[3])
+
+
+# 7. the fold on the device ------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("n_slabs, W", [(1, 3 * 57 + 1), (27, 57), (3, 58)])   # odd n; n = 27 * 57 (odd); even n
+@pytest.mark.parametrize("B", [2, 5, 64])
+def test_fold_on_the_device_equals_the_host_twin(dev, B, n_slabs, W):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import fold_replicas
+    rng = np.random.default_rng(B + W)
+    for t in (rng.integers(0, 1 << 20, (B, n_slabs, W)).astype(np.float64),
+              rng.standard_normal((B, n_slabs, W)) * 10.0 ** rng.integers(-8, 9, (B, n_slabs, W))):
+        want = fold_replicas(t)
+        got = fold_replicas(torch.from_numpy(t).to(dev))
+        torch.cuda.synchronize()
+        assert got.shape == want.shape and got.cpu().numpy().tobytes() == want.tobytes()
+    L = _lib.load()
+    d = torch.zeros((3, 8), dtype=torch.float64, device=dev)
+    for bad in (1, 65):
+        assert L.wgrt_window_replicas_fold(d.data_ptr(), bad, 8, d.data_ptr(), None) == 1
+    assert L.wgrt_window_replicas_fold(None, 4, 0, None, None) == 0
+
+
+# 8. the driver --------------------------------------------------------------------------------------------------------
+# the small job of tests/test_gpu_window_sink.py ("deep" LUT profile); R / 2 = 128 = 4 * 32
+
+NX, NY, R, STEPS, B = 5, 4, 256, 2, 4
+FIGURES = ("delta_e", "U_fov", "U_EB")
+SE = ("delta_e_se", "U_fov_se", "U_EB_se")
+_runs = {}
+
+
+def _run(evaluate_on, error_bars, **kw):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.gpu_ray_tracing_pro_fullColor import run
+    from tests import _dist
+    pts = _dist.small_job(NX, NY, R, 3, 6, "deep")[2]
+    return run(NX, NY, R, STEPS, lut_seed=3, lut_profile="deep", points=pts, verbose=False, eyebox="windows",
+               evaluate_on=evaluate_on, error_bars=error_bars, **kw)
+
+
+def _run_once(evaluate_on, error_bars):
+    if (evaluate_on, error_bars) not in _runs:
+        _runs[(evaluate_on, error_bars)] = _run(evaluate_on, error_bars)
+    return _runs[(evaluate_on, error_bars)]
+
+
+def _direct_replicas(dev):
+    """The job's replica tables from a direct trace: the driver's batch, STEPS single launches."""
+    if "direct" not in _runs:
+        from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import Scene, WindowPlan, init_rays, trace_fullcolor
+        from tests import _dist
+        geom, luts, pts = _dist.small_job(NX, NY, R, 3, 6, "deep")
+        scene, plan = Scene.from_geometry(geom, luts), WindowPlan()
+        rays, rng = init_rays(pts, NX, NY, (0, 1, 2), R, device=dev, all_columns=False)
+        table = plan.new_table(scene, replicas=B)
+        for _ in range(STEPS):
+            trace_fullcolor(scene, rays, rng, None, windows=(plan, table), replicas=B)
+        torch.cuda.synchronize()
+        _runs["direct"] = (table.cpu().numpy(), scene.eb_shape())
+        plan.close()
+        scene.close()
+    return _runs["direct"]
+
+
+def _same_job(got, want):
+    assert got["A"].dtype == want["A"].dtype and got["A"].tobytes() == want["A"].tobytes()
+    assert got["efficiency"] == want["efficiency"] and got["num_rays"] == want["num_rays"]
+    assert got["bounces"] == want["bounces"] > 0 and got["eyebox_hits"] == want["eyebox_hits"] > 0
+    for k in FIGURES:   # compared as bits
+        assert float(got[k]).hex() == float(want[k]).hex(), k
+
+
+def _check_bars(got, dev, evaluate_on):
+    reps, shape = _direct_replicas(dev)
+    num_rays = NX * NY * 3 * R
+    eff = E.efficiency_error_bars(reps, shape, num_rays, STEPS)
+    assert got["A_se"].tobytes() == eff["A_se"].tobytes()
+    names = {0: "Blue", 1: "Green", 2: "Red"}
+    assert got["efficiency_se"] == {names[k]: float(v) for k, v in enumerate(eff["efficiency_se"])}
+    assert all(v > 0 for v in got["efficiency_se"].values())
+    ev = E.evaluation_error_bars(torch.from_numpy(reps).to(dev) if evaluate_on == "device" else reps, shape,
+                                 R * STEPS, evaluate_on, image=None)
+    assert got["jackknife"].shape == (B, 3) and got["jackknife"].tobytes() == ev["jackknife"].tobytes()
+    for k in SE:
+        assert float(got[k]).hex() == float(ev[k]).hex() and np.isfinite(got[k]) and got[k] >= 0, k
+    assert got["delta_e_se"] > 0
+
+
+@pytest.mark.parametrize("evaluate_on", ["host", "device"])
+def test_driver_error_bars_change_nothing_else(dev, evaluate_on):
+    got, want = _run_once(evaluate_on, B), _run_once(evaluate_on, 0)
+    _same_job(got, want)
+    np.testing.assert_array_equal(got["rng_states"], want["rng_states"])
+    np.testing.assert_array_equal(got["center_view"], want["center_view"])
+    assert not any(k in want for k in SE + ("efficiency_se", "A_se", "jackknife"))
+    _check_bars(got, dev, evaluate_on)
+
+
+def _driver_worker(rank, world, outdir):
+    import json
+    torch.cuda.set_device(torch.device("cuda", 0))
+    res = _run("device", B)
+    np.save(f"{outdir}/rng{rank}.npy", res["rng_states"])
+    if rank != 0:
+        assert "A" not in res and "delta_e" not in res and "jackknife" not in res
+        return
+    np.save(f"{outdir}/A.npy", res["A"])
+    np.save(f"{outdir}/A_se.npy", res["A_se"])
+    np.save(f"{outdir}/jackknife.npy", res["jackknife"])
+    with open(f"{outdir}/res.json", "w") as f:
+        json.dump(dict({k: res[k] for k in ("efficiency", "efficiency_se", "bounces", "eyebox_hits", "num_rays")},
+                       **{k: float(res[k]).hex() for k in FIGURES + SE}), f)
+
+
+def test_driver_error_bars_in_two_ranks(dev, tmp_path):
+    """Two ranks on the one GPU over gloo: replicas are by global ray id, so the ranks' replica tables add, and rank
+    0's figures and standard errors are the single-process run's."""
+    import json
+
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.distributed import make_shard
+    from tests import _dist
+    world = 2
+    _dist.spawn(_driver_worker, world, str(tmp_path))
+    one = _run_once("device", B)
+    with open(tmp_path / "res.json") as f:
+        got = json.load(f)
+    for k in ("A", "A_se", "jackknife"):
+        got[k] = np.load(tmp_path / f"{k}.npy")
+    for k in FIGURES + SE:
+        got[k] = float.fromhex(got[k])
+    _same_job(got, one)
+    assert got["A_se"].tobytes() == one["A_se"].tobytes() and got["jackknife"].tobytes() == one["jackknife"].tobytes()
+    assert got["efficiency_se"] == one["efficiency_se"]
+    for k in SE:
+        assert float(got[k]).hex() == float(one[k]).hex(), k
+    for r in range(world):
+        blocks = make_shard(NX, NY, 3, R, world, r).blocks
+        want = one["rng_states"].reshape(-1, R)[blocks].reshape(-1)
+        np.testing.assert_array_equal(np.load(tmp_path / f"rng{r}.npy"), want, err_msg=f"rank {r}")
