@@ -30,11 +30,12 @@ EXPORTED = ("wgrt_scene_create", "wgrt_scene_create_ex", "wgrt_scene_destroy", "
             "wgrt_window_plan_width", "wgrt_trace_windows", "wgrt_window_plan_validate", "wgrt_window_table_host",
             "wgrt_chain_begin", "wgrt_chain_step", "wgrt_chain_end", "wgrt_trace_fate", "wgrt_fate_census",
             "wgrt_fate_census_host", "wgrt_fate_col", "wgrt_fate_cols", "wgrt_fate_reason_name", "wgrt_trace_replicas",
-            "wgrt_window_replicas_fold", "wgrt_window_replicas_fold_host")
+            "wgrt_window_replicas_fold", "wgrt_window_replicas_fold_host", "wgrt_trace_expected",
+            "wgrt_expected_weight_host")
 EXPORTED_DEBUG = ("wgrt_debug_shadow", "wgrt_debug_scene_copy", "wgrt_debug_set_auto_order",
                   "wgrt_debug_get_auto_order", "wgrt_debug_get_tile_tail", "wgrt_debug_order_host",
                   "wgrt_debug_chain_plan", "wgrt_debug_chain_set_serial", "wgrt_debug_set_byte_locator",
-                  "wgrt_debug_set_palette_cap", "wgrt_debug_scene_palette")
+                  "wgrt_debug_set_palette_cap", "wgrt_debug_scene_palette", "wgrt_debug_expected_replays")
 
 
 class WgrtError(RuntimeError):
@@ -294,6 +295,14 @@ def load():
         L.wgrt_window_replicas_fold.argtypes = [_vp, ctypes.c_int32, ctypes.c_int64, _vp, _vp]
         L.wgrt_window_replicas_fold_host.restype = st
         L.wgrt_window_replicas_fold_host.argtypes = [_vp, ctypes.c_int32, ctypes.c_int64, _vp]
+    if hasattr(L, "wgrt_trace_expected"):   # the expected-value estimator: new symbols within ABI 9, by name
+        a = L.wgrt_trace_opts.argtypes   # (wgrt_trace_opts' arguments without matrix_EB, then plan, table, replicas)
+        L.wgrt_trace_expected.restype = st
+        L.wgrt_trace_expected.argtypes = a[:5] + a[6:] + [_vp, _vp, ctypes.c_int]
+        L.wgrt_expected_weight_host.restype = ctypes.c_double
+        L.wgrt_expected_weight_host.argtypes = [ctypes.c_double] * 7
+        L.wgrt_debug_expected_replays.restype = st
+        L.wgrt_debug_expected_replays.argtypes = [_vp, _vp, _vp, _vp, ctypes.c_int64]
     if hasattr(L, "wgrt_locator_palette_host"):   # the byte locator's hooks: new symbols within ABI 9, bound by name
         L.wgrt_locator_palette_host.restype = st
         L.wgrt_locator_palette_host.argtypes = [ctypes.POINTER(SceneDesc), ctypes.c_double, _i64, _i64, _d,

@@ -12,9 +12,16 @@
 // FATE (a template parameter of interact, advance, lane_retire and trace_one; off by default): every place a trace
 // ends sets the lane's fate code (wgrt_fate.h) and lane_retire stores it beside per_ray.  Without it the lane is
 // the code it was before fates existed -- the replays inlined into the Jones kernels keep their registers.
+// EV (a template parameter of interact and trace_one; off by default): the expected-value estimator of
+// wgrt_trace_expected (wgrt_expected.h).  Every R4 / R5 interaction inside the FoV's eyebox rectangle evaluates
+// the reference's exact efficiencies and deposits the fixed-point weight q through eyebox_deposit; the analog +1 of
+// the out-coupling itself is not added (Lane::hit still says whether it would have been).  *ev_skip, when not
+// zero, is the number of such visits whose deposit has already been made (a replay of a ray the Jones lane
+// abandoned after scoring them): they are passed over.  The walk -- draws, branches, counters -- is EV = false's.
 #pragma once
 
 #include "wgrt_args.h"
+#include "wgrt_expected.h"
 #include "wgrt_fate.h"
 #include "wgrt_locator.h"
 #include "wgrt_window.h"
@@ -116,9 +123,9 @@ __device__ __forceinline__ bool eyebox_inside(const double *T, double x, double 
 
 // rep() gives the ray's replica (wgrt_trace_replicas): called only where a launch with replica tables bins into
 // them, so a launch without pays one wave-uniform test inside the table branch.
-template <class RepF>
-__device__ __forceinline__ bool eyebox_bin(const TraceArgs &A, const double *T, int l, int m, int n, double x,
-                                           double y, RepF rep) {
+// The flat grid offset of the bin under (x, y), or -1 for one outside the buffer.
+__device__ __forceinline__ int64_t eyebox_offset(const TraceArgs &A, const double *T, int l, int m, int n, double x,
+                                                 double y) {
     const double xmin = T[kTileEbRange], xmax = T[kTileEbRange + 1];
     const double ymin = T[kTileEbRange + 2], ymax = T[kTileEbRange + 3];
     const double dx = (xmax - xmin) / kEbNx, dy = (ymax - ymin) / kEbNy;
@@ -130,7 +137,14 @@ __device__ __forceinline__ bool eyebox_bin(const TraceArgs &A, const double *T, 
     if (iy < 0) iy += kEbNy;
     const int64_t off = ((((int64_t)l * A.ny + n) * A.nx + m) * kEbNy + iy) * kEbNx + ix;
     const int64_t total = (int64_t)A.nl * A.ny * A.nx * kEbNy * kEbNx;
-    if (off >= 0 && off < total) {
+    return (off >= 0 && off < total) ? off : -1;
+}
+
+template <class RepF>
+__device__ __forceinline__ bool eyebox_bin(const TraceArgs &A, const double *T, int l, int m, int n, double x,
+                                           double y, RepF rep) {
+    const int64_t off = eyebox_offset(A, T, l, m, n, x, y);
+    if (off >= 0) {
         if (A.eb) unsafeAtomicAdd(A.eb + off, 1.0f);
         if (A.win_table) {
             double *table = A.win_table;
@@ -140,6 +154,22 @@ __device__ __forceinline__ bool eyebox_bin(const TraceArgs &A, const double *T, 
         return true;
     }
     return false;
+}
+
+// The expected-value estimator's deposit (wgrt_expected.h) of a visit at (x, y) that has passed eyebox_inside: q
+// (a multiple of 2^-32; 0: nothing) added to the window table's entries under the bin, by the same membership
+// rule.  Returns whether the bin lies in the buffer -- whether an out-coupling here is an analog hit.
+template <class RepF>
+__device__ __forceinline__ bool eyebox_deposit(const TraceArgs &A, const double *T, int l, int m, int n, double x,
+                                               double y, double q, RepF rep) {
+    const int64_t off = eyebox_offset(A, T, l, m, n, x, y);
+    if (off < 0) return false;
+    if (q > 0.0) {
+        double *table = A.win_table;
+        if (A.win_reps) table += (int64_t)rep() * A.win_rep_stride;
+        window_visit(*A.win, off, [table, q](int64_t k) { unsafeAtomicAdd(table + k, q); });
+    }
+    return true;
 }
 
 template <class RepF>
@@ -184,9 +214,9 @@ __device__ __forceinline__ int take_branch(const Loc &loc, Lane &L, const double
 // or kDie (FATE: with the lane's fate set; its region is the state the ray is in, 9 at the entry).
 // Only the chosen branch's phase (two atan2) is evaluated; its field is recomputed
 // by the same operations rather than kept in registers for every branch.
-template <bool FATE = false, class Loc>
+template <bool FATE = false, bool EV = false, class Loc>
 __device__ __forceinline__ int interact(const TraceArgs &A, const Loc &loc, Lane &L, int blk, int kind,
-                                        bool entry) {
+                                        bool entry, uint32_t *ev_skip = nullptr) {
     Ray &r = L.r;
     const double *T = L.T;
     const double *B = T + kTileHeader + kBlock * blk;
@@ -198,6 +228,9 @@ __device__ __forceinline__ int interact(const TraceArgs &A, const Loc &loc, Lane
     const double denom = entry ? T[kTileCosIc1] : r.cos_t;
     const double u = rng_draw_lazy(r.s, [&]() { return ray_gid(A, L.i); });
     const int freg = entry ? kFateEntry : r.region;   // (FATE only)
+    // EV: a scored visit.  Its weight is made of the reference's own e_k, so the decision is taken on the exact
+    // path below too (either path gives the reference's decision)
+    const bool ev_here = EV && three && eyebox_inside(T, r.x, r.y);
 
     // Decide the branch.  The reference compares u with cumulative branch efficiencies
     // e_k = (hypot(Ete')^2 + hypot(Etm')^2) * cosA_k / cos(theta) [* or / n_g].  Here the
@@ -247,7 +280,7 @@ __device__ __forceinline__ int interact(const TraceArgs &A, const Loc &loc, Lane
     const bool sure = scale > 1e-290 && !tiny && tsure && fabs(u - c0) > tol && fabs(u - c1) > tol &&
                       (!three || fabs(u - c2) > tol);
     int b;
-    if (sure) {
+    if (sure && !ev_here) {
         if (u <= c0 && pass0) b = 0;
         else if (u <= c1 && pass1) b = 1;
         else if (three && u <= c2 && pass2) b = 2;
@@ -282,6 +315,15 @@ __device__ __forceinline__ int interact(const TraceArgs &A, const Loc &loc, Lane
         if (thr)
             L.libm |= ((e0 > 0.0) & (r.ener * e0 < 0x1p-1000)) | ((e1 > 0.0) & (r.ener * e1 < 0x1p-1000)) |
                       (three & (e2 > 0.0) & (r.ener * e2 < 0x1p-1000));
+        if (EV && ev_here) {
+            if (*ev_skip) {
+                --*ev_skip;   // scored by the lane that abandoned the ray
+            } else {
+                const double q = expected_deposit(e0, e1, e2, r.ener * e0, r.ener * e1, r.ener * e2, t);
+                eyebox_deposit(A, T, L.l, L.m, L.n, r.x, r.y, q,
+                               [&]() { return replica_of(ray_gid(A, L.i), (uint32_t)A.win_reps); });
+            }
+        }
         if (u <= e0 && (!thr || r.ener * e0 > t)) b = 0;
         else if (u <= e0 + e1 && (!thr || r.ener * e1 > t)) b = 1;
         else if (three && u <= e0 + e1 + e2 && r.ener * e2 > t) b = 2;
@@ -291,6 +333,10 @@ __device__ __forceinline__ int interact(const TraceArgs &A, const Loc &loc, Lane
         }
     }
 
+    if (EV && b == 2) {   // the out-coupling scores nothing more than its visit has; hit: the analog estimator's
+        if (ev_here && eyebox_offset(A, T, L.l, L.m, L.n, r.x, r.y) >= 0) L.hit = true;
+        return kDie;
+    }
     if (b == 2) {  // out-coupling (GRTF:1162-1171, 1231-1240)
         // (the replica is the global id's, as the RNG fix-up's id above)
         const auto rep = [&]() { return replica_of(ray_gid(A, L.i), (uint32_t)A.win_reps); };
@@ -395,8 +441,10 @@ __device__ __forceinline__ void add_stats(wgrt_trace_stats *stats, Counters c) {
 // Trace ray i to termination with the reference arithmetic (variant 1's lane; replays), counted in c.  With
 // s_io, the trace starts from *s_io instead of rng_states[i] and leaves its final state there
 // (rng_states untouched).
-template <bool FATE = false>
-__device__ __forceinline__ void trace_one(const TraceArgs &A, int64_t i, Counters &c, uint32_t *s_io = nullptr) {
+// EV: with the expected-value deposits (above); ev_skip: the scored visits to pass over.
+template <bool FATE = false, bool EV = false>
+__device__ __forceinline__ void trace_one(const TraceArgs &A, int64_t i, Counters &c, uint32_t *s_io = nullptr,
+                                          uint32_t ev_skip = 0) {
     Lane L;
     if (!lane_load(A, i, L)) {
         ++c.w[kCtrBadRays];
@@ -407,7 +455,7 @@ __device__ __forceinline__ void trace_one(const TraceArgs &A, int64_t i, Counter
     int blk = 0, kind = 0;
     bool entry = true;
     for (;;) {
-        const int next = interact<FATE>(A, A.loc, L, blk, kind, entry);
+        const int next = interact<FATE, EV>(A, A.loc, L, blk, kind, entry, &ev_skip);
         if (next < 0) break;
         L.r.region = next;
         entry = false;

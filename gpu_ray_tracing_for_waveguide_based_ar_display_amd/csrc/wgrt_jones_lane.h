@@ -3,6 +3,8 @@
 #pragma once
 
 #include "wgrt_args.h"
+#include "wgrt_exact_lane.h"   // eyebox_inside: the rectangle test of a scored visit (EV)
+#include "wgrt_expected.h"
 #include "wgrt_locator.h"
 #include "wgrt_seg.h"
 
@@ -393,9 +395,15 @@ __device__ __forceinline__ float amp_step(float amp, float pa, float nmin, doubl
 // are the same values the all-double evaluation gives.
 // FATE (the fate-storing instantiations, wgrt_trace_fate): the one die that is not a Monte-Carlo loss returns
 // kDieIc, so the caller can tell fate reason 6 from 2; nothing else differs.
-template <bool SINGLE, bool AMP, bool FATE, class Loc>
+// EV (the expected-value instantiations, wgrt_trace_expected; wgrt_expected.h): a certified R4 / R5 interaction
+// whose position passes the FoV's eyebox rectangle test is a scored visit: *evq is its fixed-point weight q >= 0,
+// made of the lane's double-precision evaluation (estimate64's forms and r.ener) whatever precision the decision
+// took, and -1 anywhere else.  The caller deposits it at the position the ray had before this call -- unless
+// the call returns kUncertain, which scores nothing: the replay then scores this visit.  About 3 % of bounces
+// get here; the common pass pays the kind test alone.
+template <bool SINGLE, bool AMP, bool FATE, bool EV = false, class Loc>
 __device__ __forceinline__ int interact(const TraceArgs &A, const KArgs &K, const Loc &loc, JLane &L, int blk,
-                                        int kind, bool entry, SegAcc *sg = nullptr) {
+                                        int kind, bool entry, SegAcc *sg = nullptr, double *evq = nullptr) {
     JRay &r = L.r;
     const double *T = KA(jtiles) + (size_t)L.tix * (size_t)A.jtile_d;
     const double *B = T + kJHeader + kJBlock * blk;
@@ -432,6 +440,15 @@ __device__ __forceinline__ int interact(const TraceArgs &A, const KArgs &K, cons
     // one exit for every outcome but a taken branch; an out-coupling is appended to the
     // out-coupling queue by the caller (at (r.x, r.y))
     const int code = !d.ok ? kUncertain : d.s2 ? kOut : !(d.s0 | d.s1) ? kDie : 0;
+    if (EV) {
+        *evq = -1.0;
+        if (__builtin_expect(three & d.ok, 0) &&
+            eyebox_inside(KA(tiles) + (int64_t)L.tix * KA(tile_d), r.x, r.y)) {
+            JDecision w;
+            estimate64(w, B, r, three, inv, f01, A.inv_n_g, cw);
+            *evq = expected_deposit(w.a0, w.a1, w.a2, r.ener * w.a0, r.ener * w.a1, r.ener * w.a2, t);
+        }
+    }
     if (code != 0) return code;
     const bool ba = d.s0;
     const int b = ba ? 0 : 1;

@@ -41,6 +41,7 @@ struct wgrt_scene {
     int jones_tl_grid[2][2] = {};      // ... of the debug timeline instantiations (32-bit cells): [fused]
     int jones_fate_grid[2][2][2] = {}; // ... of the fate-storing instantiations (wgrt_trace_fate): [64-bit cells][single wavelength]
     int jones_reps_grid[2][2][2] = {}; // ... of the replica-table instantiations (wgrt_trace_replicas): the same axes
+    int jones_ev_grid[2][2][2] = {};   // ... of the expected-value instantiations (wgrt_trace_expected): the same axes
     int jones_learn_grid[2][2] = {};   // ... of the learning instantiations (full colour, single trace): [64-bit cells]
     int jones_chain_grid[2][2] = {};   // ... the most a chained step may use (wgrt_chain_*): [64-bit cells], half the
                                        // resident grid less a margin (query_trace_grids)

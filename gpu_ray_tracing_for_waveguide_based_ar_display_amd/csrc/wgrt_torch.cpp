@@ -107,6 +107,14 @@ decltype(&wgrt_trace_replicas) replicas_abi() {
     return fn;
 }
 
+// wgrt_trace_expected (the expected-value estimator), new within ABI 9 too: looked up at the first trace_expected call.
+decltype(&wgrt_trace_expected) expected_abi() {
+    static const auto fn = reinterpret_cast<decltype(&wgrt_trace_expected)>(dlsym(RTLD_DEFAULT, "wgrt_trace_expected"));
+    TORCH_CHECK(fn, "wgrt.trace_expected: the loaded libwgrt.so has no wgrt_trace_expected (a build from before the "
+                    "expected-value estimator)");
+    return fn;
+}
+
 // All three launching operators: trace (the grid alone: plan 0, no table), trace_windows (the grid, the window
 // table of plan `plan` -- a wgrt_window_plan handle -- or both) and, with `chain`, chain_begin: the same checks and
 // records handed to wgrt_chain_begin, which launches nothing and leaves the chain's handle in *chain.
@@ -117,7 +125,7 @@ int64_t trace_core(int64_t scene, const Tensor &x, const Tensor &y, const Tensor
                    int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
                    int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
                    double grid_sqrt_k, int64_t plan, std::optional<Tensor> table, wgrt_chain **chain,
-                   std::optional<Tensor> fate = std::nullopt, int64_t replicas = 0) {
+                   std::optional<Tensor> fate = std::nullopt, int64_t replicas = 0, bool expected = false) {
     const wgrt_scene *s = reinterpret_cast<const wgrt_scene *>(static_cast<uintptr_t>(scene));
     TORCH_CHECK(s != nullptr, "wgrt.trace: NULL scene");
     wgrt_scene_info info{};
@@ -211,6 +219,11 @@ int64_t trace_core(int64_t scene, const Tensor &x, const Tensor &y, const Tensor
         TORCH_CHECK(!per, "wgrt.chain_begin: a chain takes no per_ray_bounces");
         return chain_abi().begin(s, &r, n_rays, gid_offset, rng, eb, stp, hip_stream, &o, tab ? wp : nullptr, tab, chain);
     }
+    if (expected) {   // trace_expected: the window table alone (its shape checked above: [tiles, W], or one per replica)
+        TORCH_CHECK(tab && !eb && !fate, "wgrt.trace_expected: needs a window table and takes no matrix_EB or fate");
+        return expected_abi()(s, &r, n_rays, gid_offset, rng, stp, per, hip_stream, &o, wp, tab,
+                              static_cast<int>(std::max<int64_t>(-1, std::min<int64_t>(replicas, 1 << 20))));
+    }
     if (replicas != 0) {   // trace_replicas (0: the call is trace_windows, below)
         TORCH_CHECK(!fate, "wgrt.trace_replicas: takes no fate");
         return replicas_abi()(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o, tab ? wp : nullptr, tab,
@@ -264,6 +277,20 @@ int64_t trace_replicas(int64_t scene, const Tensor &x, const Tensor &y, const Te
     return trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats, per_ray_bounces,
                       n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
                       gid_block_rays, debug, grid_sqrt_k, plan, table, nullptr, std::nullopt, replicas);
+}
+
+// trace_expected: trace_replicas' arguments without the grid (wgrt_trace_expected): table float64 [tiles, W] for
+// replicas 0 / 1, [replicas, tiles, W] otherwise.
+int64_t trace_expected(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
+                       const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
+                       Tensor rng_states, std::optional<Tensor> stats, std::optional<Tensor> per_ray_bounces,
+                       int64_t n_rays, int64_t gid_offset, int64_t stream, int64_t kernel, int64_t variant,
+                       int64_t workgroups, const std::optional<Tensor> &chunk_order, int64_t num_iter,
+                       const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
+                       double grid_sqrt_k, int64_t plan, Tensor table, int64_t replicas) {
+    return trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, std::nullopt, stats, per_ray_bounces,
+                      n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
+                      gid_block_rays, debug, grid_sqrt_k, plan, table, nullptr, std::nullopt, replicas, true);
 }
 
 // chain_begin: trace_windows' arguments -> the chain's handle (a user-space address: positive), or the negated
@@ -338,6 +365,13 @@ TORCH_LIBRARY(wgrt, m) {
           "int workgroups, Tensor? chunk_order, int num_iter, Tensor? gid_blocks, int gid_block_rays, int debug, "
           "float grid_sqrt_k, int plan, Tensor(e!)? table, int replicas) -> int",
           &trace_replicas);
+    // the expected-value estimator (wgrt_trace_expected): no grid; table float64 [tiles, W] or [replicas, tiles, W]
+    m.def("trace_expected(int scene, Tensor x, Tensor y, Tensor m, Tensor n, Tensor? lmd_num, Tensor te, Tensor tm, "
+          "Tensor delta_phase, Tensor(a!) rng_states, Tensor(c!)? stats, Tensor(d!)? per_ray_bounces, int n_rays, "
+          "int gid_offset, int stream, int kernel, int variant, int workgroups, Tensor? chunk_order, int num_iter, "
+          "Tensor? gid_blocks, int gid_block_rays, int debug, float grid_sqrt_k, int plan, Tensor(e!) table, "
+          "int replicas) -> int",
+          &trace_expected);
     m.def("chain_step(int chain) -> int", &chain_step);
     m.def("chain_end(int chain) -> int", &chain_end);
 }

@@ -59,6 +59,14 @@ __global__ __launch_bounds__(256) void trace_grid_fate_kernel(TraceArgs A) {
     add_stats(A.stats, c);
 }
 
+// The same with the expected-value estimator's deposits (wgrt_trace_expected with variant 1; wgrt_expected.h).
+__global__ __launch_bounds__(256) void trace_grid_ev_kernel(TraceArgs A) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    Counters c;
+    if (i < A.n_rays) trace_one<false, true>(A, i, c);
+    add_stats(A.stats, c);
+}
+
 // A counter set of the Jones-vector variants' launch scratch, each slot on its own 128-B line: the kHeads
 // work-queue heads, then the replay count, the out-coupling queue and full-block counts, and a single
 // launch's epilogue totals (a Counters record) and done count.
@@ -127,6 +135,21 @@ __device__ __forceinline__ bool bin_entry(const TraceArgs &A, uint32_t e, int nx
     const int l = (int)(g / ((uint32_t)ny * (uint32_t)nx));
     return eyebox_add(A, A.tiles + (int64_t)((l * A.nx + m) * A.ny + n) * A.tile_d, l, m, n, x, y,
                       [e]() { return REPS ? e >> kRepShift : 0u; });
+}
+
+// One scored visit of an expected-value launch (jones_body, EV): e = tile index | replica << kRepShift | the analog
+// flag << 31 (the draw out-coupled the ray here), q its fixed-point weight (0 with the flag alone: the visit only
+// counts as the walk's hit).  The weight is a double of its own because q == 1.0 does not fit 32 fractional bits.
+// Returns whether the visit is an analog eyebox hit.
+constexpr uint32_t kEvOutBit = 1u << 31;
+static_assert(WGRT_MAX_REPLICAS <= 1 << (31 - kRepShift), "the replica lies between the tile index and the analog flag");
+__device__ __forceinline__ bool bin_visit(const TraceArgs &A, uint32_t e, int nx, int ny, double x, double y, double q) {
+    const uint32_t g = e & ((1u << kRepShift) - 1u);
+    const int n = (int)(g % (uint32_t)ny), m = (int)(g / (uint32_t)ny % (uint32_t)nx);
+    const int l = (int)(g / ((uint32_t)ny * (uint32_t)nx));
+    const bool in_buffer = eyebox_deposit(A, A.tiles + (int64_t)((l * A.nx + m) * A.ny + n) * A.tile_d, l, m, n, x, y, q,
+                                          [e]() { return (e & ~kEvOutBit) >> kRepShift; });
+    return in_buffer && (e & kEvOutBit);
 }
 
 __global__ __launch_bounds__(256) void epilogue_kernel(TraceArgs A) {
@@ -244,18 +267,34 @@ __device__ __forceinline__ void record_abandoned(const KArgs &K, uint32_t i) {
 #endif
 }
 
+// The same for an expected-value launch (jones_body, EV), whose deposits up to here have been made: the entry
+// carries the number of scored visits, which the replay passes over (trace_one's ev_skip).  An expected-value launch
+// keeps its visits in LDS and has no out-coupling queue in memory, so the counts use q_i -- sized for at least one
+// entry per ray, like the replay list -- and nothing is allocated for them.
+__device__ __forceinline__ void record_abandoned_ev(const KArgs &K, uint32_t i, uint32_t seen) {
+    const unsigned long long k = atomicAdd(KA(replay_count), 1ull);
+    __hip_atomic_store(KA(replay_list) + k, i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(KA(q_i) + k, seen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
 #if WGRT_INKERNEL_REPLAY
 // The single launch's replay inside the trace kernel (the last workgroup; finish_single): the
 // reference-arithmetic lane (trace_one) over the replay list, its TraceArgs read from the kernarg segment
 // here, so nothing of it is live across the wave loop.  Inlined: as a real call it gave the wave loop 128
 // VGPRs and scratch (above).
-template <bool FATE>
+template <bool FATE, bool EV>
 __device__ __forceinline__ void replay_tail(const KArgs &K, unsigned long long nr) {
     const TraceArgs R = K.args();
     const uint32_t *const list = KA(replay_list);
     Counters c;
-    for (unsigned long long k = threadIdx.x; k < nr; k += blockDim.x)
-        trace_one<FATE>(R, (int64_t)__hip_atomic_load(list + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), c);
+    for (unsigned long long k = threadIdx.x; k < nr; k += blockDim.x) {
+        // EV: the visits the Jones lane scored before it abandoned the ray (record_abandoned_ev)
+        uint32_t skip = 0;
+        if (EV) skip = __hip_atomic_load(KA(q_i) + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        trace_one<FATE, EV>(R, (int64_t)__hip_atomic_load(list + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), c,
+                            nullptr, skip);
+    }
     c.wave_reduce();
     if (threadIdx.x == 0) c.w[kCtrReplayed] = nr;
     if ((threadIdx.x & 63) == 0 && R.stats) c.add_to(R.stats);
@@ -294,7 +333,7 @@ __device__ __forceinline__ void finish_fused(const KArgs &K, Counters c) {
 // each per workgroup: not contended), waits for them, and counts the workgroup done; the workgroup that
 // counts last reads the totals at agent scope, adds them to *stats, zeroes the next launch's counter set
 // (every other workgroup has left this one's) and replays.
-template <bool CHAIN, bool FATE>
+template <bool CHAIN, bool FATE, bool EV>
 __device__ __forceinline__ void finish_single(const KArgs &K, Counters c) {
     __shared__ unsigned long long red[4][kCtrWords];
     __shared__ int last_wg;
@@ -324,7 +363,7 @@ __device__ __forceinline__ void finish_single(const KArgs &K, Counters c) {
     const unsigned long long nr = __hip_atomic_load(KA(replay_count), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (__builtin_expect(nr != 0ull, 0)) {
         if (CHAIN) replay_tail_chain(K, nr);
-        else replay_tail<FATE>(K, nr);
+        else replay_tail<FATE, EV>(K, nr);
     }
 #endif
 }
@@ -367,9 +406,22 @@ static_assert(sizeof(TraceArgs) % 8 == 0 && sizeof(Locator) % 8 == 0 && sizeof(L
 // push, the rare path (~10 entries per wave per trace), works out the ray's replica from its global id and
 // stores it in the queue entry's top byte, where the bin step finds it; nothing is computed at refill and nothing
 // is held across passes.  Off everywhere else, where the entry is the tile index alone.
+// EV: a single launch of the expected-value estimator (wgrt_trace_expected; wgrt_expected.h): every scored visit
+// (interact's *evq) goes, with the position the ray had at it, into the wave's own LDS block of kEvBlock visits;
+// a pass that would overfill the block bins it first (one lane per visit: bin_visit) and reuses it, and the wave
+// bins what is left when it ends -- nothing in memory grows with the bounces and no visit is dropped, whatever
+// their count.  The analog out-coupling pushes nothing of its own: it rides as a flag on its visit's entry, and
+// the hit count comes from there.  The lane counts its scored visits (ev_seen) for the replay of an abandoned ray
+// (record_abandoned_ev).  The replica is worked out at the push from TraceArgs::win_reps (0: the one table).  Off
+// everywhere else, where none of this exists.
 // Loc: the locator's form, a template axis of every instantiation: LocatorT<CellT> gathers cell words,
 // ByteLocatorT<CellT> a scene's byte grid (wgrt_args.h; the workgroup copies the palette into LDS first).
-template <bool FUSED, bool SINGLE, bool TL, bool AMP, bool LEARN, bool CHAIN, bool FATE, bool REPS, class Loc>
+constexpr int kEvBlock = 64;   // scored visits a wave holds before it bins them: a pass adds at most one per lane
+struct EvBlock {
+    double x[kEvBlock], y[kEvBlock], q[kEvBlock];
+    uint32_t e[kEvBlock];
+};
+template <bool FUSED, bool SINGLE, bool TL, bool AMP, bool LEARN, bool CHAIN, bool FATE, bool REPS, bool EV, class Loc>
 __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, const Loc &loc, unsigned long long *heads,
                                           int chunk) {
     // Single launches (!FUSED) do their epilogue in this kernel (above), and retire a finished trace at one
@@ -416,6 +468,17 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
                   "fates are stored by plain single launches whose replay runs in the kernel (replay_tail<FATE>)");
     static_assert(!REPS || (!FUSED && !CHAIN && !LEARN && !TL && !FATE && WGRT_INKERNEL_REPLAY),
                   "replica tables are filled by plain single launches (the replay reads TraceArgs::win_reps itself)");
+    static_assert(!EV || (!FUSED && !CHAIN && !LEARN && !TL && !FATE && !REPS && WGRT_INKERNEL_REPLAY),
+                  "expected-value launches are plain single launches (their replica is read at run time)");
+    // EV: this wave's block of scored visits, how many it holds (wave-uniform), the lane's scored visits of the
+    // trace in flight, and the analog hits the wave has binned
+    EvBlock *evb = nullptr;
+    if constexpr (EV) {
+        __shared__ EvBlock ev_lds[4];
+        evb = &ev_lds[threadIdx.x >> 6];
+    }
+    int evfill = 0;
+    uint32_t ev_seen = 0, ev_hits = 0;
 
     // head x's items: stripes of kStripe consecutive chunks, stripe s on head s % 8, iteration-
     // major.  Every die gets a mix of all FoVs and wavelengths -- ray lifetimes differ by tile,
@@ -502,6 +565,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
         blk = 0;
         kind = 0;
         entry = true;
+        if (EV) ev_seen = 0;
     };
     // a trace's counters are added when it ends: an abandoned trace (kUncertain) adds nothing, and its
     // replay (replay_kernel or, fused, epilogue_kernel: trace_one) counts the whole trace once
@@ -590,6 +654,35 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             }
         }
     };
+    // EV: the block's visits binned, one lane each (LDS is in order within a wave: the reads see this wave's
+    // stores, and the stores after them land behind the reads) ...
+    auto ev_flush = [&]() {
+        asm volatile("" ::: "memory");
+        if (lane < evfill) {
+            const int ny = KA(ny), nx = KA(nx);
+            ev_hits += bin_visit(A, evb->e[lane], nx, ny, evb->x[lane], evb->y[lane], evb->q[lane]) ? 1u : 0u;
+        }
+        asm volatile("" ::: "memory");
+        evfill = 0;
+    };
+    // ... and this pass's visits into the block: (px, py) where the ray was scored, q its weight, out: the draw
+    // out-coupled it there
+    auto ev_push = [&](bool dep, double px, double py, double q, bool out) {
+        const uint64_t dm = __ballot(dep);
+        if (dm == 0ull) return;
+        const int nd = __popcll(dm);
+        if (evfill + nd > kEvBlock) ev_flush();
+        if (dep) {
+            const int j = evfill + __builtin_amdgcn_mbcnt_hi((uint32_t)(dm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)dm, 0));
+            const uint32_t reps = (uint32_t)KA(win_reps);
+            const uint32_t rp = reps ? replica_of(ray_gid_ka(K, (int64_t)L.i), reps) : 0u;
+            evb->x[j] = px;
+            evb->y[j] = py;
+            evb->q[j] = q;
+            evb->e[j] = L.tix | rp << kRepShift | (out ? kEvOutBit : 0u);
+        }
+        evfill += nd;
+    };
     // the outcome of an interaction (next region, or kDie / kOut / kUncertain): retire bookkeeping
     auto outcome = [&](int next) {
         if (!FUSED) {
@@ -598,7 +691,10 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             fin = (next < 0) & (next != kUncertain);
             active = next >= 0;
             L.r.region = next >= 0 ? next : L.r.region;
-            if (__builtin_expect(next == kUncertain, 0)) record_abandoned(K, L.i);
+            if (__builtin_expect(next == kUncertain, 0)) {
+                if (EV) record_abandoned_ev(K, L.i, ev_seen);
+                else record_abandoned(K, L.i);
+            }
         } else {
             // one retire site for both ends of a trace (out-coupled, died)
             L.r.region = next >= 0 ? next : L.r.region;
@@ -622,10 +718,19 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             tl_lanes += __popcll(__ballot(active));
         }
         bool out = false;
+        // EV: the visit this pass scores on this lane, where the ray stood when interact() saw it
+        bool dep = false;
+        double evq = -1.0, evx = 0.0, evy = 0.0;
         if (active && blk >= 0) {
             L.inter += entry ? 0u : 1u;
-            const int next = interact<SINGLE, AMP, FATE>(A, K, loc, L, blk, kind, entry, sg);
+            if (EV) evx = L.r.x, evy = L.r.y;
+            const int next = interact<SINGLE, AMP, FATE, EV>(A, K, loc, L, blk, kind, entry, sg, EV ? &evq : nullptr);
             out = next == kOut;
+            if (EV) {
+                const bool scored = (evq >= 0.0) & (next != kUncertain);
+                ev_seen += scored ? 1u : 0u;
+                dep = scored & ((evq > 0.0) | out);
+            }
             if (FATE && next < 0 && next != kUncertain) {
                 int reason = next == kDieIc ? kFateLeftIc : kFateLost;
                 if (out)
@@ -635,7 +740,8 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             outcome(next);
         }
         SEG_TMARK(sg, 5, L.r.er);
-        queue_out(out);
+        if constexpr (EV) ev_push(dep, evx, evy, evq, out);
+        else queue_out(out);
         SEG_MARK(sg, 6);
     };
 
@@ -856,6 +962,10 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
         const int ny = KA(ny), nx = KA(nx);
         tot_h += bin_entry<REPS>(A, g, nx, ny, px, py) ? 1u : 0u;
     };
+    if (EV) {
+        ev_flush();
+        tot_h = ev_hits;
+    }
     if (qblk) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane < qfill) bin(qbase + lane);
@@ -883,7 +993,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
     c.w[kCtrGiveups] = tot_giveup;
     c.w[kCtrInter] = tot_int;
     if (FUSED) finish_fused(K, c);
-    else finish_single<CHAIN, FATE>(K, c);
+    else finish_single<CHAIN, FATE, EV>(K, c);
 }
 
 #if !WGRT_INKERNEL_REPLAY
@@ -916,7 +1026,7 @@ constexpr int kChainMargin = 8;         // workgroups two chained grids leave fr
 template <class CellT, bool FUSED, bool SINGLE, bool AMP>
 __global__ WGRT_JONES_BOUNDS void trace_jones_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
                                                      int chunk) {
-    jones_body<FUSED, SINGLE, false, AMP, false, false, false, false>(
+    jones_body<FUSED, SINGLE, false, AMP, false, false, false, false, false>(
         A, kernel_kargs<decltype(trace_jones_kernel<CellT, FUSED, SINGLE, AMP>)>(), loc, counter, chunk);
 }
 
@@ -925,7 +1035,7 @@ __global__ WGRT_JONES_BOUNDS void trace_jones_kernel(TraceArgs A, LocatorT<CellT
 template <class CellT, bool FUSED, bool SINGLE>
 __global__ WGRT_JONES_BOUNDS void trace_jones_tl_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
                                                         int chunk) {
-    jones_body<FUSED, SINGLE, true, false, false, false, false, false>(A, kernel_kargs<decltype(trace_jones_tl_kernel<CellT, FUSED, SINGLE>)>(),
+    jones_body<FUSED, SINGLE, true, false, false, false, false, false, false>(A, kernel_kargs<decltype(trace_jones_tl_kernel<CellT, FUSED, SINGLE>)>(),
                                                   loc, counter, chunk);
 }
 
@@ -934,7 +1044,7 @@ __global__ WGRT_JONES_BOUNDS void trace_jones_tl_kernel(TraceArgs A, LocatorT<Ce
 template <class CellT>
 __global__ WGRT_JONES_BOUNDS void trace_jones_learn_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
                                                            int chunk, uint32_t *tail) {
-    jones_body<false, false, false, false, true, false, false, false>(A, kernel_kargs<decltype(trace_jones_learn_kernel<CellT>)>(), loc,
+    jones_body<false, false, false, false, true, false, false, false, false>(A, kernel_kargs<decltype(trace_jones_learn_kernel<CellT>)>(), loc,
                                                  counter, chunk);
 }
 
@@ -942,7 +1052,7 @@ __global__ WGRT_JONES_BOUNDS void trace_jones_learn_kernel(TraceArgs A, LocatorT
 template <class CellT, bool AMP>
 __global__ WGRT_JONES_BOUNDS void trace_jones_chain_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
                                                            int chunk) {
-    jones_body<false, false, false, AMP, false, true, false, false>(A, kernel_kargs<decltype(trace_jones_chain_kernel<CellT, AMP>)>(),
+    jones_body<false, false, false, AMP, false, true, false, false, false>(A, kernel_kargs<decltype(trace_jones_chain_kernel<CellT, AMP>)>(),
                                                       loc, counter, chunk);
 }
 
@@ -952,7 +1062,7 @@ __global__ WGRT_JONES_BOUNDS void trace_jones_chain_kernel(TraceArgs A, LocatorT
 template <class CellT, bool SINGLE, bool AMP>
 __global__ WGRT_JONES_BOUNDS void trace_jones_fate_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
                                                           int chunk) {
-    jones_body<false, SINGLE, false, AMP, false, false, true, false>(
+    jones_body<false, SINGLE, false, AMP, false, false, true, false, false>(
         A, kernel_kargs<decltype(trace_jones_fate_kernel<CellT, SINGLE, AMP>)>(), loc, counter, chunk);
 }
 
@@ -961,8 +1071,17 @@ __global__ WGRT_JONES_BOUNDS void trace_jones_fate_kernel(TraceArgs A, LocatorT<
 template <class CellT, bool SINGLE, bool AMP>
 __global__ WGRT_JONES_BOUNDS void trace_jones_reps_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
                                                           int chunk) {
-    jones_body<false, SINGLE, false, AMP, false, false, false, true>(
+    jones_body<false, SINGLE, false, AMP, false, false, false, true, false>(
         A, kernel_kargs<decltype(trace_jones_reps_kernel<CellT, SINGLE, AMP>)>(), loc, counter, chunk);
+}
+
+// The single-launch loop of the expected-value estimator (wgrt_trace_expected): the fate kernels' instantiations
+// again, each reading the replica count at run time; never a learning, timeline or chained launch.
+template <class CellT, bool SINGLE, bool AMP>
+__global__ WGRT_JONES_BOUNDS void trace_jones_ev_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
+                                                        int chunk) {
+    jones_body<false, SINGLE, false, AMP, false, false, false, false, true>(
+        A, kernel_kargs<decltype(trace_jones_ev_kernel<CellT, SINGLE, AMP>)>(), loc, counter, chunk);
 }
 
 // The same kernels over the byte locator (ByteLocatorT<CellT>: the scene's byte grid and palette), under names
@@ -971,43 +1090,50 @@ __global__ WGRT_JONES_BOUNDS void trace_jones_reps_kernel(TraceArgs A, LocatorT<
 template <class CellT, bool FUSED, bool SINGLE, bool AMP>
 __global__ WGRT_JONES_BOUNDS void trace_jones_b_kernel(TraceArgs A, ByteLocatorT<CellT> loc, unsigned long long *counter,
                                                        int chunk) {
-    jones_body<FUSED, SINGLE, false, AMP, false, false, false, false>(
+    jones_body<FUSED, SINGLE, false, AMP, false, false, false, false, false>(
         A, kernel_kargs<decltype(trace_jones_b_kernel<CellT, FUSED, SINGLE, AMP>)>(), loc, counter, chunk);
 }
 
 template <class CellT, bool FUSED, bool SINGLE>
 __global__ WGRT_JONES_BOUNDS void trace_jones_b_tl_kernel(TraceArgs A, ByteLocatorT<CellT> loc, unsigned long long *counter,
                                                           int chunk) {
-    jones_body<FUSED, SINGLE, true, false, false, false, false, false>(
+    jones_body<FUSED, SINGLE, true, false, false, false, false, false, false>(
         A, kernel_kargs<decltype(trace_jones_b_tl_kernel<CellT, FUSED, SINGLE>)>(), loc, counter, chunk);
 }
 
 template <class CellT>
 __global__ WGRT_JONES_BOUNDS void trace_jones_b_learn_kernel(TraceArgs A, ByteLocatorT<CellT> loc,
                                                              unsigned long long *counter, int chunk, uint32_t *tail) {
-    jones_body<false, false, false, false, true, false, false, false>(
+    jones_body<false, false, false, false, true, false, false, false, false>(
         A, kernel_kargs<decltype(trace_jones_b_learn_kernel<CellT>)>(), loc, counter, chunk);
 }
 
 template <class CellT, bool AMP>
 __global__ WGRT_JONES_BOUNDS void trace_jones_b_chain_kernel(TraceArgs A, ByteLocatorT<CellT> loc,
                                                              unsigned long long *counter, int chunk) {
-    jones_body<false, false, false, AMP, false, true, false, false>(
+    jones_body<false, false, false, AMP, false, true, false, false, false>(
         A, kernel_kargs<decltype(trace_jones_b_chain_kernel<CellT, AMP>)>(), loc, counter, chunk);
 }
 
 template <class CellT, bool SINGLE, bool AMP>
 __global__ WGRT_JONES_BOUNDS void trace_jones_b_fate_kernel(TraceArgs A, ByteLocatorT<CellT> loc,
                                                             unsigned long long *counter, int chunk) {
-    jones_body<false, SINGLE, false, AMP, false, false, true, false>(
+    jones_body<false, SINGLE, false, AMP, false, false, true, false, false>(
         A, kernel_kargs<decltype(trace_jones_b_fate_kernel<CellT, SINGLE, AMP>)>(), loc, counter, chunk);
 }
 
 template <class CellT, bool SINGLE, bool AMP>
 __global__ WGRT_JONES_BOUNDS void trace_jones_b_reps_kernel(TraceArgs A, ByteLocatorT<CellT> loc,
                                                             unsigned long long *counter, int chunk) {
-    jones_body<false, SINGLE, false, AMP, false, false, false, true>(
+    jones_body<false, SINGLE, false, AMP, false, false, false, true, false>(
         A, kernel_kargs<decltype(trace_jones_b_reps_kernel<CellT, SINGLE, AMP>)>(), loc, counter, chunk);
+}
+
+template <class CellT, bool SINGLE, bool AMP>
+__global__ WGRT_JONES_BOUNDS void trace_jones_b_ev_kernel(TraceArgs A, ByteLocatorT<CellT> loc,
+                                                          unsigned long long *counter, int chunk) {
+    jones_body<false, SINGLE, false, AMP, false, false, false, false, true>(
+        A, kernel_kargs<decltype(trace_jones_b_ev_kernel<CellT, SINGLE, AMP>)>(), loc, counter, chunk);
 }
 
 // The two ends of a chain's segment, on the caller's stream: every ray's state into its granule under the
@@ -1107,6 +1233,9 @@ const void *const kFateKernels[2][2][2][2] = {   // [byte locator][64-bit cells]
 const void *const kRepsKernels[2][2][2][2] = {   // [byte locator][64-bit cells][single wavelength][AMP]
     {WGRT_K4(trace_jones_reps_kernel, uint32_t), WGRT_K4(trace_jones_reps_kernel, uint64_t)},
     {WGRT_K4(trace_jones_b_reps_kernel, uint32_t), WGRT_K4(trace_jones_b_reps_kernel, uint64_t)}};
+const void *const kEvKernels[2][2][2][2] = {   // [byte locator][64-bit cells][single wavelength][AMP]: wgrt_trace_expected
+    {WGRT_K4(trace_jones_ev_kernel, uint32_t), WGRT_K4(trace_jones_ev_kernel, uint64_t)},
+    {WGRT_K4(trace_jones_b_ev_kernel, uint32_t), WGRT_K4(trace_jones_b_ev_kernel, uint64_t)}};
 const void *const kTimelineKernels[2][2] = {   // [byte locator][fused]
     {(const void *)trace_jones_tl_kernel<uint32_t, false, false>, (const void *)trace_jones_tl_kernel<uint32_t, true, false>},
     {(const void *)trace_jones_b_tl_kernel<uint32_t, false, false>,
@@ -1151,6 +1280,10 @@ wgrt_status query_trace_grids(wgrt_scene *s) {
                 HIP_TRY(grid_of(kRepsKernels[b][c][g][0], plain));
                 HIP_TRY(grid_of(kRepsKernels[b][c][g][1], amp));
                 s->jones_reps_grid[b][c][g] = std::min(s->jones_grid[b][c][0][g], std::min(plain, amp));
+                // ... and the expected-value instantiations
+                HIP_TRY(grid_of(kEvKernels[b][c][g][0], plain));
+                HIP_TRY(grid_of(kEvKernels[b][c][g][1], amp));
+                s->jones_ev_grid[b][c][g] = std::min(s->jones_grid[b][c][0][g], std::min(plain, amp));
             }
         for (int f = 0; f < 2; ++f) HIP_TRY(grid_of(kTimelineKernels[b][f], s->jones_tl_grid[b][f]));
         for (int c = 0; c < 2; ++c) HIP_TRY(grid_of(kLearnKernels[b][c], s->jones_learn_grid[b][c]));
@@ -1326,6 +1459,10 @@ struct LaunchCfg {
     // debug timeline, and not together with fate (validate_launch, plan_auto_order).
     int replicas = 0;
     int64_t rep_stride = 0;
+    // wgrt_trace_expected: the launch scores every out-coupler visit into win_table (wgrt_expected.h) instead of
+    // counting out-couplings; `replicas` as above (0: the one table).  It follows the replica launch's rules, has no
+    // grid (a float32 cell cannot hold the fixed-point sums) and never stores fates.
+    bool expected = false;
     // set by validate_launch: the launch runs the byte-locator instantiation (byte_locator_applies)
     bool byte = false;
 };
@@ -1373,7 +1510,7 @@ void plan_auto_order(wgrt_scene *ms, int64_t n_rays, int item, LaunchCfg &c) {
     if (learning)
         while (c.order_gen & (c.order_gen - 1)) c.order_gen &= c.order_gen - 1;
     c.auto_order = ms->learn_gen > 0 && item == kChunk;
-    if (!c.timeline && learning && !c.fate && !c.replicas) {   // (a fate or replica launch does not learn: LaunchCfg)
+    if (!c.timeline && learning && !c.fate && !c.replicas && !c.expected) {   // (a fate, replica or expected-value launch does not learn: LaunchCfg)
         c.learn = true;
         ms->learned_rays += n_rays;
         ++ms->learn_gen;
@@ -1431,6 +1568,11 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
                                                "launches (trace the iterations one call each)");
     if (c.fate && c.replicas)
         return fail(WGRT_ERR_INVALID_ARGUMENT, "a launch stores fates or fills replica tables, not both");
+    if (c.expected && c.num_iter > 1)
+        return fail(WGRT_ERR_INVALID_ARGUMENT, "num_iter > 1 takes no expected-value estimator: its tables are filled by "
+                                               "single launches (trace the iterations one call each)");
+    if (c.expected && (c.fate || matrix_EB || !c.win_table))
+        return fail(WGRT_ERR_INVALID_ARGUMENT, "the expected-value estimator fills a window table: no grid, no fates");
     if (c.chunk_order && c.variant == 1)
         return fail(WGRT_ERR_INVALID_ARGUMENT, "chunk_order needs variant 0, 7 or 9");
     if (c.gid_blocks && (c.gid_block_rays < 1 || gid_offset != 0))
@@ -1458,7 +1600,10 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
     if (c.timeline && c.replicas)
         return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel fills no replica tables: trace with replicas or with "
                                           "the timeline");
-    if (c.replicas && c.variant != 1 && (int64_t)s->nl * s->nx * s->ny >= (int64_t)1 << kRepShift)
+    if (c.timeline && c.expected)
+        return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel scores no visits: trace with the expected-value "
+                                          "estimator or with the timeline");
+    if ((c.replicas || c.expected) && c.variant != 1 && (int64_t)s->nl * s->nx * s->ny >= (int64_t)1 << kRepShift)
         return fail(WGRT_ERR_UNSUPPORTED, "replica tables with variants 7 / 9 need a scene of fewer than 2^24 tiles (the "
                                           "out-coupling queue entry carries the replica above the tile index)");
     // (a chained variant-1 call, num_iter > 1, has no chunk_order: rejected above)
@@ -1504,6 +1649,7 @@ int64_t launch_grid(const wgrt_scene *s, int64_t n_rays, int64_t item, const Lau
                    : c.chain_serial ? s->jones_chain_grid[c.byte][c.variant == 9]
                    : c.timeline     ? s->jones_tl_grid[c.byte][c.num_iter > 1]
                    : c.fate         ? s->jones_fate_grid[c.byte][c.variant == 9][c.single]
+                   : c.expected     ? s->jones_ev_grid[c.byte][c.variant == 9][c.single]
                    : c.replicas     ? s->jones_reps_grid[c.byte][c.variant == 9][c.single]
                    : c.learn        ? s->jones_learn_grid[c.byte][c.variant == 9]
                                     : s->jones_grid[c.byte][c.variant == 9][c.num_iter > 1][c.single];
@@ -1537,7 +1683,8 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
     if (c.variant == 1) {
         const int64_t blocks = (A.n_rays + 255) / 256;
         if (blocks > 0x7fffffff) return fail(WGRT_ERR_INVALID_ARGUMENT, "too many rays for one launch");
-        if (c.fate) hipLaunchKernelGGL(trace_grid_fate_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
+        if (c.expected) hipLaunchKernelGGL(trace_grid_ev_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
+        else if (c.fate) hipLaunchKernelGGL(trace_grid_fate_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
         else hipLaunchKernelGGL(trace_grid_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
         HIP_TRY(hipGetLastError());
         return WGRT_OK;
@@ -1596,6 +1743,7 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
     const void *const kernel = c.chain_serial ? kChainKernels[c.byte][wide][amp]
                                : c.timeline ? kTimelineKernels[c.byte][num_iter > 1]
                                : c.fate   ? kFateKernels[c.byte][wide][c.single][amp]
+                               : c.expected ? kEvKernels[c.byte][wide][c.single][amp]
                                : c.replicas ? kRepsKernels[c.byte][wide][c.single][amp]
                                : c.learn  ? kLearnKernels[c.byte][wide]
                                           : kJonesKernels[c.byte][wide][num_iter > 1][c.single][amp];
@@ -1932,6 +2080,28 @@ wgrt_status wgrt_trace_replicas(const wgrt_scene *s, const wgrt_rays *rays, int6
     return trace_launch(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, c);
 }
 
+wgrt_status wgrt_trace_expected(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
+                                uint32_t *rng_states, wgrt_trace_stats *stats, uint32_t *per_ray_bounces, void *stream,
+                                const wgrt_launch_opts *opts, const wgrt_window_plan *plan, double *table, int replicas) {
+    if (replicas < 0 || replicas > WGRT_MAX_REPLICAS)
+        return fail(WGRT_ERR_INVALID_ARGUMENT, "replicas must be 0, 1 or 2 .. " + std::to_string(WGRT_MAX_REPLICAS));
+    if (!table || !plan)
+        return fail(WGRT_ERR_INVALID_ARGUMENT, "the expected-value estimator needs its table [n_slabs, W] (or [replicas, "
+                                               "n_slabs, W]) and the table's plan");
+    if (!s) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL scene / rays");
+    LaunchCfg c;
+    const wgrt_status e = cfg_of_opts(s, opts, plan, table, c);
+    if (e != WGRT_OK) return e;
+    c.expected = true;
+    c.replicas = replicas >= 2 ? replicas : 0;
+    c.rep_stride = (int64_t)s->nl * s->ny * s->nx * plan->host.W;
+    return trace_launch(s, rays, n_rays, gid_offset, rng_states, nullptr, stats, per_ray_bounces, stream, c);
+}
+
+double wgrt_expected_weight_host(double e1, double e2, double e3, double en1, double en2, double en3, double threshold) {
+    return expected_deposit(e1, e2, e3, en1, en2, en3, threshold);
+}
+
 wgrt_status wgrt_chain_begin(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
                              uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats, void *stream,
                              const wgrt_launch_opts *opts, const wgrt_window_plan *plan, double *table,
@@ -2070,6 +2240,22 @@ wgrt_status wgrt_debug_get_auto_order(const wgrt_scene *s, void *stream, int32_t
                                                    std::to_string((it->second.order_rays + kChunk - 1) / kChunk) + " chunks");
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     HIP_TRY(hipMemcpy(out, it->second.order, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return WGRT_OK;
+}
+
+wgrt_status wgrt_debug_expected_replays(const wgrt_scene *s, void *stream, uint32_t *rays, uint32_t *skipped, int64_t n) {
+    if (!s || n < 0 || (n > 0 && (!rays || !skipped))) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL scene / rays / skipped");
+    wgrt_scene *ms = const_cast<wgrt_scene *>(s);
+    DEVICE_SCOPE(dev_scope, s->device);
+    std::lock_guard<std::mutex> lk(ms->scratch_mu);
+    const auto it = ms->scratch.find(stream);
+    if (it == ms->scratch.end() || n > it->second.cap || n > it->second.qcap)
+        return fail(WGRT_ERR_INVALID_ARGUMENT, "no launch on this stream has a replay list of n entries");
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    if (n) {   // (record_abandoned_ev: the list's entry k and, in q_i, the visits ray k's replay passes over)
+        HIP_TRY(hipMemcpy(rays, it->second.list, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(skipped, it->second.q_i, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
     return WGRT_OK;
 }
 

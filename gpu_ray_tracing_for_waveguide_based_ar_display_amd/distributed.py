@@ -484,7 +484,8 @@ def timed_run(trace_fn, rays, rng, eb, gid: GidMap, steps: int, per_call: int, s
     return float(t.item()), int(b.item()), local
 
 
-def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, replicas: int = 0):
+def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, replicas: int = 0,
+               expected: bool = False):
     """trace_fn for ``run_steps`` / ``trace_job`` using the HIP kernel (torch device tensors); ``stats``
     (int64[STATS_LEN] device tensor) is added to by every call.  A shard of several block ranges passes its global
     ids as ``gid_blocks``, uploaded once per map and device and kept on the map (``GidMap.device_blocks``).
@@ -503,7 +504,11 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, rep
 
     ``replicas``: ``B``, with ``windows=(plan, table)`` and ``table`` the ``[B, n_slabs, W]`` replica tables
     (``engine.trace_fullcolor(replicas=...)``): single launches only again, and no ``chain``.  A ray's replica is its
-    global id's, so the ranks' replica tables add: the collective is still ``reduce_eyebox(table)``."""
+    global id's, so the ranks' replica tables add: the collective is still ``reduce_eyebox(table)``.
+
+    ``expected``: every call scores the expected-value estimator into the table instead
+    (``engine.trace_fullcolor(expected=True)``; ``eb`` must be None): single launches only and no ``chain`` again.
+    The sums are exact multiples of 2^-32, so the ranks' tables add exactly, as the counts do."""
     from .engine import TraceChain, trace_fullcolor
 
     def ids_of(rng, gid: GidMap):
@@ -513,12 +518,12 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, rep
 
     def fn(rays, rng, eb, gid: GidMap, num_iter=1):
         trace_fullcolor(scene, rays, rng, eb, stats=stats, variant=variant, num_iter=num_iter, windows=windows,
-                        fate=fate, replicas=replicas, **ids_of(rng, gid))
+                        fate=fate, replicas=replicas, expected=expected, **ids_of(rng, gid))
 
     def chain(rays, rng, eb, gid: GidMap):
         """The same launches as a chain (``run_steps`` uses it for separate launches without a hook)."""
         return TraceChain(scene, rays, rng, eb, stats=stats, variant=variant, windows=windows, **ids_of(rng, gid))
-    if fate is None and int(replicas or 0) < 2:
+    if fate is None and int(replicas or 0) < 2 and not expected:
         fn.chain = chain
     return fn
 

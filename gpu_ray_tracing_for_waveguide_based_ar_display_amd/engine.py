@@ -53,7 +53,8 @@ def trace_fullcolor(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_E
                     per_ray_bounces: torch.Tensor | None = None, stream=None, variant: int = VARIANT_AUTO,
                     workgroups: int = 0, chunk_order: torch.Tensor | None = None, num_iter: int = 1,
                     gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
-                    grid_sqrt_k: float = 0.0, windows=None, fate: torch.Tensor | None = None, replicas: int = 0) -> None:
+                    grid_sqrt_k: float = 0.0, windows=None, fate: torch.Tensor | None = None, replicas: int = 0,
+                    expected: bool = False) -> None:
     """Asynchronous launch on ``stream`` (default: torch's current stream).
 
     rays: dict of device float32 tensors keyed like the reference columns
@@ -80,14 +81,19 @@ def trace_fullcolor(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_E
     tensor of ``plan.new_table(scene, replicas=B)``: an out-coupling of the ray with global id ``g`` counts into
     ``table[g % B]`` (``wgrt_trace_replicas``; 2 <= B <= 64), so ``table.sum(0)`` is the table a plain windows trace
     leaves, bit for bit, and ``fold_replicas`` / ``evaluation_error_bars`` turn the copies into jackknife error
-    bars; single launches only, not together with ``fate``; 0 or 1: no replicas.
+    bars; single launches only, not together with ``fate``; 0 or 1: no replicas.  expected: the expected-value
+    estimator (``wgrt_trace_expected``): needs ``windows=(plan, table)`` and ``matrix_EB=None``; the walk --
+    ``rng_states``, ``per_ray_bounces``, ``stats`` -- is the plain launch's bit for bit, but every out-coupler
+    interaction inside the FoV's eyebox rectangle adds its out-coupling probability (a multiple of 2^-32) to the
+    table instead of 1.0 per out-coupled ray: the same expectation with a fraction of the variance.  Works with
+    ``replicas=B``; a grid, ``fate``, ``num_iter > 1`` and a ``TraceChain`` raise ``ValueError``.
     """
     if scene.single_lambda:
         raise ValueError("trace_fullcolor needs a full-colour scene; use trace_single for a single-wavelength one")
     _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single=False, chunk_order=chunk_order, num_iter=num_iter, gid_blocks=gid_blocks,
            gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows, fate=fate,
-           replicas=replicas)
+           replicas=replicas, expected=expected)
 
 
 def new_stats(device) -> torch.Tensor:
@@ -130,18 +136,19 @@ def trace_single(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_EB: 
                  per_ray_bounces: torch.Tensor | None = None, stream=None, variant: int = VARIANT_AUTO,
                  workgroups: int = 0, chunk_order: torch.Tensor | None = None, num_iter: int = 1,
                  gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
-                 grid_sqrt_k: float = 0.0, windows=None, fate: torch.Tensor | None = None, replicas: int = 0) -> None:
+                 grid_sqrt_k: float = 0.0, windows=None, fate: torch.Tensor | None = None, replicas: int = 0,
+                 expected: bool = False) -> None:
     """One launch of the single-wavelength kernel (``process_rays_kernel_pro``, GRTF:419-831)
     through ``wgrt_trace_single_ex``: no ``lmd_num`` column (ignored if present),
     matrix_EB [NY, NX, 80, 120], branch guard ener * efficiency > 1e-15.  The scene must be
     a single-wavelength one (``Scene.from_geometry(..., wavelength=l)`` or 3-D LUTs).  ``windows``, ``fate``,
-    ``replicas``: as ``trace_fullcolor``."""
+    ``replicas``, ``expected``: as ``trace_fullcolor``."""
     if not scene.single_lambda:
         raise ValueError("trace_single needs a single-wavelength scene (Scene.from_geometry(..., wavelength=l))")
     _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single=True, chunk_order=chunk_order, num_iter=num_iter, gid_blocks=gid_blocks,
            gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows, fate=fate,
-           replicas=replicas)
+           replicas=replicas, expected=expected)
 
 
 MAX_REPLICAS = 64   # WGRT_MAX_REPLICAS (include/wgrt.h)
@@ -244,9 +251,20 @@ def _read_columns(rays, rng_states, n_rays, single, device):
 
 def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single, chunk_order=None, num_iter=1, gid_blocks=None, gid_block_rays=0, debug=None,
-           grid_sqrt_k=0.0, windows=None, chain=False, fate=None, replicas=0):
+           grid_sqrt_k=0.0, windows=None, chain=False, fate=None, replicas=0, expected=False):
     device = torch.device("cuda", scene.device)
     B = _replica_count(replicas)
+    if expected:   # (before anything is read or launched)
+        if matrix_EB is not None:
+            raise ValueError("expected=True takes no grid (matrix_EB=None): a float32 cell cannot hold the 2^-32 sums")
+        if windows is None:
+            raise ValueError("expected=True needs windows=(plan, table)")
+        if fate is not None:
+            raise ValueError("expected=True takes no fate")
+        if int(num_iter) > 1:
+            raise ValueError("expected=True needs num_iter == 1: its tables are filled by single launches")
+        if chain:
+            raise ValueError("a chain takes no expected-value launches")
     cols, N = _read_columns(rays, rng_states, n_rays, single, device)
     x = cols["x"]
     if matrix_EB is None and windows is None:
@@ -305,7 +323,9 @@ def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ra
         if h <= 0:   # the negated wgrt_status of the failure
             check(-h, "wgrt_chain_begin")
         return h, (args, dbg, windows)
-    if fate is not None:   # torch.ops.wgrt.trace_fate -> wgrt_trace_fate (plan 0, no table: the grid alone)
+    if expected:   # torch.ops.wgrt.trace_expected -> wgrt_trace_expected (no grid; B = 0: the one table)
+        status = ops().trace_expected(*args[:10], *args[11:], plan.handle.value, table, B)
+    elif fate is not None:   # torch.ops.wgrt.trace_fate -> wgrt_trace_fate (plan 0, no table: the grid alone)
         status = ops().trace_fate(*args, plan.handle.value if windows is not None else 0,
                                   table if windows is not None else None, fate)
     elif windows is not None and int(replicas or 0):   # torch.ops.wgrt.trace_replicas -> wgrt_trace_replicas (1: one table)
@@ -337,9 +357,11 @@ class TraceChain:
                  gid_offset: int = 0, n_rays: int | None = None, stats: torch.Tensor | None = None, stream=None,
                  variant: int = VARIANT_AUTO, workgroups: int = 0, chunk_order: torch.Tensor | None = None,
                  gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
-                 grid_sqrt_k: float = 0.0, windows=None, replicas: int = 0):
+                 grid_sqrt_k: float = 0.0, windows=None, replicas: int = 0, expected: bool = False):
         if scene.single_lambda:
             raise ValueError("TraceChain needs a full-colour scene")
+        if expected:
+            raise ValueError("a chain takes no expected-value launches: trace them with single launches")
         if _replica_count(replicas):
             raise ValueError("a chain takes no replicas: trace replica tables with single launches")
         self._h = 0
@@ -686,6 +708,14 @@ def selftest_math(a: torch.Tensor, b: torch.Tensor, stream=None) -> torch.Tensor
     return out
 
 
-__all__ = ["Scene", "WindowPlan", "TraceChain", "fold_replicas", "MAX_REPLICAS", "fate_census", "fate_census_host", "fate_col", "loss_budget", "FATE_CLASSES", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
+def expected_weight(e1: float, e2: float, e3: float, en1: float, en2: float, en3: float, threshold: float = 0.0) -> float:
+    """The deposit ``q`` of one out-coupler interaction under the expected-value estimator (``trace_*(expected=True)``)
+    through the code the kernels run (``wgrt_expected_weight_host``; no GPU needed): the out-coupling probability of
+    the reference's branch chain for efficiencies ``e1, e2, e3`` and guard products ``en_k = ener * e_k`` against
+    ``threshold``, rounded to a multiple of 2^-32."""
+    return float(load().wgrt_expected_weight_host(e1, e2, e3, en1, en2, en3, threshold))
+
+
+__all__ = ["Scene", "WindowPlan", "TraceChain", "fold_replicas", "expected_weight", "MAX_REPLICAS", "fate_census", "fate_census_host", "fate_col", "loss_budget", "FATE_CLASSES", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
            "trace_fullcolor", "trace_single", "init_rays", "schedule_by_lifetime",
            "rays_to_device", "classify_points", "shadow", "selftest_math", "RAY_COLUMNS", "_lib"]

@@ -55,7 +55,7 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
         point_seed: int | None = None, evaluate: bool = True, verbose: bool = True, variant: int = 0,
         fuse: bool | None = None, points: np.ndarray | None = None, png: str | None = None,
         eyebox: str = "host", keep_grid: bool = False, evaluate_on: str = "host",
-        keep_image: bool = False, budget: bool = False, error_bars: int = 0) -> dict:
+        keep_image: bool = False, budget: bool = False, error_bars: int = 0, estimator: str = "analog") -> dict:
     """The reference script's job on this engine; returns its printed quantities and arrays.
     ``points``: the R/2 in-coupler origins to use (default: sampled, GRTF:12-23, seeded by
     ``point_seed``); ``png``: where to write the "Eyebox Center View" image (needs ``evaluate``).
@@ -103,7 +103,25 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
     ``U_fov_se``, ``U_EB_se`` and ``jackknife`` (the leave-one-out figures ``[B, 3]``), and ``+-`` is printed beside each
     figure; everything returned before is bit-identical with and without it.  ``U_fov`` and ``U_EB`` are min / max
     ratios, for which the jackknife is an indication only.  Memory: 10.3 MB per replica at the default job (22,500
-    slabs x 57 x 8 B), 205 MB at ``B = 20``, against the grid's 864 MB."""
+    slabs x 57 x 8 B), 205 MB at ``B = 20``, against the grid's 864 MB.
+
+    ``estimator``: ``"analog"`` (the reference's: a ray counts 1 where its last draw out-couples it) or ``"expected"``
+    (``engine.trace_fullcolor(expected=True)``): the same walk -- ``rng_states``, ``bounces`` and ``eyebox_hits`` are the
+    analog job's -- but every out-coupler interaction inside the eyebox rectangle adds its out-coupling probability to
+    the window table, so ``A``, the efficiencies, the three figures and their ``_se`` come from a table with the same
+    expectation and a fraction of the variance.  It needs ``eyebox="windows"`` (a grid cannot hold the sums), goes as
+    plain single launches, combines with ``error_bars``, both ``evaluate_on`` and several GPUs, and excludes
+    ``budget=True``; anything else raises ``ValueError`` before any GPU work.  The result says which in ``estimator``."""
+    if estimator not in ("analog", "expected"):
+        raise ValueError(f"estimator must be 'analog' or 'expected', got {estimator!r}")
+    expected = estimator == "expected"
+    if expected:
+        if eyebox != "windows":
+            raise ValueError("estimator='expected' scores into the window table: it needs eyebox='windows' (a float32 "
+                             "grid cannot hold the sums)")
+        if budget:
+            raise ValueError("estimator='expected' and budget=True exclude each other: no launch both scores every "
+                             "visit and stores fates")
     error_bars = int(error_bars or 0)
     if error_bars:
         if not 2 <= error_bars <= 64:
@@ -129,6 +147,7 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
     from .engine import STAT
     with _set_up(num_FOV_x, num_FOV_y, int(num_rays_per_FoV), num_iter, lambdas, lut_dir, lut_seed, lut_profile,
                  point_seed, points, verbose, eyebox == "windows", budget, error_bars) as job:   # closes the scene on every way out
+        job.expected = expected
         kern_s = _trace(job, variant, fuse)
         t_post = time.perf_counter()   # everything below is post-processing of the traced grid
         grid, table, stats = _collect(job, eyebox != "host", keep_grid)
@@ -137,7 +156,8 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
             from .engine import fold_replicas
             reps, table = table, fold_replicas(table)[0]
         out = dict(num_rays=job.num_rays, num_iter=num_iter, gpu_seconds=kern_s, bounces=int(stats[STAT.bounces]),
-                   eyebox_hits=int(stats[STAT.eyebox_hits]), rng_states=job.rng.cpu().numpy().view(np.uint32))
+                   eyebox_hits=int(stats[STAT.eyebox_hits]), rng_states=job.rng.cpu().numpy().view(np.uint32),
+                   estimator=estimator)
         census = _census(job)
         if job.rank != 0:
             return out
@@ -229,15 +249,16 @@ def _trace(job, variant, fuse) -> float:
     if job.fate is not None:   # the budget: a launch's fates are counted before the next launch overwrites them
         per_call = 1
         hook = lambda j, when: when == "end" and fate_census(job.scene, job.rays, job.fate, table=job.census)
-    if job.replicas:   # only a single launch fills replica tables; the tracer offers no chain
-        per_call = 1
+    if job.replicas or getattr(job, "expected", False):   # only a single launch fills replica tables or scores the
+        per_call = 1                                      # expected-value estimator; the tracer offers no chain
     calls = split_calls(job.num_iter, per_call)
     if n_rays and calls:
         reserve(job.scene, n_rays, max(calls))
     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0.record()
     if n_rays:
-        run_steps(hip_tracer(job.scene, variant, job.stats, job.windows, fate=job.fate, replicas=job.replicas), job.rays, job.rng, job.eb,
+        run_steps(hip_tracer(job.scene, variant, job.stats, job.windows, fate=job.fate, replicas=job.replicas,
+                             expected=getattr(job, "expected", False)), job.rays, job.rng, job.eb,
                   job.shard.gid, job.num_iter, per_call, hook=hook)
     t1.record()
     torch.cuda.synchronize()
@@ -433,6 +454,9 @@ def main(argv=None):
     ap.add_argument("--error-bars", type=int, default=0, metavar="B",
                     help="Monte-Carlo standard errors of every printed figure from B replica window tables filled by ray "
                          "id and jackknifed (needs --eyebox windows and B dividing rays-per-fov / 2)")
+    ap.add_argument("--estimator", choices=["analog", "expected"], default="analog",
+                    help="expected: score every out-coupler visit with its out-coupling probability (needs --eyebox "
+                         "windows): the same expectation, less variance")
     ap.add_argument("--json", default=None, help="write scalar results here")
     ap.add_argument("--png", default="Eyebox Center View.png",
                     help="the eyebox-center image (MAIN:199-203); empty string: do not write it")
@@ -446,7 +470,7 @@ def main(argv=None):
     res = run(a.num_fov_x, a.num_fov_y, a.rays_per_fov, a.num_iter, lut_dir=a.lut_dir, lut_seed=a.lut_seed,
               lut_profile=a.lut_profile, point_seed=a.point_seed, evaluate=not a.no_eval,
               fuse=False if a.no_fuse else {"auto": None, "yes": True, "no": False}[a.fuse],
-              png=a.png or None, eyebox=a.eyebox, evaluate_on=a.evaluate, budget=a.budget, error_bars=a.error_bars)
+              png=a.png or None, eyebox=a.eyebox, evaluate_on=a.evaluate, budget=a.budget, error_bars=a.error_bars, estimator=a.estimator)
     if a.json and (not dist.is_initialized() or dist.get_rank() == 0):
         keep = {k: v for k, v in res.items() if isinstance(v, (int, float, dict, str))}
         with open(a.json, "w") as f:

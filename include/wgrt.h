@@ -490,6 +490,40 @@ wgrt_status wgrt_trace_replicas(const wgrt_scene *scene, const wgrt_rays *rays, 
 wgrt_status wgrt_window_replicas_fold(const double *reps, int32_t B, int64_t n, double *out, void *stream);
 wgrt_status wgrt_window_replicas_fold_host(const double *reps, int32_t B, int64_t n, double *out);
 
+/* The expected-value (collision) estimator of the eyebox (new symbols within ABI 9, looked up by name).
+ *
+ * wgrt_trace_windows counts a ray when its last draw out-couples it inside its FoV's eyebox rectangle.
+ * wgrt_trace_expected makes the same walk -- the same draws and branches, so rng_states, per_ray_bounces and every
+ * field of stats come out bit-identical to wgrt_trace_windows' (eyebox_hits keeps counting the walk's analog hits)
+ * -- but scores every out-coupler interaction (R4 / R5) inside that rectangle: it adds the probability q that the
+ * interaction's draw out-couples the ray to table[s, 0] and to every window holding the bin under the ray, through
+ * the membership rule above (the aliased offset gives the slab, an offset outside the buffer is dropped).  The
+ * out-coupling itself adds nothing more than its interaction's q.  With e1, e2, e3 the interaction's efficiencies,
+ * en_k = ener * e_k and t the scene's threshold (0 full colour, 1e-15 one wavelength), the weight is the length of the
+ * set of draws in [0, 1] for which the reference's if / elif / elif chain takes the out-coupling branch:
+ *     w = 0 if !(en3 > t);  lo = en2 > t ? e1 + e2 : en1 > t ? e1 : 0;  w = max(0, min(e1 + e2 + e3, 1) - min(lo, 1)),
+ * and q = rint(w * 2^32) * 2^-32 (ties to even; 1.0 for w == 1; q == 0 adds nothing).  Every table entry has the
+ * expectation wgrt_trace_windows' has.  Sums of multiples of 2^-32 are exact in float64 while an entry stays below
+ * 2^21: below that the table is the same bits on every run and for every work split, and shards and replicas add
+ * up exactly.  The efficiencies are the exact lane's (variant 1, replays) or the Jones lane's double-precision
+ * evaluation (variants 7 / 9), which differ from the reference's by far less than 2^-32: a q may differ from the
+ * reference arithmetic's by one quantum.
+ *   table      required: DEVICE float64 [n_slabs, W], or [B, n_slabs, W] for 2 <= replicas = B <= WGRT_MAX_REPLICAS,
+ *              the ray with global id g scoring into copy g % B as in wgrt_trace_replicas; ADDED to, never zeroed;
+ *   replicas   0 or 1: the one table; below 0 or above WGRT_MAX_REPLICAS: WGRT_ERR_INVALID_ARGUMENT.
+ * There is no matrix_EB: a float32 grid cannot hold the fixed-point sums.  An expected-value launch is a single
+ * launch, as fate and replica launches are: opts->num_iter > 1 is WGRT_ERR_INVALID_ARGUMENT, wgrt_chain_begin takes
+ * none, no entry point combines it with fates, wgrt_debug_opts.timeline is WGRT_ERR_UNSUPPORTED, it never learns
+ * the scene's tile table, and variants 7 / 9 refuse a scene of 2^24 tiles or more with WGRT_ERR_UNSUPPORTED (the
+ * visit's entry carries the replica above the tile index).  A ray the Jones lane abandons is re-traced by the exact
+ * lane past the visits already scored, so none is scored twice.  The call allocates nothing and is asynchronous on
+ * stream.  A launch through any other entry point runs the kernels it ran before this one existed. */
+wgrt_status wgrt_trace_expected(const wgrt_scene *scene, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
+                                uint32_t *rng_states, wgrt_trace_stats *stats, uint32_t *per_ray_bounces, void *stream,
+                                const wgrt_launch_opts *opts, const wgrt_window_plan *plan, double *table, int replicas);
+/* Host-only (no GPU needed): q of the rule above, through the code the kernels run (csrc/wgrt_expected.h). */
+double wgrt_expected_weight_host(double e1, double e2, double e3, double en1, double en2, double en3, double threshold);
+
 /* Host-only (no GPU needed; test hooks) through the same membership code (csrc/wgrt_window.h):
  * _validate is wgrt_window_plan_create's argument check alone; _table_host ADDS the n hits at flat grid
  * offsets offsets[n] (HOST int64; those outside [0, n_slabs * 9600) are dropped, as the grid's guard drops

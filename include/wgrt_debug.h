@@ -105,6 +105,11 @@ wgrt_status wgrt_debug_scene_palette(const wgrt_scene *scene, int *distinct_word
 /* Copies the order the stream's last automatically ordered launch used to host memory (n must be its
  * ceil(n_rays / 64) chunks); WGRT_ERR_INVALID_ARGUMENT when the stream has built none.  Waits for the stream. */
 wgrt_status wgrt_debug_get_auto_order(const wgrt_scene *scene, void *stream, int32_t *out, int64_t n);
+/* The replay list of the stream's last expected-value launch (wgrt_trace_expected, variants 7 / 9): the local index
+ * of each of its first n abandoned rays and the scored visits its replay passed over (the deposits the Jones-vector
+ * lane had made before it abandoned the ray), to host memory; n at most the launch's wgrt_trace_stats.replayed.
+ * Valid until the next launch on the stream.  Waits for the stream. */
+wgrt_status wgrt_debug_expected_replays(const wgrt_scene *scene, void *stream, uint32_t *rays, uint32_t *skipped, int64_t n);
 /* Copies the scene's tile table (uint32 counts, n = num_lmd * nx * ny, index (lambda * nx + m) * ny + n)
  * to host memory.  Waits for the device. */
 wgrt_status wgrt_debug_get_tile_tail(const wgrt_scene *scene, uint32_t *out, int64_t n);
