@@ -28,14 +28,15 @@ EXPORTED = ("wgrt_scene_create", "wgrt_scene_create_ex", "wgrt_scene_destroy", "
             "wgrt_eyebox_window_sums", "wgrt_eyebox_evaluate_workspace_bytes", "wgrt_eyebox_evaluate",
             "wgrt_eyebox_evaluate_host", "wgrt_window_plan_create", "wgrt_window_plan_destroy",
             "wgrt_window_plan_width", "wgrt_trace_windows", "wgrt_window_plan_validate", "wgrt_window_table_host",
-            "wgrt_chain_begin", "wgrt_chain_step", "wgrt_chain_end", "wgrt_trace_fate", "wgrt_fate_census",
+            "wgrt_chain_begin", "wgrt_chain_step", "wgrt_chain_end", "wgrt_chain_gather", "wgrt_trace_fate", "wgrt_fate_census",
             "wgrt_fate_census_host", "wgrt_fate_col", "wgrt_fate_cols", "wgrt_fate_reason_name", "wgrt_trace_replicas",
             "wgrt_window_replicas_fold", "wgrt_window_replicas_fold_host", "wgrt_trace_expected",
             "wgrt_expected_weight_host")
 EXPORTED_DEBUG = ("wgrt_debug_shadow", "wgrt_debug_scene_copy", "wgrt_debug_set_auto_order",
                   "wgrt_debug_get_auto_order", "wgrt_debug_get_tile_tail", "wgrt_debug_order_host",
                   "wgrt_debug_chain_plan", "wgrt_debug_chain_set_serial", "wgrt_debug_set_byte_locator",
-                  "wgrt_debug_set_palette_cap", "wgrt_debug_scene_palette", "wgrt_debug_expected_replays")
+                  "wgrt_debug_set_palette_cap", "wgrt_debug_scene_palette", "wgrt_debug_expected_replays",
+                  "wgrt_debug_chain_report")
 
 
 class WgrtError(RuntimeError):
@@ -129,6 +130,20 @@ def chain_plan(in_segment: int, serial: int, flags: int = 0) -> dict:
     check(load().wgrt_debug_chain_plan(int(in_segment), int(serial), int(flags), ctypes.byref(p)),
           "wgrt_debug_chain_plan")
     return {f: int(getattr(p, f)) for f, _ in ChainPlan._fields_}
+
+
+class ChainReport(ctypes.Structure):
+    """``wgrt_chain_report`` (include/wgrt_debug.h): what an open chain has done so far."""
+    _fields_ = [("gathering", ctypes.c_int), ("cap", ctypes.c_int), ("steps", ctypes.c_int64),
+                ("launches", ctypes.c_int64), ("fused_launches", ctypes.c_int64), ("largest_launch", ctypes.c_int64),
+                ("plain_steps", ctypes.c_int64), ("pending", ctypes.c_int64)]
+
+
+def chain_report(chain: int) -> dict:
+    """``wgrt_debug_chain_report`` of an open chain's handle (host counters; no GPU work)."""
+    r = ChainReport()
+    check(load().wgrt_debug_chain_report(ctypes.c_void_p(int(chain)), ctypes.byref(r)), "wgrt_debug_chain_report")
+    return {f: int(getattr(r, f)) for f, _ in ChainReport._fields_}
 
 
 class SceneInfo(ctypes.Structure):
@@ -274,6 +289,12 @@ def load():
         L.wgrt_debug_chain_plan.argtypes = [ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ChainPlan)]
         L.wgrt_debug_chain_set_serial.restype = st
         L.wgrt_debug_chain_set_serial.argtypes = [_vp, _vp, ctypes.c_uint32]
+    if hasattr(L, "wgrt_chain_gather"):   # the opt-in gathering chain: new within ABI 9, bound by name
+        L.wgrt_chain_gather.restype = st
+        L.wgrt_chain_gather.argtypes = [_vp, ctypes.c_int, ctypes.c_int]
+    if hasattr(L, "wgrt_debug_chain_report"):   # a chain's readout: new within ABI 9, bound by name
+        L.wgrt_debug_chain_report.restype = st
+        L.wgrt_debug_chain_report.argtypes = [_vp, ctypes.POINTER(ChainReport)]
     if hasattr(L, "wgrt_trace_fate"):   # per-ray fates and their census: new symbols within ABI 9, bound by name
         L.wgrt_trace_fate.restype = st
         L.wgrt_trace_fate.argtypes = L.wgrt_trace_opts.argtypes + [_vp, _vp, _vp]

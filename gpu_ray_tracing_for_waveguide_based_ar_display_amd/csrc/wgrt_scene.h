@@ -90,6 +90,9 @@ struct wgrt_scene {
         int64_t chain_cap = 0;
         uint32_t chain_serial = 0;
         bool chain_open = false;             // a wgrt_chain is between begin and end on this stream
+        // a gathering chain (chain_step_gather, wgrt_trace.hip): recorded behind the chain's last launch on S and
+        // queried, never waited for -- "is the stream still busy with what the chain has issued?"
+        hipEvent_t chain_ev_busy = nullptr;
     };
     std::mutex scratch_mu;
     std::map<void *, Scratch> scratch;

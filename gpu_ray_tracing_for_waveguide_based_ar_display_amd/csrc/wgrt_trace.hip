@@ -893,7 +893,15 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             start();
             taken = false;
         }
-        if (__ballot(active || waiting) == 0ull) break;   // queue exhausted, nothing in flight
+        if (__ballot(active || waiting) == 0ull) {
+            // nothing in flight: the end once the queue is exhausted.  A fused launch's refill can leave every lane
+            // free with items still queued -- 64 rays in a row that an earlier iteration abandoned are all skipped by
+            // start() -- and must then go on dequeuing: leaving here ended the wave, and with every wave's rays forced
+            // to the replay the launch, after the first such item per wave (fused launches over gathered steps meet
+            // forced bounds: tests/test_gpu_chain_gather.py).  Single launches keep the code they had.
+            if (!FUSED || exhausted) break;
+            continue;
+        }
         // single-trace launches: once the queue has run dry, the wave's remaining rays finish in
         // the tail loop below
         // (a chained step stays here while a lane still waits for its ray: the tail loop does not poll)
@@ -1319,6 +1327,7 @@ void free_scratch(wgrt_scene::Scratch &sc) {
         (void)hipFree(p);
     if (sc.chain_ev_begin) (void)hipEventDestroy(sc.chain_ev_begin);
     if (sc.chain_ev_join) (void)hipEventDestroy(sc.chain_ev_join);
+    if (sc.chain_ev_busy) (void)hipEventDestroy(sc.chain_ev_busy);
     if (sc.chain_side) (void)hipStreamDestroy(sc.chain_side);
 }
 
@@ -1444,6 +1453,9 @@ struct LaunchCfg {
     bool learn = false;    // set by plan_auto_order: this launch runs the learning instantiation ...
     bool auto_order = false;   // ... and / or is issued in the automatic order, built from the tile table as
     uint32_t order_gen = 0;    // it stood after this many learning launches
+    // a gathering chain's lone launch (chain_flush): the stream's automatic order if it is built for this batch, the
+    // natural order otherwise -- order_kernel costs as much as the launch, which a chain's rare lone launches never repay
+    bool order_cached_only = false;
     // wgrt_trace_windows: the window table the out-couplings count into and its plan's device view (NULL: none)
     double *win_table = nullptr;
     const WindowPlanView *win = nullptr;
@@ -1525,6 +1537,10 @@ wgrt_status auto_order(wgrt_scene *ms, wgrt_scene::Scratch *sc, const TraceArgs 
     std::lock_guard<std::mutex> lk(ms->scratch_mu);
     if (sc->order_rays != A.n_rays || sc->order_m != A.m || sc->order_n != A.n || sc->order_l != A.l ||
         sc->order_gen != c.order_gen) {
+        if (c.order_cached_only) {
+            *out = nullptr;
+            return WGRT_OK;
+        }
         const int64_t chunks = (A.n_rays + kChunk - 1) / kChunk;
         sc->order_rays = -1;
         hipLaunchKernelGGL(order_kernel, dim3(1), dim3(kOrderThreads), 0, st, A.m, A.n, A.l, A.n_rays, A.nx, A.ny, A.nl,
@@ -1862,6 +1878,18 @@ wgrt_chain_plan chain_plan(int64_t seg, uint32_t ser, uint32_t flags) {
     return p;
 }
 
+// The most steps a gathering chain puts into one fused launch unless its caller names fewer (wgrt_chain_gather): what
+// a memory budget for the launch's out-coupling queue (an entry per trace: ensure_scratch) allows, within [2, 64].  A fused launch's fixed cost -- its one drain
+// and its epilogue, 0.07 ms on C3 -- is 1 % of its time from 39 traces on (C3's cap under this budget).
+#ifndef WGRT_GATHER_LOG2_BYTES
+#define WGRT_GATHER_LOG2_BYTES 30
+#endif
+constexpr int64_t kGatherQueueBytes = (int64_t)1 << WGRT_GATHER_LOG2_BYTES;
+int chain_gather_cap(int64_t n_rays) {
+    const int64_t per_iter = std::max<int64_t>(n_rays, 1) * (int64_t)(sizeof(double2) + 2 * sizeof(uint32_t));
+    return (int)std::min<int64_t>(64, std::max<int64_t>(2, kGatherQueueBytes / per_iter));
+}
+
 }  // namespace
 
 // A chain between wgrt_chain_begin and wgrt_chain_end: the copied arguments of its launches and where it stands.
@@ -1880,6 +1908,14 @@ struct wgrt_chain {
     int64_t in_segment = -1;             // chained steps issued since the open segment's seed (-1: none open)
     bool failed = false;                 // a step failed: the later ones are refused
     bool prepared = false;               // begin made the side stream and sized the granules and both scratches
+    // A gathering chain (chain_step_gather): steps called while the stream is still busy with the chain's earlier
+    // launches are counted, not launched, and go out together as one fused launch.
+    bool gather = false;                 // wgrt_chain_gather chose it, before the first step
+    bool hold = false;                   // ... and that an idle stream launches nothing: only the cap, a plain step, end
+    int64_t steps_called = 0;            // wgrt_chain_step calls, gathering or not
+    int pending = 0, cap = 0;            // steps gathered so far; the most one launch takes (wgrt_chain_gather)
+    bool busy = false;                   // chain_ev_busy is recorded and has not been seen complete
+    wgrt_chain_report rep{};
 };
 
 namespace {
@@ -1960,8 +1996,88 @@ wgrt_status chain_join(wgrt_chain *ch) {
     return WGRT_OK;
 }
 
+// A gathering chain: a chain fixes every argument at begin, so steps that have not been launched
+// yet are a count, and a count of k steps is a fused launch with num_iter = k -- the launch shape that refills a
+// drained lane with the next trace's rays and has one drain per launch, not one per step.  A step goes out at
+// once when the stream has finished everything the chain issued before (nothing would be gained by holding it:
+// the GPU would stand idle); otherwise it is counted, and the count goes out as one launch when the stream is
+// seen idle at a later step, when it reaches the cap, when a step has to run as a plain launch, and at end.  "Seen
+// idle" is an event query, never a wait: nothing here blocks the host.
+
+// The launch of what has been gathered: pending == 1 is exactly the plain launch.
+wgrt_status chain_flush(wgrt_chain *ch) {
+    if (ch->pending == 0) return WGRT_OK;
+    LaunchCfg c = ch->cfg;
+    c.num_iter = ch->pending;
+    c.order_cached_only = true;
+    const wgrt_status e = trace_launch(ch->s, &ch->rays, ch->n_rays, ch->gid_offset, ch->rng, ch->eb, ch->stats, nullptr,
+                                       ch->stream, c);
+    if (e != WGRT_OK) return e;
+    ++ch->rep.launches;
+    ch->rep.fused_launches += ch->pending > 1;
+    ch->rep.largest_launch = std::max<int64_t>(ch->rep.largest_launch, ch->pending);
+    ch->pending = 0;
+    return WGRT_OK;
+}
+
+// Behind a launch of the chain: the event the next steps query.
+wgrt_status chain_mark_busy(wgrt_chain *ch) {
+    HIP_TRY(hipEventRecord(ch->sc->chain_ev_busy, (hipStream_t)ch->stream));
+    ch->busy = true;
+    return WGRT_OK;
+}
+
+wgrt_status chain_step_gather(wgrt_chain *ch) {
+    wgrt_scene *ms = ch->s;
+    uint32_t flags = would_learn(ms, ch->cfg) ? WGRT_CHAIN_LEARNS : 0u;
+    if (ch->pending == 0) {
+        // a capture that has begun on the stream since begin takes no event queries: plain launches, each at once
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        HIP_TRY(hipStreamIsCapturing((hipStream_t)ch->stream, &cap));
+        if (cap != hipStreamCaptureStatusNone) flags |= WGRT_CHAIN_CAPTURE;
+    }
+    ++ch->rep.steps;
+    if (flags) {   // a plain launch, behind what has been gathered
+        wgrt_status e = chain_flush(ch);
+        if (e == WGRT_OK)
+            e = trace_launch(ms, &ch->rays, ch->n_rays, ch->gid_offset, ch->rng, ch->eb, ch->stats, nullptr, ch->stream,
+                             ch->cfg);
+        if (e != WGRT_OK) return e;
+        ++ch->rep.launches;
+        ++ch->rep.plain_steps;
+        ch->busy = false;
+        return (flags & WGRT_CHAIN_CAPTURE) ? WGRT_OK : chain_mark_busy(ch);
+    }
+    ++ch->pending;
+    if (ch->hold && ch->pending < ch->cap) return WGRT_OK;
+    if (ch->busy && ch->pending < ch->cap) {
+        // The query is made in the relaxed capture mode: under another thread's global-mode capture (a graph being
+        // captured elsewhere in the process) an event query is otherwise refused and invalidates that capture.  This
+        // stream is not under capture (looked at above, whenever nothing is pending).
+        hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+        HIP_TRY(hipThreadExchangeStreamCaptureMode(&mode));
+        const hipError_t q = hipEventQuery(ch->sc->chain_ev_busy);
+        HIP_TRY(hipThreadExchangeStreamCaptureMode(&mode));
+        if (q == hipErrorNotReady) {
+            // not an error, and the runtime's last-error slot holds it now (whatever it held before was overwritten
+            // by the query, not by this): cleared, so that the launches' own checks do not find it
+            (void)hipGetLastError();
+            return WGRT_OK;
+        }
+        HIP_TRY(q);
+        ch->busy = false;
+    }
+    const wgrt_status e = chain_flush(ch);
+    return e == WGRT_OK ? chain_mark_busy(ch) : e;
+}
+
 wgrt_status chain_step(wgrt_chain *ch) {
     if (ch->failed) return fail(WGRT_ERR_INVALID_ARGUMENT, "an earlier step of this chain failed");
+    if (ch->gather) {
+        const wgrt_status e = chain_step_gather(ch);
+        if (e != WGRT_OK) ch->failed = true;
+        return e;
+    }
     wgrt_scene *ms = ch->s;
     hipStream_t S = (hipStream_t)ch->stream;
     wgrt_scene::Scratch *sc = ch->sc;
@@ -2152,7 +2268,47 @@ wgrt_status wgrt_chain_step(wgrt_chain *ch) {
     if (!ch) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL chain");
     if (ch->n_rays == 0) return WGRT_OK;
     DEVICE_SCOPE(dev_scope, ch->s->device);
+    ++ch->steps_called;
     return chain_step(ch);
+}
+
+wgrt_status wgrt_chain_gather(wgrt_chain *ch, int max_steps, int hold) {
+    if (!ch) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL chain");
+    if (max_steps != 0 && (max_steps < 2 || max_steps > 64))
+        return fail(WGRT_ERR_INVALID_ARGUMENT, "max_steps must be 0 or 2 .. 64");
+    if (ch->steps_called || ch->gather)
+        return fail(WGRT_ERR_INVALID_ARGUMENT, "wgrt_chain_gather comes once, before the chain's first step");
+    // (a chain that stays serial -- a flag, or a capture at begin -- keeps issuing plain launches)
+    if (ch->n_rays == 0 || ch->flags || !ch->prepared) return WGRT_OK;
+    wgrt_scene *ms = ch->s;
+    DEVICE_SCOPE(dev_scope, ms->device);
+    {
+        std::lock_guard<std::mutex> lk(ms->scratch_mu);
+        if (!ch->sc->chain_ev_busy) HIP_TRY(hipEventCreateWithFlags(&ch->sc->chain_ev_busy, hipEventDisableTiming));
+    }
+    // the caller's stream's scratch at the largest launch the chain can make: cap traces of every ray in one fused
+    // launch, on the largest grid among that launch, a plain step and a learning one; a cap the device has no
+    // memory for is halved
+    const int item = (ch->cfg.dbg && ch->cfg.dbg->chunk_rays > 0) ? std::min(ch->cfg.dbg->chunk_rays, 64) : kChunk;
+    int cap = max_steps ? std::min(max_steps, chain_gather_cap(ch->n_rays)) : chain_gather_cap(ch->n_rays);
+    for (;; cap /= 2) {
+        LaunchCfg fused = ch->cfg, learning = ch->cfg;
+        fused.num_iter = cap;
+        learning.learn = true;
+        int64_t grid = 1;
+        for (const LaunchCfg *k : {&ch->cfg, &fused, &learning})
+            grid = std::max(grid, launch_grid(ms, ch->n_rays, item, *k));
+        wgrt_scene::Scratch *tmp = nullptr;
+        const wgrt_status e = ensure_scratch(ms, ch->stream, ch->n_rays, cap, grid, &tmp);
+        if (e == WGRT_OK) break;
+        if (cap / 2 < 2) return e;
+    }
+    ch->gather = true;
+    ch->hold = hold != 0;
+    ch->cap = cap;
+    ch->rep.gathering = 1;
+    ch->rep.cap = cap;
+    return WGRT_OK;
 }
 
 wgrt_status wgrt_chain_end(wgrt_chain *ch) {
@@ -2160,7 +2316,8 @@ wgrt_status wgrt_chain_end(wgrt_chain *ch) {
     wgrt_status e = WGRT_OK;
     if (ch->sc) {
         DeviceScope dev_scope(ch->s->device);
-        e = chain_join(ch);
+        if (ch->gather && !ch->failed) e = chain_flush(ch);   // what was gathered last; the stream orders the rest
+        else e = chain_join(ch);
         std::lock_guard<std::mutex> lk(ch->s->scratch_mu);
         ch->sc->chain_open = false;
     }
@@ -2172,6 +2329,13 @@ wgrt_status wgrt_debug_chain_plan(int64_t in_segment, uint32_t serial, uint32_t 
     if (!out || in_segment < -1 || serial > WGRT_CHAIN_SERIAL_MAX)
         return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL out / bad in_segment / serial");
     *out = chain_plan(in_segment, serial, flags);
+    return WGRT_OK;
+}
+
+wgrt_status wgrt_debug_chain_report(const wgrt_chain *ch, wgrt_chain_report *out) {
+    if (!ch || !out) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL chain / out");
+    *out = ch->rep;
+    out->pending = ch->pending;
     return WGRT_OK;
 }
 

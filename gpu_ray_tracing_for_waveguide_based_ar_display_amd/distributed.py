@@ -194,13 +194,15 @@ def run_steps(trace_fn, rays, rng, eb, gid: GidMap, steps: int, per_call: int = 
     of k separate ones).  ``eb`` is handed to ``trace_fn`` as it is: None for a tracer that carries the
     window-table sink alone (``hip_tracer(windows=...)``).  ``hook(j, "start" | "end")`` brackets call j (HIP events in bench.py).
     Separate launches (``per_call == 1``, more than one step, no hook) of a tracer that offers ``chain`` are issued
-    as one: still one kernel launch per trace, the same results, consecutive launches overlapping.
+    through it.  ``hip_tracer``'s chain gathers (``engine.TraceChain(gather=True)``): this loop calls its steps back
+    to back and reads nothing in between, so the steps called while the GPU is still busy go out as fused launches --
+    the same results, fewer launches than traces.
     Returns the traces per call."""
     calls = split_calls(steps, per_call)
     chain = getattr(trace_fn, "chain", None)
     if chain is not None and per_call == 1 and steps > 1 and hook is None:
-        # separate launches all the same, issued as a chain: consecutive launches overlap across two hardware
-        # queues (engine.TraceChain).  With a hook the calls stay plain launches: it brackets each one on the stream
+        # separate traces all the same, issued through the tracer's chain (hip_tracer: a gathering one).  With a hook
+        # the calls stay plain launches: it brackets each one on the stream
         with chain(rays, rng, eb, gid) as ch:
             for _ in calls:
                 ch.step()
@@ -496,7 +498,8 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, rep
     of such a job is ``reduce_eyebox(table)``, one sum-reduce: no slab list, no scatter.
 
     ``fn.chain(rays, rng, eb, gid)`` returns an ``engine.TraceChain`` over the same arguments: a context whose
-    ``step()`` is one such call with ``num_iter = 1``.
+    ``step()`` is one such call with ``num_iter = 1``.  It is a gathering chain (``gather=True``): what uses it
+    (``run_steps``) calls the steps back to back and touches nothing before the chain ends.
 
     ``fate``: a uint8 device tensor every call stores the rays' fate codes in (``engine.trace_fullcolor(fate=...)``:
     single launches only, so ``num_iter`` must stay 1); such a tracer offers no ``chain`` (a chain takes no fates),
@@ -522,7 +525,10 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, rep
 
     def chain(rays, rng, eb, gid: GidMap):
         """The same launches as a chain (``run_steps`` uses it for separate launches without a hook)."""
-        return TraceChain(scene, rays, rng, eb, stats=stats, variant=variant, windows=windows, **ids_of(rng, gid))
+        # (a build of the library from before wgrt_chain_gather, tools/with_lib.py: the plain two-queue chain)
+        from ._lib import load
+        return TraceChain(scene, rays, rng, eb, stats=stats, variant=variant, windows=windows,
+                          gather=hasattr(load(), "wgrt_chain_gather"), **ids_of(rng, gid))
     if fate is None and int(replicas or 0) < 2 and not expected:
         fn.chain = chain
     return fn

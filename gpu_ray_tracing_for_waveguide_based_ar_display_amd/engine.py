@@ -339,7 +339,7 @@ def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ra
 
 class TraceChain:
     """A chain of single traces of one batch (``wgrt_chain_begin`` / ``_step`` / ``_end``): each ``step()`` is one
-    launch (``num_iter = 1``) and the chain leaves exactly what as many ``trace_fullcolor`` calls leave --
+    trace (``num_iter = 1``) and the chain leaves exactly what as many ``trace_fullcolor`` calls leave --
     ``rng_states``, ``matrix_EB`` / window table and ``stats``, bit for bit -- but consecutive launches run on two
     hardware queues, so one launch's drain is covered by the next one's bulk (DESIGN.md §4.3).  A context manager::
 
@@ -349,7 +349,18 @@ class TraceChain:
 
     Takes ``trace_fullcolor``'s arguments (no ``per_ray_bounces``).  Between ``__enter__`` and ``__exit__`` nothing
     else may touch ``rng_states``, ``matrix_EB``, the window table or ``stats`` on the stream; after ``__exit__``
-    the stream is ordered after every step.  The chain holds references to every tensor until it ends, and
+    the stream is ordered after every step.
+
+    ``gather=True`` (or a cap of 2 .. 64 steps) opts into ``wgrt_chain_gather``, for a caller that calls its steps back
+    to back and reads nothing before the end: a step called while the stream is still busy with the chain's earlier
+    launches is not enqueued but counted, and the count goes out as one fused launch when a later step finds the
+    stream idle, at the cap, and at the end (``hold=True``: only at the cap and at the end).  Such a step's work
+    starts no earlier than a later ``step()`` or the end, the stream's launch scratch grows to the cap (24 bytes per
+    ray and step; 1 GiB by default) and stays, and ``stats``' ``replayed`` is the fused launches' count (a ray a launch
+    abandons counts once in it): at most the plain launches'.  Everything else stays bit for bit.  ``report()`` says
+    what an open chain has launched.
+
+    The chain holds references to every tensor until it ends, and
     ``__exit__`` always ends it, also on an exception.  Steps that cannot be chained (the scene's learning
     launches, variant 1, ``chunk_order``, a debug timeline, a stream under capture) run as plain launches."""
 
@@ -357,7 +368,8 @@ class TraceChain:
                  gid_offset: int = 0, n_rays: int | None = None, stats: torch.Tensor | None = None, stream=None,
                  variant: int = VARIANT_AUTO, workgroups: int = 0, chunk_order: torch.Tensor | None = None,
                  gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
-                 grid_sqrt_k: float = 0.0, windows=None, replicas: int = 0, expected: bool = False):
+                 grid_sqrt_k: float = 0.0, windows=None, replicas: int = 0, expected: bool = False,
+                 gather: bool | int = False, hold: bool = False):
         if scene.single_lambda:
             raise ValueError("TraceChain needs a full-colour scene")
         if expected:
@@ -371,6 +383,13 @@ class TraceChain:
                                      gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k,
                                      windows=windows, chain=True)
         self.steps = 0
+        if gather:
+            try:
+                check(load().wgrt_chain_gather(ctypes.c_void_p(self._h), 0 if gather is True else int(gather),
+                                               int(bool(hold))), "wgrt_chain_gather")
+            except Exception:
+                self.end()
+                raise
 
     def step(self) -> None:
         if not self._h:
@@ -379,6 +398,13 @@ class TraceChain:
         if status:
             check(status, "wgrt_chain_step")
         self.steps += 1
+
+    def report(self) -> dict:
+        """``wgrt_debug_chain_report``: steps, launches, fused launches, the largest launch, steps still pending."""
+        if not self._h:
+            raise WgrtError("the chain has ended")
+        from ._lib import chain_report
+        return chain_report(self._h)
 
     def end(self) -> None:
         h, self._h = self._h, 0

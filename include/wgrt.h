@@ -407,6 +407,32 @@ wgrt_status wgrt_chain_begin(const wgrt_scene *scene, const wgrt_rays *rays, int
 wgrt_status wgrt_chain_step(wgrt_chain *chain);
 wgrt_status wgrt_chain_end(wgrt_chain *chain);
 
+/* A gathering chain: opt-in, for a caller that calls its steps back to back and reads nothing before end (new
+ * symbol within ABI 9, looked up by name).  A chain fixes every argument at begin, so steps not yet launched are a
+ * count, and a count of k steps is a fused launch (num_iter = k) -- the launch shape with one drain per launch, not
+ * one per step.  Called between begin and the first step, it changes how that chain's steps are issued:
+ *   - a step called when `stream` has finished everything the chain issued before is launched at once, as the
+ *     plain launch it is (hold != 0: it is counted like the others);
+ *   - a step called while the stream is still busy is counted, not enqueued; the count goes out as ONE fused launch
+ *     when a later step finds the stream idle, when it reaches the cap, before a step that must run as a plain
+ *     launch, and at end.  "Finds idle" is an event query: no call waits for the device.
+ * What the caller gives up against a plain chain, and must be able to afford:
+ *   - a counted step's work starts no earlier than a later step or end call, however long the caller takes to make
+ *     it: a caller that does host work between steps leaves the GPU idle with steps pending, and an event it
+ *     records on `stream` after a step does not follow that step's work.  Only end orders the stream after every
+ *     step.
+ *   - memory: this call grows the stream's launch scratch to the cap (24 bytes per ray and step of the cap), and the
+ *     stream keeps it.  The cap is max_steps (2 .. 64; 0: as many as 1 GiB of scratch allows, at most 64, at least
+ *     2); when the allocation fails the cap is halved until it succeeds, and WGRT_ERR_HIP is returned only when
+ *     a cap of 2 fails too.  The call may synchronise the stream.
+ *   - wgrt_trace_stats.replayed: a fused launch counts a ray it abandons once and finishes its remaining traces
+ *     on the exact lane, so on LUTs and bounds that abandon rays the count is at most the plain launches' per-trace
+ *     count.  rng_states, matrix_EB / table and every other counter stay bit for bit what plain launches leave.
+ * Steps that a plain chain runs as plain launches still do (the rule above), behind what has been gathered.  On a
+ * chain that stays serial for one of those reasons the call succeeds and changes nothing.  After the first step it
+ * is WGRT_ERR_INVALID_ARGUMENT.  wgrt_debug_chain_report (wgrt_debug.h) says what a chain has launched. */
+wgrt_status wgrt_chain_gather(wgrt_chain *chain, int max_steps, int hold);
+
 /* Where every ray ends: per-ray fates and the per-tile census (new symbols within ABI 9, looked up by name).
  *
  * A ray's fate is the code 10 * region + reason of the place its trace ended (csrc/wgrt_fate.h states it once;

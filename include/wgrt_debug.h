@@ -149,6 +149,22 @@ wgrt_status wgrt_debug_chain_plan(int64_t in_segment, uint32_t serial, uint32_t 
 /* Sets the tag serial of the stream's granules (clearing them), so that a test reaches WGRT_CHAIN_SERIAL_MAX
  * within a few steps.  No chain may be open on the stream.  Waits for the stream. */
 wgrt_status wgrt_debug_chain_set_serial(const wgrt_scene *scene, void *stream, uint32_t serial);
+/* What an open chain has done so far (host counters; no device).  A gathering chain (wgrt_chain_gather, wgrt.h)
+ * launches a step at once when the stream has finished what the chain issued before, and otherwise counts it;
+ * counted steps go out as one fused launch.  steps - plain_steps steps went into launches - plain_steps gathered
+ * launches, of which fused_launches carried more than one step, the largest largest_launch; steps not yet launched
+ * are pending.  A chain that does not gather reports gathering = 0 and zeros. */
+typedef struct {
+    int gathering;            /* 1: wgrt_chain_gather took effect; 0: one kernel per step (two queues, or plain)    */
+    int cap;                  /* gathering: the most steps one launch takes                                          */
+    int64_t steps;            /* gathering: wgrt_chain_step calls so far                                             */
+    int64_t launches;         /* ... trace launches made for them                                                    */
+    int64_t fused_launches;   /* ... of which carried more than one step                                             */
+    int64_t largest_launch;   /* ... the most steps in one launch                                                    */
+    int64_t plain_steps;      /* ... steps that ran as plain launches (learning launches, a stream under capture)    */
+    int64_t pending;          /* ... steps counted and not yet launched                                              */
+} wgrt_chain_report;
+wgrt_status wgrt_debug_chain_report(const wgrt_chain *chain, wgrt_chain_report *out);
 
 #ifdef __cplusplus
 }
