@@ -36,7 +36,8 @@ EXPORTED_DEBUG = ("wgrt_debug_shadow", "wgrt_debug_scene_copy", "wgrt_debug_set_
                   "wgrt_debug_get_auto_order", "wgrt_debug_get_tile_tail", "wgrt_debug_order_host",
                   "wgrt_debug_chain_plan", "wgrt_debug_chain_set_serial", "wgrt_debug_set_byte_locator",
                   "wgrt_debug_set_palette_cap", "wgrt_debug_scene_palette", "wgrt_debug_expected_replays",
-                  "wgrt_debug_chain_report")
+                  "wgrt_debug_chain_report", "wgrt_debug_set_fused_run", "wgrt_debug_fused_run",
+                  "wgrt_debug_fused_items_host")
 
 
 class WgrtError(RuntimeError):
@@ -335,6 +336,14 @@ def load():
         L.wgrt_debug_set_palette_cap.argtypes = [ctypes.c_int]
         L.wgrt_debug_scene_palette.restype = st
         L.wgrt_debug_scene_palette.argtypes = [_vp] + [ctypes.POINTER(ctypes.c_int)] * 3
+    if hasattr(L, "wgrt_debug_set_fused_run"):   # fused launches' runs: new symbols within ABI 9, bound by name
+        L.wgrt_debug_set_fused_run.restype = st
+        L.wgrt_debug_set_fused_run.argtypes = [ctypes.c_int]
+        L.wgrt_debug_fused_run.restype = st
+        L.wgrt_debug_fused_run.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        L.wgrt_debug_fused_items_host.restype = st
+        L.wgrt_debug_fused_items_host.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                                  ctypes.c_int64, _vp, _vp, _vp, _i64]
     L.wgrt_status_string.restype = ctypes.c_char_p
     L.wgrt_status_string.argtypes = [ctypes.c_int]
     L.wgrt_last_error.restype = ctypes.c_char_p
@@ -554,6 +563,32 @@ def locator_classify_host(geom, luts, xy: np.ndarray, cell_mm: float = 0.125) ->
 def set_byte_locator(on: bool) -> None:
     """``wgrt_debug_set_byte_locator``: the Jones-vector lane's byte locator on / off, process-wide (A/B, tests)."""
     check(load().wgrt_debug_set_byte_locator(1 if on else 0), "wgrt_debug_set_byte_locator")
+
+
+def set_fused_run(run: int = 0) -> None:
+    """``wgrt_debug_set_fused_run``: the run length of fused launches, process-wide (A/B, tests): 0 automatic, 1 a
+    hand-off after every trace, n (a power of two up to 64) runs of n traces on one lane."""
+    check(load().wgrt_debug_set_fused_run(int(run)), "wgrt_debug_set_fused_run")
+
+
+def fused_run(num_iter: int, handoff_bound: bool = False) -> int:
+    """``wgrt_debug_fused_run``: the run length a fused launch of ``num_iter`` traces runs with now (no GPU needed)."""
+    run = ctypes.c_int()
+    check(load().wgrt_debug_fused_run(int(num_iter), 1 if handoff_bound else 0, ctypes.byref(run)), "wgrt_debug_fused_run")
+    return run.value
+
+
+def fused_items_host(n_chunks: int, num_iter: int, run: int, head: int):
+    """``wgrt_debug_fused_items_host``: every work item of ``head``'s queue, in order, from the code the kernels compile
+    (no GPU needed): ``(chunk, first_trace, end_trace)`` arrays, one entry per item."""
+    cap = (int(n_chunks) + 1) * ((int(num_iter) + int(run) - 1) // int(run)) + 1
+    chunk, k0, k1 = np.zeros(cap, np.int64), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+    n = ctypes.c_int64()
+    check(load().wgrt_debug_fused_items_host(int(n_chunks), int(num_iter), int(run), int(head), 0, cap, chunk.ctypes.data,
+                                             k0.ctypes.data, k1.ctypes.data, ctypes.byref(n)),
+          "wgrt_debug_fused_items_host")
+    assert n.value < cap, "the head's queue ends before the buffer does"
+    return chunk[:n.value], k0[:n.value], k1[:n.value]
 
 
 def set_palette_cap(cap: int = 256) -> None:

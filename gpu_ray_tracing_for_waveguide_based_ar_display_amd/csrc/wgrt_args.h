@@ -126,7 +126,10 @@ struct TraceArgs {
     // the replica in its out-coupling queue entry (the REPS instantiations).  Single launches only.  Last again.
     int64_t win_rep_stride;
     int32_t win_reps;
-    int32_t pad_reps_;
+    // fused launches: the run length, the consecutive traces of a ray one work item covers and one lane keeps the
+    // ray for (wgrt_items.h; a power of two, 1: an item per trace).  In the word that padded the struct, so every
+    // other field and the kernel parameters behind it keep their places in the kernarg segment.
+    int32_t fused_run;
 };
 
 // The replica of global ray id g >= 0 among reps (2 .. 64) copies: g % reps from 32-bit remainders (the 64-bit

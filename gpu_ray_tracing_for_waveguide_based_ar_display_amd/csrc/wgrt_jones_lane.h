@@ -194,6 +194,45 @@ __device__ __forceinline__ bool lane_load_staged(const LdsU32 *S, int j, int64_t
     return tix != kBadTix;
 }
 
+// Fused launches, whose lanes keep a ray for a run of chained traces (wgrt_items.h): the lane's private copy of
+// the prepared slot, word w of it at R[w * 64] (R is the lane's own column of its wave's block: lane-indexed,
+// conflict-free).  x, y, te, Etm's real and imaginary parts; the tile index stays in JLane::tix, the RNG state in
+// the ray; word kRunS0 is the caller's (the state the run began from).
+constexpr int kRunS0 = 7;
+constexpr int kRunCols = 8;
+
+// Slot j of a prepared chunk -> the lane's private copy (at the ray's first start of a run).
+__device__ __forceinline__ void keep_slot(const LdsU32 *S, int j, LdsU32 *R) {
+    R[0 * 64] = S[0 * 64 + j];
+    R[1 * 64] = S[1 * 64 + j];
+    R[2 * 64] = S[5 * 64 + j];
+    R[3 * 64] = S[3 * 64 + j];
+    R[4 * 64] = S[4 * 64 + j];
+    R[5 * 64] = S[6 * 64 + j];
+    R[6 * 64] = S[7 * 64 + j];
+}
+
+// The ray's next trace of the run from the private copy: the start state lane_load_staged sets, with the ray
+// index, the tile index and the RNG state (where the trace before left it) as they stand.
+__device__ __forceinline__ void lane_restart(const LdsU32 *R, JLane &L) {
+    L.r.x = (double)__uint_as_float(R[0 * 64]);
+    L.r.y = (double)__uint_as_float(R[1 * 64]);
+    L.r.er = (double)__uint_as_float(R[2 * 64]);
+    L.r.ei = 0.0;
+    L.r.mr = __longlong_as_double((long long)(((uint64_t)R[4 * 64] << 32) | R[3 * 64]));
+    L.r.mi = __longlong_as_double((long long)(((uint64_t)R[6 * 64] << 32) | R[5 * 64]));
+    L.r.cos_t = 1.0;
+    L.r.ener = 1.0;
+    L.r.eerr = 0.0;
+    L.r.amp = 1.0f;
+    L.r.gx = L.r.gy = 0.0;
+    L.r.hr = 1.0;
+    L.r.hi = 0.0;
+    L.r.region = 0;
+    L.bounces = 1;
+    L.inter = 0;
+}
+
 struct JField {
     double er, ei, mr, mi;
 };

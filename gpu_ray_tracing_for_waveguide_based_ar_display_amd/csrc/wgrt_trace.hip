@@ -35,6 +35,7 @@
 #include "../../include/wgrt_debug.h"
 #include "wgrt_common.h"
 #include "wgrt_exact_lane.h"
+#include "wgrt_items.h"
 #include "wgrt_jones_lane.h"
 #include "wgrt_launch_args.h"
 #include "wgrt_order.h"
@@ -72,6 +73,7 @@ __global__ __launch_bounds__(256) void trace_grid_ev_kernel(TraceArgs A) {
 // launch's epilogue totals (a Counters record) and done count.
 constexpr int kHeadStride = 16;   // unsigned long longs between slots (128 B)
 constexpr int kHeads = 8;
+static_assert(kHeads == kItemHeads, "wgrt_items.h decodes the positions of these heads");
 enum CtrSlot : int { kSlotHeads, kSlotReplay = kHeads, kSlotQueue, kSlotFull, kSlotEpiAcc, kSlotEpiDone, kSlots };
 constexpr int kScratchCtr = kSlots * kHeadStride;
 static_assert(kCtrWords <= kHeadStride, "the epilogue totals share one line");
@@ -196,6 +198,7 @@ constexpr int kFusedRefill = 16;
 #define WGRT_STRIPE 16
 #endif
 constexpr int64_t kStripe = WGRT_STRIPE;   // chunks per stripe of the work queue (1024 rays: one C3 tile)
+static_assert(kStripe == kItemStripe, "wgrt_items.h decodes these stripes");
 
 // Compiler-visible waits (round 6).  A pass already waits for every load in flight before
 // advance() reads the cell word; stating that wait with the builtin at the top of the pass (and the staging
@@ -458,7 +461,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
     // per-lane totals in 32 bits: a lane's bounce total is added to the stats directly before it
     // could overflow (2^31 bounces on one lane: never in practice)
     uint32_t tot_b = 0, tot_bad = 0, tot_giveup = 0, tot_int = 0;
-    unsigned long long wait_t0 = 0;    // fused: when this lane started waiting for its ray (s_memrealtime)
+    unsigned long long wait_t0 = 0;    // chained step: when this lane started waiting for its ray (s_memrealtime)
     uint32_t wait_passes = 0;          // ... and the wave's passes since then
     unsigned long long qbase = 0;      // this wave's block of out-coupling slots ...
     int qfill = kQBlock;               // ... and how many of them are used (none reserved yet)
@@ -486,23 +489,12 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
     // ended the launch 60 us after the first (striping: -6 % per single launch on C3) -- while
     // a stripe's rays still share their tiles in that die's L2.
     const int64_t ns = (n_chunks + kStripe - 1) / kStripe, last = n_chunks - (ns - 1) * kStripe;
+    // (wgrt_items.h: the mapping, shared with the host.)  FUSED: an item is a run of A.fused_run consecutive traces
+    // of its chunk's rays, k the run's first trace
+    const uint32_t run = FUSED ? (uint32_t)A.fused_run : 1u;
+    const int64_t n_runs = FUSED ? (n_iter + run - 1) / run : 1;
     auto decode = [&](int x, int64_t q, int64_t &c, uint32_t &k) -> bool {
-        if (x >= ns) return false;
-        int64_t cx = ((ns - x + kHeads - 1) / kHeads) * kStripe;
-        if ((ns - 1) % kHeads == x) cx -= kStripe - last;
-        if (q >= cx * n_iter) return false;
-        // the item's iteration: 0 for a single trace; else q / cx (< 256) from a double quotient,
-        // corrected -- no 64-bit integer division on the dequeue path
-        int64_t kk = 0;
-        if (FUSED) {
-            kk = (int64_t)((double)q / (double)cx);
-            kk -= kk * cx > q;
-            kk += (kk + 1) * cx <= q;
-        }
-        k = (uint32_t)kk;
-        const int64_t r = q - kk * cx;
-        c = ((r / kStripe) * kHeads + x) * kStripe + r % kStripe;
-        return true;
+        return item_decode<FUSED>(ns, last, n_runs, run, x, q, c, k);
     };
     // this wave's two LDS buffers of staged ray columns (wgrt_jones_lane.h stage_chunk): a refill takes
     // rays of at most two chunks, the one being used up and the next
@@ -513,6 +505,22 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
     // ranges of at most 64 rays.
     int sb = 0;
     uint32_t sbase = 0, sbase_prev = 0;
+    // FUSED: the lane's private copy of its ray's prepared slot (kRunCols words, word-major: lane-indexed, so no
+    // bank conflicts), written at the ray's first start of a run and read at every restart inside the run -- the
+    // staged buffers hold a chunk only until the wave stages the chunk after next, a ray stays for a run.  Word
+    // kRunS0: the state the run began from, which its last trace's publish compares the granule against.
+    // A trace that ends inside its run leaves kAgain in blk (no register of its own), which the next pass's restart
+    // site takes: blk is dead once a trace has ended, and every start sets it.
+    constexpr int kAgain = -6;
+    static_assert(kAgain != kDie && kAgain != kTransit && kAgain != kUncertain && kAgain != kOut && kAgain != kDieIc,
+                  "kAgain is no value advance() or interact() returns");
+    LdsU32 *run_lds = nullptr;
+    if constexpr (FUSED) {
+        __shared__ uint32_t run_buf[4 * kRunCols * 64];
+        run_lds = (LdsU32 *)&run_buf[0];
+    }
+    // (worked out where it is used: an address held across the wave loop would cost the loop a VGPR)
+    auto rslot_of = [&]() -> LdsU32 * { return run_lds + (threadIdx.x >> 6) * (kRunCols * 64) + (threadIdx.x & 63); };
     // start the trace (L.i, L.k) on this lane: active, waiting (previous trace still running) or
     // skipped (bad ray / ray already handed to the replay)
     auto start = [&]() {
@@ -525,19 +533,38 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
         waiting = false;
         active = false;
         if (__builtin_expect(!ok, 0)) {
+            // FUSED: once per trace the item covers (a bad ray has no granule: nothing is handed on)
             ++tot_bad;
+            if constexpr (FUSED) tot_bad += run_end(L.k, run, (uint32_t)n_iter) - L.k - 1u;
             if (FATE) KA(fate)[L.i] = 0;   // no trace
             return;
         }
+        // the run's restarts find the ray here (a waiting lane's too: its staged slot may be gone by then); runs of
+        // one never restart (wave-uniform: a scalar branch)
+        if constexpr (FUSED)
+            if (run > 1u)
+                keep_slot(sbufs + (in_cur ? sb : sb ^ 1) * (kStageCols * 64), (int)(in_cur ? oc : L.i - sbase_prev),
+                          rslot_of());
         if (FUSED && L.k > 0) {
             const uint32_t tag = (uint32_t)w;
             if (tag == iter_tag(A.iter_epoch, L.k, false)) {
                 L.r.s = (uint32_t)(w >> 32);
+                if constexpr (FUSED) rslot_of()[kRunS0 * 64] = L.r.s;
             } else if ((tag >> 8) == ((A.iter_epoch << 1) | 1u)) {
                 return;   // abandoned in an earlier iteration: the replay kernel finishes it
             } else {
+                // (the time goes where the waiting lane has two idle words: the ray's RNG state and replay point are
+                // set when the wait ends; a register of its own cost the 64-bit AMP kernel scratch in the wave loop)
                 waiting = true;
-                wait_t0 = __builtin_amdgcn_s_memrealtime();
+                if constexpr (FUSED) {
+                    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+                    L.s0 = (uint32_t)t0;
+                    L.r.s = (uint32_t)(t0 >> 32);
+                } else {
+                    // (never runs: the other instantiations keep the statement they had here, and with it their
+                    // closures' layout and the chained kernels' register allocation)
+                    wait_t0 = __builtin_amdgcn_s_memrealtime();
+                }
                 wait_passes = 0;
                 return;
             }
@@ -579,16 +606,24 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
         }
         if (FUSED && (int64_t)L.k + 1 < n_iter) {
             const uint64_t hand = ((uint64_t)L.r.s << 32) | iter_tag(A.iter_epoch, L.k + 1, false);
-            if (L.k > 0) {
-                // the granule still holds what this trace started from, unless the waiter for the next
+            // (only a run's last trace comes here: L.k + 1 is the next run's first trace)
+            uint32_t k0 = L.k, s_k0 = L.s0;
+            if constexpr (FUSED) {   // (compile-time, like every use of the run's state in these lambdas: a single
+                                     // launch's closures capture what the parent's did)
+                k0 = L.k & ~(run - 1u);
+                if (k0 > 0) s_k0 = rslot_of()[kRunS0 * 64];
+            }
+            if (k0 > 0) {
+                // the granule still holds what this run started from (the state kept beside the ray's private
+                // slot: L.s0 is the current trace's replay point), unless the waiter for the next
                 // trace has given up and marked the ray abandoned meanwhile: the mark then stays (a
                 // compare-and-swap whose result is not used: no return, no wait), so the ray's later
                 // traces skip it instead of each waiting out the bound again
-                uint64_t was = ((uint64_t)L.s0 << 32) | iter_tag(A.iter_epoch, L.k, false);
+                uint64_t was = ((uint64_t)s_k0 << 32) | iter_tag(A.iter_epoch, k0, false);
                 __hip_atomic_compare_exchange_strong(KA(rng64) + L.i, &was, hand, __ATOMIC_RELAXED,
                                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             } else {
-                // trace 0 read no granule (its start state is rng_states): a give-up that raced this
+                // the first run read no granule (its start state is rng_states): a give-up that raced this
                 // store costs the ray's next waiter one more bound before it gives up too
                 __hip_atomic_store(KA(rng64) + L.i, hand, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
@@ -706,7 +741,14 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
                 record_abandoned(K, L.i);
                 active = false;
             } else if (next < 0) {
-                retire();
+                // inside a run the ray starts its next trace on this lane, at the next pass's restart site; a run's
+                // last trace publishes at once (the hand-off would wait a pass)
+                if constexpr (FUSED) {
+                    if (L.k + 1u < run_end(L.k, run, (uint32_t)n_iter)) blk = kAgain, active = false;
+                    else retire();
+                } else {
+                    retire();
+                }
             }
         }
     };
@@ -751,7 +793,29 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             blk = advance<FATE>(A, K, loc, L, kind, &fate);
             entry = false;
             if (!FUSED) fin |= blk == kDie;
-            else if (blk == kDie) retire();
+            else if (blk == kDie) {
+                if (L.k + 1u < run_end(L.k, run, (uint32_t)n_iter)) blk = kAgain, active = false;
+                else retire();
+            }
+        }
+        if (FUSED && blk == kAgain) {
+            // the one restart site of a pass: the trace that ended here or in the last pass's interaction adds its
+            // counters, and the ray's next trace starts on this lane from the state as it stands -- no granule, no
+            // work item, no staging, no refill; its entry interaction runs in this pass
+            tot_b += L.bounces;
+            tot_int += L.inter;
+            if (__builtin_expect(tot_b >= 0x80000000u, 0)) {
+                wgrt_trace_stats *const st = KA(stats);
+                if (st) atomicAdd((unsigned long long *)&st->bounces, (unsigned long long)tot_b);
+                tot_b = 0;
+            }
+            ++L.k;
+            lane_restart(rslot_of(), L);
+            L.s0 = L.r.s;
+            active = true;
+            blk = 0;
+            kind = 0;
+            entry = true;
         }
         if (!FUSED && fin) {   // before the refill, which reuses the lane
             retire();
@@ -765,6 +829,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             if (tag == iter_tag(A.iter_epoch, L.k, false)) {
                 L.r.s = (uint32_t)(w >> 32);
                 L.s0 = L.r.s;
+                rslot_of()[kRunS0 * 64] = L.r.s;
                 waiting = false;
                 active = true;
                 blk = 0;
@@ -773,7 +838,8 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             } else if ((tag >> 8) == ((A.iter_epoch << 1) | 1u)) {
                 waiting = false;   // abandoned in an earlier iteration: the replay kernel finishes it
             } else if ((++wait_passes > A.handoff_min_passes) &
-                       (__builtin_amdgcn_s_memrealtime() - wait_t0 > A.handoff_wait_ticks)) {
+                       (__builtin_amdgcn_s_memrealtime() - (((unsigned long long)L.r.s << 32) | L.s0) >
+                        A.handoff_wait_ticks)) {
                 // hand-off never arrived: give the trace up, visibly, and mark the ray abandoned from this
                 // trace on, so that its later traces skip it instead of each waiting out the bound again (the
                 // call's results are invalid; the Python layer raises).  Only if the granule still holds the
@@ -1487,6 +1553,25 @@ bool byte_locator_applies(const wgrt_scene *s, int variant) {
     return g_byte_locator.load(std::memory_order_relaxed) && s->d_cells8 && (variant == 9 || (variant == 7 && s->d_palette32));
 }
 
+// wgrt_debug_set_fused_run: the run length of fused launches, process-wide (the same-binary A/B; 0: the rule below).
+std::atomic<int> g_fused_run{0};
+
+// The run length of a fused launch of num_iter traces (wgrt_items.h; TraceArgs::fused_run).  Inside a run a ray
+// stays on its lane, so longer runs save hand-offs, dequeues and staging; but a launch's last run drains with
+// nothing behind it to fill the chip, and that drain grows with the run.  The rule keeps at least four runs per
+// launch: the largest power of two <= num_iter / 4, at most kAutoRunMax (DESIGN.md §5.4 has the sweep: on C3 runs
+// of 8 and 16 tie at 39 traces, 16 leads at 200, 32 loses at both).  A call
+// with a debug hand-off bound asks for hand-offs and gets them: run 1.  An explicit switch value wins over both.
+constexpr int kAutoRunMax = 16;
+int fused_run_for(int num_iter, const wgrt_debug_opts *dbg) {
+    const int set = g_fused_run.load(std::memory_order_relaxed);
+    if (set > 0) return set;
+    if (dbg && dbg->handoff_wait_ticks) return 1;
+    int run = 1;
+    while (run * 2 <= kAutoRunMax && run * 2 * 4 <= num_iter) run *= 2;
+    return run;
+}
+
 // wgrt_debug_set_auto_order: the automatic issue order (and its learning launches) on / off, process-wide.
 std::atomic<int> g_auto_order{1};
 
@@ -1655,6 +1740,7 @@ TraceArgs fill_args(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, 
     A.timeline = c.timeline ? dbg->timeline : nullptr;
     A.timeline_waves = c.timeline ? dbg->timeline_waves : 0;
     A.n_iter = 1;
+    A.fused_run = 1;
     return A;
 }
 
@@ -1715,6 +1801,7 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
     }
     if (num_iter > 1) {
         A.n_iter = num_iter;
+        A.fused_run = fused_run_for(num_iter, dbg);
         A.rng64 = sc->rng64;
         A.iter_epoch = epoch;
         A.handoff_wait_ticks = (dbg && dbg->handoff_wait_ticks) ? dbg->handoff_wait_ticks
@@ -2380,6 +2467,40 @@ wgrt_status wgrt_debug_set_auto_order(int on) {
 
 wgrt_status wgrt_debug_set_byte_locator(int on) {
     g_byte_locator.store(on != 0, std::memory_order_relaxed);
+    return WGRT_OK;
+}
+
+wgrt_status wgrt_debug_set_fused_run(int run) {
+    if (run < 0 || run > kMaxFusedRun || (run & (run - 1)) != 0)
+        return fail(WGRT_ERR_INVALID_ARGUMENT, "the run length is 0 (automatic) or a power of two up to " +
+                                                   std::to_string(kMaxFusedRun));
+    g_fused_run.store(run, std::memory_order_relaxed);
+    return WGRT_OK;
+}
+
+wgrt_status wgrt_debug_fused_run(int num_iter, int handoff_bound, int *run) {
+    if (num_iter < 1 || !run) return fail(WGRT_ERR_INVALID_ARGUMENT, "need num_iter >= 1 and run");
+    wgrt_debug_opts d{};
+    d.handoff_wait_ticks = handoff_bound ? 1u : 0u;
+    *run = num_iter > 1 ? fused_run_for(num_iter, &d) : 1;
+    return WGRT_OK;
+}
+
+wgrt_status wgrt_debug_fused_items_host(int64_t n_chunks, int num_iter, int run, int head, int64_t q0, int64_t n,
+                                        int64_t *chunk, int32_t *first_trace, int32_t *end_trace, int64_t *count) {
+    if (n_chunks < 1 || num_iter < 1 || run < 1 || run > kMaxFusedRun || (run & (run - 1)) != 0 || head < 0 ||
+        head >= kItemHeads || q0 < 0 || n < 0 || !count || (n > 0 && (!chunk || !first_trace || !end_trace)))
+        return fail(WGRT_ERR_INVALID_ARGUMENT, "bad item query");
+    const int64_t ns = (n_chunks + kItemStripe - 1) / kItemStripe, last = n_chunks - (ns - 1) * kItemStripe;
+    const int64_t n_runs = ((int64_t)num_iter + run - 1) / run;
+    int64_t k = 0;
+    for (; k < n; ++k) {
+        uint32_t k0 = 0;
+        if (!item_decode<true>(ns, last, n_runs, (uint32_t)run, head, q0 + k, chunk[k], k0)) break;
+        first_trace[k] = (int32_t)k0;
+        end_trace[k] = (int32_t)run_end(k0, (uint32_t)run, (uint32_t)num_iter);
+    }
+    *count = k;
     return WGRT_OK;
 }
 

@@ -96,6 +96,24 @@ wgrt_status wgrt_debug_set_auto_order(int on);
  * Process-wide, like the switch above, for the same-binary A/B and the tests: 0 makes every launch run the
  * word-form kernels; default 1. */
 wgrt_status wgrt_debug_set_byte_locator(int on);
+/* The run length of fused launches (num_iter > 1; csrc/wgrt_items.h): a work item covers a run of that many
+ * consecutive traces of its chunk's rays, and the lane that takes a ray keeps it for the run -- the RNG state stays in
+ * the lane from one trace to the next, and only a run's last trace hands the ray on through memory.  A scheduling
+ * detail like the chunk order: results do not depend on it.  Process-wide, for the same-binary A/B and the tests:
+ * 0 (the default) lets the library choose from num_iter (at least four runs per launch, runs of at most 16), 1 is
+ * one item per trace (a hand-off after every trace), n runs of n; a value that is not a power of two, or above 64,
+ * is WGRT_ERR_INVALID_ARGUMENT.  A call whose wgrt_debug_opts.handoff_wait_ticks is not 0 asks for hand-offs and
+ * runs with 1 under the automatic choice; an explicit value here wins. */
+wgrt_status wgrt_debug_set_fused_run(int run);
+/* The run length a fused launch of num_iter traces runs with now (the switch, else the automatic choice;
+ * handoff_bound != 0: for a call with a debug hand-off bound). */
+wgrt_status wgrt_debug_fused_run(int num_iter, int handoff_bound, int *run);
+/* The work items of a fused launch, from the code the kernels compile (csrc/wgrt_items.h; needs no GPU): positions
+ * q0 .. q0 + n - 1 of head's (0 .. 7) queue for n_chunks chunks, num_iter traces and runs of `run`.  Item k's chunk,
+ * first trace and end trace (exclusive) go to chunk[k], first_trace[k], end_trace[k]; *count is the number of
+ * positions before the head's queue ends (<= n). */
+wgrt_status wgrt_debug_fused_items_host(int64_t n_chunks, int num_iter, int run, int head, int64_t q0, int64_t n,
+                                        int64_t *chunk, int32_t *first_trace, int32_t *end_trace, int64_t *count);
 /* The most distinct cell words a scene created from now on may have and still get a byte grid (0 .. 256,
  * larger values mean 256; default 256): a test forces the word-form fallback with it. */
 wgrt_status wgrt_debug_set_palette_cap(int cap);

@@ -32,6 +32,9 @@ _sw = json.loads(os.environ.get("AB_SWITCH") or "{}")   # %byte=0|1: the byte lo
 if "byte" in _sw:
     from gpu_ray_tracing_for_waveguide_based_ar_display_amd import _lib
     _lib.set_byte_locator(bool(_sw["byte"]))
+if "run" in _sw:   # %run=0|1|2|4|...: the run length of fused launches (wgrt_debug_set_fused_run)
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd import _lib
+    _lib.set_fused_run(int(_sw["run"]))
 sc = Scene.from_geometry(g, L, **json.loads(os.environ.get("AB_SCENE") or "{}"))
 lk = json.loads(os.environ.get("AB_LAUNCH") or "{}")
 _dbg = {k[4:]: lk.pop(k) for k in [k for k in lk if k.startswith("dbg_")]}   # +dbg_<field>=v: wgrt_debug_opts

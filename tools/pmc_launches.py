@@ -5,7 +5,11 @@ whose steps hand rays over while both kernels are resident; rocprofv3 --pmc runs
 it a chained step would only wait out its hand-off bound.  Prints one JSON line with the fields
 tools/pmc_summary.py reads from a bench line (roofline.kernel, roofline.bounces_per_launch, config).
 Usage: python tools/pmc_launches.py [--config C3] [--launches 10] [--warmup 3] [--variant 0] [--byte 0|1]
---byte: wgrt_debug_set_byte_locator, the same-binary A/B of the byte locator (default: the library's)."""
+                                    [--num-iter N] [--run S]
+--byte: wgrt_debug_set_byte_locator, the same-binary A/B of the byte locator (default: the library's).
+--num-iter N > 1: fused launches of N chained traces each instead (one kernel each, so a counter pass runs them as
+they are); the line then names the fused kernel and gives the bounces of one fused launch.
+--run S: wgrt_debug_set_fused_run, the run length of those fused launches (default: the library's rule)."""
 import argparse
 import hashlib
 import json
@@ -23,6 +27,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--variant", type=int, default=0)
     ap.add_argument("--byte", type=int, default=None)
+    ap.add_argument("--num-iter", type=int, default=1)
+    ap.add_argument("--run", type=int, default=None)
     a = ap.parse_args()
     import torch
     from gpu_ray_tracing_for_waveguide_based_ar_display_amd import _lib
@@ -36,15 +42,17 @@ def main():
     geom, luts, pts = build_inputs(w)
     if a.byte is not None:
         _lib.set_byte_locator(bool(a.byte))
+    if a.run is not None:
+        _lib.set_fused_run(a.run)
     scene = Scene.from_geometry(geom, luts)
     rays, rng = hip_shard_builder(pts, nx, ny, lam, R, dev)(make_shard(nx, ny, len(lam), R, 1, 0))
     eb = torch.zeros(scene.eb_shape(), dtype=torch.float32, device=dev)
     st = new_stats(dev)
     for _ in range(a.warmup):   # (the first one learns the automatic issue order: another kernel)
-        trace_fullcolor(scene, rays, rng, eb, variant=a.variant)
+        trace_fullcolor(scene, rays, rng, eb, variant=a.variant, num_iter=a.num_iter)
     torch.cuda.synchronize()
     for _ in range(a.launches):
-        trace_fullcolor(scene, rays, rng, eb, variant=a.variant, stats=st)
+        trace_fullcolor(scene, rays, rng, eb, variant=a.variant, stats=st, num_iter=a.num_iter)
     torch.cuda.synchronize()
     variant = a.variant or (7 if scene.info()["n_polygons"] <= 16 else 9)
     cell = {7: "unsigned int", 9: "unsigned long"}[variant]
@@ -52,8 +60,8 @@ def main():
     with open(_lib.loaded_path(), "rb") as f:
         sha = hashlib.sha256(f.read()).hexdigest()[:16]
     print(json.dumps({"config": {"workload": f"{a.config}: {w.name}", "kernel_variant": a.variant, "lib_sha16": sha,
-                                 "byte_locator": pal},
-                      "roofline": {"kernel": f"trace_jones_kernel<{cell}, false, false, false>",
+                                 "byte_locator": pal, "num_iter": a.num_iter, "fused_run": a.run},
+                      "roofline": {"kernel": f"trace_jones_kernel<{cell}, {'true' if a.num_iter > 1 else 'false'}, false, false>",
                                    "bounces_per_launch": int(st[STAT.bounces]) / a.launches}}), flush=True)
     scene.close()
 

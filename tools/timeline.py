@@ -4,7 +4,8 @@
 Runs the bench workload (C3 by default), records per wave: start, queue-exhausted and end
 times, passes and lane-passes, and prints a summary: launch span, when the work queue ran dry,
 the drain (tail) after it, lane occupancy before and after, per-XCD end times.
-Usage: python tools/timeline.py [--config C3] [--num-iter 1] [--variant 0] [--shard N] [--out FILE]
+Usage: python tools/timeline.py [--config C3] [--num-iter 1] [--variant 0] [--shard N] [--run S] [--out FILE]
+--run S: the run length of a fused launch (wgrt_debug_set_fused_run; default: the library's rule).
 --shard N: rank 0's interleaved FoV x wavelength shard of N (distributed.make_shard), i.e. what one GPU
 of the N-GPU strong-scaling run traces.  Single traces use the product's grid rule (wgrt_launch_opts
 grid_sqrt_k: ceil(6.5 sqrt(work items)) workgroups), like the launches the bench times.
@@ -32,6 +33,7 @@ def main():
     ap.add_argument("--order", default="none", choices=["none", "lifetime"],
                     help="chunk issue order: ascending, or long-lived tiles first (from a previous launch)")
     ap.add_argument("--shard", type=int, default=1, help="trace rank 0's interleaved shard of N ranks")
+    ap.add_argument("--run", type=int, default=None, help="run length of fused launches (wgrt_debug_set_fused_run)")
     a = ap.parse_args()
     import torch
     from gpu_ray_tracing_for_waveguide_based_ar_display_amd.configs import CONFIGS, build_inputs
@@ -42,6 +44,9 @@ def main():
     w = CONFIGS[a.config]
     nx, ny, lam, R = w.nx, w.ny, list(w.lambdas), w.R
     geom, luts, pts = build_inputs(w)
+    if a.run is not None:
+        from gpu_ray_tracing_for_waveguide_based_ar_display_amd import _lib
+        _lib.set_fused_run(a.run)
     scene = Scene.from_geometry(geom, luts)
     shard = make_shard(nx, ny, len(lam), R, a.shard, 0)
     rays, rng = hip_shard_builder(pts, nx, ny, lam, R, dev)(shard)
@@ -106,7 +111,7 @@ def main():
             from gpu_ray_tracing_for_waveguide_based_ar_display_amd._lib import loaded_path
             with open(loaded_path(), "rb") as lf:
                 sha = hashlib.sha256(lf.read()).hexdigest()[:16]
-            json.dump({"config": a.config, "num_iter": a.num_iter, "shard_of": a.shard, "lib_sha16": sha,
+            json.dump({"config": a.config, "num_iter": a.num_iter, "shard_of": a.shard, "fused_run": a.run, "lib_sha16": sha,
                        "runs": res}, f, indent=1)
 
 
