@@ -31,13 +31,14 @@ EXPORTED = ("wgrt_scene_create", "wgrt_scene_create_ex", "wgrt_scene_destroy", "
             "wgrt_chain_begin", "wgrt_chain_step", "wgrt_chain_end", "wgrt_chain_gather", "wgrt_trace_fate", "wgrt_fate_census",
             "wgrt_fate_census_host", "wgrt_fate_col", "wgrt_fate_cols", "wgrt_fate_reason_name", "wgrt_trace_replicas",
             "wgrt_window_replicas_fold", "wgrt_window_replicas_fold_host", "wgrt_trace_expected",
-            "wgrt_expected_weight_host")
+            "wgrt_expected_weight_host", "wgrt_trace_footprint", "wgrt_footprint_plan_validate",
+            "wgrt_footprint_bin_host", "wgrt_footprint_channel_name")
 EXPORTED_DEBUG = ("wgrt_debug_shadow", "wgrt_debug_scene_copy", "wgrt_debug_set_auto_order",
                   "wgrt_debug_get_auto_order", "wgrt_debug_get_tile_tail", "wgrt_debug_order_host",
                   "wgrt_debug_chain_plan", "wgrt_debug_chain_set_serial", "wgrt_debug_set_byte_locator",
                   "wgrt_debug_set_palette_cap", "wgrt_debug_scene_palette", "wgrt_debug_expected_replays",
                   "wgrt_debug_chain_report", "wgrt_debug_set_fused_run", "wgrt_debug_fused_run",
-                  "wgrt_debug_fused_items_host")
+                  "wgrt_debug_fused_items_host", "wgrt_debug_set_footprint_aggregate")
 
 
 class WgrtError(RuntimeError):
@@ -96,6 +97,12 @@ class LaunchOpts(ctypes.Structure):
                 ("chunk_order", ctypes.c_void_p), ("n_chunk_order", ctypes.c_int64),
                 ("num_iter", ctypes.c_int), ("gid_blocks", ctypes.c_void_p), ("gid_block_rays", ctypes.c_int64),
                 ("debug", ctypes.POINTER(DebugOpts)), ("grid_sqrt_k", ctypes.c_double)]
+
+
+class FootprintPlanC(ctypes.Structure):
+    """wgrt_footprint_plan (include/wgrt.h): the footprint maps' rectangle of the plate and its cells."""
+    _fields_ = [("x0", ctypes.c_double), ("y0", ctypes.c_double), ("cell_x", ctypes.c_double),
+                ("cell_y", ctypes.c_double), ("nx_cells", ctypes.c_int32), ("ny_cells", ctypes.c_int32)]
 
 
 LUT_ORDER = ("lut_ic1", "lut_ic2", "lut_ic3", "lut_fc1", "lut_fc2", "lut_oc1", "lut_oc2")   # lut_f32_angles bits
@@ -325,6 +332,18 @@ def load():
         L.wgrt_expected_weight_host.argtypes = [ctypes.c_double] * 7
         L.wgrt_debug_expected_replays.restype = st
         L.wgrt_debug_expected_replays.argtypes = [_vp, _vp, _vp, _vp, ctypes.c_int64]
+    if hasattr(L, "wgrt_trace_footprint"):   # the footprint maps: new symbols within ABI 9, by name
+        L.wgrt_trace_footprint.restype = st
+        L.wgrt_trace_footprint.argtypes = L.wgrt_trace_opts.argtypes + [_vp, _vp, ctypes.POINTER(FootprintPlanC), _vp]
+        L.wgrt_footprint_plan_validate.restype = st
+        L.wgrt_footprint_plan_validate.argtypes = [ctypes.POINTER(FootprintPlanC)]
+        L.wgrt_footprint_bin_host.restype = st
+        L.wgrt_footprint_bin_host.argtypes = [ctypes.POINTER(FootprintPlanC), _vp, _vp, _vp, _vp, ctypes.c_int64,
+                                              ctypes.c_int32, _vp]
+        L.wgrt_footprint_channel_name.restype = ctypes.c_char_p
+        L.wgrt_footprint_channel_name.argtypes = [ctypes.c_int]
+        L.wgrt_debug_set_footprint_aggregate.restype = st
+        L.wgrt_debug_set_footprint_aggregate.argtypes = [ctypes.c_int]
     if hasattr(L, "wgrt_locator_palette_host"):   # the byte locator's hooks: new symbols within ABI 9, bound by name
         L.wgrt_locator_palette_host.restype = st
         L.wgrt_locator_palette_host.argtypes = [ctypes.POINTER(SceneDesc), ctypes.c_double, _i64, _i64, _d,
@@ -563,6 +582,12 @@ def locator_classify_host(geom, luts, xy: np.ndarray, cell_mm: float = 0.125) ->
 def set_byte_locator(on: bool) -> None:
     """``wgrt_debug_set_byte_locator``: the Jones-vector lane's byte locator on / off, process-wide (A/B, tests)."""
     check(load().wgrt_debug_set_byte_locator(1 if on else 0), "wgrt_debug_set_byte_locator")
+
+
+def set_footprint_aggregate(on: bool) -> None:
+    """``wgrt_debug_set_footprint_aggregate``: the footprint sink's on-chip summing on / off, process-wide (A/B, tests);
+    both forms give the same map."""
+    check(load().wgrt_debug_set_footprint_aggregate(1 if on else 0), "wgrt_debug_set_footprint_aggregate")
 
 
 def set_fused_run(run: int = 0) -> None:

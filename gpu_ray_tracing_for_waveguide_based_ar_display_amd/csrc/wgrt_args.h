@@ -130,6 +130,16 @@ struct TraceArgs {
     // ray for (wgrt_items.h; a power of two, 1: an item per trace).  In the word that padded the struct, so every
     // other field and the kernel parameters behind it keep their places in the kernarg segment.
     int32_t fused_run;
+    // footprint maps (wgrt_trace_footprint; wgrt_footprint.h): with fp_map, every counted draw of the bounce loop adds
+    // to the int64 map [nl, 9, fp.ny_cells, fp.nx_cells] under the plan fp (by value).  fp_seen: one word per
+    // replay-list entry of the launch scratch, the draws the Jones-vector lane had counted when it abandoned the
+    // ray, which the replay passes over.  fp_aggregate: the sink sums a wave's adds to one entry on chip (0: one atomic
+    // per lane; wgrt_debug_set_footprint_aggregate).  Single launches only, in the FP instantiations.  Last again.
+    int64_t *fp_map;
+    uint32_t *fp_seen;
+    wgrt_footprint_plan fp;
+    int32_t fp_aggregate;
+    int32_t fp_pad_;
 };
 
 // The replica of global ray id g >= 0 among reps (2 .. 64) copies: g % reps from 32-bit remainders (the 64-bit

@@ -18,11 +18,17 @@
 // the out-coupling itself is not added (Lane::hit still says whether it would have been).  *ev_skip, when not
 // zero, is the number of such visits whose deposit has already been made (a replay of a ray the Jones lane
 // abandoned after scoring them): they are passed over.  The walk -- draws, branches, counters -- is EV = false's.
+// FP (a template parameter of trace_one; off by default): the footprint maps of wgrt_trace_footprint
+// (wgrt_footprint.h).  trace_one counts every draw of the bounce loop where the ray stood before interact() moved
+// it, and reads the draw's second channel (lost / out-coupled inside / beside the eyebox) from the fate code that
+// interact<FATE> leaves in the lane -- so interact itself has no FP of its own.  Its `skip` draws are passed over
+// (counted by the Jones lane before it abandoned the ray).  The walk is FP = false's.
 #pragma once
 
 #include "wgrt_args.h"
 #include "wgrt_expected.h"
 #include "wgrt_fate.h"
+#include "wgrt_footprint.h"
 #include "wgrt_locator.h"
 #include "wgrt_window.h"
 
@@ -438,13 +444,55 @@ __device__ __forceinline__ void add_stats(wgrt_trace_stats *stats, Counters c) {
     if ((threadIdx.x & 63) == 0 && stats) c.add_to(stats);
 }
 
+// The footprint sink (wgrt_trace_footprint): one count into the int64 map at flat offset off (< 0: none), called by
+// every lane that is active at the call site, whatever the exec mask.  Unsigned 64-bit atomics whose result is not
+// used (global_atomic_add_x2, no compare-and-swap loop): integer adds commute, so the map does not depend on their
+// order.  aggregate: the lanes of the wave that hit the same entry are summed on chip -- the first pending lane's
+// offset is broadcast, the lanes that share it are counted with a ballot, and the first of them adds the count; at
+// most kFootprintRounds distinct offsets are served that way, and whoever is left adds its own 1.  Every ray starts
+// in the in-coupler, whose few cells would otherwise take a wave's 64 adds on one address at a time.
+constexpr int kFootprintRounds = 8;
+__device__ __forceinline__ void footprint_add(int64_t *map, int64_t off, bool aggregate) {
+    unsigned long long *const m = (unsigned long long *)map;
+    bool todo = off >= 0;
+    if (aggregate) {
+#pragma unroll 1
+        for (int round = 0; round < kFootprintRounds && __ballot(todo) != 0ull; ++round) {
+            if (todo) {
+                const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)(uint64_t)off);
+                const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)off >> 32));
+                const bool mine = (uint64_t)off == (((uint64_t)hi << 32) | lo);
+                const uint64_t same = __ballot(mine);
+                if (mine) {
+                    const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(same >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)same, 0));
+                    if (rank == 0) atomicAdd(m + off, (unsigned long long)__popcll(same));
+                    todo = false;
+                }
+            }
+        }
+    }
+    if (todo) atomicAdd(m + off, 1ull);
+}
+
+// One counted draw of wavelength l in state `region` at (x, y), its trace ended by it with fate reason `reason` (0: the
+// trace goes on): channel `region`, and the reason's channel if it has one (wgrt_footprint.h).
+__device__ __forceinline__ void footprint_count(const TraceArgs &A, int l, int region, int reason, double x, double y) {
+    const int32_t cell = footprint_cell(A.fp, x, y);
+    const bool agg = A.fp_aggregate != 0;
+    footprint_add(A.fp_map, cell >= 0 ? footprint_offset(A.fp, l, region, cell) : -1, agg);
+    const int c2 = footprint_end_channel(reason);
+    if (c2 >= 0) footprint_add(A.fp_map, cell >= 0 ? footprint_offset(A.fp, l, c2, cell) : -1, agg);
+}
+
 // Trace ray i to termination with the reference arithmetic (variant 1's lane; replays), counted in c.  With
 // s_io, the trace starts from *s_io instead of rng_states[i] and leaves its final state there
 // (rng_states untouched).
-// EV: with the expected-value deposits (above); ev_skip: the scored visits to pass over.
-template <bool FATE = false, bool EV = false>
+// EV: with the expected-value deposits (above); skip: the scored visits to pass over.
+// FP: with the footprint counts (above); skip: the counted draws to pass over.
+template <bool FATE = false, bool EV = false, bool FP = false>
 __device__ __forceinline__ void trace_one(const TraceArgs &A, int64_t i, Counters &c, uint32_t *s_io = nullptr,
-                                          uint32_t ev_skip = 0) {
+                                          uint32_t skip = 0) {
+    static_assert(!(EV && FP), "a launch scores visits or counts footprints: skip belongs to one of them");
     Lane L;
     if (!lane_load(A, i, L)) {
         ++c.w[kCtrBadRays];
@@ -455,7 +503,14 @@ __device__ __forceinline__ void trace_one(const TraceArgs &A, int64_t i, Counter
     int blk = 0, kind = 0;
     bool entry = true;
     for (;;) {
-        const int next = interact<FATE, EV>(A, A.loc, L, blk, kind, entry, &ev_skip);
+        // FP: where and in which state the ray stands at this draw
+        const double fx = L.r.x, fy = L.r.y;
+        const int freg = L.r.region;
+        const int next = interact<FATE || FP, EV>(A, A.loc, L, blk, kind, entry, &skip);
+        if (FP && !entry) {
+            if (skip) --skip;   // counted by the lane that abandoned the ray
+            else footprint_count(A, L.l, freg, next < 0 ? L.why % 10 : 0, fx, fy);
+        }
         if (next < 0) break;
         L.r.region = next;
         entry = false;

@@ -42,6 +42,7 @@ struct wgrt_scene {
     int jones_fate_grid[2][2][2] = {}; // ... of the fate-storing instantiations (wgrt_trace_fate): [64-bit cells][single wavelength]
     int jones_reps_grid[2][2][2] = {}; // ... of the replica-table instantiations (wgrt_trace_replicas): the same axes
     int jones_ev_grid[2][2][2] = {};   // ... of the expected-value instantiations (wgrt_trace_expected): the same axes
+    int jones_fp_grid[2][2][2] = {};   // ... of the footprint instantiations (wgrt_trace_footprint): the same axes
     int jones_learn_grid[2][2] = {};   // ... of the learning instantiations (full colour, single trace): [64-bit cells]
     int jones_chain_grid[2][2] = {};   // ... the most a chained step may use (wgrt_chain_*): [64-bit cells], half the
                                        // resident grid less a margin (query_trace_grids)
@@ -62,7 +63,8 @@ struct wgrt_scene {
         uint32_t parity = 0;                 // the set the next launch uses
         bool dirty = false;                  // a launch failed half-way: both sets need zeroing
         uint32_t *full = nullptr;            // full-block list (qcap / kQBlock entries)
-        uint32_t *list = nullptr;            // replay list
+        uint32_t *list = nullptr;            // replay list; behind its cap entries, one more word per entry: the draws a
+                                             // footprint launch had counted for the abandoned ray (TraceArgs::fp_seen)
         int64_t cap = 0;                     // replay list entries
         double2 *q_xy = nullptr;             // out-coupling queue: position, ray index
         uint32_t *q_i = nullptr;

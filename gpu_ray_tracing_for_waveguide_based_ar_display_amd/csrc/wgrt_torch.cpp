@@ -115,6 +115,14 @@ decltype(&wgrt_trace_expected) expected_abi() {
     return fn;
 }
 
+// wgrt_trace_footprint (the footprint maps), new within ABI 9 too: looked up at the first trace_footprint call.
+decltype(&wgrt_trace_footprint) footprint_abi() {
+    static const auto fn = reinterpret_cast<decltype(&wgrt_trace_footprint)>(dlsym(RTLD_DEFAULT, "wgrt_trace_footprint"));
+    TORCH_CHECK(fn, "wgrt.trace_footprint: the loaded libwgrt.so has no wgrt_trace_footprint (a build from before the "
+                    "footprint maps)");
+    return fn;
+}
+
 // All three launching operators: trace (the grid alone: plan 0, no table), trace_windows (the grid, the window
 // table of plan `plan` -- a wgrt_window_plan handle -- or both) and, with `chain`, chain_begin: the same checks and
 // records handed to wgrt_chain_begin, which launches nothing and leaves the chain's handle in *chain.
@@ -125,7 +133,8 @@ int64_t trace_core(int64_t scene, const Tensor &x, const Tensor &y, const Tensor
                    int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
                    int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
                    double grid_sqrt_k, int64_t plan, std::optional<Tensor> table, wgrt_chain **chain,
-                   std::optional<Tensor> fate = std::nullopt, int64_t replicas = 0, bool expected = false) {
+                   std::optional<Tensor> fate = std::nullopt, int64_t replicas = 0, bool expected = false,
+                   const wgrt_footprint_plan *fp = nullptr, std::optional<Tensor> fp_map = std::nullopt) {
     const wgrt_scene *s = reinterpret_cast<const wgrt_scene *>(static_cast<uintptr_t>(scene));
     TORCH_CHECK(s != nullptr, "wgrt.trace: NULL scene");
     wgrt_scene_info info{};
@@ -219,6 +228,21 @@ int64_t trace_core(int64_t scene, const Tensor &x, const Tensor &y, const Tensor
         TORCH_CHECK(!per, "wgrt.chain_begin: a chain takes no per_ray_bounces");
         return chain_abi().begin(s, &r, n_rays, gid_offset, rng, eb, stp, hip_stream, &o, tab ? wp : nullptr, tab, chain);
     }
+    if (fp_map) {   // trace_footprint: int64 [num_lmd, 9, ny_cells, nx_cells], added to by every counted draw
+        TORCH_CHECK(fp && !fate && replicas == 0 && !expected, "wgrt.trace_footprint: takes no fate, replicas or expected");
+        on_device(*fp_map, "map", c);
+        TORCH_CHECK(fp_map->scalar_type() == at::kLong, "wgrt.trace_footprint: map must be int64");
+        // (a plan the library refuses has no size to compare with: the library's check answers first)
+        // (the scene's info has its tile count, num_lmd * nx * ny: the Python layer checks the first axis exactly)
+        const bool sized = fp->nx_cells >= 1 && fp->nx_cells <= 4096 && fp->ny_cells >= 1 && fp->ny_cells <= 4096;
+        TORCH_CHECK(!sized || (fp_map->is_contiguous() && fp_map->dim() == 4 && fp_map->size(0) >= 1 &&
+                               info.tiles % fp_map->size(0) == 0 && fp_map->size(1) == WGRT_FOOTPRINT_CHANNELS &&
+                               fp_map->size(2) == fp->ny_cells && fp_map->size(3) == fp->nx_cells),
+                    "wgrt.trace_footprint: map must be contiguous [num_lmd, ", WGRT_FOOTPRINT_CHANNELS, ", ", fp->ny_cells,
+                    ", ", fp->nx_cells, "], got ", fp_map->sizes());
+        return footprint_abi()(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o, tab ? wp : nullptr, tab, fp,
+                               static_cast<int64_t *>(fp_map->data_ptr()));
+    }
     if (expected) {   // trace_expected: the window table alone (its shape checked above: [tiles, W], or one per replica)
         TORCH_CHECK(tab && !eb && !fate, "wgrt.trace_expected: needs a window table and takes no matrix_EB or fate");
         return expected_abi()(s, &r, n_rays, gid_offset, rng, stp, per, hip_stream, &o, wp, tab,
@@ -291,6 +315,28 @@ int64_t trace_expected(int64_t scene, const Tensor &x, const Tensor &y, const Te
     return trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, std::nullopt, stats, per_ray_bounces,
                       n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
                       gid_block_rays, debug, grid_sqrt_k, plan, table, nullptr, std::nullopt, replicas, true);
+}
+
+// trace_footprint: trace_windows' arguments, the footprint plan's fields and the map (wgrt_trace_footprint).
+int64_t trace_footprint(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
+                        const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
+                        Tensor rng_states, std::optional<Tensor> matrix_EB, std::optional<Tensor> stats,
+                        std::optional<Tensor> per_ray_bounces, int64_t n_rays, int64_t gid_offset, int64_t stream,
+                        int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
+                        int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
+                        double grid_sqrt_k, int64_t plan, std::optional<Tensor> table, double fp_x0, double fp_y0,
+                        double fp_cell_x, double fp_cell_y, int64_t fp_nx_cells, int64_t fp_ny_cells, Tensor map) {
+    wgrt_footprint_plan fp{};
+    fp.x0 = fp_x0;
+    fp.y0 = fp_y0;
+    fp.cell_x = fp_cell_x;
+    fp.cell_y = fp_cell_y;
+    // (out of int32 range: a count the library refuses)
+    fp.nx_cells = static_cast<int32_t>(std::max<int64_t>(-1, std::min<int64_t>(fp_nx_cells, 1 << 20)));
+    fp.ny_cells = static_cast<int32_t>(std::max<int64_t>(-1, std::min<int64_t>(fp_ny_cells, 1 << 20)));
+    return trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats, per_ray_bounces,
+                      n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
+                      gid_block_rays, debug, grid_sqrt_k, plan, table, nullptr, std::nullopt, 0, false, &fp, map);
 }
 
 // chain_begin: trace_windows' arguments -> the chain's handle (a user-space address: positive), or the negated
@@ -372,6 +418,15 @@ TORCH_LIBRARY(wgrt, m) {
           "Tensor? gid_blocks, int gid_block_rays, int debug, float grid_sqrt_k, int plan, Tensor(e!) table, "
           "int replicas) -> int",
           &trace_expected);
+    // the same launch counting every draw into the footprint maps (wgrt_trace_footprint): map int64
+    // [num_lmd, 9, ny_cells, nx_cells]
+    m.def("trace_footprint(int scene, Tensor x, Tensor y, Tensor m, Tensor n, Tensor? lmd_num, Tensor te, Tensor tm, "
+          "Tensor delta_phase, Tensor(a!) rng_states, Tensor(b!)? matrix_EB, Tensor(c!)? stats, "
+          "Tensor(d!)? per_ray_bounces, int n_rays, int gid_offset, int stream, int kernel, int variant, "
+          "int workgroups, Tensor? chunk_order, int num_iter, Tensor? gid_blocks, int gid_block_rays, int debug, "
+          "float grid_sqrt_k, int plan, Tensor(e!)? table, float fp_x0, float fp_y0, float fp_cell_x, float fp_cell_y, "
+          "int fp_nx_cells, int fp_ny_cells, Tensor(f!) map) -> int",
+          &trace_footprint);
     m.def("chain_step(int chain) -> int", &chain_step);
     m.def("chain_end(int chain) -> int", &chain_end);
 }

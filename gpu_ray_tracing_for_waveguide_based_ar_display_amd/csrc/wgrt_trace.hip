@@ -68,6 +68,14 @@ __global__ __launch_bounds__(256) void trace_grid_ev_kernel(TraceArgs A) {
     add_stats(A.stats, c);
 }
 
+// The same counting every draw into the footprint maps (wgrt_trace_footprint with variant 1; wgrt_footprint.h).
+__global__ __launch_bounds__(256) void trace_grid_fp_kernel(TraceArgs A) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    Counters c;
+    if (i < A.n_rays) trace_one<false, false, true>(A, i, c);
+    add_stats(A.stats, c);
+}
+
 // A counter set of the Jones-vector variants' launch scratch, each slot on its own 128-B line: the kHeads
 // work-queue heads, then the replay count, the out-coupling queue and full-block counts, and a single
 // launch's epilogue totals (a Counters record) and done count.
@@ -281,12 +289,23 @@ __device__ __forceinline__ void record_abandoned_ev(const KArgs &K, uint32_t i, 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// The same for a footprint launch (jones_body, FP), whose counts up to here are in the map: the entry carries the
+// number of counted draws, which the replay passes over (trace_one's skip).  A footprint launch does use the
+// out-coupling queue, so the counts have a word of their own per replay-list entry (TraceArgs::fp_seen, part of the
+// stream's launch scratch).
+__device__ __forceinline__ void record_abandoned_fp(const KArgs &K, uint32_t i, uint32_t seen) {
+    const unsigned long long k = atomicAdd(KA(replay_count), 1ull);
+    __hip_atomic_store(KA(replay_list) + k, i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(KA(fp_seen) + k, seen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
 #if WGRT_INKERNEL_REPLAY
 // The single launch's replay inside the trace kernel (the last workgroup; finish_single): the
 // reference-arithmetic lane (trace_one) over the replay list, its TraceArgs read from the kernarg segment
 // here, so nothing of it is live across the wave loop.  Inlined: as a real call it gave the wave loop 128
 // VGPRs and scratch (above).
-template <bool FATE, bool EV>
+template <bool FATE, bool EV, bool FP = false>
 __device__ __forceinline__ void replay_tail(const KArgs &K, unsigned long long nr) {
     const TraceArgs R = K.args();
     const uint32_t *const list = KA(replay_list);
@@ -295,8 +314,10 @@ __device__ __forceinline__ void replay_tail(const KArgs &K, unsigned long long n
         // EV: the visits the Jones lane scored before it abandoned the ray (record_abandoned_ev)
         uint32_t skip = 0;
         if (EV) skip = __hip_atomic_load(KA(q_i) + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        trace_one<FATE, EV>(R, (int64_t)__hip_atomic_load(list + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), c,
-                            nullptr, skip);
+        // FP: the draws it counted (record_abandoned_fp)
+        if (FP) skip = __hip_atomic_load(KA(fp_seen) + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        trace_one<FATE, EV, FP>(R, (int64_t)__hip_atomic_load(list + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), c,
+                                nullptr, skip);
     }
     c.wave_reduce();
     if (threadIdx.x == 0) c.w[kCtrReplayed] = nr;
@@ -336,7 +357,7 @@ __device__ __forceinline__ void finish_fused(const KArgs &K, Counters c) {
 // each per workgroup: not contended), waits for them, and counts the workgroup done; the workgroup that
 // counts last reads the totals at agent scope, adds them to *stats, zeroes the next launch's counter set
 // (every other workgroup has left this one's) and replays.
-template <bool CHAIN, bool FATE, bool EV>
+template <bool CHAIN, bool FATE, bool EV, bool FP = false>
 __device__ __forceinline__ void finish_single(const KArgs &K, Counters c) {
     __shared__ unsigned long long red[4][kCtrWords];
     __shared__ int last_wg;
@@ -366,7 +387,7 @@ __device__ __forceinline__ void finish_single(const KArgs &K, Counters c) {
     const unsigned long long nr = __hip_atomic_load(KA(replay_count), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (__builtin_expect(nr != 0ull, 0)) {
         if (CHAIN) replay_tail_chain(K, nr);
-        else replay_tail<FATE, EV>(K, nr);
+        else replay_tail<FATE, EV, FP>(K, nr);
     }
 #endif
 }
@@ -424,7 +445,59 @@ struct EvBlock {
     double x[kEvBlock], y[kEvBlock], q[kEvBlock];
     uint32_t e[kEvBlock];
 };
-template <bool FUSED, bool SINGLE, bool TL, bool AMP, bool LEARN, bool CHAIN, bool FATE, bool REPS, bool EV, class Loc>
+// FP: a footprint launch (wgrt_trace_footprint; wgrt_footprint.h) counts every certified draw of the bounce loop into
+// the int64 plate map.  One 8-byte atomic per count is one 64-B request at the memory side, and a launch of them runs
+// at the chip's atomic request rate whatever else it does (DESIGN.md §4.7 has the figures), so the counts are summed
+// on chip first: every wave keeps a direct-mapped cache of kFpSlots counters in LDS, an entry (offset + 1) << 20 |
+// count.  A count whose entry is cached is one LDS add; one whose slot holds another entry (or none) swaps its own
+// entry in with count 1 and adds what it swapped out to the map with one global atomic; the wave adds what its cache
+// still holds when it ends.  (What it merges depends on the map: everything on a coarse one; at 256 x 256 cells a
+// wave's counts rarely meet again, and the gain measured there is smaller: DESIGN.md §4.7.)  The cache is
+// the wave's own -- no other wave touches it, and a wave's LDS operations execute in order -- so a lane's read, the
+// matching lanes' adds and then the other lanes' swaps need no lock: whatever a swap takes out, adds included, goes
+// to the map exactly once.  (A workgroup-wide cache would merge four times as many counts but needs a
+// compare-and-swap loop per count, which the in-coupler's few cells would serialise.)
+// Without the cache (wgrt_debug_set_footprint_aggregate(0)): one global atomic per count.
+constexpr int kFpSlots = 512;             // per wave: 4 KB of LDS
+constexpr int kFpCountBits = 20;          // an entry's count stays below 2^20: a fuller one is swapped out
+typedef unsigned long long __attribute__((address_space(3))) LdsU64;
+static_assert((kFpSlots & (kFpSlots - 1)) == 0 && kFpSlots <= 65536, "fp_slot takes the product's top bits");
+__device__ __forceinline__ int fp_slot(uint64_t key) {
+    return (int)(((uint32_t)key ^ (uint32_t)(key >> 32)) * 2654435761u >> 16) & (kFpSlots - 1);
+}
+// One count at map offset off (< 0: none) through the wave's cache; called by every lane of the wave.
+__device__ __forceinline__ void fp_cached(LdsU64 *tab, int64_t *map, int64_t off) {
+    constexpr uint64_t kCountMask = (1ull << kFpCountBits) - 1ull;
+    const bool todo = off >= 0;
+    const uint64_t key = (uint64_t)off + 1ull;   // (never 0: an empty slot matches nothing)
+    LdsU64 *const e = tab + fp_slot(key);
+    bool hit = false;
+    if (todo) {
+        const uint64_t cur = *e;
+        // (64 lanes may add to one entry in this pass: the count stays within its bits)
+        hit = (cur >> kFpCountBits) == key && (cur & kCountMask) < kCountMask - 64ull;
+    }
+    if (hit) __hip_atomic_fetch_add(e, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    asm volatile("" ::: "memory");   // the adds are issued before the swaps
+    if (todo && !hit) {
+        const uint64_t old = __hip_atomic_exchange(e, (key << kFpCountBits) | 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (old != 0ull)
+            atomicAdd((unsigned long long *)map + ((old >> kFpCountBits) - 1ull), (unsigned long long)(old & kCountMask));
+    }
+    asm volatile("" ::: "memory");
+}
+// What the wave's cache still holds, added to the map: one global atomic per entry.
+__device__ __forceinline__ void fp_flush(LdsU64 *tab, int64_t *map) {
+    constexpr uint64_t kCountMask = (1ull << kFpCountBits) - 1ull;
+    asm volatile("" ::: "memory");
+    for (int k = threadIdx.x & 63; k < kFpSlots; k += 64) {
+        const uint64_t v = tab[k];
+        if (v != 0ull) atomicAdd((unsigned long long *)map + ((v >> kFpCountBits) - 1ull), (unsigned long long)(v & kCountMask));
+    }
+}
+
+template <bool FUSED, bool SINGLE, bool TL, bool AMP, bool LEARN, bool CHAIN, bool FATE, bool REPS, bool EV, class Loc,
+          bool FP = false>
 __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, const Loc &loc, unsigned long long *heads,
                                           int chunk) {
     // Single launches (!FUSED) do their epilogue in this kernel (above), and retire a finished trace at one
@@ -482,6 +555,16 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
     }
     int evfill = 0;
     uint32_t ev_seen = 0, ev_hits = 0;
+    static_assert(!FP || (!FUSED && !CHAIN && !LEARN && !TL && !FATE && !REPS && !EV && WGRT_INKERNEL_REPLAY),
+                  "footprint launches are plain single launches (the replay passes over the counted draws)");
+    uint32_t fp_seen = 0;              // FP: the draws of the trace in flight that this lane has counted
+    // FP: this wave's counter cache (fp_cached); empty at the start (the wave's own LDS stores, in order)
+    LdsU64 *fpc = nullptr;
+    if constexpr (FP) {
+        __shared__ unsigned long long fp_lds[4][kFpSlots];
+        fpc = (LdsU64 *)&fp_lds[threadIdx.x >> 6][0];
+        for (int k = threadIdx.x & 63; k < kFpSlots; k += 64) fpc[k] = 0ull;
+    }
 
     // head x's items: stripes of kStripe consecutive chunks, stripe s on head s % 8, iteration-
     // major.  Every die gets a mix of all FoVs and wavelengths -- ray lifetimes differ by tile,
@@ -593,6 +676,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
         kind = 0;
         entry = true;
         if (EV) ev_seen = 0;
+        if (FP) fp_seen = 0;
     };
     // a trace's counters are added when it ends: an abandoned trace (kUncertain) adds nothing, and its
     // replay (replay_kernel or, fused, epilogue_kernel: trace_one) counts the whole trace once
@@ -728,6 +812,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             L.r.region = next >= 0 ? next : L.r.region;
             if (__builtin_expect(next == kUncertain, 0)) {
                 if (EV) record_abandoned_ev(K, L.i, ev_seen);
+                else if (FP) record_abandoned_fp(K, L.i, fp_seen);
                 else record_abandoned(K, L.i);
             }
         } else {
@@ -763,11 +848,35 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
         // EV: the visit this pass scores on this lane, where the ray stood when interact() saw it
         bool dep = false;
         double evq = -1.0, evx = 0.0, evy = 0.0;
+        // FP: the map entries this pass counts on this lane (< 0: none): the draw's state channel and, for a draw
+        // that ends the trace, its lost / eyebox / beside channel
+        int64_t fp_a = -1, fp_b = -1;
         if (active && blk >= 0) {
             L.inter += entry ? 0u : 1u;
             if (EV) evx = L.r.x, evy = L.r.y;
-            const int next = interact<SINGLE, AMP, FATE, EV>(A, K, loc, L, blk, kind, entry, sg, EV ? &evq : nullptr);
+            // FP: where and in which state the ray stands at the draw (the FATE form of interact tells the die that
+            // is no Monte-Carlo loss apart, kDieIc: nothing else differs)
+            const double fpx = L.r.x, fpy = L.r.y;
+            const int fpreg = L.r.region;
+            const int next =
+                interact<SINGLE, AMP, FATE || FP, EV>(A, K, loc, L, blk, kind, entry, sg, EV ? &evq : nullptr);
             out = next == kOut;
+            if constexpr (FP) {
+                // counted once the decision is certified, as ev_seen: the draw that abandons the ray is the replay's
+                if (!entry && next != kUncertain) {
+                    ++fp_seen;
+                    const int32_t cell = footprint_cell(A.fp, fpx, fpy);
+                    if (cell >= 0) {
+                        const int l = SINGLE ? 0 : (int)(L.tix / (uint32_t)(KA(nx) * KA(ny)));
+                        fp_a = footprint_offset(A.fp, l, fpreg, cell);
+                        int c2 = next == kDie ? kFootprintLost : -1;
+                        if (out)
+                            c2 = eyebox_inside(KA(tiles) + (int64_t)L.tix * KA(tile_d), fpx, fpy) ? kFootprintEyebox
+                                                                                                  : kFootprintBeside;
+                        if (c2 >= 0) fp_b = footprint_offset(A.fp, l, c2, cell);
+                    }
+                }
+            }
             if (EV) {
                 const bool scored = (evq >= 0.0) & (next != kUncertain);
                 ev_seen += scored ? 1u : 0u;
@@ -784,6 +893,18 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
         SEG_TMARK(sg, 5, L.r.er);
         if constexpr (EV) ev_push(dep, evx, evy, evq, out);
         else queue_out(out);
+        if constexpr (FP) {
+            // every lane of the wave is here: the counts go through the wave's cache (fp_cached), or, with the
+            // switch off, one global atomic each; the second channel is rare (once per ray), so its sink runs only in
+            // a pass that has one
+            if (A.fp_aggregate != 0) {   // (wave-uniform)
+                fp_cached(fpc, A.fp_map, fp_a);
+                if (__ballot(fp_b >= 0) != 0ull) fp_cached(fpc, A.fp_map, fp_b);
+            } else {
+                footprint_add(A.fp_map, fp_a, false);
+                footprint_add(A.fp_map, fp_b, false);
+            }
+        }
         SEG_MARK(sg, 6);
     };
 
@@ -1040,6 +1161,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
         ev_flush();
         tot_h = ev_hits;
     }
+    if constexpr (FP) fp_flush(fpc, A.fp_map);   // (empty with the switch off)
     if (qblk) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane < qfill) bin(qbase + lane);
@@ -1067,7 +1189,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
     c.w[kCtrGiveups] = tot_giveup;
     c.w[kCtrInter] = tot_int;
     if (FUSED) finish_fused(K, c);
-    else finish_single<CHAIN, FATE, EV>(K, c);
+    else finish_single<CHAIN, FATE, EV, FP>(K, c);
 }
 
 #if !WGRT_INKERNEL_REPLAY
@@ -1158,6 +1280,15 @@ __global__ WGRT_JONES_BOUNDS void trace_jones_ev_kernel(TraceArgs A, LocatorT<Ce
         A, kernel_kargs<decltype(trace_jones_ev_kernel<CellT, SINGLE, AMP>)>(), loc, counter, chunk);
 }
 
+// The single-launch loop counting every draw into the footprint maps (wgrt_trace_footprint): the fate kernels'
+// instantiations again; never a learning, timeline or chained launch.
+template <class CellT, bool SINGLE, bool AMP>
+__global__ WGRT_JONES_BOUNDS void trace_jones_fp_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
+                                                        int chunk) {
+    jones_body<false, SINGLE, false, AMP, false, false, false, false, false, LocatorT<CellT>, true>(
+        A, kernel_kargs<decltype(trace_jones_fp_kernel<CellT, SINGLE, AMP>)>(), loc, counter, chunk);
+}
+
 // The same kernels over the byte locator (ByteLocatorT<CellT>: the scene's byte grid and palette), under names
 // of their own: the word forms above stay as they are, for scenes without a byte grid and for the A/B
 // (wgrt_debug_set_byte_locator).
@@ -1208,6 +1339,13 @@ __global__ WGRT_JONES_BOUNDS void trace_jones_b_ev_kernel(TraceArgs A, ByteLocat
                                                           unsigned long long *counter, int chunk) {
     jones_body<false, SINGLE, false, AMP, false, false, false, false, true>(
         A, kernel_kargs<decltype(trace_jones_b_ev_kernel<CellT, SINGLE, AMP>)>(), loc, counter, chunk);
+}
+
+template <class CellT, bool SINGLE, bool AMP>
+__global__ WGRT_JONES_BOUNDS void trace_jones_b_fp_kernel(TraceArgs A, ByteLocatorT<CellT> loc,
+                                                          unsigned long long *counter, int chunk) {
+    jones_body<false, SINGLE, false, AMP, false, false, false, false, false, ByteLocatorT<CellT>, true>(
+        A, kernel_kargs<decltype(trace_jones_b_fp_kernel<CellT, SINGLE, AMP>)>(), loc, counter, chunk);
 }
 
 // The two ends of a chain's segment, on the caller's stream: every ray's state into its granule under the
@@ -1310,6 +1448,9 @@ const void *const kRepsKernels[2][2][2][2] = {   // [byte locator][64-bit cells]
 const void *const kEvKernels[2][2][2][2] = {   // [byte locator][64-bit cells][single wavelength][AMP]: wgrt_trace_expected
     {WGRT_K4(trace_jones_ev_kernel, uint32_t), WGRT_K4(trace_jones_ev_kernel, uint64_t)},
     {WGRT_K4(trace_jones_b_ev_kernel, uint32_t), WGRT_K4(trace_jones_b_ev_kernel, uint64_t)}};
+const void *const kFpKernels[2][2][2][2] = {   // [byte locator][64-bit cells][single wavelength][AMP]: wgrt_trace_footprint
+    {WGRT_K4(trace_jones_fp_kernel, uint32_t), WGRT_K4(trace_jones_fp_kernel, uint64_t)},
+    {WGRT_K4(trace_jones_b_fp_kernel, uint32_t), WGRT_K4(trace_jones_b_fp_kernel, uint64_t)}};
 const void *const kTimelineKernels[2][2] = {   // [byte locator][fused]
     {(const void *)trace_jones_tl_kernel<uint32_t, false, false>, (const void *)trace_jones_tl_kernel<uint32_t, true, false>},
     {(const void *)trace_jones_b_tl_kernel<uint32_t, false, false>,
@@ -1358,6 +1499,10 @@ wgrt_status query_trace_grids(wgrt_scene *s) {
                 HIP_TRY(grid_of(kEvKernels[b][c][g][0], plain));
                 HIP_TRY(grid_of(kEvKernels[b][c][g][1], amp));
                 s->jones_ev_grid[b][c][g] = std::min(s->jones_grid[b][c][0][g], std::min(plain, amp));
+                // ... and the footprint instantiations
+                HIP_TRY(grid_of(kFpKernels[b][c][g][0], plain));
+                HIP_TRY(grid_of(kFpKernels[b][c][g][1], amp));
+                s->jones_fp_grid[b][c][g] = std::min(s->jones_grid[b][c][0][g], std::min(plain, amp));
             }
         for (int f = 0; f < 2; ++f) HIP_TRY(grid_of(kTimelineKernels[b][f], s->jones_tl_grid[b][f]));
         for (int c = 0; c < 2; ++c) HIP_TRY(grid_of(kLearnKernels[b][c], s->jones_learn_grid[b][c]));
@@ -1457,8 +1602,9 @@ wgrt_status ensure_scratch(wgrt_scene *ms, void *stream, int64_t n_rays, int num
         return hipMalloc((void **)&sc->part, (size_t)grid * kPartWords * sizeof(unsigned long long));
     });
     if (e != WGRT_OK) return e;
+    // (two words per entry: the ray, and a footprint launch's counted draws -- wgrt_scene.h)
     e = grow(sc->cap, n_rays, {(void **)&sc->list},
-             [&] { return hipMalloc((void **)&sc->list, (size_t)n_rays * sizeof(uint32_t)); });
+             [&] { return hipMalloc((void **)&sc->list, (size_t)n_rays * 2 * sizeof(uint32_t)); });
     if (e != WGRT_OK) return e;
     // a trace out-couples at most once; each wave leaves at most one block partly unused
     const int64_t qn = n_rays * num_iter + grid * 4 * kQBlock;
@@ -1541,6 +1687,11 @@ struct LaunchCfg {
     // counting out-couplings; `replicas` as above (0: the one table).  It follows the replica launch's rules, has no
     // grid (a float32 cell cannot hold the fixed-point sums) and never stores fates.
     bool expected = false;
+    // wgrt_trace_footprint: the map every counted draw adds to and its plan (NULL: none).  A footprint launch follows
+    // the fate launch's rules -- a single launch, no learning, no debug timeline, never a chained step -- and is not
+    // combined with fates, replicas or the expected-value estimator.
+    int64_t *fp_map = nullptr;
+    wgrt_footprint_plan fp{};
     // set by validate_launch: the launch runs the byte-locator instantiation (byte_locator_applies)
     bool byte = false;
 };
@@ -1552,6 +1703,9 @@ std::atomic<int> g_byte_locator{1};
 bool byte_locator_applies(const wgrt_scene *s, int variant) {
     return g_byte_locator.load(std::memory_order_relaxed) && s->d_cells8 && (variant == 9 || (variant == 7 && s->d_palette32));
 }
+
+// wgrt_debug_set_footprint_aggregate: the footprint sink's on-chip summing on / off, process-wide (the same-binary A/B).
+std::atomic<int> g_fp_aggregate{1};
 
 // wgrt_debug_set_fused_run: the run length of fused launches, process-wide (the same-binary A/B; 0: the rule below).
 std::atomic<int> g_fused_run{0};
@@ -1607,7 +1761,7 @@ void plan_auto_order(wgrt_scene *ms, int64_t n_rays, int item, LaunchCfg &c) {
     if (learning)
         while (c.order_gen & (c.order_gen - 1)) c.order_gen &= c.order_gen - 1;
     c.auto_order = ms->learn_gen > 0 && item == kChunk;
-    if (!c.timeline && learning && !c.fate && !c.replicas && !c.expected) {   // (a fate, replica or expected-value launch does not learn: LaunchCfg)
+    if (!c.timeline && learning && !c.fate && !c.replicas && !c.expected && !c.fp_map) {   // (a fate, replica, expected-value or footprint launch does not learn: LaunchCfg)
         c.learn = true;
         ms->learned_rays += n_rays;
         ++ms->learn_gen;
@@ -1674,6 +1828,15 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
                                                "single launches (trace the iterations one call each)");
     if (c.expected && (c.fate || matrix_EB || !c.win_table))
         return fail(WGRT_ERR_INVALID_ARGUMENT, "the expected-value estimator fills a window table: no grid, no fates");
+    if (c.fp_map) {
+        if (const char *why = footprint_plan_error(&c.fp)) return fail(WGRT_ERR_INVALID_ARGUMENT, why);
+        if ((uintptr_t)c.fp_map & 7) return fail(WGRT_ERR_INVALID_ARGUMENT, "the footprint map must be 8-B aligned");
+        if (c.num_iter > 1)
+            return fail(WGRT_ERR_INVALID_ARGUMENT, "num_iter > 1 takes no footprint map: the maps are filled by single "
+                                                   "launches (trace the iterations one call each)");
+        if (c.fate || c.replicas || c.expected)
+            return fail(WGRT_ERR_INVALID_ARGUMENT, "a footprint launch takes no fates, replicas or expected-value estimator");
+    }
     if (c.chunk_order && c.variant == 1)
         return fail(WGRT_ERR_INVALID_ARGUMENT, "chunk_order needs variant 0, 7 or 9");
     if (c.gid_blocks && (c.gid_block_rays < 1 || gid_offset != 0))
@@ -1704,6 +1867,9 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
     if (c.timeline && c.expected)
         return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel scores no visits: trace with the expected-value "
                                           "estimator or with the timeline");
+    if (c.timeline && c.fp_map)
+        return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel counts no footprints: trace with a footprint map or "
+                                          "with the timeline");
     if ((c.replicas || c.expected) && c.variant != 1 && (int64_t)s->nl * s->nx * s->ny >= (int64_t)1 << kRepShift)
         return fail(WGRT_ERR_UNSUPPORTED, "replica tables with variants 7 / 9 need a scene of fewer than 2^24 tiles (the "
                                           "out-coupling queue entry carries the replica above the tile index)");
@@ -1730,6 +1896,9 @@ TraceArgs fill_args(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, 
     A.fate = c.fate;
     A.win_reps = c.replicas;
     A.win_rep_stride = c.rep_stride;
+    A.fp_map = c.fp_map;
+    A.fp = c.fp;
+    A.fp_aggregate = g_fp_aggregate.load(std::memory_order_relaxed);
     A.n_rays = n_rays;
     A.gid_offset = gid_offset;
     A.gid_blocks = c.gid_blocks;
@@ -1752,6 +1921,7 @@ int64_t launch_grid(const wgrt_scene *s, int64_t n_rays, int64_t item, const Lau
                    : c.timeline     ? s->jones_tl_grid[c.byte][c.num_iter > 1]
                    : c.fate         ? s->jones_fate_grid[c.byte][c.variant == 9][c.single]
                    : c.expected     ? s->jones_ev_grid[c.byte][c.variant == 9][c.single]
+                   : c.fp_map       ? s->jones_fp_grid[c.byte][c.variant == 9][c.single]
                    : c.replicas     ? s->jones_reps_grid[c.byte][c.variant == 9][c.single]
                    : c.learn        ? s->jones_learn_grid[c.byte][c.variant == 9]
                                     : s->jones_grid[c.byte][c.variant == 9][c.num_iter > 1][c.single];
@@ -1786,6 +1956,7 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
         const int64_t blocks = (A.n_rays + 255) / 256;
         if (blocks > 0x7fffffff) return fail(WGRT_ERR_INVALID_ARGUMENT, "too many rays for one launch");
         if (c.expected) hipLaunchKernelGGL(trace_grid_ev_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
+        else if (c.fp_map) hipLaunchKernelGGL(trace_grid_fp_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
         else if (c.fate) hipLaunchKernelGGL(trace_grid_fate_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
         else hipLaunchKernelGGL(trace_grid_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
         HIP_TRY(hipGetLastError());
@@ -1818,6 +1989,7 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
     unsigned long long *ctr = sc->ctr + (size_t)parity * kScratchCtr;
     set_counter_slots(A, ctr, sc->ctr + (size_t)(parity ^ 1u) * kScratchCtr);
     A.replay_list = sc->list;
+    A.fp_seen = sc->list + sc->cap;
     A.q_xy = sc->q_xy;
     A.q_i = sc->q_i;
     A.full_list = sc->full;
@@ -1847,6 +2019,7 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
                                : c.timeline ? kTimelineKernels[c.byte][num_iter > 1]
                                : c.fate   ? kFateKernels[c.byte][wide][c.single][amp]
                                : c.expected ? kEvKernels[c.byte][wide][c.single][amp]
+                               : c.fp_map ? kFpKernels[c.byte][wide][c.single][amp]
                                : c.replicas ? kRepsKernels[c.byte][wide][c.single][amp]
                                : c.learn  ? kLearnKernels[c.byte][wide]
                                           : kJonesKernels[c.byte][wide][num_iter > 1][c.single][amp];
@@ -2303,6 +2476,27 @@ wgrt_status wgrt_trace_expected(const wgrt_scene *s, const wgrt_rays *rays, int6
 
 double wgrt_expected_weight_host(double e1, double e2, double e3, double en1, double en2, double en3, double threshold) {
     return expected_deposit(e1, e2, e3, en1, en2, en3, threshold);
+}
+
+wgrt_status wgrt_trace_footprint(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
+                                 uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats,
+                                 uint32_t *per_ray_bounces, void *stream, const wgrt_launch_opts *opts,
+                                 const wgrt_window_plan *plan, double *table, const wgrt_footprint_plan *fp, int64_t *map) {
+    if (!map)   // no map: exactly that call
+        return wgrt_trace_windows(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, opts,
+                                  plan, table);
+    if (const char *why = footprint_plan_error(fp)) return fail(WGRT_ERR_INVALID_ARGUMENT, why);
+    LaunchCfg c;
+    const wgrt_status e = cfg_of_opts(s, opts, plan, table, c);
+    if (e != WGRT_OK) return e;
+    c.fp_map = map;
+    c.fp = *fp;
+    return trace_launch(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, c);
+}
+
+wgrt_status wgrt_debug_set_footprint_aggregate(int on) {
+    g_fp_aggregate.store(on != 0, std::memory_order_relaxed);
+    return WGRT_OK;
 }
 
 wgrt_status wgrt_chain_begin(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,

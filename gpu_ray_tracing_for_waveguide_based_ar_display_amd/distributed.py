@@ -487,7 +487,7 @@ def timed_run(trace_fn, rays, rng, eb, gid: GidMap, steps: int, per_call: int, s
 
 
 def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, replicas: int = 0,
-               expected: bool = False):
+               expected: bool = False, footprint=None):
     """trace_fn for ``run_steps`` / ``trace_job`` using the HIP kernel (torch device tensors); ``stats``
     (int64[STATS_LEN] device tensor) is added to by every call.  A shard of several block ranges passes its global
     ids as ``gid_blocks``, uploaded once per map and device and kept on the map (``GidMap.device_blocks``).
@@ -511,7 +511,11 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, rep
 
     ``expected``: every call scores the expected-value estimator into the table instead
     (``engine.trace_fullcolor(expected=True)``; ``eb`` must be None): single launches only and no ``chain`` again.
-    The sums are exact multiples of 2^-32, so the ranks' tables add exactly, as the counts do."""
+    The sums are exact multiples of 2^-32, so the ranks' tables add exactly, as the counts do.
+
+    ``footprint``: ``(fp, map)``, an ``engine.FootprintPlan`` and its int64 map: every call also counts its draws into
+    the plate map (``engine.trace_fullcolor(footprint=...)``): single launches only and no ``chain`` again.  The
+    counts are integers, so the ranks' maps add: ``reduce_eyebox(map)``."""
     from .engine import TraceChain, trace_fullcolor
 
     def ids_of(rng, gid: GidMap):
@@ -521,7 +525,7 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, rep
 
     def fn(rays, rng, eb, gid: GidMap, num_iter=1):
         trace_fullcolor(scene, rays, rng, eb, stats=stats, variant=variant, num_iter=num_iter, windows=windows,
-                        fate=fate, replicas=replicas, expected=expected, **ids_of(rng, gid))
+                        fate=fate, replicas=replicas, expected=expected, footprint=footprint, **ids_of(rng, gid))
 
     def chain(rays, rng, eb, gid: GidMap):
         """The same launches as a chain (``run_steps`` uses it for separate launches without a hook)."""
@@ -529,7 +533,7 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, rep
         from ._lib import load
         return TraceChain(scene, rays, rng, eb, stats=stats, variant=variant, windows=windows,
                           gather=hasattr(load(), "wgrt_chain_gather"), **ids_of(rng, gid))
-    if fate is None and int(replicas or 0) < 2 and not expected:
+    if fate is None and int(replicas or 0) < 2 and not expected and footprint is None:
         fn.chain = chain
     return fn
 

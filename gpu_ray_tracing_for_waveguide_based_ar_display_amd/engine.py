@@ -54,7 +54,7 @@ def trace_fullcolor(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_E
                     workgroups: int = 0, chunk_order: torch.Tensor | None = None, num_iter: int = 1,
                     gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
                     grid_sqrt_k: float = 0.0, windows=None, fate: torch.Tensor | None = None, replicas: int = 0,
-                    expected: bool = False) -> None:
+                    expected: bool = False, footprint=None) -> None:
     """Asynchronous launch on ``stream`` (default: torch's current stream).
 
     rays: dict of device float32 tensors keyed like the reference columns
@@ -86,14 +86,20 @@ def trace_fullcolor(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_E
     ``rng_states``, ``per_ray_bounces``, ``stats`` -- is the plain launch's bit for bit, but every out-coupler
     interaction inside the FoV's eyebox rectangle adds its out-coupling probability (a multiple of 2^-32) to the
     table instead of 1.0 per out-coupled ray: the same expectation with a fraction of the variance.  Works with
-    ``replicas=B``; a grid, ``fate``, ``num_iter > 1`` and a ``TraceChain`` raise ``ValueError``.
+    ``replicas=B``; a grid, ``fate``, ``num_iter > 1`` and a ``TraceChain`` raise ``ValueError``.  footprint:
+    ``(fp, map)``, a ``FootprintPlan`` and the int64 ``[num_lmd, 9, ny_cells, nx_cells]`` device tensor of
+    ``fp.new_map(scene)`` (``wgrt_trace_footprint``): every Monte-Carlo draw of the bounce loop adds 1 to the map at
+    the plate cell where the ray stood, in the channel of its state R0..R5, and the draw that loses the ray or
+    out-couples it inside / beside its eyebox rectangle also in channel 6 / 7 / 8 (``FOOTPRINT_CHANNELS``); nothing
+    else the launch leaves changes.  Single launches only; ``fate``, ``replicas``, ``expected``, ``num_iter > 1`` and a
+    ``TraceChain`` raise ``ValueError``.
     """
     if scene.single_lambda:
         raise ValueError("trace_fullcolor needs a full-colour scene; use trace_single for a single-wavelength one")
     _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single=False, chunk_order=chunk_order, num_iter=num_iter, gid_blocks=gid_blocks,
            gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows, fate=fate,
-           replicas=replicas, expected=expected)
+           replicas=replicas, expected=expected, footprint=footprint)
 
 
 def new_stats(device) -> torch.Tensor:
@@ -137,18 +143,18 @@ def trace_single(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_EB: 
                  workgroups: int = 0, chunk_order: torch.Tensor | None = None, num_iter: int = 1,
                  gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
                  grid_sqrt_k: float = 0.0, windows=None, fate: torch.Tensor | None = None, replicas: int = 0,
-                 expected: bool = False) -> None:
+                 expected: bool = False, footprint=None) -> None:
     """One launch of the single-wavelength kernel (``process_rays_kernel_pro``, GRTF:419-831)
     through ``wgrt_trace_single_ex``: no ``lmd_num`` column (ignored if present),
     matrix_EB [NY, NX, 80, 120], branch guard ener * efficiency > 1e-15.  The scene must be
     a single-wavelength one (``Scene.from_geometry(..., wavelength=l)`` or 3-D LUTs).  ``windows``, ``fate``,
-    ``replicas``, ``expected``: as ``trace_fullcolor``."""
+    ``replicas``, ``expected``, ``footprint``: as ``trace_fullcolor``."""
     if not scene.single_lambda:
         raise ValueError("trace_single needs a single-wavelength scene (Scene.from_geometry(..., wavelength=l))")
     _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single=True, chunk_order=chunk_order, num_iter=num_iter, gid_blocks=gid_blocks,
            gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows, fate=fate,
-           replicas=replicas, expected=expected)
+           replicas=replicas, expected=expected, footprint=footprint)
 
 
 MAX_REPLICAS = 64   # WGRT_MAX_REPLICAS (include/wgrt.h)
@@ -210,6 +216,74 @@ class WindowPlan:
             pass
 
 
+FOOTPRINT_CHANNELS = ("R0", "R1", "R2", "R3", "R4", "R5", "lost", "eyebox", "beside_eyebox")   # wgrt_footprint_channel_name
+
+
+class FootprintPlan:
+    """The plan of the footprint maps (``wgrt_footprint_plan``; ``trace_*(footprint=(fp, map))``): a rectangle of the
+    plate from ``(x0, y0)`` in ``nx_cells`` x ``ny_cells`` cells of ``cell_x`` x ``cell_y`` mm.  A point counts into
+    cell ``ix = floor((x - x0) / cell_x)``, ``iy = floor((y - y0) / cell_y)`` and is dropped outside the rectangle.
+    Cell sizes must be > 0 and finite, the origin finite, the cell counts 1 .. 4096 (``ValueError`` otherwise; the
+    check is the library's, ``wgrt_footprint_plan_validate``).  ``new_map(scene)``: a zeroed int64
+    ``[num_lmd, 9, ny_cells, nx_cells]`` map on the scene's device."""
+
+    def __init__(self, x0: float, y0: float, cell_x: float, cell_y: float, nx_cells: int, ny_cells: int):
+        self.x0, self.y0, self.cell_x, self.cell_y = float(x0), float(y0), float(cell_x), float(cell_y)
+        self.nx_cells, self.ny_cells = int(nx_cells), int(ny_cells)
+        if not (-2 ** 31 <= self.nx_cells < 2 ** 31 and -2 ** 31 <= self.ny_cells < 2 ** 31):
+            raise ValueError("nx_cells / ny_cells must be 1 .. 4096")
+        L = load()
+        if L.wgrt_footprint_plan_validate(ctypes.byref(self.c_plan())) != 0:
+            raise ValueError(L.wgrt_last_error().decode())
+
+    def c_plan(self):
+        return _lib.FootprintPlanC(self.x0, self.y0, self.cell_x, self.cell_y, self.nx_cells, self.ny_cells)
+
+    @classmethod
+    def for_scene(cls, geom, cells=(256, 256)):
+        """The plan of ``cells = (H, W)`` cells over the bounding box of ``geom.eff_reg1`` grown by one cell on every
+        side: every counted draw lies inside ``eff_reg1`` or its 1e-12 edge band, so nothing is dropped."""
+        H, W = int(cells[0]), int(cells[1])
+        if H < 3 or W < 3:
+            raise ValueError("for_scene needs at least 3 x 3 cells (one on every side of the plate's box)")
+        box = np.asarray(geom.eff_reg1, dtype=np.float64)
+        (xmin, ymin), (xmax, ymax) = box.min(axis=0), box.max(axis=0)
+        cx, cy = (xmax - xmin) / (W - 2), (ymax - ymin) / (H - 2)
+        return cls(xmin - cx, ymin - cy, cx, cy, W, H)
+
+    def map_shape(self, scene) -> tuple:
+        return (int(scene.num_lmd), len(FOOTPRINT_CHANNELS), self.ny_cells, self.nx_cells)
+
+    def new_map(self, scene: Scene) -> torch.Tensor:
+        return torch.zeros(self.map_shape(scene), dtype=torch.int64, device=torch.device("cuda", scene.device))
+
+    def as_dict(self) -> dict:
+        return {"x0": self.x0, "y0": self.y0, "cell_x": self.cell_x, "cell_y": self.cell_y,
+                "nx_cells": self.nx_cells, "ny_cells": self.ny_cells}
+
+
+def footprint_bin(fp: FootprintPlan, x, y, l, channel, num_lmd: int, out=None) -> np.ndarray:
+    """The footprint sink on the host (``wgrt_footprint_bin_host``; numpy arrays, no GPU needed) through the kernels'
+    binning rule: point i adds 1 to ``out[l[i], channel[i], iy, ix]``; a point outside the plan, with a non-finite
+    coordinate, or with ``l`` / ``channel`` out of range is dropped.  Adds into ``out`` (C-contiguous int64
+    ``[num_lmd, 9, ny_cells, nx_cells]``) when given."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    l = np.ascontiguousarray(np.broadcast_to(np.asarray(l, dtype=np.int32), x.shape))
+    channel = np.ascontiguousarray(np.broadcast_to(np.asarray(channel, dtype=np.int32), x.shape))
+    if x.ndim != 1 or y.shape != x.shape:
+        raise ValueError("x, y must be 1-D arrays of one length")
+    shape = (int(num_lmd), len(FOOTPRINT_CHANNELS), fp.ny_cells, fp.nx_cells)
+    if out is None:
+        out = np.zeros(shape, dtype=np.int64)
+    elif out.dtype != np.int64 or not out.flags.c_contiguous or out.shape != shape:
+        raise ValueError(f"out must be a C-contiguous int64 array of shape {shape}")
+    check(load().wgrt_footprint_bin_host(ctypes.byref(fp.c_plan()), x.ctypes.data, y.ctypes.data, l.ctypes.data,
+                                         channel.ctypes.data, x.shape[0], int(num_lmd), out.ctypes.data),
+          "wgrt_footprint_bin_host")
+    return out
+
+
 def _debug_opts(debug: dict | None):
     if not debug:
         return None
@@ -251,9 +325,22 @@ def _read_columns(rays, rng_states, n_rays, single, device):
 
 def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single, chunk_order=None, num_iter=1, gid_blocks=None, gid_block_rays=0, debug=None,
-           grid_sqrt_k=0.0, windows=None, chain=False, fate=None, replicas=0, expected=False):
+           grid_sqrt_k=0.0, windows=None, chain=False, fate=None, replicas=0, expected=False, footprint=None):
     device = torch.device("cuda", scene.device)
     B = _replica_count(replicas)
+    if footprint is not None:   # (before anything is read or launched)
+        if fate is not None or B or expected:
+            raise ValueError("footprint= is not combined with fate, replicas or expected")
+        if int(num_iter) > 1:
+            raise ValueError("footprint= needs num_iter == 1: the maps are filled by single launches")
+        if chain:
+            raise ValueError("a chain takes no footprint launches")
+        fp, fp_map = footprint
+        if not isinstance(fp, FootprintPlan):
+            raise TypeError("footprint=(FootprintPlan, map)")
+        _as_dev(fp_map, torch.int64, "footprint map", device)
+        if tuple(fp_map.shape) != fp.map_shape(scene):
+            raise ValueError(f"footprint map shape {tuple(fp_map.shape)} != {fp.map_shape(scene)}")
     if expected:   # (before anything is read or launched)
         if matrix_EB is not None:
             raise ValueError("expected=True takes no grid (matrix_EB=None): a float32 cell cannot hold the 2^-32 sums")
@@ -323,7 +410,11 @@ def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ra
         if h <= 0:   # the negated wgrt_status of the failure
             check(-h, "wgrt_chain_begin")
         return h, (args, dbg, windows)
-    if expected:   # torch.ops.wgrt.trace_expected -> wgrt_trace_expected (no grid; B = 0: the one table)
+    if footprint is not None:   # torch.ops.wgrt.trace_footprint -> wgrt_trace_footprint
+        status = ops().trace_footprint(*args, plan.handle.value if windows is not None else 0,
+                                       table if windows is not None else None, fp.x0, fp.y0, fp.cell_x, fp.cell_y,
+                                       fp.nx_cells, fp.ny_cells, fp_map)
+    elif expected:   # torch.ops.wgrt.trace_expected -> wgrt_trace_expected (no grid; B = 0: the one table)
         status = ops().trace_expected(*args[:10], *args[11:], plan.handle.value, table, B)
     elif fate is not None:   # torch.ops.wgrt.trace_fate -> wgrt_trace_fate (plan 0, no table: the grid alone)
         status = ops().trace_fate(*args, plan.handle.value if windows is not None else 0,
@@ -369,9 +460,11 @@ class TraceChain:
                  variant: int = VARIANT_AUTO, workgroups: int = 0, chunk_order: torch.Tensor | None = None,
                  gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
                  grid_sqrt_k: float = 0.0, windows=None, replicas: int = 0, expected: bool = False,
-                 gather: bool | int = False, hold: bool = False):
+                 gather: bool | int = False, hold: bool = False, footprint=None):
         if scene.single_lambda:
             raise ValueError("TraceChain needs a full-colour scene")
+        if footprint is not None:
+            raise ValueError("a chain takes no footprint launches: trace footprint maps with single launches")
         if expected:
             raise ValueError("a chain takes no expected-value launches: trace them with single launches")
         if _replica_count(replicas):
@@ -742,6 +835,6 @@ def expected_weight(e1: float, e2: float, e3: float, en1: float, en2: float, en3
     return float(load().wgrt_expected_weight_host(e1, e2, e3, en1, en2, en3, threshold))
 
 
-__all__ = ["Scene", "WindowPlan", "TraceChain", "fold_replicas", "expected_weight", "MAX_REPLICAS", "fate_census", "fate_census_host", "fate_col", "loss_budget", "FATE_CLASSES", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
+__all__ = ["Scene", "WindowPlan", "FootprintPlan", "footprint_bin", "FOOTPRINT_CHANNELS", "TraceChain", "fold_replicas", "expected_weight", "MAX_REPLICAS", "fate_census", "fate_census_host", "fate_col", "loss_budget", "FATE_CLASSES", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
            "trace_fullcolor", "trace_single", "init_rays", "schedule_by_lifetime",
            "rays_to_device", "classify_points", "shadow", "selftest_math", "RAY_COLUMNS", "_lib"]

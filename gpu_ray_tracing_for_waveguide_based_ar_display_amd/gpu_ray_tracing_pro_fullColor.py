@@ -23,6 +23,8 @@ Same flow as the reference script, on the MI355X kernel:
    tile, and the loss budget -- where the rays that did not reach the eyebox went -- is printed per wavelength;
    with ``error_bars=B`` (``--error-bars B``, windows mode) the trace counts into ``B`` replica tables by ray id and
    every printed figure carries a jackknife standard error;
+   with ``footprint=(H, W)`` (``--footprint HxW``) every launch also counts each interaction into a per-wavelength
+   plate map -- where the light interacts, is lost and leaves (``wgrt_trace_footprint``);
 6. the "Eyebox Center View.png" export (MAIN:199-203): the evaluated image at the first eye row,
    last eye column, as 8-bit RGB, rows flipped (``eyebox_center_view``, written without OpenCV).
 
@@ -55,7 +57,8 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
         point_seed: int | None = None, evaluate: bool = True, verbose: bool = True, variant: int = 0,
         fuse: bool | None = None, points: np.ndarray | None = None, png: str | None = None,
         eyebox: str = "host", keep_grid: bool = False, evaluate_on: str = "host",
-        keep_image: bool = False, budget: bool = False, error_bars: int = 0, estimator: str = "analog") -> dict:
+        keep_image: bool = False, budget: bool = False, error_bars: int = 0, estimator: str = "analog",
+        footprint=None) -> dict:
     """The reference script's job on this engine; returns its printed quantities and arrays.
     ``points``: the R/2 in-coupler origins to use (default: sampled, GRTF:12-23, seeded by
     ``point_seed``); ``png``: where to write the "Eyebox Center View" image (needs ``evaluate``).
@@ -111,7 +114,24 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
     the window table, so ``A``, the efficiencies, the three figures and their ``_se`` come from a table with the same
     expectation and a fraction of the variance.  It needs ``eyebox="windows"`` (a grid cannot hold the sums), goes as
     plain single launches, combines with ``error_bars``, both ``evaluate_on`` and several GPUs, and excludes
-    ``budget=True``; anything else raises ``ValueError`` before any GPU work.  The result says which in ``estimator``."""
+    ``budget=True``; anything else raises ``ValueError`` before any GPU work.  The result says which in ``estimator``.
+
+    ``footprint``: ``(H, W)`` (None: none): also report where on the plate the light interacts, is lost and leaves.
+    Every launch counts each Monte-Carlo draw of the bounce loop into an int64 map ``[num_lmd, 9, H, W]`` over the
+    bounding box of ``eff_reg1`` (``engine.FootprintPlan.for_scene``, ``engine.trace_fullcolor(footprint=...)``):
+    channels 0..5 the draws in state R0..R5, 6 the draws that lost the ray, 7 / 8 those that out-coupled it inside /
+    beside its eyebox rectangle.  The traces go as plain single launches; several GPUs sum-reduce their maps to rank
+    0.  Returned as ``footprint`` (the numpy map) and ``footprint_plan`` (the plan's fields) and printed per
+    wavelength as totals.  Works with every ``eyebox`` mode; everything else returned is bit-identical to the run
+    without it.  ``budget=True``, ``error_bars`` and ``estimator="expected"`` with it raise ``ValueError`` before any GPU
+    work."""
+    if footprint is not None:
+        if budget or error_bars or estimator == "expected":
+            raise ValueError("footprint is not combined with budget=True, error_bars or estimator='expected': a launch "
+                             "counts footprints or does one of those")
+        if len(tuple(footprint)) != 2 or not all(3 <= int(v) <= 4096 for v in footprint):
+            raise ValueError(f"footprint must be (H, W) cells, each 3 .. 4096, got {footprint!r}")
+        footprint = (int(footprint[0]), int(footprint[1]))
     if estimator not in ("analog", "expected"):
         raise ValueError(f"estimator must be 'analog' or 'expected', got {estimator!r}")
     expected = estimator == "expected"
@@ -148,6 +168,11 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
     with _set_up(num_FOV_x, num_FOV_y, int(num_rays_per_FoV), num_iter, lambdas, lut_dir, lut_seed, lut_profile,
                  point_seed, points, verbose, eyebox == "windows", budget, error_bars) as job:   # closes the scene on every way out
         job.expected = expected
+        job.footprint = None
+        if footprint is not None:
+            from .engine import FootprintPlan
+            fp = FootprintPlan.for_scene(job.geom, cells=footprint)
+            job.footprint = (fp, fp.new_map(job.scene))
         kern_s = _trace(job, variant, fuse)
         t_post = time.perf_counter()   # everything below is post-processing of the traced grid
         grid, table, stats = _collect(job, eyebox != "host", keep_grid)
@@ -159,11 +184,17 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
                    eyebox_hits=int(stats[STAT.eyebox_hits]), rng_states=job.rng.cpu().numpy().view(np.uint32),
                    estimator=estimator)
         census = _census(job)
+        fmap = None
+        if job.footprint is not None:   # integer counts: the ranks' maps add exactly
+            from .distributed import reduce_eyebox
+            fmap = reduce_eyebox(job.footprint[1])
         if job.rank != 0:
             return out
         _report(job, out, grid, table, reps)
         if census is not None:
             _report_budget(job, out, census)
+        if fmap is not None:
+            _report_footprint(job, out, fmap)
         if evaluate:
             _evaluate(job, out, grid, table, evaluate_on, keep_image, png, reps)
         out["post_seconds"] = time.perf_counter() - t_post
@@ -228,7 +259,7 @@ def _set_up(nx, ny, R, num_iter, lambdas, lut_dir, lut_seed, lut_profile, point_
                                   dev=dev, say=say, scene=scene, shards=shards, shard=shards[rank], rays=rays, rng=rng,
                                   eb=eb, windows=(plan, plan.new_table(scene, replicas=replicas)) if windows else None,
                                   stats=new_stats(dev), num_rays=num_rays, fate=fate, census=census,
-                                  replicas=replicas)
+                                  replicas=replicas, geom=geom)
         finally:
             if plan is not None:
                 plan.close()
@@ -251,6 +282,8 @@ def _trace(job, variant, fuse) -> float:
         hook = lambda j, when: when == "end" and fate_census(job.scene, job.rays, job.fate, table=job.census)
     if job.replicas or getattr(job, "expected", False):   # only a single launch fills replica tables or scores the
         per_call = 1                                      # expected-value estimator; the tracer offers no chain
+    if getattr(job, "footprint", None) is not None:       # ... or counts footprints
+        per_call = 1
     calls = split_calls(job.num_iter, per_call)
     if n_rays and calls:
         reserve(job.scene, n_rays, max(calls))
@@ -258,7 +291,8 @@ def _trace(job, variant, fuse) -> float:
     t0.record()
     if n_rays:
         run_steps(hip_tracer(job.scene, variant, job.stats, job.windows, fate=job.fate, replicas=job.replicas,
-                             expected=getattr(job, "expected", False)), job.rays, job.rng, job.eb,
+                             expected=getattr(job, "expected", False), footprint=getattr(job, "footprint", None)),
+                  job.rays, job.rng, job.eb,
                   job.shard.gid, job.num_iter, per_call, hook=hook)
     t1.record()
     torch.cuda.synchronize()
@@ -314,6 +348,19 @@ def _report_budget(job, out: dict, census) -> None:
     for name, _, _ in FATE_CLASSES:
         row = [w["fractions"][name] for w in b["per_wavelength"]] + [b["total"]["fractions"][name]]
         job.say(f"  {name:18s}" + "".join(f"{v * 100:9.3f}%" for v in row))
+
+
+def _report_footprint(job, out: dict, fmap) -> None:
+    """The footprint map into ``out`` and its totals printed per wavelength (``engine.FOOTPRINT_CHANNELS``)."""
+    from .engine import FOOTPRINT_CHANNELS
+    out["footprint"] = m = fmap.cpu().numpy()
+    out["footprint_plan"] = job.footprint[0].as_dict()
+    names = {0: "Blue", 1: "Green", 2: "Red"}
+    tot = m.sum(axis=(2, 3))   # [num_lmd, 9]
+    job.say(f"Footprint ({m.shape[2]} x {m.shape[3]} cells): interactions per state, and where the light is lost / leaves")
+    job.say("  " + " " * 10 + "".join(f"{c:>15s}" for c in FOOTPRINT_CHANNELS))
+    for l in range(m.shape[0]):
+        job.say(f"  {names.get(l, str(l)):10s}" + "".join(f"{int(v):15,d}" for v in tot[l]))
 
 
 def _report(job, out: dict, grid, table, reps=None) -> None:
@@ -448,6 +495,11 @@ def main(argv=None):
     ap.add_argument("--evaluate", choices=["host", "device"], default="host",
                     help="where the evaluation's colour math runs: host (numpy) or device (wgrt_eyebox_evaluate on "
                          "the window-sum table; needs --eyebox device or windows)")
+    ap.add_argument("--footprint", default="", metavar="HxW",
+                    help="also count every interaction into a per-wavelength plate map of H x W cells (interactions per "
+                         "state, where light is lost and where it out-couples); not with --budget, --error-bars or "
+                         "--estimator expected")
+    ap.add_argument("--footprint-out", default="", metavar="FILE.npy", help="save the footprint map there (numpy)")
     ap.add_argument("--budget", action="store_true",
                     help="also report where every ray ended: per-ray fates, their per-tile census and the loss budget "
                          "per wavelength (the traces then run as plain single launches)")
@@ -467,10 +519,21 @@ def main(argv=None):
         local = int(os.environ.get("LOCAL_RANK", "0"))
         torch.cuda.set_device(local)
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
+    footprint = None
+    if a.footprint:
+        try:
+            footprint = tuple(int(v) for v in a.footprint.lower().split("x"))
+        except ValueError:
+            footprint = ()
+        if len(footprint) != 2:
+            ap.error(f"--footprint takes HxW, got {a.footprint!r}")
     res = run(a.num_fov_x, a.num_fov_y, a.rays_per_fov, a.num_iter, lut_dir=a.lut_dir, lut_seed=a.lut_seed,
               lut_profile=a.lut_profile, point_seed=a.point_seed, evaluate=not a.no_eval,
               fuse=False if a.no_fuse else {"auto": None, "yes": True, "no": False}[a.fuse],
-              png=a.png or None, eyebox=a.eyebox, evaluate_on=a.evaluate, budget=a.budget, error_bars=a.error_bars, estimator=a.estimator)
+              png=a.png or None, eyebox=a.eyebox, evaluate_on=a.evaluate, budget=a.budget, error_bars=a.error_bars, estimator=a.estimator,
+              footprint=footprint)
+    if a.footprint_out and "footprint" in res:   # (rank 0 has the map)
+        np.save(a.footprint_out, res["footprint"])
     if a.json and (not dist.is_initialized() or dist.get_rank() == 0):
         keep = {k: v for k, v in res.items() if isinstance(v, (int, float, dict, str))}
         with open(a.json, "w") as f:

@@ -550,6 +550,47 @@ wgrt_status wgrt_trace_expected(const wgrt_scene *scene, const wgrt_rays *rays, 
 /* Host-only (no GPU needed): q of the rule above, through the code the kernels run (csrc/wgrt_expected.h). */
 double wgrt_expected_weight_host(double e1, double e2, double e3, double en1, double en2, double en3, double threshold);
 
+/* Where on the plate: interaction and out-coupling footprint maps (new symbols within ABI 9, looked up by name).
+ *
+ * wgrt_trace_footprint is wgrt_trace_windows that also counts, per wavelength, where on the plate the rays interact,
+ * are lost and leave: map is DEVICE int64 [num_lmd, WGRT_FOOTPRINT_CHANNELS, ny_cells, nx_cells], ADDED to, never
+ * zeroed.  The plan is passed by value; a point (x, y) counts into the cell
+ *     ix = (int64_t)floor((x - x0) / cell_x),   iy = (int64_t)floor((y - y0) / cell_y)
+ * at the flat offset ((l * 9 + c) * ny_cells + iy) * nx_cells + ix, and is dropped when ix is outside [0, nx_cells),
+ * iy outside [0, ny_cells) or a coordinate is not finite.  The position is always the ray's at the draw, before the
+ * taken branch moves it.  Channels 0..5: every Monte-Carlo draw of the bounce loop in state R0..R5 (4 after the
+ * R3 -> R4 switch) -- exactly the draws wgrt_trace_stats.interactions counts; the in-coupling event is not counted.
+ * Channel 6: the draws that took no branch (fate reason 2).  Channel 7 / 8: the draws that out-coupled the ray inside /
+ * outside its FoV's eyebox rectangle (reasons 3 / 4: the rectangle test, not the aliased store).  The counts are
+ * integers: the map is the same bits on every run and for every work split, and the maps of shards add up exactly.
+ *   fp    cell sizes > 0 and finite, a finite origin, 1 <= nx_cells, ny_cells <= 4096, else WGRT_ERR_INVALID_ARGUMENT;
+ *   map   NULL: the call is exactly wgrt_trace_windows (fp is then not looked at).
+ * With a map, rng_states, matrix_EB, the window table, per_ray_bounces and every field of stats come out bit-identical
+ * to the launch without it.  A footprint launch is a single launch, as fate launches are: opts->num_iter > 1 is
+ * WGRT_ERR_INVALID_ARGUMENT, wgrt_chain_begin takes none, no entry point combines it with fates, replicas or the
+ * expected-value estimator, wgrt_debug_opts.timeline is WGRT_ERR_UNSUPPORTED, and it never learns the scene's tile
+ * table.  A ray the Jones lane abandons is re-traced by the exact lane past the draws already counted, so none is
+ * counted twice.  The call allocates nothing beyond the stream's launch scratch (wgrt_scene_reserve) and is
+ * asynchronous on stream.  A launch through any other entry point runs the kernels it ran before this one existed. */
+#define WGRT_FOOTPRINT_CHANNELS 9
+typedef struct wgrt_footprint_plan {
+    double x0, y0, cell_x, cell_y;
+    int32_t nx_cells, ny_cells;
+} wgrt_footprint_plan;
+wgrt_status wgrt_trace_footprint(const wgrt_scene *scene, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
+                                 uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats,
+                                 uint32_t *per_ray_bounces, void *stream, const wgrt_launch_opts *opts,
+                                 const wgrt_window_plan *plan, double *table, const wgrt_footprint_plan *fp,
+                                 int64_t *map);
+/* Host-only (no GPU needed) through the same rule (csrc/wgrt_footprint.h): _validate is wgrt_trace_footprint's plan
+ * check alone; _bin_host ADDS the n points (HOST x, y float64; l, channel int32) to the HOST map of num_lmd
+ * wavelengths: a point whose l is outside [0, num_lmd) or whose channel is outside [0, 9) is dropped like one
+ * outside the plan; _channel_name names channel c ("R0" .. "R5", "lost", "eyebox", "beside_eyebox"; NULL otherwise). */
+wgrt_status wgrt_footprint_plan_validate(const wgrt_footprint_plan *fp);
+wgrt_status wgrt_footprint_bin_host(const wgrt_footprint_plan *fp, const double *x, const double *y, const int32_t *l,
+                                    const int32_t *channel, int64_t n, int32_t num_lmd, int64_t *map);
+const char *wgrt_footprint_channel_name(int c);
+
 /* Host-only (no GPU needed; test hooks) through the same membership code (csrc/wgrt_window.h):
  * _validate is wgrt_window_plan_create's argument check alone; _table_host ADDS the n hits at flat grid
  * offsets offsets[n] (HOST int64; those outside [0, n_slabs * 9600) are dropped, as the grid's guard drops

@@ -184,6 +184,12 @@ typedef struct {
 } wgrt_chain_report;
 wgrt_status wgrt_debug_chain_report(const wgrt_chain *chain, wgrt_chain_report *out);
 
+/* The footprint sink's two forms in one binary (wgrt_trace_footprint; process-wide; the A/B and the tests): 1 (the
+ * default) sums the counts that share a map entry on chip before they go to the map -- the Jones-vector lane in a
+ * per-wave counter cache in LDS, the exact lane over the lanes of a wave; 0 issues one global atomic per count.  Both
+ * give the same map. */
+wgrt_status wgrt_debug_set_footprint_aggregate(int on);
+
 #ifdef __cplusplus
 }
 #endif
