@@ -10,6 +10,7 @@
 
 #include "wgrt_args.h"
 #include "wgrt_host.h"
+#include "wgrt_trace_mode.h"
 
 struct wgrt_scene {
     int device = 0;
@@ -36,16 +37,12 @@ struct wgrt_scene {
     wgrt::LocatorHost loc_host;  // grid parameters (cells / verts vectors released after upload)
     int64_t tiles = 0;
     int64_t edge_cells = 0;        // locator cells with an EDGE class
-    // resident 256-thread workgroups, each [byte locator] first: the word-form and the byte-form instantiations
-    int jones_grid[2][2][2][2] = {};   // [64-bit cells][fused][single wavelength]
-    int jones_tl_grid[2][2] = {};      // ... of the debug timeline instantiations (32-bit cells): [fused]
-    int jones_fate_grid[2][2][2] = {}; // ... of the fate-storing instantiations (wgrt_trace_fate): [64-bit cells][single wavelength]
-    int jones_reps_grid[2][2][2] = {}; // ... of the replica-table instantiations (wgrt_trace_replicas): the same axes
-    int jones_ev_grid[2][2][2] = {};   // ... of the expected-value instantiations (wgrt_trace_expected): the same axes
-    int jones_fp_grid[2][2][2] = {};   // ... of the footprint instantiations (wgrt_trace_footprint): the same axes
-    int jones_learn_grid[2][2] = {};   // ... of the learning instantiations (full colour, single trace): [64-bit cells]
-    int jones_chain_grid[2][2] = {};   // ... the most a chained step may use (wgrt_chain_*): [64-bit cells], half the
-                                       // resident grid less a margin (query_trace_grids)
+    // resident 256-thread workgroups of the Jones kernels, by [mode][byte locator][64-bit cells][fused][single
+    // wavelength] (wgrt_trace_mode.h; the smaller of the plain and the AMP instantiation's; 0: none is built) ...
+    int jones_grid[wgrt::kTraceModes][2][2][2][2] = {};
+    // ... and the most a chained step may use (wgrt_chain_*), by [byte locator][64-bit cells]: half the resident
+    // grid less a margin (query_trace_grids)
+    int jones_chain_grid[2][2] = {};
     int64_t nonunitary_blocks = 0;  // Jones blocks whose branch matrices are not scaled-unitary (their launches
                                     // run the AMP instantiations: wgrt_jones_lane.h, the amplification step)
     // The automatic issue order's statistic (wgrt_order.h): per (wavelength, FoV) tile, the traces of the
@@ -104,7 +101,7 @@ namespace wgrt {
 
 // What scene creation and destruction need from the trace unit (wgrt_trace.hip), the one place that
 // instantiates the trace kernels and knows the launch scratch:
-// the resident grid of every trace kernel instantiation (jones_grid / jones_tl_grid / jones_learn_grid) from the occupancy queries ...
+// the resident grid of every trace kernel instantiation (jones_grid, jones_chain_grid) from the occupancy queries ...
 wgrt_status query_trace_grids(wgrt_scene *s);
 // ... and the release of one stream's launch scratch (the scene's device is current)
 void free_scratch(wgrt_scene::Scratch &sc);

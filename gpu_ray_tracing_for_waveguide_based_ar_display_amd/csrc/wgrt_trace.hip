@@ -29,6 +29,7 @@
 #include <initializer_list>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/wgrt.h"
@@ -39,6 +40,7 @@
 #include "wgrt_jones_lane.h"
 #include "wgrt_launch_args.h"
 #include "wgrt_order.h"
+#include "wgrt_trace_mode.h"
 
 using namespace wgrt;
 
@@ -268,36 +270,40 @@ __device__ __host__ __forceinline__ uint32_t chain_tag(uint32_t serial, bool bro
 // An abandoned ray (kUncertain) onto the replay list.  With the in-kernel replay the entry is stored at
 // agent scope and waited for here, so it is in memory before this lane's workgroup counts itself done
 // (the last workgroup reads the list at agent scope); rare, so the wait costs nothing measurable.
-__device__ __forceinline__ void record_abandoned(const KArgs &K, uint32_t i) {
-    uint32_t *const slot = KA(replay_list) + atomicAdd(KA(replay_count), 1ull);
+//
+// Two sinks have taken part of the ray by then, and their entry carries a count that the replay passes over
+// (trace_one's skip), `seen`, in a word array beside the replay list -- the one statement of where:
+//   kEv  the scored visits whose deposits have been made.  An expected-value launch keeps its visits in LDS and has no
+//        out-coupling queue in memory, so the counts use q_i -- sized for at least one entry per ray, like the replay
+//        list -- and nothing is allocated for them;
+//   kFp  the draws counted into the map.  A footprint launch does use the out-coupling queue, so the counts have a
+//        word of their own per replay-list entry (TraceArgs::fp_seen, part of the stream's launch scratch);
+//   every other mode has written nothing of an abandoned ray, and keeps no count.
+template <TraceMode M>
+constexpr bool kSeenCounted = M == TraceMode::kEv || M == TraceMode::kFp;
+template <TraceMode M>
+__device__ __forceinline__ uint32_t *seen_counts(const KArgs &K) {
+    static_assert(kSeenCounted<M>, "only the expected-value and footprint launches count what the replay passes over");
+    if constexpr (M == TraceMode::kEv) return KA(q_i);
+    else return KA(fp_seen);
+}
+
+template <TraceMode M>
+__device__ __forceinline__ void record_abandoned(const KArgs &K, uint32_t i, uint32_t seen) {
+    if constexpr (kSeenCounted<M>) {
+        const unsigned long long k = atomicAdd(KA(replay_count), 1ull);
+        __hip_atomic_store(KA(replay_list) + k, i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(seen_counts<M>(K) + k, seen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else {
+        uint32_t *const slot = KA(replay_list) + atomicAdd(KA(replay_count), 1ull);
 #if WGRT_INKERNEL_REPLAY
-    __hip_atomic_store(slot, i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __hip_atomic_store(slot, i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #else
-    *slot = i;
+        *slot = i;
 #endif
-}
-
-// The same for an expected-value launch (jones_body, EV), whose deposits up to here have been made: the entry
-// carries the number of scored visits, which the replay passes over (trace_one's ev_skip).  An expected-value launch
-// keeps its visits in LDS and has no out-coupling queue in memory, so the counts use q_i -- sized for at least one
-// entry per ray, like the replay list -- and nothing is allocated for them.
-__device__ __forceinline__ void record_abandoned_ev(const KArgs &K, uint32_t i, uint32_t seen) {
-    const unsigned long long k = atomicAdd(KA(replay_count), 1ull);
-    __hip_atomic_store(KA(replay_list) + k, i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(KA(q_i) + k, seen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-// The same for a footprint launch (jones_body, FP), whose counts up to here are in the map: the entry carries the
-// number of counted draws, which the replay passes over (trace_one's skip).  A footprint launch does use the
-// out-coupling queue, so the counts have a word of their own per replay-list entry (TraceArgs::fp_seen, part of the
-// stream's launch scratch).
-__device__ __forceinline__ void record_abandoned_fp(const KArgs &K, uint32_t i, uint32_t seen) {
-    const unsigned long long k = atomicAdd(KA(replay_count), 1ull);
-    __hip_atomic_store(KA(replay_list) + k, i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(KA(fp_seen) + k, seen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
 }
 
 #if WGRT_INKERNEL_REPLAY
@@ -305,38 +311,29 @@ __device__ __forceinline__ void record_abandoned_fp(const KArgs &K, uint32_t i, 
 // reference-arithmetic lane (trace_one) over the replay list, its TraceArgs read from the kernarg segment
 // here, so nothing of it is live across the wave loop.  Inlined: as a real call it gave the wave loop 128
 // VGPRs and scratch (above).
-template <bool FATE, bool EV, bool FP = false>
+// kChain: the abandoned ray's start state is what the previous step published (its granule still holds it: only
+// this step's trace of the ray writes it next), and its end is published like a retire's, for the next step's
+// waiters.
+template <TraceMode M>
 __device__ __forceinline__ void replay_tail(const KArgs &K, unsigned long long nr) {
     const TraceArgs R = K.args();
     const uint32_t *const list = KA(replay_list);
     Counters c;
     for (unsigned long long k = threadIdx.x; k < nr; k += blockDim.x) {
-        // EV: the visits the Jones lane scored before it abandoned the ray (record_abandoned_ev)
-        uint32_t skip = 0;
-        if (EV) skip = __hip_atomic_load(KA(q_i) + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // FP: the draws it counted (record_abandoned_fp)
-        if (FP) skip = __hip_atomic_load(KA(fp_seen) + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        trace_one<FATE, EV, FP>(R, (int64_t)__hip_atomic_load(list + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), c,
-                                nullptr, skip);
-    }
-    c.wave_reduce();
-    if (threadIdx.x == 0) c.w[kCtrReplayed] = nr;
-    if ((threadIdx.x & 63) == 0 && R.stats) c.add_to(R.stats);
-}
-// The same for a chained step: the abandoned ray's start state is what the previous step published (its granule
-// still holds it: only this step's trace of the ray writes it next), and its end is published like a retire's,
-// for the next step's waiters.
-__device__ __forceinline__ void replay_tail_chain(const KArgs &K, unsigned long long nr) {
-    const TraceArgs R = K.args();
-    const uint32_t *const list = KA(replay_list);
-    Counters c;
-    for (unsigned long long k = threadIdx.x; k < nr; k += blockDim.x) {
-        const int64_t i = (int64_t)__hip_atomic_load(list + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uint64_t was = __hip_atomic_load(R.rng64 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uint32_t st = (uint32_t)(was >> 32);
-        trace_one(R, i, c, &st);
-        __hip_atomic_compare_exchange_strong(R.rng64 + i, &was, ((uint64_t)st << 32) | chain_tag(R.iter_epoch, false),
-                                             __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if constexpr (M == TraceMode::kChain) {
+            const int64_t i = (int64_t)__hip_atomic_load(list + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            uint64_t was = __hip_atomic_load(R.rng64 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            uint32_t st = (uint32_t)(was >> 32);
+            trace_one(R, i, c, &st);
+            __hip_atomic_compare_exchange_strong(R.rng64 + i, &was, ((uint64_t)st << 32) | chain_tag(R.iter_epoch, false),
+                                                 __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else {
+            uint32_t skip = 0;   // what the Jones lane counted before it abandoned the ray (record_abandoned)
+            if constexpr (kSeenCounted<M>)
+                skip = __hip_atomic_load(seen_counts<M>(K) + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            trace_one<M == TraceMode::kFate, M == TraceMode::kEv, M == TraceMode::kFp>(
+                R, (int64_t)__hip_atomic_load(list + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), c, nullptr, skip);
+        }
     }
     c.wave_reduce();
     if (threadIdx.x == 0) c.w[kCtrReplayed] = nr;
@@ -357,7 +354,7 @@ __device__ __forceinline__ void finish_fused(const KArgs &K, Counters c) {
 // each per workgroup: not contended), waits for them, and counts the workgroup done; the workgroup that
 // counts last reads the totals at agent scope, adds them to *stats, zeroes the next launch's counter set
 // (every other workgroup has left this one's) and replays.
-template <bool CHAIN, bool FATE, bool EV, bool FP = false>
+template <TraceMode M>
 __device__ __forceinline__ void finish_single(const KArgs &K, Counters c) {
     __shared__ unsigned long long red[4][kCtrWords];
     __shared__ int last_wg;
@@ -385,10 +382,7 @@ __device__ __forceinline__ void finish_single(const KArgs &K, Counters c) {
     // the reference arithmetic -- no replay kernel behind the launch.  Every list entry was stored at
     // agent scope and waited for by its lane before that lane's workgroup counted itself done.
     const unsigned long long nr = __hip_atomic_load(KA(replay_count), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (__builtin_expect(nr != 0ull, 0)) {
-        if (CHAIN) replay_tail_chain(K, nr);
-        else replay_tail<FATE, EV, FP>(K, nr);
-    }
+    if (__builtin_expect(nr != 0ull, 0)) replay_tail<M>(K, nr);
 #endif
 }
 
@@ -402,6 +396,7 @@ __device__ __forceinline__ void finish_single(const KArgs &K, Counters c) {
 // (waiting in place, lane idle, until the tag says k) -- the granule hand-off of
 // MI355X_MICROARCH.md's price list, valid whatever the XCD placement.  Results are identical
 // to n_iter launches: each ray's traces run in order from the same states; eyebox adds commute.
+// M: the launch's one mode (wgrt_trace_mode.h), under the names the body derives from it -- kPlain sets none of them:
 // TL: the debug wave timeline (wgrt_debug_opts.timeline); the product instantiations have TL = false
 // and contain none of its code.
 // LEARN: the learning launches of the automatic issue order (single traces; wgrt_order.h): a trace that ends
@@ -496,10 +491,16 @@ __device__ __forceinline__ void fp_flush(LdsU64 *tab, int64_t *map) {
     }
 }
 
-template <bool FUSED, bool SINGLE, bool TL, bool AMP, bool LEARN, bool CHAIN, bool FATE, bool REPS, bool EV, class Loc,
-          bool FP = false>
+template <TraceMode M, bool FUSED, bool SINGLE, bool AMP, class Loc>
 __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, const Loc &loc, unsigned long long *heads,
                                           int chunk) {
+    // the mode under the names the body tests (at most one of them is set)
+    constexpr bool TL = M == TraceMode::kTimeline, LEARN = M == TraceMode::kLearn, CHAIN = M == TraceMode::kChain,
+                   FATE = M == TraceMode::kFate, REPS = M == TraceMode::kReps, EV = M == TraceMode::kEv,
+                   FP = M == TraceMode::kFp;
+    static_assert(!FUSED || M == TraceMode::kPlain || TL, "only plain and timeline launches are built fused");
+    static_assert(!(FATE || REPS || EV || FP) || WGRT_INKERNEL_REPLAY,
+                  "the sink modes are single launches whose replay runs in the kernel (replay_tail<M>)");
     // Single launches (!FUSED) do their epilogue in this kernel (above), and retire a finished trace at one
     // place per pass, right after advance(): the rays that ended in the previous pass's interaction (fin)
     // and those advance() ends.  Fused launches retire at once: their hand-off would wait a pass.
@@ -540,12 +541,6 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
     int qfill = kQBlock;               // ... and how many of them are used (none reserved yet)
     bool qblk = false;                 // a block has been reserved
     uint32_t fate = 0;                 // FATE: the fate code of the trace that ended on this lane, until its retire
-    static_assert(!FATE || (!FUSED && !CHAIN && !LEARN && !TL && WGRT_INKERNEL_REPLAY),
-                  "fates are stored by plain single launches whose replay runs in the kernel (replay_tail<FATE>)");
-    static_assert(!REPS || (!FUSED && !CHAIN && !LEARN && !TL && !FATE && WGRT_INKERNEL_REPLAY),
-                  "replica tables are filled by plain single launches (the replay reads TraceArgs::win_reps itself)");
-    static_assert(!EV || (!FUSED && !CHAIN && !LEARN && !TL && !FATE && !REPS && WGRT_INKERNEL_REPLAY),
-                  "expected-value launches are plain single launches (their replica is read at run time)");
     // EV: this wave's block of scored visits, how many it holds (wave-uniform), the lane's scored visits of the
     // trace in flight, and the analog hits the wave has binned
     EvBlock *evb = nullptr;
@@ -555,8 +550,6 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
     }
     int evfill = 0;
     uint32_t ev_seen = 0, ev_hits = 0;
-    static_assert(!FP || (!FUSED && !CHAIN && !LEARN && !TL && !FATE && !REPS && !EV && WGRT_INKERNEL_REPLAY),
-                  "footprint launches are plain single launches (the replay passes over the counted draws)");
     uint32_t fp_seen = 0;              // FP: the draws of the trace in flight that this lane has counted
     // FP: this wave's counter cache (fp_cached); empty at the start (the wave's own LDS stores, in order)
     LdsU64 *fpc = nullptr;
@@ -811,9 +804,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             active = next >= 0;
             L.r.region = next >= 0 ? next : L.r.region;
             if (__builtin_expect(next == kUncertain, 0)) {
-                if (EV) record_abandoned_ev(K, L.i, ev_seen);
-                else if (FP) record_abandoned_fp(K, L.i, fp_seen);
-                else record_abandoned(K, L.i);
+                record_abandoned<M>(K, L.i, EV ? ev_seen : FP ? fp_seen : 0u);
             }
         } else {
             // one retire site for both ends of a trace (out-coupled, died)
@@ -823,7 +814,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
                 // so later iterations skip the ray
                 __hip_atomic_store(KA(rng64) + L.i, ((uint64_t)L.s0 << 32) | iter_tag(A.iter_epoch, L.k, true),
                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                record_abandoned(K, L.i);
+                record_abandoned<M>(K, L.i, 0u);
                 active = false;
             } else if (next < 0) {
                 // inside a run the ray starts its next trace on this lane, at the next pass's restart site; a run's
@@ -1189,7 +1180,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
     c.w[kCtrGiveups] = tot_giveup;
     c.w[kCtrInter] = tot_int;
     if (FUSED) finish_fused(K, c);
-    else finish_single<CHAIN, FATE, EV, FP>(K, c);
+    else finish_single<M>(K, c);
 }
 
 #if !WGRT_INKERNEL_REPLAY
@@ -1222,130 +1213,38 @@ constexpr int kChainMargin = 8;         // workgroups two chained grids leave fr
 template <class CellT, bool FUSED, bool SINGLE, bool AMP>
 __global__ WGRT_JONES_BOUNDS void trace_jones_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
                                                      int chunk) {
-    jones_body<FUSED, SINGLE, false, AMP, false, false, false, false, false>(
+    jones_body<TraceMode::kPlain, FUSED, SINGLE, AMP>(
         A, kernel_kargs<decltype(trace_jones_kernel<CellT, FUSED, SINGLE, AMP>)>(), loc, counter, chunk);
 }
 
-// The same loop with the debug wave timeline (wgrt_debug_opts.timeline; tools/timeline.py): a
-// separate instantiation, so the product kernels carry none of its code.
-template <class CellT, bool FUSED, bool SINGLE>
-__global__ WGRT_JONES_BOUNDS void trace_jones_tl_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
-                                                        int chunk) {
-    jones_body<FUSED, SINGLE, true, false, false, false, false, false, false>(A, kernel_kargs<decltype(trace_jones_tl_kernel<CellT, FUSED, SINGLE>)>(),
-                                                  loc, counter, chunk);
-}
-
-// The same loop counting each tile's long traces into the scene's tile_tail (the automatic issue order's
-// learning launches: full colour, single trace, scaled-unitary LUTs): again a separate instantiation.
-template <class CellT>
-__global__ WGRT_JONES_BOUNDS void trace_jones_learn_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
-                                                           int chunk, uint32_t *tail) {
-    jones_body<false, false, false, false, true, false, false, false, false>(A, kernel_kargs<decltype(trace_jones_learn_kernel<CellT>)>(), loc,
-                                                 counter, chunk);
-}
-
-// The single-launch loop as a step of a chain (wgrt_chain_*): full colour, no learning, no timeline.
-template <class CellT, bool AMP>
-__global__ WGRT_JONES_BOUNDS void trace_jones_chain_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
-                                                           int chunk) {
-    jones_body<false, false, false, AMP, false, true, false, false, false>(A, kernel_kargs<decltype(trace_jones_chain_kernel<CellT, AMP>)>(),
-                                                      loc, counter, chunk);
-}
-
-// The single-launch loop storing every ray's fate code (wgrt_trace_fate): both cell widths, full colour and
-// single wavelength, with and without the amplification step; no learning, timeline or chained twin (the launch
-// plan routes a fate launch around those: validate_launch, plan_auto_order).
-template <class CellT, bool SINGLE, bool AMP>
-__global__ WGRT_JONES_BOUNDS void trace_jones_fate_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
-                                                          int chunk) {
-    jones_body<false, SINGLE, false, AMP, false, false, true, false, false>(
-        A, kernel_kargs<decltype(trace_jones_fate_kernel<CellT, SINGLE, AMP>)>(), loc, counter, chunk);
-}
-
-// The single-launch loop into replica window tables (wgrt_trace_replicas): the same instantiations as the fate
-// kernels', and like them never a learning, timeline or chained launch (validate_launch, plan_auto_order).
-template <class CellT, bool SINGLE, bool AMP>
-__global__ WGRT_JONES_BOUNDS void trace_jones_reps_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
-                                                          int chunk) {
-    jones_body<false, SINGLE, false, AMP, false, false, false, true, false>(
-        A, kernel_kargs<decltype(trace_jones_reps_kernel<CellT, SINGLE, AMP>)>(), loc, counter, chunk);
-}
-
-// The single-launch loop of the expected-value estimator (wgrt_trace_expected): the fate kernels' instantiations
-// again, each reading the replica count at run time; never a learning, timeline or chained launch.
-template <class CellT, bool SINGLE, bool AMP>
-__global__ WGRT_JONES_BOUNDS void trace_jones_ev_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
-                                                        int chunk) {
-    jones_body<false, SINGLE, false, AMP, false, false, false, false, true>(
-        A, kernel_kargs<decltype(trace_jones_ev_kernel<CellT, SINGLE, AMP>)>(), loc, counter, chunk);
-}
-
-// The single-launch loop counting every draw into the footprint maps (wgrt_trace_footprint): the fate kernels'
-// instantiations again; never a learning, timeline or chained launch.
-template <class CellT, bool SINGLE, bool AMP>
-__global__ WGRT_JONES_BOUNDS void trace_jones_fp_kernel(TraceArgs A, LocatorT<CellT> loc, unsigned long long *counter,
-                                                        int chunk) {
-    jones_body<false, SINGLE, false, AMP, false, false, false, false, false, LocatorT<CellT>, true>(
-        A, kernel_kargs<decltype(trace_jones_fp_kernel<CellT, SINGLE, AMP>)>(), loc, counter, chunk);
-}
-
-// The same kernels over the byte locator (ByteLocatorT<CellT>: the scene's byte grid and palette), under names
+// The same kernels over the byte locator (ByteLocatorT<CellT>: the scene's byte grid and palette), under a name
 // of their own: the word forms above stay as they are, for scenes without a byte grid and for the A/B
 // (wgrt_debug_set_byte_locator).
 template <class CellT, bool FUSED, bool SINGLE, bool AMP>
 __global__ WGRT_JONES_BOUNDS void trace_jones_b_kernel(TraceArgs A, ByteLocatorT<CellT> loc, unsigned long long *counter,
                                                        int chunk) {
-    jones_body<FUSED, SINGLE, false, AMP, false, false, false, false, false>(
+    jones_body<TraceMode::kPlain, FUSED, SINGLE, AMP>(
         A, kernel_kargs<decltype(trace_jones_b_kernel<CellT, FUSED, SINGLE, AMP>)>(), loc, counter, chunk);
 }
 
-template <class CellT, bool FUSED, bool SINGLE>
-__global__ WGRT_JONES_BOUNDS void trace_jones_b_tl_kernel(TraceArgs A, ByteLocatorT<CellT> loc, unsigned long long *counter,
-                                                          int chunk) {
-    jones_body<FUSED, SINGLE, true, false, false, false, false, false, false>(
-        A, kernel_kargs<decltype(trace_jones_b_tl_kernel<CellT, FUSED, SINGLE>)>(), loc, counter, chunk);
+// The same loop in every other mode but kLearn (wgrt_trace_mode.h; jones_body's comment says what each adds), over
+// either locator form: separate instantiations, so the product kernels carry none of their code.  Which of them are
+// built is JonesKernels' business, below.
+template <class Loc, TraceMode M, bool FUSED, bool SINGLE, bool AMP>
+__global__ WGRT_JONES_BOUNDS void trace_jones_mode_kernel(TraceArgs A, Loc loc, unsigned long long *counter, int chunk) {
+    static_assert(M != TraceMode::kPlain && M != TraceMode::kLearn, "those modes have kernels of their own");
+    jones_body<M, FUSED, SINGLE, AMP>(A, kernel_kargs<decltype(trace_jones_mode_kernel<Loc, M, FUSED, SINGLE, AMP>)>(),
+                                      loc, counter, chunk);
 }
 
-template <class CellT>
-__global__ WGRT_JONES_BOUNDS void trace_jones_b_learn_kernel(TraceArgs A, ByteLocatorT<CellT> loc,
-                                                             unsigned long long *counter, int chunk, uint32_t *tail) {
-    jones_body<false, false, false, false, true, false, false, false, false>(
-        A, kernel_kargs<decltype(trace_jones_b_learn_kernel<CellT>)>(), loc, counter, chunk);
-}
-
-template <class CellT, bool AMP>
-__global__ WGRT_JONES_BOUNDS void trace_jones_b_chain_kernel(TraceArgs A, ByteLocatorT<CellT> loc,
-                                                             unsigned long long *counter, int chunk) {
-    jones_body<false, false, false, AMP, false, true, false, false, false>(
-        A, kernel_kargs<decltype(trace_jones_b_chain_kernel<CellT, AMP>)>(), loc, counter, chunk);
-}
-
-template <class CellT, bool SINGLE, bool AMP>
-__global__ WGRT_JONES_BOUNDS void trace_jones_b_fate_kernel(TraceArgs A, ByteLocatorT<CellT> loc,
-                                                            unsigned long long *counter, int chunk) {
-    jones_body<false, SINGLE, false, AMP, false, false, true, false, false>(
-        A, kernel_kargs<decltype(trace_jones_b_fate_kernel<CellT, SINGLE, AMP>)>(), loc, counter, chunk);
-}
-
-template <class CellT, bool SINGLE, bool AMP>
-__global__ WGRT_JONES_BOUNDS void trace_jones_b_reps_kernel(TraceArgs A, ByteLocatorT<CellT> loc,
-                                                            unsigned long long *counter, int chunk) {
-    jones_body<false, SINGLE, false, AMP, false, false, false, true, false>(
-        A, kernel_kargs<decltype(trace_jones_b_reps_kernel<CellT, SINGLE, AMP>)>(), loc, counter, chunk);
-}
-
-template <class CellT, bool SINGLE, bool AMP>
-__global__ WGRT_JONES_BOUNDS void trace_jones_b_ev_kernel(TraceArgs A, ByteLocatorT<CellT> loc,
-                                                          unsigned long long *counter, int chunk) {
-    jones_body<false, SINGLE, false, AMP, false, false, false, false, true>(
-        A, kernel_kargs<decltype(trace_jones_b_ev_kernel<CellT, SINGLE, AMP>)>(), loc, counter, chunk);
-}
-
-template <class CellT, bool SINGLE, bool AMP>
-__global__ WGRT_JONES_BOUNDS void trace_jones_b_fp_kernel(TraceArgs A, ByteLocatorT<CellT> loc,
-                                                          unsigned long long *counter, int chunk) {
-    jones_body<false, SINGLE, false, AMP, false, false, false, false, false, ByteLocatorT<CellT>, true>(
-        A, kernel_kargs<decltype(trace_jones_b_fp_kernel<CellT, SINGLE, AMP>)>(), loc, counter, chunk);
+// The same loop counting each tile's long traces into the scene's tile_tail (the automatic issue order's
+// learning launches: full colour, single trace, scaled-unitary LUTs), the one kernel with a fifth parameter
+// (kLearnTailOff).
+template <class Loc>
+__global__ WGRT_JONES_BOUNDS void trace_jones_learn_kernel(TraceArgs A, Loc loc, unsigned long long *counter, int chunk,
+                                                           uint32_t *tail) {
+    jones_body<TraceMode::kLearn, false, false, false>(A, kernel_kargs<decltype(trace_jones_learn_kernel<Loc>)>(), loc,
+                                                       counter, chunk);
 }
 
 // The two ends of a chain's segment, on the caller's stream: every ray's state into its granule under the
@@ -1422,91 +1321,90 @@ __global__ __launch_bounds__(kOrderThreads) void order_kernel(const float *m, co
     }
 }
 
-// Every trace kernel instantiation, stated once: the Jones kernels by [byte locator][64-bit cells][fused][single
-// wavelength][AMP], the debug timeline kernels (32-bit cells, full colour, no AMP) by [byte locator][fused].  The
-// occupancy queries loop over the tables and the launch indexes them, so a kernel cannot be in one and not the
-// other.  The fate-storing kernels (wgrt_trace_fate) by [byte locator][64-bit cells][single wavelength][AMP]: single
-// launches only; the replica kernels (wgrt_trace_replicas) likewise.  (WGRT_K2 / WGRT_K4: kernel K's instantiations over two / the last two of its bool parameters.)
-#define WGRT_K2(K, C, ...) {(const void *)K<C, ##__VA_ARGS__, false>, (const void *)K<C, ##__VA_ARGS__, true>}
-#define WGRT_K4(K, C, ...) {WGRT_K2(K, C, ##__VA_ARGS__, false), WGRT_K2(K, C, ##__VA_ARGS__, true)}
-#define WGRT_K8(K, C) {WGRT_K4(K, C, false), WGRT_K4(K, C, true)}
-const void *const kJonesKernels[2][2][2][2][2] = {
-    {WGRT_K8(trace_jones_kernel, uint32_t), WGRT_K8(trace_jones_kernel, uint64_t)},
-    {WGRT_K8(trace_jones_b_kernel, uint32_t), WGRT_K8(trace_jones_b_kernel, uint64_t)}};
-const void *const kLearnKernels[2][2] = {   // [byte locator][64-bit cells]
-    {(const void *)trace_jones_learn_kernel<uint32_t>, (const void *)trace_jones_learn_kernel<uint64_t>},
-    {(const void *)trace_jones_b_learn_kernel<uint32_t>, (const void *)trace_jones_b_learn_kernel<uint64_t>}};
-const void *const kChainKernels[2][2][2] = {   // [byte locator][64-bit cells][AMP]
-    {WGRT_K2(trace_jones_chain_kernel, uint32_t), WGRT_K2(trace_jones_chain_kernel, uint64_t)},
-    {WGRT_K2(trace_jones_b_chain_kernel, uint32_t), WGRT_K2(trace_jones_b_chain_kernel, uint64_t)}};
-const void *const kFateKernels[2][2][2][2] = {   // [byte locator][64-bit cells][single wavelength][AMP]
-    {WGRT_K4(trace_jones_fate_kernel, uint32_t), WGRT_K4(trace_jones_fate_kernel, uint64_t)},
-    {WGRT_K4(trace_jones_b_fate_kernel, uint32_t), WGRT_K4(trace_jones_b_fate_kernel, uint64_t)}};
-const void *const kRepsKernels[2][2][2][2] = {   // [byte locator][64-bit cells][single wavelength][AMP]
-    {WGRT_K4(trace_jones_reps_kernel, uint32_t), WGRT_K4(trace_jones_reps_kernel, uint64_t)},
-    {WGRT_K4(trace_jones_b_reps_kernel, uint32_t), WGRT_K4(trace_jones_b_reps_kernel, uint64_t)}};
-const void *const kEvKernels[2][2][2][2] = {   // [byte locator][64-bit cells][single wavelength][AMP]: wgrt_trace_expected
-    {WGRT_K4(trace_jones_ev_kernel, uint32_t), WGRT_K4(trace_jones_ev_kernel, uint64_t)},
-    {WGRT_K4(trace_jones_b_ev_kernel, uint32_t), WGRT_K4(trace_jones_b_ev_kernel, uint64_t)}};
-const void *const kFpKernels[2][2][2][2] = {   // [byte locator][64-bit cells][single wavelength][AMP]: wgrt_trace_footprint
-    {WGRT_K4(trace_jones_fp_kernel, uint32_t), WGRT_K4(trace_jones_fp_kernel, uint64_t)},
-    {WGRT_K4(trace_jones_b_fp_kernel, uint32_t), WGRT_K4(trace_jones_b_fp_kernel, uint64_t)}};
-const void *const kTimelineKernels[2][2] = {   // [byte locator][fused]
-    {(const void *)trace_jones_tl_kernel<uint32_t, false, false>, (const void *)trace_jones_tl_kernel<uint32_t, true, false>},
-    {(const void *)trace_jones_b_tl_kernel<uint32_t, false, false>,
-     (const void *)trace_jones_b_tl_kernel<uint32_t, true, false>}};
-#undef WGRT_K8
-#undef WGRT_K4
-#undef WGRT_K2
+// Every Jones kernel instantiation, stated once, by [mode][byte locator][64-bit cells][fused][single wavelength][AMP];
+// NULL: not built.  The occupancy queries loop over the table and the launch looks its kernel up in it, so a kernel
+// cannot be in one and not the other.
+struct JonesKernels {
+    const void *k[kTraceModes][2][2][2][2][2] = {};
+    template <bool BYTE, class CellT, TraceMode M, bool FUSED, bool SINGLE, bool AMP>
+    static const void *kernel_of() {
+        using Loc = std::conditional_t<BYTE, ByteLocatorT<CellT>, LocatorT<CellT>>;
+        if constexpr (M == TraceMode::kLearn) return (const void *)trace_jones_learn_kernel<Loc>;
+        else if constexpr (M != TraceMode::kPlain) return (const void *)trace_jones_mode_kernel<Loc, M, FUSED, SINGLE, AMP>;
+        else if constexpr (BYTE) return (const void *)trace_jones_b_kernel<CellT, FUSED, SINGLE, AMP>;
+        else return (const void *)trace_jones_kernel<CellT, FUSED, SINGLE, AMP>;
+    }
+    // one instantiation in both locator forms and (WIDE) both cell widths
+    template <TraceMode M, bool FUSED, bool SINGLE, bool AMP, bool WIDE = true>
+    void add() {
+        auto &e = k[(int)M];
+        e[0][0][FUSED][SINGLE][AMP] = kernel_of<false, uint32_t, M, FUSED, SINGLE, AMP>();
+        e[1][0][FUSED][SINGLE][AMP] = kernel_of<true, uint32_t, M, FUSED, SINGLE, AMP>();
+        if constexpr (WIDE) {
+            e[0][1][FUSED][SINGLE][AMP] = kernel_of<false, uint64_t, M, FUSED, SINGLE, AMP>();
+            e[1][1][FUSED][SINGLE][AMP] = kernel_of<true, uint64_t, M, FUSED, SINGLE, AMP>();
+        }
+    }
+    template <TraceMode M, bool FUSED, bool SINGLE>
+    void add_amp() {
+        add<M, FUSED, SINGLE, false>();
+        add<M, FUSED, SINGLE, true>();
+    }
+    template <TraceMode M, bool FUSED>
+    void add_single_amp() {
+        add_amp<M, FUSED, false>();
+        add_amp<M, FUSED, true>();
+    }
+    JonesKernels() {
+        add_single_amp<TraceMode::kPlain, false>();                    // every combination: 32
+        add_single_amp<TraceMode::kPlain, true>();
+        add<TraceMode::kTimeline, false, false, false, false>();       // 32-bit cells, full colour, no AMP: 4
+        add<TraceMode::kTimeline, true, false, false, false>();
+        add<TraceMode::kLearn, false, false, false>();                 // full colour, no AMP: 4
+        add_amp<TraceMode::kChain, false, false>();                    // full colour: 8
+        add_single_amp<TraceMode::kFate, false>();                     // the sinks: single launches, 16 each
+        add_single_amp<TraceMode::kReps, false>();
+        add_single_amp<TraceMode::kEv, false>();
+        add_single_amp<TraceMode::kFp, false>();
+    }
+};
+const void *jones_kernel(TraceMode m, bool byte, bool wide, bool fused, bool single, bool amp) {
+    static const JonesKernels table;
+    return table.k[(int)m][byte][wide][fused][single][amp];
+}
 
 }  // namespace
 
 namespace wgrt {
 
-// The resident grid of every trace kernel instantiation (wgrt_scene.h; scene creation calls it on the
-// scene's device): cell width x fused x single wavelength, the smaller of the plain and the AMP one.
+// The resident grid of every trace kernel instantiation (wgrt_scene.h; scene creation calls it on the scene's
+// device): per table entry but the AMP axis, the smaller of the plain and the AMP kernel's (of those that are built).
 wgrt_status query_trace_grids(wgrt_scene *s) {
     int cus = 0;
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device));
-    auto grid_of = [&](const void *k, int &out) -> hipError_t {
-        int per_cu = 0;
-        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 256, 0);
-        out = std::max(1, cus * std::max(1, per_cu));
-        return e;
-    };
-    // (each locator form from its own instantiations: a launch takes the grid of the kernel it runs)
-    for (int b = 0; b < 2; ++b) {
-        for (int c = 0; c < 2; ++c)
-            for (int f = 0; f < 2; ++f)
-                for (int g = 0; g < 2; ++g) {
-                    int plain = 0, amp = 0;
-                    HIP_TRY(grid_of(kJonesKernels[b][c][f][g][0], plain));
-                    HIP_TRY(grid_of(kJonesKernels[b][c][f][g][1], amp));
-                    s->jones_grid[b][c][f][g] = std::min(plain, amp);
-                }
-        // the fate instantiations: never more workgroups than the plain launch of the same kind gets
-        for (int c = 0; c < 2; ++c)
-            for (int g = 0; g < 2; ++g) {
-                int plain = 0, amp = 0;
-                HIP_TRY(grid_of(kFateKernels[b][c][g][0], plain));
-                HIP_TRY(grid_of(kFateKernels[b][c][g][1], amp));
-                s->jones_fate_grid[b][c][g] = std::min(s->jones_grid[b][c][0][g], std::min(plain, amp));
-                // ... and the replica instantiations, by the same rule
-                HIP_TRY(grid_of(kRepsKernels[b][c][g][0], plain));
-                HIP_TRY(grid_of(kRepsKernels[b][c][g][1], amp));
-                s->jones_reps_grid[b][c][g] = std::min(s->jones_grid[b][c][0][g], std::min(plain, amp));
-                // ... and the expected-value instantiations
-                HIP_TRY(grid_of(kEvKernels[b][c][g][0], plain));
-                HIP_TRY(grid_of(kEvKernels[b][c][g][1], amp));
-                s->jones_ev_grid[b][c][g] = std::min(s->jones_grid[b][c][0][g], std::min(plain, amp));
-                // ... and the footprint instantiations
-                HIP_TRY(grid_of(kFpKernels[b][c][g][0], plain));
-                HIP_TRY(grid_of(kFpKernels[b][c][g][1], amp));
-                s->jones_fp_grid[b][c][g] = std::min(s->jones_grid[b][c][0][g], std::min(plain, amp));
-            }
-        for (int f = 0; f < 2; ++f) HIP_TRY(grid_of(kTimelineKernels[b][f], s->jones_tl_grid[b][f]));
-        for (int c = 0; c < 2; ++c) HIP_TRY(grid_of(kLearnKernels[b][c], s->jones_learn_grid[b][c]));
-    }
+    // (each locator form from its own instantiations: a launch takes the grid of the kernel it runs; the modes in
+    // the enum's order, kPlain first)
+    for (int m = 0; m < kTraceModes; ++m)
+        for (int b = 0; b < 2; ++b)
+            for (int c = 0; c < 2; ++c)
+                for (int f = 0; f < 2; ++f)
+                    for (int g = 0; g < 2; ++g) {
+                        int grid = 0;   // (stays 0 where nothing is built: no launch reads it, dispatch refuses first)
+                        for (int a = 0; a < 2; ++a) {
+                            const void *const k = jones_kernel((TraceMode)m, b, c, f, g, a);
+                            if (!k) continue;
+                            int per_cu = 0;
+                            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 256, 0));
+                            const int resident = std::max(1, cus * std::max(1, per_cu));
+                            grid = grid ? std::min(grid, resident) : resident;
+                        }
+                        // the sinks: never more workgroups than the plain launch of the same kind gets
+                        const TraceMode mode = (TraceMode)m;
+                        if (grid && (mode == TraceMode::kFate || mode == TraceMode::kReps || mode == TraceMode::kEv ||
+                                     mode == TraceMode::kFp))
+                            grid = std::min(grid, s->jones_grid[(int)TraceMode::kPlain][b][c][f][g]);
+                        s->jones_grid[m][b][c][f][g] = grid;
+                    }
     // A chained step's waves spin on rays that only the previous step's launch can finish, so that launch must
     // always be able to get workgroups resident while this one is.  Two steps are in flight at a time (stream order
     // on each side), so a chained grid is at most half of what the chip holds, less kChainMargin workgroups (one per
@@ -1523,7 +1421,8 @@ wgrt_status query_trace_grids(wgrt_scene *s) {
             int per_cu = 0;
             for (int a = 0; a < 2; ++a) {
                 int k = 0;
-                HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&k, kChainKernels[b][c][a], 256, 0));
+                HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                    &k, jones_kernel(TraceMode::kChain, b, c, false, false, a), 256, 0));
                 per_cu = a == 0 ? k : std::min(per_cu, k);
             }
             s->jones_chain_grid[b][c] =
@@ -1661,9 +1560,11 @@ struct LaunchCfg {
     int64_t gid_block_rays = 0;
     const wgrt_debug_opts *dbg = nullptr;
     double grid_k = 0.0;   // wgrt_launch_opts.grid_sqrt_k (0: kGridSqrtK; < 0: the resident grid)
-    bool timeline = false; // set by validate_launch: the debug wave timeline is asked for
-    bool learn = false;    // set by plan_auto_order: this launch runs the learning instantiation ...
-    bool auto_order = false;   // ... and / or is issued in the automatic order, built from the tile table as
+    // The instantiation the launch runs (wgrt_trace_mode.h).  An entry point asks for kEv here (wgrt_trace_expected:
+    // the one mode that no payload field below implies); validate_launch then settles it (launch_mode), and
+    // plan_auto_order may turn a kPlain launch into a kLearn one.
+    TraceMode mode = TraceMode::kPlain;
+    bool auto_order = false;   // the launch is issued in the automatic order, built from the tile table as
     uint32_t order_gen = 0;    // it stood after this many learning launches
     // a gathering chain's lone launch (chain_flush): the stream's automatic order if it is built for this batch, the
     // natural order otherwise -- order_kernel costs as much as the launch, which a chain's rare lone launches never repay
@@ -1684,9 +1585,8 @@ struct LaunchCfg {
     int replicas = 0;
     int64_t rep_stride = 0;
     // wgrt_trace_expected: the launch scores every out-coupler visit into win_table (wgrt_expected.h) instead of
-    // counting out-couplings; `replicas` as above (0: the one table).  It follows the replica launch's rules, has no
-    // grid (a float32 cell cannot hold the fixed-point sums) and never stores fates.
-    bool expected = false;
+    // counting out-couplings (mode kEv); `replicas` as above (0: the one table).  It follows the replica launch's
+    // rules, has no grid (a float32 cell cannot hold the fixed-point sums) and never stores fates.
     // wgrt_trace_footprint: the map every counted draw adds to and its plan (NULL: none).  A footprint launch follows
     // the fate launch's rules -- a single launch, no learning, no debug timeline, never a chained step -- and is not
     // combined with fates, replicas or the expected-value estimator.
@@ -1695,6 +1595,22 @@ struct LaunchCfg {
     // set by validate_launch: the launch runs the byte-locator instantiation (byte_locator_applies)
     bool byte = false;
 };
+
+// The mode of a launch, the one place that orders them: a chained step, the debug timeline, then the sinks -- the
+// expected-value estimator before the replicas, because such a launch may fill replica tables too -- and only then
+// a learning launch.  (validate_launch refuses the other combinations; a chained step has no sink.)  What asks for
+// a mode: c.mode itself for kChain (chain_step), kEv (wgrt_trace_expected) and kLearn (plan_auto_order), the debug
+// options for the timeline, the sink's payload for the rest.
+TraceMode launch_mode(const LaunchCfg &c, bool timeline) {
+    return c.mode == TraceMode::kChain   ? TraceMode::kChain
+           : timeline                    ? TraceMode::kTimeline
+           : c.fate                      ? TraceMode::kFate
+           : c.mode == TraceMode::kEv    ? TraceMode::kEv
+           : c.fp_map                    ? TraceMode::kFp
+           : c.replicas                  ? TraceMode::kReps
+           : c.mode == TraceMode::kLearn ? TraceMode::kLearn
+                                         : TraceMode::kPlain;
+}
 
 // wgrt_debug_set_byte_locator: the byte locator on / off, process-wide (the same-binary A/B; default on).  A
 // launch runs the byte form when the switch is on and its scene has a byte grid (at most kPaletteMax distinct cell
@@ -1745,7 +1661,7 @@ bool still_learning(const wgrt_scene *ms) {   // (under scratch_mu)
 // Would a plain launch of this configuration learn now?  Such a step of a chain runs as one: the table has one
 // writer at a time, and no chained instantiation learns.
 bool would_learn(wgrt_scene *ms, const LaunchCfg &c) {
-    if (!auto_order_applies(ms, c) || c.timeline) return false;
+    if (!auto_order_applies(ms, c) || c.mode == TraceMode::kTimeline) return false;
     std::lock_guard<std::mutex> lk(ms->scratch_mu);
     return still_learning(ms);
 }
@@ -1753,7 +1669,7 @@ bool would_learn(wgrt_scene *ms, const LaunchCfg &c) {
 void plan_auto_order(wgrt_scene *ms, int64_t n_rays, int item, LaunchCfg &c) {
     if (!auto_order_applies(ms, c)) return;
     std::lock_guard<std::mutex> lk(ms->scratch_mu);
-    const bool learning = !c.chain_serial && still_learning(ms);
+    const bool learning = c.mode != TraceMode::kChain && still_learning(ms);
     // While the scene still learns (a batch of few rays per tile: a shard), the order is rebuilt after 1, 2,
     // 4, ... learning launches only, not after each: order_kernel is one workgroup (0.24 ms for C3's 21,168
     // chunks), about a launch's time at every size.
@@ -1761,8 +1677,8 @@ void plan_auto_order(wgrt_scene *ms, int64_t n_rays, int item, LaunchCfg &c) {
     if (learning)
         while (c.order_gen & (c.order_gen - 1)) c.order_gen &= c.order_gen - 1;
     c.auto_order = ms->learn_gen > 0 && item == kChunk;
-    if (!c.timeline && learning && !c.fate && !c.replicas && !c.expected && !c.fp_map) {   // (a fate, replica, expected-value or footprint launch does not learn: LaunchCfg)
-        c.learn = true;
+    if (learning && c.mode == TraceMode::kPlain) {   // (a timeline launch or a sink does not learn: LaunchCfg)
+        c.mode = TraceMode::kLearn;
         ms->learned_rays += n_rays;
         ++ms->learn_gen;
     }
@@ -1800,13 +1716,14 @@ constexpr double kGridSqrtK = 6.5;
 
 // Step 1 of a launch: every argument check, in the order the entry points have always made them (the
 // caller has checked s, rays, n_rays and gid_offset, which selecting the scene's device needs).  Resolves
-// c.variant (0 = auto), clamps c.num_iter and sets c.timeline.  n_rays == 0 is valid and ends the checks
+// c.variant (0 = auto), clamps c.num_iter and sets c.mode.  n_rays == 0 is valid and ends the checks
 // where it always has: the caller returns at once.
 wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
                             const uint32_t *rng_states, const float *matrix_EB, const uint32_t *per_ray_bounces,
                             LaunchCfg &c) {
     const bool single = c.single;
     const wgrt_debug_opts *dbg = c.dbg;
+    const bool expected = c.mode == TraceMode::kEv;
     if (single && s->nl != 1)
         return fail(WGRT_ERR_INVALID_ARGUMENT, "single-wavelength trace needs a scene built with num_lmd == 1");
     if (c.variant != 0 && c.variant != 1 && c.variant != 7 && c.variant != 9)
@@ -1823,10 +1740,10 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
                                                "launches (trace the iterations one call each)");
     if (c.fate && c.replicas)
         return fail(WGRT_ERR_INVALID_ARGUMENT, "a launch stores fates or fills replica tables, not both");
-    if (c.expected && c.num_iter > 1)
+    if (expected && c.num_iter > 1)
         return fail(WGRT_ERR_INVALID_ARGUMENT, "num_iter > 1 takes no expected-value estimator: its tables are filled by "
                                                "single launches (trace the iterations one call each)");
-    if (c.expected && (c.fate || matrix_EB || !c.win_table))
+    if (expected && (c.fate || matrix_EB || !c.win_table))
         return fail(WGRT_ERR_INVALID_ARGUMENT, "the expected-value estimator fills a window table: no grid, no fates");
     if (c.fp_map) {
         if (const char *why = footprint_plan_error(&c.fp)) return fail(WGRT_ERR_INVALID_ARGUMENT, why);
@@ -1834,7 +1751,7 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
         if (c.num_iter > 1)
             return fail(WGRT_ERR_INVALID_ARGUMENT, "num_iter > 1 takes no footprint map: the maps are filled by single "
                                                    "launches (trace the iterations one call each)");
-        if (c.fate || c.replicas || c.expected)
+        if (c.fate || c.replicas || expected)
             return fail(WGRT_ERR_INVALID_ARGUMENT, "a footprint launch takes no fates, replicas or expected-value estimator");
     }
     if (c.chunk_order && c.variant == 1)
@@ -1853,29 +1770,30 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
         return fail(WGRT_ERR_UNSUPPORTED, "variants 7 / 9 index at most 2^32 - 1 rays per launch");
     if (c.variant == 0) c.variant = n_rays > 0xffffffffll ? 1 : (s->d_cells32 ? 7 : 9);   // auto
     c.byte = byte_locator_applies(s, c.variant);
-    c.timeline = dbg && dbg->timeline && dbg->timeline_waves > 0;
-    if (c.timeline && (c.variant != 7 || single))
+    const bool timeline = dbg && dbg->timeline && dbg->timeline_waves > 0;
+    if (timeline && (c.variant != 7 || single))
         return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline is built for the full-colour 32-bit-cell kernel only");
-    if (c.timeline && s->nonunitary_blocks)
+    if (timeline && s->nonunitary_blocks)
         return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline is built without the amplification step: scaled-unitary "
                                           "LUTs only");
-    if (c.timeline && c.fate)
+    if (timeline && c.fate)
         return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel stores no fates: trace with fate or with the timeline");
-    if (c.timeline && c.replicas)
+    if (timeline && c.replicas)
         return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel fills no replica tables: trace with replicas or with "
                                           "the timeline");
-    if (c.timeline && c.expected)
+    if (timeline && expected)
         return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel scores no visits: trace with the expected-value "
                                           "estimator or with the timeline");
-    if (c.timeline && c.fp_map)
+    if (timeline && c.fp_map)
         return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel counts no footprints: trace with a footprint map or "
                                           "with the timeline");
-    if ((c.replicas || c.expected) && c.variant != 1 && (int64_t)s->nl * s->nx * s->ny >= (int64_t)1 << kRepShift)
+    if ((c.replicas || expected) && c.variant != 1 && (int64_t)s->nl * s->nx * s->ny >= (int64_t)1 << kRepShift)
         return fail(WGRT_ERR_UNSUPPORTED, "replica tables with variants 7 / 9 need a scene of fewer than 2^24 tiles (the "
                                           "out-coupling queue entry carries the replica above the tile index)");
     // (a chained variant-1 call, num_iter > 1, has no chunk_order: rejected above)
     if (c.chunk_order && c.n_chunk_order != (n_rays + kChunk - 1) / kChunk)
         return fail(WGRT_ERR_INVALID_ARGUMENT, "chunk_order must list ceil(n_rays / 64) chunks");
+    c.mode = launch_mode(c, timeline);
     return WGRT_OK;
 }
 
@@ -1906,8 +1824,8 @@ TraceArgs fill_args(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, 
     if (dbg && dbg->cert_tol > 0.0) A.cert_tol = dbg->cert_tol;
     if (dbg && dbg->cert_tol32 > 0.0) A.cert_tol32 = dbg->cert_tol32;
     A.cert_tol32 = std::max(A.cert_tol32, A.cert_tol);   // raising the double bound raises this one too
-    A.timeline = c.timeline ? dbg->timeline : nullptr;
-    A.timeline_waves = c.timeline ? dbg->timeline_waves : 0;
+    A.timeline = c.mode == TraceMode::kTimeline ? dbg->timeline : nullptr;
+    A.timeline_waves = c.mode == TraceMode::kTimeline ? dbg->timeline_waves : 0;
     A.n_iter = 1;
     A.fused_run = 1;
     return A;
@@ -1917,14 +1835,7 @@ TraceArgs fill_args(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, 
 // grid, fewer for a single trace (grid_sqrt_k), never more than have work; c.workgroups overrides.
 int64_t launch_grid(const wgrt_scene *s, int64_t n_rays, int64_t item, const LaunchCfg &c) {
     int64_t grid = c.workgroups > 0 ? c.workgroups
-                   : c.chain_serial ? s->jones_chain_grid[c.byte][c.variant == 9]
-                   : c.timeline     ? s->jones_tl_grid[c.byte][c.num_iter > 1]
-                   : c.fate         ? s->jones_fate_grid[c.byte][c.variant == 9][c.single]
-                   : c.expected     ? s->jones_ev_grid[c.byte][c.variant == 9][c.single]
-                   : c.fp_map       ? s->jones_fp_grid[c.byte][c.variant == 9][c.single]
-                   : c.replicas     ? s->jones_reps_grid[c.byte][c.variant == 9][c.single]
-                   : c.learn        ? s->jones_learn_grid[c.byte][c.variant == 9]
-                                    : s->jones_grid[c.byte][c.variant == 9][c.num_iter > 1][c.single];
+                                    : s->jones_grid[(int)c.mode][c.byte][c.variant == 9][c.num_iter > 1][c.single];
     // a workgroup's 4 waves need 4 work items to all have work (debug chunk_rays: smaller items)
     const int64_t useful = (n_rays + 4 * item - 1) / (4 * item);
     if (c.workgroups <= 0 && c.num_iter <= 1 && c.grid_k >= 0.0) {
@@ -1939,8 +1850,9 @@ int64_t launch_grid(const wgrt_scene *s, int64_t n_rays, int64_t item, const Lau
         const int64_t want = std::max<int64_t>(1, (int64_t)std::ceil(K * std::sqrt((double)items)));
         if (grid > want) grid = want;
     }
-    // (a chained step never fills the chip, whoever chose its grid: query_trace_grids)
-    if (c.chain_serial) grid = std::min<int64_t>(grid, s->jones_chain_grid[c.byte][c.variant == 9]);
+    // (a chained step never fills the chip, whoever chose its grid: query_trace_grids; never more than its
+    // kernel's resident grid, above)
+    if (c.mode == TraceMode::kChain) grid = std::min<int64_t>(grid, s->jones_chain_grid[c.byte][c.variant == 9]);
     return std::min(grid, useful);
 }
 
@@ -1955,13 +1867,21 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
     if (c.variant == 1) {
         const int64_t blocks = (A.n_rays + 255) / 256;
         if (blocks > 0x7fffffff) return fail(WGRT_ERR_INVALID_ARGUMENT, "too many rays for one launch");
-        if (c.expected) hipLaunchKernelGGL(trace_grid_ev_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
-        else if (c.fp_map) hipLaunchKernelGGL(trace_grid_fp_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
-        else if (c.fate) hipLaunchKernelGGL(trace_grid_fate_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
-        else hipLaunchKernelGGL(trace_grid_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
+        switch (c.mode) {   // (the exact lane reads a replica launch's TraceArgs::win_reps itself: the plain kernel)
+        case TraceMode::kEv: hipLaunchKernelGGL(trace_grid_ev_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A); break;
+        case TraceMode::kFp: hipLaunchKernelGGL(trace_grid_fp_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A); break;
+        case TraceMode::kFate: hipLaunchKernelGGL(trace_grid_fate_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A); break;
+        default: hipLaunchKernelGGL(trace_grid_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
+        }
         HIP_TRY(hipGetLastError());
         return WGRT_OK;
     }
+    // the table's kernel; the amplification step only for scenes that need it (wgrt_jones_lane.h, "Amplification")
+    const bool amp = s->nonunitary_blocks != 0, wide = c.variant == 9;
+    const void *const kernel = jones_kernel(c.mode, c.byte, wide, num_iter > 1, c.single, amp);
+    if (!kernel)   // (a planning bug: validate_launch and plan_auto_order route every launch to a built kernel)
+        return fail(WGRT_ERR_UNSUPPORTED, "no trace kernel is built for mode " + std::to_string((int)c.mode) +
+                                              " with this cell width / fused / single-wavelength / AMP combination");
     wgrt_scene *ms = const_cast<wgrt_scene *>(s);
     wgrt_scene::Scratch *sc = nullptr;
     uint32_t epoch = 0, parity = 0;
@@ -1980,7 +1900,7 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
         // a debug bound (fault-injection tests) gives up on the clock alone
         A.handoff_min_passes = (dbg && dbg->handoff_wait_ticks) ? 0u : kHandoffMinPasses;
     }
-    if (c.chain_serial) {   // the fused hand-off's operands, across the kernel boundary (jones_body, CHAIN)
+    if (c.mode == TraceMode::kChain) {   // the fused hand-off's operands, across the kernel boundary (jones_body)
         A.rng64 = c.chain_gran;
         A.iter_epoch = c.chain_serial;
         A.handoff_wait_ticks = (dbg && dbg->handoff_wait_ticks) ? dbg->handoff_wait_ticks : kHandoffTicksPerIter * 2ull;
@@ -2004,8 +1924,7 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
     }
     // chunk_order is given in 64-ray chunks; a staged chunk is one ray per lane
     int jchunk = A.order ? kChunk : item;
-    // the timeline kernels and variant 7 read 32-bit cell words; the amplification step only for scenes that
-    // need it (wgrt_jones_lane.h, "Amplification")
+    // the timeline kernels and variant 7 read 32-bit cell words
     // ... and the byte locator where the launch runs it (LaunchCfg::byte): the same view with the byte grid and the
     // palette of the kernel's word width
     LocatorT<uint32_t> l32{};
@@ -2014,15 +1933,6 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
     if (c.variant != 9) l32 = make_locator32(s);
     if (c.byte && c.variant != 9) b32 = make_byte_locator(s, A.loc, s->d_palette32);
     if (c.byte && c.variant == 9) b64 = make_byte_locator(s, A.loc, s->d_palette);
-    const bool amp = s->nonunitary_blocks != 0, wide = c.variant == 9;
-    const void *const kernel = c.chain_serial ? kChainKernels[c.byte][wide][amp]
-                               : c.timeline ? kTimelineKernels[c.byte][num_iter > 1]
-                               : c.fate   ? kFateKernels[c.byte][wide][c.single][amp]
-                               : c.expected ? kEvKernels[c.byte][wide][c.single][amp]
-                               : c.fp_map ? kFpKernels[c.byte][wide][c.single][amp]
-                               : c.replicas ? kRepsKernels[c.byte][wide][c.single][amp]
-                               : c.learn  ? kLearnKernels[c.byte][wide]
-                                          : kJonesKernels[c.byte][wide][num_iter > 1][c.single][amp];
     uint32_t *tail = ms->d_tile_tail;   // the learning kernels' last parameter (the others take four)
     void *const locp = c.byte ? (wide ? (void *)&b64 : (void *)&b32) : (wide ? (void *)&A.loc : (void *)&l32);
     void *args[] = {&A, locp, &ctr, &jchunk, &tail};
@@ -2218,8 +2128,8 @@ wgrt_status chain_prepare(wgrt_chain *ch) {
         // the largest grid a step of this chain can be launched on: chained, plain, or plain and learning
         const int item = (ch->cfg.dbg && ch->cfg.dbg->chunk_rays > 0) ? std::min(ch->cfg.dbg->chunk_rays, 64) : kChunk;
         LaunchCfg chained = ch->cfg, learning = ch->cfg;
-        chained.chain_serial = 1;
-        learning.learn = true;
+        chained.mode = TraceMode::kChain;
+        learning.mode = TraceMode::kLearn;
         int64_t grid = 1;
         for (const LaunchCfg *k : {&ch->cfg, &chained, &learning})
             grid = std::max(grid, launch_grid(ms, ch->n_rays, item, *k));
@@ -2374,6 +2284,7 @@ wgrt_status chain_step(wgrt_chain *ch) {
             LaunchCfg c = ch->cfg;
             c.chain_gran = sc->chain_gran;
             c.chain_serial = p.publish_serial;
+            c.mode = TraceMode::kChain;
             e = trace_launch(ms, &ch->rays, ch->n_rays, ch->gid_offset, ch->rng, ch->eb, ch->stats, nullptr,
                              p.side ? (void *)sc->chain_side : ch->stream, c);
         }
@@ -2395,7 +2306,8 @@ wgrt_status wgrt_scene_reserve(const wgrt_scene *s, int64_t n_rays, int num_iter
     for (int b = 0; b < 2; ++b)
         for (int c = 0; c < 2; ++c)
             for (int f = 0; f < 2; ++f)
-                for (int g = 0; g < 2; ++g) grid = std::max<int64_t>(grid, s->jones_grid[b][c][f][g]);
+                for (int g = 0; g < 2; ++g)
+                    grid = std::max<int64_t>(grid, s->jones_grid[(int)TraceMode::kPlain][b][c][f][g]);
     wgrt_scene::Scratch *sc = nullptr;
     return ensure_scratch(const_cast<wgrt_scene *>(s), stream, n_rays, std::max(num_iter, 1),
                           std::min<int64_t>(grid, (n_rays + 255) / 256), &sc);
@@ -2468,7 +2380,7 @@ wgrt_status wgrt_trace_expected(const wgrt_scene *s, const wgrt_rays *rays, int6
     LaunchCfg c;
     const wgrt_status e = cfg_of_opts(s, opts, plan, table, c);
     if (e != WGRT_OK) return e;
-    c.expected = true;
+    c.mode = TraceMode::kEv;
     c.replicas = replicas >= 2 ? replicas : 0;
     c.rep_stride = (int64_t)s->nl * s->ny * s->nx * plan->host.W;
     return trace_launch(s, rays, n_rays, gid_offset, rng_states, nullptr, stats, per_ray_bounces, stream, c);
@@ -2528,13 +2440,15 @@ wgrt_status wgrt_chain_begin(const wgrt_scene *s, const wgrt_rays *rays, int64_t
         ch->cfg.dbg = &ch->dbg;
     }
     ch->flags = (c.variant == 1 ? WGRT_CHAIN_VARIANT1 : 0u) | (c.single ? WGRT_CHAIN_SINGLE : 0u) |
-                (c.num_iter > 1 ? WGRT_CHAIN_FUSED : 0u) | ((c.chunk_order || c.timeline) ? WGRT_CHAIN_DEBUG : 0u);
+                (c.num_iter > 1 ? WGRT_CHAIN_FUSED : 0u) |
+                ((c.chunk_order || c.mode == TraceMode::kTimeline) ? WGRT_CHAIN_DEBUG : 0u);
     // A launch whose own grid is the kernel's resident grid fills the chip alone: two of them in flight crowd each
     // other's drain and gain nothing (C4: +6.6 % per step chained), so such a batch stays serial.
     // Chained are the batches the sqrt(items) grid rule (or the caller) gives fewer workgroups.
     if (!ch->flags && n_rays) {
         const int item = (c.dbg && c.dbg->chunk_rays > 0) ? std::min(c.dbg->chunk_rays, 64) : kChunk;
-        if (launch_grid(s, n_rays, item, c) >= s->jones_grid[c.byte][c.variant == 9][0][0]) ch->flags |= WGRT_CHAIN_FULL;
+        if (launch_grid(s, n_rays, item, c) >= s->jones_grid[(int)TraceMode::kPlain][c.byte][c.variant == 9][0][0])
+            ch->flags |= WGRT_CHAIN_FULL;
     }
     e = n_rays ? chain_prepare(ch) : WGRT_OK;
     if (e != WGRT_OK) {
@@ -2575,7 +2489,7 @@ wgrt_status wgrt_chain_gather(wgrt_chain *ch, int max_steps, int hold) {
     for (;; cap /= 2) {
         LaunchCfg fused = ch->cfg, learning = ch->cfg;
         fused.num_iter = cap;
-        learning.learn = true;
+        learning.mode = TraceMode::kLearn;
         int64_t grid = 1;
         for (const LaunchCfg *k : {&ch->cfg, &fused, &learning})
             grid = std::max(grid, launch_grid(ms, ch->n_rays, item, *k));

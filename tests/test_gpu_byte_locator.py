@@ -182,3 +182,37 @@ def test_amp_and_single_wavelength(dev, key, variant):
         off, _ = _run(c, dev, shape, variant, False)
         assert info["active"]
         _assert_same(on, off)
+
+
+@pytest.mark.parametrize("num_iter", [1, 3])
+@pytest.mark.parametrize("byte", [True, False])
+def test_timeline_kernels_in_both_forms(dev, byte, num_iter):
+    """The debug wave timeline's kernels (``wgrt_debug_opts.timeline``: variant 7, full colour, single and fused),
+    which gather bytes or words like the product's: 130 rays -- two whole 64-ray chunks and a partial one, on one
+    workgroup -- leave what variant 1 leaves, and every wave wrote its record."""
+    c = _case("c1_rgb")
+    N = 130
+    scene = engine.Scene.from_geometry(c.geom, c.luts)
+    assert scene.palette_info()["byte_grid"]
+    rays = engine.rays_to_device(c.rays, dev)
+    tl = torch.zeros((4, 8), dtype=torch.int64, device=dev)   # 8 words per wave: start, dry, end, passes, ...
+    out = {}
+    for variant in (7, 1):
+        rng = torch.from_numpy(c.fresh_rng().view(np.int32)).to(dev)
+        eb = torch.zeros(c.eb_shape(), dtype=torch.float32, device=dev)
+        stats = engine.new_stats(dev)
+        _lib.set_byte_locator(byte)
+        engine.trace_fullcolor(scene, rays, rng, eb, n_rays=N, stats=stats, variant=variant, num_iter=num_iter,
+                               debug=dict(timeline=tl.view(-1)) if variant == 7 else None)
+        torch.cuda.synchronize()
+        _lib.set_byte_locator(True)
+        out[variant] = {k: v.cpu().numpy().copy() for k, v in dict(rng=rng, eb=eb, stats=stats).items()}
+    scene.close()
+    for k in ("rng", "eb"):
+        assert out[7][k].tobytes() == out[1][k].tobytes(), k
+    for k in (STAT.bounces, STAT.eyebox_hits, STAT.bad_rays):
+        assert int(out[7]["stats"][k]) == int(out[1]["stats"][k]), k
+    assert int(out[7]["stats"][STAT.bounces]) > 0 and int(out[7]["stats"][STAT.handoff_giveups]) == 0
+    t = tl.cpu().numpy()
+    assert (t[:, 0] > 0).all() and (t[:, 2] >= t[:, 0]).all()   # every wave of the workgroup: start and end times
+    assert t[:, 3].sum() > 0 and t[:, 4].sum() >= N              # passes, and lane-passes with a ray in flight

@@ -157,7 +157,8 @@ def pmc(a) -> dict:
             print(r.stdout[-2000:], r.stderr[-4000:], file=sys.stderr)
             raise SystemExit(r.returncode)
         line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-        want = "trace_jones" if form == "plain" else "fp_kernel"
+        # (the footprint kernels: trace_jones_mode_kernel<..., (wgrt::TraceMode)7, ...>, TraceMode::kFp)
+        want = "trace_jones" if form == "plain" else "TraceMode)7"
         per = {}
         for f in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):
             for row in csv.DictReader(open(f)):
