@@ -140,6 +140,18 @@ struct TraceArgs {
     wgrt_footprint_plan fp;
     int32_t fp_aggregate;
     int32_t fp_pad_;
+    // the hit list (wgrt_trace_hits; wgrt_hits.h): with hits, every out-coupling of the launch reserves an index with a
+    // returning add on *hits_count and, where the index is below hits_cap, stores its record at hits[index], tagged
+    // hits_tag.  Only the HITS instantiations read them: the exact lane appends at interact's out-coupling
+    // (trace_grid_hits_kernel, the kHits replay), the Jones-vector lane where it bins its queue, and its push also
+    // stores the entry's local ray index in q_ray (beside q_i; allocated by a hits launch's scratch growth only).
+    // Single launches only.  Last again.
+    wgrt_hit *hits;
+    int64_t hits_cap;
+    unsigned long long *hits_count;
+    uint32_t *q_ray;
+    uint32_t hits_tag;
+    uint32_t hits_pad_;
 };
 
 // The replica of global ray id g >= 0 among reps (2 .. 64) copies: g % reps from 32-bit remainders (the 64-bit

@@ -23,12 +23,16 @@
 // it, and reads the draw's second channel (lost / out-coupled inside / beside the eyebox) from the fate code that
 // interact<FATE> leaves in the lane -- so interact itself has no FP of its own.  Its `skip` draws are passed over
 // (counted by the Jones lane before it abandoned the ray).  The walk is FP = false's.
+// HITS (a template parameter of interact and trace_one; off by default): the hit list of wgrt_trace_hits
+// (wgrt_hits.h).  interact's out-coupling appends one record for both outcomes of the rectangle test (hit_store).  A
+// template parameter and not a test of TraceArgs::hits, so that every other kernel is the code it was.
 #pragma once
 
 #include "wgrt_args.h"
 #include "wgrt_expected.h"
 #include "wgrt_fate.h"
 #include "wgrt_footprint.h"
+#include "wgrt_hits.h"
 #include "wgrt_locator.h"
 #include "wgrt_window.h"
 
@@ -184,6 +188,20 @@ __device__ __forceinline__ bool eyebox_add(const TraceArgs &A, const double *T, 
     return eyebox_inside(T, x, y) && eyebox_bin(A, T, l, m, n, x, y, rep);
 }
 
+// One record of the hit list (wgrt_trace_hits; wgrt_hits.h) at its reserved index: stored iff the index is below
+// the capacity, as two 16-byte stores (position; global id, tile index, flags), so nothing at or beyond hits + cap is
+// written.  Both lanes append through it.
+__device__ __forceinline__ void hit_store(wgrt_hit *hits, int64_t cap, unsigned long long idx, double x, double y,
+                                          int64_t gid, uint32_t tile, uint32_t flags) {
+    static_assert(offsetof(wgrt_hit, gid) == 16 && offsetof(wgrt_hit, tile) == 24 && offsetof(wgrt_hit, flags) == 28,
+                  "the second half: gid, then tile below flags in one 64-bit word");
+    if (idx < (unsigned long long)cap) {
+        double2 *const p = (double2 *)(hits + idx);
+        p[0] = double2{x, y};
+        ((ulonglong2 *)p)[1] = ulonglong2{(unsigned long long)gid, (unsigned long long)tile | (unsigned long long)flags << 32};
+    }
+}
+
 // Take branch b (0 or 1) of block B in state `kind` (GRTF:872-882 and every branch body after it): cte / ctm are
 // the branch's exact magnitudes (correctly rounded hypot of E_field_cal's components), dphi its wrapped phase
 // difference (GRTF:145-150) and e its exact efficiency.  Returns the next region, or kDie for a ray that the
@@ -220,7 +238,7 @@ __device__ __forceinline__ int take_branch(const Loc &loc, Lane &L, const double
 // or kDie (FATE: with the lane's fate set; its region is the state the ray is in, 9 at the entry).
 // Only the chosen branch's phase (two atan2) is evaluated; its field is recomputed
 // by the same operations rather than kept in registers for every branch.
-template <bool FATE = false, bool EV = false, class Loc>
+template <bool FATE = false, bool EV = false, bool HITS = false, class Loc>
 __device__ __forceinline__ int interact(const TraceArgs &A, const Loc &loc, Lane &L, int blk, int kind,
                                         bool entry, uint32_t *ev_skip = nullptr) {
     Ray &r = L.r;
@@ -346,7 +364,16 @@ __device__ __forceinline__ int interact(const TraceArgs &A, const Loc &loc, Lane
     if (b == 2) {  // out-coupling (GRTF:1162-1171, 1231-1240)
         // (the replica is the global id's, as the RNG fix-up's id above)
         const auto rep = [&]() { return replica_of(ray_gid(A, L.i), (uint32_t)A.win_reps); };
-        if (FATE) {
+        if (HITS) {
+            // a hits launch (wgrt_trace_hits; the HITS instantiations only, so that every other kernel is the code it
+            // was): the record for both outcomes of the rectangle test, its index reserved by this thread's own
+            // returning add (the path is rare)
+            const bool in = eyebox_inside(T, r.x, r.y);
+            hit_store(A.hits, A.hits_cap, atomicAdd(A.hits_count, 1ull), r.x, r.y, ray_gid(A, L.i),
+                      (uint32_t)((L.l * A.nx + L.m) * A.ny + L.n), hit_flags(in, A.hits_tag));
+            if (in && eyebox_bin(A, T, L.l, L.m, L.n, r.x, r.y, rep)) L.hit = true;
+            if (FATE) L.why = fate_code(freg, in ? kFateEyebox : kFateBeside);
+        } else if (FATE) {
             const bool in = eyebox_inside(T, r.x, r.y);
             if (in && eyebox_bin(A, T, L.l, L.m, L.n, r.x, r.y, rep)) L.hit = true;
             L.why = fate_code(freg, in ? kFateEyebox : kFateBeside);
@@ -489,7 +516,8 @@ __device__ __forceinline__ void footprint_count(const TraceArgs &A, int l, int r
 // (rng_states untouched).
 // EV: with the expected-value deposits (above); skip: the scored visits to pass over.
 // FP: with the footprint counts (above); skip: the counted draws to pass over.
-template <bool FATE = false, bool EV = false, bool FP = false>
+// HITS: with the hit list's appends (interact<.., HITS>).
+template <bool FATE = false, bool EV = false, bool FP = false, bool HITS = false>
 __device__ __forceinline__ void trace_one(const TraceArgs &A, int64_t i, Counters &c, uint32_t *s_io = nullptr,
                                           uint32_t skip = 0) {
     static_assert(!(EV && FP), "a launch scores visits or counts footprints: skip belongs to one of them");
@@ -506,7 +534,7 @@ __device__ __forceinline__ void trace_one(const TraceArgs &A, int64_t i, Counter
         // FP: where and in which state the ray stands at this draw
         const double fx = L.r.x, fy = L.r.y;
         const int freg = L.r.region;
-        const int next = interact<FATE || FP, EV>(A, A.loc, L, blk, kind, entry, &skip);
+        const int next = interact<FATE || FP, EV, HITS>(A, A.loc, L, blk, kind, entry, &skip);
         if (FP && !entry) {
             if (skip) --skip;   // counted by the lane that abandoned the ray
             else footprint_count(A, L.l, freg, next < 0 ? L.why % 10 : 0, fx, fy);

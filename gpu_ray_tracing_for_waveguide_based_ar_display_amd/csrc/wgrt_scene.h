@@ -66,6 +66,8 @@ struct wgrt_scene {
         double2 *q_xy = nullptr;             // out-coupling queue: position, ray index
         uint32_t *q_i = nullptr;
         int64_t qcap = 0;
+        uint32_t *q_ray = nullptr;           // a hits launch's third queue column, the entry's local ray index: grown
+        int64_t qcap_ray = 0;                // by hits launches only (wgrt_trace_hits)
         unsigned long long *part = nullptr;  // per-wave counter partials (kPartWords words per slot)
         int64_t part_slots = 0;
         uint64_t *rng64 = nullptr;           // fused launches: per-ray {state, tag} granules

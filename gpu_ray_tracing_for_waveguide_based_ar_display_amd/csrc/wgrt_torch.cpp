@@ -123,6 +123,13 @@ decltype(&wgrt_trace_footprint) footprint_abi() {
     return fn;
 }
 
+// wgrt_trace_hits (the hit list), new within ABI 9 too: looked up at the first trace_hits call.
+decltype(&wgrt_trace_hits) hits_abi() {
+    static const auto fn = reinterpret_cast<decltype(&wgrt_trace_hits)>(dlsym(RTLD_DEFAULT, "wgrt_trace_hits"));
+    TORCH_CHECK(fn, "wgrt.trace_hits: the loaded libwgrt.so has no wgrt_trace_hits (a build from before the hit list)");
+    return fn;
+}
+
 // All three launching operators: trace (the grid alone: plan 0, no table), trace_windows (the grid, the window
 // table of plan `plan` -- a wgrt_window_plan handle -- or both) and, with `chain`, chain_begin: the same checks and
 // records handed to wgrt_chain_begin, which launches nothing and leaves the chain's handle in *chain.
@@ -134,7 +141,9 @@ int64_t trace_core(int64_t scene, const Tensor &x, const Tensor &y, const Tensor
                    int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
                    double grid_sqrt_k, int64_t plan, std::optional<Tensor> table, wgrt_chain **chain,
                    std::optional<Tensor> fate = std::nullopt, int64_t replicas = 0, bool expected = false,
-                   const wgrt_footprint_plan *fp = nullptr, std::optional<Tensor> fp_map = std::nullopt) {
+                   const wgrt_footprint_plan *fp = nullptr, std::optional<Tensor> fp_map = std::nullopt,
+                   std::optional<Tensor> hits = std::nullopt, int64_t hit_capacity = 0,
+                   std::optional<Tensor> hit_count = std::nullopt, int64_t hit_tag = 0) {
     const wgrt_scene *s = reinterpret_cast<const wgrt_scene *>(static_cast<uintptr_t>(scene));
     TORCH_CHECK(s != nullptr, "wgrt.trace: NULL scene");
     wgrt_scene_info info{};
@@ -227,6 +236,26 @@ int64_t trace_core(int64_t scene, const Tensor &x, const Tensor &y, const Tensor
     if (chain) {
         TORCH_CHECK(!per, "wgrt.chain_begin: a chain takes no per_ray_bounces");
         return chain_abi().begin(s, &r, n_rays, gid_offset, rng, eb, stp, hip_stream, &o, tab ? wp : nullptr, tab, chain);
+    }
+    if (hits) {   // trace_hits: the record buffer (uint8, 32 bytes per record), its capacity, the counter and the tag
+        TORCH_CHECK(!fp_map && !fate && replicas == 0 && !expected,
+                    "wgrt.trace_hits: takes no fate, replicas, expected or footprint map");
+        on_device(*hits, "hits", c);
+        TORCH_CHECK(hits->scalar_type() == at::kByte && hits->is_contiguous(), "wgrt.trace_hits: hits must be contiguous uint8");
+        // (a negative capacity is the library's to refuse; a positive one must lie inside the buffer)
+        TORCH_CHECK(hit_capacity <= 0 || hit_capacity <= hits->numel() / (int64_t)sizeof(wgrt_hit),
+                    "wgrt.trace_hits: capacity ", hit_capacity, " exceeds the buffer's ", hits->numel() / (int64_t)sizeof(wgrt_hit),
+                    " records");
+        uint64_t *cnt = nullptr;
+        if (hit_count) {
+            on_device(*hit_count, "count", c);
+            TORCH_CHECK(hit_count->scalar_type() == at::kLong && hit_count->numel() == 1, "wgrt.trace_hits: count must be int64[1]");
+            cnt = static_cast<uint64_t *>(hit_count->data_ptr());
+        }
+        // (out of uint32 range: a tag the library refuses)
+        const uint32_t tag = hit_tag < 0 || hit_tag > 0xffffffffll ? 0xffffffffu : static_cast<uint32_t>(hit_tag);
+        return hits_abi()(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o, tab ? wp : nullptr, tab,
+                          static_cast<wgrt_hit *>(hits->data_ptr()), hit_capacity, cnt, tag);
     }
     if (fp_map) {   // trace_footprint: int64 [num_lmd, 9, ny_cells, nx_cells], added to by every counted draw
         TORCH_CHECK(fp && !fate && replicas == 0 && !expected, "wgrt.trace_footprint: takes no fate, replicas or expected");
@@ -339,6 +368,22 @@ int64_t trace_footprint(int64_t scene, const Tensor &x, const Tensor &y, const T
                       gid_block_rays, debug, grid_sqrt_k, plan, table, nullptr, std::nullopt, 0, false, &fp, map);
 }
 
+// trace_hits: trace_windows' arguments, the record buffer, its capacity in records, the counter and the tag
+// (wgrt_trace_hits).
+int64_t trace_hits(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
+                   const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
+                   Tensor rng_states, std::optional<Tensor> matrix_EB, std::optional<Tensor> stats,
+                   std::optional<Tensor> per_ray_bounces, int64_t n_rays, int64_t gid_offset, int64_t stream,
+                   int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
+                   int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
+                   double grid_sqrt_k, int64_t plan, std::optional<Tensor> table, Tensor hits, int64_t capacity,
+                   std::optional<Tensor> count, int64_t tag) {
+    return trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats, per_ray_bounces,
+                      n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
+                      gid_block_rays, debug, grid_sqrt_k, plan, table, nullptr, std::nullopt, 0, false, nullptr,
+                      std::nullopt, hits, capacity, count, tag);
+}
+
 // chain_begin: trace_windows' arguments -> the chain's handle (a user-space address: positive), or the negated
 // wgrt_status of a failure (wgrt_last_error has the detail).  The
 // Python layer keeps every tensor alive until chain_end (engine.TraceChain).
@@ -427,6 +472,14 @@ TORCH_LIBRARY(wgrt, m) {
           "float grid_sqrt_k, int plan, Tensor(e!)? table, float fp_x0, float fp_y0, float fp_cell_x, float fp_cell_y, "
           "int fp_nx_cells, int fp_ny_cells, Tensor(f!) map) -> int",
           &trace_footprint);
+    // the same launch appending one record per out-coupling to a hit list (wgrt_trace_hits): hits uint8, 32 bytes
+    // per record, capacity in records; count int64[1], added to
+    m.def("trace_hits(int scene, Tensor x, Tensor y, Tensor m, Tensor n, Tensor? lmd_num, Tensor te, Tensor tm, "
+          "Tensor delta_phase, Tensor(a!) rng_states, Tensor(b!)? matrix_EB, Tensor(c!)? stats, "
+          "Tensor(d!)? per_ray_bounces, int n_rays, int gid_offset, int stream, int kernel, int variant, "
+          "int workgroups, Tensor? chunk_order, int num_iter, Tensor? gid_blocks, int gid_block_rays, int debug, "
+          "float grid_sqrt_k, int plan, Tensor(e!)? table, Tensor(f!) hits, int capacity, Tensor(g!)? count, int tag) -> int",
+          &trace_hits);
     m.def("chain_step(int chain) -> int", &chain_step);
     m.def("chain_end(int chain) -> int", &chain_end);
 }

@@ -78,6 +78,14 @@ __global__ __launch_bounds__(256) void trace_grid_fp_kernel(TraceArgs A) {
     add_stats(A.stats, c);
 }
 
+// The same appending every out-coupling to the hit list (wgrt_trace_hits with variant 1; wgrt_hits.h).
+__global__ __launch_bounds__(256) void trace_grid_hits_kernel(TraceArgs A) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    Counters c;
+    if (i < A.n_rays) trace_one<false, false, false, true>(A, i, c);
+    add_stats(A.stats, c);
+}
+
 // A counter set of the Jones-vector variants' launch scratch, each slot on its own 128-B line: the kHeads
 // work-queue heads, then the replay count, the out-coupling queue and full-block counts, and a single
 // launch's epilogue totals (a Counters record) and done count.
@@ -331,7 +339,7 @@ __device__ __forceinline__ void replay_tail(const KArgs &K, unsigned long long n
             uint32_t skip = 0;   // what the Jones lane counted before it abandoned the ray (record_abandoned)
             if constexpr (kSeenCounted<M>)
                 skip = __hip_atomic_load(seen_counts<M>(K) + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            trace_one<M == TraceMode::kFate, M == TraceMode::kEv, M == TraceMode::kFp>(
+            trace_one<M == TraceMode::kFate, M == TraceMode::kEv, M == TraceMode::kFp, M == TraceMode::kHits>(
                 R, (int64_t)__hip_atomic_load(list + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), c, nullptr, skip);
         }
     }
@@ -433,6 +441,11 @@ static_assert(sizeof(TraceArgs) % 8 == 0 && sizeof(Locator) % 8 == 0 && sizeof(L
 // the hit count comes from there.  The lane counts its scored visits (ev_seen) for the replay of an abandoned ray
 // (record_abandoned_ev).  The replica is worked out at the push from TraceArgs::win_reps (0: the one table).  Off
 // everywhere else, where none of this exists.
+// HITS: a single launch that keeps every out-coupling as a record of the caller's hit list (wgrt_trace_hits;
+// wgrt_hits.h): the out-coupling push also stores the ray's index in the queue's third column (TraceArgs::q_ray), and
+// the wave appends one record per queue entry where it bins its blocks, after the wave loop (bin_hits).  An abandoned
+// ray has pushed nothing: its replay on the exact lane appends its record.  Off everywhere else, where the entry is
+// stored and decoded as it always was.
 // Loc: the locator's form, a template axis of every instantiation: LocatorT<CellT> gathers cell words,
 // ByteLocatorT<CellT> a scene's byte grid (wgrt_args.h; the workgroup copies the palette into LDS first).
 constexpr int kEvBlock = 64;   // scored visits a wave holds before it bins them: a pass adds at most one per lane
@@ -497,9 +510,9 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
     // the mode under the names the body tests (at most one of them is set)
     constexpr bool TL = M == TraceMode::kTimeline, LEARN = M == TraceMode::kLearn, CHAIN = M == TraceMode::kChain,
                    FATE = M == TraceMode::kFate, REPS = M == TraceMode::kReps, EV = M == TraceMode::kEv,
-                   FP = M == TraceMode::kFp;
+                   FP = M == TraceMode::kFp, HITS = M == TraceMode::kHits;
     static_assert(!FUSED || M == TraceMode::kPlain || TL, "only plain and timeline launches are built fused");
-    static_assert(!(FATE || REPS || EV || FP) || WGRT_INKERNEL_REPLAY,
+    static_assert(!(FATE || REPS || EV || FP || HITS) || WGRT_INKERNEL_REPLAY,
                   "the sink modes are single launches whose replay runs in the kernel (replay_tail<M>)");
     // Single launches (!FUSED) do their epilogue in this kernel (above), and retire a finished trace at one
     // place per pass, right after advance(): the rays that ended in the previous pass's interaction (fin)
@@ -744,6 +757,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
                 KA(q_xy)[j] = double2{L.r.x, L.r.y};
                 if (REPS) KA(q_i)[j] = L.tix | replica_of(ray_gid_ka(K, (int64_t)L.i), (uint32_t)KA(win_reps)) << kRepShift;
                 else KA(q_i)[j] = L.tix;
+                if constexpr (HITS) KA(q_ray)[j] = L.i;   // the record's global id is worked out where it is appended
             }
             if (nblk) {
                 const uint32_t b0 = (uint32_t)(nb / kQBlock), old = (uint32_t)(qbase / kQBlock);
@@ -1148,6 +1162,32 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
         const int ny = KA(ny), nx = KA(nx);
         tot_h += bin_entry<REPS>(A, g, nx, ny, px, py) ? 1u : 0u;
     };
+    // HITS: a block of cnt entries (wave-uniform; one lane per entry, lanes 0 .. cnt - 1) binned as above and appended
+    // to the hit list: the rectangle test is made once and shared by the bin and the record's flag, lane 0 reserves
+    // the block's indices with one returning add on the list's counter, and each lane whose index is below the
+    // capacity stores its record (hit_store).  Called by every lane of the wave.
+    auto bin_hits = [&](unsigned long long base, int cnt) {
+        const bool has = lane < cnt;
+        unsigned long long first = 0;
+        if (lane == 0) first = atomicAdd(KA(hits_count), (unsigned long long)cnt);
+        first = uni64(__shfl(first, 0));
+        if (has) {
+            const unsigned long long j = base + lane;
+            const uint32_t g = __hip_atomic_load(KA(q_i) + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint32_t ri = __hip_atomic_load(KA(q_ray) + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const double *pq = (const double *)(KA(q_xy) + j);
+            const double px = __hip_atomic_load(pq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const double py = __hip_atomic_load(pq + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int ny = KA(ny), nx = KA(nx);
+            const int n = (int)(g % (uint32_t)ny), m = (int)(g / (uint32_t)ny % (uint32_t)nx);
+            const int l = (int)(g / ((uint32_t)ny * (uint32_t)nx));
+            const double *T = A.tiles + (int64_t)((l * A.nx + m) * A.ny + n) * A.tile_d;
+            const bool in = eyebox_inside(T, px, py);
+            tot_h += in && eyebox_bin(A, T, l, m, n, px, py, []() { return 0u; }) ? 1u : 0u;
+            hit_store(KA(hits), KA(hits_cap), first + (unsigned long long)lane, px, py, ray_gid_ka(K, (int64_t)ri), g,
+                      hit_flags(in, KA(hits_tag)));
+        }
+    };
     if (EV) {
         ev_flush();
         tot_h = ev_hits;
@@ -1155,13 +1195,15 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
     if constexpr (FP) fp_flush(fpc, A.fp_map);   // (empty with the switch off)
     if (qblk) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane < qfill) bin(qbase + lane);
+        if constexpr (HITS) bin_hits(qbase, qfill);
+        else if (lane < qfill) bin(qbase + lane);
         if (!FUSED) {   // ... and, with the in-kernel epilogue, every block it filled before, along the links
             uint32_t prev = __builtin_amdgcn_readfirstlane(
                 __hip_atomic_load(KA(full_list) + qbase / kQBlock, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
             while (prev != 0u) {
                 const uint32_t b = prev - 1u;
-                if (lane < kQBlock) bin((unsigned long long)b * kQBlock + lane);
+                if constexpr (HITS) bin_hits((unsigned long long)b * kQBlock, kQBlock);
+                else if (lane < kQBlock) bin((unsigned long long)b * kQBlock + lane);
                 prev = __builtin_amdgcn_readfirstlane(
                     __hip_atomic_load(KA(full_list) + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
             }
@@ -1366,6 +1408,7 @@ struct JonesKernels {
         add_single_amp<TraceMode::kReps, false>();
         add_single_amp<TraceMode::kEv, false>();
         add_single_amp<TraceMode::kFp, false>();
+        add_single_amp<TraceMode::kHits, false>();
     }
 };
 const void *jones_kernel(TraceMode m, bool byte, bool wide, bool fused, bool single, bool amp) {
@@ -1401,7 +1444,7 @@ wgrt_status query_trace_grids(wgrt_scene *s) {
                         // the sinks: never more workgroups than the plain launch of the same kind gets
                         const TraceMode mode = (TraceMode)m;
                         if (grid && (mode == TraceMode::kFate || mode == TraceMode::kReps || mode == TraceMode::kEv ||
-                                     mode == TraceMode::kFp))
+                                     mode == TraceMode::kFp || mode == TraceMode::kHits))
                             grid = std::min(grid, s->jones_grid[(int)TraceMode::kPlain][b][c][f][g]);
                         s->jones_grid[m][b][c][f][g] = grid;
                     }
@@ -1432,7 +1475,7 @@ wgrt_status query_trace_grids(wgrt_scene *s) {
 }
 
 void free_scratch(wgrt_scene::Scratch &sc) {
-    for (void *p : {(void *)sc.ctr, (void *)sc.list, (void *)sc.q_xy, (void *)sc.q_i, (void *)sc.full, (void *)sc.rng64,
+    for (void *p : {(void *)sc.ctr, (void *)sc.list, (void *)sc.q_xy, (void *)sc.q_i, (void *)sc.q_ray, (void *)sc.full, (void *)sc.rng64,
                     (void *)sc.part, (void *)sc.order, (void *)sc.chain_gran})
         (void)hipFree(p);
     if (sc.chain_ev_begin) (void)hipEventDestroy(sc.chain_ev_begin);
@@ -1454,7 +1497,8 @@ namespace {
 // call zeroes both sets before it uses either.  For a fused launch (epoch != NULL) the launch
 // epoch of the granule tags is advanced here, under the same lock, and returned.
 wgrt_status ensure_scratch(wgrt_scene *ms, void *stream, int64_t n_rays, int num_iter, int64_t grid,
-                           wgrt_scene::Scratch **out, uint32_t *epoch = nullptr, uint32_t *parity = nullptr) {
+                           wgrt_scene::Scratch **out, uint32_t *epoch = nullptr, uint32_t *parity = nullptr,
+                           bool hits = false) {
     hipStream_t st = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(ms->scratch_mu);
     wgrt_scene::Scratch *sc = &ms->scratch[stream];
@@ -1514,6 +1558,11 @@ wgrt_status ensure_scratch(wgrt_scene *ms, void *stream, int64_t n_rays, int num
         return h;
     });
     if (e != WGRT_OK) return e;
+    if (hits) {   // a hits launch's third queue column (the entry's ray); no other launch allocates it
+        e = grow(sc->qcap_ray, sc->qcap, {(void **)&sc->q_ray},
+                 [&] { return hipMalloc((void **)&sc->q_ray, (size_t)sc->qcap * sizeof(uint32_t)); });
+        if (e != WGRT_OK) return e;
+    }
     // the automatic issue order's three arrays (order, the sort's other buffer, class keys); new ones hold no order
     const int64_t chunks = (n_rays + kChunk - 1) / kChunk;
     e = grow(sc->order_cap, chunks, {(void **)&sc->order}, [&] {
@@ -1592,6 +1641,13 @@ struct LaunchCfg {
     // combined with fates, replicas or the expected-value estimator.
     int64_t *fp_map = nullptr;
     wgrt_footprint_plan fp{};
+    // wgrt_trace_hits: the list every out-coupling is appended to, its capacity, its device counter and the call's tag
+    // (NULL: none).  A hits launch follows the fate launch's rules too, and is not combined with fates, replicas, the
+    // expected-value estimator or footprints.
+    wgrt_hit *hits = nullptr;
+    int64_t hits_cap = 0;
+    unsigned long long *hits_count = nullptr;
+    uint32_t hits_tag = 0;
     // set by validate_launch: the launch runs the byte-locator instantiation (byte_locator_applies)
     bool byte = false;
 };
@@ -1607,6 +1663,7 @@ TraceMode launch_mode(const LaunchCfg &c, bool timeline) {
            : c.fate                      ? TraceMode::kFate
            : c.mode == TraceMode::kEv    ? TraceMode::kEv
            : c.fp_map                    ? TraceMode::kFp
+           : c.hits                      ? TraceMode::kHits
            : c.replicas                  ? TraceMode::kReps
            : c.mode == TraceMode::kLearn ? TraceMode::kLearn
                                          : TraceMode::kPlain;
@@ -1754,6 +1811,19 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
         if (c.fate || c.replicas || expected)
             return fail(WGRT_ERR_INVALID_ARGUMENT, "a footprint launch takes no fates, replicas or expected-value estimator");
     }
+    if (c.hits) {
+        if (!c.hits_count) return fail(WGRT_ERR_INVALID_ARGUMENT, "a hit list needs its device counter");
+        if (c.hits_cap < 0) return fail(WGRT_ERR_INVALID_ARGUMENT, "the hit list's capacity must be >= 0");
+        if (c.hits_tag > kHitMaxTag) return fail(WGRT_ERR_INVALID_ARGUMENT, "the hit list's tag must be <= 65535");
+        if (((uintptr_t)c.hits & 15) || ((uintptr_t)c.hits_count & 7))
+            return fail(WGRT_ERR_INVALID_ARGUMENT, "the hit list must be 16-B aligned (and its counter 8-B)");
+        if (c.num_iter > 1)
+            return fail(WGRT_ERR_INVALID_ARGUMENT, "num_iter > 1 takes no hit list: the lists are filled by single "
+                                                   "launches (trace the iterations one call each)");
+        if (c.fate || c.replicas || expected || c.fp_map)
+            return fail(WGRT_ERR_INVALID_ARGUMENT, "a hits launch takes no fates, replicas, expected-value estimator or "
+                                                   "footprint map");
+    }
     if (c.chunk_order && c.variant == 1)
         return fail(WGRT_ERR_INVALID_ARGUMENT, "chunk_order needs variant 0, 7 or 9");
     if (c.gid_blocks && (c.gid_block_rays < 1 || gid_offset != 0))
@@ -1787,6 +1857,9 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
     if (timeline && c.fp_map)
         return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel counts no footprints: trace with a footprint map or "
                                           "with the timeline");
+    if (timeline && c.hits)
+        return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel keeps no hit list: trace with a hit list or with the "
+                                          "timeline");
     if ((c.replicas || expected) && c.variant != 1 && (int64_t)s->nl * s->nx * s->ny >= (int64_t)1 << kRepShift)
         return fail(WGRT_ERR_UNSUPPORTED, "replica tables with variants 7 / 9 need a scene of fewer than 2^24 tiles (the "
                                           "out-coupling queue entry carries the replica above the tile index)");
@@ -1817,6 +1890,10 @@ TraceArgs fill_args(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, 
     A.fp_map = c.fp_map;
     A.fp = c.fp;
     A.fp_aggregate = g_fp_aggregate.load(std::memory_order_relaxed);
+    A.hits = c.hits;
+    A.hits_cap = c.hits_cap;
+    A.hits_count = c.hits_count;
+    A.hits_tag = c.hits_tag;
     A.n_rays = n_rays;
     A.gid_offset = gid_offset;
     A.gid_blocks = c.gid_blocks;
@@ -1871,6 +1948,7 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
         case TraceMode::kEv: hipLaunchKernelGGL(trace_grid_ev_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A); break;
         case TraceMode::kFp: hipLaunchKernelGGL(trace_grid_fp_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A); break;
         case TraceMode::kFate: hipLaunchKernelGGL(trace_grid_fate_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A); break;
+        case TraceMode::kHits: hipLaunchKernelGGL(trace_grid_hits_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A); break;
         default: hipLaunchKernelGGL(trace_grid_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
         }
         HIP_TRY(hipGetLastError());
@@ -1887,7 +1965,8 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
     uint32_t epoch = 0, parity = 0;
     {
         const wgrt_status e =
-            ensure_scratch(ms, stream, A.n_rays, num_iter, grid, &sc, num_iter > 1 ? &epoch : nullptr, &parity);
+            ensure_scratch(ms, stream, A.n_rays, num_iter, grid, &sc, num_iter > 1 ? &epoch : nullptr, &parity,
+                           c.mode == TraceMode::kHits);
         if (e != WGRT_OK) return e;
     }
     if (num_iter > 1) {
@@ -1912,6 +1991,7 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
     A.fp_seen = sc->list + sc->cap;
     A.q_xy = sc->q_xy;
     A.q_i = sc->q_i;
+    A.q_ray = sc->q_ray;
     A.full_list = sc->full;
     A.part = sc->part;
     A.n_trace_waves = (int)grid;   // one partial slot per trace workgroup
@@ -2405,6 +2485,25 @@ wgrt_status wgrt_trace_footprint(const wgrt_scene *s, const wgrt_rays *rays, int
     c.fp = *fp;
     return trace_launch(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, c);
 }
+
+wgrt_status wgrt_trace_hits(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
+                            uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats, uint32_t *per_ray_bounces,
+                            void *stream, const wgrt_launch_opts *opts, const wgrt_window_plan *plan, double *table,
+                            wgrt_hit *hits, int64_t capacity, uint64_t *count, uint32_t tag) {
+    if (!hits)   // no list: exactly that call
+        return wgrt_trace_windows(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, opts,
+                                  plan, table);
+    LaunchCfg c;
+    const wgrt_status e = cfg_of_opts(s, opts, plan, table, c);
+    if (e != WGRT_OK) return e;
+    c.hits = hits;
+    c.hits_cap = capacity;
+    c.hits_count = (unsigned long long *)count;
+    c.hits_tag = tag;
+    return trace_launch(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, c);
+}
+
+int32_t wgrt_hit_bytes(void) { return (int32_t)sizeof(wgrt_hit); }
 
 wgrt_status wgrt_debug_set_footprint_aggregate(int on) {
     g_fp_aggregate.store(on != 0, std::memory_order_relaxed);

@@ -15,6 +15,7 @@ enum class TraceMode : int {
     kReps,       // fills replica window tables (wgrt_trace_replicas)
     kEv,         // the expected-value estimator (wgrt_trace_expected)
     kFp,         // counts every draw into the footprint maps (wgrt_trace_footprint)
+    kHits,       // appends one record per out-coupling to the hit list (wgrt_trace_hits)
     kCount
 };
 constexpr int kTraceModes = (int)TraceMode::kCount;

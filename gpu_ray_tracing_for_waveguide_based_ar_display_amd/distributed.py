@@ -487,7 +487,7 @@ def timed_run(trace_fn, rays, rng, eb, gid: GidMap, steps: int, per_call: int, s
 
 
 def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, replicas: int = 0,
-               expected: bool = False, footprint=None):
+               expected: bool = False, footprint=None, hits=None):
     """trace_fn for ``run_steps`` / ``trace_job`` using the HIP kernel (torch device tensors); ``stats``
     (int64[STATS_LEN] device tensor) is added to by every call.  A shard of several block ranges passes its global
     ids as ``gid_blocks``, uploaded once per map and device and kept on the map (``GidMap.device_blocks``).
@@ -515,8 +515,14 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, rep
 
     ``footprint``: ``(fp, map)``, an ``engine.FootprintPlan`` and its int64 map: every call also counts its draws into
     the plate map (``engine.trace_fullcolor(footprint=...)``): single launches only and no ``chain`` again.  The
-    counts are integers, so the ranks' maps add: ``reduce_eyebox(map)``."""
+    counts are integers, so the ranks' maps add: ``reduce_eyebox(map)``.
+
+    ``hits``: an ``engine.HitList``: every call also appends its out-couplings to the list
+    (``engine.trace_fullcolor(hits=...)``), tagged with the number of calls made before it (the iteration, for the
+    single launches this takes): single launches only and no ``chain`` again.  The records' ids are global, so the
+    ranks' lists concatenate."""
     from .engine import TraceChain, trace_fullcolor
+    calls = [0]
 
     def ids_of(rng, gid: GidMap):
         off = gid.offset
@@ -525,7 +531,9 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, rep
 
     def fn(rays, rng, eb, gid: GidMap, num_iter=1):
         trace_fullcolor(scene, rays, rng, eb, stats=stats, variant=variant, num_iter=num_iter, windows=windows,
-                        fate=fate, replicas=replicas, expected=expected, footprint=footprint, **ids_of(rng, gid))
+                        fate=fate, replicas=replicas, expected=expected, footprint=footprint,
+                        hits=None if hits is None else (hits, calls[0]), **ids_of(rng, gid))
+        calls[0] += 1
 
     def chain(rays, rng, eb, gid: GidMap):
         """The same launches as a chain (``run_steps`` uses it for separate launches without a hook)."""
@@ -533,7 +541,7 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, rep
         from ._lib import load
         return TraceChain(scene, rays, rng, eb, stats=stats, variant=variant, windows=windows,
                           gather=hasattr(load(), "wgrt_chain_gather"), **ids_of(rng, gid))
-    if fate is None and int(replicas or 0) < 2 and not expected and footprint is None:
+    if fate is None and int(replicas or 0) < 2 and not expected and footprint is None and hits is None:
         fn.chain = chain
     return fn
 

@@ -54,7 +54,7 @@ def trace_fullcolor(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_E
                     workgroups: int = 0, chunk_order: torch.Tensor | None = None, num_iter: int = 1,
                     gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
                     grid_sqrt_k: float = 0.0, windows=None, fate: torch.Tensor | None = None, replicas: int = 0,
-                    expected: bool = False, footprint=None) -> None:
+                    expected: bool = False, footprint=None, hits=None) -> None:
     """Asynchronous launch on ``stream`` (default: torch's current stream).
 
     rays: dict of device float32 tensors keyed like the reference columns
@@ -92,14 +92,17 @@ def trace_fullcolor(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_E
     the plate cell where the ray stood, in the channel of its state R0..R5, and the draw that loses the ray or
     out-couples it inside / beside its eyebox rectangle also in channel 6 / 7 / 8 (``FOOTPRINT_CHANNELS``); nothing
     else the launch leaves changes.  Single launches only; ``fate``, ``replicas``, ``expected``, ``num_iter > 1`` and a
-    ``TraceChain`` raise ``ValueError``.
+    ``TraceChain`` raise ``ValueError``.  hits: ``(hit_list, tag)``, a ``HitList`` on the scene's device and a tag
+    0 .. 65535 (``wgrt_trace_hits``): every out-coupling of the launch, inside its eyebox rectangle or beside it, is
+    appended to the list as one record tagged ``tag``; nothing else the launch leaves changes.  Single launches only;
+    ``fate``, ``replicas``, ``expected``, ``footprint``, ``num_iter > 1`` and a ``TraceChain`` raise ``ValueError``.
     """
     if scene.single_lambda:
         raise ValueError("trace_fullcolor needs a full-colour scene; use trace_single for a single-wavelength one")
     _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single=False, chunk_order=chunk_order, num_iter=num_iter, gid_blocks=gid_blocks,
            gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows, fate=fate,
-           replicas=replicas, expected=expected, footprint=footprint)
+           replicas=replicas, expected=expected, footprint=footprint, hits=hits)
 
 
 def new_stats(device) -> torch.Tensor:
@@ -143,18 +146,18 @@ def trace_single(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_EB: 
                  workgroups: int = 0, chunk_order: torch.Tensor | None = None, num_iter: int = 1,
                  gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
                  grid_sqrt_k: float = 0.0, windows=None, fate: torch.Tensor | None = None, replicas: int = 0,
-                 expected: bool = False, footprint=None) -> None:
+                 expected: bool = False, footprint=None, hits=None) -> None:
     """One launch of the single-wavelength kernel (``process_rays_kernel_pro``, GRTF:419-831)
     through ``wgrt_trace_single_ex``: no ``lmd_num`` column (ignored if present),
     matrix_EB [NY, NX, 80, 120], branch guard ener * efficiency > 1e-15.  The scene must be
     a single-wavelength one (``Scene.from_geometry(..., wavelength=l)`` or 3-D LUTs).  ``windows``, ``fate``,
-    ``replicas``, ``expected``, ``footprint``: as ``trace_fullcolor``."""
+    ``replicas``, ``expected``, ``footprint``, ``hits``: as ``trace_fullcolor``."""
     if not scene.single_lambda:
         raise ValueError("trace_single needs a single-wavelength scene (Scene.from_geometry(..., wavelength=l))")
     _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single=True, chunk_order=chunk_order, num_iter=num_iter, gid_blocks=gid_blocks,
            gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows, fate=fate,
-           replicas=replicas, expected=expected, footprint=footprint)
+           replicas=replicas, expected=expected, footprint=footprint, hits=hits)
 
 
 MAX_REPLICAS = 64   # WGRT_MAX_REPLICAS (include/wgrt.h)
@@ -284,6 +287,133 @@ def footprint_bin(fp: FootprintPlan, x, y, l, channel, num_lmd: int, out=None) -
     return out
 
 
+HIT_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("gid", "<i8"), ("tile", "<u4"), ("flags", "<u4")])   # wgrt_hit
+HIT_MAX_TAG = 65535
+
+
+class HitListOverflow(WgrtError):
+    """A hit list counted more out-couplings than it has room for (``check_hits``)."""
+
+
+def hit_inside(records) -> np.ndarray:
+    """Per record: inside its FoV's eyebox rectangle (flag bit 0; fate reason 3, else reason 4)."""
+    return (records["flags"] & 1).astype(bool)
+
+
+def hit_tag(records) -> np.ndarray:
+    """Per record: the tag of the call that appended it (flag bits 16..31)."""
+    return (records["flags"] >> 16).astype(np.int64)
+
+
+def hit_lmn(records, nx: int, ny: int):
+    """Per record: ``(l, m, n)`` of its tile index ``(l * nx + m) * ny + n``."""
+    t = records["tile"].astype(np.int64)
+    return t // (int(nx) * int(ny)), t // int(ny) % int(nx), t % int(ny)
+
+
+def sort_hits(records) -> np.ndarray:
+    """The records sorted by ``(tag, gid)``, which is unique per record."""
+    return records[np.lexsort((records["gid"], hit_tag(records)))]
+
+
+class HitList:
+    """A hit list (``wgrt_hit`` records; ``trace_*(hits=(hit_list, tag))``): the record buffer, a uint8
+    ``[capacity, 32]`` device tensor, and the device counter the launches add to.  ``count()`` is the number of
+    out-couplings so far (stored or not), ``stored()`` is ``min(count, capacity)``; both synchronise.  ``records()``
+    is the stored records as a numpy structured array (``HIT_DTYPE``: ``x, y, gid, tile, flags``) sorted by
+    ``(tag, gid)``; ``hit_inside``, ``hit_tag`` and ``hit_lmn`` decode them.  ``grid(scene, H, W, ranges=None)`` bins
+    the stored records on the device into a float32 ``[num_lmd, ny, nx, H, W]`` grid (``wgrt_hits_grid``): over the
+    scene's eyebox ranges the records inside their rectangle, over ``ranges`` (``[nx, ny, 4]``: xmin, xmax, ymin, ymax
+    per FoV) those inside the caller's -- at ``(80, 120)`` over the scene's, ``matrix_EB`` of the same launches bit for
+    bit.  ``clear()`` zeroes the counter."""
+
+    def __init__(self, capacity: int, device=0):
+        self.capacity = int(capacity)
+        if self.capacity < 0:
+            raise ValueError("capacity must be >= 0")
+        if int(load().wgrt_hit_bytes()) != HIT_DTYPE.itemsize:
+            raise WgrtError("the library's wgrt_hit is not 32 bytes")
+        self.device = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
+        self.buffer = torch.zeros((self.capacity, HIT_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+        self.counter = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def clear(self) -> None:
+        self.counter.zero_()
+
+    def count(self) -> int:
+        return int(self.counter.cpu()[0])
+
+    def stored(self) -> int:
+        return min(self.count(), self.capacity)
+
+    def raw(self) -> np.ndarray:
+        """The stored records in the buffer's order."""
+        n = self.stored()
+        return self.buffer[:n].cpu().numpy().reshape(-1).view(HIT_DTYPE).copy()
+
+    def records(self) -> np.ndarray:
+        return sort_hits(self.raw())
+
+    def grid(self, scene: Scene, H: int, W: int, ranges=None, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        if torch.device("cuda", scene.device) != self.device:
+            raise ValueError(f"the hit list is on {self.device}, the scene on device {scene.device}")
+        H, W = int(H), int(W)
+        if not (1 <= H <= 4096 and 1 <= W <= 4096):
+            raise ValueError("H and W must be 1 .. 4096")
+        shape = tuple(scene.eb_shape()[:-2]) + (H, W)
+        if out is None:
+            out = torch.zeros(shape, dtype=torch.float32, device=self.device)
+        else:
+            _as_dev(out, torch.float32, "grid", self.device)
+            if tuple(out.shape) != shape:
+                raise ValueError(f"grid shape {tuple(out.shape)} != {shape}")
+        r = None
+        if ranges is not None:
+            r = torch.as_tensor(np.ascontiguousarray(ranges, dtype=np.float64)).to(self.device) \
+                if not isinstance(ranges, torch.Tensor) else ranges
+            _as_dev(r, torch.float64, "ranges", self.device, scene.nx * scene.ny * 4)
+        check(load().wgrt_hits_grid(scene.handle, self.buffer.data_ptr(), self.stored(), r.data_ptr() if r is not None else None,
+                                    H, W, out.data_ptr(), ctypes.c_void_p(_stream_handle(self.device, stream))),
+              "wgrt_hits_grid")
+        return out
+
+
+def check_hits(hit_list: HitList) -> None:
+    """Raise ``HitListOverflow`` if the list counted more out-couplings than it stores.  Synchronises."""
+    n = hit_list.count()
+    if n > hit_list.capacity:
+        raise HitListOverflow(f"the hit list counted {n} out-couplings but has room for {hit_list.capacity}: "
+                              f"a capacity of {n} would have sufficed")
+
+
+def hits_grid_host(records, nx: int, ny: int, num_lmd: int, scene_ranges, H: int, W: int, ranges=None,
+                   out=None) -> np.ndarray:
+    """``HitList.grid`` on the host (``wgrt_hits_grid_host``; numpy arrays, no GPU needed) through the same rule:
+    ``records`` a ``HIT_DTYPE`` array, ``scene_ranges`` the scene's ``eff_reg_FOV_range`` ``[nx, ny, 4]``.  Adds into
+    ``out`` (C-contiguous float32 ``[num_lmd, ny, nx, H, W]``) when given."""
+    rec = np.ascontiguousarray(records, dtype=HIT_DTYPE)
+    sr = np.ascontiguousarray(scene_ranges, dtype=np.float64)
+    if sr.size != int(nx) * int(ny) * 4:
+        raise ValueError("scene_ranges must be [nx, ny, 4]")
+    cr = None
+    if ranges is not None:
+        cr = np.ascontiguousarray(ranges, dtype=np.float64)
+        if cr.size != int(nx) * int(ny) * 4:
+            raise ValueError("ranges must be [nx, ny, 4]")
+    shape = (int(num_lmd), int(ny), int(nx), int(H), int(W))
+    if out is None:
+        if not all(1 <= v <= 4096 for v in shape[3:]):
+            raise ValueError("H and W must be 1 .. 4096")
+        out = np.zeros(shape, dtype=np.float32)
+    elif out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != shape:
+        raise ValueError(f"out must be a C-contiguous float32 array of shape {shape}")
+    # (records are 16-B aligned in the library's eyes: numpy allocations are)
+    check(load().wgrt_hits_grid_host(int(nx), int(ny), int(num_lmd), sr.ctypes.data, rec.ctypes.data, rec.shape[0],
+                                     cr.ctypes.data if cr is not None else None, int(H), int(W), out.ctypes.data),
+          "wgrt_hits_grid_host")
+    return out
+
+
 def _debug_opts(debug: dict | None):
     if not debug:
         return None
@@ -325,9 +455,22 @@ def _read_columns(rays, rng_states, n_rays, single, device):
 
 def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single, chunk_order=None, num_iter=1, gid_blocks=None, gid_block_rays=0, debug=None,
-           grid_sqrt_k=0.0, windows=None, chain=False, fate=None, replicas=0, expected=False, footprint=None):
+           grid_sqrt_k=0.0, windows=None, chain=False, fate=None, replicas=0, expected=False, footprint=None,
+           hits=None):
     device = torch.device("cuda", scene.device)
     B = _replica_count(replicas)
+    if hits is not None:   # (before anything is read or launched)
+        if fate is not None or B or expected or footprint is not None:
+            raise ValueError("hits= is not combined with fate, replicas, expected or footprint")
+        if int(num_iter) > 1:
+            raise ValueError("hits= needs num_iter == 1: the lists are filled by single launches")
+        if chain:
+            raise ValueError("a chain takes no hits launches")
+        hit_list, hit_tag = hits
+        if not isinstance(hit_list, HitList):
+            raise TypeError("hits=(HitList, tag)")
+        if hit_list.device != device:
+            raise ValueError(f"the hit list is on {hit_list.device}, expected {device}")
     if footprint is not None:   # (before anything is read or launched)
         if fate is not None or B or expected:
             raise ValueError("footprint= is not combined with fate, replicas or expected")
@@ -410,7 +553,11 @@ def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ra
         if h <= 0:   # the negated wgrt_status of the failure
             check(-h, "wgrt_chain_begin")
         return h, (args, dbg, windows)
-    if footprint is not None:   # torch.ops.wgrt.trace_footprint -> wgrt_trace_footprint
+    if hits is not None:   # torch.ops.wgrt.trace_hits -> wgrt_trace_hits
+        status = ops().trace_hits(*args, plan.handle.value if windows is not None else 0,
+                                  table if windows is not None else None, hit_list.buffer, hit_list.capacity,
+                                  hit_list.counter, int(hit_tag))
+    elif footprint is not None:   # torch.ops.wgrt.trace_footprint -> wgrt_trace_footprint
         status = ops().trace_footprint(*args, plan.handle.value if windows is not None else 0,
                                        table if windows is not None else None, fp.x0, fp.y0, fp.cell_x, fp.cell_y,
                                        fp.nx_cells, fp.ny_cells, fp_map)
@@ -460,9 +607,11 @@ class TraceChain:
                  variant: int = VARIANT_AUTO, workgroups: int = 0, chunk_order: torch.Tensor | None = None,
                  gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
                  grid_sqrt_k: float = 0.0, windows=None, replicas: int = 0, expected: bool = False,
-                 gather: bool | int = False, hold: bool = False, footprint=None):
+                 gather: bool | int = False, hold: bool = False, footprint=None, hits=None):
         if scene.single_lambda:
             raise ValueError("TraceChain needs a full-colour scene")
+        if hits is not None:
+            raise ValueError("a chain takes no hits launches: fill a hit list with single launches")
         if footprint is not None:
             raise ValueError("a chain takes no footprint launches: trace footprint maps with single launches")
         if expected:
@@ -835,6 +984,6 @@ def expected_weight(e1: float, e2: float, e3: float, en1: float, en2: float, en3
     return float(load().wgrt_expected_weight_host(e1, e2, e3, en1, en2, en3, threshold))
 
 
-__all__ = ["Scene", "WindowPlan", "FootprintPlan", "footprint_bin", "FOOTPRINT_CHANNELS", "TraceChain", "fold_replicas", "expected_weight", "MAX_REPLICAS", "fate_census", "fate_census_host", "fate_col", "loss_budget", "FATE_CLASSES", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
+__all__ = ["Scene", "WindowPlan", "FootprintPlan", "footprint_bin", "FOOTPRINT_CHANNELS", "HitList", "HitListOverflow", "check_hits", "hits_grid_host", "sort_hits", "hit_inside", "hit_tag", "hit_lmn", "HIT_DTYPE", "TraceChain", "fold_replicas", "expected_weight", "MAX_REPLICAS", "fate_census", "fate_census_host", "fate_col", "loss_budget", "FATE_CLASSES", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
            "trace_fullcolor", "trace_single", "init_rays", "schedule_by_lifetime",
            "rays_to_device", "classify_points", "shadow", "selftest_math", "RAY_COLUMNS", "_lib"]

@@ -58,7 +58,7 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
         fuse: bool | None = None, points: np.ndarray | None = None, png: str | None = None,
         eyebox: str = "host", keep_grid: bool = False, evaluate_on: str = "host",
         keep_image: bool = False, budget: bool = False, error_bars: int = 0, estimator: str = "analog",
-        footprint=None) -> dict:
+        footprint=None, hits=None) -> dict:
     """The reference script's job on this engine; returns its printed quantities and arrays.
     ``points``: the R/2 in-coupler origins to use (default: sampled, GRTF:12-23, seeded by
     ``point_seed``); ``png``: where to write the "Eyebox Center View" image (needs ``evaluate``).
@@ -124,7 +124,28 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
     0.  Returned as ``footprint`` (the numpy map) and ``footprint_plan`` (the plan's fields) and printed per
     wavelength as totals.  Works with every ``eyebox`` mode; everything else returned is bit-identical to the run
     without it.  ``budget=True``, ``error_bars`` and ``estimator="expected"`` with it raise ``ValueError`` before any GPU
-    work."""
+    work.
+
+    ``hits``: ``True`` or a capacity in records (None / False: none): also keep every out-coupling -- inside its FoV's
+    eyebox rectangle or beside it -- as a record ``(x, y, gid, tile, flags)`` (``engine.HitList``,
+    ``engine.trace_fullcolor(hits=...)``).  The traces go as plain single launches, tagged with their iteration
+    number.  ``True`` sizes the list to ``ceil(0.125 * rays of the shard * num_iter)`` records, about twice the 6 % of
+    rays that the default LUT profile out-couples on the small jobs of the test suite; a list that is too small raises
+    ``engine.HitListOverflow`` after the trace, naming the capacity that would have sufficed.  Several GPUs send their
+    stored records to rank 0 (the counts all-gathered first, then the buffers padded to the largest); the ids are
+    global, so the sorted concatenation is the single-process list.  Returned as ``hits`` (the structured array, sorted
+    by tag and global id) and ``hit_count``, and printed per wavelength: out-couplings inside and beside the eyebox, and
+    the beside share.  Works with every ``eyebox`` mode; everything else returned is bit-identical to the run without
+    it.  ``budget=True``, ``error_bars``, ``estimator="expected"`` and ``footprint`` with it raise ``ValueError`` before
+    any GPU work."""
+    if hits is None or hits is False:
+        hits = None
+    else:
+        if budget or error_bars or estimator == "expected" or footprint is not None:
+            raise ValueError("hits is not combined with budget=True, error_bars, estimator='expected' or footprint: a "
+                             "launch keeps a hit list or does one of those")
+        if hits is not True and (isinstance(hits, bool) or int(hits) != hits or int(hits) < 0):
+            raise ValueError(f"hits must be True or a capacity >= 0 in records, got {hits!r}")
     if footprint is not None:
         if budget or error_bars or estimator == "expected":
             raise ValueError("footprint is not combined with budget=True, error_bars or estimator='expected': a launch "
@@ -173,6 +194,11 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
             from .engine import FootprintPlan
             fp = FootprintPlan.for_scene(job.geom, cells=footprint)
             job.footprint = (fp, fp.new_map(job.scene))
+        job.hits = None
+        if hits is not None:
+            from .engine import HitList
+            cap = -(-job.shard.n_rays * int(num_iter) // 8) if hits is True else int(hits)
+            job.hits = HitList(cap, job.dev)
         kern_s = _trace(job, variant, fuse)
         t_post = time.perf_counter()   # everything below is post-processing of the traced grid
         grid, table, stats = _collect(job, eyebox != "host", keep_grid)
@@ -188,6 +214,7 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
         if job.footprint is not None:   # integer counts: the ranks' maps add exactly
             from .distributed import reduce_eyebox
             fmap = reduce_eyebox(job.footprint[1])
+        records = _gather_hits(job) if job.hits is not None else None
         if job.rank != 0:
             return out
         _report(job, out, grid, table, reps)
@@ -195,6 +222,8 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
             _report_budget(job, out, census)
         if fmap is not None:
             _report_footprint(job, out, fmap)
+        if records is not None:
+            _report_hits(job, out, records)
         if evaluate:
             _evaluate(job, out, grid, table, evaluate_on, keep_image, png, reps)
         out["post_seconds"] = time.perf_counter() - t_post
@@ -284,6 +313,8 @@ def _trace(job, variant, fuse) -> float:
         per_call = 1                                      # expected-value estimator; the tracer offers no chain
     if getattr(job, "footprint", None) is not None:       # ... or counts footprints
         per_call = 1
+    if getattr(job, "hits", None) is not None:            # ... or keeps a hit list
+        per_call = 1
     calls = split_calls(job.num_iter, per_call)
     if n_rays and calls:
         reserve(job.scene, n_rays, max(calls))
@@ -291,7 +322,8 @@ def _trace(job, variant, fuse) -> float:
     t0.record()
     if n_rays:
         run_steps(hip_tracer(job.scene, variant, job.stats, job.windows, fate=job.fate, replicas=job.replicas,
-                             expected=getattr(job, "expected", False), footprint=getattr(job, "footprint", None)),
+                             expected=getattr(job, "expected", False), footprint=getattr(job, "footprint", None),
+                             hits=getattr(job, "hits", None)),
                   job.rays, job.rng, job.eb,
                   job.shard.gid, job.num_iter, per_call, hook=hook)
     t1.record()
@@ -348,6 +380,54 @@ def _report_budget(job, out: dict, census) -> None:
     for name, _, _ in FATE_CLASSES:
         row = [w["fractions"][name] for w in b["per_wavelength"]] + [b["total"]["fractions"][name]]
         job.say(f"  {name:18s}" + "".join(f"{v * 100:9.3f}%" for v in row))
+
+
+def _gather_hits(job):
+    """The job's hit list on rank 0 (None elsewhere), sorted by (tag, global id): every rank checks its own list for
+    overflow (together: a rank whose list overflowed raises on every rank), the counts are all-gathered, and the
+    stored records gathered as buffers padded to the largest."""
+    import torch
+    import torch.distributed as dist
+
+    from .engine import HIT_DTYPE, HitListOverflow, sort_hits
+    hl = job.hits
+    n, cap = hl.count(), hl.capacity
+    counts = torch.tensor([n, min(n, cap), cap], dtype=torch.int64, device=job.dev)
+    every = [counts]
+    if job.world > 1:
+        every = [torch.zeros_like(counts) for _ in range(job.world)]
+        dist.all_gather(every, counts)
+    every = [tuple(int(v) for v in t.cpu()) for t in every]
+    over = [(r, c) for r, c in enumerate(every) if c[0] > c[2]]
+    if over:
+        raise HitListOverflow("; ".join(f"rank {r}: the hit list counted {c[0]} out-couplings but has room for {c[2]} "
+                                        f"(a capacity of {c[0]} would have sufficed)" for r, c in over))
+    if job.world == 1:
+        return hl.records()
+    width = max(c[1] for c in every)
+    mine = torch.zeros((width, HIT_DTYPE.itemsize), dtype=torch.uint8, device=job.dev)
+    mine[:every[job.rank][1]] = hl.buffer[:every[job.rank][1]]
+    parts = [torch.zeros_like(mine) for _ in range(job.world)] if job.rank == 0 else None
+    dist.gather(mine, parts, dst=0)
+    if job.rank != 0:
+        return None
+    rec = np.concatenate([p[:c[1]].cpu().numpy().reshape(-1).view(HIT_DTYPE) for p, c in zip(parts, every)])
+    return sort_hits(rec)
+
+
+def _report_hits(job, out: dict, records) -> None:
+    """The hit list into ``out`` and, per wavelength, its out-couplings inside and beside the eyebox printed."""
+    from .engine import hit_inside, hit_lmn
+    out["hits"] = records
+    out["hit_count"] = int(len(records))
+    names = {0: "Blue", 1: "Green", 2: "Red"}
+    l = hit_lmn(records, job.nx, job.ny)[0]
+    inside = hit_inside(records)
+    job.say(f"Out-couplings kept: {len(records):,} records")
+    job.say(f"  {'':10s}{'inside eyebox':>15s}{'beside eyebox':>15s}{'beside share':>15s}")
+    for k in range(job.scene.num_lmd):
+        a, b = int((inside & (l == k)).sum()), int((~inside & (l == k)).sum())
+        job.say(f"  {names.get(k, str(k)):10s}{a:15,d}{b:15,d}{(b / (a + b) if a + b else 0.0) * 100:14.2f}%")
 
 
 def _report_footprint(job, out: dict, fmap) -> None:
@@ -500,6 +580,10 @@ def main(argv=None):
                          "state, where light is lost and where it out-couples); not with --budget, --error-bars or "
                          "--estimator expected")
     ap.add_argument("--footprint-out", default="", metavar="FILE.npy", help="save the footprint map there (numpy)")
+    ap.add_argument("--hits", nargs="?", const=-1, default=None, type=int, metavar="N",
+                    help="also keep every out-coupling, inside the eyebox or beside it, as a record (x, y, global ray id, "
+                         "tile, flags): N records of room (default: an eighth of the traces)")
+    ap.add_argument("--hits-out", default="", metavar="FILE.npy", help="save the records there (numpy structured array)")
     ap.add_argument("--budget", action="store_true",
                     help="also report where every ray ended: per-ray fates, their per-tile census and the loss budget "
                          "per wavelength (the traces then run as plain single launches)")
@@ -531,9 +615,11 @@ def main(argv=None):
               lut_profile=a.lut_profile, point_seed=a.point_seed, evaluate=not a.no_eval,
               fuse=False if a.no_fuse else {"auto": None, "yes": True, "no": False}[a.fuse],
               png=a.png or None, eyebox=a.eyebox, evaluate_on=a.evaluate, budget=a.budget, error_bars=a.error_bars, estimator=a.estimator,
-              footprint=footprint)
+              footprint=footprint, hits=None if a.hits is None else (True if a.hits < 0 else a.hits))
     if a.footprint_out and "footprint" in res:   # (rank 0 has the map)
         np.save(a.footprint_out, res["footprint"])
+    if a.hits_out and "hits" in res:   # (rank 0 has the list)
+        np.save(a.hits_out, res["hits"])
     if a.json and (not dist.is_initialized() or dist.get_rank() == 0):
         keep = {k: v for k, v in res.items() if isinstance(v, (int, float, dict, str))}
         with open(a.json, "w") as f:

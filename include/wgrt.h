@@ -591,6 +591,61 @@ wgrt_status wgrt_footprint_bin_host(const wgrt_footprint_plan *fp, const double 
                                     const int32_t *channel, int64_t n, int32_t num_lmd, int64_t *map);
 const char *wgrt_footprint_channel_name(int c);
 
+/* Keep every out-coupling: a hit list, and eyebox grids of any resolution from it (new symbols within ABI 9, looked up
+ * by name).
+ *
+ * wgrt_trace_hits is wgrt_trace_windows that also appends one record per out-coupling of the launch -- a draw that
+ * took the out-coupling branch (fate reasons 3 and 4), inside its FoV's eyebox rectangle or beside it, whether its
+ * aliased grid offset was stored or dropped -- to hits, DEVICE wgrt_hit [capacity], 16-byte aligned.
+ *   count     DEVICE uint64[1], ADDED to, never zeroed: it grows by the launch's out-couplings.  A record whose reserved
+ *             index (the counter's value when it was reserved) is below capacity is stored at hits[index]; the others
+ *             are counted and not stored.  Nothing at or beyond hits + capacity is written.  Several launches may
+ *             append to one list; the tag tells them apart.  The order of the records is unspecified; (tag, gid) is
+ *             unique per record, because a trace out-couples at most once.
+ *   hits      NULL: the call is exactly wgrt_trace_windows (capacity, count and tag are not looked at).  Otherwise
+ *             count != NULL, capacity >= 0 (0 only counts), tag <= 65535 and an aligned hits, else
+ *             WGRT_ERR_INVALID_ARGUMENT.
+ * With a list, rng_states, matrix_EB, the window table, per_ray_bounces and every field of stats come out bit-identical
+ * to the launch without it.  A hits launch is a single launch, as fate launches are: opts->num_iter > 1 is
+ * WGRT_ERR_INVALID_ARGUMENT, wgrt_chain_begin takes none, no entry point combines it with fates, replicas, the
+ * expected-value estimator or footprints, wgrt_debug_opts.timeline is WGRT_ERR_UNSUPPORTED, and it never learns the
+ * scene's tile table.  A ray the Jones lane abandons has appended nothing (a record is appended at the terminal
+ * out-coupling only), so its re-trace on the exact lane appends its record exactly once.  The call allocates nothing
+ * beyond the stream's launch scratch and is asynchronous on stream.  A launch through any other entry point runs the
+ * kernels it ran before this one existed. */
+typedef struct __attribute__((aligned(16))) wgrt_hit {   /* 32 bytes */
+    double x, y;               /* the out-coupling position: the ray's position at its last draw */
+    int64_t gid;               /* global ray id: gid_offset + i, or the id opts->gid_blocks gives ray i */
+    uint32_t tile;             /* (lambda * nx + m) * ny + n */
+    uint32_t flags;            /* bit 0: inside the FoV's eyebox rectangle (fate reason 3; clear: reason 4);
+                                  bits 16..31: the call's tag; every other bit 0 */
+} wgrt_hit;
+wgrt_status wgrt_trace_hits(const wgrt_scene *scene, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
+                            uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats, uint32_t *per_ray_bounces,
+                            void *stream, const wgrt_launch_opts *opts, const wgrt_window_plan *plan, double *table,
+                            wgrt_hit *hits, int64_t capacity, uint64_t *count, uint32_t tag);
+int32_t wgrt_hit_bytes(void);   /* sizeof(wgrt_hit) of the library */
+/* A list binned into an eyebox grid on the device: grid is DEVICE float32 [num_lmd, ny, nx, H, W], laid out as
+ * matrix_EB with (80, 120) replaced by (H, W), ADDED to, never zeroed; hits DEVICE wgrt_hit [n].  Record k's tile gives
+ * (l, m, n); a record whose tile is >= num_lmd * nx * ny is dropped.
+ *   ranges == NULL  the range (xmin, xmax, ymin, ymax) is the scene's eff_reg_FOV_range[m, n], and the record counts
+ *                   iff flag bit 0 is set.
+ *   ranges != NULL  DEVICE float64 [NX, NY, 4] in eff_reg_FOV_range's layout; the record counts iff
+ *                   xmin <= x <= xmax && ymin <= y <= ymax, the flag ignored: a beside-the-eyebox out-coupling gets
+ *                   into a larger or moved eyebox without a re-trace.
+ * The bin is the trace's own (csrc/wgrt_hits.h): dx = (xmax - xmin) / W, ix = (int64_t)floor((x - xmin) / dx), a
+ * negative index wraps once, an index equal to the axis length aliases through the flat offset, and the offset is
+ * guarded by 0 <= off < total -- so at ranges == NULL, H = 80, W = 120 the grid equals matrix_EB of the same launches
+ * bit for bit.  1 <= H, W <= 4096 and at most 2^31 floats, else WGRT_ERR_INVALID_ARGUMENT; n == 0 is WGRT_OK without a
+ * launch.  One thread per record, +1.0f atomics: counts are integers, so the grid is the same bits for any record
+ * order while a bin stays below 2^24.  Asynchronous on stream.
+ * _host is the twin over HOST pointers through the same header (no GPU needed): the scene is stated by nx, ny,
+ * num_lmd and scene_ranges, HOST float64 [nx, ny, 4] (eff_reg_FOV_range). */
+wgrt_status wgrt_hits_grid(const wgrt_scene *scene, const wgrt_hit *hits, int64_t n, const double *ranges, int32_t H,
+                           int32_t W, float *grid, void *stream);
+wgrt_status wgrt_hits_grid_host(int32_t nx, int32_t ny, int32_t num_lmd, const double *scene_ranges, const wgrt_hit *hits,
+                                int64_t n, const double *ranges, int32_t H, int32_t W, float *grid);
+
 /* Host-only (no GPU needed; test hooks) through the same membership code (csrc/wgrt_window.h):
  * _validate is wgrt_window_plan_create's argument check alone; _table_host ADDS the n hits at flat grid
  * offsets offsets[n] (HOST int64; those outside [0, n_slabs * 9600) are dropped, as the grid's guard drops

@@ -1,0 +1,521 @@
+"""The hit list on the GPU (``wgrt_trace_hits`` through ``torch.ops.wgrt.trace_hits``), its re-binning on the device
+(``wgrt_hits_grid``) and the driver's ``run(hits=...)``.
+
+Unless a test says otherwise, the comparison with the checker (``tests/oracle_hits.c``: the CPU oracle with its hooks
+defined) is the sorted records' bytes against the checker's sorted records' bytes: the positions are the same doubles
+on both lanes and in the oracle, as the footprint tests already rely on.  The walk is compared as bytes with the same
+launches without a list."""
+import ctypes
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+from gpu_ray_tracing_for_waveguide_based_ar_display_amd import _lib  # noqa: E402
+from gpu_ray_tracing_for_waveguide_based_ar_display_amd._lib import STAT  # noqa: E402
+from tests import _hits as H  # noqa: E402
+from tests._fixtures import GoldenCase  # noqa: E402
+from tests.test_gpu_parity import _config  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+FIXTURES = ["c1_rgb", "h6_edge_rgb", "s1_532"]
+_CONFIGS = {"c2s": dict(nx=11, ny=11, lambdas=[1], R=64),                      # 7,744 rays: > replay_tail's 256 threads
+            "small": dict(nx=5, ny=4, lambdas=[0, 1, 2], R=100),
+            "small_deep": dict(nx=5, ny=4, lambdas=[0, 1, 2], R=100, profile="deep", seed=3),
+            # the AMP instantiations: ``small_amp`` (R=100, seed 3) out-couples one ray or none per launch; this
+            # adversarial_polarizing config's checker list has 30, 27, 32 and 33 records in its four launches (asserted >= 20 below)
+            "amp_hits": dict(nx=5, ny=4, lambdas=[0, 1, 2], R=2500, profile="adversarial_polarizing", seed=2)}
+# launch 0's out-couplings (inside the eyebox rectangle, beside it): the oracle's own counts
+COUNTS = {"c1_rgb": (37, 62), "h6_edge_rgb": (26, 73), "s1_532": (8, 19), "c2s": (137, 225), "small": (133, 227),
+          "small_deep": (26, 27)}
+WIDEN = 1.5   # tests/test_hits.py: 254 of small's 360 records against 133
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("no HIP device")
+    return torch.device("cuda", 0)
+
+
+@pytest.fixture(autouse=True)
+def _switches():
+    yield
+    _lib.set_byte_locator(True)
+
+
+_cases, _checked = {}, {}
+
+
+def _case(name):
+    if name not in _cases:
+        _cases[name] = GoldenCase(name) if name in FIXTURES else _config(**_CONFIGS[name])
+    return _cases[name]
+
+
+def checked(name, launches=1):
+    """The checker on case ``name``, once per key and shared, read-only: ``dict(rec, rng, bounces, eb, counts)``."""
+    key = (name, launches)
+    if key not in _checked:
+        from oracle import OracleScene
+        c = _case(name)
+        sc = OracleScene.from_geometry(c.geom, c.luts, wavelength=getattr(c, "wavelength", None))
+        eb = np.zeros(c.eb_shape(), np.float32)
+        rec, rng, bounces, counts = H.checker(sc, c.rays, c.fresh_rng(), launches, eb=eb)
+        if name in COUNTS:
+            in0 = int(((rec["flags"] >> 16 == 0) & (rec["flags"] & 1 == 1)).sum())
+            assert (in0, counts[0] - in0) == COUNTS[name]
+        for a in (rec, rng, bounces, eb):
+            a.setflags(write=False)
+        _checked[key] = dict(rec=rec, rng=rng, bounces=bounces, eb=eb, counts=counts)
+    return _checked[key]
+
+
+def _ranges(c):
+    return np.ascontiguousarray(c.geom.eff_reg_FOV_range, dtype=np.float64)
+
+
+def _trace(c, dev, launches=1, variant=0, hits=True, capacity=None, hl=None, tags=None, rays=None, rng=None, scene=None,
+           keep=False, **kw):
+    """``launches`` single launches into the grid, the window table and (``hits``) one list, launch k tagged
+    ``tags[k]`` (default k): ``SimpleNamespace(rec, count, rng, eb, table, stats, per)`` on the host (``rec`` sorted).
+    ``hits=False``: the same calls without a list.  ``keep``: also ``hl`` and ``scene``, left open."""
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import (HitList, Scene, WindowPlan, new_stats,
+                                                                           rays_to_device, trace_fullcolor, trace_single)
+    wl = getattr(c, "wavelength", None)
+    own = scene is None
+    if own:
+        scene = Scene.from_geometry(c.geom, c.luts, wavelength=wl)
+    plan = WindowPlan()
+    trace = trace_single if wl is not None else trace_fullcolor
+    if hl is None and hits:
+        hl = HitList(c.N * launches if capacity is None else capacity, dev)
+    table = plan.new_table(scene)
+    eb = torch.zeros(scene.eb_shape(), dtype=torch.float32, device=dev)
+    rays = rays_to_device(c.rays, dev) if rays is None else rays
+    rng = torch.from_numpy(c.fresh_rng().view(np.int32)).to(dev) if rng is None else rng
+    stats = new_stats(dev)
+    per = torch.zeros(rng.numel(), dtype=torch.int32, device=dev)
+    tags = list(range(launches)) if tags is None else tags
+    for k in range(launches):
+        trace(scene, rays, rng, eb, stats=stats, per_ray_bounces=per, variant=variant, windows=(plan, table),
+              hits=(hl, tags[k]) if hits else None, **kw)
+    torch.cuda.synchronize()
+    out = SimpleNamespace(rec=hl.records() if hits else None, count=hl.count() if hits else None,
+                          rng=rng.cpu().numpy().view(np.uint32).copy(), eb=eb.cpu().numpy(), table=table.cpu().numpy(),
+                          stats=stats.cpu().numpy().copy(), per=per.cpu().numpy().view(np.uint32).copy())
+    plan.close()
+    if keep:
+        out.hl, out.scene, out.eb_dev = hl, scene, eb
+    elif own:
+        scene.close()
+    return out
+
+
+def _same_walk(a, b):
+    np.testing.assert_array_equal(a.rng, b.rng)
+    np.testing.assert_array_equal(a.per, b.per)
+    np.testing.assert_array_equal(a.stats, b.stats)
+    assert a.eb.tobytes() == b.eb.tobytes() and a.table.tobytes() == b.table.tobytes()
+
+
+def _same_list(got, want):
+    assert got.dtype == want.dtype == H.HIT_DTYPE and got.shape == want.shape, (got.shape, want.shape)
+    assert got.tobytes() == want.tobytes()
+
+
+def _stored_hits(rec, c, nl):
+    """The flagged records whose 80 x 120 offset lies in the buffer: what ``stats.eyebox_hits`` counts."""
+    return int((H.rule_offsets(rec, c.nx, c.ny, nl, _ranges(c), 80, 120) >= 0).sum())
+
+
+# 1. every variant, four tagged launches into one list --------------------------------------------------------------
+
+@pytest.mark.parametrize("variant", [1, 7, 9])
+@pytest.mark.parametrize("name", FIXTURES + ["small", "c2s"])
+def test_list_and_walk(dev, name, variant):
+    c = _case(name)
+    chk = checked(name, 4)
+    got = _trace(c, dev, launches=4, variant=variant)
+    _same_list(got.rec, chk["rec"])
+    assert got.count == len(chk["rec"]) == sum(chk["counts"]) > 0
+    nl = got.eb.size // (c.ny * c.nx * 80 * 120)   # (1 for the single-wavelength scene)
+    assert _stored_hits(got.rec, c, nl) == int(got.stats[STAT.eyebox_hits]) > 0
+    np.testing.assert_array_equal(got.rng, chk["rng"])
+    np.testing.assert_array_equal(got.per, chk["bounces"])
+    assert got.eb.tobytes() == chk["eb"].tobytes()
+    _same_walk(got, _trace(c, dev, launches=4, variant=variant, hits=False))
+
+
+# 2. the grid from the list -----------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("variant", [1, 7])
+@pytest.mark.parametrize("name", ["h6_edge_rgb", "small"])
+def test_grid_from_the_list_is_matrix_eb(dev, name, variant):
+    """At 80 x 120 over the scene's ranges the list's grid is the matrix_EB the same launches filled, byte for byte
+    (H6 aliasing included); at other resolutions, with and without caller ranges, the device grid is the host twin's."""
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import hits_grid_host
+    from tests.test_hits import widened
+    c = _case(name)
+    got = _trace(c, dev, launches=4, variant=variant, keep=True)
+    try:
+        g = got.hl.grid(got.scene, 80, 120)
+        torch.cuda.synchronize()
+        assert g.dtype == torch.float32 and tuple(g.shape) == tuple(got.eb.shape)
+        assert g.cpu().numpy().tobytes() == got.eb.tobytes() and got.eb.sum() > 0
+        # added to, never zeroed
+        g2 = got.hl.grid(got.scene, 80, 120, out=g)
+        assert g2 is g and g.cpu().numpy().tobytes() == (2 * got.eb).tobytes()
+        nl = got.eb.shape[0]
+        wide = widened(_ranges(c), WIDEN)
+        for HW in ((7, 13), (160, 240)):
+            for r in (None, wide):
+                dev_grid = got.hl.grid(got.scene, *HW, ranges=r).cpu().numpy()
+                host = hits_grid_host(got.hl.raw(), c.nx, c.ny, nl, _ranges(c), *HW, ranges=r)
+                assert dev_grid.tobytes() == host.tobytes()
+                assert host.tobytes() == H.grid_rule(got.rec, c.nx, c.ny, nl, _ranges(c), *HW, ranges=r).tobytes()
+                if r is not None:
+                    assert dev_grid.sum() > got.eb.sum()
+    finally:
+        got.scene.close()
+
+
+def test_grid_argument_errors(dev):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import HitList, Scene
+    c = _case("c1_rgb")
+    scene = Scene.from_geometry(c.geom, c.luts)
+    hl = HitList(8, dev)
+    L = _lib.load()
+    g = torch.zeros(3 * 3 * 3 * 4, dtype=torch.float32, device=dev)
+    call = lambda n=8, Hh=2, W=2, hits=hl.buffer.data_ptr(): L.wgrt_hits_grid(scene.handle, hits, n, None, Hh, W,
+                                                                            g.data_ptr(), None)
+    assert call(Hh=0) == 1 and call(W=4097) == 1 and call(n=-1) == 1 and call(hits=hl.buffer.data_ptr() + 8) == 1
+    # (more than 2^31 floats needs a scene of more than 128 tiles: the host twin's test has that case)
+    assert call(n=0, hits=None) == 0
+    assert call() == 0                                                 # zeroed records: tile 0, not flagged
+    torch.cuda.synchronize()
+    assert not g.any()
+    with pytest.raises(ValueError):
+        hl.grid(scene, 0, 4)
+    scene.close()
+
+
+# 3. refills: 13-ray work items on two workgroups --------------------------------------------------------------------
+
+def test_refills(dev):
+    c = _case("small_deep")
+    chk = checked("small_deep")
+    got = _trace(c, dev, variant=7, workgroups=2, debug=dict(chunk_rays=13))
+    _same_list(got.rec, chk["rec"])
+    assert got.count == sum(COUNTS["small_deep"])
+    np.testing.assert_array_equal(got.rng, chk["rng"])
+    _same_walk(got, _trace(c, dev, variant=7, workgroups=2, debug=dict(chunk_rays=13), hits=False))
+
+
+# 4. abandoned rays: the exact lane's re-trace appends the record, once ----------------------------------------------
+
+@pytest.mark.parametrize("debug, every", [(dict(cert_tol=1e-2), False), (dict(cert_tol=1e3, cert_tol32=1e3), True)])
+def test_abandoned_rays_are_recorded_once(dev, debug, every):
+    """A raised certification bound abandons rays in mid-walk (every ray at its first draw with ``cert_tol=1e3``): an
+    abandoned ray has pushed nothing, and its replay on the exact lane appends its record."""
+    c = _case("c2s")
+    chk = checked("c2s")
+    got = _trace(c, dev, variant=7, debug=debug)
+    traced, replayed = c.N - int(got.stats[STAT.bad_rays]), int(got.stats[STAT.replayed])
+    print(f"replayed {replayed} of {traced}")
+    if every:
+        assert replayed == traced > 256
+    else:
+        assert 0 < replayed < traced
+    assert len(np.unique(got.rec["gid"])) == len(got.rec) == got.count == sum(COUNTS["c2s"])   # none twice, none missing
+    _same_list(got.rec, chk["rec"])
+    np.testing.assert_array_equal(got.per, chk["bounces"])
+    np.testing.assert_array_equal(got.rng, chk["rng"])
+    _same_walk(got, _trace(c, dev, variant=7, debug=debug, hits=False))
+
+
+# 5. both locator forms, the single-wavelength kernel, an AMP profile, split batches ----------------------------------
+
+@pytest.mark.parametrize("variant", [7, 9])
+def test_byte_and_word_locator(dev, variant):
+    c = _case("small")
+    chk = checked("small")
+    for byte in (True, False):
+        _lib.set_byte_locator(byte)
+        got = _trace(c, dev, variant=variant)
+        _same_list(got.rec, chk["rec"])
+        np.testing.assert_array_equal(got.rng, chk["rng"])
+    _lib.set_byte_locator(True)
+
+
+def test_single_wavelength(dev):
+    c = _case("s1_532")
+    assert getattr(c, "wavelength", None) is not None
+    chk = checked("s1_532")
+    for variant in (1, 7, 9):
+        got = _trace(c, dev, variant=variant)
+        assert got.rec["tile"].max() < c.nx * c.ny
+        _same_list(got.rec, chk["rec"])
+        np.testing.assert_array_equal(got.rng, chk["rng"])
+
+
+def test_amp_profile(dev):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import Scene
+    c = _case("amp_hits")
+    sc = Scene.from_geometry(c.geom, c.luts)
+    assert sc.info()["nonunitary_blocks"] > 0
+    sc.close()
+    chk = checked("amp_hits", 4)
+    print("records per launch:", chk["counts"])
+    assert min(chk["counts"]) >= 20
+    for variant in (7, 9):
+        got = _trace(c, dev, launches=4, variant=variant, capacity=1024)
+        _same_list(got.rec, chk["rec"])
+        np.testing.assert_array_equal(got.rng, chk["rng"])
+        assert got.count == sum(chk["counts"])
+
+
+@pytest.mark.parametrize("variant", [1, 7])
+def test_a_batch_split_at_ray_37(dev, variant):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import HitList, Scene, rays_to_device
+    c = _case("c1_rgb")
+    chk = checked("c1_rgb")
+    scene = Scene.from_geometry(c.geom, c.luts)
+    hl = HitList(c.N, dev)
+    full = rays_to_device(c.rays, dev)
+    rng_all = torch.from_numpy(c.fresh_rng().view(np.int32)).to(dev)
+    got_rng = []
+    for lo, hi in ((0, 37), (37, c.N)):
+        rays = {k: v[lo:hi].contiguous() for k, v in full.items()}
+        r = _trace(c, dev, variant=variant, rays=rays, rng=rng_all[lo:hi].contiguous(), hl=hl, scene=scene,
+                   gid_offset=lo)
+        got_rng.append(r.rng)
+    rec = hl.records()
+    scene.close()
+    _same_list(rec, chk["rec"])
+    np.testing.assert_array_equal(np.concatenate(got_rng), chk["rng"])
+
+
+def test_two_gid_blocks_shards_make_the_whole_list(dev):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.distributed import make_shard
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import init_rays, sort_hits
+    c = _case("c1_rgb")
+    chk = checked("c1_rgb")
+    parts = []
+    for r in range(2):
+        shard = make_shard(c.nx, c.ny, len(c.lambdas), c.R, 2, r)
+        rays, rng = init_rays(c.f["points"], c.nx, c.ny, c.lambdas, c.R, block_list=shard.blocks, device=dev)
+        gb = torch.from_numpy(shard.gid.block_gid).to(dev)
+        rec = _trace(c, dev, variant=7, rays=rays, rng=rng, n_rays=rng.numel(), gid_blocks=gb, gid_block_rays=c.R,
+                     capacity=c.N).rec
+        assert len(rec) > 0
+        parts.append(rec)
+    _same_list(sort_hits(np.concatenate(parts)), chk["rec"])
+
+
+# 6. capacity --------------------------------------------------------------------------------------------------------
+
+CANARY = 0xA5
+
+
+@pytest.mark.parametrize("variant", [1, 7])
+def test_capacity(dev, variant):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import HitList, HitListOverflow, check_hits
+    c = _case("small")
+    chk = checked("small", 2)
+    want0 = chk["rec"][chk["rec"]["flags"] >> 16 == 0]
+    n0, n1 = chk["counts"]
+    assert n0 == 360
+    # capacity 10 inside a buffer with a canary pattern behind it
+    hl = HitList(64, dev)
+    hl.buffer.fill_(CANARY)
+    hl.capacity = 10
+    got = _trace(c, dev, variant=variant, hl=hl)
+    assert got.count == 360 and hl.stored() == 10
+    raw = hl.buffer.cpu().numpy()
+    assert (raw[10:] == CANARY).all()
+    have = {r.tobytes() for r in want0}
+    assert len({r.tobytes() for r in got.rec}) == 10 and all(r.tobytes() in have for r in got.rec)
+    with pytest.raises(HitListOverflow, match="360.*10"):
+        check_hits(hl)
+    _same_walk(got, _trace(c, dev, variant=variant, hits=False))
+    # capacity 0 counts and stores nothing
+    hl = HitList(16, dev)
+    hl.buffer.fill_(CANARY)
+    hl.capacity = 0
+    got = _trace(c, dev, variant=variant, hl=hl)
+    assert got.count == 360 and len(got.rec) == 0 and (hl.buffer.cpu().numpy() == CANARY).all()
+    # a second launch into a list of capacity 400 that already holds 360
+    hl = HitList(400 + 8, dev)
+    hl.buffer[400:].fill_(CANARY)
+    hl.capacity = 400
+    got = _trace(c, dev, launches=2, variant=variant, hl=hl)
+    assert got.count == 360 + n1 and n1 > 40 and hl.stored() == 400
+    assert (hl.buffer[400:].cpu().numpy() == CANARY).all()
+    tag = got.rec["flags"] >> 16
+    _same_list(got.rec[tag == 0], want0)
+    new = got.rec[tag == 1]
+    have1 = {r.tobytes() for r in chk["rec"][chk["rec"]["flags"] >> 16 == 1]}
+    assert len(new) == 40 == len({r.tobytes() for r in new}) and all(r.tobytes() in have1 for r in new)
+    check_hits(HitList(0, dev))
+
+
+# 7. argument errors -------------------------------------------------------------------------------------------------
+
+def test_argument_errors(dev):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import (FootprintPlan, HitList, Scene, TraceChain,
+                                                                           WindowPlan, _debug_opts, rays_to_device,
+                                                                           trace_fullcolor)
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd._lib import load, ops
+    c = _case("c1_rgb")
+    scene, plan = Scene.from_geometry(c.geom, c.luts), WindowPlan()
+    rays = rays_to_device(c.rays, dev)
+    rng = torch.from_numpy(c.fresh_rng().view(np.int32)).to(dev)
+    before = rng.clone()
+    hl = HitList(c.N, dev)
+    grid = torch.zeros(c.eb_shape(), dtype=torch.float32, device=dev)
+    table = plan.new_table(scene)
+    go = lambda **kw: trace_fullcolor(scene, rays, rng, grid, variant=7, hits=(hl, 0), **kw)
+    with pytest.raises(ValueError, match="num_iter"):
+        go(num_iter=2)
+    with pytest.raises(ValueError, match="fate"):
+        go(fate=torch.zeros(c.N, dtype=torch.uint8, device=dev))
+    with pytest.raises(ValueError, match="replicas"):
+        go(windows=(plan, plan.new_table(scene, replicas=4)), replicas=4)
+    with pytest.raises(ValueError, match="expected"):
+        trace_fullcolor(scene, rays, rng, None, windows=(plan, table), expected=True, hits=(hl, 0))
+    fp = FootprintPlan.for_scene(c.geom, cells=(8, 8))
+    with pytest.raises(ValueError, match="footprint"):
+        go(footprint=(fp, fp.new_map(scene)))
+    with pytest.raises(ValueError, match="chain"):
+        TraceChain(scene, rays, rng, grid, hits=(hl, 0))
+    with pytest.raises(TypeError):
+        trace_fullcolor(scene, rays, rng, grid, hits=(hl.buffer, 0))
+
+    # the operator and the C entry point themselves
+    def op(buf=hl.buffer, cap=c.N, count=hl.counter, tag=0, num_iter=1, debug=0, variant=7):
+        return ops().trace_hits(scene.handle.value, rays["x"], rays["y"], rays["m"], rays["n"], rays["lmd_num"],
+                                rays["te"], rays["tm"], rays["delta_phase"], rng, grid, None, None, c.N, 0, 0, 0, variant,
+                                0, None, num_iter, None, 0, debug, 0.0, 0, None, buf, cap, count, tag)
+    for v in (1, 7):
+        assert op(num_iter=2, variant=v) == 1                                      # WGRT_ERR_INVALID_ARGUMENT
+        assert op(count=None, variant=v) == 1
+        assert op(cap=-1, variant=v) == 1
+        assert op(tag=65536, variant=v) == 1 and op(tag=-1, variant=v) == 1
+        assert op(buf=hl.buffer.reshape(-1)[8:], cap=4, variant=v) == 1            # a misaligned list
+    tl = torch.zeros(8 * 64, dtype=torch.int64, device=dev)
+    dbg = _debug_opts(dict(timeline=tl))
+    assert op(debug=ctypes.addressof(dbg)) == 4                                    # WGRT_ERR_UNSUPPORTED
+    with pytest.raises(RuntimeError, match="uint8"):
+        op(buf=hl.buffer.to(torch.int32))
+    with pytest.raises(RuntimeError, match="must be on"):
+        op(buf=hl.buffer.cpu())
+    with pytest.raises(RuntimeError, match="exceeds"):
+        op(cap=c.N + 1)
+    with pytest.raises(RuntimeError, match="int64"):
+        op(count=hl.counter.to(torch.int32))
+    torch.cuda.synchronize()
+    assert torch.equal(rng, before) and not grid.any() and not tl.any() and hl.count() == 0   # nothing was launched
+    assert not hl.buffer.any()
+
+    # hits == NULL: the windows launch, bit for bit (capacity, count and tag are not looked at)
+    L = load()
+    cols = _lib.Rays(**{k: ctypes.c_void_p(rays[k].data_ptr()) for k in ("x", "y", "m", "n", "lmd_num", "te", "tm",
+                                                                          "delta_phase")})
+    opts = _lib.LaunchOpts()
+    opts.variant = 7
+    st = torch.zeros(_lib.STATS_LEN, dtype=torch.int64, device=dev)
+    assert L.wgrt_trace_hits(scene.handle, ctypes.byref(cols), c.N, 0, rng.data_ptr(), grid.data_ptr(),
+                             st.data_ptr(), None, None, ctypes.byref(opts), plan.handle, table.data_ptr(), None,
+                             -5, None, 1 << 20) == 0
+    rng2, grid2, table2, st2 = before.clone(), torch.zeros_like(grid), torch.zeros_like(table), torch.zeros_like(st)
+    assert L.wgrt_trace_windows(scene.handle, ctypes.byref(cols), c.N, 0, rng2.data_ptr(), grid2.data_ptr(),
+                                st2.data_ptr(), None, None, ctypes.byref(opts), plan.handle, table2.data_ptr()) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(rng, rng2) and torch.equal(grid, grid2) and torch.equal(table, table2) and torch.equal(st, st2)
+    assert grid.sum() > 0 and hl.count() == 0
+    plan.close()
+    scene.close()
+
+
+# 8. the driver ------------------------------------------------------------------------------------------------------
+# the small job of tests/test_gpu_window_sink.py ("deep" LUT profile)
+
+NX, NY, R, STEPS = 5, 4, 256, 2
+_runs = {}
+
+
+def _run(hits, eyebox="windows", **kw):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.gpu_ray_tracing_pro_fullColor import run
+    from tests import _dist
+    pts = _dist.small_job(NX, NY, R, 3, 6, "deep")[2]
+    return run(NX, NY, R, STEPS, lut_seed=3, lut_profile="deep", points=pts, verbose=False, eyebox=eyebox,
+               evaluate_on="device" if eyebox != "host" else "host", hits=hits, **kw)
+
+
+def _run_once(hits):
+    if hits not in _runs:
+        _runs[hits] = _run(hits)
+    return _runs[hits]
+
+
+def test_driver_hits(dev):
+    from oracle import OracleScene
+    from tests import _dist
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import HitListOverflow
+    got, plain = _run_once(True), _run_once(None)
+    assert set(got) - set(plain) == {"hits", "hit_count"}
+    for k in plain:   # everything returned before, bit for bit (the timings aside)
+        if k in ("gpu_seconds", "post_seconds"):
+            continue
+        a, b = got[k], plain[k]
+        if isinstance(a, np.ndarray):
+            assert a.tobytes() == b.tobytes(), k
+        else:
+            assert a == b or (isinstance(a, float) and float(a).hex() == float(b).hex()), k
+    # the checker on the driver's batch: launch k tagged k
+    geom, luts, pts = _dist.small_job(NX, NY, R, 3, 6, "deep")
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.rays import build_rays, rng_seeds
+    rays = build_rays(pts, NX, NY, (0, 1, 2), R)
+    want = H.checker(OracleScene.from_geometry(geom, luts), rays, rng_seeds(rays["x"].shape[0]), STEPS)
+    _same_list(got["hits"], want[0])
+    assert got["hit_count"] == len(want[0]) > 0
+    np.testing.assert_array_equal(got["rng_states"], want[1])
+    for bad in (dict(budget=True), dict(error_bars=4), dict(estimator="expected"), dict(footprint=(64, 96))):
+        with pytest.raises(ValueError, match="hits"):
+            _run(True, **bad)
+    with pytest.raises(ValueError, match="hits"):
+        _run(-3)
+    # a capacity that does not suffice: raised after the trace, naming the one that would have
+    with pytest.raises(HitListOverflow, match=str(len(want[0]))):
+        _run(5)
+    # any eyebox mode: the same list, and from it the grid that run kept
+    r = _run(True, eyebox="device", keep_grid=True)
+    _same_list(r["hits"], got["hits"])
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import hits_grid_host
+    g = hits_grid_host(r["hits"], NX, NY, 3, np.asarray(geom.eff_reg_FOV_range, np.float64), 80, 120)
+    assert g.tobytes() == np.ascontiguousarray(r["matrix_EB"]).tobytes()
+
+
+def _driver_worker(rank, world, outdir):
+    torch.cuda.set_device(torch.device("cuda", 0))
+    res = _run(True)
+    np.save(f"{outdir}/rng{rank}.npy", res["rng_states"])
+    if rank != 0:
+        assert "hits" not in res
+        return
+    np.save(f"{outdir}/hits.npy", res["hits"])
+    np.save(f"{outdir}/count.npy", np.array([res["hit_count"]]))
+
+
+def test_driver_hits_in_two_ranks(dev, tmp_path):
+    """Two ranks on the one GPU over gloo: the ids are global, so the sorted concatenation of the ranks' lists is the
+    single-process list."""
+    from tests import _dist
+    _dist.spawn(_driver_worker, 2, str(tmp_path))
+    one = _run_once(True)
+    _same_list(np.load(tmp_path / "hits.npy"), one["hits"])
+    assert int(np.load(tmp_path / "count.npy")[0]) == one["hit_count"]
