@@ -33,7 +33,8 @@ EXPORTED = ("wgrt_scene_create", "wgrt_scene_create_ex", "wgrt_scene_destroy", "
             "wgrt_window_replicas_fold", "wgrt_window_replicas_fold_host", "wgrt_trace_expected",
             "wgrt_expected_weight_host", "wgrt_trace_footprint", "wgrt_footprint_plan_validate",
             "wgrt_footprint_bin_host", "wgrt_footprint_channel_name", "wgrt_trace_hits", "wgrt_hit_bytes",
-            "wgrt_hits_grid", "wgrt_hits_grid_host")
+            "wgrt_hits_grid", "wgrt_hits_grid_host", "wgrt_trace_paths", "wgrt_path_vertex_bytes",
+            "wgrt_paths_footprint", "wgrt_paths_footprint_host")
 EXPORTED_DEBUG = ("wgrt_debug_shadow", "wgrt_debug_scene_copy", "wgrt_debug_set_auto_order",
                   "wgrt_debug_get_auto_order", "wgrt_debug_get_tile_tail", "wgrt_debug_order_host",
                   "wgrt_debug_chain_plan", "wgrt_debug_chain_set_serial", "wgrt_debug_set_byte_locator",
@@ -355,6 +356,15 @@ def load():
         L.wgrt_hits_grid_host.restype = st
         L.wgrt_hits_grid_host.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, ctypes.c_int64, _vp,
                                           ctypes.c_int32, ctypes.c_int32, _vp]
+    if hasattr(L, "wgrt_trace_paths"):   # ray paths and their reduction: new symbols within ABI 9, by name
+        L.wgrt_trace_paths.restype = st
+        L.wgrt_trace_paths.argtypes = L.wgrt_trace_opts.argtypes + [_vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_uint32, _vp]
+        L.wgrt_path_vertex_bytes.restype = ctypes.c_int32
+        L.wgrt_path_vertex_bytes.argtypes = []
+        L.wgrt_paths_footprint.restype = st
+        L.wgrt_paths_footprint.argtypes = [_vp, ctypes.c_int64, ctypes.c_int32, _vp, _vp, _vp]
+        L.wgrt_paths_footprint_host.restype = st
+        L.wgrt_paths_footprint_host.argtypes = [_vp, ctypes.c_int64, ctypes.c_int32, _vp, _vp]
     if hasattr(L, "wgrt_locator_palette_host"):   # the byte locator's hooks: new symbols within ABI 9, bound by name
         L.wgrt_locator_palette_host.restype = st
         L.wgrt_locator_palette_host.argtypes = [ctypes.POINTER(SceneDesc), ctypes.c_double, _i64, _i64, _d,

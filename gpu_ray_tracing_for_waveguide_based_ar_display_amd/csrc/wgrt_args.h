@@ -152,6 +152,19 @@ struct TraceArgs {
     uint32_t *q_ray;
     uint32_t hits_tag;
     uint32_t hits_pad_;
+    // the path list (wgrt_trace_paths; wgrt_paths.h): with paths, every draw of the bounce loop of a selected ray, and
+    // the end of a trace that leaves eff_reg1 or misses in R5, is a record of the list: an index is reserved on
+    // *paths_count and, where it is below paths_cap, the record is stored at paths[index], tagged paths_tag.  select:
+    // one byte per ray of the batch, nonzero: record the ray (NULL: every ray).  Only the PATHS instantiations read
+    // them: the exact lane appends one record at a time (trace_grid_paths_kernel, the kPaths replay), the Jones-vector
+    // lane stages a wave's records in LDS and reserves a block's indices at once; the draws it had recorded of a ray it
+    // abandons go to the replay in fp_seen's storage.  Single launches only.  Last again.
+    wgrt_path_vertex *paths;
+    int64_t paths_cap;
+    unsigned long long *paths_count;
+    const uint8_t *select;
+    uint32_t paths_tag;
+    uint32_t paths_pad_;
 };
 
 // The replica of global ray id g >= 0 among reps (2 .. 64) copies: g % reps from 32-bit remainders (the 64-bit

@@ -34,6 +34,7 @@
 #include "wgrt_footprint.h"
 #include "wgrt_hits.h"
 #include "wgrt_locator.h"
+#include "wgrt_paths.h"
 #include "wgrt_window.h"
 
 namespace wgrt {
@@ -199,6 +200,20 @@ __device__ __forceinline__ void hit_store(wgrt_hit *hits, int64_t cap, unsigned 
         double2 *const p = (double2 *)(hits + idx);
         p[0] = double2{x, y};
         ((ulonglong2 *)p)[1] = ulonglong2{(unsigned long long)gid, (unsigned long long)tile | (unsigned long long)flags << 32};
+    }
+}
+
+// One record of the path list (wgrt_trace_paths; wgrt_paths.h) at its reserved index, by hit_store's pattern: stored
+// iff the index is below the capacity, as two 16-byte stores (position; global id, step below flags).
+__device__ __forceinline__ void path_store(wgrt_path_vertex *paths, int64_t cap, unsigned long long idx, double x,
+                                           double y, int64_t gid, uint32_t step, uint32_t flags) {
+    static_assert(offsetof(wgrt_path_vertex, gid) == 16 && offsetof(wgrt_path_vertex, step) == 24 &&
+                      offsetof(wgrt_path_vertex, flags) == 28,
+                  "the second half: gid, then step below flags in one 64-bit word");
+    if (idx < (unsigned long long)cap) {
+        double2 *const p = (double2 *)(paths + idx);
+        p[0] = double2{x, y};
+        ((ulonglong2 *)p)[1] = ulonglong2{(unsigned long long)gid, (unsigned long long)step | (unsigned long long)flags << 32};
     }
 }
 
@@ -517,10 +532,14 @@ __device__ __forceinline__ void footprint_count(const TraceArgs &A, int l, int r
 // EV: with the expected-value deposits (above); skip: the scored visits to pass over.
 // FP: with the footprint counts (above); skip: the counted draws to pass over.
 // HITS: with the hit list's appends (interact<.., HITS>).
-template <bool FATE = false, bool EV = false, bool FP = false, bool HITS = false>
+// PATHS: with the path list's appends (wgrt_paths.h), for a ray that A.select names: one record per draw of the bounce
+// loop, numbered from 0, and the end record of a trace that advance() ends with reason 1 or 5; skip: the draws to pass
+// over, recorded by the Jones lane before it abandoned the ray, which the numbering counts on from.
+template <bool FATE = false, bool EV = false, bool FP = false, bool HITS = false, bool PATHS = false>
 __device__ __forceinline__ void trace_one(const TraceArgs &A, int64_t i, Counters &c, uint32_t *s_io = nullptr,
                                           uint32_t skip = 0) {
-    static_assert(!(EV && FP), "a launch scores visits or counts footprints: skip belongs to one of them");
+    static_assert(!(EV && FP) && !(EV && PATHS) && !(FP && PATHS),
+                  "a launch scores visits, counts footprints or records paths: skip belongs to one of them");
     Lane L;
     if (!lane_load(A, i, L)) {
         ++c.w[kCtrBadRays];
@@ -530,20 +549,37 @@ __device__ __forceinline__ void trace_one(const TraceArgs &A, int64_t i, Counter
     if (s_io) L.r.s = *s_io;
     int blk = 0, kind = 0;
     bool entry = true;
+    // PATHS: whether the ray is recorded, and the ordinal of its next record
+    const bool psel = PATHS && (!A.select || A.select[i] != 0);
+    const int64_t pgid = psel ? ray_gid(A, L.i) : 0;   // (once per ray, not per record)
+    uint32_t pstep = 0;
     for (;;) {
-        // FP: where and in which state the ray stands at this draw
+        // FP, PATHS: where and in which state the ray stands at this draw
         const double fx = L.r.x, fy = L.r.y;
         const int freg = L.r.region;
-        const int next = interact<FATE || FP, EV, HITS>(A, A.loc, L, blk, kind, entry, &skip);
+        const int next = interact<FATE || FP || PATHS, EV, HITS>(A, A.loc, L, blk, kind, entry, &skip);
         if (FP && !entry) {
             if (skip) --skip;   // counted by the lane that abandoned the ray
             else footprint_count(A, L.l, freg, next < 0 ? L.why % 10 : 0, fx, fy);
         }
+        if (PATHS && !entry) {
+            if (skip) --skip;   // recorded by the lane that abandoned the ray
+            else if (psel)
+                path_store(A.paths, A.paths_cap, atomicAdd(A.paths_count, 1ull), fx, fy, pgid, pstep,
+                           path_flags(freg, path_draw_kind(next < 0 ? L.why % 10 : 0), L.l, A.paths_tag));
+            ++pstep;
+        }
         if (next < 0) break;
         L.r.region = next;
         entry = false;
-        blk = advance<FATE>(A, A.loc, L, kind);
-        if (blk < 0) break;
+        blk = advance<FATE || PATHS>(A, A.loc, L, kind);
+        if (blk < 0) {
+            // PATHS: the trace ended outside a draw, where the ray stands now
+            if (PATHS && psel && path_end_reason(L.why % 10))
+                path_store(A.paths, A.paths_cap, atomicAdd(A.paths_count, 1ull), L.r.x, L.r.y, pgid, pstep,
+                           path_flags(L.why / 10, L.why % 10, L.l, A.paths_tag));
+            break;
+        }
         ++c.w[kCtrInter];   // the interactions after the in-coupling event
     }
     if (s_io) *s_io = L.r.s;

@@ -130,6 +130,19 @@ decltype(&wgrt_trace_hits) hits_abi() {
     return fn;
 }
 
+// wgrt_trace_paths and wgrt_paths_footprint (ray paths), new within ABI 9 too: looked up at the first call of either.
+struct PathsAbi {
+    decltype(&wgrt_trace_paths) trace;
+    decltype(&wgrt_paths_footprint) footprint;
+};
+const PathsAbi &paths_abi() {
+    static const PathsAbi abi{reinterpret_cast<decltype(&wgrt_trace_paths)>(dlsym(RTLD_DEFAULT, "wgrt_trace_paths")),
+                              reinterpret_cast<decltype(&wgrt_paths_footprint)>(dlsym(RTLD_DEFAULT, "wgrt_paths_footprint"))};
+    TORCH_CHECK(abi.trace && abi.footprint,
+                "wgrt.trace_paths: the loaded libwgrt.so has no wgrt_trace_paths (a build from before the ray paths)");
+    return abi;
+}
+
 // All three launching operators: trace (the grid alone: plan 0, no table), trace_windows (the grid, the window
 // table of plan `plan` -- a wgrt_window_plan handle -- or both) and, with `chain`, chain_begin: the same checks and
 // records handed to wgrt_chain_begin, which launches nothing and leaves the chain's handle in *chain.
@@ -143,7 +156,8 @@ int64_t trace_core(int64_t scene, const Tensor &x, const Tensor &y, const Tensor
                    std::optional<Tensor> fate = std::nullopt, int64_t replicas = 0, bool expected = false,
                    const wgrt_footprint_plan *fp = nullptr, std::optional<Tensor> fp_map = std::nullopt,
                    std::optional<Tensor> hits = std::nullopt, int64_t hit_capacity = 0,
-                   std::optional<Tensor> hit_count = std::nullopt, int64_t hit_tag = 0) {
+                   std::optional<Tensor> hit_count = std::nullopt, int64_t hit_tag = 0, bool as_paths = false,
+                   const std::optional<Tensor> &select = std::nullopt) {
     const wgrt_scene *s = reinterpret_cast<const wgrt_scene *>(static_cast<uintptr_t>(scene));
     TORCH_CHECK(s != nullptr, "wgrt.trace: NULL scene");
     wgrt_scene_info info{};
@@ -237,23 +251,35 @@ int64_t trace_core(int64_t scene, const Tensor &x, const Tensor &y, const Tensor
         TORCH_CHECK(!per, "wgrt.chain_begin: a chain takes no per_ray_bounces");
         return chain_abi().begin(s, &r, n_rays, gid_offset, rng, eb, stp, hip_stream, &o, tab ? wp : nullptr, tab, chain);
     }
-    if (hits) {   // trace_hits: the record buffer (uint8, 32 bytes per record), its capacity, the counter and the tag
-        TORCH_CHECK(!fp_map && !fate && replicas == 0 && !expected,
-                    "wgrt.trace_hits: takes no fate, replicas, expected or footprint map");
-        on_device(*hits, "hits", c);
-        TORCH_CHECK(hits->scalar_type() == at::kByte && hits->is_contiguous(), "wgrt.trace_hits: hits must be contiguous uint8");
+    if (hits) {   // trace_hits / trace_paths: the record buffer (uint8, 32 bytes per record), its capacity, the counter
+                  // and the tag; trace_paths (as_paths) also the batch's select bytes
+        static_assert(sizeof(wgrt_hit) == sizeof(wgrt_path_vertex), "both lists hold 32-byte records");
+        const char *const op = as_paths ? "wgrt.trace_paths" : "wgrt.trace_hits";
+        TORCH_CHECK(!fp_map && !fate && replicas == 0 && !expected, op, ": takes no fate, replicas, expected or footprint map");
+        on_device(*hits, "list", c);
+        TORCH_CHECK(hits->scalar_type() == at::kByte && hits->is_contiguous(), op, ": the list must be contiguous uint8");
         // (a negative capacity is the library's to refuse; a positive one must lie inside the buffer)
-        TORCH_CHECK(hit_capacity <= 0 || hit_capacity <= hits->numel() / (int64_t)sizeof(wgrt_hit),
-                    "wgrt.trace_hits: capacity ", hit_capacity, " exceeds the buffer's ", hits->numel() / (int64_t)sizeof(wgrt_hit),
-                    " records");
+        TORCH_CHECK(hit_capacity <= 0 || hit_capacity <= hits->numel() / (int64_t)sizeof(wgrt_hit), op, ": capacity ",
+                    hit_capacity, " exceeds the buffer's ", hits->numel() / (int64_t)sizeof(wgrt_hit), " records");
         uint64_t *cnt = nullptr;
         if (hit_count) {
             on_device(*hit_count, "count", c);
-            TORCH_CHECK(hit_count->scalar_type() == at::kLong && hit_count->numel() == 1, "wgrt.trace_hits: count must be int64[1]");
+            TORCH_CHECK(hit_count->scalar_type() == at::kLong && hit_count->numel() == 1, op, ": count must be int64[1]");
             cnt = static_cast<uint64_t *>(hit_count->data_ptr());
         }
         // (out of uint32 range: a tag the library refuses)
         const uint32_t tag = hit_tag < 0 || hit_tag > 0xffffffffll ? 0xffffffffu : static_cast<uint32_t>(hit_tag);
+        if (as_paths) {
+            const uint8_t *sel = nullptr;
+            if (select) {
+                on_device(*select, "select", c);
+                TORCH_CHECK(select->scalar_type() == at::kByte && select->is_contiguous() && select->numel() >= n_rays,
+                            "wgrt.trace_paths: select must be contiguous uint8 with >= ", n_rays, " entries");
+                sel = static_cast<const uint8_t *>(select->const_data_ptr());
+            }
+            return paths_abi().trace(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o, tab ? wp : nullptr, tab,
+                                     static_cast<wgrt_path_vertex *>(hits->data_ptr()), hit_capacity, cnt, tag, sel);
+        }
         return hits_abi()(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o, tab ? wp : nullptr, tab,
                           static_cast<wgrt_hit *>(hits->data_ptr()), hit_capacity, cnt, tag);
     }
@@ -384,6 +410,50 @@ int64_t trace_hits(int64_t scene, const Tensor &x, const Tensor &y, const Tensor
                       std::nullopt, hits, capacity, count, tag);
 }
 
+// trace_paths: trace_hits' arguments over a path list, and the batch's select bytes (wgrt_trace_paths).
+int64_t trace_paths(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
+                    const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
+                    Tensor rng_states, std::optional<Tensor> matrix_EB, std::optional<Tensor> stats,
+                    std::optional<Tensor> per_ray_bounces, int64_t n_rays, int64_t gid_offset, int64_t stream,
+                    int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
+                    int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
+                    double grid_sqrt_k, int64_t plan, std::optional<Tensor> table, Tensor paths, int64_t capacity,
+                    std::optional<Tensor> count, int64_t tag, const std::optional<Tensor> &select) {
+    return trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats, per_ray_bounces,
+                      n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
+                      gid_block_rays, debug, grid_sqrt_k, plan, table, nullptr, std::nullopt, 0, false, nullptr,
+                      std::nullopt, paths, capacity, count, tag, true, select);
+}
+
+// paths_footprint: the first n records of a path list added into a footprint map on the list's device
+// (wgrt_paths_footprint).
+int64_t paths_footprint(const Tensor &paths, int64_t n, int64_t num_lmd, double fp_x0, double fp_y0, double fp_cell_x,
+                        double fp_cell_y, int64_t fp_nx_cells, int64_t fp_ny_cells, Tensor map, int64_t stream) {
+    TORCH_CHECK(paths.is_cuda() && map.is_cuda() && paths.device() == map.device(),
+                "wgrt.paths_footprint: the list and the map must be on one GPU");
+    TORCH_CHECK(paths.scalar_type() == at::kByte && paths.is_contiguous(), "wgrt.paths_footprint: the list must be contiguous uint8");
+    TORCH_CHECK(n >= 0 && n <= paths.numel() / (int64_t)sizeof(wgrt_path_vertex), "wgrt.paths_footprint: n = ", n,
+                " exceeds the buffer's ", paths.numel() / (int64_t)sizeof(wgrt_path_vertex), " records");
+    wgrt_footprint_plan fp{};
+    fp.x0 = fp_x0;
+    fp.y0 = fp_y0;
+    fp.cell_x = fp_cell_x;
+    fp.cell_y = fp_cell_y;
+    fp.nx_cells = static_cast<int32_t>(std::max<int64_t>(-1, std::min<int64_t>(fp_nx_cells, 1 << 20)));
+    fp.ny_cells = static_cast<int32_t>(std::max<int64_t>(-1, std::min<int64_t>(fp_ny_cells, 1 << 20)));
+    const bool sized = fp.nx_cells >= 1 && fp.nx_cells <= 4096 && fp.ny_cells >= 1 && fp.ny_cells <= 4096;
+    TORCH_CHECK(map.scalar_type() == at::kLong, "wgrt.paths_footprint: map must be int64");
+    TORCH_CHECK(!sized || num_lmd < 1 ||
+                    (map.is_contiguous() && map.dim() == 4 && map.size(0) == num_lmd &&
+                     map.size(1) == WGRT_FOOTPRINT_CHANNELS && map.size(2) == fp.ny_cells && map.size(3) == fp.nx_cells),
+                "wgrt.paths_footprint: map must be contiguous [", num_lmd, ", ", WGRT_FOOTPRINT_CHANNELS, ", ", fp.ny_cells,
+                ", ", fp.nx_cells, "], got ", map.sizes());
+    const c10::DeviceGuard guard(paths.device());
+    return paths_abi().footprint(static_cast<const wgrt_path_vertex *>(paths.const_data_ptr()), n,
+                                 static_cast<int32_t>(std::max<int64_t>(-1, std::min<int64_t>(num_lmd, 1 << 20))), &fp,
+                                 static_cast<int64_t *>(map.data_ptr()), reinterpret_cast<void *>(static_cast<uintptr_t>(stream)));
+}
+
 // chain_begin: trace_windows' arguments -> the chain's handle (a user-space address: positive), or the negated
 // wgrt_status of a failure (wgrt_last_error has the detail).  The
 // Python layer keeps every tensor alive until chain_end (engine.TraceChain).
@@ -480,6 +550,19 @@ TORCH_LIBRARY(wgrt, m) {
           "int workgroups, Tensor? chunk_order, int num_iter, Tensor? gid_blocks, int gid_block_rays, int debug, "
           "float grid_sqrt_k, int plan, Tensor(e!)? table, Tensor(f!) hits, int capacity, Tensor(g!)? count, int tag) -> int",
           &trace_hits);
+    // the same launch appending one record per draw of the selected rays to a path list (wgrt_trace_paths): paths uint8,
+    // 32 bytes per record, capacity in records; count int64[1], added to; select uint8 [n_rays] or None (every ray)
+    m.def("trace_paths(int scene, Tensor x, Tensor y, Tensor m, Tensor n, Tensor? lmd_num, Tensor te, Tensor tm, "
+          "Tensor delta_phase, Tensor(a!) rng_states, Tensor(b!)? matrix_EB, Tensor(c!)? stats, "
+          "Tensor(d!)? per_ray_bounces, int n_rays, int gid_offset, int stream, int kernel, int variant, "
+          "int workgroups, Tensor? chunk_order, int num_iter, Tensor? gid_blocks, int gid_block_rays, int debug, "
+          "float grid_sqrt_k, int plan, Tensor(e!)? table, Tensor(f!) paths, int capacity, Tensor(g!)? count, int tag, "
+          "Tensor? select) -> int",
+          &trace_paths);
+    // a path list's first n records added into a footprint map (wgrt_paths_footprint)
+    m.def("paths_footprint(Tensor paths, int n, int num_lmd, float fp_x0, float fp_y0, float fp_cell_x, float fp_cell_y, "
+          "int fp_nx_cells, int fp_ny_cells, Tensor(a!) map, int stream) -> int",
+          &paths_footprint);
     m.def("chain_step(int chain) -> int", &chain_step);
     m.def("chain_end(int chain) -> int", &chain_end);
 }

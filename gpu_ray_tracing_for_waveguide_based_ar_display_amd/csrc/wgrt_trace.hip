@@ -36,6 +36,7 @@
 #include "../../include/wgrt_debug.h"
 #include "wgrt_common.h"
 #include "wgrt_exact_lane.h"
+#include "wgrt_footprint_cache.h"
 #include "wgrt_items.h"
 #include "wgrt_jones_lane.h"
 #include "wgrt_launch_args.h"
@@ -83,6 +84,14 @@ __global__ __launch_bounds__(256) void trace_grid_hits_kernel(TraceArgs A) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     Counters c;
     if (i < A.n_rays) trace_one<false, false, false, true>(A, i, c);
+    add_stats(A.stats, c);
+}
+
+// The same appending every draw of the selected rays to the path list (wgrt_trace_paths with variant 1; wgrt_paths.h).
+__global__ __launch_bounds__(256) void trace_grid_paths_kernel(TraceArgs A) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    Counters c;
+    if (i < A.n_rays) trace_one<false, false, false, false, true>(A, i, c);
     add_stats(A.stats, c);
 }
 
@@ -286,12 +295,14 @@ __device__ __host__ __forceinline__ uint32_t chain_tag(uint32_t serial, bool bro
 //        list -- and nothing is allocated for them;
 //   kFp  the draws counted into the map.  A footprint launch does use the out-coupling queue, so the counts have a
 //        word of their own per replay-list entry (TraceArgs::fp_seen, part of the stream's launch scratch);
+//   kPaths  the draws recorded in the path list (or passed by, for a ray the launch does not record), in the
+//        footprint launch's word: the replay passes over them and numbers its records on from there;
 //   every other mode has written nothing of an abandoned ray, and keeps no count.
 template <TraceMode M>
-constexpr bool kSeenCounted = M == TraceMode::kEv || M == TraceMode::kFp;
+constexpr bool kSeenCounted = M == TraceMode::kEv || M == TraceMode::kFp || M == TraceMode::kPaths;
 template <TraceMode M>
 __device__ __forceinline__ uint32_t *seen_counts(const KArgs &K) {
-    static_assert(kSeenCounted<M>, "only the expected-value and footprint launches count what the replay passes over");
+    static_assert(kSeenCounted<M>, "only the expected-value, footprint and paths launches count what the replay passes over");
     if constexpr (M == TraceMode::kEv) return KA(q_i);
     else return KA(fp_seen);
 }
@@ -339,7 +350,8 @@ __device__ __forceinline__ void replay_tail(const KArgs &K, unsigned long long n
             uint32_t skip = 0;   // what the Jones lane counted before it abandoned the ray (record_abandoned)
             if constexpr (kSeenCounted<M>)
                 skip = __hip_atomic_load(seen_counts<M>(K) + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            trace_one<M == TraceMode::kFate, M == TraceMode::kEv, M == TraceMode::kFp, M == TraceMode::kHits>(
+            trace_one<M == TraceMode::kFate, M == TraceMode::kEv, M == TraceMode::kFp, M == TraceMode::kHits,
+                      M == TraceMode::kPaths>(
                 R, (int64_t)__hip_atomic_load(list + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), c, nullptr, skip);
         }
     }
@@ -453,56 +465,20 @@ struct EvBlock {
     double x[kEvBlock], y[kEvBlock], q[kEvBlock];
     uint32_t e[kEvBlock];
 };
+// PATHS: a single launch that keeps every draw of the selected rays as a record of the caller's path list
+// (wgrt_trace_paths; wgrt_paths.h).  A lane reads its ray's select byte when it takes the ray, records a draw once its
+// decision is certified (as FP counts it), and records the end of a trace that advance() ends with reason 1 or 5 at
+// the retire site, where the fate code rides in a register (the FATE forms of interact and advance, as FP).  A pass
+// makes at most one record per lane, and a returning atomic per pass on the list's one counter would put its latency
+// on every pass: the wave stages its records in LDS, kPathBlock of them (2 KB per wave), and when the block cannot
+// take a pass's records lane 0 reserves the block's indices with one returning add and the lanes store one record
+// each (two 16-byte stores, below the capacity only); what is left goes out when the wave ends.  An abandoned ray
+// hands the replay its count of recorded draws (record_abandoned), and has not retired here, so its end record is the
+// replay's.  Off everywhere else, where none of this exists.
+constexpr int kPathBlock = 64;   // records a wave stages before it reserves their indices: a pass adds at most one per lane
 // FP: a footprint launch (wgrt_trace_footprint; wgrt_footprint.h) counts every certified draw of the bounce loop into
-// the int64 plate map.  One 8-byte atomic per count is one 64-B request at the memory side, and a launch of them runs
-// at the chip's atomic request rate whatever else it does (DESIGN.md §4.7 has the figures), so the counts are summed
-// on chip first: every wave keeps a direct-mapped cache of kFpSlots counters in LDS, an entry (offset + 1) << 20 |
-// count.  A count whose entry is cached is one LDS add; one whose slot holds another entry (or none) swaps its own
-// entry in with count 1 and adds what it swapped out to the map with one global atomic; the wave adds what its cache
-// still holds when it ends.  (What it merges depends on the map: everything on a coarse one; at 256 x 256 cells a
-// wave's counts rarely meet again, and the gain measured there is smaller: DESIGN.md §4.7.)  The cache is
-// the wave's own -- no other wave touches it, and a wave's LDS operations execute in order -- so a lane's read, the
-// matching lanes' adds and then the other lanes' swaps need no lock: whatever a swap takes out, adds included, goes
-// to the map exactly once.  (A workgroup-wide cache would merge four times as many counts but needs a
-// compare-and-swap loop per count, which the in-coupler's few cells would serialise.)
-// Without the cache (wgrt_debug_set_footprint_aggregate(0)): one global atomic per count.
-constexpr int kFpSlots = 512;             // per wave: 4 KB of LDS
-constexpr int kFpCountBits = 20;          // an entry's count stays below 2^20: a fuller one is swapped out
-typedef unsigned long long __attribute__((address_space(3))) LdsU64;
-static_assert((kFpSlots & (kFpSlots - 1)) == 0 && kFpSlots <= 65536, "fp_slot takes the product's top bits");
-__device__ __forceinline__ int fp_slot(uint64_t key) {
-    return (int)(((uint32_t)key ^ (uint32_t)(key >> 32)) * 2654435761u >> 16) & (kFpSlots - 1);
-}
-// One count at map offset off (< 0: none) through the wave's cache; called by every lane of the wave.
-__device__ __forceinline__ void fp_cached(LdsU64 *tab, int64_t *map, int64_t off) {
-    constexpr uint64_t kCountMask = (1ull << kFpCountBits) - 1ull;
-    const bool todo = off >= 0;
-    const uint64_t key = (uint64_t)off + 1ull;   // (never 0: an empty slot matches nothing)
-    LdsU64 *const e = tab + fp_slot(key);
-    bool hit = false;
-    if (todo) {
-        const uint64_t cur = *e;
-        // (64 lanes may add to one entry in this pass: the count stays within its bits)
-        hit = (cur >> kFpCountBits) == key && (cur & kCountMask) < kCountMask - 64ull;
-    }
-    if (hit) __hip_atomic_fetch_add(e, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    asm volatile("" ::: "memory");   // the adds are issued before the swaps
-    if (todo && !hit) {
-        const uint64_t old = __hip_atomic_exchange(e, (key << kFpCountBits) | 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (old != 0ull)
-            atomicAdd((unsigned long long *)map + ((old >> kFpCountBits) - 1ull), (unsigned long long)(old & kCountMask));
-    }
-    asm volatile("" ::: "memory");
-}
-// What the wave's cache still holds, added to the map: one global atomic per entry.
-__device__ __forceinline__ void fp_flush(LdsU64 *tab, int64_t *map) {
-    constexpr uint64_t kCountMask = (1ull << kFpCountBits) - 1ull;
-    asm volatile("" ::: "memory");
-    for (int k = threadIdx.x & 63; k < kFpSlots; k += 64) {
-        const uint64_t v = tab[k];
-        if (v != 0ull) atomicAdd((unsigned long long *)map + ((v >> kFpCountBits) - 1ull), (unsigned long long)(v & kCountMask));
-    }
-}
+// the int64 plate map through a per-wave counter cache in LDS (fp_cached, fp_flush: wgrt_footprint_cache.h, shared
+// with the reduction of a path list); without it (wgrt_debug_set_footprint_aggregate(0)), one global atomic per count.
 
 template <TraceMode M, bool FUSED, bool SINGLE, bool AMP, class Loc>
 __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, const Loc &loc, unsigned long long *heads,
@@ -510,9 +486,9 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
     // the mode under the names the body tests (at most one of them is set)
     constexpr bool TL = M == TraceMode::kTimeline, LEARN = M == TraceMode::kLearn, CHAIN = M == TraceMode::kChain,
                    FATE = M == TraceMode::kFate, REPS = M == TraceMode::kReps, EV = M == TraceMode::kEv,
-                   FP = M == TraceMode::kFp, HITS = M == TraceMode::kHits;
+                   FP = M == TraceMode::kFp, HITS = M == TraceMode::kHits, PATHS = M == TraceMode::kPaths;
     static_assert(!FUSED || M == TraceMode::kPlain || TL, "only plain and timeline launches are built fused");
-    static_assert(!(FATE || REPS || EV || FP || HITS) || WGRT_INKERNEL_REPLAY,
+    static_assert(!(FATE || REPS || EV || FP || HITS || PATHS) || WGRT_INKERNEL_REPLAY,
                   "the sink modes are single launches whose replay runs in the kernel (replay_tail<M>)");
     // Single launches (!FUSED) do their epilogue in this kernel (above), and retire a finished trace at one
     // place per pass, right after advance(): the rays that ended in the previous pass's interaction (fin)
@@ -571,6 +547,17 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
         fpc = (LdsU64 *)&fp_lds[threadIdx.x >> 6][0];
         for (int k = threadIdx.x & 63; k < kFpSlots; k += 64) fpc[k] = 0ull;
     }
+    // PATHS: this wave's block of staged records (four 64-bit words each) and how many it holds (wave-uniform); the
+    // draws of the trace in flight that this lane has passed (the next record's step), and its ray's wavelength index if
+    // the ray is recorded (-1: it is not), both worked out once, when the lane takes the ray
+    LdsU64 *pthb = nullptr;
+    if constexpr (PATHS) {
+        __shared__ __attribute__((aligned(16))) unsigned long long path_lds[4][4 * kPathBlock];
+        pthb = (LdsU64 *)&path_lds[threadIdx.x >> 6][0];
+    }
+    int pfill = 0;
+    uint32_t p_seen = 0;
+    int p_l = -1;
 
     // head x's items: stripes of kStripe consecutive chunks, stripe s on head s % 8, iteration-
     // major.  Every die gets a mix of all FoVs and wavelengths -- ray lifetimes differ by tile,
@@ -683,6 +670,11 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
         entry = true;
         if (EV) ev_seen = 0;
         if (FP) fp_seen = 0;
+        if constexpr (PATHS) {
+            p_seen = 0;
+            const uint8_t *const sel = KA(select);
+            p_l = (!sel || sel[L.i] != 0) ? (SINGLE ? 0 : (int)(L.tix / (uint32_t)(KA(nx) * KA(ny)))) : -1;
+        }
     };
     // a trace's counters are added when it ends: an abandoned trace (kUncertain) adds nothing, and its
     // replay (replay_kernel or, fused, epilogue_kernel: trace_one) counts the whole trace once
@@ -809,6 +801,46 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
         }
         evfill += nd;
     };
+    // PATHS: the staged block's records into the list, one lane each: lane 0 reserves their indices with one returning
+    // add, and a record whose index is below the capacity is stored as its two halves (LDS is in order within a wave,
+    // as for the EV block) ...
+    auto path_flush = [&]() {
+        asm volatile("" ::: "memory");
+        unsigned long long first = 0;
+        if (lane == 0) first = atomicAdd(KA(paths_count), (unsigned long long)pfill);
+        first = uni64(__shfl(first, 0));
+        if (lane < pfill) {
+            const unsigned long long idx = first + (unsigned long long)lane;
+            if (idx < (unsigned long long)KA(paths_cap)) {
+                ulonglong2 *const dst = (ulonglong2 *)(KA(paths) + idx);
+                dst[0] = ulonglong2{pthb[4 * lane], pthb[4 * lane + 1]};
+                dst[1] = ulonglong2{pthb[4 * lane + 2], pthb[4 * lane + 3]};
+            }
+        }
+        asm volatile("" ::: "memory");
+        pfill = 0;
+    };
+    // ... and this pass's records into the block (has: this lane has one); called by every lane of the wave
+    auto path_push = [&](bool has, double px, double py, int state, int pkind) {
+        const uint64_t pm = __ballot(has);
+        if (pm == 0ull) return;
+        const int np = __popcll(pm);
+        if (pfill + np > kPathBlock) path_flush();
+        if (has) {
+            const int j = pfill + __builtin_amdgcn_mbcnt_hi((uint32_t)(pm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pm, 0));
+            const uint32_t flags = path_flags(state, pkind, p_l, KA(paths_tag));
+            pthb[4 * j] = (unsigned long long)__double_as_longlong(px);
+            pthb[4 * j + 1] = (unsigned long long)__double_as_longlong(py);
+            pthb[4 * j + 2] = (unsigned long long)ray_gid_ka(K, (int64_t)L.i);
+            pthb[4 * j + 3] = (unsigned long long)p_seen | (unsigned long long)flags << 32;
+        }
+        pfill += np;
+    };
+    // ... and the end record of the trace this lane is about to retire (fin), if it has one: the fate register holds
+    // advance()'s code (reason 1, 5 or 7) or, for a trace that ended at a draw, 0; called by every lane
+    auto path_end = [&]() {
+        path_push(fin & (p_l >= 0) & path_end_reason((int)(fate % 10u)), L.r.x, L.r.y, (int)(fate / 10u), (int)(fate % 10u));
+    };
     // the outcome of an interaction (next region, or kDie / kOut / kUncertain): retire bookkeeping
     auto outcome = [&](int next) {
         if (!FUSED) {
@@ -818,7 +850,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             active = next >= 0;
             L.r.region = next >= 0 ? next : L.r.region;
             if (__builtin_expect(next == kUncertain, 0)) {
-                record_abandoned<M>(K, L.i, EV ? ev_seen : FP ? fp_seen : 0u);
+                record_abandoned<M>(K, L.i, EV ? ev_seen : FP ? fp_seen : PATHS ? p_seen : 0u);
             }
         } else {
             // one retire site for both ends of a trace (out-coupled, died)
@@ -856,6 +888,10 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
         // FP: the map entries this pass counts on this lane (< 0: none): the draw's state channel and, for a draw
         // that ends the trace, its lost / eyebox / beside channel
         int64_t fp_a = -1, fp_b = -1;
+        // PATHS: the draw this pass certifies on this lane (p_draw), where and in which state the ray stood, and its kind
+        bool p_draw = false;
+        double p_x = 0.0, p_y = 0.0;
+        int p_state = 0, p_kind = kPathDraw;
         if (active && blk >= 0) {
             L.inter += entry ? 0u : 1u;
             if (EV) evx = L.r.x, evy = L.r.y;
@@ -864,8 +900,19 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             const double fpx = L.r.x, fpy = L.r.y;
             const int fpreg = L.r.region;
             const int next =
-                interact<SINGLE, AMP, FATE || FP, EV>(A, K, loc, L, blk, kind, entry, sg, EV ? &evq : nullptr);
+                interact<SINGLE, AMP, FATE || FP || PATHS, EV>(A, K, loc, L, blk, kind, entry, sg, EV ? &evq : nullptr);
             out = next == kOut;
+            if constexpr (PATHS) {
+                // recorded once the decision is certified, as FP counts: the draw that abandons the ray is the replay's
+                p_draw = !entry && next != kUncertain;
+                p_x = fpx, p_y = fpy;
+                p_state = fpreg;
+                if (next == kDie) p_kind = kFateLost;
+                if (out)
+                    p_kind = eyebox_inside(KA(tiles) + (int64_t)L.tix * KA(tile_d), fpx, fpy) ? kFateEyebox : kFateBeside;
+                // (a trace that ended here has no end record: path_end reads advance()'s code, or none)
+                if (next < 0 && next != kUncertain) fate = 0;
+            }
             if constexpr (FP) {
                 // counted once the decision is certified, as ev_seen: the draw that abandons the ray is the replay's
                 if (!entry && next != kUncertain) {
@@ -910,13 +957,17 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
                 footprint_add(A.fp_map, fp_b, false);
             }
         }
+        if constexpr (PATHS) {   // every lane of the wave is here
+            path_push(p_draw & (p_l >= 0), p_x, p_y, p_state, p_kind);
+            p_seen += p_draw ? 1u : 0u;
+        }
         SEG_MARK(sg, 6);
     };
 
     for (;;) {
         __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
         if (active) {
-            blk = advance<FATE>(A, K, loc, L, kind, &fate);
+            blk = advance<FATE || PATHS>(A, K, loc, L, kind, &fate);
             entry = false;
             if (!FUSED) fin |= blk == kDie;
             else if (blk == kDie) {
@@ -943,6 +994,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             kind = 0;
             entry = true;
         }
+        if constexpr (PATHS) path_end();   // (every lane of the wave; before the retire, which frees the lane)
         if (!FUSED && fin) {   // before the refill, which reuses the lane
             retire();
             fin = false;
@@ -1129,11 +1181,12 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             }
 #endif
             if (!first && active) {
-                blk = advance<FATE>(A, K, loc, L, kind, &fate);
+                blk = advance<FATE || PATHS>(A, K, loc, L, kind, &fate);
                 entry = false;
                 fin |= blk == kDie;
             }
             SEG_MARK_DEP(sg, 0, (double)blk + L.r.x);
+            if constexpr (PATHS) path_end();
             if (fin) {
                 retire();
                 fin = false;
@@ -1193,6 +1246,8 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
         tot_h = ev_hits;
     }
     if constexpr (FP) fp_flush(fpc, A.fp_map);   // (empty with the switch off)
+    if constexpr (PATHS)
+        if (pfill) path_flush();   // (wave-uniform)
     if (qblk) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if constexpr (HITS) bin_hits(qbase, qfill);
@@ -1409,6 +1464,7 @@ struct JonesKernels {
         add_single_amp<TraceMode::kEv, false>();
         add_single_amp<TraceMode::kFp, false>();
         add_single_amp<TraceMode::kHits, false>();
+        add_single_amp<TraceMode::kPaths, false>();
     }
 };
 const void *jones_kernel(TraceMode m, bool byte, bool wide, bool fused, bool single, bool amp) {
@@ -1444,7 +1500,7 @@ wgrt_status query_trace_grids(wgrt_scene *s) {
                         // the sinks: never more workgroups than the plain launch of the same kind gets
                         const TraceMode mode = (TraceMode)m;
                         if (grid && (mode == TraceMode::kFate || mode == TraceMode::kReps || mode == TraceMode::kEv ||
-                                     mode == TraceMode::kFp || mode == TraceMode::kHits))
+                                     mode == TraceMode::kFp || mode == TraceMode::kHits || mode == TraceMode::kPaths))
                             grid = std::min(grid, s->jones_grid[(int)TraceMode::kPlain][b][c][f][g]);
                         s->jones_grid[m][b][c][f][g] = grid;
                     }
@@ -1648,6 +1704,15 @@ struct LaunchCfg {
     int64_t hits_cap = 0;
     unsigned long long *hits_count = nullptr;
     uint32_t hits_tag = 0;
+    // wgrt_trace_paths: the list every draw of a selected ray is appended to, its capacity, its device counter, the
+    // call's tag and the batch's select bytes (paths NULL: none; select NULL: every ray).  A paths launch follows the
+    // hits launch's rules, and is not combined with fates, replicas, the expected-value estimator, footprints or hit
+    // lists.
+    wgrt_path_vertex *paths = nullptr;
+    int64_t paths_cap = 0;
+    unsigned long long *paths_count = nullptr;
+    uint32_t paths_tag = 0;
+    const uint8_t *select = nullptr;
     // set by validate_launch: the launch runs the byte-locator instantiation (byte_locator_applies)
     bool byte = false;
 };
@@ -1664,6 +1729,7 @@ TraceMode launch_mode(const LaunchCfg &c, bool timeline) {
            : c.mode == TraceMode::kEv    ? TraceMode::kEv
            : c.fp_map                    ? TraceMode::kFp
            : c.hits                      ? TraceMode::kHits
+           : c.paths                     ? TraceMode::kPaths
            : c.replicas                  ? TraceMode::kReps
            : c.mode == TraceMode::kLearn ? TraceMode::kLearn
                                          : TraceMode::kPlain;
@@ -1679,6 +1745,12 @@ bool byte_locator_applies(const wgrt_scene *s, int variant) {
 
 // wgrt_debug_set_footprint_aggregate: the footprint sink's on-chip summing on / off, process-wide (the same-binary A/B).
 std::atomic<int> g_fp_aggregate{1};
+}  // namespace
+namespace wgrt {
+// (wgrt_paths.hip reads the switch too: the merge form of a path list's reduction)
+int footprint_aggregate_on() { return g_fp_aggregate.load(std::memory_order_relaxed); }
+}  // namespace wgrt
+namespace {
 
 // wgrt_debug_set_fused_run: the run length of fused launches, process-wide (the same-binary A/B; 0: the rule below).
 std::atomic<int> g_fused_run{0};
@@ -1824,6 +1896,21 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
             return fail(WGRT_ERR_INVALID_ARGUMENT, "a hits launch takes no fates, replicas, expected-value estimator or "
                                                    "footprint map");
     }
+    if (c.paths) {
+        if (!c.paths_count) return fail(WGRT_ERR_INVALID_ARGUMENT, "a path list needs its device counter");
+        if (c.paths_cap < 0) return fail(WGRT_ERR_INVALID_ARGUMENT, "the path list's capacity must be >= 0");
+        if (c.paths_tag > kPathMaxTag) return fail(WGRT_ERR_INVALID_ARGUMENT, "the path list's tag must be <= 65535");
+        if (((uintptr_t)c.paths & 15) || ((uintptr_t)c.paths_count & 7))
+            return fail(WGRT_ERR_INVALID_ARGUMENT, "the path list must be 16-B aligned (and its counter 8-B)");
+        if (s->nl > kPathMaxLmd)
+            return fail(WGRT_ERR_INVALID_ARGUMENT, "a path record names at most 256 wavelengths: the scene has more");
+        if (c.num_iter > 1)
+            return fail(WGRT_ERR_INVALID_ARGUMENT, "num_iter > 1 takes no path list: the lists are filled by single "
+                                                   "launches (trace the iterations one call each)");
+        if (c.fate || c.replicas || expected || c.fp_map || c.hits)
+            return fail(WGRT_ERR_INVALID_ARGUMENT, "a paths launch takes no fates, replicas, expected-value estimator, "
+                                                   "footprint map or hit list");
+    }
     if (c.chunk_order && c.variant == 1)
         return fail(WGRT_ERR_INVALID_ARGUMENT, "chunk_order needs variant 0, 7 or 9");
     if (c.gid_blocks && (c.gid_block_rays < 1 || gid_offset != 0))
@@ -1860,6 +1947,9 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
     if (timeline && c.hits)
         return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel keeps no hit list: trace with a hit list or with the "
                                           "timeline");
+    if (timeline && c.paths)
+        return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel keeps no path list: trace with a path list or with "
+                                          "the timeline");
     if ((c.replicas || expected) && c.variant != 1 && (int64_t)s->nl * s->nx * s->ny >= (int64_t)1 << kRepShift)
         return fail(WGRT_ERR_UNSUPPORTED, "replica tables with variants 7 / 9 need a scene of fewer than 2^24 tiles (the "
                                           "out-coupling queue entry carries the replica above the tile index)");
@@ -1894,6 +1984,11 @@ TraceArgs fill_args(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, 
     A.hits_cap = c.hits_cap;
     A.hits_count = c.hits_count;
     A.hits_tag = c.hits_tag;
+    A.paths = c.paths;
+    A.paths_cap = c.paths_cap;
+    A.paths_count = c.paths_count;
+    A.paths_tag = c.paths_tag;
+    A.select = c.select;
     A.n_rays = n_rays;
     A.gid_offset = gid_offset;
     A.gid_blocks = c.gid_blocks;
@@ -1949,6 +2044,7 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
         case TraceMode::kFp: hipLaunchKernelGGL(trace_grid_fp_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A); break;
         case TraceMode::kFate: hipLaunchKernelGGL(trace_grid_fate_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A); break;
         case TraceMode::kHits: hipLaunchKernelGGL(trace_grid_hits_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A); break;
+        case TraceMode::kPaths: hipLaunchKernelGGL(trace_grid_paths_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A); break;
         default: hipLaunchKernelGGL(trace_grid_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
         }
         HIP_TRY(hipGetLastError());
@@ -2504,6 +2600,27 @@ wgrt_status wgrt_trace_hits(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
 }
 
 int32_t wgrt_hit_bytes(void) { return (int32_t)sizeof(wgrt_hit); }
+
+wgrt_status wgrt_trace_paths(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
+                             uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats, uint32_t *per_ray_bounces,
+                             void *stream, const wgrt_launch_opts *opts, const wgrt_window_plan *plan, double *table,
+                             wgrt_path_vertex *paths, int64_t capacity, uint64_t *count, uint32_t tag,
+                             const uint8_t *select) {
+    if (!paths)   // no list: exactly that call
+        return wgrt_trace_windows(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, opts,
+                                  plan, table);
+    LaunchCfg c;
+    const wgrt_status e = cfg_of_opts(s, opts, plan, table, c);
+    if (e != WGRT_OK) return e;
+    c.paths = paths;
+    c.paths_cap = capacity;
+    c.paths_count = (unsigned long long *)count;
+    c.paths_tag = tag;
+    c.select = select;
+    return trace_launch(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, c);
+}
+
+int32_t wgrt_path_vertex_bytes(void) { return (int32_t)sizeof(wgrt_path_vertex); }
 
 wgrt_status wgrt_debug_set_footprint_aggregate(int on) {
     g_fp_aggregate.store(on != 0, std::memory_order_relaxed);

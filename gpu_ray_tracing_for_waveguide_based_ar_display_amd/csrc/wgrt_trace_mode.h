@@ -16,6 +16,7 @@ enum class TraceMode : int {
     kEv,         // the expected-value estimator (wgrt_trace_expected)
     kFp,         // counts every draw into the footprint maps (wgrt_trace_footprint)
     kHits,       // appends one record per out-coupling to the hit list (wgrt_trace_hits)
+    kPaths,      // appends one record per draw of the selected rays to the path list (wgrt_trace_paths)
     kCount
 };
 constexpr int kTraceModes = (int)TraceMode::kCount;

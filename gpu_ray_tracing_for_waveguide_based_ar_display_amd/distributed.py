@@ -487,7 +487,7 @@ def timed_run(trace_fn, rays, rng, eb, gid: GidMap, steps: int, per_call: int, s
 
 
 def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, replicas: int = 0,
-               expected: bool = False, footprint=None, hits=None):
+               expected: bool = False, footprint=None, hits=None, paths=None):
     """trace_fn for ``run_steps`` / ``trace_job`` using the HIP kernel (torch device tensors); ``stats``
     (int64[STATS_LEN] device tensor) is added to by every call.  A shard of several block ranges passes its global
     ids as ``gid_blocks``, uploaded once per map and device and kept on the map (``GidMap.device_blocks``).
@@ -520,9 +520,38 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, rep
     ``hits``: an ``engine.HitList``: every call also appends its out-couplings to the list
     (``engine.trace_fullcolor(hits=...)``), tagged with the number of calls made before it (the iteration, for the
     single launches this takes): single launches only and no ``chain`` again.  The records' ids are global, so the
-    ranks' lists concatenate."""
-    from .engine import TraceChain, trace_fullcolor
+    ranks' lists concatenate.
+
+    ``paths``: a record with ``list`` (an ``engine.PathList``), ``classes`` (fate class names or codes, or None for every
+    ray), ``selected`` (int64 ``[num_lmd]`` device tensor, added to: the rays recorded per wavelength) and, for a class
+    selection, ``fate`` (uint8 per ray), ``windows`` (a scratch plan and table) and optionally ``bounces`` (int32 per ray:
+    the first pass then stores its per-ray bounces there, and the list is grown before the paths launch to hold
+    ``bounces + 1`` records of every selected ray, so that it cannot overflow): every call records the draws of the
+    selected rays in the list (``engine.trace_fullcolor(paths=..., select=...)``), tagged like ``hits``.  For a class
+    selection the call first runs a fate launch with no grid on a clone of the RNG states into the scratch table,
+    builds the mask from its fates (``engine.select_by_fate``), and then runs the paths launch from the original
+    states.  Single launches only and no ``chain`` again; the ids are global, so the ranks' lists concatenate."""
+    from .engine import TraceChain, select_by_fate, trace_fullcolor
     calls = [0]
+
+    def select_for(rays, rng, gid):
+        """The paths launch's mask (None: every ray), the rays it names counted per wavelength."""
+        import torch
+        lmd = rays["lmd_num"].long()
+        if paths.classes is None:
+            paths.selected += torch.bincount(lmd, minlength=paths.selected.numel())
+            return None
+        bounces = getattr(paths, "bounces", None)
+        trace_fullcolor(scene, rays, rng.clone(), None, variant=variant, windows=paths.windows, fate=paths.fate,
+                        per_ray_bounces=bounces, **ids_of(rng, gid))
+        mask = select_by_fate(paths.fate, paths.classes)
+        paths.selected += torch.bincount(lmd[mask != 0], minlength=paths.selected.numel())
+        if bounces is not None:
+            # the list sized from the first pass: a draw is made in a loop iteration, and every iteration counts a
+            # bounce, so a selected ray leaves at most its bounces + 1 records (the end record).  Synchronises.
+            need = int((bounces[mask != 0].long() + 1).sum().item())
+            paths.list.reserve(paths.list.count() + need)
+        return mask
 
     def ids_of(rng, gid: GidMap):
         off = gid.offset
@@ -530,9 +559,10 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, rep
                                                                  gid_block_rays=gid.rays_per_block)
 
     def fn(rays, rng, eb, gid: GidMap, num_iter=1):
+        more = {} if paths is None else dict(paths=(paths.list, calls[0]), select=select_for(rays, rng, gid))
         trace_fullcolor(scene, rays, rng, eb, stats=stats, variant=variant, num_iter=num_iter, windows=windows,
                         fate=fate, replicas=replicas, expected=expected, footprint=footprint,
-                        hits=None if hits is None else (hits, calls[0]), **ids_of(rng, gid))
+                        hits=None if hits is None else (hits, calls[0]), **more, **ids_of(rng, gid))
         calls[0] += 1
 
     def chain(rays, rng, eb, gid: GidMap):
@@ -541,7 +571,7 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, rep
         from ._lib import load
         return TraceChain(scene, rays, rng, eb, stats=stats, variant=variant, windows=windows,
                           gather=hasattr(load(), "wgrt_chain_gather"), **ids_of(rng, gid))
-    if fate is None and int(replicas or 0) < 2 and not expected and footprint is None and hits is None:
+    if fate is None and int(replicas or 0) < 2 and not expected and footprint is None and hits is None and paths is None:
         fn.chain = chain
     return fn
 

@@ -54,7 +54,7 @@ def trace_fullcolor(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_E
                     workgroups: int = 0, chunk_order: torch.Tensor | None = None, num_iter: int = 1,
                     gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
                     grid_sqrt_k: float = 0.0, windows=None, fate: torch.Tensor | None = None, replicas: int = 0,
-                    expected: bool = False, footprint=None, hits=None) -> None:
+                    expected: bool = False, footprint=None, hits=None, paths=None, select=None) -> None:
     """Asynchronous launch on ``stream`` (default: torch's current stream).
 
     rays: dict of device float32 tensors keyed like the reference columns
@@ -96,13 +96,19 @@ def trace_fullcolor(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_E
     0 .. 65535 (``wgrt_trace_hits``): every out-coupling of the launch, inside its eyebox rectangle or beside it, is
     appended to the list as one record tagged ``tag``; nothing else the launch leaves changes.  Single launches only;
     ``fate``, ``replicas``, ``expected``, ``footprint``, ``num_iter > 1`` and a ``TraceChain`` raise ``ValueError``.
+    paths: ``(path_list, tag)``, a ``PathList`` on the scene's device and a tag 0 .. 65535 (``wgrt_trace_paths``): every
+    draw of the bounce loop of the rays ``select`` names -- a uint8 / bool device tensor ``[n_rays]``, nonzero: record
+    the ray; None: every ray (``select_by_fate`` builds one from a fate launch of the same RNG states) -- is appended
+    as one record, and the end of a trace that leaves the plate or misses in R5 as one more; nothing else the launch
+    leaves changes.  Single launches only; ``fate``, ``replicas``, ``expected``, ``footprint``, ``hits``,
+    ``num_iter > 1`` and a ``TraceChain`` raise ``ValueError``.
     """
     if scene.single_lambda:
         raise ValueError("trace_fullcolor needs a full-colour scene; use trace_single for a single-wavelength one")
     _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single=False, chunk_order=chunk_order, num_iter=num_iter, gid_blocks=gid_blocks,
            gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows, fate=fate,
-           replicas=replicas, expected=expected, footprint=footprint, hits=hits)
+           replicas=replicas, expected=expected, footprint=footprint, hits=hits, paths=paths, select=select)
 
 
 def new_stats(device) -> torch.Tensor:
@@ -146,18 +152,18 @@ def trace_single(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_EB: 
                  workgroups: int = 0, chunk_order: torch.Tensor | None = None, num_iter: int = 1,
                  gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
                  grid_sqrt_k: float = 0.0, windows=None, fate: torch.Tensor | None = None, replicas: int = 0,
-                 expected: bool = False, footprint=None, hits=None) -> None:
+                 expected: bool = False, footprint=None, hits=None, paths=None, select=None) -> None:
     """One launch of the single-wavelength kernel (``process_rays_kernel_pro``, GRTF:419-831)
     through ``wgrt_trace_single_ex``: no ``lmd_num`` column (ignored if present),
     matrix_EB [NY, NX, 80, 120], branch guard ener * efficiency > 1e-15.  The scene must be
     a single-wavelength one (``Scene.from_geometry(..., wavelength=l)`` or 3-D LUTs).  ``windows``, ``fate``,
-    ``replicas``, ``expected``, ``footprint``, ``hits``: as ``trace_fullcolor``."""
+    ``replicas``, ``expected``, ``footprint``, ``hits``, ``paths``, ``select``: as ``trace_fullcolor``."""
     if not scene.single_lambda:
         raise ValueError("trace_single needs a single-wavelength scene (Scene.from_geometry(..., wavelength=l))")
     _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single=True, chunk_order=chunk_order, num_iter=num_iter, gid_blocks=gid_blocks,
            gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows, fate=fate,
-           replicas=replicas, expected=expected, footprint=footprint, hits=hits)
+           replicas=replicas, expected=expected, footprint=footprint, hits=hits, paths=paths, select=select)
 
 
 MAX_REPLICAS = 64   # WGRT_MAX_REPLICAS (include/wgrt.h)
@@ -414,6 +420,153 @@ def hits_grid_host(records, nx: int, ny: int, num_lmd: int, scene_ranges, H: int
     return out
 
 
+PATH_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("gid", "<i8"), ("step", "<u4"), ("flags", "<u4")])   # wgrt_path_vertex
+PATH_MAX_TAG = 65535
+PATH_KINDS = {0: "draw", 1: "end_left_plate", 2: "draw_lost", 3: "draw_eyebox", 4: "draw_beside_eyebox", 5: "end_oc_miss"}
+
+
+class PathListOverflow(WgrtError):
+    """A path list counted more records than it has room for (``check_paths``)."""
+
+
+def path_state(records) -> np.ndarray:
+    """Per record: the state R0..R5 the ray is in (flag bits 0..2; 4 after the R3 -> R4 switch)."""
+    return (records["flags"] & 7).astype(np.int64)
+
+
+def path_kind(records) -> np.ndarray:
+    """Per record: its kind (flag bits 4..7; ``PATH_KINDS``): 0 / 2 / 3 / 4 a draw, 1 / 5 an end record."""
+    return (records["flags"] >> 4 & 15).astype(np.int64)
+
+
+def path_lmd(records) -> np.ndarray:
+    """Per record: the wavelength index of its ray (flag bits 8..15)."""
+    return (records["flags"] >> 8 & 255).astype(np.int64)
+
+
+def path_tag(records) -> np.ndarray:
+    """Per record: the tag of the call that appended it (flag bits 16..31)."""
+    return (records["flags"] >> 16).astype(np.int64)
+
+
+def sort_paths(records) -> np.ndarray:
+    """The records sorted by ``(tag, gid, step)``, which is unique per record."""
+    return records[np.lexsort((records["step"], records["gid"], path_tag(records)))]
+
+
+def path_polylines(records) -> dict:
+    """``{tag: {gid: float64 [k, 2]}}``: every ray's records in step order as the points of its polyline after the
+    start point (the draws' positions, then the end record's if the trace has one)."""
+    rec = sort_paths(np.asarray(records, dtype=PATH_DTYPE))
+    out: dict = {}
+    if not len(rec):
+        return out
+    tag = path_tag(rec)
+    first = np.flatnonzero(np.r_[True, (tag[1:] != tag[:-1]) | (rec["gid"][1:] != rec["gid"][:-1])])
+    xy = np.stack([rec["x"], rec["y"]], axis=1)
+    for a, b in zip(first, np.r_[first[1:], len(rec)]):
+        out.setdefault(int(tag[a]), {})[int(rec["gid"][a])] = xy[a:b].copy()
+    return out
+
+
+class PathList:
+    """A path list (``wgrt_path_vertex`` records; ``trace_*(paths=(path_list, tag), select=mask)``), the twin of
+    ``HitList``: the record buffer, a uint8 ``[capacity, 32]`` device tensor, and the device counter the launches add
+    to.  ``count()`` is the number of records so far (stored or not), ``stored()`` is ``min(count, capacity)``; both
+    synchronise.  ``records()`` is the stored records as a numpy structured array (``PATH_DTYPE``: ``x, y, gid, step,
+    flags``) sorted by ``(tag, gid, step)``; ``path_state``, ``path_kind``, ``path_lmd`` and ``path_tag`` decode them.
+    ``footprint(scene, fp, out=None)`` adds the stored records on the device into an int64 footprint map of plan
+    ``fp`` (``wgrt_paths_footprint``): of launches with ``select=None``, ``trace_*(footprint=...)``'s map of the same
+    launches bit for bit; of a fate-selected list, the footprint of those rays alone.  ``polylines()``:
+    ``path_polylines`` of the stored records.  ``clear()`` zeroes the counter; ``reserve(capacity)`` grows the buffer,
+    keeping the stored records (a ray leaves at most its bounces + 1 records: a first pass's ``per_ray_bounces`` bound
+    the room a selection needs)."""
+
+    def __init__(self, capacity: int, device=0):
+        self.capacity = int(capacity)
+        if self.capacity < 0:
+            raise ValueError("capacity must be >= 0")
+        if int(load().wgrt_path_vertex_bytes()) != PATH_DTYPE.itemsize:
+            raise WgrtError("the library's wgrt_path_vertex is not 32 bytes")
+        self.device = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
+        self.buffer = torch.zeros((self.capacity, PATH_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+        self.counter = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def clear(self) -> None:
+        self.counter.zero_()
+
+    def reserve(self, capacity: int) -> None:
+        """Room for at least ``capacity`` records: a larger buffer takes the stored records' place, in their order (the
+        counter is the same tensor as before).  Nothing happens when the list is large enough.  Synchronises."""
+        capacity = int(capacity)
+        if capacity <= self.capacity:
+            return
+        n = self.stored()
+        buffer = torch.zeros((capacity, PATH_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+        buffer[:n] = self.buffer[:n]
+        self.buffer, self.capacity = buffer, capacity
+
+    def count(self) -> int:
+        return int(self.counter.cpu()[0])
+
+    def stored(self) -> int:
+        return min(self.count(), self.capacity)
+
+    def raw(self) -> np.ndarray:
+        """The stored records in the buffer's order."""
+        n = self.stored()
+        return self.buffer[:n].cpu().numpy().reshape(-1).view(PATH_DTYPE).copy()
+
+    def records(self) -> np.ndarray:
+        return sort_paths(self.raw())
+
+    def polylines(self) -> dict:
+        return path_polylines(self.raw())
+
+    def footprint(self, scene: Scene, fp: FootprintPlan, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        if torch.device("cuda", scene.device) != self.device:
+            raise ValueError(f"the path list is on {self.device}, the scene on device {scene.device}")
+        if not isinstance(fp, FootprintPlan):
+            raise TypeError("footprint(scene, FootprintPlan)")
+        if out is None:
+            out = fp.new_map(scene)
+        else:
+            _as_dev(out, torch.int64, "map", self.device)
+            if tuple(out.shape) != fp.map_shape(scene):
+                raise ValueError(f"map shape {tuple(out.shape)} != {fp.map_shape(scene)}")
+        check(ops().paths_footprint(self.buffer, self.stored(), int(scene.num_lmd), fp.x0, fp.y0, fp.cell_x, fp.cell_y,
+                                    fp.nx_cells, fp.ny_cells, out, _stream_handle(self.device, stream)),
+              "wgrt_paths_footprint")
+        return out
+
+
+def check_paths(path_list: PathList) -> None:
+    """Raise ``PathListOverflow`` if the list counted more records than it stores.  Synchronises."""
+    n = path_list.count()
+    if n > path_list.capacity:
+        raise PathListOverflow(f"the path list counted {n} records but has room for {path_list.capacity}: "
+                               f"a capacity of {n} would have sufficed")
+
+
+def paths_footprint_host(records, fp: FootprintPlan, num_lmd: int, out=None) -> np.ndarray:
+    """``PathList.footprint`` on the host (``wgrt_paths_footprint_host``; numpy arrays, no GPU needed) through the same
+    rule: ``records`` a ``PATH_DTYPE`` array.  Adds into ``out`` (C-contiguous int64 ``[num_lmd, 9, ny_cells,
+    nx_cells]``) when given."""
+    rec = np.ascontiguousarray(records, dtype=PATH_DTYPE)
+    if rec.ndim != 1:
+        raise ValueError("records must be a 1-D PATH_DTYPE array")
+    if not 1 <= int(num_lmd) <= 256:
+        raise ValueError("num_lmd must be 1 .. 256")
+    shape = (int(num_lmd), len(FOOTPRINT_CHANNELS), fp.ny_cells, fp.nx_cells)
+    if out is None:
+        out = np.zeros(shape, dtype=np.int64)
+    elif out.dtype != np.int64 or not out.flags.c_contiguous or out.shape != shape:
+        raise ValueError(f"out must be a C-contiguous int64 array of shape {shape}")
+    check(load().wgrt_paths_footprint_host(rec.ctypes.data, rec.shape[0], int(num_lmd), ctypes.byref(fp.c_plan()),
+                                           out.ctypes.data), "wgrt_paths_footprint_host")
+    return out
+
+
 def _debug_opts(debug: dict | None):
     if not debug:
         return None
@@ -456,9 +609,25 @@ def _read_columns(rays, rng_states, n_rays, single, device):
 def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single, chunk_order=None, num_iter=1, gid_blocks=None, gid_block_rays=0, debug=None,
            grid_sqrt_k=0.0, windows=None, chain=False, fate=None, replicas=0, expected=False, footprint=None,
-           hits=None):
+           hits=None, paths=None, select=None):
     device = torch.device("cuda", scene.device)
     B = _replica_count(replicas)
+    if select is not None and paths is None:
+        raise ValueError("select= chooses the rays of a paths launch: it needs paths=(PathList, tag)")
+    if paths is not None:   # (before anything is read or launched)
+        if fate is not None or B or expected or footprint is not None or hits is not None:
+            raise ValueError("paths= is not combined with fate, replicas, expected, footprint or hits")
+        if int(num_iter) > 1:
+            raise ValueError("paths= needs num_iter == 1: the lists are filled by single launches")
+        if chain:
+            raise ValueError("a chain takes no paths launches")
+        path_list, path_tag_ = paths
+        if not isinstance(path_list, PathList):
+            raise TypeError("paths=(PathList, tag)")
+        if path_list.device != device:
+            raise ValueError(f"the path list is on {path_list.device}, expected {device}")
+        if int(scene.num_lmd) > 256:
+            raise ValueError("a path record names at most 256 wavelengths: the scene has more")
     if hits is not None:   # (before anything is read or launched)
         if fate is not None or B or expected or footprint is not None:
             raise ValueError("hits= is not combined with fate, replicas, expected or footprint")
@@ -535,6 +704,10 @@ def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ra
         if gid_block_rays < 1:
             raise ValueError("gid_blocks needs gid_block_rays >= 1")
         _as_dev(gid_blocks, torch.int64, "gid_blocks", device, (N + gid_block_rays - 1) // gid_block_rays if N else None)
+    if select is not None:
+        if select.dtype == torch.bool:
+            select = select.view(torch.uint8)
+        _as_dev(select, torch.uint8, "select", device, N if N else None)
     dbg = _debug_opts(debug)
     # the launch: torch.ops.wgrt.trace (csrc/wgrt_torch.cpp) -> wgrt_trace_opts on the caller's stream; with a
     # window table torch.ops.wgrt.trace_windows -> wgrt_trace_windows
@@ -553,7 +726,11 @@ def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ra
         if h <= 0:   # the negated wgrt_status of the failure
             check(-h, "wgrt_chain_begin")
         return h, (args, dbg, windows)
-    if hits is not None:   # torch.ops.wgrt.trace_hits -> wgrt_trace_hits
+    if paths is not None:   # torch.ops.wgrt.trace_paths -> wgrt_trace_paths
+        status = ops().trace_paths(*args, plan.handle.value if windows is not None else 0,
+                                   table if windows is not None else None, path_list.buffer, path_list.capacity,
+                                   path_list.counter, int(path_tag_), select)
+    elif hits is not None:   # torch.ops.wgrt.trace_hits -> wgrt_trace_hits
         status = ops().trace_hits(*args, plan.handle.value if windows is not None else 0,
                                   table if windows is not None else None, hit_list.buffer, hit_list.capacity,
                                   hit_list.counter, int(hit_tag))
@@ -607,11 +784,13 @@ class TraceChain:
                  variant: int = VARIANT_AUTO, workgroups: int = 0, chunk_order: torch.Tensor | None = None,
                  gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
                  grid_sqrt_k: float = 0.0, windows=None, replicas: int = 0, expected: bool = False,
-                 gather: bool | int = False, hold: bool = False, footprint=None, hits=None):
+                 gather: bool | int = False, hold: bool = False, footprint=None, hits=None, paths=None, select=None):
         if scene.single_lambda:
             raise ValueError("TraceChain needs a full-colour scene")
         if hits is not None:
             raise ValueError("a chain takes no hits launches: fill a hit list with single launches")
+        if paths is not None or select is not None:
+            raise ValueError("a chain takes no paths launches: fill a path list with single launches")
         if footprint is not None:
             raise ValueError("a chain takes no footprint launches: trace footprint maps with single launches")
         if expected:
@@ -780,6 +959,29 @@ def fate_census_host(fate, m, n, lmd_num, nx: int, ny: int, num_lmd: int, table=
                                   cols[2].ctypes.data if cols[2] is not None else None, fate.shape[0], int(nx), int(ny),
                                   int(num_lmd), table.ctypes.data), "wgrt_fate_census_host")
     return table
+
+
+def select_by_fate(fate: torch.Tensor, classes) -> torch.Tensor:
+    """The ``select`` mask of a paths launch from the fate codes of a fate launch of the same batch and RNG states
+    (``trace_*(fate=...)`` on a clone of the states): a uint8 device tensor, 1 where the ray's fate belongs to one of
+    ``classes`` -- a class name of ``FATE_CLASSES`` (``"eyebox"``, ``"left_plate"``, ``"lost_fc"``, ...), a raw fate code
+    (int), or a list / tuple of either.  The classes are ``loss_budget``'s, from the one table."""
+    if isinstance(classes, (str, int, np.integer)):
+        classes = [classes]
+    by_name = {name: [10 * region + reason for region in regions] for name, reason, regions in FATE_CLASSES}
+    lut = torch.zeros(256, dtype=torch.uint8)
+    for c in classes:
+        if isinstance(c, str):
+            if c not in by_name:
+                raise ValueError(f"{c!r} is not a fate class (one of {', '.join(by_name)})")
+            codes = by_name[c]
+        else:
+            fate_col(int(c))   # (raises for a code no trace can end with)
+            codes = [int(c)]
+        lut[codes] = 1
+    if fate.dtype != torch.uint8:
+        raise TypeError("fate must be a uint8 tensor of fate codes")
+    return lut.to(fate.device)[fate.long()]
 
 
 def loss_budget(census, scene) -> dict:
@@ -984,6 +1186,6 @@ def expected_weight(e1: float, e2: float, e3: float, en1: float, en2: float, en3
     return float(load().wgrt_expected_weight_host(e1, e2, e3, en1, en2, en3, threshold))
 
 
-__all__ = ["Scene", "WindowPlan", "FootprintPlan", "footprint_bin", "FOOTPRINT_CHANNELS", "HitList", "HitListOverflow", "check_hits", "hits_grid_host", "sort_hits", "hit_inside", "hit_tag", "hit_lmn", "HIT_DTYPE", "TraceChain", "fold_replicas", "expected_weight", "MAX_REPLICAS", "fate_census", "fate_census_host", "fate_col", "loss_budget", "FATE_CLASSES", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
+__all__ = ["Scene", "WindowPlan", "FootprintPlan", "footprint_bin", "FOOTPRINT_CHANNELS", "PathList", "PathListOverflow", "check_paths", "paths_footprint_host", "sort_paths", "path_polylines", "path_state", "path_kind", "path_lmd", "path_tag", "PATH_DTYPE", "PATH_KINDS", "select_by_fate", "HitList", "HitListOverflow", "check_hits", "hits_grid_host", "sort_hits", "hit_inside", "hit_tag", "hit_lmn", "HIT_DTYPE", "TraceChain", "fold_replicas", "expected_weight", "MAX_REPLICAS", "fate_census", "fate_census_host", "fate_col", "loss_budget", "FATE_CLASSES", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
            "trace_fullcolor", "trace_single", "init_rays", "schedule_by_lifetime",
            "rays_to_device", "classify_points", "shadow", "selftest_math", "RAY_COLUMNS", "_lib"]

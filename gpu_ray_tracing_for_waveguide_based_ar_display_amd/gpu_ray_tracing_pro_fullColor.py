@@ -25,6 +25,8 @@ Same flow as the reference script, on the MI355X kernel:
    every printed figure carries a jackknife standard error;
    with ``footprint=(H, W)`` (``--footprint HxW``) every launch also counts each interaction into a per-wavelength
    plate map -- where the light interacts, is lost and leaves (``wgrt_trace_footprint``);
+   with ``paths="eyebox"`` (``--paths eyebox``; any fate class, or ``all``) the draws of the selected rays are kept as
+   records -- which way that light went (``wgrt_trace_paths``) -- and reduced to a conditional footprint on request;
 6. the "Eyebox Center View.png" export (MAIN:199-203): the evaluated image at the first eye row,
    last eye column, as 8-bit RGB, rows flipped (``eyebox_center_view``, written without OpenCV).
 
@@ -58,7 +60,7 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
         fuse: bool | None = None, points: np.ndarray | None = None, png: str | None = None,
         eyebox: str = "host", keep_grid: bool = False, evaluate_on: str = "host",
         keep_image: bool = False, budget: bool = False, error_bars: int = 0, estimator: str = "analog",
-        footprint=None, hits=None) -> dict:
+        footprint=None, hits=None, paths=None, paths_capacity=None, paths_footprint=None) -> dict:
     """The reference script's job on this engine; returns its printed quantities and arrays.
     ``points``: the R/2 in-coupler origins to use (default: sampled, GRTF:12-23, seeded by
     ``point_seed``); ``png``: where to write the "Eyebox Center View" image (needs ``evaluate``).
@@ -137,7 +139,52 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
     by tag and global id) and ``hit_count``, and printed per wavelength: out-couplings inside and beside the eyebox, and
     the beside share.  Works with every ``eyebox`` mode; everything else returned is bit-identical to the run without
     it.  ``budget=True``, ``error_bars``, ``estimator="expected"`` and ``footprint`` with it raise ``ValueError`` before
-    any GPU work."""
+    any GPU work.
+
+    ``paths``: ``"all"``, a fate class name of ``engine.FATE_CLASSES`` (``"eyebox"``, ``"left_plate"``, ``"lost_fc"``,
+    ...) or a list of them (None: none): also record which way the selected rays went -- one record ``(x, y, gid, step,
+    flags)`` per Monte-Carlo draw of the bounce loop, and one more where a trace leaves the plate or misses in R5
+    (``engine.PathList``, ``engine.trace_fullcolor(paths=..., select=...)``).  The traces go as plain single launches,
+    tagged with their iteration number.  For a class selection each iteration clones the RNG states, runs a fate launch
+    with no grid on the clone, builds the mask from its fates (``engine.select_by_fate``) and runs the paths launch from
+    the original states; ``"all"`` skips the first pass.  ``paths_capacity``: the list's room in records.  By default a
+    selection's list is sized from its first pass and cannot overflow: a draw is made in a loop iteration and every
+    iteration counts a bounce, so before each paths launch the list is grown to hold ``bounces + 1`` records of every
+    selected ray (the first pass's per-ray bounces; one more for the end record).  ``"all"`` has no first pass and gets 8
+    records per ray of the shard and iteration (measured: 3.7 per ray on BASELINE config 3, 3.9 on the 5 x 4 x 3 test
+    job).  A list that is too small -- a given capacity, or ``"all"``'s default -- raises
+    ``engine.PathListOverflow`` after the trace, naming the capacity that would have sufficed.  Several GPUs send their
+    stored records to rank 0; the ids are global, so the sorted concatenation is the single-process list.  Returned as
+    ``paths`` (the structured array, sorted by tag, global id and step) and ``paths_selected`` (rays recorded per
+    wavelength, over all iterations), and printed per wavelength: rays selected, records kept, mean draws per selected
+    ray.  ``paths_footprint=(H, W)``: also the list reduced on the device into a footprint map over the plate's
+    bounding box (``PathList.footprint``: the conditional footprint of the selected rays), returned as
+    ``paths_footprint`` / ``paths_footprint_plan``.  Works with every ``eyebox`` mode; everything else returned is
+    bit-identical to the run without it.  ``budget=True``, ``error_bars``, ``estimator="expected"``, ``footprint`` and
+    ``hits`` with it raise ``ValueError`` before any GPU work."""
+    path_classes = None   # the fate classes of a selection (None: none, or every ray)
+    if paths is None or paths is False:
+        paths = None
+        if paths_capacity is not None or paths_footprint is not None:
+            raise ValueError("paths_capacity / paths_footprint need paths")
+    else:
+        if budget or error_bars or estimator == "expected" or footprint is not None or not (hits is None or hits is False):
+            raise ValueError("paths is not combined with budget=True, error_bars, estimator='expected', footprint or "
+                             "hits: a launch keeps a path list or does one of those")
+        from .engine import FATE_CLASSES
+        names = [paths] if isinstance(paths, str) else list(paths)
+        known = [c[0] for c in FATE_CLASSES]
+        if not names or not all(isinstance(n, str) and (n in known or (n == "all" and len(names) == 1)) for n in names):
+            raise ValueError(f"paths must be 'all', a fate class or a list of fate classes ({', '.join(known)}), "
+                             f"got {paths!r}")
+        path_classes = None if names == ["all"] else names
+        if paths_capacity is not None and (isinstance(paths_capacity, bool) or int(paths_capacity) != paths_capacity
+                                           or int(paths_capacity) < 0):
+            raise ValueError(f"paths_capacity must be a capacity >= 0 in records, got {paths_capacity!r}")
+        if paths_footprint is not None:
+            if len(tuple(paths_footprint)) != 2 or not all(3 <= int(v) <= 4096 for v in paths_footprint):
+                raise ValueError(f"paths_footprint must be (H, W) cells, each 3 .. 4096, got {paths_footprint!r}")
+            paths_footprint = (int(paths_footprint[0]), int(paths_footprint[1]))
     if hits is None or hits is False:
         hits = None
     else:
@@ -199,7 +246,29 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
             from .engine import HitList
             cap = -(-job.shard.n_rays * int(num_iter) // 8) if hits is True else int(hits)
             job.hits = HitList(cap, job.dev)
-        kern_s = _trace(job, variant, fuse)
+        job.paths = None
+        if paths is not None:
+            import torch
+
+            from .engine import PathList, WindowPlan
+            # the default room: "all" has no first pass to size the list from, and gets 8 records per ray and iteration;
+            # a selection starts empty and is grown from each first pass's mask and bounces (hip_tracer)
+            auto = paths_capacity is None and path_classes is not None
+            cap = int(paths_capacity) if paths_capacity is not None else \
+                (0 if auto else job.shard.n_rays * int(num_iter) * 8)
+            job.paths = SimpleNamespace(list=PathList(cap, job.dev), classes=path_classes, fate=None, windows=None,
+                                        selected=torch.zeros(job.scene.num_lmd, dtype=torch.int64, device=job.dev))
+            if path_classes is not None:   # a selection's first pass: its fates, and a table for its out-couplings
+                job.paths.fate = torch.zeros(job.shard.n_rays, dtype=torch.uint8, device=job.dev)
+                scratch = WindowPlan(device=job.dev.index)
+                job.paths.windows = (scratch, scratch.new_table(job.scene))
+                if auto:
+                    job.paths.bounces = torch.zeros(job.shard.n_rays, dtype=torch.int32, device=job.dev)
+        try:
+            kern_s = _trace(job, variant, fuse)
+        finally:
+            if job.paths is not None and job.paths.windows is not None:
+                job.paths.windows[0].close()
         t_post = time.perf_counter()   # everything below is post-processing of the traced grid
         grid, table, stats = _collect(job, eyebox != "host", keep_grid)
         reps = None
@@ -215,6 +284,15 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
             from .distributed import reduce_eyebox
             fmap = reduce_eyebox(job.footprint[1])
         records = _gather_hits(job) if job.hits is not None else None
+        path_records = path_map = path_sel = None
+        if job.paths is not None:
+            from .distributed import reduce_eyebox
+            path_records = _gather_paths(job)
+            path_sel = reduce_eyebox(job.paths.selected)
+            if paths_footprint is not None:   # every rank reduces its own list; integer counts: the maps add exactly
+                from .engine import FootprintPlan
+                pfp = FootprintPlan.for_scene(job.geom, cells=paths_footprint)
+                path_map = reduce_eyebox(job.paths.list.footprint(job.scene, pfp))
         if job.rank != 0:
             return out
         _report(job, out, grid, table, reps)
@@ -224,6 +302,8 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
             _report_footprint(job, out, fmap)
         if records is not None:
             _report_hits(job, out, records)
+        if path_records is not None:
+            _report_paths(job, out, path_records, path_sel, path_map, pfp if path_map is not None else None)
         if evaluate:
             _evaluate(job, out, grid, table, evaluate_on, keep_image, png, reps)
         out["post_seconds"] = time.perf_counter() - t_post
@@ -315,6 +395,8 @@ def _trace(job, variant, fuse) -> float:
         per_call = 1
     if getattr(job, "hits", None) is not None:            # ... or keeps a hit list
         per_call = 1
+    if getattr(job, "paths", None) is not None:           # ... or a path list
+        per_call = 1
     calls = split_calls(job.num_iter, per_call)
     if n_rays and calls:
         reserve(job.scene, n_rays, max(calls))
@@ -323,7 +405,7 @@ def _trace(job, variant, fuse) -> float:
     if n_rays:
         run_steps(hip_tracer(job.scene, variant, job.stats, job.windows, fate=job.fate, replicas=job.replicas,
                              expected=getattr(job, "expected", False), footprint=getattr(job, "footprint", None),
-                             hits=getattr(job, "hits", None)),
+                             hits=getattr(job, "hits", None), paths=getattr(job, "paths", None)),
                   job.rays, job.rng, job.eb,
                   job.shard.gid, job.num_iter, per_call, hook=hook)
     t1.record()
@@ -382,15 +464,43 @@ def _report_budget(job, out: dict, census) -> None:
         job.say(f"  {name:18s}" + "".join(f"{v * 100:9.3f}%" for v in row))
 
 
+def _gather_paths(job):
+    """The job's path list on rank 0 (None elsewhere), sorted by (tag, global id, step) (``_gather_list``)."""
+    from .engine import PATH_DTYPE, PathListOverflow, sort_paths
+    return _gather_list(job, job.paths.list, PATH_DTYPE, sort_paths, PathListOverflow, "path", "records")
+
+
+def _report_paths(job, out: dict, records, selected, fmap, fp) -> None:
+    """The path list into ``out`` and, per wavelength, the rays selected, the records kept and the mean draws per
+    selected ray printed."""
+    from .engine import path_kind, path_lmd
+    out["paths"] = records
+    out["paths_selected"] = selected.cpu().numpy() if hasattr(selected, "cpu") else np.asarray(selected)
+    if fmap is not None:
+        out["paths_footprint"] = fmap.cpu().numpy()
+        out["paths_footprint_plan"] = fp.as_dict()
+    names = {0: "Blue", 1: "Green", 2: "Red"}
+    l, draw = path_lmd(records), ~np.isin(path_kind(records), (1, 5))
+    what = "every ray" if job.paths.classes is None else ", ".join(job.paths.classes)
+    job.say(f"Ray paths kept ({what}): {len(records):,} records")
+    job.say(f"  {'':10s}{'rays selected':>15s}{'records':>15s}{'draws per ray':>15s}")
+    for k in range(job.scene.num_lmd):
+        n, r, d = int(out["paths_selected"][k]), int((l == k).sum()), int((draw & (l == k)).sum())
+        job.say(f"  {names.get(k, str(k)):10s}{n:15,d}{r:15,d}{(d / n if n else 0.0):15.2f}")
+
+
 def _gather_hits(job):
-    """The job's hit list on rank 0 (None elsewhere), sorted by (tag, global id): every rank checks its own list for
-    overflow (together: a rank whose list overflowed raises on every rank), the counts are all-gathered, and the
-    stored records gathered as buffers padded to the largest."""
+    """The job's hit list on rank 0 (None elsewhere), sorted by (tag, global id) (``_gather_list``)."""
+    from .engine import HIT_DTYPE, HitListOverflow, sort_hits
+    return _gather_list(job, job.hits, HIT_DTYPE, sort_hits, HitListOverflow, "hit", "out-couplings")
+
+
+def _gather_list(job, hl, dtype, sort, overflow, what, counted):
+    """A record list of the job (``engine.HitList``, ``engine.PathList``) on rank 0 (None elsewhere), sorted: every rank
+    checks its own list for overflow (together: a rank whose list overflowed raises on every rank), the counts are
+    all-gathered, and the stored records gathered as buffers padded to the largest."""
     import torch
     import torch.distributed as dist
-
-    from .engine import HIT_DTYPE, HitListOverflow, sort_hits
-    hl = job.hits
     n, cap = hl.count(), hl.capacity
     counts = torch.tensor([n, min(n, cap), cap], dtype=torch.int64, device=job.dev)
     every = [counts]
@@ -400,19 +510,19 @@ def _gather_hits(job):
     every = [tuple(int(v) for v in t.cpu()) for t in every]
     over = [(r, c) for r, c in enumerate(every) if c[0] > c[2]]
     if over:
-        raise HitListOverflow("; ".join(f"rank {r}: the hit list counted {c[0]} out-couplings but has room for {c[2]} "
-                                        f"(a capacity of {c[0]} would have sufficed)" for r, c in over))
+        raise overflow("; ".join(f"rank {r}: the {what} list counted {c[0]} {counted} but has room for {c[2]} "
+                                 f"(a capacity of {c[0]} would have sufficed)" for r, c in over))
     if job.world == 1:
         return hl.records()
     width = max(c[1] for c in every)
-    mine = torch.zeros((width, HIT_DTYPE.itemsize), dtype=torch.uint8, device=job.dev)
+    mine = torch.zeros((width, dtype.itemsize), dtype=torch.uint8, device=job.dev)
     mine[:every[job.rank][1]] = hl.buffer[:every[job.rank][1]]
     parts = [torch.zeros_like(mine) for _ in range(job.world)] if job.rank == 0 else None
     dist.gather(mine, parts, dst=0)
     if job.rank != 0:
         return None
-    rec = np.concatenate([p[:c[1]].cpu().numpy().reshape(-1).view(HIT_DTYPE) for p, c in zip(parts, every)])
-    return sort_hits(rec)
+    rec = np.concatenate([p[:c[1]].cpu().numpy().reshape(-1).view(dtype) for p, c in zip(parts, every)])
+    return sort(rec)
 
 
 def _report_hits(job, out: dict, records) -> None:
@@ -584,6 +694,14 @@ def main(argv=None):
                     help="also keep every out-coupling, inside the eyebox or beside it, as a record (x, y, global ray id, "
                          "tile, flags): N records of room (default: an eighth of the traces)")
     ap.add_argument("--hits-out", default="", metavar="FILE.npy", help="save the records there (numpy structured array)")
+    ap.add_argument("--paths", default="", metavar="CLASS[,CLASS...]",
+                    help="also record which way the selected rays went, one record per Monte-Carlo draw: 'all', or fate "
+                         "classes such as eyebox, left_plate, lost_fc (a fate launch per iteration then chooses the rays); "
+                         "not with --budget, --error-bars, --estimator expected, --footprint or --hits")
+    ap.add_argument("--paths-capacity", type=int, default=None, metavar="N", help="records of room in the path list")
+    ap.add_argument("--paths-out", default="", metavar="FILE.npy", help="save the path records there (numpy structured array)")
+    ap.add_argument("--paths-footprint", default="", metavar="HxW",
+                    help="also reduce the path list into a footprint map of H x W cells: the conditional footprint")
     ap.add_argument("--budget", action="store_true",
                     help="also report where every ray ended: per-ray fates, their per-tile census and the loss budget "
                          "per wavelength (the traces then run as plain single launches)")
@@ -603,23 +721,31 @@ def main(argv=None):
         local = int(os.environ.get("LOCAL_RANK", "0"))
         torch.cuda.set_device(local)
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-    footprint = None
-    if a.footprint:
+    def cells(flag, text):   # "HxW" -> (H, W); None for a flag not given
+        if not text:
+            return None
         try:
-            footprint = tuple(int(v) for v in a.footprint.lower().split("x"))
+            hw = tuple(int(v) for v in text.lower().split("x"))
         except ValueError:
-            footprint = ()
-        if len(footprint) != 2:
-            ap.error(f"--footprint takes HxW, got {a.footprint!r}")
+            hw = ()
+        if len(hw) != 2:
+            ap.error(f"{flag} takes HxW, got {text!r}")
+        return hw
+    footprint = cells("--footprint", a.footprint)
+    paths_footprint = cells("--paths-footprint", a.paths_footprint)
     res = run(a.num_fov_x, a.num_fov_y, a.rays_per_fov, a.num_iter, lut_dir=a.lut_dir, lut_seed=a.lut_seed,
               lut_profile=a.lut_profile, point_seed=a.point_seed, evaluate=not a.no_eval,
               fuse=False if a.no_fuse else {"auto": None, "yes": True, "no": False}[a.fuse],
               png=a.png or None, eyebox=a.eyebox, evaluate_on=a.evaluate, budget=a.budget, error_bars=a.error_bars, estimator=a.estimator,
-              footprint=footprint, hits=None if a.hits is None else (True if a.hits < 0 else a.hits))
+              footprint=footprint, hits=None if a.hits is None else (True if a.hits < 0 else a.hits),
+              paths=None if not a.paths else (a.paths.split(",") if "," in a.paths else a.paths),
+              paths_capacity=a.paths_capacity, paths_footprint=paths_footprint)
     if a.footprint_out and "footprint" in res:   # (rank 0 has the map)
         np.save(a.footprint_out, res["footprint"])
     if a.hits_out and "hits" in res:   # (rank 0 has the list)
         np.save(a.hits_out, res["hits"])
+    if a.paths_out and "paths" in res:   # (rank 0 has the list)
+        np.save(a.paths_out, res["paths"])
     if a.json and (not dist.is_initialized() or dist.get_rank() == 0):
         keep = {k: v for k, v in res.items() if isinstance(v, (int, float, dict, str))}
         with open(a.json, "w") as f:

@@ -646,6 +646,63 @@ wgrt_status wgrt_hits_grid(const wgrt_scene *scene, const wgrt_hit *hits, int64_
 wgrt_status wgrt_hits_grid_host(int32_t nx, int32_t ny, int32_t num_lmd, const double *scene_ranges, const wgrt_hit *hits,
                                 int64_t n, const double *ranges, int32_t H, int32_t W, float *grid);
 
+/* Ray paths: every draw of selected rays as a record, and a path list reduced to a footprint map (new symbols within
+ * ABI 9, looked up by name; the rule is stated once in csrc/wgrt_paths.h).
+ *
+ * wgrt_trace_paths is wgrt_trace_windows that also appends, for every selected ray, one record per Monte-Carlo draw of
+ * the bounce loop -- exactly the draws wgrt_trace_stats.interactions and footprint channels 0..5 count; the
+ * in-coupling event is not one -- at the ray's position before the taken branch moves it, draw k of the trace with
+ * step = k (0-based); and, for a trace that ends by the loop-top eff_reg1 test or by an R5 miss (fate reasons 1, 5),
+ * one more END record at the ray's position there, whose step is the number of draws the trace made.  A trace that
+ * ends at the bounce cap (reason 7) or at the in-coupling event appends no end record.  A draw at which the
+ * in-coupler's second order leaves the in-coupler (reason 6) is kind 0.  So (tag, gid, step) is unique per record, a
+ * ray's records sorted by step are its polyline after the start point, and the number of draw records of a ray is its
+ * interaction count.
+ *   paths     DEVICE wgrt_path_vertex [capacity], 16-byte aligned.  NULL: the call is exactly wgrt_trace_windows
+ *             (capacity, count, tag and select are not looked at).  Otherwise count != NULL, capacity >= 0 (0 only
+ *             counts), tag <= 65535, else WGRT_ERR_INVALID_ARGUMENT; so is a scene of more than 256 wavelengths.
+ *   count     DEVICE uint64[1], ADDED to, never zeroed.  A record whose reserved index is below capacity is stored at
+ *             paths[index]; the others are counted and not stored.  Nothing at or beyond paths + capacity is written.
+ *             The order of the records is unspecified: sort by (tag, gid, step).
+ *   select    DEVICE uint8 [n_rays]: nonzero records the ray; NULL: every ray.  The walk is a pure function of the RNG
+ *             states, so a first launch (wgrt_trace_fate on a copy of the states) can choose the rays of a second.
+ * Every other output -- rng_states, matrix_EB, the window table, per_ray_bounces, every field of stats -- is the bytes
+ * of the same launch through wgrt_trace_windows.  A paths launch is a single launch, as a hits launch is:
+ * opts->num_iter > 1 is WGRT_ERR_INVALID_ARGUMENT, wgrt_chain_begin takes no list, no entry point combines it with
+ * fates, replicas, the expected-value estimator, footprints or hit lists, wgrt_debug_opts.timeline is
+ * WGRT_ERR_UNSUPPORTED, and it never learns the scene's tile table.  The Jones lane records a draw once its decision
+ * is certified; a ray it abandons is re-traced on the exact lane, which passes over the draws already recorded and
+ * appends the rest, the end record included, exactly once.  Asynchronous on stream.  A launch through any other entry
+ * point runs the kernels it ran before this one existed. */
+typedef struct __attribute__((aligned(16))) wgrt_path_vertex {   /* 32 bytes */
+    double x, y;               /* the ray's position at the event (at a draw: before the taken branch moves it) */
+    int64_t gid;               /* global ray id: gid_offset + i, or the id opts->gid_blocks gives ray i */
+    uint32_t step;             /* ordinal of the record within the ray's trace */
+    uint32_t flags;            /* bits 0..2: state R0..R5 (4 after the R3 -> R4 switch, as the fate code's region);
+                                  bits 4..7: kind -- 0 draw, the trace goes on; 2 draw, Monte-Carlo loss; 3 / 4 draw,
+                                  out-coupled inside / beside the FoV's eyebox rectangle; 1 end record, left eff_reg1;
+                                  5 end record, R5 miss; bits 8..15: wavelength index; bits 16..31: the call's tag */
+} wgrt_path_vertex;
+wgrt_status wgrt_trace_paths(const wgrt_scene *scene, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
+                             uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats, uint32_t *per_ray_bounces,
+                             void *stream, const wgrt_launch_opts *opts, const wgrt_window_plan *plan, double *table,
+                             wgrt_path_vertex *paths, int64_t capacity, uint64_t *count, uint32_t tag,
+                             const uint8_t *select);
+int32_t wgrt_path_vertex_bytes(void);   /* sizeof(wgrt_path_vertex) of the library */
+/* A path list added into a footprint map on the device: map is DEVICE int64 [num_lmd, 9, fp->ny_cells, fp->nx_cells]
+ * (wgrt_trace_footprint's), ADDED to, never zeroed; paths DEVICE wgrt_path_vertex [n], 16-byte aligned.  A draw record
+ * counts into the channel of its state through the footprint's own cell rule, one of kind 2 / 3 / 4 also into channel
+ * 6 / 7 / 8; end records and records whose wavelength index is >= num_lmd count nothing.  The list of launches with
+ * select == NULL gives wgrt_trace_footprint's map of the same launches bit for bit; a fate-selected list gives the
+ * conditional footprint.  Each workgroup takes a contiguous span of records and merges equal offsets in a per-wave
+ * counter cache before they reach the map (wgrt_debug_set_footprint_aggregate(0): one atomic per count).  n == 0 is
+ * WGRT_OK without a launch.  Asynchronous on stream (the current device's).
+ * _host is the twin over HOST pointers through the same header (no GPU needed). */
+wgrt_status wgrt_paths_footprint(const wgrt_path_vertex *paths, int64_t n, int32_t num_lmd,
+                                 const wgrt_footprint_plan *fp, int64_t *map, void *stream);
+wgrt_status wgrt_paths_footprint_host(const wgrt_path_vertex *paths, int64_t n, int32_t num_lmd,
+                                      const wgrt_footprint_plan *fp, int64_t *map);
+
 /* Host-only (no GPU needed; test hooks) through the same membership code (csrc/wgrt_window.h):
  * _validate is wgrt_window_plan_create's argument check alone; _table_host ADDS the n hits at flat grid
  * offsets offsets[n] (HOST int64; those outside [0, n_slabs * 9600) are dropped, as the grid's guard drops

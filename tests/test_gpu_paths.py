@@ -1,0 +1,577 @@
+"""Ray paths on the GPU (``wgrt_trace_paths`` through ``torch.ops.wgrt.trace_paths``) and the reduction of a path list
+into a footprint map on the device (``wgrt_paths_footprint``).
+
+Every list comparison is equality of the sorted records' bytes with the checker's (``tests/oracle_paths.c``: the CPU
+oracle with its hooks defined): the positions are the same doubles on both lanes and in the oracle, as the footprint
+tests already rely on.  Every map comparison is ``assert_array_equal`` on int64.  The walk is compared as bytes with the
+same launches without a list."""
+import ctypes
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+from gpu_ray_tracing_for_waveguide_based_ar_display_amd import _lib  # noqa: E402
+from gpu_ray_tracing_for_waveguide_based_ar_display_amd._lib import STAT  # noqa: E402
+from tests import _footprint as F  # noqa: E402
+from tests import _paths as P  # noqa: E402
+from tests._fixtures import GoldenCase  # noqa: E402
+from tests.test_gpu_parity import _config  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+FIXTURES = ["c1_rgb", "h6_edge_rgb", "s1_532"]
+_CONFIGS = {"c2s": dict(nx=11, ny=11, lambdas=[1], R=64),                      # 7,744 rays: > replay_tail's 256 threads
+            "small": dict(nx=5, ny=4, lambdas=[0, 1, 2], R=100),
+            "small_deep": dict(nx=5, ny=4, lambdas=[0, 1, 2], R=100, profile="deep", seed=3),
+            "small_amp": dict(nx=5, ny=4, lambdas=[0, 1, 2], R=100, profile="adversarial_polarizing", seed=3)}
+CELLS = (48, 80)
+CANARY = 0xA5
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("no HIP device")
+    return torch.device("cuda", 0)
+
+
+@pytest.fixture(autouse=True)
+def _switches():
+    yield
+    _lib.set_byte_locator(True)
+    _lib.set_footprint_aggregate(True)
+
+
+_cases, _checked = {}, {}
+
+
+def _case(name):
+    if name not in _cases:
+        _cases[name] = GoldenCase(name) if name in FIXTURES else _config(**_CONFIGS[name])
+    return _cases[name]
+
+
+def _plan(c):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import FootprintPlan
+    return FootprintPlan.for_scene(c.geom, cells=CELLS)
+
+
+def checked(name, launches=1):
+    """The checkers on case ``name`` with every ray recorded, once per key and shared, read-only:
+    ``dict(rec, rng, bounces, fates, eb, map)`` (``map``: the footprint checker's, of the same launches)."""
+    key = (name, launches)
+    if key not in _checked:
+        from oracle import OracleScene
+        c = _case(name)
+        sc = OracleScene.from_geometry(c.geom, c.luts, wavelength=getattr(c, "wavelength", None))
+        eb = np.zeros(c.eb_shape(), np.float32)
+        rec, rng, bounces, fates = P.checker(sc, c.rays, c.fresh_rng(), launches, eb=eb)
+        fmap = F.checker(sc, c.rays, c.fresh_rng(), _plan(c), launches)[0]
+        r = dict(rec=rec, rng=rng, bounces=bounces, fates=fates, eb=eb, map=fmap)
+        for v in r.values():
+            v.setflags(write=False)
+        _checked[key] = r
+    return _checked[key]
+
+
+def _trace(c, dev, launches=1, variant=0, paths=True, capacity=None, pl=None, select=None, rays=None, rng=None,
+           scene=None, keep=False, footprint=False, **kw):
+    """``launches`` single launches into the grid, the window table and (``paths``) one list, launch k tagged k:
+    ``SimpleNamespace(rec, count, rng, eb, table, stats, per)`` on the host (``rec`` sorted).  ``paths=False``: the same
+    calls without a list; ``footprint``: with a footprint map instead (``map``).  ``keep``: also ``pl`` and ``scene``,
+    left open."""
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import (PathList, Scene, WindowPlan, new_stats,
+                                                                           rays_to_device, trace_fullcolor, trace_single)
+    wl = getattr(c, "wavelength", None)
+    own = scene is None
+    if own:
+        scene = Scene.from_geometry(c.geom, c.luts, wavelength=wl)
+    plan = WindowPlan()
+    trace = trace_single if wl is not None else trace_fullcolor
+    paths = paths and not footprint
+    if pl is None and paths:
+        pl = PathList(40 * c.N * launches if capacity is None else capacity, dev)
+    fp = _plan(c)
+    fmap = fp.new_map(scene) if footprint else None
+    table = plan.new_table(scene)
+    eb = torch.zeros(scene.eb_shape(), dtype=torch.float32, device=dev)
+    rays = rays_to_device(c.rays, dev) if rays is None else rays
+    rng = torch.from_numpy(c.fresh_rng().view(np.int32)).to(dev) if rng is None else rng
+    stats = new_stats(dev)
+    per = torch.zeros(rng.numel(), dtype=torch.int32, device=dev)
+    for k in range(launches):
+        if paths:
+            kw2 = dict(paths=(pl, k), select=select[k] if isinstance(select, list) else select)
+        else:
+            kw2 = dict(footprint=(fp, fmap)) if footprint else {}
+        trace(scene, rays, rng, eb, stats=stats, per_ray_bounces=per, variant=variant, windows=(plan, table), **kw2, **kw)
+    torch.cuda.synchronize()
+    out = SimpleNamespace(rec=pl.records() if paths else None, count=pl.count() if paths else None,
+                          map=fmap.cpu().numpy() if footprint else None,
+                          rng=rng.cpu().numpy().view(np.uint32).copy(), eb=eb.cpu().numpy(), table=table.cpu().numpy(),
+                          stats=stats.cpu().numpy().copy(), per=per.cpu().numpy().view(np.uint32).copy())
+    plan.close()
+    if keep:
+        out.pl, out.scene = pl, scene
+    elif own:
+        scene.close()
+    return out
+
+
+def _same_walk(a, b):
+    np.testing.assert_array_equal(a.rng, b.rng)
+    np.testing.assert_array_equal(a.per, b.per)
+    np.testing.assert_array_equal(a.stats, b.stats)
+    assert a.eb.tobytes() == b.eb.tobytes() and a.table.tobytes() == b.table.tobytes()
+
+
+def _same_list(got, want):
+    assert got.dtype == want.dtype == P.DTYPE and got.shape == want.shape, (got.shape, want.shape)
+    assert got.tobytes() == want.tobytes()
+
+
+def _unique(rec):
+    key = np.stack([P.tag(rec), rec["gid"], rec["step"].astype(np.int64)], axis=1)
+    return len(np.unique(key, axis=0)) == len(rec)
+
+
+def _ends(rec):
+    return int(np.isin(P.kind(rec), (1, 5)).sum())
+
+
+# 1. select = None: every variant, four tagged launches into one list; the anchor -----------------------------------
+
+@pytest.mark.parametrize("variant", [1, 7, 9])
+@pytest.mark.parametrize("name", FIXTURES + ["small", "c2s"])
+def test_list_walk_and_map(dev, name, variant):
+    c = _case(name)
+    chk = checked(name, 4)
+    got = _trace(c, dev, launches=4, variant=variant, keep=True)
+    try:
+        _same_list(got.rec, chk["rec"])
+        assert got.count == len(chk["rec"]) > 0 and _unique(got.rec)
+        # the draw records are the interactions; the end records ride on top
+        assert got.count == int(got.stats[STAT.interactions]) + _ends(got.rec) and _ends(got.rec) > 0
+        np.testing.assert_array_equal(got.rng, chk["rng"])
+        np.testing.assert_array_equal(got.per, chk["bounces"])
+        assert got.eb.tobytes() == chk["eb"].tobytes()
+        _same_walk(got, _trace(c, dev, launches=4, variant=variant, paths=False, scene=got.scene))
+        # the list reduced on the device is the footprint launch's map of the same launches, and the checker's; in both
+        # merge forms, and added to, never zeroed
+        fmap = got.pl.footprint(got.scene, _plan(c))
+        torch.cuda.synchronize()
+        assert fmap.dtype == torch.int64
+        np.testing.assert_array_equal(fmap.cpu().numpy(), chk["map"])
+        np.testing.assert_array_equal(_trace(c, dev, launches=4, variant=variant, footprint=True, scene=got.scene).map,
+                                      chk["map"])
+        _lib.set_footprint_aggregate(False)
+        assert got.pl.footprint(got.scene, _plan(c), out=fmap) is fmap
+        np.testing.assert_array_equal(fmap.cpu().numpy(), 2 * chk["map"])
+    finally:
+        got.scene.close()
+
+
+# 2. two-pass selection: a fate launch from a clone of the states chooses the rays of the paths launch ---------------
+
+@pytest.mark.parametrize("variant", [1, 7])
+@pytest.mark.parametrize("cls", ["eyebox", "left_plate"])
+@pytest.mark.parametrize("name", ["small", "c2s"])
+def test_two_pass_selection(dev, name, cls, variant):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import (Scene, rays_to_device, select_by_fate,
+                                                                           trace_fullcolor)
+    from oracle import inside_many
+    c = _case(name)
+    chk = checked(name)
+    scene = Scene.from_geometry(c.geom, c.luts)
+    rays = rays_to_device(c.rays, dev)
+    rng = torch.from_numpy(c.fresh_rng().view(np.int32)).to(dev)
+    fate = torch.zeros(c.N, dtype=torch.uint8, device=dev)
+    eb = torch.zeros(scene.eb_shape(), dtype=torch.float32, device=dev)
+    trace_fullcolor(scene, rays, rng.clone(), eb, variant=variant, fate=fate)
+    mask = select_by_fate(fate, [cls])
+    assert mask.dtype == torch.uint8 and mask.device == fate.device
+    got = _trace(c, dev, variant=variant, select=mask, rays=rays, rng=rng, scene=scene)
+    scene.close()
+    m = mask.cpu().numpy()
+    np.testing.assert_array_equal(fate.cpu().numpy(), chk["fates"][0])
+    assert 0 < m.sum() < c.N
+    want = chk["rec"][m[chk["rec"]["gid"]] != 0]
+    _same_list(got.rec, want)
+    assert got.count == len(want) and not (m[got.rec["gid"]] == 0).any()          # unselected gids have no record
+    np.testing.assert_array_equal(got.rng, chk["rng"])
+    last = np.r_[got.rec["gid"][1:] != got.rec["gid"][:-1], True]
+    assert int(last.sum()) == int(m.sum())                                         # every selected ray has a last record
+    kinds = P.kind(got.rec)[last]
+    if cls == "eyebox":
+        assert (kinds == 3).all()
+    else:
+        assert (kinds == 1).all()
+        end = got.rec[last]
+        assert not inside_many(np.stack([end["x"], end["y"]], axis=1), c.geom.eff_reg1).any()   # outside eff_reg1
+
+
+def test_an_all_zero_mask_records_nothing(dev):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import PathList
+    c = _case("small")
+    for variant in (1, 7):
+        pl = PathList(64, dev)
+        pl.buffer.fill_(CANARY)
+        pl.counter.fill_(5)
+        got = _trace(c, dev, variant=variant, pl=pl, select=torch.zeros(c.N, dtype=torch.uint8, device=dev))
+        assert pl.count() == 5 and (pl.buffer.cpu().numpy() == CANARY).all()
+        _same_walk(got, _trace(c, dev, variant=variant, paths=False))
+
+
+# 3. abandoned rays: the replay passes over the recorded draws and numbers on ----------------------------------------
+
+@pytest.mark.parametrize("debug, every", [(dict(cert_tol=1e-2), False), (dict(cert_tol=1e3, cert_tol32=1e3), True)])
+def test_abandoned_rays_are_recorded_once(dev, debug, every):
+    c = _case("c2s")
+    chk = checked("c2s")
+    got = _trace(c, dev, variant=7, debug=debug)
+    traced, replayed = c.N - int(got.stats[STAT.bad_rays]), int(got.stats[STAT.replayed])
+    print(f"replayed {replayed} of {traced}")
+    if every:
+        assert replayed == traced > 256
+    else:
+        assert 0 < replayed < traced
+    assert _unique(got.rec)
+    _same_list(got.rec, chk["rec"])
+    np.testing.assert_array_equal(got.per, chk["bounces"])
+    np.testing.assert_array_equal(got.rng, chk["rng"])
+    _same_walk(got, _trace(c, dev, variant=7, debug=debug, paths=False))
+
+
+# 4. the staging block ------------------------------------------------------------------------------------------------
+
+def test_many_blocks_per_wave(dev):
+    """c2s with every ray selected: each wave fills its 64-record block many times over."""
+    c = _case("c2s")
+    chk = checked("c2s")
+    got = _trace(c, dev, variant=9)
+    assert got.count == int(got.stats[STAT.interactions]) + _ends(got.rec) == len(chk["rec"])
+    waves = 4 * ((c.N + 255) // 256)          # a workgroup per 256 rays at the most
+    assert got.count > 3 * 64 * waves         # 28,330 records: more than three blocks for every wave on average
+    _same_list(got.rec, chk["rec"])
+
+
+def test_refills(dev):
+    c = _case("small_deep")
+    chk = checked("small_deep")
+    got = _trace(c, dev, variant=7, workgroups=2, debug=dict(chunk_rays=13))
+    _same_list(got.rec, chk["rec"])
+    np.testing.assert_array_equal(got.rng, chk["rng"])
+    _same_walk(got, _trace(c, dev, variant=7, workgroups=2, debug=dict(chunk_rays=13), paths=False))
+
+
+# 5. both locator forms, the single-wavelength kernel, the AMP profile, split batches ---------------------------------
+
+@pytest.mark.parametrize("variant", [7, 9])
+def test_byte_and_word_locator(dev, variant):
+    c = _case("small")
+    chk = checked("small")
+    for byte in (True, False):
+        _lib.set_byte_locator(byte)
+        got = _trace(c, dev, variant=variant)
+        _same_list(got.rec, chk["rec"])
+        np.testing.assert_array_equal(got.rng, chk["rng"])
+    _lib.set_byte_locator(True)
+
+
+def test_single_wavelength(dev):
+    c = _case("s1_532")
+    assert getattr(c, "wavelength", None) is not None
+    chk = checked("s1_532")
+    for variant in (1, 7, 9):
+        got = _trace(c, dev, variant=variant)
+        assert (P.lmd(got.rec) == 0).all()
+        _same_list(got.rec, chk["rec"])
+        np.testing.assert_array_equal(got.rng, chk["rng"])
+
+
+def test_amp_profile(dev):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import Scene
+    c = _case("small_amp")
+    sc = Scene.from_geometry(c.geom, c.luts)
+    assert sc.info()["nonunitary_blocks"] > 0
+    sc.close()
+    chk = checked("small_amp", 2)
+    for variant in (7, 9):
+        got = _trace(c, dev, launches=2, variant=variant)
+        _same_list(got.rec, chk["rec"])
+        np.testing.assert_array_equal(got.rng, chk["rng"])
+
+
+@pytest.mark.parametrize("variant", [1, 7])
+def test_a_batch_split_at_ray_37(dev, variant):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import PathList, Scene, rays_to_device
+    c = _case("c1_rgb")
+    chk = checked("c1_rgb")
+    m = (np.arange(c.N) % 3 != 1).astype(np.uint8)          # the mask is sliced with the batch
+    scene = Scene.from_geometry(c.geom, c.luts)
+    pl = PathList(40 * c.N, dev)
+    full = rays_to_device(c.rays, dev)
+    rng_all = torch.from_numpy(c.fresh_rng().view(np.int32)).to(dev)
+    sel = torch.from_numpy(m).to(dev)
+    got_rng = []
+    for lo, hi in ((0, 37), (37, c.N)):
+        rays = {k: v[lo:hi].contiguous() for k, v in full.items()}
+        r = _trace(c, dev, variant=variant, rays=rays, rng=rng_all[lo:hi].contiguous(), pl=pl, scene=scene,
+                   select=sel[lo:hi].contiguous(), gid_offset=lo)
+        got_rng.append(r.rng)
+    rec = pl.records()
+    scene.close()
+    _same_list(rec, chk["rec"][m[chk["rec"]["gid"]] != 0])
+    np.testing.assert_array_equal(np.concatenate(got_rng), chk["rng"])
+
+
+def test_two_gid_blocks_shards_make_the_whole_list(dev):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.distributed import make_shard
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import init_rays, sort_paths
+    c = _case("c1_rgb")
+    chk = checked("c1_rgb")
+    parts = []
+    for r in range(2):
+        shard = make_shard(c.nx, c.ny, len(c.lambdas), c.R, 2, r)
+        rays, rng = init_rays(c.f["points"], c.nx, c.ny, c.lambdas, c.R, block_list=shard.blocks, device=dev)
+        gb = torch.from_numpy(shard.gid.block_gid).to(dev)
+        rec = _trace(c, dev, variant=7, rays=rays, rng=rng, n_rays=rng.numel(), gid_blocks=gb, gid_block_rays=c.R,
+                     capacity=40 * c.N).rec
+        assert len(rec) > 0
+        parts.append(rec)
+    _same_list(sort_paths(np.concatenate(parts)), chk["rec"])
+
+
+# 6. capacity --------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("variant", [1, 7])
+def test_capacity(dev, variant):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import PathList, PathListOverflow, check_paths
+    c = _case("small")
+    chk = checked("small")
+    n = len(chk["rec"])
+    have = {r.tobytes() for r in chk["rec"]}
+    # capacity 10 inside a buffer with a canary pattern behind it
+    pl = PathList(64, dev)
+    pl.buffer.fill_(CANARY)
+    pl.capacity = 10
+    got = _trace(c, dev, variant=variant, pl=pl)
+    assert got.count == n and pl.stored() == 10
+    assert (pl.buffer.cpu().numpy()[10:] == CANARY).all()
+    assert len({r.tobytes() for r in got.rec}) == 10 and all(r.tobytes() in have for r in got.rec)
+    with pytest.raises(PathListOverflow, match=f"{n}.*10"):
+        check_paths(pl)
+    _same_walk(got, _trace(c, dev, variant=variant, paths=False))
+    # capacity 0 counts and stores nothing
+    pl = PathList(16, dev)
+    pl.buffer.fill_(CANARY)
+    pl.capacity = 0
+    got = _trace(c, dev, variant=variant, pl=pl)
+    assert got.count == n and len(got.rec) == 0 and (pl.buffer.cpu().numpy() == CANARY).all()
+    # exact
+    pl = PathList(n + 8, dev)
+    pl.buffer[n:].fill_(CANARY)
+    pl.capacity = n
+    got = _trace(c, dev, variant=variant, pl=pl)
+    assert got.count == n and (pl.buffer[n:].cpu().numpy() == CANARY).all()
+    _same_list(got.rec, chk["rec"])
+    check_paths(pl)
+    check_paths(PathList(0, dev))
+
+
+# 7. refusals --------------------------------------------------------------------------------------------------------
+
+def test_refusals(dev):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import (FootprintPlan, HitList, PathList, Scene,
+                                                                           TraceChain, WindowPlan, _debug_opts,
+                                                                           rays_to_device, trace_fullcolor)
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd._lib import load, ops
+    c = _case("c1_rgb")
+    scene, plan = Scene.from_geometry(c.geom, c.luts), WindowPlan()
+    rays = rays_to_device(c.rays, dev)
+    rng = torch.from_numpy(c.fresh_rng().view(np.int32)).to(dev)
+    before = rng.clone()
+    pl = PathList(c.N, dev)
+    grid = torch.zeros(c.eb_shape(), dtype=torch.float32, device=dev)
+    table = plan.new_table(scene)
+    go = lambda **kw: trace_fullcolor(scene, rays, rng, grid, variant=7, paths=(pl, 0), **kw)
+    with pytest.raises(ValueError, match="num_iter"):
+        go(num_iter=2)
+    with pytest.raises(ValueError, match="fate"):
+        go(fate=torch.zeros(c.N, dtype=torch.uint8, device=dev))
+    with pytest.raises(ValueError, match="replicas"):
+        go(windows=(plan, plan.new_table(scene, replicas=4)), replicas=4)
+    with pytest.raises(ValueError, match="expected"):
+        trace_fullcolor(scene, rays, rng, None, windows=(plan, table), expected=True, paths=(pl, 0))
+    fp = FootprintPlan.for_scene(c.geom, cells=(8, 8))
+    with pytest.raises(ValueError, match="footprint"):
+        go(footprint=(fp, fp.new_map(scene)))
+    with pytest.raises(ValueError, match="hits"):
+        go(hits=(HitList(4, dev), 0))
+    with pytest.raises(ValueError, match="chain"):
+        TraceChain(scene, rays, rng, grid, paths=(pl, 0))
+    with pytest.raises(ValueError, match="select"):
+        trace_fullcolor(scene, rays, rng, grid, select=torch.zeros(c.N, dtype=torch.uint8, device=dev))
+    with pytest.raises(TypeError):
+        trace_fullcolor(scene, rays, rng, grid, paths=(pl.buffer, 0))
+    with pytest.raises(ValueError, match="select"):
+        go(select=torch.zeros(c.N - 1, dtype=torch.uint8, device=dev))
+
+    # the operator and the C entry point themselves
+    def op(buf=pl.buffer, cap=c.N, count=pl.counter, tag=0, num_iter=1, debug=0, variant=7, select=None):
+        return ops().trace_paths(scene.handle.value, rays["x"], rays["y"], rays["m"], rays["n"], rays["lmd_num"],
+                                 rays["te"], rays["tm"], rays["delta_phase"], rng, grid, None, None, c.N, 0, 0, 0, variant,
+                                 0, None, num_iter, None, 0, debug, 0.0, 0, None, buf, cap, count, tag, select)
+    for v in (1, 7):
+        assert op(num_iter=2, variant=v) == 1                                      # WGRT_ERR_INVALID_ARGUMENT
+        assert op(count=None, variant=v) == 1
+        assert op(cap=-1, variant=v) == 1
+        assert op(tag=65536, variant=v) == 1 and op(tag=-1, variant=v) == 1
+        assert op(buf=pl.buffer.reshape(-1)[8:], cap=4, variant=v) == 1            # a misaligned list
+    tl = torch.zeros(8 * 64, dtype=torch.int64, device=dev)
+    dbg = _debug_opts(dict(timeline=tl))
+    assert op(debug=ctypes.addressof(dbg)) == 4                                    # WGRT_ERR_UNSUPPORTED
+    with pytest.raises(RuntimeError, match="uint8"):
+        op(buf=pl.buffer.to(torch.int32))
+    with pytest.raises(RuntimeError, match="exceeds"):
+        op(cap=c.N + 1)
+    with pytest.raises(RuntimeError, match="select"):
+        op(select=torch.zeros(c.N, dtype=torch.int32, device=dev))
+    torch.cuda.synchronize()
+    assert torch.equal(rng, before) and not grid.any() and not tl.any() and pl.count() == 0   # nothing was launched
+    assert not pl.buffer.any()
+
+    # paths == NULL: the windows launch, bit for bit (capacity, count, tag and select are not looked at)
+    L = load()
+    cols = _lib.Rays(**{k: ctypes.c_void_p(rays[k].data_ptr()) for k in ("x", "y", "m", "n", "lmd_num", "te", "tm",
+                                                                          "delta_phase")})
+    opts = _lib.LaunchOpts()
+    opts.variant = 7
+    st = torch.zeros(_lib.STATS_LEN, dtype=torch.int64, device=dev)
+    assert L.wgrt_trace_paths(scene.handle, ctypes.byref(cols), c.N, 0, rng.data_ptr(), grid.data_ptr(),
+                              st.data_ptr(), None, None, ctypes.byref(opts), plan.handle, table.data_ptr(), None,
+                              -5, None, 1 << 20, None) == 0
+    rng2, grid2, table2, st2 = before.clone(), torch.zeros_like(grid), torch.zeros_like(table), torch.zeros_like(st)
+    assert L.wgrt_trace_windows(scene.handle, ctypes.byref(cols), c.N, 0, rng2.data_ptr(), grid2.data_ptr(),
+                                st2.data_ptr(), None, None, ctypes.byref(opts), plan.handle, table2.data_ptr()) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(rng, rng2) and torch.equal(grid, grid2) and torch.equal(table, table2) and torch.equal(st, st2)
+    assert grid.sum() > 0 and pl.count() == 0
+    plan.close()
+    scene.close()
+
+
+def test_more_than_256_wavelengths_is_refused_on_the_host(dev):
+    """The host-side check of the Python layer: no scene of 257 wavelengths is built, nothing is launched."""
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import PathList, _trace as engine_trace
+    pl = PathList(4, dev)
+    scene = SimpleNamespace(device=dev.index, num_lmd=257, single_lambda=False)
+    with pytest.raises(ValueError, match="256"):
+        engine_trace(scene, {}, None, None, 0, None, None, None, None, 7, 0, single=False, paths=(pl, 0))
+    assert pl.count() == 0
+
+
+# 8. the driver ------------------------------------------------------------------------------------------------------
+# the small job of tests/test_gpu_window_sink.py ("deep" LUT profile)
+
+NX, NY, R, STEPS = 5, 4, 256, 2
+_runs = {}
+
+
+def _run(paths, eyebox="windows", **kw):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.gpu_ray_tracing_pro_fullColor import run
+    from tests import _dist
+    pts = _dist.small_job(NX, NY, R, 3, 6, "deep")[2]
+    return run(NX, NY, R, STEPS, lut_seed=3, lut_profile="deep", points=pts, verbose=False, eyebox=eyebox,
+               evaluate_on="device" if eyebox != "host" else "host", paths=paths, **kw)
+
+
+def _run_once(paths):
+    if paths not in _runs:
+        _runs[paths] = _run(paths, paths_footprint=CELLS) if paths else _run(None)
+    return _runs[paths]
+
+
+def test_driver_paths(dev):
+    from oracle import OracleScene
+    from tests import _dist
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import (FootprintPlan, PathListOverflow,
+                                                                           paths_footprint_host, select_by_fate)
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.rays import build_rays, rng_seeds
+    got, plain = _run_once("eyebox"), _run_once(None)
+    assert set(got) - set(plain) == {"paths", "paths_selected", "paths_footprint", "paths_footprint_plan"}
+    for k in plain:   # efficiencies, evaluation and everything else returned before, bit for bit (the timings aside)
+        if k in ("gpu_seconds", "post_seconds"):
+            continue
+        a, b = got[k], plain[k]
+        if isinstance(a, np.ndarray):
+            assert a.tobytes() == b.tobytes(), k
+        else:
+            assert a == b or (isinstance(a, float) and float(a).hex() == float(b).hex()), k
+    # the checker on the driver's batch: launch k tagged k, its mask from the checker's own fates of launch k
+    geom, luts, pts = _dist.small_job(NX, NY, R, 3, 6, "deep")
+    rays = build_rays(pts, NX, NY, (0, 1, 2), R)
+    N = rays["x"].shape[0]
+    sc = OracleScene.from_geometry(geom, luts)
+    full, rng, _, fates = P.checker(sc, rays, rng_seeds(N), STEPS)
+    masks = [select_by_fate(torch.from_numpy(fates[k].copy()), "eyebox").numpy() for k in range(STEPS)]
+    keep = np.zeros(len(full), bool)
+    for k in range(STEPS):
+        keep |= (P.tag(full) == k) & (masks[k][full["gid"]] != 0)
+    want = full[keep]
+    _same_list(got["paths"], want)
+    assert len(want) > 0
+    np.testing.assert_array_equal(got["rng_states"], rng)
+    lmd = rays["lmd_num"].astype(np.int64)
+    np.testing.assert_array_equal(got["paths_selected"], sum(np.bincount(lmd[m != 0], minlength=3) for m in masks))
+    fp = FootprintPlan.for_scene(geom, cells=CELLS)
+    assert got["paths_footprint_plan"] == fp.as_dict()
+    np.testing.assert_array_equal(got["paths_footprint"], paths_footprint_host(want, fp, 3))
+    assert int(got["paths_footprint"][:, 7].sum()) == int(got["paths_selected"].sum())
+    # "all" skips the first pass and keeps every ray's records
+    _same_list(_run("all")["paths"], full)
+    # the largest loss class and another one under the default capacity: the list is sized from each first pass (the
+    # selected rays' bounces + 1), so nothing overflows and nothing is missing
+    big = _run(["left_plate", "lost_fc"])
+    keep = np.zeros(len(full), bool)
+    n_sel = 0
+    for k in range(STEPS):
+        m = select_by_fate(torch.from_numpy(fates[k].copy()), ["left_plate", "lost_fc"]).numpy()
+        keep |= (P.tag(full) == k) & (m[full["gid"]] != 0)
+        n_sel += int(m.sum())
+    _same_list(big["paths"], full[keep])
+    assert int(big["paths_selected"].sum()) == n_sel > N // 4 and len(big["paths"]) > 2 * n_sel
+    for bad in (dict(budget=True), dict(error_bars=4), dict(estimator="expected"), dict(footprint=(64, 96)), dict(hits=True)):
+        with pytest.raises(ValueError, match="paths"):
+            _run("eyebox", **bad)
+    with pytest.raises(ValueError, match="paths"):
+        _run("nowhere")
+    with pytest.raises(ValueError, match="paths"):
+        _run(None, paths_capacity=5)
+    with pytest.raises(PathListOverflow, match=str(len(want))):
+        _run("eyebox", paths_capacity=5)
+
+
+def _driver_worker(rank, world, outdir):
+    torch.cuda.set_device(torch.device("cuda", 0))
+    res = _run("eyebox", paths_footprint=CELLS)
+    if rank != 0:
+        assert "paths" not in res
+        return
+    np.save(f"{outdir}/paths.npy", res["paths"])
+    np.save(f"{outdir}/map.npy", res["paths_footprint"])
+    np.save(f"{outdir}/sel.npy", res["paths_selected"])
+
+
+def test_driver_paths_in_two_ranks(dev, tmp_path):
+    """Two ranks on the one GPU over gloo: the ids are global, so the sorted concatenation of the ranks' lists is the
+    single-process list, and the ranks' maps add up to its map."""
+    from tests import _dist
+    _dist.spawn(_driver_worker, 2, str(tmp_path))
+    one = _run_once("eyebox")
+    _same_list(np.load(tmp_path / "paths.npy"), one["paths"])
+    np.testing.assert_array_equal(np.load(tmp_path / "map.npy"), one["paths_footprint"])
+    np.testing.assert_array_equal(np.load(tmp_path / "sel.npy"), one["paths_selected"])
