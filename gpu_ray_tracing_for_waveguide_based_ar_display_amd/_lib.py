@@ -34,7 +34,9 @@ EXPORTED = ("wgrt_scene_create", "wgrt_scene_create_ex", "wgrt_scene_destroy", "
             "wgrt_expected_weight_host", "wgrt_trace_footprint", "wgrt_footprint_plan_validate",
             "wgrt_footprint_bin_host", "wgrt_footprint_channel_name", "wgrt_trace_hits", "wgrt_hit_bytes",
             "wgrt_hits_grid", "wgrt_hits_grid_host", "wgrt_trace_paths", "wgrt_path_vertex_bytes",
-            "wgrt_paths_footprint", "wgrt_paths_footprint_host")
+            "wgrt_paths_footprint", "wgrt_paths_footprint_host", "wgrt_trace_visits", "wgrt_visit_channels",
+            "wgrt_visits_sensitivity", "wgrt_visits_reweight", "wgrt_visits_sensitivity_host",
+            "wgrt_visits_reweight_host", "wgrt_visit_channel_host", "wgrt_visit_channel_count_host")
 EXPORTED_DEBUG = ("wgrt_debug_shadow", "wgrt_debug_scene_copy", "wgrt_debug_set_auto_order",
                   "wgrt_debug_get_auto_order", "wgrt_debug_get_tile_tail", "wgrt_debug_order_host",
                   "wgrt_debug_chain_plan", "wgrt_debug_chain_set_serial", "wgrt_debug_set_byte_locator",
@@ -365,6 +367,25 @@ def load():
         L.wgrt_paths_footprint.argtypes = [_vp, ctypes.c_int64, ctypes.c_int32, _vp, _vp, _vp]
         L.wgrt_paths_footprint_host.restype = st
         L.wgrt_paths_footprint_host.argtypes = [_vp, ctypes.c_int64, ctypes.c_int32, _vp, _vp]
+    if hasattr(L, "wgrt_trace_visits"):   # branch visit counts and their reductions: new symbols within ABI 9, by name
+        i32 = ctypes.c_int32
+        L.wgrt_trace_visits.restype = st
+        L.wgrt_trace_visits.argtypes = L.wgrt_trace_opts.argtypes + [_vp, _vp, _vp, ctypes.c_int64, _vp, _vp]
+        L.wgrt_visit_channels.restype = i32
+        L.wgrt_visit_channels.argtypes = [_vp]
+        L.wgrt_visits_sensitivity.restype = st
+        L.wgrt_visits_sensitivity.argtypes = [_vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp]
+        L.wgrt_visits_reweight.restype = st
+        L.wgrt_visits_reweight.argtypes = [_vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp]
+        L.wgrt_visits_sensitivity_host.restype = st
+        L.wgrt_visits_sensitivity_host.argtypes = [i32, i32, i32, i32, _vp, _vp, i32, i32, i32, _vp, _vp, ctypes.c_int64, _vp]
+        L.wgrt_visits_reweight_host.restype = st
+        L.wgrt_visits_reweight_host.argtypes = [i32, i32, i32, i32, _vp, _vp, i32, i32, i32, _vp, _vp, ctypes.c_int64, _vp,
+                                                _vp]
+        L.wgrt_visit_channel_host.restype = i32
+        L.wgrt_visit_channel_host.argtypes = [i32, i32, i32, i32, i32]
+        L.wgrt_visit_channel_count_host.restype = i32
+        L.wgrt_visit_channel_count_host.argtypes = [i32, i32]
     if hasattr(L, "wgrt_locator_palette_host"):   # the byte locator's hooks: new symbols within ABI 9, bound by name
         L.wgrt_locator_palette_host.restype = st
         L.wgrt_locator_palette_host.argtypes = [ctypes.POINTER(SceneDesc), ctypes.c_double, _i64, _i64, _d,

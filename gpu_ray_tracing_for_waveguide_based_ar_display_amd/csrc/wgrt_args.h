@@ -165,6 +165,18 @@ struct TraceArgs {
     const uint8_t *select;
     uint32_t paths_tag;
     uint32_t paths_pad_;
+    // branch visit counts (wgrt_trace_visits; wgrt_visits.h): with vis_counts, ray i is counted into row
+    // vis_slot ? vis_slot[i] : i (negative: not counted): every draw that takes a branch, the in-coupling event's
+    // included, adds 1 to vis_counts[row * vis_channels + channel], and a last draw that out-couples writes
+    // vis_ends[row].  Only the VISITS instantiations read them: both lanes add with one unsigned atomic whose result is
+    // not used (trace_grid_visits_kernel, the kVisits replay; the Jones-vector lane once the draw is certified); the
+    // draws the Jones-vector lane had counted of a ray it abandons go to the replay in fp_seen's storage.  Single
+    // launches only.  Last again.
+    const int32_t *vis_slot;
+    uint32_t *vis_counts;
+    wgrt_visit_end *vis_ends;
+    int32_t vis_channels;
+    int32_t vis_pad_;
 };
 
 // The replica of global ray id g >= 0 among reps (2 .. 64) copies: g % reps from 32-bit remainders (the 64-bit

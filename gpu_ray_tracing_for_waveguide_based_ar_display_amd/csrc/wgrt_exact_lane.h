@@ -35,6 +35,7 @@
 #include "wgrt_hits.h"
 #include "wgrt_locator.h"
 #include "wgrt_paths.h"
+#include "wgrt_visits.h"
 #include "wgrt_window.h"
 
 namespace wgrt {
@@ -214,6 +215,25 @@ __device__ __forceinline__ void path_store(wgrt_path_vertex *paths, int64_t cap,
         double2 *const p = (double2 *)(paths + idx);
         p[0] = double2{x, y};
         ((ulonglong2 *)p)[1] = ulonglong2{(unsigned long long)gid, (unsigned long long)step | (unsigned long long)flags << 32};
+    }
+}
+
+// One certified draw of a counted ray (wgrt_trace_visits; wgrt_visits.h), by both lanes: the taken branch's channel c
+// (< 0: the draw took none) adds 1 to the ray's row -- an unsigned add whose result is not used -- and a draw that
+// out-couples writes the row's end record as two 16-byte stores (position; global id, tile index below flags).  gid():
+// the ray's global id, looked up only there.
+template <class GidFn>
+__device__ __forceinline__ void visit_count(uint32_t *counts, wgrt_visit_end *ends, int C, int64_t row, int c, bool out,
+                                            bool inside, double x, double y, uint32_t tile, GidFn gid) {
+    static_assert(offsetof(wgrt_visit_end, gid) == 16 && offsetof(wgrt_visit_end, tile) == 24 &&
+                      offsetof(wgrt_visit_end, flags) == 28,
+                  "the second half: gid, then tile below flags in one 64-bit word");
+    if (c >= 0) atomicAdd(counts + row * C + c, 1u);
+    if (out) {
+        const uint32_t flags = kVisitOut | (inside ? kVisitInside : 0u);
+        double2 *const p = (double2 *)(ends + row);
+        p[0] = double2{x, y};
+        ((ulonglong2 *)p)[1] = ulonglong2{(unsigned long long)gid(), (unsigned long long)tile | (unsigned long long)flags << 32};
     }
 }
 
@@ -535,11 +555,15 @@ __device__ __forceinline__ void footprint_count(const TraceArgs &A, int l, int r
 // PATHS: with the path list's appends (wgrt_paths.h), for a ray that A.select names: one record per draw of the bounce
 // loop, numbered from 0, and the end record of a trace that advance() ends with reason 1 or 5; skip: the draws to pass
 // over, recorded by the Jones lane before it abandoned the ray, which the numbering counts on from.
-template <bool FATE = false, bool EV = false, bool FP = false, bool HITS = false, bool PATHS = false>
+// VISITS: with the branch counts of wgrt_trace_visits (wgrt_visits.h), for a ray whose slot is not negative: every draw
+// that takes a branch, the in-coupling event's included, counts into its channel -- the branch read from where the draw
+// led and the fate code interact<FATE> leaves -- and an out-coupling writes the row's end record; skip: the draws to
+// pass over (the event's among them), counted by the Jones lane before it abandoned the ray.
+template <bool FATE = false, bool EV = false, bool FP = false, bool HITS = false, bool PATHS = false, bool VISITS = false>
 __device__ __forceinline__ void trace_one(const TraceArgs &A, int64_t i, Counters &c, uint32_t *s_io = nullptr,
                                           uint32_t skip = 0) {
-    static_assert(!(EV && FP) && !(EV && PATHS) && !(FP && PATHS),
-                  "a launch scores visits, counts footprints or records paths: skip belongs to one of them");
+    static_assert(!(EV && FP) && !(EV && PATHS) && !(FP && PATHS) && !(VISITS && (EV || FP || PATHS)),
+                  "a launch scores visits, counts footprints, records paths or counts branches: skip belongs to one of them");
     Lane L;
     if (!lane_load(A, i, L)) {
         ++c.w[kCtrBadRays];
@@ -553,11 +577,24 @@ __device__ __forceinline__ void trace_one(const TraceArgs &A, int64_t i, Counter
     const bool psel = PATHS && (!A.select || A.select[i] != 0);
     const int64_t pgid = psel ? ray_gid(A, L.i) : 0;   // (once per ray, not per record)
     uint32_t pstep = 0;
+    // VISITS: the row the ray is counted into (< 0: it is not)
+    const int64_t vrow = VISITS ? (A.vis_slot ? (int64_t)A.vis_slot[i] : i) : -1;
     for (;;) {
         // FP, PATHS: where and in which state the ray stands at this draw
         const double fx = L.r.x, fy = L.r.y;
         const int freg = L.r.region;
-        const int next = interact<FATE || FP || PATHS, EV, HITS>(A, A.loc, L, blk, kind, entry, &skip);
+        const int next = interact<FATE || FP || PATHS || VISITS, EV, HITS>(A, A.loc, L, blk, kind, entry, &skip);
+        if (VISITS) {   // (blk and kind are still this draw's)
+            if (skip) --skip;   // counted by the lane that abandoned the ray
+            else if (vrow >= 0) {
+                const int why = next < 0 ? L.why % 10 : 0;
+                const bool out = why == kFateEyebox || why == kFateBeside;
+                const int b = visit_branch(kind, next, why == kFateLeftIc, out);
+                visit_count(A.vis_counts, A.vis_ends, A.vis_channels, vrow, b >= 0 ? visit_channel(blk, b, A.nfc, A.noc) : -1,
+                            out, why == kFateEyebox, fx, fy, (uint32_t)((L.l * A.nx + L.m) * A.ny + L.n),
+                            [&]() { return ray_gid(A, L.i); });
+            }
+        }
         if (FP && !entry) {
             if (skip) --skip;   // counted by the lane that abandoned the ray
             else footprint_count(A, L.l, freg, next < 0 ? L.why % 10 : 0, fx, fy);

@@ -143,6 +143,32 @@ const PathsAbi &paths_abi() {
     return abi;
 }
 
+// wgrt_trace_visits and the two reductions (branch visit counts), new within ABI 9 too: looked up at the first call.
+struct VisitsAbi {
+    decltype(&wgrt_trace_visits) trace;
+    decltype(&wgrt_visits_sensitivity) sensitivity;
+    decltype(&wgrt_visits_reweight) reweight;
+    decltype(&wgrt_visit_channels) channels;
+};
+const VisitsAbi &visits_abi() {
+    static const VisitsAbi abi{
+        reinterpret_cast<decltype(&wgrt_trace_visits)>(dlsym(RTLD_DEFAULT, "wgrt_trace_visits")),
+        reinterpret_cast<decltype(&wgrt_visits_sensitivity)>(dlsym(RTLD_DEFAULT, "wgrt_visits_sensitivity")),
+        reinterpret_cast<decltype(&wgrt_visits_reweight)>(dlsym(RTLD_DEFAULT, "wgrt_visits_reweight")),
+        reinterpret_cast<decltype(&wgrt_visit_channels)>(dlsym(RTLD_DEFAULT, "wgrt_visit_channels"))};
+    TORCH_CHECK(abi.trace && abi.sensitivity && abi.reweight && abi.channels,
+                "wgrt.trace_visits: the loaded libwgrt.so has no wgrt_trace_visits (a build from before the visit counts)");
+    return abi;
+}
+
+// A visits launch's rows (trace_visits): counts int32 [n_rows, C] (the library's uint32 words), ends uint8 [n_rows, 32],
+// slot int32 [n_rays] or none.
+struct VisitRows {
+    const std::optional<Tensor> &slot;
+    Tensor counts, ends;
+    int64_t n_rows;
+};
+
 // All three launching operators: trace (the grid alone: plan 0, no table), trace_windows (the grid, the window
 // table of plan `plan` -- a wgrt_window_plan handle -- or both) and, with `chain`, chain_begin: the same checks and
 // records handed to wgrt_chain_begin, which launches nothing and leaves the chain's handle in *chain.
@@ -157,7 +183,7 @@ int64_t trace_core(int64_t scene, const Tensor &x, const Tensor &y, const Tensor
                    const wgrt_footprint_plan *fp = nullptr, std::optional<Tensor> fp_map = std::nullopt,
                    std::optional<Tensor> hits = std::nullopt, int64_t hit_capacity = 0,
                    std::optional<Tensor> hit_count = std::nullopt, int64_t hit_tag = 0, bool as_paths = false,
-                   const std::optional<Tensor> &select = std::nullopt) {
+                   const std::optional<Tensor> &select = std::nullopt, const VisitRows *visits = nullptr) {
     const wgrt_scene *s = reinterpret_cast<const wgrt_scene *>(static_cast<uintptr_t>(scene));
     TORCH_CHECK(s != nullptr, "wgrt.trace: NULL scene");
     wgrt_scene_info info{};
@@ -250,6 +276,31 @@ int64_t trace_core(int64_t scene, const Tensor &x, const Tensor &y, const Tensor
     if (chain) {
         TORCH_CHECK(!per, "wgrt.chain_begin: a chain takes no per_ray_bounces");
         return chain_abi().begin(s, &r, n_rays, gid_offset, rng, eb, stp, hip_stream, &o, tab ? wp : nullptr, tab, chain);
+    }
+    if (visits) {   // trace_visits: the rows' counts and end records, and the batch's slots
+        TORCH_CHECK(!hits && !fp_map && !fate && replicas == 0 && !expected,
+                    "wgrt.trace_visits: takes no fate, replicas, expected, footprint map or list");
+        const int64_t C = visits_abi().channels(s);
+        on_device(visits->counts, "counts", c);
+        on_device(visits->ends, "ends", c);
+        // (a negative n_rows is the library's to refuse; the rows must lie inside both buffers)
+        TORCH_CHECK(visits->counts.scalar_type() == at::kInt && visits->counts.is_contiguous() &&
+                        visits->counts.numel() >= std::max<int64_t>(visits->n_rows, 0) * C,
+                    "wgrt.trace_visits: counts must be contiguous int32 with >= n_rows * ", C, " entries");
+        TORCH_CHECK(visits->ends.scalar_type() == at::kByte && visits->ends.is_contiguous() &&
+                        visits->ends.numel() >= std::max<int64_t>(visits->n_rows, 0) * (int64_t)sizeof(wgrt_visit_end),
+                    "wgrt.trace_visits: ends must be contiguous uint8 with >= n_rows * 32 bytes");
+        const int32_t *slot = nullptr;
+        if (visits->slot) {
+            on_device(*visits->slot, "slot", c);
+            TORCH_CHECK(visits->slot->scalar_type() == at::kInt && visits->slot->is_contiguous() &&
+                            visits->slot->numel() >= n_rays,
+                        "wgrt.trace_visits: slot must be contiguous int32 with >= ", n_rays, " entries");
+            slot = static_cast<const int32_t *>(visits->slot->const_data_ptr());
+        }
+        return visits_abi().trace(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o, tab ? wp : nullptr, tab, slot,
+                                  visits->n_rows, static_cast<uint32_t *>(visits->counts.data_ptr()),
+                                  static_cast<wgrt_visit_end *>(visits->ends.data_ptr()));
     }
     if (hits) {   // trace_hits / trace_paths: the record buffer (uint8, 32 bytes per record), its capacity, the counter
                   // and the tag; trace_paths (as_paths) also the batch's select bytes
@@ -425,6 +476,59 @@ int64_t trace_paths(int64_t scene, const Tensor &x, const Tensor &y, const Tenso
                       std::nullopt, paths, capacity, count, tag, true, select);
 }
 
+// trace_visits: trace_windows' arguments, the batch's slots (or None), the rows there are, their counts and their end
+// records (wgrt_trace_visits).
+int64_t trace_visits(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
+                     const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
+                     Tensor rng_states, std::optional<Tensor> matrix_EB, std::optional<Tensor> stats,
+                     std::optional<Tensor> per_ray_bounces, int64_t n_rays, int64_t gid_offset, int64_t stream,
+                     int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
+                     int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
+                     double grid_sqrt_k, int64_t plan, std::optional<Tensor> table, const std::optional<Tensor> &slot,
+                     int64_t n_rows, Tensor counts, Tensor ends) {
+    const VisitRows rows{slot, counts, ends, n_rows};
+    return trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats, per_ray_bounces,
+                      n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
+                      gid_block_rays, debug, grid_sqrt_k, plan, table, nullptr, std::nullopt, 0, false, nullptr,
+                      std::nullopt, std::nullopt, 0, std::nullopt, 0, false, std::nullopt, &rows);
+}
+
+// visits_reduce: the first n_rows rows of a visits table reduced on the scene's device: without lnscale into the
+// sensitivity tables out [C, n_slabs, W] (wgrt_visits_sensitivity), with lnscale float64 [C] into the re-weighted window
+// table out [n_slabs, W] (wgrt_visits_reweight).  Both add to out.
+int64_t visits_reduce(int64_t scene, int64_t plan, const Tensor &counts, const Tensor &ends, int64_t n_rows,
+                      const std::optional<Tensor> &lnscale, Tensor out, int64_t stream) {
+    const wgrt_scene *s = reinterpret_cast<const wgrt_scene *>(static_cast<uintptr_t>(scene));
+    const wgrt_window_plan *wp = reinterpret_cast<const wgrt_window_plan *>(static_cast<uintptr_t>(plan));
+    TORCH_CHECK(s != nullptr && wp != nullptr, "wgrt.visits_reduce: NULL scene / plan");
+    wgrt_scene_info info{};
+    const wgrt_status st = wgrt_scene_get_info(s, &info);
+    if (st != WGRT_OK) return st;
+    const c10::Device dev(c10::DeviceType::CUDA, static_cast<c10::DeviceIndex>(info.device));
+    const int64_t C = visits_abi().channels(s), W = window_abi().width(wp);
+    TORCH_CHECK(W > 0, "wgrt.visits_reduce: a bad window plan");
+    TORCH_CHECK(counts.device() == dev && ends.device() == dev && out.device() == dev,
+                "wgrt.visits_reduce: counts, ends and out must be on the scene's device");
+    TORCH_CHECK(n_rows >= 0 && counts.scalar_type() == at::kInt && counts.is_contiguous() && counts.numel() >= n_rows * C,
+                "wgrt.visits_reduce: counts must be contiguous int32 with >= n_rows * ", C, " entries");
+    TORCH_CHECK(ends.scalar_type() == at::kByte && ends.is_contiguous() &&
+                    ends.numel() >= n_rows * (int64_t)sizeof(wgrt_visit_end),
+                "wgrt.visits_reduce: ends must be contiguous uint8 with >= n_rows * 32 bytes");
+    TORCH_CHECK(out.scalar_type() == at::kDouble && out.is_contiguous() &&
+                    out.numel() == (lnscale ? 1 : C) * (int64_t)info.tiles * W,
+                "wgrt.visits_reduce: out must be contiguous float64 [", lnscale ? "" : "C, ", info.tiles, ", ", W, "]");
+    const c10::DeviceGuard guard(dev);
+    void *const hip_stream = reinterpret_cast<void *>(static_cast<uintptr_t>(stream));
+    const uint32_t *cnt = static_cast<const uint32_t *>(counts.const_data_ptr());
+    const wgrt_visit_end *e = static_cast<const wgrt_visit_end *>(ends.const_data_ptr());
+    if (!lnscale) return visits_abi().sensitivity(s, wp, cnt, e, n_rows, out.data_ptr<double>(), hip_stream);
+    TORCH_CHECK(lnscale->device() == dev && lnscale->scalar_type() == at::kDouble && lnscale->is_contiguous() &&
+                    lnscale->numel() == C,
+                "wgrt.visits_reduce: lnscale must be contiguous float64 [", C, "] on the scene's device");
+    return visits_abi().reweight(s, wp, cnt, e, n_rows, lnscale->const_data_ptr<double>(), out.data_ptr<double>(),
+                                 hip_stream);
+}
+
 // paths_footprint: the first n records of a path list added into a footprint map on the list's device
 // (wgrt_paths_footprint).
 int64_t paths_footprint(const Tensor &paths, int64_t n, int64_t num_lmd, double fp_x0, double fp_y0, double fp_cell_x,
@@ -563,6 +667,19 @@ TORCH_LIBRARY(wgrt, m) {
     m.def("paths_footprint(Tensor paths, int n, int num_lmd, float fp_x0, float fp_y0, float fp_cell_x, float fp_cell_y, "
           "int fp_nx_cells, int fp_ny_cells, Tensor(a!) map, int stream) -> int",
           &paths_footprint);
+    // the same launch counting the taken branches of the counted rays (wgrt_trace_visits): slot int32 [n_rays] or None (ray
+    // i into row i), counts int32 [n_rows, C] added to, ends uint8 [n_rows, 32]
+    m.def("trace_visits(int scene, Tensor x, Tensor y, Tensor m, Tensor n, Tensor? lmd_num, Tensor te, Tensor tm, "
+          "Tensor delta_phase, Tensor(a!) rng_states, Tensor(b!)? matrix_EB, Tensor(c!)? stats, "
+          "Tensor(d!)? per_ray_bounces, int n_rays, int gid_offset, int stream, int kernel, int variant, "
+          "int workgroups, Tensor? chunk_order, int num_iter, Tensor? gid_blocks, int gid_block_rays, int debug, "
+          "float grid_sqrt_k, int plan, Tensor(e!)? table, Tensor? slot, int n_rows, Tensor(f!) counts, Tensor(g!) ends) "
+          "-> int",
+          &trace_visits);
+    // a visits table reduced into sensitivity tables (lnscale None) or a re-weighted window table
+    m.def("visits_reduce(int scene, int plan, Tensor counts, Tensor ends, int n_rows, Tensor? lnscale, Tensor(a!) out, "
+          "int stream) -> int",
+          &visits_reduce);
     m.def("chain_step(int chain) -> int", &chain_step);
     m.def("chain_end(int chain) -> int", &chain_end);
 }

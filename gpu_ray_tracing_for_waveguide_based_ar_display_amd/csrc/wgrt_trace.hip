@@ -95,6 +95,14 @@ __global__ __launch_bounds__(256) void trace_grid_paths_kernel(TraceArgs A) {
     add_stats(A.stats, c);
 }
 
+// The same counting the taken branches of the counted rays (wgrt_trace_visits with variant 1; wgrt_visits.h).
+__global__ __launch_bounds__(256) void trace_grid_visits_kernel(TraceArgs A) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    Counters c;
+    if (i < A.n_rays) trace_one<false, false, false, false, false, true>(A, i, c);
+    add_stats(A.stats, c);
+}
+
 // A counter set of the Jones-vector variants' launch scratch, each slot on its own 128-B line: the kHeads
 // work-queue heads, then the replay count, the out-coupling queue and full-block counts, and a single
 // launch's epilogue totals (a Counters record) and done count.
@@ -297,12 +305,16 @@ __device__ __host__ __forceinline__ uint32_t chain_tag(uint32_t serial, bool bro
 //        word of their own per replay-list entry (TraceArgs::fp_seen, part of the stream's launch scratch);
 //   kPaths  the draws recorded in the path list (or passed by, for a ray the launch does not record), in the
 //        footprint launch's word: the replay passes over them and numbers its records on from there;
+//   kVisits  the draws whose branch is counted (or passed by, for a ray the launch does not count), the in-coupling
+//        event's included, in the same word: the replay passes over them, so every branch is counted exactly once;
 //   every other mode has written nothing of an abandoned ray, and keeps no count.
 template <TraceMode M>
-constexpr bool kSeenCounted = M == TraceMode::kEv || M == TraceMode::kFp || M == TraceMode::kPaths;
+constexpr bool kSeenCounted =
+    M == TraceMode::kEv || M == TraceMode::kFp || M == TraceMode::kPaths || M == TraceMode::kVisits;
 template <TraceMode M>
 __device__ __forceinline__ uint32_t *seen_counts(const KArgs &K) {
-    static_assert(kSeenCounted<M>, "only the expected-value, footprint and paths launches count what the replay passes over");
+    static_assert(kSeenCounted<M>,
+                  "only the expected-value, footprint, paths and visits launches count what the replay passes over");
     if constexpr (M == TraceMode::kEv) return KA(q_i);
     else return KA(fp_seen);
 }
@@ -351,7 +363,7 @@ __device__ __forceinline__ void replay_tail(const KArgs &K, unsigned long long n
             if constexpr (kSeenCounted<M>)
                 skip = __hip_atomic_load(seen_counts<M>(K) + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             trace_one<M == TraceMode::kFate, M == TraceMode::kEv, M == TraceMode::kFp, M == TraceMode::kHits,
-                      M == TraceMode::kPaths>(
+                      M == TraceMode::kPaths, M == TraceMode::kVisits>(
                 R, (int64_t)__hip_atomic_load(list + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), c, nullptr, skip);
         }
     }
@@ -476,6 +488,13 @@ struct EvBlock {
 // hands the replay its count of recorded draws (record_abandoned), and has not retired here, so its end record is the
 // replay's.  Off everywhere else, where none of this exists.
 constexpr int kPathBlock = 64;   // records a wave stages before it reserves their indices: a pass adds at most one per lane
+// VISITS: a single launch that counts the taken branches of the counted rays per channel (wgrt_trace_visits;
+// wgrt_visits.h).  A lane reads its ray's slot when it takes the ray; a draw whose decision is certified adds 1 to its
+// channel in the ray's row with one unsigned global atomic whose result is not used (visit_count: no lane keeps the C
+// counters in registers or LDS; the rows of the few counted rays stay in L2), the branch read from where the draw led
+// (the FATE form of interact tells kDieIc apart); a draw that out-couples also writes the row's end record.  An
+// abandoned ray hands the replay its count of certified draws, the in-coupling event's included (record_abandoned).
+// The out-coupling itself is queued and binned as ever.  Off everywhere else, where none of this exists.
 // FP: a footprint launch (wgrt_trace_footprint; wgrt_footprint.h) counts every certified draw of the bounce loop into
 // the int64 plate map through a per-wave counter cache in LDS (fp_cached, fp_flush: wgrt_footprint_cache.h, shared
 // with the reduction of a path list); without it (wgrt_debug_set_footprint_aggregate(0)), one global atomic per count.
@@ -486,9 +505,10 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
     // the mode under the names the body tests (at most one of them is set)
     constexpr bool TL = M == TraceMode::kTimeline, LEARN = M == TraceMode::kLearn, CHAIN = M == TraceMode::kChain,
                    FATE = M == TraceMode::kFate, REPS = M == TraceMode::kReps, EV = M == TraceMode::kEv,
-                   FP = M == TraceMode::kFp, HITS = M == TraceMode::kHits, PATHS = M == TraceMode::kPaths;
+                   FP = M == TraceMode::kFp, HITS = M == TraceMode::kHits, PATHS = M == TraceMode::kPaths,
+                   VISITS = M == TraceMode::kVisits;
     static_assert(!FUSED || M == TraceMode::kPlain || TL, "only plain and timeline launches are built fused");
-    static_assert(!(FATE || REPS || EV || FP || HITS || PATHS) || WGRT_INKERNEL_REPLAY,
+    static_assert(!(FATE || REPS || EV || FP || HITS || PATHS || VISITS) || WGRT_INKERNEL_REPLAY,
                   "the sink modes are single launches whose replay runs in the kernel (replay_tail<M>)");
     // Single launches (!FUSED) do their epilogue in this kernel (above), and retire a finished trace at one
     // place per pass, right after advance(): the rays that ended in the previous pass's interaction (fin)
@@ -558,6 +578,8 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
     int pfill = 0;
     uint32_t p_seen = 0;
     int p_l = -1;
+    // VISITS: the same two words -- p_seen the certified draws of the trace in flight, the in-coupling event's included,
+    // and p_l the row the lane's ray is counted into (-1: it is not), read from its slot when the lane takes the ray
 
     // head x's items: stripes of kStripe consecutive chunks, stripe s on head s % 8, iteration-
     // major.  Every die gets a mix of all FoVs and wavelengths -- ray lifetimes differ by tile,
@@ -674,6 +696,11 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             p_seen = 0;
             const uint8_t *const sel = KA(select);
             p_l = (!sel || sel[L.i] != 0) ? (SINGLE ? 0 : (int)(L.tix / (uint32_t)(KA(nx) * KA(ny)))) : -1;
+        }
+        if constexpr (VISITS) {
+            p_seen = 0;
+            const int32_t *const slot = KA(vis_slot);
+            p_l = slot ? (int)slot[L.i] : (int)L.i;   // (a visits launch without slots has fewer than 2^31 rays)
         }
     };
     // a trace's counters are added when it ends: an abandoned trace (kUncertain) adds nothing, and its
@@ -850,7 +877,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             active = next >= 0;
             L.r.region = next >= 0 ? next : L.r.region;
             if (__builtin_expect(next == kUncertain, 0)) {
-                record_abandoned<M>(K, L.i, EV ? ev_seen : FP ? fp_seen : PATHS ? p_seen : 0u);
+                record_abandoned<M>(K, L.i, EV ? ev_seen : FP ? fp_seen : (PATHS || VISITS) ? p_seen : 0u);
             }
         } else {
             // one retire site for both ends of a trace (out-coupled, died)
@@ -900,8 +927,22 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             const double fpx = L.r.x, fpy = L.r.y;
             const int fpreg = L.r.region;
             const int next =
-                interact<SINGLE, AMP, FATE || FP || PATHS, EV>(A, K, loc, L, blk, kind, entry, sg, EV ? &evq : nullptr);
+                interact<SINGLE, AMP, FATE || FP || PATHS || VISITS, EV>(A, K, loc, L, blk, kind, entry, sg, EV ? &evq : nullptr);
             out = next == kOut;
+            if constexpr (VISITS) {
+                // counted once the decision is certified, the in-coupling event's draw too: the draw that abandons the
+                // ray is the replay's.  (blk and kind are still this draw's; a lost ray's draw counts nothing.)
+                if (next != kUncertain) {
+                    ++p_seen;
+                    if (p_l >= 0) {
+                        const int b = visit_branch(kind, next, next == kDieIc, out);
+                        visit_count(KA(vis_counts), KA(vis_ends), KA(vis_channels), (int64_t)p_l,
+                                    b >= 0 ? visit_channel(blk, b, A.nfc, A.noc) : -1, out,
+                                    out && eyebox_inside(KA(tiles) + (int64_t)L.tix * KA(tile_d), fpx, fpy), fpx, fpy, L.tix,
+                                    [&]() { return ray_gid_ka(K, (int64_t)L.i); });
+                    }
+                }
+            }
             if constexpr (PATHS) {
                 // recorded once the decision is certified, as FP counts: the draw that abandons the ray is the replay's
                 p_draw = !entry && next != kUncertain;
@@ -1465,6 +1506,7 @@ struct JonesKernels {
         add_single_amp<TraceMode::kFp, false>();
         add_single_amp<TraceMode::kHits, false>();
         add_single_amp<TraceMode::kPaths, false>();
+        add_single_amp<TraceMode::kVisits, false>();
     }
 };
 const void *jones_kernel(TraceMode m, bool byte, bool wide, bool fused, bool single, bool amp) {
@@ -1500,7 +1542,8 @@ wgrt_status query_trace_grids(wgrt_scene *s) {
                         // the sinks: never more workgroups than the plain launch of the same kind gets
                         const TraceMode mode = (TraceMode)m;
                         if (grid && (mode == TraceMode::kFate || mode == TraceMode::kReps || mode == TraceMode::kEv ||
-                                     mode == TraceMode::kFp || mode == TraceMode::kHits || mode == TraceMode::kPaths))
+                                     mode == TraceMode::kFp || mode == TraceMode::kHits || mode == TraceMode::kPaths ||
+                                     mode == TraceMode::kVisits))
                             grid = std::min(grid, s->jones_grid[(int)TraceMode::kPlain][b][c][f][g]);
                         s->jones_grid[m][b][c][f][g] = grid;
                     }
@@ -1713,6 +1756,13 @@ struct LaunchCfg {
     unsigned long long *paths_count = nullptr;
     uint32_t paths_tag = 0;
     const uint8_t *select = nullptr;
+    // wgrt_trace_visits: the rows' branch counts and end records, the rows there are and the batch's slots (vis_counts
+    // NULL: none; vis_slot NULL: ray i into row i).  A visits launch follows the hits launch's rules, and is not
+    // combined with fates, replicas, the expected-value estimator, footprints, hit lists or path lists.
+    uint32_t *vis_counts = nullptr;
+    wgrt_visit_end *vis_ends = nullptr;
+    const int32_t *vis_slot = nullptr;
+    int64_t vis_rows = 0;
     // set by validate_launch: the launch runs the byte-locator instantiation (byte_locator_applies)
     bool byte = false;
 };
@@ -1730,6 +1780,7 @@ TraceMode launch_mode(const LaunchCfg &c, bool timeline) {
            : c.fp_map                    ? TraceMode::kFp
            : c.hits                      ? TraceMode::kHits
            : c.paths                     ? TraceMode::kPaths
+           : c.vis_counts                ? TraceMode::kVisits
            : c.replicas                  ? TraceMode::kReps
            : c.mode == TraceMode::kLearn ? TraceMode::kLearn
                                          : TraceMode::kPlain;
@@ -1911,6 +1962,21 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
             return fail(WGRT_ERR_INVALID_ARGUMENT, "a paths launch takes no fates, replicas, expected-value estimator, "
                                                    "footprint map or hit list");
     }
+    if (c.vis_counts) {
+        if (!c.vis_ends) return fail(WGRT_ERR_INVALID_ARGUMENT, "visit counts need their end records");
+        if (c.vis_rows < 0) return fail(WGRT_ERR_INVALID_ARGUMENT, "n_rows must be >= 0");
+        if (((uintptr_t)c.vis_ends & 15) || ((uintptr_t)c.vis_counts & 3) || ((uintptr_t)c.vis_slot & 3))
+            return fail(WGRT_ERR_INVALID_ARGUMENT, "the end records must be 16-B aligned (the counts and slots 4-B)");
+        if (!c.vis_slot && (c.vis_rows < n_rays || n_rays > 0x7fffffffll))
+            return fail(WGRT_ERR_INVALID_ARGUMENT, "without slots ray i is counted into row i: need n_rays <= n_rows "
+                                                   "and fewer than 2^31 rays");
+        if (c.num_iter > 1)
+            return fail(WGRT_ERR_INVALID_ARGUMENT, "num_iter > 1 takes no visit counts: the rows are filled by single "
+                                                   "launches (trace the iterations one call each)");
+        if (c.fate || c.replicas || expected || c.fp_map || c.hits || c.paths)
+            return fail(WGRT_ERR_INVALID_ARGUMENT, "a visits launch takes no fates, replicas, expected-value estimator, "
+                                                   "footprint map, hit list or path list");
+    }
     if (c.chunk_order && c.variant == 1)
         return fail(WGRT_ERR_INVALID_ARGUMENT, "chunk_order needs variant 0, 7 or 9");
     if (c.gid_blocks && (c.gid_block_rays < 1 || gid_offset != 0))
@@ -1949,6 +2015,9 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
                                           "timeline");
     if (timeline && c.paths)
         return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel keeps no path list: trace with a path list or with "
+                                          "the timeline");
+    if (timeline && c.vis_counts)
+        return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel counts no branches: trace with visit counts or with "
                                           "the timeline");
     if ((c.replicas || expected) && c.variant != 1 && (int64_t)s->nl * s->nx * s->ny >= (int64_t)1 << kRepShift)
         return fail(WGRT_ERR_UNSUPPORTED, "replica tables with variants 7 / 9 need a scene of fewer than 2^24 tiles (the "
@@ -1989,6 +2058,10 @@ TraceArgs fill_args(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, 
     A.paths_count = c.paths_count;
     A.paths_tag = c.paths_tag;
     A.select = c.select;
+    A.vis_slot = c.vis_slot;
+    A.vis_counts = c.vis_counts;
+    A.vis_ends = c.vis_ends;
+    A.vis_channels = visit_channel_count(s->nfc, s->noc);
     A.n_rays = n_rays;
     A.gid_offset = gid_offset;
     A.gid_blocks = c.gid_blocks;
@@ -2045,6 +2118,7 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
         case TraceMode::kFate: hipLaunchKernelGGL(trace_grid_fate_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A); break;
         case TraceMode::kHits: hipLaunchKernelGGL(trace_grid_hits_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A); break;
         case TraceMode::kPaths: hipLaunchKernelGGL(trace_grid_paths_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A); break;
+        case TraceMode::kVisits: hipLaunchKernelGGL(trace_grid_visits_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A); break;
         default: hipLaunchKernelGGL(trace_grid_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
         }
         HIP_TRY(hipGetLastError());
@@ -2621,6 +2695,23 @@ wgrt_status wgrt_trace_paths(const wgrt_scene *s, const wgrt_rays *rays, int64_t
 }
 
 int32_t wgrt_path_vertex_bytes(void) { return (int32_t)sizeof(wgrt_path_vertex); }
+
+wgrt_status wgrt_trace_visits(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
+                              uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats, uint32_t *per_ray_bounces,
+                              void *stream, const wgrt_launch_opts *opts, const wgrt_window_plan *plan, double *table,
+                              const int32_t *slot, int64_t n_rows, uint32_t *counts, wgrt_visit_end *ends) {
+    if (!counts)   // no counts: exactly that call
+        return wgrt_trace_windows(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, opts,
+                                  plan, table);
+    LaunchCfg c;
+    const wgrt_status e = cfg_of_opts(s, opts, plan, table, c);
+    if (e != WGRT_OK) return e;
+    c.vis_counts = counts;
+    c.vis_ends = ends;
+    c.vis_slot = slot;
+    c.vis_rows = n_rows;
+    return trace_launch(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, c);
+}
 
 wgrt_status wgrt_debug_set_footprint_aggregate(int on) {
     g_fp_aggregate.store(on != 0, std::memory_order_relaxed);

@@ -17,6 +17,7 @@ enum class TraceMode : int {
     kFp,         // counts every draw into the footprint maps (wgrt_trace_footprint)
     kHits,       // appends one record per out-coupling to the hit list (wgrt_trace_hits)
     kPaths,      // appends one record per draw of the selected rays to the path list (wgrt_trace_paths)
+    kVisits,     // counts the taken branches of the counted rays per channel (wgrt_trace_visits)
     kCount
 };
 constexpr int kTraceModes = (int)TraceMode::kCount;

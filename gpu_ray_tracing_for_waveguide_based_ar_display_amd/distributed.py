@@ -487,7 +487,7 @@ def timed_run(trace_fn, rays, rng, eb, gid: GidMap, steps: int, per_call: int, s
 
 
 def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, replicas: int = 0,
-               expected: bool = False, footprint=None, hits=None, paths=None):
+               expected: bool = False, footprint=None, hits=None, paths=None, visits=None):
     """trace_fn for ``run_steps`` / ``trace_job`` using the HIP kernel (torch device tensors); ``stats``
     (int64[STATS_LEN] device tensor) is added to by every call.  A shard of several block ranges passes its global
     ids as ``gid_blocks``, uploaded once per map and device and kept on the map (``GidMap.device_blocks``).
@@ -530,9 +530,34 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, rep
     selected rays in the list (``engine.trace_fullcolor(paths=..., select=...)``), tagged like ``hits``.  For a class
     selection the call first runs a fate launch with no grid on a clone of the RNG states into the scratch table,
     builds the mask from its fates (``engine.select_by_fate``), and then runs the paths launch from the original
-    states.  Single launches only and no ``chain`` again; the ids are global, so the ranks' lists concatenate."""
-    from .engine import TraceChain, select_by_fate, trace_fullcolor
+    states.  Single launches only and no ``chain`` again; the ids are global, so the ranks' lists concatenate.
+
+    ``visits``: a record with ``plan`` (the job's ``engine.WindowPlan``), ``fate`` (uint8 per ray), ``windows`` (a scratch
+    plan and table), ``sens`` (float64 ``[C, n_slabs, W]``, added to; None: no sensitivities are wanted) and, for a what-if, ``scales`` (``{channel: s}``),
+    ``table`` (float64 ``[n_slabs, W]``, added to) and ``sums`` (float64 ``[2, num_lmd]``, added to: the weights' sum and
+    sum of squares): every call first runs a fate launch with no grid on a clone of the RNG states into the scratch table,
+    gives the rays of the ``eyebox`` class the rows 0, 1, ... (an exclusive cumsum of the mask), runs the visits launch
+    from the original states (``engine.trace_fullcolor(visits=...)``) and reduces its rows into ``sens`` (and ``table``).
+    Single launches only and no ``chain`` again; the tables are sums over rays, so the ranks' tables add."""
+    from .engine import TraceChain, VisitTable, select_by_fate, trace_fullcolor
     calls = [0]
+
+    def visits_for(rays, rng, gid):
+        """The visits launch's table and slots: the delivered rays, one row each."""
+        import torch
+        trace_fullcolor(scene, rays, rng.clone(), None, variant=variant, windows=visits.windows, fate=visits.fate,
+                        **ids_of(rng, gid))
+        mask = select_by_fate(visits.fate, "eyebox").to(torch.int32)
+        first = torch.cumsum(mask, 0, dtype=torch.int32) - mask          # exclusive
+        slot = torch.where(mask != 0, first, torch.full_like(first, -1))
+        return VisitTable(scene, int(mask.sum().item())), slot           # (synchronises)
+
+    def reduce_visits(vt):
+        if visits.sens is not None:
+            vt.sensitivity(visits.plan, out=visits.sens)
+        if getattr(visits, "scales", None) is not None:
+            vt.reweight(visits.plan, visits.scales, out=visits.table)
+            visits.sums += vt.weight_sums(visits.scales)
 
     def select_for(rays, rng, gid):
         """The paths launch's mask (None: every ray), the rays it names counted per wavelength."""
@@ -560,9 +585,13 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, rep
 
     def fn(rays, rng, eb, gid: GidMap, num_iter=1):
         more = {} if paths is None else dict(paths=(paths.list, calls[0]), select=select_for(rays, rng, gid))
+        if visits is not None:
+            more = dict(visits=visits_for(rays, rng, gid))
         trace_fullcolor(scene, rays, rng, eb, stats=stats, variant=variant, num_iter=num_iter, windows=windows,
                         fate=fate, replicas=replicas, expected=expected, footprint=footprint,
                         hits=None if hits is None else (hits, calls[0]), **more, **ids_of(rng, gid))
+        if visits is not None:
+            reduce_visits(more["visits"][0])
         calls[0] += 1
 
     def chain(rays, rng, eb, gid: GidMap):
@@ -571,7 +600,8 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, rep
         from ._lib import load
         return TraceChain(scene, rays, rng, eb, stats=stats, variant=variant, windows=windows,
                           gather=hasattr(load(), "wgrt_chain_gather"), **ids_of(rng, gid))
-    if fate is None and int(replicas or 0) < 2 and not expected and footprint is None and hits is None and paths is None:
+    if fate is None and int(replicas or 0) < 2 and not expected and footprint is None and hits is None and paths is None \
+            and visits is None:
         fn.chain = chain
     return fn
 

@@ -54,7 +54,7 @@ def trace_fullcolor(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_E
                     workgroups: int = 0, chunk_order: torch.Tensor | None = None, num_iter: int = 1,
                     gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
                     grid_sqrt_k: float = 0.0, windows=None, fate: torch.Tensor | None = None, replicas: int = 0,
-                    expected: bool = False, footprint=None, hits=None, paths=None, select=None) -> None:
+                    expected: bool = False, footprint=None, hits=None, paths=None, select=None, visits=None) -> None:
     """Asynchronous launch on ``stream`` (default: torch's current stream).
 
     rays: dict of device float32 tensors keyed like the reference columns
@@ -102,13 +102,21 @@ def trace_fullcolor(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_E
     as one record, and the end of a trace that leaves the plate or misses in R5 as one more; nothing else the launch
     leaves changes.  Single launches only; ``fate``, ``replicas``, ``expected``, ``footprint``, ``hits``,
     ``num_iter > 1`` and a ``TraceChain`` raise ``ValueError``.
+    visits: ``(visit_table, slot)``, a ``VisitTable`` on the scene's device and an int32 device tensor ``[n_rays]`` or
+    None (``wgrt_trace_visits``): ray i is counted into row ``slot[i]`` (negative: not counted; None: row i) -- every
+    Monte-Carlo draw that takes a branch adds 1 to its channel (``visit_channels``) in the row, and a ray that
+    out-couples leaves its row's end record; nothing else the launch leaves changes.  Raises ``ValueError`` if
+    ``slot.max() >= n_rows`` (the device does not validate slots; the check synchronises).  Single launches only;
+    ``fate``, ``replicas``, ``expected``, ``footprint``, ``hits``, ``paths``, ``num_iter > 1`` and a ``TraceChain``
+    raise ``ValueError``.
     """
     if scene.single_lambda:
         raise ValueError("trace_fullcolor needs a full-colour scene; use trace_single for a single-wavelength one")
     _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single=False, chunk_order=chunk_order, num_iter=num_iter, gid_blocks=gid_blocks,
            gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows, fate=fate,
-           replicas=replicas, expected=expected, footprint=footprint, hits=hits, paths=paths, select=select)
+           replicas=replicas, expected=expected, footprint=footprint, hits=hits, paths=paths, select=select,
+           visits=visits)
 
 
 def new_stats(device) -> torch.Tensor:
@@ -152,18 +160,19 @@ def trace_single(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_EB: 
                  workgroups: int = 0, chunk_order: torch.Tensor | None = None, num_iter: int = 1,
                  gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
                  grid_sqrt_k: float = 0.0, windows=None, fate: torch.Tensor | None = None, replicas: int = 0,
-                 expected: bool = False, footprint=None, hits=None, paths=None, select=None) -> None:
+                 expected: bool = False, footprint=None, hits=None, paths=None, select=None, visits=None) -> None:
     """One launch of the single-wavelength kernel (``process_rays_kernel_pro``, GRTF:419-831)
     through ``wgrt_trace_single_ex``: no ``lmd_num`` column (ignored if present),
     matrix_EB [NY, NX, 80, 120], branch guard ener * efficiency > 1e-15.  The scene must be
     a single-wavelength one (``Scene.from_geometry(..., wavelength=l)`` or 3-D LUTs).  ``windows``, ``fate``,
-    ``replicas``, ``expected``, ``footprint``, ``hits``, ``paths``, ``select``: as ``trace_fullcolor``."""
+    ``replicas``, ``expected``, ``footprint``, ``hits``, ``paths``, ``select``, ``visits``: as ``trace_fullcolor``."""
     if not scene.single_lambda:
         raise ValueError("trace_single needs a single-wavelength scene (Scene.from_geometry(..., wavelength=l))")
     _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single=True, chunk_order=chunk_order, num_iter=num_iter, gid_blocks=gid_blocks,
            gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows, fate=fate,
-           replicas=replicas, expected=expected, footprint=footprint, hits=hits, paths=paths, select=select)
+           replicas=replicas, expected=expected, footprint=footprint, hits=hits, paths=paths, select=select,
+           visits=visits)
 
 
 MAX_REPLICAS = 64   # WGRT_MAX_REPLICAS (include/wgrt.h)
@@ -567,6 +576,178 @@ def paths_footprint_host(records, fp: FootprintPlan, num_lmd: int, out=None) -> 
     return out
 
 
+VISIT_END_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("gid", "<i8"), ("tile", "<u4"), ("flags", "<u4")])   # wgrt_visit_end
+VISIT_INSIDE, VISIT_OUT = 1, 2   # wgrt_visit_end.flags: bit 0 inside the FoV's eyebox rectangle, bit 1 out-coupled
+
+
+def visit_channels(scene) -> list:
+    """The names of a scene's visit channels in index order (csrc/wgrt_visits.h; ``scene``: anything with
+    ``n_fc_slices`` and ``n_oc_slices``, or the pair itself): ``ic.b1, ic.b2`` the in-coupling event's two branches,
+    ``r0.b1 .. r1.b2`` the in-coupler states', ``r2[i].b1/.b2`` and ``r3[i].b1/.b2`` in fold-coupler slice i,
+    ``r4[i].b1/.b2/.b3`` and ``r5[i].b1/.b2/.b3`` in out-coupler slice i (``b3``: the out-coupling) --
+    ``6 + 4 n_fc_slices + 6 n_oc_slices`` of them."""
+    nfc, noc = (scene if isinstance(scene, (tuple, list)) else (scene.n_fc_slices, scene.n_oc_slices))
+    names = ["ic.b1", "ic.b2", "r0.b1", "r0.b2", "r1.b1", "r1.b2"]
+    for i in range(int(nfc)):
+        names += [f"r{r}[{i}].b{b}" for r in (2, 3) for b in (1, 2)]
+    for i in range(int(noc)):
+        names += [f"r{r}[{i}].b{b}" for r in (4, 5) for b in (1, 2, 3)]
+    return names
+
+
+def _lnscale(names, scales, device=None):
+    """``scales`` -- ``{channel name: s}`` or a length-C array / tensor of s -- as float64 ``log s`` per channel."""
+    if isinstance(scales, dict):
+        ln = np.zeros(len(names), dtype=np.float64)
+        for k, v in scales.items():
+            if k not in names:
+                raise ValueError(f"{k!r} is not a visit channel of this scene")
+            if not (float(v) > 0.0 and np.isfinite(float(v))):
+                raise ValueError(f"the scale of {k!r} must be positive and finite, got {v!r}")
+            ln[names.index(k)] = np.log(float(v))
+        out = torch.from_numpy(ln)
+    else:
+        out = torch.as_tensor(scales, dtype=torch.float64).detach().cpu().reshape(-1)
+        if out.numel() != len(names):
+            raise ValueError(f"scales must name channels or hold {len(names)} values, got {out.numel()}")
+        if not bool((out > 0).all()) or not bool(torch.isfinite(out).all()):
+            raise ValueError("every scale must be positive and finite")
+        out = out.log()
+    return out if device is None else out.to(device)
+
+
+class VisitTable:
+    """The rows of visits launches (``trace_*(visits=(visit_table, slot))``; ``wgrt_trace_visits``): ``counts``, an int32
+    ``[n_rows, C]`` device tensor (the library's uint32 words) that the launches add to, and ``ends``, a uint8
+    ``[n_rows, 32]`` device tensor of ``wgrt_visit_end`` records (``VISIT_END_DTYPE``: ``x, y, gid, tile, flags``) that
+    a counted ray writes when it out-couples.  ``clear()`` zeroes both (the launches never do).  ``channels``: the
+    names.  ``sensitivity(plan, out=None)`` adds, for every delivered row, its counts into float64
+    ``[C, n_slabs, W]`` tables (``wgrt_visits_sensitivity``): ``d table / d log s_c``, binned as the window table.
+    ``reweight(plan, scales, out=None)`` adds the rows re-weighted by ``prod_c s_c^N_c`` into a float64
+    ``[n_slabs, W]`` table (``wgrt_visits_reweight``; ``scales``: ``{channel name: s}`` or C values): the window table
+    of the design whose channels are scaled so, without a re-trace; with every scale 1, the launches' own table bit for
+    bit.  ``ess(scales)``: the effective sample size ``(sum w)^2 / sum w^2`` of those weights per wavelength (a float64
+    device tensor ``[num_lmd]``; 0 where nothing was delivered).  ``host()``: ``(counts uint32, ends)`` as numpy."""
+
+    def __init__(self, scene: Scene, n_rows: int, device=None):
+        self.n_rows = int(n_rows)
+        if self.n_rows < 0:
+            raise ValueError("n_rows must be >= 0")
+        self.scene = scene
+        self.channels = visit_channels(scene)
+        self.n_channels = len(self.channels)
+        if int(load().wgrt_visit_channels(scene.handle)) != self.n_channels:
+            raise WgrtError("the library's channel count differs from engine.visit_channels")
+        device = scene.device if device is None else device
+        self.device = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
+        if self.device.type == "cuda" and self.device.index is None:   # "cuda": the current device, named
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if self.device != torch.device("cuda", scene.device):
+            raise ValueError(f"the visit table is on {self.device}, the scene on device {scene.device}")
+        self.counts = torch.zeros((self.n_rows, self.n_channels), dtype=torch.int32, device=self.device)
+        self.ends = torch.zeros((self.n_rows, VISIT_END_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+
+    def clear(self) -> None:
+        self.counts.zero_()
+        self.ends.zero_()
+
+    def host(self):
+        return (self.counts.cpu().numpy().view(np.uint32).copy(),
+                self.ends.cpu().numpy().reshape(-1).view(VISIT_END_DTYPE).copy())
+
+    def _reduce(self, plan, lnscale, out, shape, stream):
+        if plan.device != self.scene.device:
+            raise ValueError(f"the plan is on device {plan.device}, the scene on device {self.scene.device}")
+        if out is None:
+            out = torch.zeros(shape, dtype=torch.float64, device=self.device)
+        else:
+            _as_dev(out, torch.float64, "out", self.device)
+            if tuple(out.shape) != shape:
+                raise ValueError(f"out shape {tuple(out.shape)} != {shape}")
+        check(ops().visits_reduce(self.scene.handle.value, plan.handle.value, self.counts, self.ends, self.n_rows,
+                                  lnscale, out, _stream_handle(self.device, stream)),
+              "wgrt_visits_sensitivity" if lnscale is None else "wgrt_visits_reweight")
+        return out
+
+    def sensitivity(self, plan: WindowPlan, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        n_slabs = self.scene.num_lmd * self.scene.ny * self.scene.nx
+        return self._reduce(plan, None, out, (self.n_channels, n_slabs, plan.W), stream)
+
+    def reweight(self, plan: WindowPlan, scales, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        n_slabs = self.scene.num_lmd * self.scene.ny * self.scene.nx
+        return self._reduce(plan, _lnscale(self.channels, scales, self.device), out, (n_slabs, plan.W), stream)
+
+    def weight_sums(self, scales) -> torch.Tensor:
+        """Float64 ``[2, num_lmd]``: per wavelength, the sum and the sum of squares of the delivered rows' weights
+        ``prod_c s_c^N_c`` (torch, from the same rows; sums of several tables add)."""
+        ln = _lnscale(self.channels, scales, self.device)
+        ends = self.ends[:self.n_rows].view(torch.int32)   # [n_rows, 8]: x, y, gid (two words each), tile, flags
+        on = (ends[:, 7] & VISIT_INSIDE) != 0
+        w = torch.exp(self.counts[:self.n_rows][on].double() @ ln)
+        l = (ends[on, 6].long() // (self.scene.nx * self.scene.ny)).clamp_(0, self.scene.num_lmd - 1)
+        out = torch.zeros((2, self.scene.num_lmd), dtype=torch.float64, device=self.device)
+        out[0].index_add_(0, l, w)
+        out[1].index_add_(0, l, w * w)
+        return out
+
+    def ess(self, scales) -> torch.Tensor:
+        return ess_of(self.weight_sums(scales))
+
+
+def ess_of(sums) -> torch.Tensor:
+    """The effective sample size ``(sum w)^2 / sum w^2`` per wavelength of ``VisitTable.weight_sums`` (0 where nothing
+    was delivered)."""
+    s1, s2 = sums[0], sums[1]
+    return torch.where(s2 > 0, s1 * s1 / s2.clamp_min(1e-300), torch.zeros_like(s1))
+
+
+def _visits_host(fn, name, counts, ends, nx, ny, num_lmd, scene_ranges, plan_mask, step_y, step_x, shape, out, *more):
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    ends = np.ascontiguousarray(ends, dtype=VISIT_END_DTYPE)
+    if counts.ndim != 2 or ends.shape != (counts.shape[0],):
+        raise ValueError("counts must be [n_rows, C] and ends [n_rows]")
+    rg = np.ascontiguousarray(scene_ranges, dtype=np.float64)
+    if rg.shape != (int(nx), int(ny), 4):
+        raise ValueError(f"scene_ranges must have shape {(int(nx), int(ny), 4)}")
+    mask = np.ascontiguousarray(plan_mask, dtype=np.float32)
+    if out is None:
+        out = np.zeros(shape, dtype=np.float64)
+    elif out.dtype != np.float64 or not out.flags.c_contiguous or out.shape != shape:
+        raise ValueError(f"out must be a C-contiguous float64 array of shape {shape}")
+    check(fn(int(nx), int(ny), int(num_lmd), counts.shape[1], rg.ctypes.data, mask.ctypes.data, mask.shape[0],
+             int(step_y), int(step_x), counts.ctypes.data, ends.ctypes.data, counts.shape[0], *more, out.ctypes.data), name)
+    return out
+
+
+def _window_width(mask, step_y, step_x):
+    ms = np.asarray(mask).shape[0]
+    return 1 + ((80 - ms) // int(step_y) + 1) * ((120 - ms) // int(step_x) + 1)
+
+
+def visits_sensitivity_host(counts, ends, nx: int, ny: int, num_lmd: int, scene_ranges, mask, step_y: int = 8,
+                            step_x: int = 12, out=None) -> np.ndarray:
+    """``VisitTable.sensitivity`` on the host (``wgrt_visits_sensitivity_host``; numpy arrays, no GPU needed) through the
+    same rule: ``counts`` uint32 ``[n_rows, C]``, ``ends`` a ``VISIT_END_DTYPE`` array, ``scene_ranges`` the scene's
+    ``eff_reg_FOV_range`` ``[nx, ny, 4]``, ``mask`` the plan's binary pupil mask.  Adds into ``out`` (float64
+    ``[C, num_lmd * ny * nx, W]``) when given."""
+    C = np.asarray(counts).shape[1]
+    shape = (C, int(num_lmd) * int(ny) * int(nx), _window_width(mask, step_y, step_x))
+    return _visits_host(load().wgrt_visits_sensitivity_host, "wgrt_visits_sensitivity_host", counts, ends, nx, ny, num_lmd,
+                        scene_ranges, mask, step_y, step_x, shape, out)
+
+
+def visits_reweight_host(counts, ends, lnscale, nx: int, ny: int, num_lmd: int, scene_ranges, mask, step_y: int = 8,
+                         step_x: int = 12, out=None) -> np.ndarray:
+    """``VisitTable.reweight`` on the host (``wgrt_visits_reweight_host``): ``lnscale`` float64 ``[C]``, ``log s`` per
+    channel.  Adds into ``out`` (float64 ``[num_lmd * ny * nx, W]``) when given."""
+    ln = np.ascontiguousarray(lnscale, dtype=np.float64)
+    if ln.shape != (np.asarray(counts).shape[1],):
+        raise ValueError("lnscale must hold one value per channel")
+    shape = (int(num_lmd) * int(ny) * int(nx), _window_width(mask, step_y, step_x))
+    return _visits_host(load().wgrt_visits_reweight_host, "wgrt_visits_reweight_host", counts, ends, nx, ny, num_lmd,
+                        scene_ranges, mask, step_y, step_x, shape, out, ln.ctypes.data)
+
+
 def _debug_opts(debug: dict | None):
     if not debug:
         return None
@@ -609,9 +790,24 @@ def _read_columns(rays, rng_states, n_rays, single, device):
 def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single, chunk_order=None, num_iter=1, gid_blocks=None, gid_block_rays=0, debug=None,
            grid_sqrt_k=0.0, windows=None, chain=False, fate=None, replicas=0, expected=False, footprint=None,
-           hits=None, paths=None, select=None):
+           hits=None, paths=None, select=None, visits=None):
     device = torch.device("cuda", scene.device)
     B = _replica_count(replicas)
+    if visits is not None:   # (before anything is read or launched)
+        if fate is not None or B or expected or footprint is not None or hits is not None or paths is not None:
+            raise ValueError("visits= is not combined with fate, replicas, expected, footprint, hits or paths")
+        if int(num_iter) > 1:
+            raise ValueError("visits= needs num_iter == 1: the rows are filled by single launches")
+        if chain:
+            raise ValueError("a chain takes no visits launches")
+        visit_table, visit_slot = visits
+        if not isinstance(visit_table, VisitTable):
+            raise TypeError("visits=(VisitTable, slot)")
+        if visit_table.device != device:
+            raise ValueError(f"the visit table is on {visit_table.device}, expected {device}")
+        if visit_table.n_channels != len(visit_channels(scene)):
+            raise ValueError(f"the visit table has {visit_table.n_channels} channels, the scene "
+                             f"{len(visit_channels(scene))}")
     if select is not None and paths is None:
         raise ValueError("select= chooses the rays of a paths launch: it needs paths=(PathList, tag)")
     if paths is not None:   # (before anything is read or launched)
@@ -708,6 +904,17 @@ def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ra
         if select.dtype == torch.bool:
             select = select.view(torch.uint8)
         _as_dev(select, torch.uint8, "select", device, N if N else None)
+    if visits is not None:
+        if visit_slot is None:
+            if N > visit_table.n_rows:
+                raise ValueError(f"without slots ray i is counted into row i: {N} rays need {N} rows, the table has "
+                                 f"{visit_table.n_rows}")
+        else:
+            _as_dev(visit_slot, torch.int32, "slot", device, x.numel())
+            top = int(visit_slot[:N].max()) if N else -1   # (the device does not validate slots; synchronises)
+            if top >= visit_table.n_rows:
+                raise ValueError(f"slot.max() = {top} is not below the table's "
+                                 f"{visit_table.n_rows} rows")
     dbg = _debug_opts(debug)
     # the launch: torch.ops.wgrt.trace (csrc/wgrt_torch.cpp) -> wgrt_trace_opts on the caller's stream; with a
     # window table torch.ops.wgrt.trace_windows -> wgrt_trace_windows
@@ -726,7 +933,11 @@ def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ra
         if h <= 0:   # the negated wgrt_status of the failure
             check(-h, "wgrt_chain_begin")
         return h, (args, dbg, windows)
-    if paths is not None:   # torch.ops.wgrt.trace_paths -> wgrt_trace_paths
+    if visits is not None:   # torch.ops.wgrt.trace_visits -> wgrt_trace_visits
+        status = ops().trace_visits(*args, plan.handle.value if windows is not None else 0,
+                                    table if windows is not None else None, visit_slot, visit_table.n_rows,
+                                    visit_table.counts, visit_table.ends)
+    elif paths is not None:   # torch.ops.wgrt.trace_paths -> wgrt_trace_paths
         status = ops().trace_paths(*args, plan.handle.value if windows is not None else 0,
                                    table if windows is not None else None, path_list.buffer, path_list.capacity,
                                    path_list.counter, int(path_tag_), select)
@@ -784,9 +995,12 @@ class TraceChain:
                  variant: int = VARIANT_AUTO, workgroups: int = 0, chunk_order: torch.Tensor | None = None,
                  gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
                  grid_sqrt_k: float = 0.0, windows=None, replicas: int = 0, expected: bool = False,
-                 gather: bool | int = False, hold: bool = False, footprint=None, hits=None, paths=None, select=None):
+                 gather: bool | int = False, hold: bool = False, footprint=None, hits=None, paths=None, select=None,
+                 visits=None):
         if scene.single_lambda:
             raise ValueError("TraceChain needs a full-colour scene")
+        if visits is not None:
+            raise ValueError("a chain takes no visits launches: fill a visit table with single launches")
         if hits is not None:
             raise ValueError("a chain takes no hits launches: fill a hit list with single launches")
         if paths is not None or select is not None:
@@ -1186,6 +1400,6 @@ def expected_weight(e1: float, e2: float, e3: float, en1: float, en2: float, en3
     return float(load().wgrt_expected_weight_host(e1, e2, e3, en1, en2, en3, threshold))
 
 
-__all__ = ["Scene", "WindowPlan", "FootprintPlan", "footprint_bin", "FOOTPRINT_CHANNELS", "PathList", "PathListOverflow", "check_paths", "paths_footprint_host", "sort_paths", "path_polylines", "path_state", "path_kind", "path_lmd", "path_tag", "PATH_DTYPE", "PATH_KINDS", "select_by_fate", "HitList", "HitListOverflow", "check_hits", "hits_grid_host", "sort_hits", "hit_inside", "hit_tag", "hit_lmn", "HIT_DTYPE", "TraceChain", "fold_replicas", "expected_weight", "MAX_REPLICAS", "fate_census", "fate_census_host", "fate_col", "loss_budget", "FATE_CLASSES", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
+__all__ = ["VisitTable", "visit_channels", "ess_of", "visits_sensitivity_host", "visits_reweight_host", "VISIT_END_DTYPE", "Scene", "WindowPlan", "FootprintPlan", "footprint_bin", "FOOTPRINT_CHANNELS", "PathList", "PathListOverflow", "check_paths", "paths_footprint_host", "sort_paths", "path_polylines", "path_state", "path_kind", "path_lmd", "path_tag", "PATH_DTYPE", "PATH_KINDS", "select_by_fate", "HitList", "HitListOverflow", "check_hits", "hits_grid_host", "sort_hits", "hit_inside", "hit_tag", "hit_lmn", "HIT_DTYPE", "TraceChain", "fold_replicas", "expected_weight", "MAX_REPLICAS", "fate_census", "fate_census_host", "fate_col", "loss_budget", "FATE_CLASSES", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
            "trace_fullcolor", "trace_single", "init_rays", "schedule_by_lifetime",
            "rays_to_device", "classify_points", "shadow", "selftest_math", "RAY_COLUMNS", "_lib"]

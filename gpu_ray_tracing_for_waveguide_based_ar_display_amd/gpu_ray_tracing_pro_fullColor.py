@@ -27,6 +27,9 @@ Same flow as the reference script, on the MI355X kernel:
    plate map -- where the light interacts, is lost and leaves (``wgrt_trace_footprint``);
    with ``paths="eyebox"`` (``--paths eyebox``; any fate class, or ``all``) the draws of the selected rays are kept as
    records -- which way that light went (``wgrt_trace_paths``) -- and reduced to a conditional footprint on request;
+   with ``sensitivity=True`` (``--sensitivity``) the branches the delivered rays took are counted per channel
+   (``wgrt_trace_visits``): which grating to change; with ``what_if={channel: scale}`` (``--what-if``) the same rays,
+   re-weighted, give the figures of the scaled design without a re-trace;
 6. the "Eyebox Center View.png" export (MAIN:199-203): the evaluated image at the first eye row,
    last eye column, as 8-bit RGB, rows flipped (``eyebox_center_view``, written without OpenCV).
 
@@ -60,7 +63,8 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
         fuse: bool | None = None, points: np.ndarray | None = None, png: str | None = None,
         eyebox: str = "host", keep_grid: bool = False, evaluate_on: str = "host",
         keep_image: bool = False, budget: bool = False, error_bars: int = 0, estimator: str = "analog",
-        footprint=None, hits=None, paths=None, paths_capacity=None, paths_footprint=None) -> dict:
+        footprint=None, hits=None, paths=None, paths_capacity=None, paths_footprint=None, sensitivity=None,
+        what_if=None) -> dict:
     """The reference script's job on this engine; returns its printed quantities and arrays.
     ``points``: the R/2 in-coupler origins to use (default: sampled, GRTF:12-23, seeded by
     ``point_seed``); ``png``: where to write the "Eyebox Center View" image (needs ``evaluate``).
@@ -161,7 +165,57 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
     bounding box (``PathList.footprint``: the conditional footprint of the selected rays), returned as
     ``paths_footprint`` / ``paths_footprint_plan``.  Works with every ``eyebox`` mode; everything else returned is
     bit-identical to the run without it.  ``budget=True``, ``error_bars``, ``estimator="expected"``, ``footprint`` and
-    ``hits`` with it raise ``ValueError`` before any GPU work."""
+    ``hits`` with it raise ``ValueError`` before any GPU work.
+
+    ``sensitivity``: ``True`` or K (None: off; needs ``eyebox="windows"``): also the design sensitivities.  A ray reaches
+    the eyebox with probability ``prod e_taken``, so for a delivered ray ``d log p / d log s_c = N_c``, the times it
+    took channel c -- a (state, coupler slice, branch) triple, ``engine.visit_channels``.  The traces go as plain single
+    launches.  Each iteration clones the RNG states, runs a fate launch with no grid on the clone, gives the rays of the
+    ``eyebox`` class one row each, runs the visits launch from the original states (``engine.VisitTable``,
+    ``engine.trace_fullcolor(visits=...)``) and reduces its rows on the device into one float64 ``[C, n_slabs, 57]``
+    table (``VisitTable.sensitivity``): ``d table / d log s_c``, binned exactly as the window table; several GPUs sum
+    theirs.  Returned as ``sensitivity`` and ``sensitivity_channels`` (the names), and printed per wavelength: the K
+    (default 8) channels of largest elasticity ``sum_slabs sens[c, s, 0] / sum_slabs table[s, 0]`` -- the mean visits per
+    delivered ray: the % change of that wavelength's efficiency per % change of the channel's efficiency.
+
+    ``what_if``: ``{channel name: scale}`` (None: off; needs ``eyebox="windows"``): each iteration also re-weights its
+    delivered rays by ``prod_c s_c^N_c`` into a second window table (``VisitTable.reweight``) -- the table of the design
+    whose channels' efficiencies are scaled so, unbiased while every ``e1 + e2 + e3`` stays <= 1.  After
+    the baseline's figures the same efficiencies and evaluation are printed for that table, with the weights' effective
+    sample size per wavelength.  Returned as ``what_if``: ``scales``, ``table``, ``A``, ``efficiency``, ``ess`` and, with
+    ``evaluate``, ``delta_e``, ``U_fov``, ``U_EB``.
+
+    Both work together and leave everything else returned bit-identical to the run without them.  ``budget=True``,
+    ``error_bars``, ``estimator="expected"``, ``footprint``, ``hits`` and ``paths`` with either raise ``ValueError``
+    before any GPU work."""
+    top_k = 0
+    if sensitivity is None or sensitivity is False:
+        sensitivity = None
+    else:
+        top_k = 8 if sensitivity is True else sensitivity
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or int(top_k) < 1:
+            raise ValueError(f"sensitivity must be True or the number K >= 1 of channels to print, got {sensitivity!r}")
+        top_k = int(top_k)
+    if what_if is not None:
+        if not isinstance(what_if, dict) or not what_if:
+            raise ValueError(f"what_if must be a dict {{channel name: scale}}, got {what_if!r}")
+        from .luts import channel_quad
+        for name, sc_ in what_if.items():
+            try:
+                channel_quad(name)
+                ok = float(sc_) > 0.0 and np.isfinite(float(sc_))
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f"what_if: {name!r}={sc_!r} is not a visit channel with a positive finite scale")
+        what_if = {str(k): float(v) for k, v in what_if.items()}
+    if sensitivity is not None or what_if is not None:
+        if budget or error_bars or estimator == "expected" or footprint is not None or \
+                not (hits is None or hits is False) or not (paths is None or paths is False):
+            raise ValueError("sensitivity / what_if are not combined with budget=True, error_bars, estimator='expected', "
+                             "footprint, hits or paths: a launch counts branch visits or does one of those")
+        if eyebox != "windows":
+            raise ValueError("sensitivity / what_if reduce into window tables: they need eyebox='windows'")
     path_classes = None   # the fate classes of a selection (None: none, or every ray)
     if paths is None or paths is False:
         paths = None
@@ -264,11 +318,30 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
                 job.paths.windows = (scratch, scratch.new_table(job.scene))
                 if auto:
                     job.paths.bounces = torch.zeros(job.shard.n_rays, dtype=torch.int32, device=job.dev)
+        job.visits = None
+        if sensitivity is not None or what_if is not None:
+            import torch
+
+            from .engine import WindowPlan, visit_channels
+            names = visit_channels(job.scene)
+            if what_if is not None and not set(what_if) <= set(names):
+                raise ValueError(f"what_if names no visit channel of this scene: {sorted(set(what_if) - set(names))}")
+            n_slabs, W = job.windows[1].shape
+            scratch = WindowPlan(device=job.dev.index)
+            job.visits = SimpleNamespace(
+                plan=job.windows[0], fate=torch.zeros(job.shard.n_rays, dtype=torch.uint8, device=job.dev),
+                windows=(scratch, scratch.new_table(job.scene)), channels=names,
+                sens=(torch.zeros((len(names), n_slabs, W), dtype=torch.float64, device=job.dev)
+                      if sensitivity is not None else None), scales=what_if,
+                table=torch.zeros((n_slabs, W), dtype=torch.float64, device=job.dev) if what_if is not None else None,
+                sums=torch.zeros((2, job.scene.num_lmd), dtype=torch.float64, device=job.dev))
         try:
             kern_s = _trace(job, variant, fuse)
         finally:
             if job.paths is not None and job.paths.windows is not None:
                 job.paths.windows[0].close()
+            if job.visits is not None:
+                job.visits.windows[0].close()
         t_post = time.perf_counter()   # everything below is post-processing of the traced grid
         grid, table, stats = _collect(job, eyebox != "host", keep_grid)
         reps = None
@@ -293,6 +366,12 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
                 from .engine import FootprintPlan
                 pfp = FootprintPlan.for_scene(job.geom, cells=paths_footprint)
                 path_map = reduce_eyebox(job.paths.list.footprint(job.scene, pfp))
+        sens = wtable = wsums = None
+        if job.visits is not None:   # sums over rays: the ranks' tables add
+            from .distributed import reduce_eyebox
+            sens = reduce_eyebox(job.visits.sens) if job.visits.sens is not None else None
+            if what_if is not None:
+                wtable, wsums = reduce_eyebox(job.visits.table), reduce_eyebox(job.visits.sums)
         if job.rank != 0:
             return out
         _report(job, out, grid, table, reps)
@@ -306,6 +385,10 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
             _report_paths(job, out, path_records, path_sel, path_map, pfp if path_map is not None else None)
         if evaluate:
             _evaluate(job, out, grid, table, evaluate_on, keep_image, png, reps)
+        if sens is not None and sensitivity is not None:
+            _report_sensitivity(job, out, sens, table, top_k)
+        if wtable is not None:
+            _report_what_if(job, out, what_if, wtable, wsums, evaluate, evaluate_on)
         out["post_seconds"] = time.perf_counter() - t_post
         job.say(f"Post-processing time  : {out['post_seconds']:.4f} s  (eyebox reduced "
                 f"{'by the trace' if eyebox == 'windows' else 'on the ' + eyebox})")
@@ -397,6 +480,8 @@ def _trace(job, variant, fuse) -> float:
         per_call = 1
     if getattr(job, "paths", None) is not None:           # ... or a path list
         per_call = 1
+    if getattr(job, "visits", None) is not None:          # ... or counts branch visits
+        per_call = 1
     calls = split_calls(job.num_iter, per_call)
     if n_rays and calls:
         reserve(job.scene, n_rays, max(calls))
@@ -405,7 +490,8 @@ def _trace(job, variant, fuse) -> float:
     if n_rays:
         run_steps(hip_tracer(job.scene, variant, job.stats, job.windows, fate=job.fate, replicas=job.replicas,
                              expected=getattr(job, "expected", False), footprint=getattr(job, "footprint", None),
-                             hits=getattr(job, "hits", None), paths=getattr(job, "paths", None)),
+                             hits=getattr(job, "hits", None), paths=getattr(job, "paths", None),
+                             visits=getattr(job, "visits", None)),
                   job.rays, job.rng, job.eb,
                   job.shard.gid, job.num_iter, per_call, hook=hook)
     t1.record()
@@ -462,6 +548,57 @@ def _report_budget(job, out: dict, census) -> None:
     for name, _, _ in FATE_CLASSES:
         row = [w["fractions"][name] for w in b["per_wavelength"]] + [b["total"]["fractions"][name]]
         job.say(f"  {name:18s}" + "".join(f"{v * 100:9.3f}%" for v in row))
+
+
+def _report_sensitivity(job, out: dict, sens, table, top_k: int) -> None:
+    """The sensitivity tables into ``out`` and, per wavelength, the ``top_k`` channels of largest elasticity printed: the
+    visits of channel c per delivered ray, ``sum_slabs sens[c, s, 0] / sum_slabs table[s, 0]``."""
+    out["sensitivity"] = s = sens.cpu().numpy()
+    out["sensitivity_channels"] = list(job.visits.channels)
+    nl = job.scene.num_lmd
+    per = s[:, :, 0].reshape(s.shape[0], nl, -1).sum(axis=2)                 # [C, num_lmd]
+    tot = table[:, 0].cpu().numpy().reshape(nl, -1).sum(axis=1)              # [num_lmd]
+    names = {0: "Blue", 1: "Green", 2: "Red"}
+    job.say(f"Design sensitivities: the {top_k} channels of largest elasticity (% efficiency per % of the channel)")
+    for l in range(nl):
+        el = per[:, l] / tot[l] if tot[l] else np.zeros(s.shape[0])
+        order = np.argsort(-el, kind="stable")[:top_k]
+        job.say(f"  {names.get(l, str(l)):6s}" + "".join(f"  {job.visits.channels[c]}={el[c]:.3f}" for c in order))
+
+
+def _report_what_if(job, out: dict, scales: dict, wtable, wsums, evaluate: bool, evaluate_on: str) -> None:
+    """The what-if table's figures into ``out["what_if"]`` and printed: the efficiencies and the evaluation ``_report``
+    and ``_evaluate`` give for the baseline's table, and the weights' effective sample size."""
+    from .AR_system_evaluation_functions import (evaluation_from_perceive, evaluation_from_window_sums,
+                                                 perceive_from_window_sums)
+    from .engine import ess_of
+    shape = job.scene.eb_shape()
+    A = wtable[:, 0].cpu().numpy().reshape(shape[:-2]).astype(np.float32) / job.num_rays / job.num_iter
+    names = {0: "Blue", 1: "Green", 2: "Red"}
+    eff = {names.get(k, str(k)): float(np.sum(A[k] * 3)) for k in range(A.shape[0])}
+    ess = ess_of(wsums).cpu().numpy()
+    w = dict(scales=dict(scales), table=wtable.cpu().numpy(), A=A, efficiency=eff, ess=ess)
+    job.say("What if " + ", ".join(f"{k} x {v:g}" for k, v in scales.items()) + " (the same rays, re-weighted)")
+    if any(v > 1.0 for v in scales.values()):
+        # (a scale above 1 can push a state's e1 + e2 + e3 past 1, where the scaled design gains less than the weights
+        # say: the figures below are then too high; DESIGN.md 4.10 has the size of it on the synthetic LUTs)
+        job.say("  note: scaled up -- unbiased only where the state's branch efficiencies still sum to <= 1; "
+                "check the scaled LUTs (luts.scale_channel) or confirm with a direct run")
+    for c in ("Red", "Green", "Blue"):
+        if c in eff:
+            k = {v: i for i, v in names.items()}[c]
+            job.say(f"Efficiency ({c:5s})    : {eff[c] * 100:8.3f} %  (effective sample size {ess[k]:,.0f})")
+    if evaluate:
+        divisor = job.R * job.num_iter
+        if evaluate_on == "device":
+            *figures, _ = evaluation_from_window_sums(wtable, shape, divisor, image="center")
+        else:
+            *figures, _ = evaluation_from_perceive(perceive_from_window_sums(w["table"], shape, divisor))
+        w["delta_e"], w["U_fov"], w["U_EB"] = (float(v) for v in figures)
+        job.say(f"Color dispersion      : {w['delta_e']:8.2f}")
+        job.say(f"FoV uniformity        : {w['U_fov'] * 100:8.2f} %")
+        job.say(f"Eyebox uniformity     : {w['U_EB'] * 100:8.2f} %")
+    out["what_if"] = w
 
 
 def _gather_paths(job):
@@ -702,6 +839,15 @@ def main(argv=None):
     ap.add_argument("--paths-out", default="", metavar="FILE.npy", help="save the path records there (numpy structured array)")
     ap.add_argument("--paths-footprint", default="", metavar="HxW",
                     help="also reduce the path list into a footprint map of H x W cells: the conditional footprint")
+    ap.add_argument("--sensitivity", nargs="?", const=8, default=None, type=int, metavar="K",
+                    help="also count the branches the delivered rays took per channel (state, coupler slice, branch) and "
+                         "print, per wavelength, the K (default 8) channels whose efficiency the result is most sensitive "
+                         "to; needs --eyebox windows; not with --budget, --error-bars, --estimator expected, --footprint, "
+                         "--hits or --paths")
+    ap.add_argument("--sensitivity-out", default="", metavar="FILE.npy", help="save the sensitivity tables there (numpy)")
+    ap.add_argument("--what-if", default="", metavar="CHANNEL=SCALE[,...]",
+                    help="also the figures of the design whose channels' efficiencies are scaled so, from the same rays "
+                         "re-weighted, e.g. 'r4[2].b3=1.2,r2[0].b2=0.9'; needs --eyebox windows")
     ap.add_argument("--budget", action="store_true",
                     help="also report where every ray ended: per-ray fates, their per-tile census and the loss budget "
                          "per wavelength (the traces then run as plain single launches)")
@@ -731,6 +877,19 @@ def main(argv=None):
         if len(hw) != 2:
             ap.error(f"{flag} takes HxW, got {text!r}")
         return hw
+    what_if = None
+    if a.what_if:
+        what_if = {}
+        for item in a.what_if.split(","):
+            name, eq, value = item.partition("=")
+            try:
+                what_if[name.strip()] = float(value)
+            except ValueError:
+                eq = ""
+            if not eq or not name.strip():
+                ap.error(f"--what-if takes CHANNEL=SCALE[,CHANNEL=SCALE...], got {a.what_if!r}")
+    if a.sensitivity is not None and a.sensitivity < 1:
+        ap.error(f"--sensitivity takes the number K >= 1 of channels to print, got {a.sensitivity}")
     footprint = cells("--footprint", a.footprint)
     paths_footprint = cells("--paths-footprint", a.paths_footprint)
     res = run(a.num_fov_x, a.num_fov_y, a.rays_per_fov, a.num_iter, lut_dir=a.lut_dir, lut_seed=a.lut_seed,
@@ -739,7 +898,10 @@ def main(argv=None):
               png=a.png or None, eyebox=a.eyebox, evaluate_on=a.evaluate, budget=a.budget, error_bars=a.error_bars, estimator=a.estimator,
               footprint=footprint, hits=None if a.hits is None else (True if a.hits < 0 else a.hits),
               paths=None if not a.paths else (a.paths.split(",") if "," in a.paths else a.paths),
-              paths_capacity=a.paths_capacity, paths_footprint=paths_footprint)
+              paths_capacity=a.paths_capacity, paths_footprint=paths_footprint, sensitivity=a.sensitivity,
+              what_if=what_if)
+    if a.sensitivity_out and "sensitivity" in res:   # (rank 0 has the tables)
+        np.save(a.sensitivity_out, res["sensitivity"])
     if a.footprint_out and "footprint" in res:   # (rank 0 has the map)
         np.save(a.footprint_out, res["footprint"])
     if a.hits_out and "hits" in res:   # (rank 0 has the list)
@@ -748,6 +910,9 @@ def main(argv=None):
         np.save(a.paths_out, res["paths"])
     if a.json and (not dist.is_initialized() or dist.get_rank() == 0):
         keep = {k: v for k, v in res.items() if isinstance(v, (int, float, dict, str))}
+        if "what_if" in keep:   # (its arrays stay out, as the top level's do; the ESS goes as a list)
+            keep["what_if"] = {k: (v.tolist() if k == "ess" else v) for k, v in keep["what_if"].items()
+                               if k == "ess" or isinstance(v, (int, float, dict, str))}
         with open(a.json, "w") as f:
             json.dump(keep, f, indent=1)
     if dist.is_initialized():

@@ -314,3 +314,52 @@ def single_wavelength(luts: dict, lut_TIR: np.ndarray, lut_gap: np.ndarray, l: i
     for k in ("lut_fc1", "lut_fc2", "lut_oc1", "lut_oc2"):
         out[k] = np.ascontiguousarray(luts[k][:, l])
     return out, np.ascontiguousarray(lut_TIR[l]), np.ascontiguousarray(lut_gap[l])
+
+
+# The visit channels (csrc/wgrt_visits.h; engine.visit_channels): per state, its LUT and the coefficient quadruple of
+# each branch -- the four channels one E_field_cal call of that branch reads (GRTF:860-1246).
+_CHANNEL_QUADS = {
+    "ic": ("lut_ic1", ((13, 18, 33, 38), (15, 20, 35, 40))),
+    "r0": ("lut_ic2", ((4, 9, 24, 29), (6, 11, 26, 31))),
+    "r1": ("lut_ic3", ((2, 22, 7, 27), (4, 9, 24, 29))),
+    "r2": ("lut_fc1", ((3, 6, 15, 18), (2, 5, 14, 17))),
+    "r3": ("lut_fc2", ((4, 7, 16, 19), (3, 6, 15, 18))),
+    "r4": ("lut_oc1", ((4, 9, 24, 29), (2, 7, 22, 27), (13, 18, 33, 38))),
+    "r5": ("lut_oc2", ((6, 11, 26, 31), (4, 9, 24, 29), (15, 20, 35, 40))),
+}
+
+
+def channel_quad(name: str):
+    """``(lut name, slice index or None, the four channel numbers)`` of a visit channel such as ``"ic.b1"``,
+    ``"r2[3].b2"`` or ``"r4[2].b3"`` (``engine.visit_channels``)."""
+    import re
+    m = re.fullmatch(r"(ic|r[0-5])(?:\[(\d+)\])?\.b([123])", name)
+    if not m or (m.group(2) is None) != (m.group(1) in ("ic", "r0", "r1")):
+        raise ValueError(f"{name!r} is not a visit channel (ic.b1, r0.b2, r2[i].b1, r4[i].b3, ...)")
+    lut, quads = _CHANNEL_QUADS[m.group(1)]
+    b = int(m.group(3)) - 1
+    if b >= len(quads):
+        raise ValueError(f"{name!r}: that state has {len(quads)} branches")
+    return lut, (None if m.group(2) is None else int(m.group(2))), quads[b]
+
+
+def scale_channel(luts: dict, name: str, s: float, lmd: int | None = None) -> dict:
+    """A copy of the LUT dict with the Jones coefficient quadruple of visit channel ``name`` multiplied by ``sqrt(s)``,
+    in every tile or (``lmd``) in that wavelength's tiles only: the branch's efficiency is multiplied by ``s``, the
+    normalised field it hands on and every other branch's efficiency are unchanged.  Only the named LUT is copied.
+    Full-colour LUT shapes (``[L, NX, NY, C]`` / ``[n_slices, L, NX, NY, C]``)."""
+    lut, sl, quad = channel_quad(name)
+    if not (float(s) > 0.0 and np.isfinite(float(s))):
+        raise ValueError(f"the scale must be positive and finite, got {s!r}")
+    out = dict(luts)
+    a = np.array(luts[lut], copy=True)
+    if sl is not None and not 0 <= sl < a.shape[0]:
+        raise ValueError(f"{name!r}: the LUT has {a.shape[0]} slices")
+    tiles = a if sl is None else a[sl]          # [L, NX, NY, C]
+    if lmd is not None:
+        if tiles.ndim != 4 or not 0 <= int(lmd) < tiles.shape[0]:
+            raise ValueError(f"lmd={lmd!r} out of range for {lut}")
+        tiles = tiles[int(lmd)]
+    tiles[..., list(quad)] *= np.sqrt(float(s))
+    out[lut] = a
+    return out

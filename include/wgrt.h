@@ -703,6 +703,79 @@ wgrt_status wgrt_paths_footprint(const wgrt_path_vertex *paths, int64_t n, int32
 wgrt_status wgrt_paths_footprint_host(const wgrt_path_vertex *paths, int64_t n, int32_t num_lmd,
                                       const wgrt_footprint_plan *fp, int64_t *map);
 
+/* Branch visit counts: design sensitivities and what-if window tables from one ordinary trace (new symbols within ABI
+ * 9, looked up by name; the channel table and the rule are stated once in csrc/wgrt_visits.h).
+ *
+ * A channel is (state, coupler slice, branch) -- one quadruple of Jones coefficients of one LUT; a scene has
+ * C = wgrt_visit_channels(scene) = 6 + 4 n_fc_slices + 6 n_oc_slices of them: 0, 1 the in-coupling event's two
+ * branches; 2, 3 R0's; 4, 5 R1's; 6 + 4 i + {0, 1} R2's and + {2, 3} R3's in fold-coupler slice i; B + 6 i + {0, 1, 2}
+ * R4's and + {3, 4, 5} R5's in out-coupler slice i (B = 6 + 4 n_fc_slices; the third branch is the out-coupling).
+ *
+ * wgrt_trace_visits is wgrt_trace_windows that also counts the branches of counted rays.  Ray i is counted into row
+ * slot ? slot[i] : i; a negative slot: the ray is not counted.  The device does not validate slots: every non-negative
+ * one must be below n_rows.
+ *   counts    DEVICE uint32 [n_rows, C].  Every Monte-Carlo draw of a counted ray that takes a branch, the in-coupling
+ *             event's included, adds 1 to counts[row, c] of its channel; a draw that loses the ray adds nothing; a draw
+ *             whose second in-coupler branch leaves the in-coupler (fate reason 6) still counts its b2.  ADDED to, never
+ *             zeroed.  NULL: the call is exactly wgrt_trace_windows (slot, n_rows and ends are not looked at).
+ *   ends      DEVICE wgrt_visit_end [n_rows], 16-byte aligned, required with counts.  Written once, as two 16-byte
+ *             stores, when a counted ray's last draw out-couples: the position before the move (wgrt_hit's), the global
+ *             id, the tile index, flags bit 1 (out-coupled) and bit 0 (inside the FoV's eyebox rectangle).  The row of a
+ *             ray that did not out-couple is not touched: the caller zeroes the array.
+ * Every other output -- rng_states, matrix_EB, the window table, per_ray_bounces, every field of stats -- is the bytes
+ * of the same launch without counts.  A visits launch is a single launch, as hits and paths launches are:
+ * opts->num_iter > 1 is WGRT_ERR_INVALID_ARGUMENT, wgrt_chain_begin takes none, no entry point combines it with fates,
+ * replicas, the expected-value estimator, footprints, hit lists or path lists, wgrt_debug_opts.timeline is
+ * WGRT_ERR_UNSUPPORTED, and it never learns the scene's tile table; n_rows < 0 and a misaligned ends are
+ * WGRT_ERR_INVALID_ARGUMENT.  It works with opts->gid_blocks (rows are local) and with wgrt_trace_single scenes.  The
+ * Jones lane counts a draw once its decision is certified; a ray it abandons is re-traced on the exact lane, which
+ * passes over the draws already counted, so every branch is counted exactly once.  The counts are unsigned adds whose
+ * result is not used.  Asynchronous on stream.  A launch through any other entry point runs the kernels it ran before
+ * this one existed. */
+typedef struct __attribute__((aligned(16))) wgrt_visit_end {   /* 32 bytes */
+    double x, y;               /* the out-coupling position: the ray's position at its last draw */
+    int64_t gid;               /* global ray id: gid_offset + i, or the id opts->gid_blocks gives ray i */
+    uint32_t tile;             /* (lambda * nx + m) * ny + n */
+    uint32_t flags;            /* bit 0: inside the FoV's eyebox rectangle (delivered); bit 1: out-coupled */
+} wgrt_visit_end;
+int32_t wgrt_visit_channels(const wgrt_scene *scene);   /* C; -1 for a NULL scene */
+wgrt_status wgrt_trace_visits(const wgrt_scene *scene, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
+                              uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats, uint32_t *per_ray_bounces,
+                              void *stream, const wgrt_launch_opts *opts, const wgrt_window_plan *plan, double *table,
+                              const int32_t *slot, int64_t n_rows, uint32_t *counts, wgrt_visit_end *ends);
+/* The two reductions of a table of counted rays, on the scene's device.  A row is delivered when flag bit 0 of its end
+ * record is set; its eyebox bin is computed from x, y and the tile exactly as the trace computes it, and a deposit goes
+ * to column 0 of the bin's slab and to every window of `plan` that holds the bin -- the window sink's own membership
+ * (an aliased offset gives the slab; an offset outside the buffer is dropped).
+ *   _sensitivity  sens DEVICE float64 [C, n_slabs, W], ADDED to: for every delivered row and every c with
+ *                 counts[row, c] > 0, the count is deposited into sens[c].  One wave per row, the lanes striding over the
+ *                 channels.  Integer sums: exact and order-free below 2^53.  d table / d log s_c, binned as the table.
+ *   _reweight     lnscale DEVICE float64 [C]; out DEVICE float64 [n_slabs, W], ADDED to: per delivered row
+ *                 a = sum_c counts[row, c] * lnscale[c] (ascending c, one fma each), w = exp(a), and
+ *                 q = rint(w * 2^32) * 2^-32 is deposited.  One thread per row.  With lnscale all zero, out is the
+ *                 launch's window table bit for bit; with lnscale[c] = log s_c, the table of the design whose channel c
+ *                 is scaled by s_c, from the same rays.
+ * n_rows == 0 is WGRT_OK without a launch.  Asynchronous on stream.
+ * _host are the twins over HOST pointers through the same header (no GPU needed): the scene is stated by nx, ny,
+ * num_lmd, its channel count and scene_ranges, HOST float64 [nx, ny, 4] (eff_reg_FOV_range); the plan by its mask.
+ * wgrt_visit_channel_host is the channel table itself: the index of branch `branch` (0-based) of `state` (9: the
+ * in-coupling event; 0..5: R0..R5) in slice `slice`, or -1; wgrt_visit_channel_count_host is C. */
+wgrt_status wgrt_visits_sensitivity(const wgrt_scene *scene, const wgrt_window_plan *plan, const uint32_t *counts,
+                                    const wgrt_visit_end *ends, int64_t n_rows, double *sens, void *stream);
+wgrt_status wgrt_visits_reweight(const wgrt_scene *scene, const wgrt_window_plan *plan, const uint32_t *counts,
+                                 const wgrt_visit_end *ends, int64_t n_rows, const double *lnscale, double *out,
+                                 void *stream);
+wgrt_status wgrt_visits_sensitivity_host(int32_t nx, int32_t ny, int32_t num_lmd, int32_t n_channels,
+                                         const double *scene_ranges, const float *mask, int32_t ms, int32_t step_y,
+                                         int32_t step_x, const uint32_t *counts, const wgrt_visit_end *ends,
+                                         int64_t n_rows, double *sens);
+wgrt_status wgrt_visits_reweight_host(int32_t nx, int32_t ny, int32_t num_lmd, int32_t n_channels,
+                                      const double *scene_ranges, const float *mask, int32_t ms, int32_t step_y,
+                                      int32_t step_x, const uint32_t *counts, const wgrt_visit_end *ends, int64_t n_rows,
+                                      const double *lnscale, double *out);
+int32_t wgrt_visit_channel_host(int32_t n_fc_slices, int32_t n_oc_slices, int32_t state, int32_t slice, int32_t branch);
+int32_t wgrt_visit_channel_count_host(int32_t n_fc_slices, int32_t n_oc_slices);
+
 /* Host-only (no GPU needed; test hooks) through the same membership code (csrc/wgrt_window.h):
  * _validate is wgrt_window_plan_create's argument check alone; _table_host ADDS the n hits at flat grid
  * offsets offsets[n] (HOST int64; those outside [0, n_slabs * 9600) are dropped, as the grid's guard drops
