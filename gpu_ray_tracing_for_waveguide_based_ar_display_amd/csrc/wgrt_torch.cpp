@@ -30,6 +30,8 @@
 #include <algorithm>
 #include <cstdint>
 #include <optional>
+#include <string>
+#include <variant>
 
 #include "wgrt.h"
 
@@ -63,434 +65,375 @@ void *u32(const Tensor &t, const char *name, const Ctx &c, int64_t need) {
     return t.data_ptr();
 }
 
-// wgrt_trace_windows / wgrt_window_plan_width of the loaded libwgrt.so (global scope), or an error.
-struct WindowAbi {
-    decltype(&wgrt_trace_windows) trace;
-    decltype(&wgrt_window_plan_width) width;
+// An entry point of the loaded libwgrt.so (global scope) that arrived within ABI 9, looked up by name at its first
+// use (as _lib.load binds them): the operator library still loads over an earlier build, where the call raises.
+// `lead` is the launching operator the entry point came with, `since` what that build is from before.
+template <class Fn>
+Fn lib_symbol(const char *name, const char *lead, const char *since) {
+    const Fn fn = reinterpret_cast<Fn>(dlsym(RTLD_DEFAULT, name));
+    TORCH_CHECK(fn, "wgrt.", lead, ": the loaded libwgrt.so has no wgrt_", lead, " (a build from before ", since, ")");
+    return fn;
+}
+#define WGRT_SYM(fn, lead, since) \
+    ([] { static const auto f = lib_symbol<decltype(&fn)>(#fn, lead, since); return f; }())
+#define WINDOW_SYM(fn) WGRT_SYM(fn, "trace_windows", "the window-table sink")
+#define CHAIN_SYM(fn) WGRT_SYM(fn, "chain_begin", "the chained launches")
+#define PATHS_SYM(fn) WGRT_SYM(fn, "trace_paths", "the ray paths")
+#define VISITS_SYM(fn) WGRT_SYM(fn, "trace_visits", "the visit counts")
+
+// The arguments every launching operator shares, in the schemas' order, written once: as parameters, as the record
+// trace_core takes, and as that record's initialiser.  (trace has no plan / table and trace_expected no matrix_EB:
+// they declare the missing ones as locals.)
+#define TRACE_HEAD_PARAMS                                                                                        \
+    int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,                           \
+        const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,     \
+        Tensor rng_states
+#define TRACE_TAIL_PARAMS                                                                                        \
+    std::optional<Tensor> stats, std::optional<Tensor> per_ray_bounces, int64_t n_rays, int64_t gid_offset,      \
+        int64_t stream, int64_t kernel, int64_t variant, int64_t workgroups,                                     \
+        const std::optional<Tensor> &chunk_order, int64_t num_iter, const std::optional<Tensor> &gid_blocks,     \
+        int64_t gid_block_rays, int64_t debug, double grid_sqrt_k
+#define TRACE_PARAMS \
+    TRACE_HEAD_PARAMS, std::optional<Tensor> matrix_EB, TRACE_TAIL_PARAMS, int64_t plan, std::optional<Tensor> table
+#define TRACE_COMMON                                                                                             \
+    Common {                                                                                                     \
+        scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats, per_ray_bounces, n_rays,  \
+            gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks, gid_block_rays,  \
+            debug, grid_sqrt_k, plan, table                                                                      \
+    }
+struct Common {
+    int64_t scene;
+    const Tensor &x, &y, &m, &n;
+    const std::optional<Tensor> &lmd_num;
+    const Tensor &te, &tm, &delta_phase, &rng_states;
+    const std::optional<Tensor> &matrix_EB, &stats, &per_ray_bounces;
+    int64_t n_rays, gid_offset, stream, kernel, variant, workgroups;
+    const std::optional<Tensor> &chunk_order;
+    int64_t num_iter;
+    const std::optional<Tensor> &gid_blocks;
+    int64_t gid_block_rays, debug;
+    double grid_sqrt_k;
+    int64_t plan;
+    const std::optional<Tensor> &table;
 };
-const WindowAbi &window_abi() {
-    static const WindowAbi abi{reinterpret_cast<decltype(&wgrt_trace_windows)>(dlsym(RTLD_DEFAULT, "wgrt_trace_windows")),
-                               reinterpret_cast<decltype(&wgrt_window_plan_width)>(
-                                   dlsym(RTLD_DEFAULT, "wgrt_window_plan_width"))};
-    TORCH_CHECK(abi.trace && abi.width, "wgrt.trace_windows: the loaded libwgrt.so has no wgrt_trace_windows (a build "
-                                        "from before the window-table sink)");
-    return abi;
-}
 
-// The chain's entry points (wgrt_chain_*), new within ABI 9 as well: looked up at the first chain_begin.
-struct ChainAbi {
-    decltype(&wgrt_chain_begin) begin;
-    decltype(&wgrt_chain_step) step;
-    decltype(&wgrt_chain_end) end;
+// What a launching operator adds to the shared arguments: its one sink's tensors (engine._launch_sink states the
+// rule), the replica count of a launch into replica tables, or the chain a chain_begin opens.
+struct NoSink {};   // trace, trace_windows
+struct ChainSink {
+    wgrt_chain **out;
 };
-const ChainAbi &chain_abi() {
-    static const ChainAbi abi{reinterpret_cast<decltype(&wgrt_chain_begin)>(dlsym(RTLD_DEFAULT, "wgrt_chain_begin")),
-                              reinterpret_cast<decltype(&wgrt_chain_step)>(dlsym(RTLD_DEFAULT, "wgrt_chain_step")),
-                              reinterpret_cast<decltype(&wgrt_chain_end)>(dlsym(RTLD_DEFAULT, "wgrt_chain_end"))};
-    TORCH_CHECK(abi.begin && abi.step && abi.end, "wgrt.chain_begin: the loaded libwgrt.so has no wgrt_chain_begin (a "
-                                                  "build from before the chained launches)");
-    return abi;
-}
-
-// wgrt_trace_fate (per-ray fate codes), new within ABI 9 too: looked up at the first trace_fate call.
-decltype(&wgrt_trace_fate) fate_abi() {
-    static const auto fn = reinterpret_cast<decltype(&wgrt_trace_fate)>(dlsym(RTLD_DEFAULT, "wgrt_trace_fate"));
-    TORCH_CHECK(fn, "wgrt.trace_fate: the loaded libwgrt.so has no wgrt_trace_fate (a build from before the ray fates)");
-    return fn;
-}
-
-// wgrt_trace_replicas (replica window tables), new within ABI 9 too: looked up at the first trace_replicas call.
-decltype(&wgrt_trace_replicas) replicas_abi() {
-    static const auto fn = reinterpret_cast<decltype(&wgrt_trace_replicas)>(dlsym(RTLD_DEFAULT, "wgrt_trace_replicas"));
-    TORCH_CHECK(fn, "wgrt.trace_replicas: the loaded libwgrt.so has no wgrt_trace_replicas (a build from before the "
-                    "replica tables)");
-    return fn;
-}
-
-// wgrt_trace_expected (the expected-value estimator), new within ABI 9 too: looked up at the first trace_expected call.
-decltype(&wgrt_trace_expected) expected_abi() {
-    static const auto fn = reinterpret_cast<decltype(&wgrt_trace_expected)>(dlsym(RTLD_DEFAULT, "wgrt_trace_expected"));
-    TORCH_CHECK(fn, "wgrt.trace_expected: the loaded libwgrt.so has no wgrt_trace_expected (a build from before the "
-                    "expected-value estimator)");
-    return fn;
-}
-
-// wgrt_trace_footprint (the footprint maps), new within ABI 9 too: looked up at the first trace_footprint call.
-decltype(&wgrt_trace_footprint) footprint_abi() {
-    static const auto fn = reinterpret_cast<decltype(&wgrt_trace_footprint)>(dlsym(RTLD_DEFAULT, "wgrt_trace_footprint"));
-    TORCH_CHECK(fn, "wgrt.trace_footprint: the loaded libwgrt.so has no wgrt_trace_footprint (a build from before the "
-                    "footprint maps)");
-    return fn;
-}
-
-// wgrt_trace_hits (the hit list), new within ABI 9 too: looked up at the first trace_hits call.
-decltype(&wgrt_trace_hits) hits_abi() {
-    static const auto fn = reinterpret_cast<decltype(&wgrt_trace_hits)>(dlsym(RTLD_DEFAULT, "wgrt_trace_hits"));
-    TORCH_CHECK(fn, "wgrt.trace_hits: the loaded libwgrt.so has no wgrt_trace_hits (a build from before the hit list)");
-    return fn;
-}
-
-// wgrt_trace_paths and wgrt_paths_footprint (ray paths), new within ABI 9 too: looked up at the first call of either.
-struct PathsAbi {
-    decltype(&wgrt_trace_paths) trace;
-    decltype(&wgrt_paths_footprint) footprint;
+struct FateSink {   // uint8 [rays]
+    const Tensor &fate;
 };
-const PathsAbi &paths_abi() {
-    static const PathsAbi abi{reinterpret_cast<decltype(&wgrt_trace_paths)>(dlsym(RTLD_DEFAULT, "wgrt_trace_paths")),
-                              reinterpret_cast<decltype(&wgrt_paths_footprint)>(dlsym(RTLD_DEFAULT, "wgrt_paths_footprint"))};
-    TORCH_CHECK(abi.trace && abi.footprint,
-                "wgrt.trace_paths: the loaded libwgrt.so has no wgrt_trace_paths (a build from before the ray paths)");
-    return abi;
-}
-
-// wgrt_trace_visits and the two reductions (branch visit counts), new within ABI 9 too: looked up at the first call.
-struct VisitsAbi {
-    decltype(&wgrt_trace_visits) trace;
-    decltype(&wgrt_visits_sensitivity) sensitivity;
-    decltype(&wgrt_visits_reweight) reweight;
-    decltype(&wgrt_visit_channels) channels;
+struct ReplicasSink {   // table float64 [replicas, tiles, W] for replicas >= 2
+    int64_t replicas;
 };
-const VisitsAbi &visits_abi() {
-    static const VisitsAbi abi{
-        reinterpret_cast<decltype(&wgrt_trace_visits)>(dlsym(RTLD_DEFAULT, "wgrt_trace_visits")),
-        reinterpret_cast<decltype(&wgrt_visits_sensitivity)>(dlsym(RTLD_DEFAULT, "wgrt_visits_sensitivity")),
-        reinterpret_cast<decltype(&wgrt_visits_reweight)>(dlsym(RTLD_DEFAULT, "wgrt_visits_reweight")),
-        reinterpret_cast<decltype(&wgrt_visit_channels)>(dlsym(RTLD_DEFAULT, "wgrt_visit_channels"))};
-    TORCH_CHECK(abi.trace && abi.sensitivity && abi.reweight && abi.channels,
-                "wgrt.trace_visits: the loaded libwgrt.so has no wgrt_trace_visits (a build from before the visit counts)");
-    return abi;
-}
-
-// A visits launch's rows (trace_visits): counts int32 [n_rows, C] (the library's uint32 words), ends uint8 [n_rows, 32],
-// slot int32 [n_rays] or none.
-struct VisitRows {
+struct ExpectedSink {   // the same, no grid
+    int64_t replicas;
+};
+struct FootprintSink {   // int64 [num_lmd, 9, ny_cells, nx_cells]
+    wgrt_footprint_plan fp;
+    const Tensor &map;
+};
+struct HitsSink {   // the record buffer (uint8, 32 bytes per record), its capacity in records, the counter and the tag
+    const Tensor &list;
+    int64_t capacity;
+    const std::optional<Tensor> &count;
+    int64_t tag;
+};
+struct PathsSink {   // the same over a path list, and the batch's select bytes
+    HitsSink list;
+    const std::optional<Tensor> &select;
+};
+struct VisitsSink {   // slot int32 [n_rays] or none, counts int32 [n_rows, C] (the library's uint32 words), ends uint8 [n_rows, 32]
     const std::optional<Tensor> &slot;
-    Tensor counts, ends;
     int64_t n_rows;
+    const Tensor &counts, &ends;
 };
+using OpSink = std::variant<NoSink, ChainSink, FateSink, ReplicasSink, ExpectedSink, FootprintSink, HitsSink, PathsSink, VisitsSink>;
 
-// All three launching operators: trace (the grid alone: plan 0, no table), trace_windows (the grid, the window
-// table of plan `plan` -- a wgrt_window_plan handle -- or both) and, with `chain`, chain_begin: the same checks and
-// records handed to wgrt_chain_begin, which launches nothing and leaves the chain's handle in *chain.
-int64_t trace_core(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
-                   const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
-                   Tensor rng_states, std::optional<Tensor> matrix_EB, std::optional<Tensor> stats,
-                   std::optional<Tensor> per_ray_bounces, int64_t n_rays, int64_t gid_offset, int64_t stream,
-                   int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
-                   int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
-                   double grid_sqrt_k, int64_t plan, std::optional<Tensor> table, wgrt_chain **chain,
-                   std::optional<Tensor> fate = std::nullopt, int64_t replicas = 0, bool expected = false,
-                   const wgrt_footprint_plan *fp = nullptr, std::optional<Tensor> fp_map = std::nullopt,
-                   std::optional<Tensor> hits = std::nullopt, int64_t hit_capacity = 0,
-                   std::optional<Tensor> hit_count = std::nullopt, int64_t hit_tag = 0, bool as_paths = false,
-                   const std::optional<Tensor> &select = std::nullopt, const VisitRows *visits = nullptr) {
-    const wgrt_scene *s = reinterpret_cast<const wgrt_scene *>(static_cast<uintptr_t>(scene));
+// The footprint plan of an operator's six fp_* arguments (out of int32 range: a count the library refuses).
+wgrt_footprint_plan footprint_plan_of(double x0, double y0, double cell_x, double cell_y, int64_t nx_cells, int64_t ny_cells) {
+    wgrt_footprint_plan fp{};
+    fp.x0 = x0;
+    fp.y0 = y0;
+    fp.cell_x = cell_x;
+    fp.cell_y = cell_y;
+    fp.nx_cells = static_cast<int32_t>(std::max<int64_t>(-1, std::min<int64_t>(nx_cells, 1 << 20)));
+    fp.ny_cells = static_cast<int32_t>(std::max<int64_t>(-1, std::min<int64_t>(ny_cells, 1 << 20)));
+    return fp;
+}
+
+// A footprint map against its plan: int64, contiguous [num_lmd, 9, ny_cells, nx_cells].  With the scene's tile count,
+// num_lmd * nx * ny, the first axis divides it (trace_footprint: the Python layer checks it exactly); else it is num_lmd.
+// (a plan or a wavelength count the library refuses has no size to compare with: the library's check answers first)
+void check_footprint_map(const char *op, const Tensor &map, const wgrt_footprint_plan &fp, int64_t num_lmd, int64_t tiles) {
+    TORCH_CHECK(map.scalar_type() == at::kLong, op, ": map must be int64");
+    const bool sized = fp.nx_cells >= 1 && fp.nx_cells <= 4096 && fp.ny_cells >= 1 && fp.ny_cells <= 4096;
+    if (!sized || (!tiles && num_lmd < 1)) return;
+    const bool first = map.dim() == 4 && (tiles ? map.size(0) >= 1 && tiles % map.size(0) == 0 : map.size(0) == num_lmd);
+    TORCH_CHECK(first && map.is_contiguous() && map.size(1) == WGRT_FOOTPRINT_CHANNELS && map.size(2) == fp.ny_cells &&
+                    map.size(3) == fp.nx_cells,
+                op, ": map must be contiguous [", tiles ? "num_lmd" : std::to_string(num_lmd), ", ", WGRT_FOOTPRINT_CHANNELS,
+                ", ", fp.ny_cells, ", ", fp.nx_cells, "], got ", map.sizes());
+}
+
+// A record list (trace_hits / trace_paths; both hold 32-byte records) against its capacity: the counter and the tag.
+struct RecordList {
+    void *buf;
+    uint64_t *count;
+    uint32_t tag;
+};
+RecordList record_list(const char *op, const HitsSink &k, const Ctx &c) {
+    static_assert(sizeof(wgrt_hit) == sizeof(wgrt_path_vertex), "both lists hold 32-byte records");
+    on_device(k.list, "list", c);
+    TORCH_CHECK(k.list.scalar_type() == at::kByte && k.list.is_contiguous(), op, ": the list must be contiguous uint8");
+    // (a negative capacity is the library's to refuse; a positive one must lie inside the buffer)
+    TORCH_CHECK(k.capacity <= 0 || k.capacity <= k.list.numel() / (int64_t)sizeof(wgrt_hit), op, ": capacity ", k.capacity,
+                " exceeds the buffer's ", k.list.numel() / (int64_t)sizeof(wgrt_hit), " records");
+    uint64_t *cnt = nullptr;
+    if (k.count) {
+        on_device(*k.count, "count", c);
+        TORCH_CHECK(k.count->scalar_type() == at::kLong && k.count->numel() == 1, op, ": count must be int64[1]");
+        cnt = static_cast<uint64_t *>(k.count->data_ptr());
+    }
+    // (out of uint32 range: a tag the library refuses)
+    return {k.list.data_ptr(), cnt, k.tag < 0 || k.tag > 0xffffffffll ? 0xffffffffu : static_cast<uint32_t>(k.tag)};
+}
+
+// Every launching operator: the shared arguments checked against the scene and made into the library's records, then
+// the sink's own tensors checked and the sink's entry point called -- wgrt_trace_opts / wgrt_trace_windows without one,
+// wgrt_chain_begin (which launches nothing and leaves the chain's handle) for a ChainSink.
+int64_t trace_core(const Common &a, const OpSink &sink) {
+    const wgrt_scene *s = reinterpret_cast<const wgrt_scene *>(static_cast<uintptr_t>(a.scene));
     TORCH_CHECK(s != nullptr, "wgrt.trace: NULL scene");
     wgrt_scene_info info{};
     const wgrt_status st = wgrt_scene_get_info(s, &info);
     if (st != WGRT_OK) return st;
-    const Ctx c{c10::Device(c10::DeviceType::CUDA, static_cast<c10::DeviceIndex>(info.device)), x.numel()};
+    const Ctx c{c10::Device(c10::DeviceType::CUDA, static_cast<c10::DeviceIndex>(info.device)), a.x.numel()};
     // the scene's device is current for the call (the library selects it too, include/wgrt.h) and the
     // caller's comes back on return
     const c10::DeviceGuard guard(c.dev);
+    const int64_t n_rays = a.n_rays;
     TORCH_CHECK(n_rays >= 0 && n_rays <= c.rays, "wgrt.trace: n_rays=", n_rays, " out of range for ", c.rays, " rays");
-    TORCH_CHECK(kernel == 0 || kernel == 1, "wgrt.trace: kernel must be 0 (full colour) or 1 (single wavelength)");
+    TORCH_CHECK(a.kernel == 0 || a.kernel == 1, "wgrt.trace: kernel must be 0 (full colour) or 1 (single wavelength)");
 
     wgrt_rays r{};
-    r.x = column(x, "x", c);
-    r.y = column(y, "y", c);
-    r.m = column(m, "m", c);
-    r.n = column(n, "n", c);
-    if (kernel == 0) {
-        TORCH_CHECK(lmd_num.has_value(), "wgrt.trace: the full-colour kernel needs lmd_num");
-        r.lmd_num = column(*lmd_num, "lmd_num", c);
+    r.x = column(a.x, "x", c);
+    r.y = column(a.y, "y", c);
+    r.m = column(a.m, "m", c);
+    r.n = column(a.n, "n", c);
+    if (a.kernel == 0) {
+        TORCH_CHECK(a.lmd_num.has_value(), "wgrt.trace: the full-colour kernel needs lmd_num");
+        r.lmd_num = column(*a.lmd_num, "lmd_num", c);
     }
-    r.te = column(te, "te", c);
-    r.tm = column(tm, "tm", c);
-    r.delta_phase = column(delta_phase, "delta_phase", c);
+    r.te = column(a.te, "te", c);
+    r.tm = column(a.tm, "tm", c);
+    r.delta_phase = column(a.delta_phase, "delta_phase", c);
 
-    uint32_t *rng = static_cast<uint32_t *>(u32(rng_states, "rng_states", c, c.rays));
-    TORCH_CHECK(matrix_EB.has_value() || table.has_value(), "wgrt.trace: needs matrix_EB, a window table, or both");
+    uint32_t *rng = static_cast<uint32_t *>(u32(a.rng_states, "rng_states", c, c.rays));
+    TORCH_CHECK(a.matrix_EB.has_value() || a.table.has_value(), "wgrt.trace: needs matrix_EB, a window table, or both");
     float *eb = nullptr;
-    if (matrix_EB) {
-        on_device(*matrix_EB, "matrix_EB", c);
-        TORCH_CHECK(matrix_EB->scalar_type() == at::kFloat, "wgrt.trace: matrix_EB must be float32");
+    if (a.matrix_EB) {
+        on_device(*a.matrix_EB, "matrix_EB", c);
+        TORCH_CHECK(a.matrix_EB->scalar_type() == at::kFloat, "wgrt.trace: matrix_EB must be float32");
         const int64_t eb_want = (int64_t)info.tiles * 80 * 120;   // [L,] NY, NX, 80, 120
-        TORCH_CHECK(matrix_EB->numel() == eb_want, "wgrt.trace: matrix_EB holds ", matrix_EB->numel(),
+        TORCH_CHECK(a.matrix_EB->numel() == eb_want, "wgrt.trace: matrix_EB holds ", a.matrix_EB->numel(),
                     " floats, the scene's grid has ", eb_want);
-        eb = matrix_EB->data_ptr<float>();
+        eb = a.matrix_EB->data_ptr<float>();
     }
-    const wgrt_window_plan *wp = reinterpret_cast<const wgrt_window_plan *>(static_cast<uintptr_t>(plan));
+    const wgrt_window_plan *wp = reinterpret_cast<const wgrt_window_plan *>(static_cast<uintptr_t>(a.plan));
+    // the replica count describes the table: trace_replicas' and trace_expected's (the library checks its range)
+    const ReplicasSink *const reps = std::get_if<ReplicasSink>(&sink);
+    const ExpectedSink *const expected = std::get_if<ExpectedSink>(&sink);
+    const int64_t replicas = reps ? reps->replicas : expected ? expected->replicas : 0;
     double *tab = nullptr;
-    if (table) {
-        const int64_t W = window_abi().width(wp);
+    if (a.table) {
+        const Tensor &table = *a.table;
+        const int64_t W = WINDOW_SYM(wgrt_window_plan_width)(wp);
         TORCH_CHECK(W > 0, "wgrt.trace: a window table needs its plan");
-        on_device(*table, "table", c);
-        TORCH_CHECK(table->scalar_type() == at::kDouble, "wgrt.trace: table must be float64");
-        if (replicas >= 2) {   // trace_replicas: one table per replica (the library checks the count's range)
-            TORCH_CHECK(table->dim() == 3 && table->size(0) == replicas && table->size(1) == info.tiles && table->size(2) == W,
+        on_device(table, "table", c);
+        TORCH_CHECK(table.scalar_type() == at::kDouble, "wgrt.trace: table must be float64");
+        if (replicas >= 2) {   // one table per replica
+            TORCH_CHECK(table.dim() == 3 && table.size(0) == replicas && table.size(1) == info.tiles && table.size(2) == W,
                         "wgrt.trace_replicas: table must have shape [", replicas, ", ", info.tiles, ", ", W, "], got ",
-                        table->sizes());
+                        table.sizes());
         } else {
-            TORCH_CHECK(table->dim() == 2 && table->size(0) == info.tiles && table->size(1) == W,
-                        "wgrt.trace: table must have shape [", info.tiles, ", ", W, "], got ", table->sizes());
+            TORCH_CHECK(table.dim() == 2 && table.size(0) == info.tiles && table.size(1) == W,
+                        "wgrt.trace: table must have shape [", info.tiles, ", ", W, "], got ", table.sizes());
         }
-        tab = table->data_ptr<double>();
+        tab = table.data_ptr<double>();
     }
     wgrt_trace_stats *stp = nullptr;
-    if (stats) {
-        on_device(*stats, "stats", c);
-        TORCH_CHECK(stats->scalar_type() == at::kLong && stats->numel() * 8 == (int64_t)sizeof(wgrt_trace_stats),
+    if (a.stats) {
+        on_device(*a.stats, "stats", c);
+        TORCH_CHECK(a.stats->scalar_type() == at::kLong && a.stats->numel() * 8 == (int64_t)sizeof(wgrt_trace_stats),
                     "wgrt.trace: stats must be int64[", sizeof(wgrt_trace_stats) / 8, "]");
-        stp = static_cast<wgrt_trace_stats *>(stats->data_ptr());
+        stp = static_cast<wgrt_trace_stats *>(a.stats->data_ptr());
     }
-    uint32_t *per = per_ray_bounces ? static_cast<uint32_t *>(u32(*per_ray_bounces, "per_ray_bounces", c, c.rays))
-                                    : nullptr;
+    uint32_t *per = a.per_ray_bounces ? static_cast<uint32_t *>(u32(*a.per_ray_bounces, "per_ray_bounces", c, c.rays))
+                                      : nullptr;
 
     wgrt_launch_opts o{};
-    o.kernel = (int)kernel;
-    o.variant = (int)variant;
-    o.workgroups = (int)workgroups;
-    if (chunk_order) {
-        on_device(*chunk_order, "chunk_order", c);
+    o.kernel = (int)a.kernel;
+    o.variant = (int)a.variant;
+    o.workgroups = (int)a.workgroups;
+    if (a.chunk_order) {
+        on_device(*a.chunk_order, "chunk_order", c);
         const int64_t chunks = (n_rays + 63) / 64;
-        TORCH_CHECK(chunk_order->scalar_type() == at::kInt && chunk_order->numel() == chunks,
+        TORCH_CHECK(a.chunk_order->scalar_type() == at::kInt && a.chunk_order->numel() == chunks,
                     "wgrt.trace: chunk_order must be int32[", chunks, "]");
-        o.chunk_order = static_cast<const int32_t *>(chunk_order->const_data_ptr());
+        o.chunk_order = static_cast<const int32_t *>(a.chunk_order->const_data_ptr());
         o.n_chunk_order = chunks;
     }
-    o.num_iter = (int)num_iter;
-    if (gid_blocks) {
-        on_device(*gid_blocks, "gid_blocks", c);
-        TORCH_CHECK(gid_block_rays >= 1, "wgrt.trace: gid_blocks needs gid_block_rays >= 1");
-        const int64_t blocks = (n_rays + gid_block_rays - 1) / gid_block_rays;
-        TORCH_CHECK(gid_blocks->scalar_type() == at::kLong && gid_blocks->numel() >= blocks,
+    o.num_iter = (int)a.num_iter;
+    if (a.gid_blocks) {
+        on_device(*a.gid_blocks, "gid_blocks", c);
+        TORCH_CHECK(a.gid_block_rays >= 1, "wgrt.trace: gid_blocks needs gid_block_rays >= 1");
+        const int64_t blocks = (n_rays + a.gid_block_rays - 1) / a.gid_block_rays;
+        TORCH_CHECK(a.gid_blocks->scalar_type() == at::kLong && a.gid_blocks->numel() >= blocks,
                     "wgrt.trace: gid_blocks must be int64 with >= ", blocks, " entries");
-        o.gid_blocks = static_cast<const int64_t *>(gid_blocks->const_data_ptr());
-        o.gid_block_rays = gid_block_rays;
+        o.gid_blocks = static_cast<const int64_t *>(a.gid_blocks->const_data_ptr());
+        o.gid_block_rays = a.gid_block_rays;
     }
     // test / profiling hooks: the address of a wgrt_debug_opts record the caller keeps alive (0: none)
-    o.debug = reinterpret_cast<const wgrt_debug_opts *>(static_cast<uintptr_t>(debug));
-    o.grid_sqrt_k = grid_sqrt_k;
-    void *const hip_stream = reinterpret_cast<void *>(static_cast<uintptr_t>(stream));
-    if (chain) {
+    o.debug = reinterpret_cast<const wgrt_debug_opts *>(static_cast<uintptr_t>(a.debug));
+    o.grid_sqrt_k = a.grid_sqrt_k;
+    void *const hip_stream = reinterpret_cast<void *>(static_cast<uintptr_t>(a.stream));
+    // an entry point over trace_windows' arguments and the sink's own
+    auto launch = [&](auto fn, auto... own) {
+        return fn(s, &r, n_rays, a.gid_offset, rng, eb, stp, per, hip_stream, &o, tab ? wp : nullptr, tab, own...);
+    };
+    const int clamped = static_cast<int>(std::max<int64_t>(-1, std::min<int64_t>(replicas, 1 << 20)));
+
+    if (const auto *k = std::get_if<ChainSink>(&sink)) {
         TORCH_CHECK(!per, "wgrt.chain_begin: a chain takes no per_ray_bounces");
-        return chain_abi().begin(s, &r, n_rays, gid_offset, rng, eb, stp, hip_stream, &o, tab ? wp : nullptr, tab, chain);
+        return CHAIN_SYM(wgrt_chain_begin)(s, &r, n_rays, a.gid_offset, rng, eb, stp, hip_stream, &o, tab ? wp : nullptr, tab,
+                                           k->out);
     }
-    if (visits) {   // trace_visits: the rows' counts and end records, and the batch's slots
-        TORCH_CHECK(!hits && !fp_map && !fate && replicas == 0 && !expected,
-                    "wgrt.trace_visits: takes no fate, replicas, expected, footprint map or list");
-        const int64_t C = visits_abi().channels(s);
-        on_device(visits->counts, "counts", c);
-        on_device(visits->ends, "ends", c);
+    if (const auto *k = std::get_if<VisitsSink>(&sink)) {
+        const int64_t C = VISITS_SYM(wgrt_visit_channels)(s);
+        on_device(k->counts, "counts", c);
+        on_device(k->ends, "ends", c);
         // (a negative n_rows is the library's to refuse; the rows must lie inside both buffers)
-        TORCH_CHECK(visits->counts.scalar_type() == at::kInt && visits->counts.is_contiguous() &&
-                        visits->counts.numel() >= std::max<int64_t>(visits->n_rows, 0) * C,
+        TORCH_CHECK(k->counts.scalar_type() == at::kInt && k->counts.is_contiguous() &&
+                        k->counts.numel() >= std::max<int64_t>(k->n_rows, 0) * C,
                     "wgrt.trace_visits: counts must be contiguous int32 with >= n_rows * ", C, " entries");
-        TORCH_CHECK(visits->ends.scalar_type() == at::kByte && visits->ends.is_contiguous() &&
-                        visits->ends.numel() >= std::max<int64_t>(visits->n_rows, 0) * (int64_t)sizeof(wgrt_visit_end),
+        TORCH_CHECK(k->ends.scalar_type() == at::kByte && k->ends.is_contiguous() &&
+                        k->ends.numel() >= std::max<int64_t>(k->n_rows, 0) * (int64_t)sizeof(wgrt_visit_end),
                     "wgrt.trace_visits: ends must be contiguous uint8 with >= n_rows * 32 bytes");
         const int32_t *slot = nullptr;
-        if (visits->slot) {
-            on_device(*visits->slot, "slot", c);
-            TORCH_CHECK(visits->slot->scalar_type() == at::kInt && visits->slot->is_contiguous() &&
-                            visits->slot->numel() >= n_rays,
+        if (k->slot) {
+            on_device(*k->slot, "slot", c);
+            TORCH_CHECK(k->slot->scalar_type() == at::kInt && k->slot->is_contiguous() && k->slot->numel() >= n_rays,
                         "wgrt.trace_visits: slot must be contiguous int32 with >= ", n_rays, " entries");
-            slot = static_cast<const int32_t *>(visits->slot->const_data_ptr());
+            slot = static_cast<const int32_t *>(k->slot->const_data_ptr());
         }
-        return visits_abi().trace(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o, tab ? wp : nullptr, tab, slot,
-                                  visits->n_rows, static_cast<uint32_t *>(visits->counts.data_ptr()),
-                                  static_cast<wgrt_visit_end *>(visits->ends.data_ptr()));
+        return launch(VISITS_SYM(wgrt_trace_visits), slot, k->n_rows, static_cast<uint32_t *>(k->counts.data_ptr()),
+                      static_cast<wgrt_visit_end *>(k->ends.data_ptr()));
     }
-    if (hits) {   // trace_hits / trace_paths: the record buffer (uint8, 32 bytes per record), its capacity, the counter
-                  // and the tag; trace_paths (as_paths) also the batch's select bytes
-        static_assert(sizeof(wgrt_hit) == sizeof(wgrt_path_vertex), "both lists hold 32-byte records");
-        const char *const op = as_paths ? "wgrt.trace_paths" : "wgrt.trace_hits";
-        TORCH_CHECK(!fp_map && !fate && replicas == 0 && !expected, op, ": takes no fate, replicas, expected or footprint map");
-        on_device(*hits, "list", c);
-        TORCH_CHECK(hits->scalar_type() == at::kByte && hits->is_contiguous(), op, ": the list must be contiguous uint8");
-        // (a negative capacity is the library's to refuse; a positive one must lie inside the buffer)
-        TORCH_CHECK(hit_capacity <= 0 || hit_capacity <= hits->numel() / (int64_t)sizeof(wgrt_hit), op, ": capacity ",
-                    hit_capacity, " exceeds the buffer's ", hits->numel() / (int64_t)sizeof(wgrt_hit), " records");
-        uint64_t *cnt = nullptr;
-        if (hit_count) {
-            on_device(*hit_count, "count", c);
-            TORCH_CHECK(hit_count->scalar_type() == at::kLong && hit_count->numel() == 1, op, ": count must be int64[1]");
-            cnt = static_cast<uint64_t *>(hit_count->data_ptr());
+    if (const auto *k = std::get_if<PathsSink>(&sink)) {
+        const RecordList l = record_list("wgrt.trace_paths", k->list, c);
+        const uint8_t *sel = nullptr;
+        if (k->select) {
+            const Tensor &select = *k->select;
+            on_device(select, "select", c);
+            TORCH_CHECK(select.scalar_type() == at::kByte && select.is_contiguous() && select.numel() >= n_rays,
+                        "wgrt.trace_paths: select must be contiguous uint8 with >= ", n_rays, " entries");
+            sel = static_cast<const uint8_t *>(select.const_data_ptr());
         }
-        // (out of uint32 range: a tag the library refuses)
-        const uint32_t tag = hit_tag < 0 || hit_tag > 0xffffffffll ? 0xffffffffu : static_cast<uint32_t>(hit_tag);
-        if (as_paths) {
-            const uint8_t *sel = nullptr;
-            if (select) {
-                on_device(*select, "select", c);
-                TORCH_CHECK(select->scalar_type() == at::kByte && select->is_contiguous() && select->numel() >= n_rays,
-                            "wgrt.trace_paths: select must be contiguous uint8 with >= ", n_rays, " entries");
-                sel = static_cast<const uint8_t *>(select->const_data_ptr());
-            }
-            return paths_abi().trace(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o, tab ? wp : nullptr, tab,
-                                     static_cast<wgrt_path_vertex *>(hits->data_ptr()), hit_capacity, cnt, tag, sel);
-        }
-        return hits_abi()(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o, tab ? wp : nullptr, tab,
-                          static_cast<wgrt_hit *>(hits->data_ptr()), hit_capacity, cnt, tag);
+        return launch(PATHS_SYM(wgrt_trace_paths), static_cast<wgrt_path_vertex *>(l.buf), k->list.capacity, l.count, l.tag,
+                      sel);
     }
-    if (fp_map) {   // trace_footprint: int64 [num_lmd, 9, ny_cells, nx_cells], added to by every counted draw
-        TORCH_CHECK(fp && !fate && replicas == 0 && !expected, "wgrt.trace_footprint: takes no fate, replicas or expected");
-        on_device(*fp_map, "map", c);
-        TORCH_CHECK(fp_map->scalar_type() == at::kLong, "wgrt.trace_footprint: map must be int64");
-        // (a plan the library refuses has no size to compare with: the library's check answers first)
-        // (the scene's info has its tile count, num_lmd * nx * ny: the Python layer checks the first axis exactly)
-        const bool sized = fp->nx_cells >= 1 && fp->nx_cells <= 4096 && fp->ny_cells >= 1 && fp->ny_cells <= 4096;
-        TORCH_CHECK(!sized || (fp_map->is_contiguous() && fp_map->dim() == 4 && fp_map->size(0) >= 1 &&
-                               info.tiles % fp_map->size(0) == 0 && fp_map->size(1) == WGRT_FOOTPRINT_CHANNELS &&
-                               fp_map->size(2) == fp->ny_cells && fp_map->size(3) == fp->nx_cells),
-                    "wgrt.trace_footprint: map must be contiguous [num_lmd, ", WGRT_FOOTPRINT_CHANNELS, ", ", fp->ny_cells,
-                    ", ", fp->nx_cells, "], got ", fp_map->sizes());
-        return footprint_abi()(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o, tab ? wp : nullptr, tab, fp,
-                               static_cast<int64_t *>(fp_map->data_ptr()));
+    if (const auto *k = std::get_if<HitsSink>(&sink)) {
+        const RecordList l = record_list("wgrt.trace_hits", *k, c);
+        return launch(WGRT_SYM(wgrt_trace_hits, "trace_hits", "the hit list"), static_cast<wgrt_hit *>(l.buf), k->capacity,
+                      l.count, l.tag);
     }
-    if (expected) {   // trace_expected: the window table alone (its shape checked above: [tiles, W], or one per replica)
-        TORCH_CHECK(tab && !eb && !fate, "wgrt.trace_expected: needs a window table and takes no matrix_EB or fate");
-        return expected_abi()(s, &r, n_rays, gid_offset, rng, stp, per, hip_stream, &o, wp, tab,
-                              static_cast<int>(std::max<int64_t>(-1, std::min<int64_t>(replicas, 1 << 20))));
+    if (const auto *k = std::get_if<FootprintSink>(&sink)) {   // added to by every counted draw
+        on_device(k->map, "map", c);
+        check_footprint_map("wgrt.trace_footprint", k->map, k->fp, 0, info.tiles);
+        return launch(WGRT_SYM(wgrt_trace_footprint, "trace_footprint", "the footprint maps"), &k->fp,
+                      static_cast<int64_t *>(k->map.data_ptr()));
     }
-    if (replicas != 0) {   // trace_replicas (0: the call is trace_windows, below)
-        TORCH_CHECK(!fate, "wgrt.trace_replicas: takes no fate");
-        return replicas_abi()(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o, tab ? wp : nullptr, tab,
-                              static_cast<int>(std::max<int64_t>(-1, std::min<int64_t>(replicas, 1 << 20))));
+    if (expected)   // the window table alone (its shape checked above: [tiles, W], or one per replica)
+        return WGRT_SYM(wgrt_trace_expected, "trace_expected", "the expected-value estimator")(
+            s, &r, n_rays, a.gid_offset, rng, stp, per, hip_stream, &o, wp, tab, clamped);
+    if (reps && replicas != 0)   // (0: the call is trace_windows, below)
+        return launch(WGRT_SYM(wgrt_trace_replicas, "trace_replicas", "the replica tables"), clamped);
+    if (const auto *k = std::get_if<FateSink>(&sink)) {   // one uint8 per ray of the batch, written by the lane that ends
+        on_device(k->fate, "fate", c);                    // the ray's trace
+        TORCH_CHECK(k->fate.scalar_type() == at::kByte, "wgrt.trace_fate: fate must be uint8");
+        TORCH_CHECK(k->fate.numel() == c.rays, "wgrt.trace_fate: fate holds ", k->fate.numel(), " entries, the batch has ",
+                    c.rays);
+        return launch(WGRT_SYM(wgrt_trace_fate, "trace_fate", "the ray fates"), static_cast<uint8_t *>(k->fate.data_ptr()));
     }
-    if (fate) {   // trace_fate: one uint8 per ray of the batch, written by the lane that ends the ray's trace
-        on_device(*fate, "fate", c);
-        TORCH_CHECK(fate->scalar_type() == at::kByte, "wgrt.trace_fate: fate must be uint8");
-        TORCH_CHECK(fate->numel() == c.rays, "wgrt.trace_fate: fate holds ", fate->numel(), " entries, the batch has ", c.rays);
-        return fate_abi()(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o, tab ? wp : nullptr, tab,
-                          static_cast<uint8_t *>(fate->data_ptr()));
-    }
-    if (!tab) return wgrt_trace_opts(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o);
-    return window_abi().trace(s, &r, n_rays, gid_offset, rng, eb, stp, per, hip_stream, &o, wp, tab);
+    if (!tab) return wgrt_trace_opts(s, &r, n_rays, a.gid_offset, rng, eb, stp, per, hip_stream, &o);
+    return WINDOW_SYM(wgrt_trace_windows)(s, &r, n_rays, a.gid_offset, rng, eb, stp, per, hip_stream, &o, wp, tab);
 }
 
-int64_t trace_impl(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
-                   const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
-                   Tensor rng_states, std::optional<Tensor> matrix_EB, std::optional<Tensor> stats,
-                   std::optional<Tensor> per_ray_bounces, int64_t n_rays, int64_t gid_offset, int64_t stream,
-                   int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
-                   int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
-                   double grid_sqrt_k, int64_t plan, std::optional<Tensor> table) {
-    return trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats, per_ray_bounces,
-                      n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
-                      gid_block_rays, debug, grid_sqrt_k, plan, table, nullptr);
+// trace_windows: the grid, the window table of plan `plan` -- a wgrt_window_plan handle -- or both.
+int64_t trace_impl(TRACE_PARAMS) { return trace_core(TRACE_COMMON, NoSink{}); }
+
+// trace: the grid alone (plan 0, no table).
+int64_t trace(TRACE_HEAD_PARAMS, Tensor grid, TRACE_TAIL_PARAMS) {
+    const std::optional<Tensor> matrix_EB(std::move(grid)), table;
+    const int64_t plan = 0;
+    return trace_core(TRACE_COMMON, NoSink{});
+}
+
+// chain_begin: trace_windows' arguments -> the chain's handle (a user-space address: positive), or the negated
+// wgrt_status of a failure (wgrt_last_error has the detail).  The
+// Python layer keeps every tensor alive until chain_end (engine.TraceChain).
+int64_t chain_begin(TRACE_PARAMS) {
+    wgrt_chain *ch = nullptr;
+    const int64_t st = trace_core(TRACE_COMMON, ChainSink{&ch});
+    return st == WGRT_OK ? static_cast<int64_t>(reinterpret_cast<uintptr_t>(ch)) : -st;
+}
+int64_t chain_step(int64_t chain) {
+    return CHAIN_SYM(wgrt_chain_step)(reinterpret_cast<wgrt_chain *>(static_cast<uintptr_t>(chain)));
+}
+int64_t chain_end(int64_t chain) {
+    return CHAIN_SYM(wgrt_chain_end)(reinterpret_cast<wgrt_chain *>(static_cast<uintptr_t>(chain)));
 }
 
 // trace_fate: trace_windows' arguments and the fate buffer (wgrt_trace_fate).
-int64_t trace_fate(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
-                   const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
-                   Tensor rng_states, std::optional<Tensor> matrix_EB, std::optional<Tensor> stats,
-                   std::optional<Tensor> per_ray_bounces, int64_t n_rays, int64_t gid_offset, int64_t stream,
-                   int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
-                   int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
-                   double grid_sqrt_k, int64_t plan, std::optional<Tensor> table, Tensor fate) {
-    return trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats, per_ray_bounces,
-                      n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
-                      gid_block_rays, debug, grid_sqrt_k, plan, table, nullptr, fate);
-}
+int64_t trace_fate(TRACE_PARAMS, Tensor fate) { return trace_core(TRACE_COMMON, FateSink{fate}); }
 
-// trace_replicas: trace_windows' arguments and the replica count (wgrt_trace_replicas): table float64
-// [replicas, tiles, W] for replicas >= 2.
-int64_t trace_replicas(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
-                       const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
-                       Tensor rng_states, std::optional<Tensor> matrix_EB, std::optional<Tensor> stats,
-                       std::optional<Tensor> per_ray_bounces, int64_t n_rays, int64_t gid_offset, int64_t stream,
-                       int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
-                       int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
-                       double grid_sqrt_k, int64_t plan, std::optional<Tensor> table, int64_t replicas) {
-    return trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats, per_ray_bounces,
-                      n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
-                      gid_block_rays, debug, grid_sqrt_k, plan, table, nullptr, std::nullopt, replicas);
-}
+// trace_replicas: trace_windows' arguments and the replica count (wgrt_trace_replicas).
+int64_t trace_replicas(TRACE_PARAMS, int64_t replicas) { return trace_core(TRACE_COMMON, ReplicasSink{replicas}); }
 
 // trace_expected: trace_replicas' arguments without the grid (wgrt_trace_expected): table float64 [tiles, W] for
 // replicas 0 / 1, [replicas, tiles, W] otherwise.
-int64_t trace_expected(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
-                       const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
-                       Tensor rng_states, std::optional<Tensor> stats, std::optional<Tensor> per_ray_bounces,
-                       int64_t n_rays, int64_t gid_offset, int64_t stream, int64_t kernel, int64_t variant,
-                       int64_t workgroups, const std::optional<Tensor> &chunk_order, int64_t num_iter,
-                       const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
-                       double grid_sqrt_k, int64_t plan, Tensor table, int64_t replicas) {
-    return trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, std::nullopt, stats, per_ray_bounces,
-                      n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
-                      gid_block_rays, debug, grid_sqrt_k, plan, table, nullptr, std::nullopt, replicas, true);
+int64_t trace_expected(TRACE_HEAD_PARAMS, TRACE_TAIL_PARAMS, int64_t plan, Tensor window_table, int64_t replicas) {
+    const std::optional<Tensor> matrix_EB, table(std::move(window_table));
+    return trace_core(TRACE_COMMON, ExpectedSink{replicas});
 }
 
 // trace_footprint: trace_windows' arguments, the footprint plan's fields and the map (wgrt_trace_footprint).
-int64_t trace_footprint(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
-                        const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
-                        Tensor rng_states, std::optional<Tensor> matrix_EB, std::optional<Tensor> stats,
-                        std::optional<Tensor> per_ray_bounces, int64_t n_rays, int64_t gid_offset, int64_t stream,
-                        int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
-                        int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
-                        double grid_sqrt_k, int64_t plan, std::optional<Tensor> table, double fp_x0, double fp_y0,
-                        double fp_cell_x, double fp_cell_y, int64_t fp_nx_cells, int64_t fp_ny_cells, Tensor map) {
-    wgrt_footprint_plan fp{};
-    fp.x0 = fp_x0;
-    fp.y0 = fp_y0;
-    fp.cell_x = fp_cell_x;
-    fp.cell_y = fp_cell_y;
-    // (out of int32 range: a count the library refuses)
-    fp.nx_cells = static_cast<int32_t>(std::max<int64_t>(-1, std::min<int64_t>(fp_nx_cells, 1 << 20)));
-    fp.ny_cells = static_cast<int32_t>(std::max<int64_t>(-1, std::min<int64_t>(fp_ny_cells, 1 << 20)));
-    return trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats, per_ray_bounces,
-                      n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
-                      gid_block_rays, debug, grid_sqrt_k, plan, table, nullptr, std::nullopt, 0, false, &fp, map);
+int64_t trace_footprint(TRACE_PARAMS, double fp_x0, double fp_y0, double fp_cell_x, double fp_cell_y, int64_t fp_nx_cells,
+                        int64_t fp_ny_cells, Tensor map) {
+    return trace_core(TRACE_COMMON,
+                      FootprintSink{footprint_plan_of(fp_x0, fp_y0, fp_cell_x, fp_cell_y, fp_nx_cells, fp_ny_cells), map});
 }
 
 // trace_hits: trace_windows' arguments, the record buffer, its capacity in records, the counter and the tag
 // (wgrt_trace_hits).
-int64_t trace_hits(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
-                   const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
-                   Tensor rng_states, std::optional<Tensor> matrix_EB, std::optional<Tensor> stats,
-                   std::optional<Tensor> per_ray_bounces, int64_t n_rays, int64_t gid_offset, int64_t stream,
-                   int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
-                   int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
-                   double grid_sqrt_k, int64_t plan, std::optional<Tensor> table, Tensor hits, int64_t capacity,
-                   std::optional<Tensor> count, int64_t tag) {
-    return trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats, per_ray_bounces,
-                      n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
-                      gid_block_rays, debug, grid_sqrt_k, plan, table, nullptr, std::nullopt, 0, false, nullptr,
-                      std::nullopt, hits, capacity, count, tag);
+int64_t trace_hits(TRACE_PARAMS, Tensor hits, int64_t capacity, std::optional<Tensor> count, int64_t tag) {
+    return trace_core(TRACE_COMMON, HitsSink{hits, capacity, count, tag});
 }
 
 // trace_paths: trace_hits' arguments over a path list, and the batch's select bytes (wgrt_trace_paths).
-int64_t trace_paths(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
-                    const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
-                    Tensor rng_states, std::optional<Tensor> matrix_EB, std::optional<Tensor> stats,
-                    std::optional<Tensor> per_ray_bounces, int64_t n_rays, int64_t gid_offset, int64_t stream,
-                    int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
-                    int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
-                    double grid_sqrt_k, int64_t plan, std::optional<Tensor> table, Tensor paths, int64_t capacity,
-                    std::optional<Tensor> count, int64_t tag, const std::optional<Tensor> &select) {
-    return trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats, per_ray_bounces,
-                      n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
-                      gid_block_rays, debug, grid_sqrt_k, plan, table, nullptr, std::nullopt, 0, false, nullptr,
-                      std::nullopt, paths, capacity, count, tag, true, select);
+int64_t trace_paths(TRACE_PARAMS, Tensor paths, int64_t capacity, std::optional<Tensor> count, int64_t tag,
+                    const std::optional<Tensor> &select) {
+    return trace_core(TRACE_COMMON, PathsSink{{paths, capacity, count, tag}, select});
 }
 
 // trace_visits: trace_windows' arguments, the batch's slots (or None), the rows there are, their counts and their end
 // records (wgrt_trace_visits).
-int64_t trace_visits(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
-                     const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
-                     Tensor rng_states, std::optional<Tensor> matrix_EB, std::optional<Tensor> stats,
-                     std::optional<Tensor> per_ray_bounces, int64_t n_rays, int64_t gid_offset, int64_t stream,
-                     int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
-                     int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
-                     double grid_sqrt_k, int64_t plan, std::optional<Tensor> table, const std::optional<Tensor> &slot,
-                     int64_t n_rows, Tensor counts, Tensor ends) {
-    const VisitRows rows{slot, counts, ends, n_rows};
-    return trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats, per_ray_bounces,
-                      n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
-                      gid_block_rays, debug, grid_sqrt_k, plan, table, nullptr, std::nullopt, 0, false, nullptr,
-                      std::nullopt, std::nullopt, 0, std::nullopt, 0, false, std::nullopt, &rows);
+int64_t trace_visits(TRACE_PARAMS, const std::optional<Tensor> &slot, int64_t n_rows, Tensor counts, Tensor ends) {
+    return trace_core(TRACE_COMMON, VisitsSink{slot, n_rows, counts, ends});
 }
 
 // visits_reduce: the first n_rows rows of a visits table reduced on the scene's device: without lnscale into the
@@ -505,7 +448,7 @@ int64_t visits_reduce(int64_t scene, int64_t plan, const Tensor &counts, const T
     const wgrt_status st = wgrt_scene_get_info(s, &info);
     if (st != WGRT_OK) return st;
     const c10::Device dev(c10::DeviceType::CUDA, static_cast<c10::DeviceIndex>(info.device));
-    const int64_t C = visits_abi().channels(s), W = window_abi().width(wp);
+    const int64_t C = VISITS_SYM(wgrt_visit_channels)(s), W = WINDOW_SYM(wgrt_window_plan_width)(wp);
     TORCH_CHECK(W > 0, "wgrt.visits_reduce: a bad window plan");
     TORCH_CHECK(counts.device() == dev && ends.device() == dev && out.device() == dev,
                 "wgrt.visits_reduce: counts, ends and out must be on the scene's device");
@@ -521,12 +464,12 @@ int64_t visits_reduce(int64_t scene, int64_t plan, const Tensor &counts, const T
     void *const hip_stream = reinterpret_cast<void *>(static_cast<uintptr_t>(stream));
     const uint32_t *cnt = static_cast<const uint32_t *>(counts.const_data_ptr());
     const wgrt_visit_end *e = static_cast<const wgrt_visit_end *>(ends.const_data_ptr());
-    if (!lnscale) return visits_abi().sensitivity(s, wp, cnt, e, n_rows, out.data_ptr<double>(), hip_stream);
+    if (!lnscale) return VISITS_SYM(wgrt_visits_sensitivity)(s, wp, cnt, e, n_rows, out.data_ptr<double>(), hip_stream);
     TORCH_CHECK(lnscale->device() == dev && lnscale->scalar_type() == at::kDouble && lnscale->is_contiguous() &&
                     lnscale->numel() == C,
                 "wgrt.visits_reduce: lnscale must be contiguous float64 [", C, "] on the scene's device");
-    return visits_abi().reweight(s, wp, cnt, e, n_rows, lnscale->const_data_ptr<double>(), out.data_ptr<double>(),
-                                 hip_stream);
+    return VISITS_SYM(wgrt_visits_reweight)(s, wp, cnt, e, n_rows, lnscale->const_data_ptr<double>(), out.data_ptr<double>(),
+                                            hip_stream);
 }
 
 // paths_footprint: the first n records of a path list added into a footprint map on the list's device
@@ -538,58 +481,13 @@ int64_t paths_footprint(const Tensor &paths, int64_t n, int64_t num_lmd, double 
     TORCH_CHECK(paths.scalar_type() == at::kByte && paths.is_contiguous(), "wgrt.paths_footprint: the list must be contiguous uint8");
     TORCH_CHECK(n >= 0 && n <= paths.numel() / (int64_t)sizeof(wgrt_path_vertex), "wgrt.paths_footprint: n = ", n,
                 " exceeds the buffer's ", paths.numel() / (int64_t)sizeof(wgrt_path_vertex), " records");
-    wgrt_footprint_plan fp{};
-    fp.x0 = fp_x0;
-    fp.y0 = fp_y0;
-    fp.cell_x = fp_cell_x;
-    fp.cell_y = fp_cell_y;
-    fp.nx_cells = static_cast<int32_t>(std::max<int64_t>(-1, std::min<int64_t>(fp_nx_cells, 1 << 20)));
-    fp.ny_cells = static_cast<int32_t>(std::max<int64_t>(-1, std::min<int64_t>(fp_ny_cells, 1 << 20)));
-    const bool sized = fp.nx_cells >= 1 && fp.nx_cells <= 4096 && fp.ny_cells >= 1 && fp.ny_cells <= 4096;
-    TORCH_CHECK(map.scalar_type() == at::kLong, "wgrt.paths_footprint: map must be int64");
-    TORCH_CHECK(!sized || num_lmd < 1 ||
-                    (map.is_contiguous() && map.dim() == 4 && map.size(0) == num_lmd &&
-                     map.size(1) == WGRT_FOOTPRINT_CHANNELS && map.size(2) == fp.ny_cells && map.size(3) == fp.nx_cells),
-                "wgrt.paths_footprint: map must be contiguous [", num_lmd, ", ", WGRT_FOOTPRINT_CHANNELS, ", ", fp.ny_cells,
-                ", ", fp.nx_cells, "], got ", map.sizes());
+    const wgrt_footprint_plan fp = footprint_plan_of(fp_x0, fp_y0, fp_cell_x, fp_cell_y, fp_nx_cells, fp_ny_cells);
+    check_footprint_map("wgrt.paths_footprint", map, fp, num_lmd, 0);
     const c10::DeviceGuard guard(paths.device());
-    return paths_abi().footprint(static_cast<const wgrt_path_vertex *>(paths.const_data_ptr()), n,
-                                 static_cast<int32_t>(std::max<int64_t>(-1, std::min<int64_t>(num_lmd, 1 << 20))), &fp,
-                                 static_cast<int64_t *>(map.data_ptr()), reinterpret_cast<void *>(static_cast<uintptr_t>(stream)));
-}
-
-// chain_begin: trace_windows' arguments -> the chain's handle (a user-space address: positive), or the negated
-// wgrt_status of a failure (wgrt_last_error has the detail).  The
-// Python layer keeps every tensor alive until chain_end (engine.TraceChain).
-int64_t chain_begin(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
-                    const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
-                    Tensor rng_states, std::optional<Tensor> matrix_EB, std::optional<Tensor> stats,
-                    std::optional<Tensor> per_ray_bounces, int64_t n_rays, int64_t gid_offset, int64_t stream,
-                    int64_t kernel, int64_t variant, int64_t workgroups, const std::optional<Tensor> &chunk_order,
-                    int64_t num_iter, const std::optional<Tensor> &gid_blocks, int64_t gid_block_rays, int64_t debug,
-                    double grid_sqrt_k, int64_t plan, std::optional<Tensor> table) {
-    wgrt_chain *ch = nullptr;
-    const int64_t st = trace_core(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats,
-                                  per_ray_bounces, n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order,
-                                  num_iter, gid_blocks, gid_block_rays, debug, grid_sqrt_k, plan, table, &ch);
-    return st == WGRT_OK ? static_cast<int64_t>(reinterpret_cast<uintptr_t>(ch)) : -st;
-}
-int64_t chain_step(int64_t chain) {
-    return chain_abi().step(reinterpret_cast<wgrt_chain *>(static_cast<uintptr_t>(chain)));
-}
-int64_t chain_end(int64_t chain) {
-    return chain_abi().end(reinterpret_cast<wgrt_chain *>(static_cast<uintptr_t>(chain)));
-}
-
-int64_t trace(int64_t scene, const Tensor &x, const Tensor &y, const Tensor &m, const Tensor &n,
-              const std::optional<Tensor> &lmd_num, const Tensor &te, const Tensor &tm, const Tensor &delta_phase,
-              Tensor rng_states, Tensor matrix_EB, std::optional<Tensor> stats, std::optional<Tensor> per_ray_bounces,
-              int64_t n_rays, int64_t gid_offset, int64_t stream, int64_t kernel, int64_t variant, int64_t workgroups,
-              const std::optional<Tensor> &chunk_order, int64_t num_iter, const std::optional<Tensor> &gid_blocks,
-              int64_t gid_block_rays, int64_t debug, double grid_sqrt_k) {
-    return trace_impl(scene, x, y, m, n, lmd_num, te, tm, delta_phase, rng_states, matrix_EB, stats, per_ray_bounces,
-                      n_rays, gid_offset, stream, kernel, variant, workgroups, chunk_order, num_iter, gid_blocks,
-                      gid_block_rays, debug, grid_sqrt_k, 0, std::nullopt);
+    return PATHS_SYM(wgrt_paths_footprint)(static_cast<const wgrt_path_vertex *>(paths.const_data_ptr()), n,
+                                           static_cast<int32_t>(std::max<int64_t>(-1, std::min<int64_t>(num_lmd, 1 << 20))),
+                                           &fp, static_cast<int64_t *>(map.data_ptr()),
+                                           reinterpret_cast<void *>(static_cast<uintptr_t>(stream)));
 }
 
 }  // namespace

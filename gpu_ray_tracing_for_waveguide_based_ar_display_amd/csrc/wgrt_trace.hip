@@ -1699,6 +1699,42 @@ void mark_dirty(wgrt_scene *ms, wgrt_scene::Scratch *sc) {
     sc->dirty = true;
 }
 
+// What a launch leaves besides the grid and the window table: its one sink ("Adding a sink").  The kind is
+// the sink's TraceMode -- kFate, kEv, kFp, kHits, kPaths, kVisits; kPlain: none -- and the payload is that kind's (the
+// expected-value estimator has none: it scores into the window table).
+struct Sink {
+    struct Footprint {   // wgrt_trace_footprint: the map every counted draw adds to, and its plan
+        int64_t *map;
+        wgrt_footprint_plan plan;
+    };
+    struct Records {   // wgrt_trace_hits / wgrt_trace_paths: the record list, its capacity, its device counter and the
+        void *buf;     // call's tag; a path list also the batch's select bytes (NULL: every ray)
+        int64_t cap;
+        unsigned long long *count;
+        uint32_t tag;
+        const uint8_t *select;
+    };
+    struct Visits {   // wgrt_trace_visits: the rows' branch counts and end records, the batch's slots (NULL: ray i into
+        uint32_t *counts;   // row i) and the rows there are
+        wgrt_visit_end *ends;
+        const int32_t *slot;
+        int64_t rows;
+    };
+    TraceMode kind = TraceMode::kPlain;
+    union {
+        uint8_t *fate;   // wgrt_trace_fate: the per-ray fate codes
+        Footprint fp;
+        Records list;
+        Visits visits;
+    };
+    Sink() : fp{} {}
+    static Sink of(TraceMode kind) {
+        Sink k;
+        k.kind = kind;
+        return k;
+    }
+};
+
 struct LaunchCfg {
     int variant = 0, workgroups = 0, num_iter = 1;
     bool single = false;
@@ -1708,9 +1744,8 @@ struct LaunchCfg {
     int64_t gid_block_rays = 0;
     const wgrt_debug_opts *dbg = nullptr;
     double grid_k = 0.0;   // wgrt_launch_opts.grid_sqrt_k (0: kGridSqrtK; < 0: the resident grid)
-    // The instantiation the launch runs (wgrt_trace_mode.h).  An entry point asks for kEv here (wgrt_trace_expected:
-    // the one mode that no payload field below implies); validate_launch then settles it (launch_mode), and
-    // plan_auto_order may turn a kPlain launch into a kLearn one.
+    // The instantiation the launch runs (wgrt_trace_mode.h).  chain_step asks for kChain here; validate_launch settles
+    // it (launch_mode), and plan_auto_order may turn a kPlain launch into a kLearn one.
     TraceMode mode = TraceMode::kPlain;
     bool auto_order = false;   // the launch is issued in the automatic order, built from the tile table as
     uint32_t order_gen = 0;    // it stood after this many learning launches
@@ -1720,68 +1755,51 @@ struct LaunchCfg {
     // wgrt_trace_windows: the window table the out-couplings count into and its plan's device view (NULL: none)
     double *win_table = nullptr;
     const WindowPlanView *win = nullptr;
+    // wgrt_trace_replicas / wgrt_trace_expected: win_table is `replicas` tables of rep_stride = n_slabs * W entries each
+    // (0: the one table of wgrt_trace_windows).  They describe the table, so they stand beside it, not in the sink.
+    int replicas = 0;
+    int64_t rep_stride = 0;
     // a chained step (wgrt_chain_step): the chain's granules and the tag serial this step publishes (0: not chained)
     uint64_t *chain_gran = nullptr;
     uint32_t chain_serial = 0;
-    // wgrt_trace_fate: the per-ray fate codes (NULL: none).  A fate launch is a single launch (validate_launch),
-    // never learns the tile table (plan_auto_order: no learning instantiation stores fates; the scene learns from
-    // its next plain launch instead) and takes no debug timeline (validate_launch refuses it).
-    uint8_t *fate = nullptr;
-    // wgrt_trace_replicas: win_table is `replicas` tables of rep_stride = n_slabs * W entries each (0: the one table
-    // of wgrt_trace_windows).  A replica launch follows the fate launch's rules: a single launch, no learning, no
-    // debug timeline, and not together with fate (validate_launch, plan_auto_order).
-    int replicas = 0;
-    int64_t rep_stride = 0;
-    // wgrt_trace_expected: the launch scores every out-coupler visit into win_table (wgrt_expected.h) instead of
-    // counting out-couplings (mode kEv); `replicas` as above (0: the one table).  It follows the replica launch's
-    // rules, has no grid (a float32 cell cannot hold the fixed-point sums) and never stores fates.
-    // wgrt_trace_footprint: the map every counted draw adds to and its plan (NULL: none).  A footprint launch follows
-    // the fate launch's rules -- a single launch, no learning, no debug timeline, never a chained step -- and is not
-    // combined with fates, replicas or the expected-value estimator.
-    int64_t *fp_map = nullptr;
-    wgrt_footprint_plan fp{};
-    // wgrt_trace_hits: the list every out-coupling is appended to, its capacity, its device counter and the call's tag
-    // (NULL: none).  A hits launch follows the fate launch's rules too, and is not combined with fates, replicas, the
-    // expected-value estimator or footprints.
-    wgrt_hit *hits = nullptr;
-    int64_t hits_cap = 0;
-    unsigned long long *hits_count = nullptr;
-    uint32_t hits_tag = 0;
-    // wgrt_trace_paths: the list every draw of a selected ray is appended to, its capacity, its device counter, the
-    // call's tag and the batch's select bytes (paths NULL: none; select NULL: every ray).  A paths launch follows the
-    // hits launch's rules, and is not combined with fates, replicas, the expected-value estimator, footprints or hit
-    // lists.
-    wgrt_path_vertex *paths = nullptr;
-    int64_t paths_cap = 0;
-    unsigned long long *paths_count = nullptr;
-    uint32_t paths_tag = 0;
-    const uint8_t *select = nullptr;
-    // wgrt_trace_visits: the rows' branch counts and end records, the rows there are and the batch's slots (vis_counts
-    // NULL: none; vis_slot NULL: ray i into row i).  A visits launch follows the hits launch's rules, and is not
-    // combined with fates, replicas, the expected-value estimator, footprints, hit lists or path lists.
-    uint32_t *vis_counts = nullptr;
-    wgrt_visit_end *vis_ends = nullptr;
-    const int32_t *vis_slot = nullptr;
-    int64_t vis_rows = 0;
+    // the launch's one sink.  A launch with a sink or with replicas is a single, unchained launch that neither learns
+    // the tile table nor takes the debug timeline: the rule is stated in DESIGN.md ("Adding a sink") and enforced
+    // from kSinkTraits (validate_launch, plan_auto_order).
+    Sink sink;
     // set by validate_launch: the launch runs the byte-locator instantiation (byte_locator_applies)
     bool byte = false;
 };
 
-// The mode of a launch, the one place that orders them: a chained step, the debug timeline, then the sinks -- the
-// expected-value estimator before the replicas, because such a launch may fill replica tables too -- and only then
-// a learning launch.  (validate_launch refuses the other combinations; a chained step has no sink.)  What asks for
-// a mode: c.mode itself for kChain (chain_step), kEv (wgrt_trace_expected) and kLearn (plan_auto_order), the debug
-// options for the timeline, the sink's payload for the rest.
+// One row per sink, and one for replica tables: the mode such a launch runs and the noun its refusals use.  From it
+// come the num_iter > 1 and the timeline refusal (validate_launch) and the launch's mode (launch_mode).
+struct SinkTrait {
+    TraceMode mode;
+    const char *noun;
+};
+constexpr SinkTrait kSinkTraits[] = {
+    {TraceMode::kFate, "fate"},          {TraceMode::kEv, "expected-value estimator"},
+    {TraceMode::kFp, "footprint map"},   {TraceMode::kHits, "hit list"},
+    {TraceMode::kPaths, "path list"},    {TraceMode::kVisits, "visit counts"},
+    {TraceMode::kReps, "replicas"},
+};
+// The launch's row: its sink's, else the replicas' if it fills replica tables, else none.  (The estimator may fill
+// replica tables too: such a launch is the estimator's.)
+const SinkTrait *sink_trait(const LaunchCfg &c) {
+    const TraceMode want = c.sink.kind != TraceMode::kPlain ? c.sink.kind : c.replicas ? TraceMode::kReps : TraceMode::kPlain;
+    for (const SinkTrait &t : kSinkTraits)
+        if (t.mode == want) return &t;
+    return nullptr;
+}
+
+// The mode of a launch, the one place that orders them: a chained step, the debug timeline, the sink's mode, the
+// replicas, and only then a learning launch.  (validate_launch refuses a sink under the timeline; a chained step has
+// none.)  What asks for a mode: c.mode itself for kChain (chain_step) and kLearn (plan_auto_order), the debug options
+// for the timeline, the trait row for the rest.
 TraceMode launch_mode(const LaunchCfg &c, bool timeline) {
+    const SinkTrait *const t = sink_trait(c);
     return c.mode == TraceMode::kChain   ? TraceMode::kChain
            : timeline                    ? TraceMode::kTimeline
-           : c.fate                      ? TraceMode::kFate
-           : c.mode == TraceMode::kEv    ? TraceMode::kEv
-           : c.fp_map                    ? TraceMode::kFp
-           : c.hits                      ? TraceMode::kHits
-           : c.paths                     ? TraceMode::kPaths
-           : c.vis_counts                ? TraceMode::kVisits
-           : c.replicas                  ? TraceMode::kReps
+           : t                           ? t->mode
            : c.mode == TraceMode::kLearn ? TraceMode::kLearn
                                          : TraceMode::kPlain;
 }
@@ -1903,7 +1921,8 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
                             LaunchCfg &c) {
     const bool single = c.single;
     const wgrt_debug_opts *dbg = c.dbg;
-    const bool expected = c.mode == TraceMode::kEv;
+    const bool expected = c.sink.kind == TraceMode::kEv;
+    const SinkTrait *const trait = sink_trait(c);
     if (single && s->nl != 1)
         return fail(WGRT_ERR_INVALID_ARGUMENT, "single-wavelength trace needs a scene built with num_lmd == 1");
     if (c.variant != 0 && c.variant != 1 && c.variant != 7 && c.variant != 9)
@@ -1912,70 +1931,47 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
     if (c.num_iter > 255) return fail(WGRT_ERR_INVALID_ARGUMENT, "num_iter must be <= 255");
     if (c.num_iter > 1 && (per_ray_bounces || c.chunk_order))
         return fail(WGRT_ERR_INVALID_ARGUMENT, "num_iter > 1 takes no per_ray_bounces / chunk_order");
-    if (c.num_iter > 1 && c.fate)
-        return fail(WGRT_ERR_INVALID_ARGUMENT, "num_iter > 1 takes no fate: a fused launch's retire sites publish hand-off "
-                                               "granules, not per-trace results (trace the iterations one call each)");
-    if (c.num_iter > 1 && c.replicas)
-        return fail(WGRT_ERR_INVALID_ARGUMENT, "num_iter > 1 takes no replicas: replica tables are filled by single "
-                                               "launches (trace the iterations one call each)");
-    if (c.fate && c.replicas)
-        return fail(WGRT_ERR_INVALID_ARGUMENT, "a launch stores fates or fills replica tables, not both");
-    if (expected && c.num_iter > 1)
-        return fail(WGRT_ERR_INVALID_ARGUMENT, "num_iter > 1 takes no expected-value estimator: its tables are filled by "
-                                               "single launches (trace the iterations one call each)");
-    if (expected && (c.fate || matrix_EB || !c.win_table))
-        return fail(WGRT_ERR_INVALID_ARGUMENT, "the expected-value estimator fills a window table: no grid, no fates");
-    if (c.fp_map) {
-        if (const char *why = footprint_plan_error(&c.fp)) return fail(WGRT_ERR_INVALID_ARGUMENT, why);
-        if ((uintptr_t)c.fp_map & 7) return fail(WGRT_ERR_INVALID_ARGUMENT, "the footprint map must be 8-B aligned");
-        if (c.num_iter > 1)
-            return fail(WGRT_ERR_INVALID_ARGUMENT, "num_iter > 1 takes no footprint map: the maps are filled by single "
-                                                   "launches (trace the iterations one call each)");
-        if (c.fate || c.replicas || expected)
-            return fail(WGRT_ERR_INVALID_ARGUMENT, "a footprint launch takes no fates, replicas or expected-value estimator");
+    if (c.num_iter > 1 && trait)
+        return fail(WGRT_ERR_INVALID_ARGUMENT, std::string("num_iter > 1 takes no ") + trait->noun +
+                                                   ": a sink and replica tables are filled by single launches (trace the "
+                                                   "iterations one call each)");
+    if (expected && (matrix_EB || !c.win_table))
+        return fail(WGRT_ERR_INVALID_ARGUMENT, "the expected-value estimator fills a window table: it needs one and takes "
+                                               "no grid");
+    switch (c.sink.kind) {   // the payload's own checks
+    case TraceMode::kFp: {
+        const Sink::Footprint &f = c.sink.fp;
+        if (const char *why = footprint_plan_error(&f.plan)) return fail(WGRT_ERR_INVALID_ARGUMENT, why);
+        if ((uintptr_t)f.map & 7) return fail(WGRT_ERR_INVALID_ARGUMENT, "the footprint map must be 8-B aligned");
+        break;
     }
-    if (c.hits) {
-        if (!c.hits_count) return fail(WGRT_ERR_INVALID_ARGUMENT, "a hit list needs its device counter");
-        if (c.hits_cap < 0) return fail(WGRT_ERR_INVALID_ARGUMENT, "the hit list's capacity must be >= 0");
-        if (c.hits_tag > kHitMaxTag) return fail(WGRT_ERR_INVALID_ARGUMENT, "the hit list's tag must be <= 65535");
-        if (((uintptr_t)c.hits & 15) || ((uintptr_t)c.hits_count & 7))
-            return fail(WGRT_ERR_INVALID_ARGUMENT, "the hit list must be 16-B aligned (and its counter 8-B)");
-        if (c.num_iter > 1)
-            return fail(WGRT_ERR_INVALID_ARGUMENT, "num_iter > 1 takes no hit list: the lists are filled by single "
-                                                   "launches (trace the iterations one call each)");
-        if (c.fate || c.replicas || expected || c.fp_map)
-            return fail(WGRT_ERR_INVALID_ARGUMENT, "a hits launch takes no fates, replicas, expected-value estimator or "
-                                                   "footprint map");
-    }
-    if (c.paths) {
-        if (!c.paths_count) return fail(WGRT_ERR_INVALID_ARGUMENT, "a path list needs its device counter");
-        if (c.paths_cap < 0) return fail(WGRT_ERR_INVALID_ARGUMENT, "the path list's capacity must be >= 0");
-        if (c.paths_tag > kPathMaxTag) return fail(WGRT_ERR_INVALID_ARGUMENT, "the path list's tag must be <= 65535");
-        if (((uintptr_t)c.paths & 15) || ((uintptr_t)c.paths_count & 7))
-            return fail(WGRT_ERR_INVALID_ARGUMENT, "the path list must be 16-B aligned (and its counter 8-B)");
-        if (s->nl > kPathMaxLmd)
+    case TraceMode::kHits:
+    case TraceMode::kPaths: {
+        static_assert(kHitMaxTag == kPathMaxTag, "both record lists carry a 16-bit tag");
+        const Sink::Records &l = c.sink.list;
+        auto bad = [&](const char *what) {   // "the hit list ..." / "the path list ..."
+            return fail(WGRT_ERR_INVALID_ARGUMENT, std::string("the ") + trait->noun + what);
+        };
+        if (!l.count) return bad(" needs its device counter");
+        if (l.cap < 0) return bad("'s capacity must be >= 0");
+        if (l.tag > kHitMaxTag) return bad("'s tag must be <= 65535");
+        if (((uintptr_t)l.buf & 15) || ((uintptr_t)l.count & 7)) return bad(" must be 16-B aligned (and its counter 8-B)");
+        if (c.sink.kind == TraceMode::kPaths && s->nl > kPathMaxLmd)
             return fail(WGRT_ERR_INVALID_ARGUMENT, "a path record names at most 256 wavelengths: the scene has more");
-        if (c.num_iter > 1)
-            return fail(WGRT_ERR_INVALID_ARGUMENT, "num_iter > 1 takes no path list: the lists are filled by single "
-                                                   "launches (trace the iterations one call each)");
-        if (c.fate || c.replicas || expected || c.fp_map || c.hits)
-            return fail(WGRT_ERR_INVALID_ARGUMENT, "a paths launch takes no fates, replicas, expected-value estimator, "
-                                                   "footprint map or hit list");
+        break;
     }
-    if (c.vis_counts) {
-        if (!c.vis_ends) return fail(WGRT_ERR_INVALID_ARGUMENT, "visit counts need their end records");
-        if (c.vis_rows < 0) return fail(WGRT_ERR_INVALID_ARGUMENT, "n_rows must be >= 0");
-        if (((uintptr_t)c.vis_ends & 15) || ((uintptr_t)c.vis_counts & 3) || ((uintptr_t)c.vis_slot & 3))
+    case TraceMode::kVisits: {
+        const Sink::Visits &v = c.sink.visits;
+        if (!v.ends) return fail(WGRT_ERR_INVALID_ARGUMENT, "visit counts need their end records");
+        if (v.rows < 0) return fail(WGRT_ERR_INVALID_ARGUMENT, "n_rows must be >= 0");
+        if (((uintptr_t)v.ends & 15) || ((uintptr_t)v.counts & 3) || ((uintptr_t)v.slot & 3))
             return fail(WGRT_ERR_INVALID_ARGUMENT, "the end records must be 16-B aligned (the counts and slots 4-B)");
-        if (!c.vis_slot && (c.vis_rows < n_rays || n_rays > 0x7fffffffll))
+        if (!v.slot && (v.rows < n_rays || n_rays > 0x7fffffffll))
             return fail(WGRT_ERR_INVALID_ARGUMENT, "without slots ray i is counted into row i: need n_rays <= n_rows "
                                                    "and fewer than 2^31 rays");
-        if (c.num_iter > 1)
-            return fail(WGRT_ERR_INVALID_ARGUMENT, "num_iter > 1 takes no visit counts: the rows are filled by single "
-                                                   "launches (trace the iterations one call each)");
-        if (c.fate || c.replicas || expected || c.fp_map || c.hits || c.paths)
-            return fail(WGRT_ERR_INVALID_ARGUMENT, "a visits launch takes no fates, replicas, expected-value estimator, "
-                                                   "footprint map, hit list or path list");
+        break;
+    }
+    default: break;   // (fate: one byte per ray, nothing to check; the estimator: above)
     }
     if (c.chunk_order && c.variant == 1)
         return fail(WGRT_ERR_INVALID_ARGUMENT, "chunk_order needs variant 0, 7 or 9");
@@ -1999,26 +1995,9 @@ wgrt_status validate_launch(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
     if (timeline && s->nonunitary_blocks)
         return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline is built without the amplification step: scaled-unitary "
                                           "LUTs only");
-    if (timeline && c.fate)
-        return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel stores no fates: trace with fate or with the timeline");
-    if (timeline && c.replicas)
-        return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel fills no replica tables: trace with replicas or with "
-                                          "the timeline");
-    if (timeline && expected)
-        return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel scores no visits: trace with the expected-value "
-                                          "estimator or with the timeline");
-    if (timeline && c.fp_map)
-        return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel counts no footprints: trace with a footprint map or "
-                                          "with the timeline");
-    if (timeline && c.hits)
-        return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel keeps no hit list: trace with a hit list or with the "
-                                          "timeline");
-    if (timeline && c.paths)
-        return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel keeps no path list: trace with a path list or with "
-                                          "the timeline");
-    if (timeline && c.vis_counts)
-        return fail(WGRT_ERR_UNSUPPORTED, "the wave timeline kernel counts no branches: trace with visit counts or with "
-                                          "the timeline");
+    if (timeline && trait)
+        return fail(WGRT_ERR_UNSUPPORTED, std::string("the wave timeline kernel has no sink and fills no replica tables: "
+                                                      "trace with ") + trait->noun + " or with the timeline");
     if ((c.replicas || expected) && c.variant != 1 && (int64_t)s->nl * s->nx * s->ny >= (int64_t)1 << kRepShift)
         return fail(WGRT_ERR_UNSUPPORTED, "replica tables with variants 7 / 9 need a scene of fewer than 2^24 tiles (the "
                                           "out-coupling queue entry carries the replica above the tile index)");
@@ -2043,24 +2022,35 @@ TraceArgs fill_args(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, 
     A.win = c.win;
     A.stats = stats;
     A.per_ray = per_ray_bounces;
-    A.fate = c.fate;
     A.win_reps = c.replicas;
     A.win_rep_stride = c.rep_stride;
-    A.fp_map = c.fp_map;
-    A.fp = c.fp;
     A.fp_aggregate = g_fp_aggregate.load(std::memory_order_relaxed);
-    A.hits = c.hits;
-    A.hits_cap = c.hits_cap;
-    A.hits_count = c.hits_count;
-    A.hits_tag = c.hits_tag;
-    A.paths = c.paths;
-    A.paths_cap = c.paths_cap;
-    A.paths_count = c.paths_count;
-    A.paths_tag = c.paths_tag;
-    A.select = c.select;
-    A.vis_slot = c.vis_slot;
-    A.vis_counts = c.vis_counts;
-    A.vis_ends = c.vis_ends;
+    switch (c.sink.kind) {   // the sink's payload, the one place it is copied
+    case TraceMode::kFate: A.fate = c.sink.fate; break;
+    case TraceMode::kFp:
+        A.fp_map = c.sink.fp.map;
+        A.fp = c.sink.fp.plan;
+        break;
+    case TraceMode::kHits:
+        A.hits = static_cast<wgrt_hit *>(c.sink.list.buf);
+        A.hits_cap = c.sink.list.cap;
+        A.hits_count = c.sink.list.count;
+        A.hits_tag = c.sink.list.tag;
+        break;
+    case TraceMode::kPaths:
+        A.paths = static_cast<wgrt_path_vertex *>(c.sink.list.buf);
+        A.paths_cap = c.sink.list.cap;
+        A.paths_count = c.sink.list.count;
+        A.paths_tag = c.sink.list.tag;
+        A.select = c.sink.list.select;
+        break;
+    case TraceMode::kVisits:
+        A.vis_slot = c.sink.visits.slot;
+        A.vis_counts = c.sink.visits.counts;
+        A.vis_ends = c.sink.visits.ends;
+        break;
+    default: break;
+    }
     A.vis_channels = visit_channel_count(s->nfc, s->noc);
     A.n_rays = n_rays;
     A.gid_offset = gid_offset;
@@ -2265,6 +2255,24 @@ wgrt_status cfg_of_opts(const wgrt_scene *s, const wgrt_launch_opts *opts, const
         c.win = plan->d_view;
     }
     return WGRT_OK;
+}
+
+// wgrt_trace_windows and every wgrt_trace_<sink>: the options, the window table and the sink as a configuration, then
+// the launch.  replicas >= 0: the table is that many tables (0: one) of n_slabs * W entries each -- wgrt_trace_replicas
+// and wgrt_trace_expected, which have checked s and the table.
+wgrt_status trace_sink(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset, uint32_t *rng_states,
+                       float *matrix_EB, wgrt_trace_stats *stats, uint32_t *per_ray_bounces, void *stream,
+                       const wgrt_launch_opts *opts, const wgrt_window_plan *plan, double *table, const Sink &sink,
+                       int replicas = -1) {
+    LaunchCfg c;
+    const wgrt_status e = cfg_of_opts(s, opts, plan, table, c);
+    if (e != WGRT_OK) return e;
+    c.sink = sink;
+    if (replicas >= 0) {
+        c.replicas = replicas;
+        c.rep_stride = (int64_t)s->nl * s->ny * s->nx * plan->host.W;
+    }
+    return trace_launch(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, c);
 }
 
 // Where a chain's next step goes (wgrt_debug_chain_plan states the rule; no device).
@@ -2582,21 +2590,20 @@ wgrt_status wgrt_trace_windows(const wgrt_scene *s, const wgrt_rays *rays, int64
                                uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats,
                                uint32_t *per_ray_bounces, void *stream, const wgrt_launch_opts *opts,
                                const wgrt_window_plan *plan, double *table) {
-    LaunchCfg c;
-    const wgrt_status e = cfg_of_opts(s, opts, plan, table, c);
-    if (e != WGRT_OK) return e;
-    return trace_launch(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, c);
+    return trace_sink(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, opts, plan, table,
+                      Sink());
 }
 
 wgrt_status wgrt_trace_fate(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
                             uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats, uint32_t *per_ray_bounces,
                             void *stream, const wgrt_launch_opts *opts, const wgrt_window_plan *plan, double *table,
                             uint8_t *fate) {
-    LaunchCfg c;
-    const wgrt_status e = cfg_of_opts(s, opts, plan, table, c);
-    if (e != WGRT_OK) return e;
-    c.fate = fate;
-    return trace_launch(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, c);
+    if (!fate)   // no fates: exactly that call
+        return wgrt_trace_windows(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, opts,
+                                  plan, table);
+    Sink k = Sink::of(TraceMode::kFate);
+    k.fate = fate;
+    return trace_sink(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, opts, plan, table, k);
 }
 
 wgrt_status wgrt_trace_replicas(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
@@ -2610,12 +2617,8 @@ wgrt_status wgrt_trace_replicas(const wgrt_scene *s, const wgrt_rays *rays, int6
         return fail(WGRT_ERR_INVALID_ARGUMENT, "replicas must be 0, 1 or 2 .. " + std::to_string(WGRT_MAX_REPLICAS));
     if (!table) return fail(WGRT_ERR_INVALID_ARGUMENT, "replicas need their table [replicas, n_slabs, W]");
     if (!s) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL scene / rays");
-    LaunchCfg c;
-    const wgrt_status e = cfg_of_opts(s, opts, plan, table, c);
-    if (e != WGRT_OK) return e;
-    c.replicas = replicas;
-    c.rep_stride = (int64_t)s->nl * s->ny * s->nx * plan->host.W;
-    return trace_launch(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, c);
+    return trace_sink(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, opts, plan, table,
+                      Sink(), replicas);
 }
 
 wgrt_status wgrt_trace_expected(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
@@ -2627,13 +2630,8 @@ wgrt_status wgrt_trace_expected(const wgrt_scene *s, const wgrt_rays *rays, int6
         return fail(WGRT_ERR_INVALID_ARGUMENT, "the expected-value estimator needs its table [n_slabs, W] (or [replicas, "
                                                "n_slabs, W]) and the table's plan");
     if (!s) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL scene / rays");
-    LaunchCfg c;
-    const wgrt_status e = cfg_of_opts(s, opts, plan, table, c);
-    if (e != WGRT_OK) return e;
-    c.mode = TraceMode::kEv;
-    c.replicas = replicas >= 2 ? replicas : 0;
-    c.rep_stride = (int64_t)s->nl * s->ny * s->nx * plan->host.W;
-    return trace_launch(s, rays, n_rays, gid_offset, rng_states, nullptr, stats, per_ray_bounces, stream, c);
+    return trace_sink(s, rays, n_rays, gid_offset, rng_states, nullptr, stats, per_ray_bounces, stream, opts, plan, table,
+                      Sink::of(TraceMode::kEv), replicas >= 2 ? replicas : 0);
 }
 
 double wgrt_expected_weight_host(double e1, double e2, double e3, double en1, double en2, double en3, double threshold) {
@@ -2648,12 +2646,9 @@ wgrt_status wgrt_trace_footprint(const wgrt_scene *s, const wgrt_rays *rays, int
         return wgrt_trace_windows(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, opts,
                                   plan, table);
     if (const char *why = footprint_plan_error(fp)) return fail(WGRT_ERR_INVALID_ARGUMENT, why);
-    LaunchCfg c;
-    const wgrt_status e = cfg_of_opts(s, opts, plan, table, c);
-    if (e != WGRT_OK) return e;
-    c.fp_map = map;
-    c.fp = *fp;
-    return trace_launch(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, c);
+    Sink k = Sink::of(TraceMode::kFp);
+    k.fp = {map, *fp};
+    return trace_sink(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, opts, plan, table, k);
 }
 
 wgrt_status wgrt_trace_hits(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
@@ -2663,14 +2658,9 @@ wgrt_status wgrt_trace_hits(const wgrt_scene *s, const wgrt_rays *rays, int64_t 
     if (!hits)   // no list: exactly that call
         return wgrt_trace_windows(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, opts,
                                   plan, table);
-    LaunchCfg c;
-    const wgrt_status e = cfg_of_opts(s, opts, plan, table, c);
-    if (e != WGRT_OK) return e;
-    c.hits = hits;
-    c.hits_cap = capacity;
-    c.hits_count = (unsigned long long *)count;
-    c.hits_tag = tag;
-    return trace_launch(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, c);
+    Sink k = Sink::of(TraceMode::kHits);
+    k.list = {hits, capacity, (unsigned long long *)count, tag, nullptr};
+    return trace_sink(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, opts, plan, table, k);
 }
 
 int32_t wgrt_hit_bytes(void) { return (int32_t)sizeof(wgrt_hit); }
@@ -2683,15 +2673,9 @@ wgrt_status wgrt_trace_paths(const wgrt_scene *s, const wgrt_rays *rays, int64_t
     if (!paths)   // no list: exactly that call
         return wgrt_trace_windows(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, opts,
                                   plan, table);
-    LaunchCfg c;
-    const wgrt_status e = cfg_of_opts(s, opts, plan, table, c);
-    if (e != WGRT_OK) return e;
-    c.paths = paths;
-    c.paths_cap = capacity;
-    c.paths_count = (unsigned long long *)count;
-    c.paths_tag = tag;
-    c.select = select;
-    return trace_launch(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, c);
+    Sink k = Sink::of(TraceMode::kPaths);
+    k.list = {paths, capacity, (unsigned long long *)count, tag, select};
+    return trace_sink(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, opts, plan, table, k);
 }
 
 int32_t wgrt_path_vertex_bytes(void) { return (int32_t)sizeof(wgrt_path_vertex); }
@@ -2703,14 +2687,9 @@ wgrt_status wgrt_trace_visits(const wgrt_scene *s, const wgrt_rays *rays, int64_
     if (!counts)   // no counts: exactly that call
         return wgrt_trace_windows(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, opts,
                                   plan, table);
-    LaunchCfg c;
-    const wgrt_status e = cfg_of_opts(s, opts, plan, table, c);
-    if (e != WGRT_OK) return e;
-    c.vis_counts = counts;
-    c.vis_ends = ends;
-    c.vis_slot = slot;
-    c.vis_rows = n_rows;
-    return trace_launch(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, c);
+    Sink k = Sink::of(TraceMode::kVisits);
+    k.visits = {counts, ends, slot, n_rows};
+    return trace_sink(s, rays, n_rays, gid_offset, rng_states, matrix_EB, stats, per_ray_bounces, stream, opts, plan, table, k);
 }
 
 wgrt_status wgrt_debug_set_footprint_aggregate(int on) {

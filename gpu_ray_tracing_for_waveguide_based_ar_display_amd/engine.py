@@ -331,25 +331,21 @@ def sort_hits(records) -> np.ndarray:
     return records[np.lexsort((records["gid"], hit_tag(records)))]
 
 
-class HitList:
-    """A hit list (``wgrt_hit`` records; ``trace_*(hits=(hit_list, tag))``): the record buffer, a uint8
-    ``[capacity, 32]`` device tensor, and the device counter the launches add to.  ``count()`` is the number of
-    out-couplings so far (stored or not), ``stored()`` is ``min(count, capacity)``; both synchronise.  ``records()``
-    is the stored records as a numpy structured array (``HIT_DTYPE``: ``x, y, gid, tile, flags``) sorted by
-    ``(tag, gid)``; ``hit_inside``, ``hit_tag`` and ``hit_lmn`` decode them.  ``grid(scene, H, W, ranges=None)`` bins
-    the stored records on the device into a float32 ``[num_lmd, ny, nx, H, W]`` grid (``wgrt_hits_grid``): over the
-    scene's eyebox ranges the records inside their rectangle, over ``ranges`` (``[nx, ny, 4]``: xmin, xmax, ymin, ymax
-    per FoV) those inside the caller's -- at ``(80, 120)`` over the scene's, ``matrix_EB`` of the same launches bit for
-    bit.  ``clear()`` zeroes the counter."""
+class _RecordList:
+    """What ``HitList`` and ``PathList`` share: the record buffer, a uint8 ``[capacity, 32]`` device tensor, the device
+    counter the launches add to, and the reading of both.  A subclass names its records: their numpy dtype, the
+    library's struct (whose size ``<struct>_bytes()`` gives), the noun and unit of its overflow message and that
+    message's exception class."""
+    _dtype = _struct = _noun = _unit = _overflow = None
 
     def __init__(self, capacity: int, device=0):
         self.capacity = int(capacity)
         if self.capacity < 0:
             raise ValueError("capacity must be >= 0")
-        if int(load().wgrt_hit_bytes()) != HIT_DTYPE.itemsize:
-            raise WgrtError("the library's wgrt_hit is not 32 bytes")
+        if int(getattr(load(), self._struct + "_bytes")()) != self._dtype.itemsize:
+            raise WgrtError(f"the library's {self._struct} is not 32 bytes")
         self.device = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
-        self.buffer = torch.zeros((self.capacity, HIT_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+        self.buffer = torch.zeros((self.capacity, self._dtype.itemsize), dtype=torch.uint8, device=self.device)
         self.counter = torch.zeros(1, dtype=torch.int64, device=self.device)
 
     def clear(self) -> None:
@@ -364,7 +360,27 @@ class HitList:
     def raw(self) -> np.ndarray:
         """The stored records in the buffer's order."""
         n = self.stored()
-        return self.buffer[:n].cpu().numpy().reshape(-1).view(HIT_DTYPE).copy()
+        return self.buffer[:n].cpu().numpy().reshape(-1).view(self._dtype).copy()
+
+    def check_overflow(self) -> None:
+        """Raise the list's overflow exception if it counted more records than it stores.  Synchronises."""
+        n = self.count()
+        if n > self.capacity:
+            raise self._overflow(f"the {self._noun} counted {n} {self._unit} but has room for {self.capacity}: "
+                                 f"a capacity of {n} would have sufficed")
+
+
+class HitList(_RecordList):
+    """A hit list (``wgrt_hit`` records; ``trace_*(hits=(hit_list, tag))``): the record buffer, a uint8
+    ``[capacity, 32]`` device tensor, and the device counter the launches add to.  ``count()`` is the number of
+    out-couplings so far (stored or not), ``stored()`` is ``min(count, capacity)``; both synchronise.  ``records()``
+    is the stored records as a numpy structured array (``HIT_DTYPE``: ``x, y, gid, tile, flags``) sorted by
+    ``(tag, gid)``; ``hit_inside``, ``hit_tag`` and ``hit_lmn`` decode them.  ``grid(scene, H, W, ranges=None)`` bins
+    the stored records on the device into a float32 ``[num_lmd, ny, nx, H, W]`` grid (``wgrt_hits_grid``): over the
+    scene's eyebox ranges the records inside their rectangle, over ``ranges`` (``[nx, ny, 4]``: xmin, xmax, ymin, ymax
+    per FoV) those inside the caller's -- at ``(80, 120)`` over the scene's, ``matrix_EB`` of the same launches bit for
+    bit.  ``clear()`` zeroes the counter."""
+    _dtype, _struct, _noun, _unit, _overflow = HIT_DTYPE, "wgrt_hit", "hit list", "out-couplings", HitListOverflow
 
     def records(self) -> np.ndarray:
         return sort_hits(self.raw())
@@ -395,10 +411,7 @@ class HitList:
 
 def check_hits(hit_list: HitList) -> None:
     """Raise ``HitListOverflow`` if the list counted more out-couplings than it stores.  Synchronises."""
-    n = hit_list.count()
-    if n > hit_list.capacity:
-        raise HitListOverflow(f"the hit list counted {n} out-couplings but has room for {hit_list.capacity}: "
-                              f"a capacity of {n} would have sufficed")
+    hit_list.check_overflow()
 
 
 def hits_grid_host(records, nx: int, ny: int, num_lmd: int, scene_ranges, H: int, W: int, ranges=None,
@@ -478,7 +491,7 @@ def path_polylines(records) -> dict:
     return out
 
 
-class PathList:
+class PathList(_RecordList):
     """A path list (``wgrt_path_vertex`` records; ``trace_*(paths=(path_list, tag), select=mask)``), the twin of
     ``HitList``: the record buffer, a uint8 ``[capacity, 32]`` device tensor, and the device counter the launches add
     to.  ``count()`` is the number of records so far (stored or not), ``stored()`` is ``min(count, capacity)``; both
@@ -491,18 +504,7 @@ class PathList:
     keeping the stored records (a ray leaves at most its bounces + 1 records: a first pass's ``per_ray_bounces`` bound
     the room a selection needs)."""
 
-    def __init__(self, capacity: int, device=0):
-        self.capacity = int(capacity)
-        if self.capacity < 0:
-            raise ValueError("capacity must be >= 0")
-        if int(load().wgrt_path_vertex_bytes()) != PATH_DTYPE.itemsize:
-            raise WgrtError("the library's wgrt_path_vertex is not 32 bytes")
-        self.device = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
-        self.buffer = torch.zeros((self.capacity, PATH_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
-        self.counter = torch.zeros(1, dtype=torch.int64, device=self.device)
-
-    def clear(self) -> None:
-        self.counter.zero_()
+    _dtype, _struct, _noun, _unit, _overflow = PATH_DTYPE, "wgrt_path_vertex", "path list", "records", PathListOverflow
 
     def reserve(self, capacity: int) -> None:
         """Room for at least ``capacity`` records: a larger buffer takes the stored records' place, in their order (the
@@ -514,17 +516,6 @@ class PathList:
         buffer = torch.zeros((capacity, PATH_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
         buffer[:n] = self.buffer[:n]
         self.buffer, self.capacity = buffer, capacity
-
-    def count(self) -> int:
-        return int(self.counter.cpu()[0])
-
-    def stored(self) -> int:
-        return min(self.count(), self.capacity)
-
-    def raw(self) -> np.ndarray:
-        """The stored records in the buffer's order."""
-        n = self.stored()
-        return self.buffer[:n].cpu().numpy().reshape(-1).view(PATH_DTYPE).copy()
 
     def records(self) -> np.ndarray:
         return sort_paths(self.raw())
@@ -551,10 +542,7 @@ class PathList:
 
 def check_paths(path_list: PathList) -> None:
     """Raise ``PathListOverflow`` if the list counted more records than it stores.  Synchronises."""
-    n = path_list.count()
-    if n > path_list.capacity:
-        raise PathListOverflow(f"the path list counted {n} records but has room for {path_list.capacity}: "
-                               f"a capacity of {n} would have sufficed")
+    path_list.check_overflow()
 
 
 def paths_footprint_host(records, fp: FootprintPlan, num_lmd: int, out=None) -> np.ndarray:
@@ -787,20 +775,55 @@ def _read_columns(rays, rng_states, n_rays, single, device):
     return cols, N
 
 
+_SINKS = ("fate", "replicas", "expected", "footprint", "hits", "paths", "visits")   # the keywords, as they arrived
+
+
+def _launch_sink(fate, replicas, expected, footprint, hits, paths, select, visits, num_iter, chain):
+    """The one rule of what a launch may be asked to leave besides the grid and the window table, checked before any
+    payload is looked at: a launch has at most one sink -- ``fate``, ``expected``, ``footprint``, ``hits``, ``paths``
+    (with its ``select``) or ``visits``; ``replicas`` describe the window table and go alone or with ``expected``; and
+    a launch with a sink or with replicas is a single one (``num_iter == 1``), not a chain's.  Returns ``(kind,
+    payload, B)``: the sink's keyword and its value (``"replicas"`` and ``B`` for replica tables alone, ``None, None``
+    for none) and the replica count (0: the one table).  Raises ``ValueError`` otherwise."""
+    B = _replica_count(replicas)
+    values = (fate, B or None, expected or None, footprint, hits, paths, visits)
+    given = [k for k, v in zip(_SINKS, values) if v is not None]
+    if len(given) > 1 and given != ["replicas", "expected"]:
+        raise ValueError(f"a launch has at most one sink: {given[-1]}= takes no {' or '.join(given[:-1])}")
+    if select is not None and paths is None:
+        raise ValueError("select= chooses the rays of a paths launch: it needs paths=(PathList, tag)")
+    if not given:
+        return None, None, 0
+    kind = given[-1]
+    if int(num_iter) > 1:
+        raise ValueError(f"{kind}= needs num_iter == 1: a sink and replica tables are filled by single launches")
+    if chain:
+        raise ValueError(f"a chain takes no {kind} launches: trace them with single launches")
+    return kind, values[_SINKS.index(kind)], B
+
+
+# kind -> the operator and, from the sink's validated payload, the arguments it adds to trace_windows'
+_SINK_OPS = {
+    None: ("trace_windows", lambda _: ()),
+    "fate": ("trace_fate", lambda fate: (fate,)),
+    "replicas": ("trace_replicas", lambda B: (B,)),
+    "footprint": ("trace_footprint", lambda p: (p[0].x0, p[0].y0, p[0].cell_x, p[0].cell_y, p[0].nx_cells, p[0].ny_cells,
+                                                p[1])),
+    "hits": ("trace_hits", lambda p: (p[0].buffer, p[0].capacity, p[0].counter, int(p[1]))),
+    "paths": ("trace_paths", lambda p: (p[0].buffer, p[0].capacity, p[0].counter, int(p[1]), p[2])),   # (list, tag, select)
+    "visits": ("trace_visits", lambda p: (p[1], p[0].n_rows, p[0].counts, p[0].ends)),
+}
+
+
 def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single, chunk_order=None, num_iter=1, gid_blocks=None, gid_block_rays=0, debug=None,
            grid_sqrt_k=0.0, windows=None, chain=False, fate=None, replicas=0, expected=False, footprint=None,
            hits=None, paths=None, select=None, visits=None):
+    kind, payload, B = _launch_sink(fate, replicas, expected, footprint, hits, paths, select, visits, num_iter, chain)
     device = torch.device("cuda", scene.device)
-    B = _replica_count(replicas)
-    if visits is not None:   # (before anything is read or launched)
-        if fate is not None or B or expected or footprint is not None or hits is not None or paths is not None:
-            raise ValueError("visits= is not combined with fate, replicas, expected, footprint, hits or paths")
-        if int(num_iter) > 1:
-            raise ValueError("visits= needs num_iter == 1: the rows are filled by single launches")
-        if chain:
-            raise ValueError("a chain takes no visits launches")
-        visit_table, visit_slot = visits
+    # the sink's own payload (before anything is read or launched)
+    if kind == "visits":
+        visit_table, visit_slot = payload
         if not isinstance(visit_table, VisitTable):
             raise TypeError("visits=(VisitTable, slot)")
         if visit_table.device != device:
@@ -808,58 +831,26 @@ def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ra
         if visit_table.n_channels != len(visit_channels(scene)):
             raise ValueError(f"the visit table has {visit_table.n_channels} channels, the scene "
                              f"{len(visit_channels(scene))}")
-    if select is not None and paths is None:
-        raise ValueError("select= chooses the rays of a paths launch: it needs paths=(PathList, tag)")
-    if paths is not None:   # (before anything is read or launched)
-        if fate is not None or B or expected or footprint is not None or hits is not None:
-            raise ValueError("paths= is not combined with fate, replicas, expected, footprint or hits")
-        if int(num_iter) > 1:
-            raise ValueError("paths= needs num_iter == 1: the lists are filled by single launches")
-        if chain:
-            raise ValueError("a chain takes no paths launches")
-        path_list, path_tag_ = paths
-        if not isinstance(path_list, PathList):
-            raise TypeError("paths=(PathList, tag)")
-        if path_list.device != device:
-            raise ValueError(f"the path list is on {path_list.device}, expected {device}")
-        if int(scene.num_lmd) > 256:
+    elif kind in ("hits", "paths"):
+        record_list, _ = payload
+        if not isinstance(record_list, PathList if kind == "paths" else HitList):
+            raise TypeError("paths=(PathList, tag)" if kind == "paths" else "hits=(HitList, tag)")
+        if record_list.device != device:
+            raise ValueError(f"the {record_list._noun} is on {record_list.device}, expected {device}")
+        if kind == "paths" and int(scene.num_lmd) > 256:
             raise ValueError("a path record names at most 256 wavelengths: the scene has more")
-    if hits is not None:   # (before anything is read or launched)
-        if fate is not None or B or expected or footprint is not None:
-            raise ValueError("hits= is not combined with fate, replicas, expected or footprint")
-        if int(num_iter) > 1:
-            raise ValueError("hits= needs num_iter == 1: the lists are filled by single launches")
-        if chain:
-            raise ValueError("a chain takes no hits launches")
-        hit_list, hit_tag = hits
-        if not isinstance(hit_list, HitList):
-            raise TypeError("hits=(HitList, tag)")
-        if hit_list.device != device:
-            raise ValueError(f"the hit list is on {hit_list.device}, expected {device}")
-    if footprint is not None:   # (before anything is read or launched)
-        if fate is not None or B or expected:
-            raise ValueError("footprint= is not combined with fate, replicas or expected")
-        if int(num_iter) > 1:
-            raise ValueError("footprint= needs num_iter == 1: the maps are filled by single launches")
-        if chain:
-            raise ValueError("a chain takes no footprint launches")
-        fp, fp_map = footprint
+    elif kind == "footprint":
+        fp, fp_map = payload
         if not isinstance(fp, FootprintPlan):
             raise TypeError("footprint=(FootprintPlan, map)")
         _as_dev(fp_map, torch.int64, "footprint map", device)
         if tuple(fp_map.shape) != fp.map_shape(scene):
             raise ValueError(f"footprint map shape {tuple(fp_map.shape)} != {fp.map_shape(scene)}")
-    if expected:   # (before anything is read or launched)
+    elif kind == "expected":
         if matrix_EB is not None:
             raise ValueError("expected=True takes no grid (matrix_EB=None): a float32 cell cannot hold the 2^-32 sums")
         if windows is None:
             raise ValueError("expected=True needs windows=(plan, table)")
-        if fate is not None:
-            raise ValueError("expected=True takes no fate")
-        if int(num_iter) > 1:
-            raise ValueError("expected=True needs num_iter == 1: its tables are filled by single launches")
-        if chain:
-            raise ValueError("a chain takes no expected-value launches")
     cols, N = _read_columns(rays, rng_states, n_rays, single, device)
     x = cols["x"]
     if matrix_EB is None and windows is None:
@@ -880,19 +871,10 @@ def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ra
         if per_ray_bounces.dtype not in (torch.int32, torch.uint32):
             raise TypeError("per_ray_bounces must be uint32 / int32")
         _as_dev(per_ray_bounces, per_ray_bounces.dtype, "per_ray_bounces", device, x.numel())
-    if fate is not None:
+    if kind == "fate":
         _as_dev(fate, torch.uint8, "fate", device, x.numel())
-        if int(num_iter) > 1:
-            raise ValueError("fate needs num_iter == 1: a fused launch stores no per-trace fates")
-    if B:
-        if windows is None:
-            raise ValueError("replicas need windows=(plan, table): a grid has no replicas")
-        if int(num_iter) > 1:
-            raise ValueError("replicas need num_iter == 1: replica tables are filled by single launches")
-        if fate is not None:
-            raise ValueError("a launch stores fates or fills replica tables, not both")
-        if chain:
-            raise ValueError("a chain takes no replicas")
+    if B and windows is None:
+        raise ValueError("replicas need windows=(plan, table): a grid has no replicas")
     n_chunks = (N + CHUNK - 1) // CHUNK
     if chunk_order is not None:
         _as_dev(chunk_order, torch.int32, "chunk_order", device, n_chunks)
@@ -904,7 +886,7 @@ def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ra
         if select.dtype == torch.bool:
             select = select.view(torch.uint8)
         _as_dev(select, torch.uint8, "select", device, N if N else None)
-    if visits is not None:
+    if kind == "visits":
         if visit_slot is None:
             if N > visit_table.n_rows:
                 raise ValueError(f"without slots ray i is counted into row i: {N} rays need {N} rows, the table has "
@@ -933,33 +915,16 @@ def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ra
         if h <= 0:   # the negated wgrt_status of the failure
             check(-h, "wgrt_chain_begin")
         return h, (args, dbg, windows)
-    if visits is not None:   # torch.ops.wgrt.trace_visits -> wgrt_trace_visits
-        status = ops().trace_visits(*args, plan.handle.value if windows is not None else 0,
-                                    table if windows is not None else None, visit_slot, visit_table.n_rows,
-                                    visit_table.counts, visit_table.ends)
-    elif paths is not None:   # torch.ops.wgrt.trace_paths -> wgrt_trace_paths
-        status = ops().trace_paths(*args, plan.handle.value if windows is not None else 0,
-                                   table if windows is not None else None, path_list.buffer, path_list.capacity,
-                                   path_list.counter, int(path_tag_), select)
-    elif hits is not None:   # torch.ops.wgrt.trace_hits -> wgrt_trace_hits
-        status = ops().trace_hits(*args, plan.handle.value if windows is not None else 0,
-                                  table if windows is not None else None, hit_list.buffer, hit_list.capacity,
-                                  hit_list.counter, int(hit_tag))
-    elif footprint is not None:   # torch.ops.wgrt.trace_footprint -> wgrt_trace_footprint
-        status = ops().trace_footprint(*args, plan.handle.value if windows is not None else 0,
-                                       table if windows is not None else None, fp.x0, fp.y0, fp.cell_x, fp.cell_y,
-                                       fp.nx_cells, fp.ny_cells, fp_map)
-    elif expected:   # torch.ops.wgrt.trace_expected -> wgrt_trace_expected (no grid; B = 0: the one table)
-        status = ops().trace_expected(*args[:10], *args[11:], plan.handle.value, table, B)
-    elif fate is not None:   # torch.ops.wgrt.trace_fate -> wgrt_trace_fate (plan 0, no table: the grid alone)
-        status = ops().trace_fate(*args, plan.handle.value if windows is not None else 0,
-                                  table if windows is not None else None, fate)
-    elif windows is not None and int(replicas or 0):   # torch.ops.wgrt.trace_replicas -> wgrt_trace_replicas (1: one table)
-        status = ops().trace_replicas(*args, plan.handle.value, table, B or 1)
-    elif windows is None:
+    if kind is None and windows is None:
         status = ops().trace(*args)
-    else:
-        status = ops().trace_windows(*args, plan.handle.value, table)
+    elif kind == "expected":   # no grid among its arguments
+        status = ops().trace_expected(*args[:10], *args[11:], plan.handle.value, table, B)
+    else:   # torch.ops.wgrt.trace_<kind> -> wgrt_trace_<kind>: trace_windows' arguments (plan 0, no table: the grid alone)
+        if kind == "paths":
+            payload = (*payload, select)
+        op, own = _SINK_OPS[kind]
+        status = getattr(ops(), op)(*args, plan.handle.value if windows is not None else 0,
+                                    table if windows is not None else None, *own(payload))
     check(status, "wgrt_trace_single" if single else "wgrt_trace_fullcolor")
 
 
@@ -999,18 +964,7 @@ class TraceChain:
                  visits=None):
         if scene.single_lambda:
             raise ValueError("TraceChain needs a full-colour scene")
-        if visits is not None:
-            raise ValueError("a chain takes no visits launches: fill a visit table with single launches")
-        if hits is not None:
-            raise ValueError("a chain takes no hits launches: fill a hit list with single launches")
-        if paths is not None or select is not None:
-            raise ValueError("a chain takes no paths launches: fill a path list with single launches")
-        if footprint is not None:
-            raise ValueError("a chain takes no footprint launches: trace footprint maps with single launches")
-        if expected:
-            raise ValueError("a chain takes no expected-value launches: trace them with single launches")
-        if _replica_count(replicas):
-            raise ValueError("a chain takes no replicas: trace replica tables with single launches")
+        _launch_sink(None, replicas, expected, footprint, hits, paths, select, visits, 1, chain=True)
         self._h = 0
         self._step = ops().chain_step
         self._h, self._keep = _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, None, stream,
