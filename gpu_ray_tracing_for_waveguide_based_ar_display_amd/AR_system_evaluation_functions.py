@@ -551,3 +551,80 @@ def evaluation_device(eb, divisor, evaluate_on: str = "host"):
     if evaluate_on == "device":
         return evaluation_from_window_sums(sums, eb.shape, divisor)
     return evaluation_from_perceive(perceive_from_window_sums(sums, eb.shape, divisor))
+
+
+# ---- polarisation of the delivered light: the Stokes window tables of wgrt_trace_stokes (csrc/wgrt_stokes.h) -------------
+STOKES_QUANTUM = 2.0 ** -30   # a deposit is rint(s_k * 2^30) per normalised Stokes parameter s_k
+
+
+def _f64(a):
+    """``a`` as float64: a torch tensor stays one (on its device), anything else becomes a numpy array."""
+    if hasattr(a, "detach"):
+        import torch
+        return a.detach().to(torch.float64)
+    return np.asarray(a, dtype=np.float64)
+
+
+def _stokes_pair(N, S):
+    N, S = _f64(N), _f64(S)
+    if S.ndim != 3 or S.shape[0] != 3 or tuple(S.shape[1:]) != tuple(N.shape):
+        raise ValueError(f"Stokes tables of shape {tuple(S.shape)} do not lie beside a window table of shape "
+                         f"{tuple(N.shape)}: expected [3, n_slabs, W] and [n_slabs, W]")
+    return N, S
+
+
+def polarisation_from_stokes(N, S) -> dict:
+    """The polarisation state per (slab, window) entry from the window table ``N`` ``[n_slabs, W]`` and the Stokes tables
+    ``S`` int64 ``[3, n_slabs, W]`` of the same launches (``engine.StokesTable``), as float64 numpy arrays: ``mean``
+    ``[3, n_slabs, W]``, the mean normalised Stokes vector ``S_k * 2^-30 / N`` of the out-couplings the entry counts;
+    ``dop`` its length, the degree of polarisation of their incoherent sum; ``orientation`` ``atan2(s2, s1) / 2``, the
+    angle of the ellipse's major axis from the TE axis, in (-pi/2, pi/2]; ``ellipticity`` ``asin(s3 / dop) / 2`` in
+    [-pi/4, pi/4] (0 where ``dop`` is 0).  All NaN where ``N == 0``.  The basis is each FoV's own TE / TM basis of its
+    out-coupled order (``stokes_rotate`` turns it)."""
+    N, S = _stokes_pair(N, S)
+    if hasattr(N, "detach"):
+        N, S = N.cpu().numpy(), S.cpu().numpy()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = np.where(N > 0, S * STOKES_QUANTUM / N, np.nan)
+        dop = np.sqrt((mean * mean).sum(axis=0))
+        orientation = 0.5 * np.arctan2(mean[1], mean[0])
+        ellipticity = np.where(dop > 0, 0.5 * np.arcsin(np.clip(mean[2] / np.where(dop > 0, dop, 1.0), -1.0, 1.0)),
+                               np.where(N > 0, 0.0, np.nan))
+    return dict(mean=mean, dop=dop, orientation=orientation, ellipticity=ellipticity)
+
+
+def stokes_rotate(S, psi):
+    """The Stokes tables ``S`` ``[3, n_slabs, W]`` in a basis turned by ``-psi``: every entry's orientation grows by
+    ``psi`` (radians; a scalar or one angle per slab, ``[n_slabs]``), i.e. ``(S1, S2)`` turn by ``2 psi`` and ``S3``
+    stays.  Float64, still in quanta, so the result feeds ``polarisation_from_stokes`` and ``analyser_table`` as the
+    tables do.  A torch tensor is turned where it lives."""
+    S = _f64(S)
+    if S.ndim != 3 or S.shape[0] != 3:
+        raise ValueError(f"expected Stokes tables [3, n_slabs, W], got {tuple(S.shape)}")
+    if hasattr(S, "detach"):
+        import torch
+        a = 2.0 * torch.as_tensor(psi, dtype=torch.float64, device=S.device)
+        c, s = torch.cos(a), torch.sin(a)
+        stack = torch.stack
+    else:
+        a = 2.0 * np.asarray(psi, dtype=np.float64)
+        c, s = np.cos(a), np.sin(a)
+        stack = np.stack
+    if a.ndim == 1:
+        if a.shape[0] != S.shape[1]:
+            raise ValueError(f"{a.shape[0]} angles for {S.shape[1]} slabs")
+        c, s = c[:, None], s[:, None]
+    elif a.ndim != 0:
+        raise ValueError("psi must be a scalar or one angle per slab")
+    return stack([c * S[0] - s * S[1], s * S[0] + c * S[1], S[2]])
+
+
+def analyser_table(N, S, theta):
+    """The window table seen through an ideal linear polariser whose axis lies at ``theta`` (radians) from the TE axis:
+    ``(N + cos(2 theta) * S1 * 2^-30 + sin(2 theta) * S2 * 2^-30) / 2`` per entry (Malus's law summed over the
+    out-couplings), float64 ``[n_slabs, W]`` -- a window table like ``N``, so it feeds ``evaluation_from_window_sums``,
+    ``perceive_from_window_sums`` and the efficiencies (column 0) unchanged.  A torch tensor stays on its device."""
+    import math
+    N, S = _stokes_pair(N, S)
+    c, s = math.cos(2.0 * float(theta)), math.sin(2.0 * float(theta))
+    return 0.5 * (N + c * (S[0] * STOKES_QUANTUM) + s * (S[1] * STOKES_QUANTUM))

@@ -36,7 +36,8 @@ EXPORTED = ("wgrt_scene_create", "wgrt_scene_create_ex", "wgrt_scene_destroy", "
             "wgrt_hits_grid", "wgrt_hits_grid_host", "wgrt_trace_paths", "wgrt_path_vertex_bytes",
             "wgrt_paths_footprint", "wgrt_paths_footprint_host", "wgrt_trace_visits", "wgrt_visit_channels",
             "wgrt_visits_sensitivity", "wgrt_visits_reweight", "wgrt_visits_sensitivity_host",
-            "wgrt_visits_reweight_host", "wgrt_visit_channel_host", "wgrt_visit_channel_count_host")
+            "wgrt_visits_reweight_host", "wgrt_visit_channel_host", "wgrt_visit_channel_count_host",
+            "wgrt_trace_stokes", "wgrt_stokes_quanta_host")
 EXPORTED_DEBUG = ("wgrt_debug_shadow", "wgrt_debug_scene_copy", "wgrt_debug_set_auto_order",
                   "wgrt_debug_get_auto_order", "wgrt_debug_get_tile_tail", "wgrt_debug_order_host",
                   "wgrt_debug_chain_plan", "wgrt_debug_chain_set_serial", "wgrt_debug_set_byte_locator",
@@ -386,6 +387,11 @@ def load():
         L.wgrt_visit_channel_host.argtypes = [i32, i32, i32, i32, i32]
         L.wgrt_visit_channel_count_host.restype = i32
         L.wgrt_visit_channel_count_host.argtypes = [i32, i32]
+    if hasattr(L, "wgrt_trace_stokes"):   # the Stokes window tables: new symbols within ABI 9, by name
+        L.wgrt_trace_stokes.restype = st
+        L.wgrt_trace_stokes.argtypes = L.wgrt_trace_opts.argtypes + [_vp, _vp, _vp]
+        L.wgrt_stokes_quanta_host.restype = None
+        L.wgrt_stokes_quanta_host.argtypes = [ctypes.c_double] * 4 + [ctypes.POINTER(ctypes.c_int32)]
     if hasattr(L, "wgrt_locator_palette_host"):   # the byte locator's hooks: new symbols within ABI 9, bound by name
         L.wgrt_locator_palette_host.restype = st
         L.wgrt_locator_palette_host.argtypes = [ctypes.POINTER(SceneDesc), ctypes.c_double, _i64, _i64, _d,

@@ -177,6 +177,15 @@ struct TraceArgs {
     wgrt_visit_end *vis_ends;
     int32_t vis_channels;
     int32_t vis_pad_;
+    // Stokes window tables (wgrt_trace_stokes; wgrt_stokes.h): with stokes, an out-coupling that the window table counts
+    // also adds its three quanta q_k to the same entries of table k of the int64 [3, n_slabs, W] tables, stokes_stride
+    // = n_slabs * W entries apart.  Only the STOKES instantiations read them: the exact lane deposits at interact's
+    // out-coupling (trace_grid_stokes_kernel, the kStokes replay); the Jones-vector lane computes the quanta where
+    // interact returns kOut, pushes them with the queue entry into q_stokes (beside q_i; allocated by a Stokes launch's
+    // scratch growth only) and deposits where it bins its queue.  Single launches only.  Last again.
+    int64_t *stokes;
+    int64_t stokes_stride;
+    int4 *q_stokes;
 };
 
 // The replica of global ray id g >= 0 among reps (2 .. 64) copies: g % reps from 32-bit remainders (the 64-bit

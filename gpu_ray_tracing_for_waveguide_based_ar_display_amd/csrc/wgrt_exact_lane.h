@@ -26,6 +26,11 @@
 // HITS (a template parameter of interact and trace_one; off by default): the hit list of wgrt_trace_hits
 // (wgrt_hits.h).  interact's out-coupling appends one record for both outcomes of the rectangle test (hit_store).  A
 // template parameter and not a test of TraceArgs::hits, so that every other kernel is the code it was.
+// STOKES (a template parameter of interact and trace_one; off by default): the Stokes window tables of
+// wgrt_trace_stokes (wgrt_stokes.h).  interact's out-coupling, inside the FoV's eyebox rectangle, evaluates the
+// out-coupled order's field E3 (the third E_field_cal of the interaction, as the reference computes it) and adds its
+// three quanta to the entries the window table counts the out-coupling into (eyebox_bin_stokes).  A template parameter
+// for the same reason.
 #pragma once
 
 #include "wgrt_args.h"
@@ -35,6 +40,7 @@
 #include "wgrt_hits.h"
 #include "wgrt_locator.h"
 #include "wgrt_paths.h"
+#include "wgrt_stokes.h"
 #include "wgrt_visits.h"
 #include "wgrt_window.h"
 
@@ -168,6 +174,27 @@ __device__ __forceinline__ bool eyebox_bin(const TraceArgs &A, const double *T, 
     return false;
 }
 
+// An out-coupling of a Stokes launch (wgrt_trace_stokes; wgrt_stokes.h) that has passed eyebox_inside: eyebox_bin's
+// adds (no replicas: such a launch has none), and the quanta q[k] added to table k of A.stokes at every entry the
+// window table counts it into -- unsigned 64-bit adds of the sign-extended quanta whose result is not used, so the
+// tables do not depend on the order.  Both lanes deposit through it.
+__device__ __forceinline__ bool eyebox_bin_stokes(const TraceArgs &A, const double *T, int l, int m, int n, double x,
+                                                  double y, int32_t q0, int32_t q1, int32_t q2) {
+    const int64_t off = eyebox_offset(A, T, l, m, n, x, y);
+    if (off < 0) return false;
+    if (A.eb) unsafeAtomicAdd(A.eb + off, 1.0f);
+    double *const table = A.win_table;
+    unsigned long long *const st = (unsigned long long *)A.stokes;
+    const int64_t stride = A.stokes_stride;
+    window_visit(*A.win, off, [=](int64_t k) {
+        unsafeAtomicAdd(table + k, 1.0);
+        if (q0) atomicAdd(st + k, (unsigned long long)(int64_t)q0);
+        if (q1) atomicAdd(st + stride + k, (unsigned long long)(int64_t)q1);
+        if (q2) atomicAdd(st + 2 * stride + k, (unsigned long long)(int64_t)q2);
+    });
+    return true;
+}
+
 // The expected-value estimator's deposit (wgrt_expected.h) of a visit at (x, y) that has passed eyebox_inside: q
 // (a multiple of 2^-32; 0: nothing) added to the window table's entries under the bin, by the same membership
 // rule.  Returns whether the bin lies in the buffer -- whether an out-coupling here is an analog hit.
@@ -273,7 +300,7 @@ __device__ __forceinline__ int take_branch(const Loc &loc, Lane &L, const double
 // or kDie (FATE: with the lane's fate set; its region is the state the ray is in, 9 at the entry).
 // Only the chosen branch's phase (two atan2) is evaluated; its field is recomputed
 // by the same operations rather than kept in registers for every branch.
-template <bool FATE = false, bool EV = false, bool HITS = false, class Loc>
+template <bool FATE = false, bool EV = false, bool HITS = false, bool STOKES = false, class Loc>
 __device__ __forceinline__ int interact(const TraceArgs &A, const Loc &loc, Lane &L, int blk, int kind,
                                         bool entry, uint32_t *ev_skip = nullptr) {
     Ray &r = L.r;
@@ -399,7 +426,17 @@ __device__ __forceinline__ int interact(const TraceArgs &A, const Loc &loc, Lane
     if (b == 2) {  // out-coupling (GRTF:1162-1171, 1231-1240)
         // (the replica is the global id's, as the RNG fix-up's id above)
         const auto rep = [&]() { return replica_of(ray_gid(A, L.i), (uint32_t)A.win_reps); };
-        if (HITS) {
+        if (STOKES) {
+            // a Stokes launch (wgrt_trace_stokes; the STOKES instantiations only, as HITS below): the out-coupled
+            // order's field E3, the reference's own third E_field_cal of this interaction, for an out-coupling inside
+            // the rectangle -- beside it nothing is deposited
+            if (eyebox_inside(T, r.x, r.y)) {
+                const Field f3 = efield(r.te, r.tm, cd, sd, B + kBlockRec + 16);
+                int32_t q[3];
+                stokes_quanta(f3.te_re, f3.te_im, f3.tm_re, f3.tm_im, q);
+                if (eyebox_bin_stokes(A, T, L.l, L.m, L.n, r.x, r.y, q[0], q[1], q[2])) L.hit = true;
+            }
+        } else if (HITS) {
             // a hits launch (wgrt_trace_hits; the HITS instantiations only, so that every other kernel is the code it
             // was): the record for both outcomes of the rectangle test, its index reserved by this thread's own
             // returning add (the path is rare)
@@ -555,11 +592,13 @@ __device__ __forceinline__ void footprint_count(const TraceArgs &A, int l, int r
 // PATHS: with the path list's appends (wgrt_paths.h), for a ray that A.select names: one record per draw of the bounce
 // loop, numbered from 0, and the end record of a trace that advance() ends with reason 1 or 5; skip: the draws to pass
 // over, recorded by the Jones lane before it abandoned the ray, which the numbering counts on from.
+// STOKES: with the Stokes tables' deposits (interact<.., STOKES>).
 // VISITS: with the branch counts of wgrt_trace_visits (wgrt_visits.h), for a ray whose slot is not negative: every draw
 // that takes a branch, the in-coupling event's included, counts into its channel -- the branch read from where the draw
 // led and the fate code interact<FATE> leaves -- and an out-coupling writes the row's end record; skip: the draws to
 // pass over (the event's among them), counted by the Jones lane before it abandoned the ray.
-template <bool FATE = false, bool EV = false, bool FP = false, bool HITS = false, bool PATHS = false, bool VISITS = false>
+template <bool FATE = false, bool EV = false, bool FP = false, bool HITS = false, bool PATHS = false, bool VISITS = false,
+          bool STOKES = false>
 __device__ __forceinline__ void trace_one(const TraceArgs &A, int64_t i, Counters &c, uint32_t *s_io = nullptr,
                                           uint32_t skip = 0) {
     static_assert(!(EV && FP) && !(EV && PATHS) && !(FP && PATHS) && !(VISITS && (EV || FP || PATHS)),
@@ -583,7 +622,7 @@ __device__ __forceinline__ void trace_one(const TraceArgs &A, int64_t i, Counter
         // FP, PATHS: where and in which state the ray stands at this draw
         const double fx = L.r.x, fy = L.r.y;
         const int freg = L.r.region;
-        const int next = interact<FATE || FP || PATHS || VISITS, EV, HITS>(A, A.loc, L, blk, kind, entry, &skip);
+        const int next = interact<FATE || FP || PATHS || VISITS, EV, HITS, STOKES>(A, A.loc, L, blk, kind, entry, &skip);
         if (VISITS) {   // (blk and kind are still this draw's)
             if (skip) --skip;   // counted by the lane that abandoned the ray
             else if (vrow >= 0) {

@@ -7,6 +7,7 @@
 #include "wgrt_expected.h"
 #include "wgrt_locator.h"
 #include "wgrt_seg.h"
+#include "wgrt_stokes.h"
 
 namespace wgrt {
 
@@ -440,9 +441,14 @@ __device__ __forceinline__ float amp_step(float amp, float pa, float nmin, doubl
 // took, and -1 anywhere else.  The caller deposits it at the position the ray had before this call -- unless
 // the call returns kUncertain, which scores nothing: the replay then scores this visit.  About 3 % of bounces
 // get here; the common pass pays the kind test alone.
-template <bool SINGLE, bool AMP, bool FATE, bool EV = false, class Loc>
+// STOKES (the Stokes instantiations, wgrt_trace_stokes; wgrt_stokes.h): a draw that out-couples the ray (kOut) also
+// evaluates the out-coupled order's field M3 E -- block record 2, which wgrt_pack.h leaves unrotated, in double
+// precision -- and leaves its three quanta in sq[0..2] for the caller's queue push.  About 2 % of rays get here, once
+// each; every other path is the code it was.
+template <bool SINGLE, bool AMP, bool FATE, bool EV = false, bool STOKES = false, class Loc>
 __device__ __forceinline__ int interact(const TraceArgs &A, const KArgs &K, const Loc &loc, JLane &L, int blk,
-                                        int kind, bool entry, SegAcc *sg = nullptr, double *evq = nullptr) {
+                                        int kind, bool entry, SegAcc *sg = nullptr, double *evq = nullptr,
+                                        int32_t *sq = nullptr) {
     JRay &r = L.r;
     const double *T = KA(jtiles) + (size_t)L.tix * (size_t)A.jtile_d;
     const double *B = T + kJHeader + kJBlock * blk;
@@ -486,6 +492,12 @@ __device__ __forceinline__ int interact(const TraceArgs &A, const KArgs &K, cons
             JDecision w;
             estimate64(w, B, r, three, inv, f01, A.inv_n_g, cw);
             *evq = expected_deposit(w.a0, w.a1, w.a2, r.ener * w.a0, r.ener * w.a1, r.ener * w.a2, t);
+        }
+    }
+    if constexpr (STOKES) {
+        if (__builtin_expect(code == kOut, 0)) {
+            const JField f3 = jones(load_rec(B + kJBlockRec + 16), r);
+            stokes_quanta(f3.er, f3.ei, f3.mr, f3.mi, sq);
         }
     }
     if (code != 0) return code;

@@ -68,6 +68,8 @@ struct wgrt_scene {
         int64_t qcap = 0;
         uint32_t *q_ray = nullptr;           // a hits launch's third queue column, the entry's local ray index: grown
         int64_t qcap_ray = 0;                // by hits launches only (wgrt_trace_hits)
+        int4 *q_stokes = nullptr;            // a Stokes launch's fourth queue column, the entry's three quanta (one
+        int64_t qcap_stokes = 0;             // 16-byte store): grown by Stokes launches only (wgrt_trace_stokes)
         unsigned long long *part = nullptr;  // per-wave counter partials (kPartWords words per slot)
         int64_t part_slots = 0;
         uint64_t *rng64 = nullptr;           // fused launches: per-ray {state, tag} granules

@@ -151,7 +151,11 @@ struct VisitsSink {   // slot int32 [n_rays] or none, counts int32 [n_rows, C] (
     int64_t n_rows;
     const Tensor &counts, &ends;
 };
-using OpSink = std::variant<NoSink, ChainSink, FateSink, ReplicasSink, ExpectedSink, FootprintSink, HitsSink, PathsSink, VisitsSink>;
+struct StokesSink {   // int64 [3, tiles, W], beside the window table
+    const Tensor &stokes;
+};
+using OpSink = std::variant<NoSink, ChainSink, FateSink, ReplicasSink, ExpectedSink, FootprintSink, HitsSink, PathsSink, VisitsSink,
+                            StokesSink>;
 
 // The footprint plan of an operator's six fp_* arguments (out of int32 range: a count the library refuses).
 wgrt_footprint_plan footprint_plan_of(double x0, double y0, double cell_x, double cell_y, int64_t nx_cells, int64_t ny_cells) {
@@ -333,6 +337,18 @@ int64_t trace_core(const Common &a, const OpSink &sink) {
         return launch(VISITS_SYM(wgrt_trace_visits), slot, k->n_rows, static_cast<uint32_t *>(k->counts.data_ptr()),
                       static_cast<wgrt_visit_end *>(k->ends.data_ptr()));
     }
+    if (const auto *k = std::get_if<StokesSink>(&sink)) {   // added to by every out-coupling the window table counts
+        on_device(k->stokes, "stokes", c);
+        TORCH_CHECK(tab, "wgrt.trace_stokes: the Stokes tables lie beside a window table: the launch needs the table and "
+                         "its plan");
+        const int64_t W = WINDOW_SYM(wgrt_window_plan_width)(wp);
+        TORCH_CHECK(k->stokes.scalar_type() == at::kLong && k->stokes.is_contiguous() && k->stokes.dim() == 3 &&
+                        k->stokes.size(0) == 3 && k->stokes.size(1) == info.tiles && k->stokes.size(2) == W,
+                    "wgrt.trace_stokes: stokes must be contiguous int64 [3, ", info.tiles, ", ", W, "], got ",
+                    k->stokes.sizes());
+        return launch(WGRT_SYM(wgrt_trace_stokes, "trace_stokes", "the Stokes tables"),
+                      static_cast<int64_t *>(k->stokes.data_ptr()));
+    }
     if (const auto *k = std::get_if<PathsSink>(&sink)) {
         const RecordList l = record_list("wgrt.trace_paths", k->list, c);
         const uint8_t *sel = nullptr;
@@ -435,6 +451,9 @@ int64_t trace_paths(TRACE_PARAMS, Tensor paths, int64_t capacity, std::optional<
 int64_t trace_visits(TRACE_PARAMS, const std::optional<Tensor> &slot, int64_t n_rows, Tensor counts, Tensor ends) {
     return trace_core(TRACE_COMMON, VisitsSink{slot, n_rows, counts, ends});
 }
+
+// trace_stokes: trace_windows' arguments and the Stokes tables (wgrt_trace_stokes).
+int64_t trace_stokes(TRACE_PARAMS, Tensor stokes) { return trace_core(TRACE_COMMON, StokesSink{stokes}); }
 
 // visits_reduce: the first n_rows rows of a visits table reduced on the scene's device: without lnscale into the
 // sensitivity tables out [C, n_slabs, W] (wgrt_visits_sensitivity), with lnscale float64 [C] into the re-weighted window
@@ -574,6 +593,14 @@ TORCH_LIBRARY(wgrt, m) {
           "float grid_sqrt_k, int plan, Tensor(e!)? table, Tensor? slot, int n_rows, Tensor(f!) counts, Tensor(g!) ends) "
           "-> int",
           &trace_visits);
+    // the same launch adding every counted out-coupling's Stokes quanta to the tables beside the window table
+    // (wgrt_trace_stokes): stokes int64 [3, tiles, W], added to
+    m.def("trace_stokes(int scene, Tensor x, Tensor y, Tensor m, Tensor n, Tensor? lmd_num, Tensor te, Tensor tm, "
+          "Tensor delta_phase, Tensor(a!) rng_states, Tensor(b!)? matrix_EB, Tensor(c!)? stats, "
+          "Tensor(d!)? per_ray_bounces, int n_rays, int gid_offset, int stream, int kernel, int variant, "
+          "int workgroups, Tensor? chunk_order, int num_iter, Tensor? gid_blocks, int gid_block_rays, int debug, "
+          "float grid_sqrt_k, int plan, Tensor(e!)? table, Tensor(f!) stokes) -> int",
+          &trace_stokes);
     // a visits table reduced into sensitivity tables (lnscale None) or a re-weighted window table
     m.def("visits_reduce(int scene, int plan, Tensor counts, Tensor ends, int n_rows, Tensor? lnscale, Tensor(a!) out, "
           "int stream) -> int",

@@ -18,6 +18,7 @@ enum class TraceMode : int {
     kHits,       // appends one record per out-coupling to the hit list (wgrt_trace_hits)
     kPaths,      // appends one record per draw of the selected rays to the path list (wgrt_trace_paths)
     kVisits,     // counts the taken branches of the counted rays per channel (wgrt_trace_visits)
+    kStokes,     // adds every counted out-coupling's Stokes quanta to the tables beside the window table (wgrt_trace_stokes)
     kCount
 };
 constexpr int kTraceModes = (int)TraceMode::kCount;

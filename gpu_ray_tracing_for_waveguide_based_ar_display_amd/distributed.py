@@ -487,7 +487,7 @@ def timed_run(trace_fn, rays, rng, eb, gid: GidMap, steps: int, per_call: int, s
 
 
 def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, replicas: int = 0,
-               expected: bool = False, footprint=None, hits=None, paths=None, visits=None):
+               expected: bool = False, footprint=None, hits=None, paths=None, visits=None, stokes=None):
     """trace_fn for ``run_steps`` / ``trace_job`` using the HIP kernel (torch device tensors); ``stats``
     (int64[STATS_LEN] device tensor) is added to by every call.  A shard of several block ranges passes its global
     ids as ``gid_blocks``, uploaded once per map and device and kept on the map (``GidMap.device_blocks``).
@@ -538,7 +538,11 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, rep
     sum of squares): every call first runs a fate launch with no grid on a clone of the RNG states into the scratch table,
     gives the rays of the ``eyebox`` class the rows 0, 1, ... (an exclusive cumsum of the mask), runs the visits launch
     from the original states (``engine.trace_fullcolor(visits=...)``) and reduces its rows into ``sens`` (and ``table``).
-    Single launches only and no ``chain`` again; the tables are sums over rays, so the ranks' tables add."""
+    Single launches only and no ``chain`` again; the tables are sums over rays, so the ranks' tables add.
+
+    ``stokes``: an ``engine.StokesTable`` of the job's plan (needs ``windows``): every call also adds the Stokes quanta of
+    the out-couplings its window table counts to the int64 tables (``engine.trace_fullcolor(stokes=...)``): single
+    launches only and no ``chain`` again.  Integer sums: the ranks' tables add exactly, ``reduce_eyebox(stokes.raw())``."""
     from .engine import TraceChain, VisitTable, select_by_fate, trace_fullcolor
     calls = [0]
 
@@ -589,7 +593,7 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, rep
             more = dict(visits=visits_for(rays, rng, gid))
         trace_fullcolor(scene, rays, rng, eb, stats=stats, variant=variant, num_iter=num_iter, windows=windows,
                         fate=fate, replicas=replicas, expected=expected, footprint=footprint,
-                        hits=None if hits is None else (hits, calls[0]), **more, **ids_of(rng, gid))
+                        hits=None if hits is None else (hits, calls[0]), stokes=stokes, **more, **ids_of(rng, gid))
         if visits is not None:
             reduce_visits(more["visits"][0])
         calls[0] += 1
@@ -601,7 +605,7 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, rep
         return TraceChain(scene, rays, rng, eb, stats=stats, variant=variant, windows=windows,
                           gather=hasattr(load(), "wgrt_chain_gather"), **ids_of(rng, gid))
     if fate is None and int(replicas or 0) < 2 and not expected and footprint is None and hits is None and paths is None \
-            and visits is None:
+            and visits is None and stokes is None:
         fn.chain = chain
     return fn
 

@@ -54,7 +54,8 @@ def trace_fullcolor(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_E
                     workgroups: int = 0, chunk_order: torch.Tensor | None = None, num_iter: int = 1,
                     gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
                     grid_sqrt_k: float = 0.0, windows=None, fate: torch.Tensor | None = None, replicas: int = 0,
-                    expected: bool = False, footprint=None, hits=None, paths=None, select=None, visits=None) -> None:
+                    expected: bool = False, footprint=None, hits=None, paths=None, select=None, visits=None,
+                 stokes=None) -> None:
     """Asynchronous launch on ``stream`` (default: torch's current stream).
 
     rays: dict of device float32 tensors keyed like the reference columns
@@ -109,6 +110,11 @@ def trace_fullcolor(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_E
     ``slot.max() >= n_rows`` (the device does not validate slots; the check synchronises).  Single launches only;
     ``fate``, ``replicas``, ``expected``, ``footprint``, ``hits``, ``paths``, ``num_iter > 1`` and a ``TraceChain``
     raise ``ValueError``.
+    stokes: a ``StokesTable`` of the scene and the window plan (``wgrt_trace_stokes``; needs ``windows=(plan, table)``):
+    every out-coupling the window table counts also adds the three fixed-point normalised Stokes parameters of the
+    out-coupled field (``q_k = rint(s_k * 2^30)``, in the TE / TM basis of that FoV's out-coupled order) to the same
+    entries of the int64 ``[3, n_slabs, W]`` tables; nothing else the launch leaves changes.  Single launches only; any
+    other sink, ``replicas``, ``num_iter > 1`` and a ``TraceChain`` raise ``ValueError``.
     """
     if scene.single_lambda:
         raise ValueError("trace_fullcolor needs a full-colour scene; use trace_single for a single-wavelength one")
@@ -116,7 +122,7 @@ def trace_fullcolor(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_E
            workgroups, single=False, chunk_order=chunk_order, num_iter=num_iter, gid_blocks=gid_blocks,
            gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows, fate=fate,
            replicas=replicas, expected=expected, footprint=footprint, hits=hits, paths=paths, select=select,
-           visits=visits)
+           visits=visits, stokes=stokes)
 
 
 def new_stats(device) -> torch.Tensor:
@@ -160,19 +166,20 @@ def trace_single(scene: Scene, rays: dict, rng_states: torch.Tensor, matrix_EB: 
                  workgroups: int = 0, chunk_order: torch.Tensor | None = None, num_iter: int = 1,
                  gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
                  grid_sqrt_k: float = 0.0, windows=None, fate: torch.Tensor | None = None, replicas: int = 0,
-                 expected: bool = False, footprint=None, hits=None, paths=None, select=None, visits=None) -> None:
+                 expected: bool = False, footprint=None, hits=None, paths=None, select=None, visits=None,
+                 stokes=None) -> None:
     """One launch of the single-wavelength kernel (``process_rays_kernel_pro``, GRTF:419-831)
     through ``wgrt_trace_single_ex``: no ``lmd_num`` column (ignored if present),
     matrix_EB [NY, NX, 80, 120], branch guard ener * efficiency > 1e-15.  The scene must be
     a single-wavelength one (``Scene.from_geometry(..., wavelength=l)`` or 3-D LUTs).  ``windows``, ``fate``,
-    ``replicas``, ``expected``, ``footprint``, ``hits``, ``paths``, ``select``, ``visits``: as ``trace_fullcolor``."""
+    ``replicas``, ``expected``, ``footprint``, ``hits``, ``paths``, ``select``, ``visits``, ``stokes``: as ``trace_fullcolor``."""
     if not scene.single_lambda:
         raise ValueError("trace_single needs a single-wavelength scene (Scene.from_geometry(..., wavelength=l))")
     _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single=True, chunk_order=chunk_order, num_iter=num_iter, gid_blocks=gid_blocks,
            gid_block_rays=gid_block_rays, debug=debug, grid_sqrt_k=grid_sqrt_k, windows=windows, fate=fate,
            replicas=replicas, expected=expected, footprint=footprint, hits=hits, paths=paths, select=select,
-           visits=visits)
+           visits=visits, stokes=stokes)
 
 
 MAX_REPLICAS = 64   # WGRT_MAX_REPLICAS (include/wgrt.h)
@@ -736,6 +743,48 @@ def visits_reweight_host(counts, ends, lnscale, nx: int, ny: int, num_lmd: int, 
                         scene_ranges, mask, step_y, step_x, shape, out, ln.ctypes.data)
 
 
+STOKES_SCALE = 2.0 ** 30   # quanta per unit of a normalised Stokes parameter (csrc/wgrt_stokes.h)
+
+
+class StokesTable:
+    """The Stokes window tables of ``trace_*(stokes=table)`` (``wgrt_trace_stokes``; csrc/wgrt_stokes.h): ``tables``, an
+    int64 ``[3, n_slabs, plan.W]`` device tensor that the launches add to -- table k holds, entry by entry beside the
+    window table ``N`` of the same launches, the sum of ``q_k = rint(s_k * 2^30)`` over the out-couplings ``N`` counts,
+    ``s_1 .. s_3`` the normalised Stokes parameters of the out-coupled field in the TE / TM basis of that FoV's
+    out-coupled order.  ``clear()`` zeroes them (the launches never do); ``raw()`` is the tensor; ``host()`` a numpy
+    copy.  ``AR_system_evaluation_functions.polarisation_from_stokes(N, S)`` turns them into mean Stokes vectors."""
+
+    def __init__(self, scene: Scene, plan: WindowPlan, device=None):
+        self.scene, self.plan = scene, plan
+        device = scene.device if device is None else device
+        self.device = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
+        if self.device.type == "cuda" and self.device.index is None:   # "cuda": the current device, named
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if self.device != torch.device("cuda", scene.device):
+            raise ValueError(f"the Stokes tables are on {self.device}, the scene on device {scene.device}")
+        if plan.device != scene.device:
+            raise ValueError(f"the plan is on device {plan.device}, the scene on device {scene.device}")
+        self.tables = torch.zeros((3, scene.num_lmd * scene.ny * scene.nx, plan.W), dtype=torch.int64, device=self.device)
+
+    def clear(self) -> None:
+        self.tables.zero_()
+
+    def raw(self) -> torch.Tensor:
+        return self.tables
+
+    def host(self) -> np.ndarray:
+        return self.tables.cpu().numpy().copy()
+
+
+def stokes_quanta(a: complex, b: complex) -> tuple:
+    """The three quanta ``(q1, q2, q3)`` of the field with complex TE amplitude ``a`` and TM amplitude ``b``, through the
+    code the kernels run (``wgrt_stokes_quanta_host``; no GPU needed)."""
+    q = (ctypes.c_int32 * 3)()
+    a, b = complex(a), complex(b)
+    load().wgrt_stokes_quanta_host(a.real, a.imag, b.real, b.imag, q)
+    return int(q[0]), int(q[1]), int(q[2])
+
+
 def _debug_opts(debug: dict | None):
     if not debug:
         return None
@@ -775,18 +824,18 @@ def _read_columns(rays, rng_states, n_rays, single, device):
     return cols, N
 
 
-_SINKS = ("fate", "replicas", "expected", "footprint", "hits", "paths", "visits")   # the keywords, as they arrived
+_SINKS = ("fate", "replicas", "expected", "footprint", "hits", "paths", "visits", "stokes")   # the keywords, as they arrived
 
 
-def _launch_sink(fate, replicas, expected, footprint, hits, paths, select, visits, num_iter, chain):
+def _launch_sink(fate, replicas, expected, footprint, hits, paths, select, visits, num_iter, chain, stokes=None):
     """The one rule of what a launch may be asked to leave besides the grid and the window table, checked before any
     payload is looked at: a launch has at most one sink -- ``fate``, ``expected``, ``footprint``, ``hits``, ``paths``
-    (with its ``select``) or ``visits``; ``replicas`` describe the window table and go alone or with ``expected``; and
+    (with its ``select``), ``visits`` or ``stokes``; ``replicas`` describe the window table and go alone or with ``expected``; and
     a launch with a sink or with replicas is a single one (``num_iter == 1``), not a chain's.  Returns ``(kind,
     payload, B)``: the sink's keyword and its value (``"replicas"`` and ``B`` for replica tables alone, ``None, None``
     for none) and the replica count (0: the one table).  Raises ``ValueError`` otherwise."""
     B = _replica_count(replicas)
-    values = (fate, B or None, expected or None, footprint, hits, paths, visits)
+    values = (fate, B or None, expected or None, footprint, hits, paths, visits, stokes)
     given = [k for k, v in zip(_SINKS, values) if v is not None]
     if len(given) > 1 and given != ["replicas", "expected"]:
         raise ValueError(f"a launch has at most one sink: {given[-1]}= takes no {' or '.join(given[:-1])}")
@@ -812,14 +861,16 @@ _SINK_OPS = {
     "hits": ("trace_hits", lambda p: (p[0].buffer, p[0].capacity, p[0].counter, int(p[1]))),
     "paths": ("trace_paths", lambda p: (p[0].buffer, p[0].capacity, p[0].counter, int(p[1]), p[2])),   # (list, tag, select)
     "visits": ("trace_visits", lambda p: (p[1], p[0].n_rows, p[0].counts, p[0].ends)),
+    "stokes": ("trace_stokes", lambda t: (t.tables,)),
 }
 
 
 def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ray_bounces, stream, variant,
            workgroups, single, chunk_order=None, num_iter=1, gid_blocks=None, gid_block_rays=0, debug=None,
            grid_sqrt_k=0.0, windows=None, chain=False, fate=None, replicas=0, expected=False, footprint=None,
-           hits=None, paths=None, select=None, visits=None):
-    kind, payload, B = _launch_sink(fate, replicas, expected, footprint, hits, paths, select, visits, num_iter, chain)
+           hits=None, paths=None, select=None, visits=None, stokes=None):
+    kind, payload, B = _launch_sink(fate, replicas, expected, footprint, hits, paths, select, visits, num_iter, chain,
+                                    stokes)
     device = torch.device("cuda", scene.device)
     # the sink's own payload (before anything is read or launched)
     if kind == "visits":
@@ -846,6 +897,16 @@ def _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, per_ra
         _as_dev(fp_map, torch.int64, "footprint map", device)
         if tuple(fp_map.shape) != fp.map_shape(scene):
             raise ValueError(f"footprint map shape {tuple(fp_map.shape)} != {fp.map_shape(scene)}")
+    elif kind == "stokes":
+        if not isinstance(payload, StokesTable):
+            raise TypeError("stokes=StokesTable")
+        if payload.device != device:
+            raise ValueError(f"the Stokes tables are on {payload.device}, expected {device}")
+        if windows is None:
+            raise ValueError("stokes= lies beside a window table: it needs windows=(plan, table)")
+        if tuple(payload.tables.shape) != (3, scene.num_lmd * scene.ny * scene.nx, windows[0].W):
+            raise ValueError(f"the Stokes tables' shape {tuple(payload.tables.shape)} != "
+                             f"{(3, scene.num_lmd * scene.ny * scene.nx, windows[0].W)}")
     elif kind == "expected":
         if matrix_EB is not None:
             raise ValueError("expected=True takes no grid (matrix_EB=None): a float32 cell cannot hold the 2^-32 sums")
@@ -961,10 +1022,10 @@ class TraceChain:
                  gid_blocks: torch.Tensor | None = None, gid_block_rays: int = 0, debug: dict | None = None,
                  grid_sqrt_k: float = 0.0, windows=None, replicas: int = 0, expected: bool = False,
                  gather: bool | int = False, hold: bool = False, footprint=None, hits=None, paths=None, select=None,
-                 visits=None):
+                 visits=None, stokes=None):
         if scene.single_lambda:
             raise ValueError("TraceChain needs a full-colour scene")
-        _launch_sink(None, replicas, expected, footprint, hits, paths, select, visits, 1, chain=True)
+        _launch_sink(None, replicas, expected, footprint, hits, paths, select, visits, 1, chain=True, stokes=stokes)
         self._h = 0
         self._step = ops().chain_step
         self._h, self._keep = _trace(scene, rays, rng_states, matrix_EB, gid_offset, n_rays, stats, None, stream,
@@ -1354,6 +1415,6 @@ def expected_weight(e1: float, e2: float, e3: float, en1: float, en2: float, en3
     return float(load().wgrt_expected_weight_host(e1, e2, e3, en1, en2, en3, threshold))
 
 
-__all__ = ["VisitTable", "visit_channels", "ess_of", "visits_sensitivity_host", "visits_reweight_host", "VISIT_END_DTYPE", "Scene", "WindowPlan", "FootprintPlan", "footprint_bin", "FOOTPRINT_CHANNELS", "PathList", "PathListOverflow", "check_paths", "paths_footprint_host", "sort_paths", "path_polylines", "path_state", "path_kind", "path_lmd", "path_tag", "PATH_DTYPE", "PATH_KINDS", "select_by_fate", "HitList", "HitListOverflow", "check_hits", "hits_grid_host", "sort_hits", "hit_inside", "hit_tag", "hit_lmn", "HIT_DTYPE", "TraceChain", "fold_replicas", "expected_weight", "MAX_REPLICAS", "fate_census", "fate_census_host", "fate_col", "loss_budget", "FATE_CLASSES", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
+__all__ = ["StokesTable", "stokes_quanta", "STOKES_SCALE", "VisitTable", "visit_channels", "ess_of", "visits_sensitivity_host", "visits_reweight_host", "VISIT_END_DTYPE", "Scene", "WindowPlan", "FootprintPlan", "footprint_bin", "FOOTPRINT_CHANNELS", "PathList", "PathListOverflow", "check_paths", "paths_footprint_host", "sort_paths", "path_polylines", "path_state", "path_kind", "path_lmd", "path_tag", "PATH_DTYPE", "PATH_KINDS", "select_by_fate", "HitList", "HitListOverflow", "check_hits", "hits_grid_host", "sort_hits", "hit_inside", "hit_tag", "hit_lmn", "HIT_DTYPE", "TraceChain", "fold_replicas", "expected_weight", "MAX_REPLICAS", "fate_census", "fate_census_host", "fate_col", "loss_budget", "FATE_CLASSES", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
            "trace_fullcolor", "trace_single", "init_rays", "schedule_by_lifetime",
            "rays_to_device", "classify_points", "shadow", "selftest_math", "RAY_COLUMNS", "_lib"]

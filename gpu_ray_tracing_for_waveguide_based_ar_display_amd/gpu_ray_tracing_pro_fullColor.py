@@ -64,7 +64,7 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
         eyebox: str = "host", keep_grid: bool = False, evaluate_on: str = "host",
         keep_image: bool = False, budget: bool = False, error_bars: int = 0, estimator: str = "analog",
         footprint=None, hits=None, paths=None, paths_capacity=None, paths_footprint=None, sensitivity=None,
-        what_if=None) -> dict:
+        what_if=None, polarisation: bool = False, analyser=None, analyser_frame: str = "fov") -> dict:
     """The reference script's job on this engine; returns its printed quantities and arrays.
     ``points``: the R/2 in-coupler origins to use (default: sampled, GRTF:12-23, seeded by
     ``point_seed``); ``png``: where to write the "Eyebox Center View" image (needs ``evaluate``).
@@ -187,7 +187,41 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
 
     Both work together and leave everything else returned bit-identical to the run without them.  ``budget=True``,
     ``error_bars``, ``estimator="expected"``, ``footprint``, ``hits`` and ``paths`` with either raise ``ValueError``
-    before any GPU work."""
+    before any GPU work.
+
+    ``polarisation``: also the polarisation state of the delivered light (needs ``eyebox="windows"``).  The traces go as
+    plain single launches that add, for every out-coupling the window table counts, the three fixed-point normalised
+    Stokes parameters of the out-coupled field to int64 tables ``[3, n_slabs, 57]`` beside it (``engine.StokesTable``,
+    ``engine.trace_fullcolor(stokes=...)``); several GPUs sum-reduce theirs to rank 0.  The basis is each FoV's own
+    TE / TM basis of its out-coupled order, as the LUTs define it (``analyser_frame="fov"``); ``"lab"`` turns each FoV's
+    table by its out-coupled azimuth plus 90 degrees (``geom.angles["phi_in_ic"]``, ``couplers_coor._field_angles``'
+    ``ph``; ``stokes_rotate``) into the plate's x / y axes -- the paraxial form: it neglects ``cos(theta_polar)``, under
+    2 % at this field of view.  Printed per wavelength: the mean Stokes vector and the degree of polarisation of all
+    delivered light, and the spread of the per-FoV degree of polarisation.  ``analyser``: degrees (None: none): also the
+    efficiencies and the evaluation of the table seen through an ideal linear polariser at that angle from the frame's
+    first axis (``analyser_table``), with no re-trace.  Returned as ``stokes`` (the int64 tables, always in the FoVs' own
+    bases), ``polarisation`` (``frame``, ``mean`` ``[L, 3]``, ``dop`` ``[L]``, ``dop_fov`` ``[L, NY, NX]``) and, with an
+    analyser, ``analysed`` (``theta_deg``, ``frame``, ``table``, ``A``, ``efficiency`` and, with ``evaluate``,
+    ``delta_e``, ``U_fov``, ``U_EB``).  Everything returned before is bit-identical with and without it.  ``budget=True``,
+    ``error_bars``, ``estimator="expected"``, ``footprint``, ``hits``, ``paths``, ``sensitivity`` and ``what_if`` with it
+    raise ``ValueError`` before any GPU work."""
+    if analyser_frame not in ("fov", "lab"):
+        raise ValueError(f"analyser_frame must be 'fov' or 'lab', got {analyser_frame!r}")
+    if analyser is not None:
+        if isinstance(analyser, bool) or not isinstance(analyser, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(float(analyser)):
+            raise ValueError(f"analyser must be an angle in degrees, got {analyser!r}")
+        if not polarisation:
+            raise ValueError("analyser needs polarisation=True: the analysed table comes from the Stokes tables")
+        analyser = float(analyser)
+    if polarisation:
+        if budget or error_bars or estimator == "expected" or footprint is not None or \
+                not (hits is None or hits is False) or not (paths is None or paths is False) or \
+                not (sensitivity is None or sensitivity is False) or what_if is not None:
+            raise ValueError("polarisation is not combined with budget=True, error_bars, estimator='expected', footprint, "
+                             "hits, paths, sensitivity or what_if: a launch fills Stokes tables or does one of those")
+        if eyebox != "windows":
+            raise ValueError("polarisation fills tables beside the window table: it needs eyebox='windows'")
     top_k = 0
     if sensitivity is None or sensitivity is False:
         sensitivity = None
@@ -318,6 +352,10 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
                 job.paths.windows = (scratch, scratch.new_table(job.scene))
                 if auto:
                     job.paths.bounces = torch.zeros(job.shard.n_rays, dtype=torch.int32, device=job.dev)
+        job.stokes = None
+        if polarisation:
+            from .engine import StokesTable
+            job.stokes = StokesTable(job.scene, job.windows[0], job.dev)
         job.visits = None
         if sensitivity is not None or what_if is not None:
             import torch
@@ -372,6 +410,10 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
             sens = reduce_eyebox(job.visits.sens) if job.visits.sens is not None else None
             if what_if is not None:
                 wtable, wsums = reduce_eyebox(job.visits.table), reduce_eyebox(job.visits.sums)
+        stokes = None
+        if job.stokes is not None:   # integer sums: the ranks' tables add exactly
+            from .distributed import reduce_eyebox
+            stokes = reduce_eyebox(job.stokes.raw())
         if job.rank != 0:
             return out
         _report(job, out, grid, table, reps)
@@ -389,6 +431,8 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
             _report_sensitivity(job, out, sens, table, top_k)
         if wtable is not None:
             _report_what_if(job, out, what_if, wtable, wsums, evaluate, evaluate_on)
+        if stokes is not None:
+            _report_polarisation(job, out, table, stokes, analyser, analyser_frame, evaluate, evaluate_on)
         out["post_seconds"] = time.perf_counter() - t_post
         job.say(f"Post-processing time  : {out['post_seconds']:.4f} s  (eyebox reduced "
                 f"{'by the trace' if eyebox == 'windows' else 'on the ' + eyebox})")
@@ -482,6 +526,8 @@ def _trace(job, variant, fuse) -> float:
         per_call = 1
     if getattr(job, "visits", None) is not None:          # ... or counts branch visits
         per_call = 1
+    if getattr(job, "stokes", None) is not None:          # ... or fills Stokes tables
+        per_call = 1
     calls = split_calls(job.num_iter, per_call)
     if n_rays and calls:
         reserve(job.scene, n_rays, max(calls))
@@ -491,7 +537,7 @@ def _trace(job, variant, fuse) -> float:
         run_steps(hip_tracer(job.scene, variant, job.stats, job.windows, fate=job.fate, replicas=job.replicas,
                              expected=getattr(job, "expected", False), footprint=getattr(job, "footprint", None),
                              hits=getattr(job, "hits", None), paths=getattr(job, "paths", None),
-                             visits=getattr(job, "visits", None)),
+                             visits=getattr(job, "visits", None), stokes=getattr(job, "stokes", None)),
                   job.rays, job.rng, job.eb,
                   job.shard.gid, job.num_iter, per_call, hook=hook)
     t1.record()
@@ -599,6 +645,61 @@ def _report_what_if(job, out: dict, scales: dict, wtable, wsums, evaluate: bool,
         job.say(f"FoV uniformity        : {w['U_fov'] * 100:8.2f} %")
         job.say(f"Eyebox uniformity     : {w['U_EB'] * 100:8.2f} %")
     out["what_if"] = w
+
+
+def _report_polarisation(job, out: dict, table, stokes, analyser, frame: str, evaluate: bool, evaluate_on: str) -> None:
+    """The Stokes tables into ``out["stokes"]``, the polarisation of the delivered light into ``out["polarisation"]`` and
+    printed per wavelength, and, with an analyser, the analysed table's efficiencies and evaluation into
+    ``out["analysed"]`` (as ``_report`` and ``_evaluate`` give them for the job's own table)."""
+    from .AR_system_evaluation_functions import (analyser_table, evaluation_from_perceive, evaluation_from_window_sums,
+                                                 perceive_from_window_sums, polarisation_from_stokes, stokes_rotate)
+    shape = job.scene.eb_shape()
+    nl, ny, nx = (int(v) for v in shape[:3])
+    out["stokes"] = stokes.cpu().numpy()
+    S = stokes
+    if frame == "lab":
+        # slab (l, n, m) of FoV (m, n): its TE axis lies at the out-coupled azimuth + 90 degrees (paraxial)
+        import torch
+        ph = np.asarray(job.geom.angles["phi_in_ic"], dtype=np.float64)[0]   # [nx, ny]
+        psi = np.broadcast_to(ph.T[None] + np.pi / 2, (nl, ny, nx)).reshape(-1)
+        S = stokes_rotate(stokes, torch.from_numpy(np.ascontiguousarray(psi)).to(stokes.device))
+    N0 = table[:, 0].cpu().numpy().astype(np.float64)                      # the slabs' totals
+    S0 = (S[:, :, 0].cpu().numpy()).astype(np.float64)                     # [3, n_slabs]
+    per_fov = polarisation_from_stokes(N0[:, None], S0[:, :, None])
+    dop_fov = per_fov["dop"][:, 0].reshape(nl, ny, nx)
+    whole = polarisation_from_stokes(N0.reshape(nl, -1).sum(axis=1)[:, None],
+                                     S0.reshape(3, nl, -1).sum(axis=2)[:, :, None])
+    mean, dop = whole["mean"][:, :, 0].T, whole["dop"][:, 0]               # [L, 3], [L]
+    out["polarisation"] = dict(frame=frame, mean=mean, dop=dop, dop_fov=dop_fov)
+    names = {0: "Blue", 1: "Green", 2: "Red"}
+    basis = "each FoV's own TE / TM basis" if frame == "fov" else "the plate's axes, paraxial"
+    job.say(f"Polarisation of the delivered light ({basis})")
+    job.say(f"  {'':10s}{'s1':>9s}{'s2':>9s}{'s3':>9s}{'DoP':>9s}{'DoP over the FoVs: min / mean / max':>40s}")
+    for k in range(nl):
+        d = dop_fov[k][np.isfinite(dop_fov[k])]
+        spread = f"{d.min():.3f} / {d.mean():.3f} / {d.max():.3f}" if d.size else "-"
+        job.say(f"  {names.get(k, str(k)):10s}{mean[k, 0]:9.4f}{mean[k, 1]:9.4f}{mean[k, 2]:9.4f}{dop[k]:9.4f}{spread:>40s}")
+    if analyser is None:
+        return
+    atab = analyser_table(table, S, np.deg2rad(analyser))
+    A = atab[:, 0].cpu().numpy().reshape(shape[:-2]).astype(np.float32) / job.num_rays / job.num_iter
+    eff = {names.get(k, str(k)): float(np.sum(A[k] * 3)) for k in range(A.shape[0])}
+    a = dict(theta_deg=analyser, frame=frame, table=atab.cpu().numpy(), A=A, efficiency=eff)
+    job.say(f"Through a linear polariser at {analyser:g} degrees ({frame} frame)")
+    for c in ("Red", "Green", "Blue"):
+        if c in eff:
+            job.say(f"Efficiency ({c:5s})    : {eff[c] * 100:8.3f} %")
+    if evaluate:
+        divisor = job.R * job.num_iter
+        if evaluate_on == "device":
+            *figures, _ = evaluation_from_window_sums(atab.contiguous(), shape, divisor, image="center")
+        else:
+            *figures, _ = evaluation_from_perceive(perceive_from_window_sums(a["table"], shape, divisor))
+        a["delta_e"], a["U_fov"], a["U_EB"] = (float(v) for v in figures)
+        job.say(f"Color dispersion      : {a['delta_e']:8.2f}")
+        job.say(f"FoV uniformity        : {a['U_fov'] * 100:8.2f} %")
+        job.say(f"Eyebox uniformity     : {a['U_EB'] * 100:8.2f} %")
+    out["analysed"] = a
 
 
 def _gather_paths(job):
@@ -848,6 +949,18 @@ def main(argv=None):
     ap.add_argument("--what-if", default="", metavar="CHANNEL=SCALE[,...]",
                     help="also the figures of the design whose channels' efficiencies are scaled so, from the same rays "
                          "re-weighted, e.g. 'r4[2].b3=1.2,r2[0].b2=0.9'; needs --eyebox windows")
+    ap.add_argument("--polarisation", action="store_true",
+                    help="also the polarisation of the delivered light: Stokes tables beside the window table, the mean "
+                         "Stokes vector and degree of polarisation per wavelength; needs --eyebox windows; not with "
+                         "--budget, --error-bars, --estimator expected, --footprint, --hits, --paths, --sensitivity or "
+                         "--what-if")
+    ap.add_argument("--analyser", type=float, default=None, metavar="DEG",
+                    help="with --polarisation: also the efficiencies and the evaluation through an ideal linear polariser "
+                         "at DEG degrees, from the same trace")
+    ap.add_argument("--analyser-frame", choices=["fov", "lab"], default="fov",
+                    help="the frame of the Stokes vectors and the analyser: each FoV's own TE / TM basis, or the plate's "
+                         "axes (each FoV's table turned by its out-coupled azimuth + 90 degrees; paraxial)")
+    ap.add_argument("--polarisation-out", default="", metavar="FILE.npy", help="save the Stokes tables there (numpy int64)")
     ap.add_argument("--budget", action="store_true",
                     help="also report where every ray ended: per-ray fates, their per-tile census and the loss budget "
                          "per wavelength (the traces then run as plain single launches)")
@@ -899,7 +1012,9 @@ def main(argv=None):
               footprint=footprint, hits=None if a.hits is None else (True if a.hits < 0 else a.hits),
               paths=None if not a.paths else (a.paths.split(",") if "," in a.paths else a.paths),
               paths_capacity=a.paths_capacity, paths_footprint=paths_footprint, sensitivity=a.sensitivity,
-              what_if=what_if)
+              what_if=what_if, polarisation=a.polarisation, analyser=a.analyser, analyser_frame=a.analyser_frame)
+    if a.polarisation_out and "stokes" in res:   # (rank 0 has the tables)
+        np.save(a.polarisation_out, res["stokes"])
     if a.sensitivity_out and "sensitivity" in res:   # (rank 0 has the tables)
         np.save(a.sensitivity_out, res["sensitivity"])
     if a.footprint_out and "footprint" in res:   # (rank 0 has the map)

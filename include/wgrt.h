@@ -776,6 +776,32 @@ wgrt_status wgrt_visits_reweight_host(int32_t nx, int32_t ny, int32_t num_lmd, i
 int32_t wgrt_visit_channel_host(int32_t n_fc_slices, int32_t n_oc_slices, int32_t state, int32_t slice, int32_t branch);
 int32_t wgrt_visit_channel_count_host(int32_t n_fc_slices, int32_t n_oc_slices);
 
+/* Polarisation of the delivered light: Stokes window tables (new symbols within ABI 9, looked up by name; the rule is
+ * stated once in csrc/wgrt_stokes.h).
+ *
+ * wgrt_trace_stokes is wgrt_trace_windows that also keeps the polarisation state of every out-coupling the window table
+ * counts.  With a / b the complex TE / TM amplitudes of the out-coupled order's field (the reference's third
+ * E_field_cal of the R4 / R5 interaction), S0 = |a|^2 + |b|^2, s1 = (|a|^2 - |b|^2) / S0, s2 = 2 Re(a conj b) / S0,
+ * s3 = 2 Im(conj a b) / S0, a deposit is the three int32 quanta q_k = rint(s_k * 2^30) ((0, 0, 0) unless S0 is positive
+ * and finite).  The basis is the TE / TM basis of that FoV's out-coupled order, exactly as the reference's LUTs define
+ * it; nothing rotates it into a frame common to the FoVs.
+ *   stokes  DEVICE int64 [3, n_slabs, W], 8-B aligned, caller-owned, ADDED to: an out-coupling inside its FoV's eyebox
+ *           rectangle whose aliased offset lies in the buffer adds q_k to table k at exactly the entries of `table` it
+ *           adds 1 to (the slab's total and every window holding the bin).  Out-couplings beside the rectangle deposit
+ *           nothing.  Integer atomics: order-independent, the same bits on every run, shards add exactly; exact while
+ *           an entry has fewer than 2^33 deposits.
+ * `table` and `plan` are required; matrix_EB stays optional.  rng_states, matrix_EB, table, per_ray_bounces and every
+ * field of stats are the bytes of the launch without the tables.  A single launch: num_iter > 1 is
+ * WGRT_ERR_INVALID_ARGUMENT, the debug timeline WGRT_ERR_UNSUPPORTED, a chain takes no tables, the launch never learns
+ * the tile table, and no entry point combines it with another sink or with replicas.  stokes == NULL is exactly
+ * wgrt_trace_windows.
+ * wgrt_stokes_quanta_host is the rule itself over one field (no GPU needed): q HOST int32 [3]. */
+wgrt_status wgrt_trace_stokes(const wgrt_scene *scene, const wgrt_rays *rays, int64_t n_rays, int64_t gid_offset,
+                              uint32_t *rng_states, float *matrix_EB, wgrt_trace_stats *stats, uint32_t *per_ray_bounces,
+                              void *stream, const wgrt_launch_opts *opts, const wgrt_window_plan *plan, double *table,
+                              int64_t *stokes);
+void wgrt_stokes_quanta_host(double a_re, double a_im, double b_re, double b_im, int32_t *q);
+
 /* Host-only (no GPU needed; test hooks) through the same membership code (csrc/wgrt_window.h):
  * _validate is wgrt_window_plan_create's argument check alone; _table_host ADDS the n hits at flat grid
  * offsets offsets[n] (HOST int64; those outside [0, n_slabs * 9600) are dropped, as the grid's guard drops

@@ -1,0 +1,516 @@
+"""The Stokes window tables on the GPU (``wgrt_trace_stokes`` through ``torch.ops.wgrt.trace_stokes``) and the driver's
+``run(polarisation=True)``.
+
+Against the checker (``tests/oracle_stokes.c``: the CPU oracle with its hooks defined, the rule restated on its own) the
+bound is ``|got - want| <= N[entry]`` quanta per entry and component, ``N`` the window table's count of that entry: one
+``rint`` flip per deposit.  It is derived, not measured: a quantum (2^-30 = 9.3e-10) lies above the Jones-vector lane's
+certified state error (1e-10) and far above the rounding of either double-precision evaluation, so a
+deposit's normalised parameters differ by less than a quantum between the lanes and the oracle, and its quanta by at
+most one.  The walk -- ``rng_states``, per-ray bounces, ``stats``, the window table and ``matrix_EB`` -- is compared as
+bytes with the same launches without the tables, and with the checker's.  The crafted scenes compare with no tolerance.
+Every figure is printed before it is asserted (``profiles/stokes_parity.json`` records them)."""
+import ctypes
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+from gpu_ray_tracing_for_waveguide_based_ar_display_amd import _lib  # noqa: E402
+from gpu_ray_tracing_for_waveguide_based_ar_display_amd._lib import STAT  # noqa: E402
+from tests import _stokes as K  # noqa: E402
+from tests._fixtures import GoldenCase  # noqa: E402
+from tests.test_gpu_parity import _config  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+Q = 2 ** 30
+FIXTURES = ["c1_rgb", "h6_edge_rgb", "g5x4_rgb", "s1_532"]
+_CONFIGS = {"c2s": dict(nx=11, ny=11, lambdas=[1], R=64),                      # 7,744 rays: > replay_tail's 256 threads
+            "small": dict(nx=5, ny=4, lambdas=[0, 1, 2], R=100),
+            "small_deep": dict(nx=5, ny=4, lambdas=[0, 1, 2], R=100, profile="deep", seed=3),
+            # the AMP instantiations (tests/test_gpu_hits.py: about 30 out-couplings per launch)
+            "amp": dict(nx=5, ny=4, lambdas=[0, 1, 2], R=2500, profile="adversarial_polarizing", seed=2),
+            "rank1": dict(nx=5, ny=4, lambdas=[0, 1, 2], R=2500, profile="adversarial_rank1", seed=2)}
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("no HIP device")
+    return torch.device("cuda", 0)
+
+
+@pytest.fixture(autouse=True)
+def _switches():
+    yield
+    _lib.set_byte_locator(True)
+
+
+_cases, _checked = {}, {}
+
+
+def _case(name):
+    if name not in _cases:
+        _cases[name] = GoldenCase(name) if name in FIXTURES else _config(**_CONFIGS[name])
+    return _cases[name]
+
+
+def checked(name, launches=1, luts=None, key=None):
+    """The checker on case ``name``, once per key and shared, read-only: ``dict(want, D, rng, bounces, eb)``."""
+    key = (name, launches, key)
+    if key not in _checked:
+        from oracle import OracleScene
+        c = _case(name)
+        sc = OracleScene.from_geometry(c.geom, c.luts if luts is None else luts, wavelength=getattr(c, "wavelength", None))
+        eb = np.zeros(c.eb_shape(), np.float32)
+        stokes, count, rng, bounces = K.checker(sc, c.rays, c.fresh_rng(), launches, analog=eb)
+        want, D = K.tables(stokes, count)
+        for a in (want, D, rng, bounces, eb):
+            a.setflags(write=False)
+        _checked[key] = dict(want=want, D=D, rng=rng, bounces=bounces, eb=eb)
+    return _checked[key]
+
+
+def _trace(c, dev, launches=1, variant=0, stokes=True, st=None, rays=None, rng=None, scene=None, luts=None, grid=True,
+           canary=False, **kw):
+    """``launches`` single launches into the grid, the window table and (``stokes``) one set of Stokes tables:
+    ``SimpleNamespace(S, rng, eb, table, stats, per)`` on the host.  ``stokes=False``: the same calls without the tables.
+    ``canary``: the tables are a view into a larger buffer whose other words must stay untouched (``out.guard``)."""
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import (Scene, StokesTable, WindowPlan, new_stats,
+                                                                           rays_to_device, trace_fullcolor, trace_single)
+    wl = getattr(c, "wavelength", None)
+    own = scene is None
+    if own:
+        scene = Scene.from_geometry(c.geom, c.luts if luts is None else luts, wavelength=wl)
+    plan = WindowPlan()
+    trace = trace_single if wl is not None else trace_fullcolor
+    buf = None
+    if st is None and stokes:
+        st = StokesTable(scene, plan, dev)
+        if canary:
+            n = st.tables.numel()
+            buf = torch.full((n + 512,), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64, device=dev)
+            buf[256:256 + n].zero_()
+            st.tables = buf[256:256 + n].view(st.tables.shape)
+    table = plan.new_table(scene)
+    eb = torch.zeros(scene.eb_shape(), dtype=torch.float32, device=dev) if grid else None
+    rays = rays_to_device(c.rays, dev) if rays is None else rays
+    rng = torch.from_numpy(c.fresh_rng().view(np.int32)).to(dev) if rng is None else rng
+    stats = new_stats(dev)
+    per = torch.zeros(rng.numel(), dtype=torch.int32, device=dev)
+    for _ in range(launches):
+        trace(scene, rays, rng, eb, stats=stats, per_ray_bounces=per, variant=variant, windows=(plan, table),
+              stokes=st if stokes else None, **kw)
+    torch.cuda.synchronize()
+    out = SimpleNamespace(S=st.host() if stokes else None, rng=rng.cpu().numpy().view(np.uint32).copy(),
+                          eb=eb.cpu().numpy() if grid else None, table=table.cpu().numpy(),
+                          stats=stats.cpu().numpy().copy(), per=per.cpu().numpy().view(np.uint32).copy())
+    if buf is not None:
+        n = st.tables.numel()
+        out.guard = torch.cat([buf[:256], buf[256 + n:]]).cpu().numpy()
+    plan.close()
+    if own:
+        scene.close()
+    return out
+
+
+def _same_walk(a, b):
+    np.testing.assert_array_equal(a.rng, b.rng)
+    np.testing.assert_array_equal(a.per, b.per)
+    np.testing.assert_array_equal(a.stats, b.stats)
+    assert a.table.tobytes() == b.table.tobytes()
+    assert (a.eb is None and b.eb is None) or a.eb.tobytes() == b.eb.tobytes()
+
+
+def _within(got, chk, label):
+    """The bound, against the launch's own window table ``N`` (which must be the checker's ``D``): prints, then asserts."""
+    np.testing.assert_array_equal(got.table, chk["D"])
+    assert got.S.dtype == np.int64 and got.S.shape == chk["want"].shape
+    ok, differ, worst = K.within_bound(got.S, chk["want"], got.table)
+    print(f"stokes parity {label}: {int((got.table > 0).sum())} entries, {int(got.table[:, 0].sum())} deposits, "
+          f"{differ} entries differ, by at most {worst} quanta")
+    assert ok
+    assert (np.abs(got.S) <= got.table[None] * Q).all() and got.table[:, 0].sum() > 0
+    return differ, worst
+
+
+# 1. every variant, four launches into one set of tables --------------------------------------------------------------
+
+@pytest.mark.parametrize("variant", [1, 7, 9])
+@pytest.mark.parametrize("name", ["c1_rgb", "h6_edge_rgb", "g5x4_rgb", "small", "c2s"])
+def test_tables_and_walk(dev, name, variant):
+    c = _case(name)
+    chk = checked(name, 4)
+    got = _trace(c, dev, launches=4, variant=variant)
+    _within(got, chk, f"{name} v{variant}")
+    np.testing.assert_array_equal(got.rng, chk["rng"])
+    np.testing.assert_array_equal(got.per, chk["bounces"])
+    assert got.eb.tobytes() == chk["eb"].tobytes()
+    _same_walk(got, _trace(c, dev, launches=4, variant=variant, stokes=False))
+
+
+def test_without_a_grid_and_behind_a_canary(dev):
+    """``matrix_EB`` stays optional; nothing beside the tables is written."""
+    c = _case("small")
+    chk = checked("small")
+    for variant in (1, 7):
+        got = _trace(c, dev, variant=variant, grid=False, canary=True)
+        _within(got, chk, f"small v{variant} no grid")
+        assert (got.guard == 0x5A5A5A5A5A5A5A5A).all()
+        _same_walk(got, _trace(c, dev, variant=variant, grid=False, stokes=False))
+
+
+# 2. two crafted scenes, with no tolerance ---------------------------------------------------------------------------
+
+def crafted_luts(c, kind: str) -> dict:
+    """The out-coupling matrices of R4 / R5 (``r4[i].b3`` / ``r5[i].b3``: Ete' = p Ete + r Etm, Etm' = q Ete + s Etm, the
+    quadruple being (p, q, r, s)) with their TM row (q, s) zeroed (``"te"``: every out-coupled field is all TE) or set to
+    i times their TE row (``"circular"``: b = i a for every state)."""
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.luts import channel_quad
+    out = {k: np.array(v, copy=True) for k, v in c.luts.items()}
+    for i in range(c.geom.num_oc_slices):
+        for r in (4, 5):
+            lut, sl, (p, q, rr, s) = channel_quad(f"r{r}[{i}].b3")
+            t = out[lut][sl]
+            if kind == "te":
+                t[..., [q, s]] = 0.0
+            else:
+                t[..., q], t[..., s] = 1j * t[..., p], 1j * t[..., rr]
+    return out
+
+
+@pytest.mark.parametrize("variant", [1, 7])
+@pytest.mark.parametrize("kind", ["te", "circular"])
+def test_crafted_scenes(dev, kind, variant):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd import AR_system_evaluation_functions as E
+    c = _case("small")
+    luts = crafted_luts(c, kind)
+    got = _trace(c, dev, launches=2, variant=variant, luts=luts)
+    N = got.table
+    print(f"crafted {kind} v{variant}: {int(N[:, 0].sum())} deposits")
+    assert N[:, 0].sum() > 50
+    full = (N * Q).astype(np.int64)
+    zero = np.zeros_like(full)
+    if kind == "te":
+        np.testing.assert_array_equal(got.S, np.stack([full, zero, zero]))
+        # through the analyser: everything passes at 0 degrees, nothing at 90 -- every efficiency is 0
+        np.testing.assert_array_equal(E.analyser_table(N, got.S, 0.0), N)
+        crossed = E.analyser_table(N, got.S, np.pi / 2)
+        np.testing.assert_array_equal(crossed, np.zeros_like(N))
+        A = crossed[:, 0].reshape(c.eb_shape()[:-2]) / c.N / 2
+        assert all(float(np.sum(A[k] * 3)) == 0.0 for k in range(A.shape[0]))
+        *fig, _ = E.evaluation_from_window_sums(E.analyser_table(N, got.S, 0.0), c.eb_shape(), c.R * 2, image=None)
+        *ref, _ = E.evaluation_from_window_sums(N, c.eb_shape(), c.R * 2, image=None)
+        assert [float(v).hex() for v in fig] == [float(v).hex() for v in ref]
+    else:
+        np.testing.assert_array_equal(got.S, np.stack([zero, zero, full]))
+    # and the checker agrees on the same scene, within the bound
+    _within(got, checked("small", 2, luts=luts, key=kind), f"crafted {kind} v{variant}")
+
+
+# 3. the cases the other sinks pin ----------------------------------------------------------------------------------
+
+def test_refills(dev):
+    """13-ray work items on two workgroups."""
+    c = _case("small_deep")
+    chk = checked("small_deep")
+    got = _trace(c, dev, variant=7, workgroups=2, debug=dict(chunk_rays=13))
+    _within(got, chk, "small_deep 13-ray items")
+    np.testing.assert_array_equal(got.rng, chk["rng"])
+    _same_walk(got, _trace(c, dev, variant=7, workgroups=2, debug=dict(chunk_rays=13), stokes=False))
+
+
+@pytest.mark.parametrize("debug, every", [(dict(cert_tol=1e-2), False), (dict(cert_tol=1e3, cert_tol32=1e3), True)])
+def test_abandoned_rays_deposit_once(dev, debug, every):
+    """A raised certification bound abandons rays in mid-walk (every ray at its first draw with ``cert_tol=1e3``): an
+    abandoned ray has pushed nothing, and its replay on the exact lane deposits.  The window table stays exact and the
+    Stokes tables within the bound."""
+    c = _case("c2s")
+    chk = checked("c2s")
+    got = _trace(c, dev, variant=7, debug=debug)
+    traced, replayed = c.N - int(got.stats[STAT.bad_rays]), int(got.stats[STAT.replayed])
+    print(f"replayed {replayed} of {traced}")
+    if every:
+        assert replayed == traced > 256
+    else:
+        assert 0 < replayed < traced
+    _within(got, chk, f"c2s cert_tol={debug['cert_tol']:g}")
+    np.testing.assert_array_equal(got.per, chk["bounces"])
+    np.testing.assert_array_equal(got.rng, chk["rng"])
+    _same_walk(got, _trace(c, dev, variant=7, debug=debug, stokes=False))
+
+
+@pytest.mark.parametrize("variant", [7, 9])
+def test_byte_and_word_locator(dev, variant):
+    c = _case("small")
+    chk = checked("small")
+    tables = []
+    for byte in (True, False):
+        _lib.set_byte_locator(byte)
+        got = _trace(c, dev, variant=variant)
+        _within(got, chk, f"small v{variant} byte={byte}")
+        np.testing.assert_array_equal(got.rng, chk["rng"])
+        tables.append(got.S)
+    _lib.set_byte_locator(True)
+    np.testing.assert_array_equal(tables[0], tables[1])   # the same lane, the same arithmetic
+
+
+def test_single_wavelength(dev):
+    c = _case("s1_532")
+    assert getattr(c, "wavelength", None) is not None
+    chk = checked("s1_532", 4)
+    for variant in (1, 7, 9):
+        got = _trace(c, dev, launches=4, variant=variant)
+        _within(got, chk, f"s1_532 v{variant}")
+        np.testing.assert_array_equal(got.rng, chk["rng"])
+
+
+def test_amp_profile(dev):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import Scene
+    c = _case("amp")
+    sc = Scene.from_geometry(c.geom, c.luts)
+    assert sc.info()["nonunitary_blocks"] > 0
+    sc.close()
+    chk = checked("amp", 4)
+    for variant in (7, 9):
+        got = _trace(c, dev, launches=4, variant=variant)
+        _within(got, chk, f"adversarial_polarizing v{variant}")
+        np.testing.assert_array_equal(got.rng, chk["rng"])
+        _same_walk(got, _trace(c, dev, launches=4, variant=variant, stokes=False))
+
+
+def test_rank1_profile(dev):
+    """``adversarial_rank1``: nearly singular branch matrices amplify the lanes' state discrepancy, so only the walk's
+    byte-identity and ``|S_k| <= N 2^30`` are asserted; the differences from the checker are printed and recorded."""
+    c = _case("rank1")
+    chk = checked("rank1", 2)
+    for variant in (7, 9):
+        got = _trace(c, dev, launches=2, variant=variant)
+        _same_walk(got, _trace(c, dev, launches=2, variant=variant, stokes=False))
+        np.testing.assert_array_equal(got.table, chk["D"])
+        np.testing.assert_array_equal(got.rng, chk["rng"])
+        assert (np.abs(got.S) <= got.table[None] * Q).all()
+        ok, differ, worst = K.within_bound(got.S, chk["want"], got.table)
+        print(f"stokes parity adversarial_rank1 v{variant}: {int((got.table > 0).sum())} entries, "
+              f"{int(got.table[:, 0].sum())} deposits, {differ} entries differ, by at most {worst} quanta, within N: {ok}")
+
+
+@pytest.mark.parametrize("variant", [1, 7])
+def test_a_batch_split_at_ray_37(dev, variant):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import Scene, StokesTable, WindowPlan, rays_to_device
+    c = _case("c1_rgb")
+    chk = checked("c1_rgb")
+    scene = Scene.from_geometry(c.geom, c.luts)
+    plan = WindowPlan()
+    st = StokesTable(scene, plan, dev)
+    full = rays_to_device(c.rays, dev)
+    rng_all = torch.from_numpy(c.fresh_rng().view(np.int32)).to(dev)
+    got_rng, N = [], 0
+    for lo, hi in ((0, 37), (37, c.N)):
+        rays = {k: v[lo:hi].contiguous() for k, v in full.items()}
+        r = _trace(c, dev, variant=variant, rays=rays, rng=rng_all[lo:hi].contiguous(), st=st, scene=scene, gid_offset=lo)
+        got_rng.append(r.rng)
+        N = N + r.table
+    whole = SimpleNamespace(S=st.host(), table=N)
+    plan.close()
+    scene.close()
+    _within(whole, chk, f"c1_rgb split v{variant}")
+    np.testing.assert_array_equal(np.concatenate(got_rng), chk["rng"])
+
+
+def test_two_gid_blocks_shards_add_up_exactly(dev):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.distributed import make_shard
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import init_rays
+    c = _case("c1_rgb")
+    chk = checked("c1_rgb")
+    one = _trace(c, dev, variant=7)
+    parts = []
+    for r in range(2):
+        shard = make_shard(c.nx, c.ny, len(c.lambdas), c.R, 2, r)
+        rays, rng = init_rays(c.f["points"], c.nx, c.ny, c.lambdas, c.R, block_list=shard.blocks, device=dev)
+        gb = torch.from_numpy(shard.gid.block_gid).to(dev)
+        parts.append(_trace(c, dev, variant=7, rays=rays, rng=rng, n_rays=rng.numel(), gid_blocks=gb, gid_block_rays=c.R))
+        assert np.abs(parts[-1].S).sum() > 0
+    np.testing.assert_array_equal(parts[0].S + parts[1].S, one.S)             # integer sums: exactly
+    np.testing.assert_array_equal(parts[0].table + parts[1].table, one.table)
+    _within(one, chk, "c1_rgb unsplit")
+
+
+# 4. argument errors -------------------------------------------------------------------------------------------------
+
+def test_argument_errors(dev):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.engine import (HitList, Scene, StokesTable, TraceChain,
+                                                                           WindowPlan, _debug_opts, rays_to_device,
+                                                                           trace_fullcolor)
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd._lib import load, ops
+    c = _case("c1_rgb")
+    scene, plan = Scene.from_geometry(c.geom, c.luts), WindowPlan()
+    rays = rays_to_device(c.rays, dev)
+    rng = torch.from_numpy(c.fresh_rng().view(np.int32)).to(dev)
+    before = rng.clone()
+    st = StokesTable(scene, plan, dev)
+    grid = torch.zeros(c.eb_shape(), dtype=torch.float32, device=dev)
+    table = plan.new_table(scene)
+    go = lambda **kw: trace_fullcolor(scene, rays, rng, grid, variant=7, windows=(plan, table), stokes=st, **kw)
+    with pytest.raises(ValueError, match="num_iter"):
+        go(num_iter=2)
+    with pytest.raises(ValueError, match="fate"):
+        go(fate=torch.zeros(c.N, dtype=torch.uint8, device=dev))
+    with pytest.raises(ValueError, match="hits"):
+        go(hits=(HitList(8, dev), 0))
+    with pytest.raises(ValueError, match="replicas"):
+        trace_fullcolor(scene, rays, rng, grid, windows=(plan, plan.new_table(scene, replicas=4)), replicas=4, stokes=st)
+    with pytest.raises(ValueError, match="needs windows"):
+        trace_fullcolor(scene, rays, rng, grid, variant=7, stokes=st)
+    with pytest.raises(ValueError, match="chain"):
+        TraceChain(scene, rays, rng, grid, windows=(plan, table), stokes=st)
+    with pytest.raises(TypeError):
+        go(stokes=st.tables)
+
+    # the operator and the C entry point themselves
+    def op(stokes=st.tables, num_iter=1, debug=0, variant=7, plan_h=plan.handle.value, tab=table):
+        return ops().trace_stokes(scene.handle.value, rays["x"], rays["y"], rays["m"], rays["n"], rays["lmd_num"],
+                                  rays["te"], rays["tm"], rays["delta_phase"], rng, grid, None, None, c.N, 0, 0, 0, variant,
+                                  0, None, num_iter, None, 0, debug, 0.0, plan_h, tab, stokes)
+    for v in (1, 7):
+        assert op(num_iter=2, variant=v) == 1                                      # WGRT_ERR_INVALID_ARGUMENT
+    tl = torch.zeros(8 * 64, dtype=torch.int64, device=dev)
+    dbg = _debug_opts(dict(timeline=tl))
+    assert op(debug=ctypes.addressof(dbg)) == 4                                    # WGRT_ERR_UNSUPPORTED
+    with pytest.raises(RuntimeError, match="needs the table"):
+        op(tab=None)
+    with pytest.raises(RuntimeError, match="plan"):
+        op(plan_h=0)
+    with pytest.raises(RuntimeError, match="int64"):
+        op(stokes=st.tables.to(torch.int32))
+    with pytest.raises(RuntimeError, match="int64"):
+        op(stokes=st.tables[:2])
+    with pytest.raises(RuntimeError, match="must be on"):
+        op(stokes=st.tables.cpu())
+    L = load()
+    cols = _lib.Rays(**{k: ctypes.c_void_p(rays[k].data_ptr()) for k in ("x", "y", "m", "n", "lmd_num", "te", "tm",
+                                                                          "delta_phase")})
+    opts = _lib.LaunchOpts()
+    opts.variant = 7
+    stats = torch.zeros(_lib.STATS_LEN, dtype=torch.int64, device=dev)
+
+    def capi(stokes=st.tables.data_ptr(), plan_h=plan.handle, tab=table.data_ptr()):
+        return L.wgrt_trace_stokes(scene.handle, ctypes.byref(cols), c.N, 0, rng.data_ptr(), grid.data_ptr(),
+                                   stats.data_ptr(), None, None, ctypes.byref(opts), plan_h, tab, stokes)
+    assert capi(stokes=st.tables.data_ptr() + 4) == 1        # a misaligned payload
+    assert capi(tab=None) == 1                               # a NULL table with a payload
+    assert capi(plan_h=None) == 1                            # no plan
+    torch.cuda.synchronize()
+    assert torch.equal(rng, before) and not grid.any() and not tl.any() and not st.tables.any() and not table.any()
+    assert not stats.any()                                   # nothing was launched
+
+    # stokes == NULL: the windows launch, bit for bit
+    assert capi(stokes=None) == 0
+    rng2, grid2, table2, st2 = before.clone(), torch.zeros_like(grid), torch.zeros_like(table), torch.zeros_like(stats)
+    assert L.wgrt_trace_windows(scene.handle, ctypes.byref(cols), c.N, 0, rng2.data_ptr(), grid2.data_ptr(),
+                                st2.data_ptr(), None, None, ctypes.byref(opts), plan.handle, table2.data_ptr()) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(rng, rng2) and torch.equal(grid, grid2) and torch.equal(table, table2) and torch.equal(stats, st2)
+    assert grid.sum() > 0 and not st.tables.any()
+    plan.close()
+    scene.close()
+
+
+# 5. the driver ------------------------------------------------------------------------------------------------------
+# the small job of tests/test_gpu_window_sink.py ("deep" LUT profile)
+
+NX, NY, R, STEPS = 5, 4, 256, 2
+_runs = {}
+
+
+def _run(polarisation, **kw):
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.gpu_ray_tracing_pro_fullColor import run
+    from tests import _dist
+    pts = _dist.small_job(NX, NY, R, 3, 6, "deep")[2]
+    return run(NX, NY, R, STEPS, lut_seed=3, lut_profile="deep", points=pts, verbose=False, eyebox="windows",
+               evaluate_on="device", polarisation=polarisation, **kw)
+
+
+def _run_once(polarisation, **kw):
+    key = (polarisation, tuple(sorted(kw.items())))
+    if key not in _runs:
+        _runs[key] = _run(polarisation, **kw)
+    return _runs[key]
+
+
+def _unchanged(got, plain):
+    for k in plain:   # everything returned before, bit for bit (the timings aside)
+        if k in ("gpu_seconds", "post_seconds"):
+            continue
+        a, b = got[k], plain[k]
+        if isinstance(a, np.ndarray):
+            assert a.tobytes() == b.tobytes(), k
+        else:
+            assert a == b or (isinstance(a, float) and float(a).hex() == float(b).hex()), k
+
+
+def test_driver_polarisation(dev):
+    from oracle import OracleScene
+    from tests import _dist
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd import AR_system_evaluation_functions as E
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.rays import build_rays, rng_seeds
+    got, plain = _run_once(True, analyser=30.0), _run_once(False)
+    assert set(got) - set(plain) == {"stokes", "polarisation", "analysed"}
+    _unchanged(got, plain)
+    # the checker on the driver's batch
+    geom, luts, pts = _dist.small_job(NX, NY, R, 3, 6, "deep")
+    rays = build_rays(pts, NX, NY, (0, 1, 2), R)
+    stokes, count, rng, _ = K.checker(OracleScene.from_geometry(geom, luts), rays, rng_seeds(rays["x"].shape[0]), STEPS)
+    want, D = K.tables(stokes, count)
+    S = got["stokes"]
+    ok, differ, worst = K.within_bound(S, want, D)
+    print(f"stokes parity driver: {int(D[:, 0].sum())} deposits, {differ} entries differ, by at most {worst} quanta")
+    assert ok and D[:, 0].sum() > 0 and S.dtype == np.int64
+    np.testing.assert_array_equal(got["rng_states"], rng)
+    p = got["polarisation"]
+    assert p["frame"] == "fov" and p["mean"].shape == (3, 3) and p["dop"].shape == (3,) and p["dop_fov"].shape == (3, NY, NX)
+    tot = E.polarisation_from_stokes(D[:, 0].reshape(3, -1).sum(1)[:, None], S[:, :, 0].reshape(3, 3, -1).sum(2)[:, :, None])
+    np.testing.assert_array_equal(p["mean"], tot["mean"][:, :, 0].T)
+    assert ((p["dop"] > 0) & (p["dop"] <= 1)).all()
+    a = got["analysed"]
+    assert a["theta_deg"] == 30.0 and a["frame"] == "fov"
+    np.testing.assert_array_equal(a["table"], E.analyser_table(D, S, np.deg2rad(30.0)))
+    assert all(0 <= a["efficiency"][k] <= plain["efficiency"][k] for k in plain["efficiency"])
+    assert 0 < sum(a["efficiency"].values()) < sum(plain["efficiency"].values())
+    assert all(np.isfinite(a[k]) for k in ("delta_e", "U_fov", "U_EB"))
+    # the lab frame: the tables returned are the same; the analysed table is the rotated tables'
+    lab = _run(True, analyser=30.0, analyser_frame="lab")
+    np.testing.assert_array_equal(lab["stokes"], S)
+    _unchanged(lab, plain)
+    psi = np.broadcast_to(np.asarray(geom.angles["phi_in_ic"])[0].T[None] + np.pi / 2, (3, NY, NX)).reshape(-1)
+    np.testing.assert_allclose(lab["analysed"]["table"], E.analyser_table(D, E.stokes_rotate(S, psi), np.deg2rad(30.0)),
+                               rtol=1e-12, atol=1e-9)
+    np.testing.assert_allclose(lab["polarisation"]["dop_fov"], p["dop_fov"], rtol=1e-12)   # a rotation keeps the DoP
+    # without an analyser
+    only = _run(True)
+    assert set(only) - set(plain) == {"stokes", "polarisation"}
+    np.testing.assert_array_equal(only["stokes"], S)
+
+
+def _driver_worker(rank, world, outdir):
+    torch.cuda.set_device(torch.device("cuda", 0))
+    res = _run(True, analyser=30.0)
+    np.save(f"{outdir}/rng{rank}.npy", res["rng_states"])
+    if rank != 0:
+        assert "stokes" not in res
+        return
+    np.save(f"{outdir}/stokes.npy", res["stokes"])
+    np.save(f"{outdir}/analysed.npy", res["analysed"]["table"])
+    np.save(f"{outdir}/A.npy", res["A"])
+
+
+def test_driver_polarisation_in_two_ranks(dev, tmp_path):
+    """Two ranks on the one GPU over gloo: integer tables, so the ranks' sum is the single-process table exactly."""
+    from tests import _dist
+    _dist.spawn(_driver_worker, 2, str(tmp_path))
+    one = _run_once(True, analyser=30.0)
+    np.testing.assert_array_equal(np.load(tmp_path / "stokes.npy"), one["stokes"])
+    np.testing.assert_array_equal(np.load(tmp_path / "analysed.npy"), one["analysed"]["table"])
+    assert np.load(tmp_path / "A.npy").tobytes() == one["A"].tobytes()
