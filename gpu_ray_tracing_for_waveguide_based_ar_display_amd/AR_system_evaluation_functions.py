@@ -519,6 +519,28 @@ def evaluation_error_bars(reps_table, shape, divisor, evaluate_on: str = "host",
                 U_fov_se=float(se[1]), U_EB_se=float(se[2]), jackknife=loo, image=img, table=rows[0])
 
 
+def evaluation_ensemble(tables, shape, divisor, evaluate_on: str = "host", ms: int = 30, step_y: int = 8,
+                        step_x: int = 12) -> dict:
+    """The three figures of every design of an ensemble: ``tables`` ``[K, n_slabs, W]`` (``VisitTable.reweight_many``'s;
+    a device tensor or a numpy array), ``shape`` and ``divisor`` as for the one table.  One
+    ``evaluation_from_window_sums(image=None)`` per design -- ``evaluate_on="device"`` where the tables live, ``"host"``
+    on their host copy -- so row k is, bit for bit, what that call gives for ``tables[k]`` there.  Returns ``delta_e``,
+    ``U_fov`` and ``U_EB``, float64 ``[K]`` each."""
+    if evaluate_on not in ("host", "device"):
+        raise ValueError(f"evaluate_on must be 'host' or 'device', got {evaluate_on!r}")
+    if len(tables.shape) != 3 or tables.shape[0] < 1:
+        raise ValueError(f"tables of shape {tuple(tables.shape)} are not [K >= 1, n_slabs, W]")
+    K = int(tables.shape[0])
+    if evaluate_on == "device":
+        if not getattr(tables, "is_cuda", False):
+            raise ValueError("evaluate_on='device' needs the tables as a device tensor")
+    elif hasattr(tables, "detach"):
+        tables = tables.detach().cpu().numpy()
+    rows = np.array([[float(v) for v in evaluation_from_window_sums(tables[k], shape, divisor, ms, step_y, step_x,
+                                                                    image=None)[:3]] for k in range(K)], dtype=np.float64)
+    return dict(delta_e=rows[:, 0].copy(), U_fov=rows[:, 1].copy(), U_EB=rows[:, 2].copy())
+
+
 def efficiency_error_bars(reps_table, shape, num_rays, num_iter) -> dict:
     """Standard errors of the efficiencies from the replica tables ``[B, n_slabs, W]``: replica ``b`` alone estimates
     ``A_b = B * table[b, :, 0] / num_rays / num_iter`` (it holds a ``B``-th of the rays), so the mean of the ``A_b`` is

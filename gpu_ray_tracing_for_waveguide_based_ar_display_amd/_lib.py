@@ -37,13 +37,15 @@ EXPORTED = ("wgrt_scene_create", "wgrt_scene_create_ex", "wgrt_scene_destroy", "
             "wgrt_paths_footprint", "wgrt_paths_footprint_host", "wgrt_trace_visits", "wgrt_visit_channels",
             "wgrt_visits_sensitivity", "wgrt_visits_reweight", "wgrt_visits_sensitivity_host",
             "wgrt_visits_reweight_host", "wgrt_visit_channel_host", "wgrt_visit_channel_count_host",
-            "wgrt_trace_stokes", "wgrt_stokes_quanta_host")
+            "wgrt_trace_stokes", "wgrt_stokes_quanta_host", "wgrt_visits_reweight_many",
+            "wgrt_visits_reweight_many_host", "wgrt_visit_wavelengths")
 EXPORTED_DEBUG = ("wgrt_debug_shadow", "wgrt_debug_scene_copy", "wgrt_debug_set_auto_order",
                   "wgrt_debug_get_auto_order", "wgrt_debug_get_tile_tail", "wgrt_debug_order_host",
                   "wgrt_debug_chain_plan", "wgrt_debug_chain_set_serial", "wgrt_debug_set_byte_locator",
                   "wgrt_debug_set_palette_cap", "wgrt_debug_scene_palette", "wgrt_debug_expected_replays",
                   "wgrt_debug_chain_report", "wgrt_debug_set_fused_run", "wgrt_debug_fused_run",
-                  "wgrt_debug_fused_items_host", "wgrt_debug_set_footprint_aggregate")
+                  "wgrt_debug_fused_items_host", "wgrt_debug_set_footprint_aggregate",
+                  "wgrt_debug_set_reweight_layout")
 
 
 class WgrtError(RuntimeError):
@@ -387,6 +389,17 @@ def load():
         L.wgrt_visit_channel_host.argtypes = [i32, i32, i32, i32, i32]
         L.wgrt_visit_channel_count_host.restype = i32
         L.wgrt_visit_channel_count_host.argtypes = [i32, i32]
+    if hasattr(L, "wgrt_visits_reweight_many"):   # design ensembles: new symbols within ABI 9, by name
+        i32 = ctypes.c_int32
+        L.wgrt_visits_reweight_many.restype = st
+        L.wgrt_visits_reweight_many.argtypes = [_vp, _vp, _vp, _vp, ctypes.c_int64, _vp, i32, _vp, _vp, _vp]
+        L.wgrt_visits_reweight_many_host.restype = st
+        L.wgrt_visits_reweight_many_host.argtypes = [i32, i32, i32, i32, _vp, _vp, i32, i32, i32, _vp, _vp, ctypes.c_int64,
+                                                     _vp, i32, _vp, _vp]
+        L.wgrt_visit_wavelengths.restype = i32
+        L.wgrt_visit_wavelengths.argtypes = [_vp]
+        L.wgrt_debug_set_reweight_layout.restype = st
+        L.wgrt_debug_set_reweight_layout.argtypes = [ctypes.c_int]
     if hasattr(L, "wgrt_trace_stokes"):   # the Stokes window tables: new symbols within ABI 9, by name
         L.wgrt_trace_stokes.restype = st
         L.wgrt_trace_stokes.argtypes = L.wgrt_trace_opts.argtypes + [_vp, _vp, _vp]
@@ -630,6 +643,13 @@ def locator_classify_host(geom, luts, xy: np.ndarray, cell_mm: float = 0.125) ->
 def set_byte_locator(on: bool) -> None:
     """``wgrt_debug_set_byte_locator``: the Jones-vector lane's byte locator on / off, process-wide (A/B, tests)."""
     check(load().wgrt_debug_set_byte_locator(1 if on else 0), "wgrt_debug_set_byte_locator")
+
+
+def set_reweight_layout(interleaved: bool) -> None:
+    """``wgrt_debug_set_reweight_layout``: the form of ``wgrt_visits_reweight_many``'s deposits, process-wide (A/B, tests):
+    through a scratch interleaved over a chunk's designs (the default) or straight into the tables; both give the same
+    bits."""
+    check(load().wgrt_debug_set_reweight_layout(1 if interleaved else 0), "wgrt_debug_set_reweight_layout")
 
 
 def set_footprint_aggregate(on: bool) -> None:

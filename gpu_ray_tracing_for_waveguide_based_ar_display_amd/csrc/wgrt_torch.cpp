@@ -491,6 +491,46 @@ int64_t visits_reduce(int64_t scene, int64_t plan, const Tensor &counts, const T
                                             hip_stream);
 }
 
+// visits_reweight_many: the first n_rows rows re-weighted for K designs at once (wgrt_visits_reweight_many): lnscale
+// float64 [K, C], out float64 [K, n_slabs, W], wsums int64 [K, 2, num_lmd] or None.  Both outputs are added to.
+int64_t visits_reweight_many(int64_t scene, int64_t plan, const Tensor &counts, const Tensor &ends, int64_t n_rows,
+                             const Tensor &lnscale, Tensor out, std::optional<Tensor> wsums, int64_t stream) {
+    const wgrt_scene *s = reinterpret_cast<const wgrt_scene *>(static_cast<uintptr_t>(scene));
+    const wgrt_window_plan *wp = reinterpret_cast<const wgrt_window_plan *>(static_cast<uintptr_t>(plan));
+    TORCH_CHECK(s != nullptr && wp != nullptr, "wgrt.visits_reweight_many: NULL scene / plan");
+    wgrt_scene_info info{};
+    const wgrt_status st = wgrt_scene_get_info(s, &info);
+    if (st != WGRT_OK) return st;
+    const c10::Device dev(c10::DeviceType::CUDA, static_cast<c10::DeviceIndex>(info.device));
+    const int64_t C = VISITS_SYM(wgrt_visit_channels)(s), W = WINDOW_SYM(wgrt_window_plan_width)(wp);
+    const int64_t nl = WGRT_SYM(wgrt_visit_wavelengths, "visits_reweight_many", "the design ensembles")(s);
+    TORCH_CHECK(W > 0, "wgrt.visits_reweight_many: a bad window plan");
+    TORCH_CHECK(counts.device() == dev && ends.device() == dev && out.device() == dev && lnscale.device() == dev &&
+                    (!wsums || wsums->device() == dev),
+                "wgrt.visits_reweight_many: counts, ends, lnscale, out and wsums must be on the scene's device");
+    TORCH_CHECK(n_rows >= 0 && counts.scalar_type() == at::kInt && counts.is_contiguous() && counts.numel() >= n_rows * C,
+                "wgrt.visits_reweight_many: counts must be contiguous int32 with >= n_rows * ", C, " entries");
+    TORCH_CHECK(ends.scalar_type() == at::kByte && ends.is_contiguous() &&
+                    ends.numel() >= n_rows * (int64_t)sizeof(wgrt_visit_end),
+                "wgrt.visits_reweight_many: ends must be contiguous uint8 with >= n_rows * 32 bytes");
+    TORCH_CHECK(lnscale.scalar_type() == at::kDouble && lnscale.is_contiguous() && lnscale.dim() == 2 &&
+                    lnscale.size(0) >= 1 && lnscale.size(0) <= INT32_MAX && lnscale.size(1) == C,
+                "wgrt.visits_reweight_many: lnscale must be contiguous float64 [K >= 1, ", C, "]");
+    const int64_t K = lnscale.size(0);
+    TORCH_CHECK(out.scalar_type() == at::kDouble && out.is_contiguous() && out.dim() == 3 && out.size(0) == K &&
+                    out.size(1) == (int64_t)info.tiles && out.size(2) == W,
+                "wgrt.visits_reweight_many: out must be contiguous float64 [", K, ", ", info.tiles, ", ", W, "]");
+    TORCH_CHECK(!wsums || (wsums->scalar_type() == at::kLong && wsums->is_contiguous() && wsums->dim() == 3 &&
+                           wsums->size(0) == K && wsums->size(1) == 2 && wsums->size(2) == nl),
+                "wgrt.visits_reweight_many: wsums must be contiguous int64 [", K, ", 2, ", nl, "]");
+    const c10::DeviceGuard guard(dev);
+    return WGRT_SYM(wgrt_visits_reweight_many, "visits_reweight_many", "the design ensembles")(
+        s, wp, static_cast<const uint32_t *>(counts.const_data_ptr()),
+        static_cast<const wgrt_visit_end *>(ends.const_data_ptr()), n_rows, lnscale.const_data_ptr<double>(), (int32_t)K,
+        out.data_ptr<double>(), wsums ? wsums->data_ptr<int64_t>() : nullptr,
+        reinterpret_cast<void *>(static_cast<uintptr_t>(stream)));
+}
+
 // paths_footprint: the first n records of a path list added into a footprint map on the list's device
 // (wgrt_paths_footprint).
 int64_t paths_footprint(const Tensor &paths, int64_t n, int64_t num_lmd, double fp_x0, double fp_y0, double fp_cell_x,
@@ -605,6 +645,10 @@ TORCH_LIBRARY(wgrt, m) {
     m.def("visits_reduce(int scene, int plan, Tensor counts, Tensor ends, int n_rows, Tensor? lnscale, Tensor(a!) out, "
           "int stream) -> int",
           &visits_reduce);
+    // the same rows re-weighted for K designs at once, with the weights' sums in quanta of 2^-32
+    m.def("visits_reweight_many(int scene, int plan, Tensor counts, Tensor ends, int n_rows, Tensor lnscale, "
+          "Tensor(a!) out, Tensor(b!)? wsums, int stream) -> int",
+          &visits_reweight_many);
     m.def("chain_step(int chain) -> int", &chain_step);
     m.def("chain_end(int chain) -> int", &chain_end);
 }

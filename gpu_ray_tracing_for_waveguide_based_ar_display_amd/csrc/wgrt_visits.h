@@ -105,6 +105,47 @@ WGRT_HD double visit_log_weight(const uint32_t *counts, const double *lnscale, i
     return a;
 }
 
+// Design ensembles (wgrt_visits_reweight_many): K designs from one pass over the rows.  Design k has the log-scales
+// lnscale[k * C + c]; a row deposits for it exactly what wgrt_visits_reweight deposits with lnscale + k * C,
+//     q = expected_quantize(exp(visit_log_weight(counts_row, lnscale + k * C, C))),
+// through window_visit at visit_end_offset's offset into out + k * n_slabs * W, and a row whose offset is negative
+// deposits nothing for any design.  Table k is therefore the single call's table bit for bit on the same device: the
+// same fma chain in ascending c, the same exp, and sums on the 2^-32 grid, which do not depend on their order.
+//
+// Skipping zero counts.  A kernel may walk only a row's non-zero counts, in ascending c, and get visit_log_weight's
+// bits.  A step with a zero count is a = fma(0.0, x, a): for finite x the product is +0 or -0 exactly, and a + (+-0)
+// is a for every a but -0.0, which a never is: it starts at +0.0, and a sum that is exactly zero rounds to +0.0 (to
+// nearest) unless both terms are -0.0, which would need a to have been -0.0 before.  So the zero steps change nothing,
+// and leaving them out leaves the chain of the non-zero steps, each still one fma, in the same order.  (A non-finite
+// lnscale breaks the argument -- 0 * inf is NaN -- and is outside the contract; the Python layer refuses it.)
+//
+// Weight sums.  Every row that deposits also adds, with l = tile / (nx * ny), visit_quanta(q * 2^32) to
+// wsums[k][0][l] and visit_quanta(q * q * 2^32) to wsums[k][1][l] (int64 [K, 2, num_lmd], quanta of 2^-32).  Integer
+// adds: exact, order-free and additive over shards at any job size, where a float64 sum on the grid stops being exact
+// at 2^21.  The effective sample size is s1^2 / s2 of these sums.
+constexpr double kVisitQuantaLimit = 0x1p62;
+
+// v as int64 quanta: rint(v), and 2^62 for a v that is not below 2^62 (an overflowed exp, a NaN): such a design has no
+// meaningful effective sample size, and the guard keeps the conversion defined.
+WGRT_HD int64_t visit_quanta(double v) { return v < kVisitQuantaLimit ? (int64_t)rint(v) : (int64_t)1 << 62; }
+
+// visit_log_weight over the non-zero counts only (the argument above): the host twin's form of what the kernel does
+// with a ballot.
+WGRT_HD double visit_log_weight_sparse(const uint32_t *counts, const double *lnscale, int C) {
+    double a = 0.0;
+    for (int c = 0; c < C; ++c)
+        if (counts[c]) a = fma((double)counts[c], lnscale[c], a);
+    return a;
+}
+
+// NULL, or why the ensemble's own arguments are refused (after visits_reduce_error).
+inline const char *visits_many_error(const void *lnscale, int64_t K, const void *wsums) {
+    if (K < 1) return "need K >= 1 designs";
+    if (!lnscale || ((uintptr_t)lnscale & 7)) return "NULL or misaligned lnscale";
+    if ((uintptr_t)wsums & 7) return "wsums must be 8-B aligned";
+    return nullptr;
+}
+
 // NULL, or why the arguments of a reduction are refused.
 inline const char *visits_reduce_error(const void *plan, const void *counts, const void *ends, int64_t n_rows,
                                        const void *out) {

@@ -1,8 +1,9 @@
-// wgrt_visits.hip -- the two reductions of a table of counted rays on the device (wgrt_visits_sensitivity,
-// wgrt_visits_reweight, include/wgrt.h) and the scene's channel count, through the rule of wgrt_visits.h.
+// wgrt_visits.hip -- the reductions of a table of counted rays on the device (wgrt_visits_sensitivity,
+// wgrt_visits_reweight and, for K designs at once, wgrt_visits_reweight_many; include/wgrt.h) and the scene's channel
+// count, through the rule of wgrt_visits.h.
 //
 // The table is small -- the driver counts the delivered rays only, a few per cent of a launch -- and each delivered
-// row deposits into one slab column and the windows that hold its bin, so neither kernel sums on chip first.
+// row deposits into one slab column and the windows that hold its bin, so no kernel sums a table on chip first.
 //   sensitivity  one wave per row: every lane reads the row's end record (one 32-byte broadcast), the lanes stride
 //                over the row's C counts (a coalesced read), and a lane with a non-zero count deposits it into its
 //                channel's table.  The deposits are integers in float64: exact and order-free below 2^53.
@@ -14,10 +15,12 @@
 // [0, n_slabs * 9600), hence below n_slabs * W (times C for the sensitivity).
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
 #include <string>
 
 #include "../../include/wgrt.h"
+#include "../../include/wgrt_debug.h"
 #include "wgrt_scene.h"
 #include "wgrt_visits.h"
 
@@ -75,6 +78,122 @@ __global__ __launch_bounds__(kVisitsThreads) void visits_reweight_kernel(const u
     window_visit(*plan, off, [out, q](int64_t e) { unsafeAtomicAdd(out + e, q); });
 }
 
+// The ensemble (wgrt_visits_reweight_many; the rule and the zero-skipping argument: wgrt_visits.h).  A workgroup takes
+// kManyRows rows and one chunk of kManyDesigns = 64 designs, a lane per design, a wave per row.
+//   * The chunk's log-scales sit in LDS channel-major, lns[c * 65 + j]: the 64 lanes of a wave read 64 consecutive
+//     doubles (two conflict-free bank rows), and the stride of 65 spreads the fill's writes, which run along c.
+//   * A wave reads its row's end record (a broadcast) and its counts (lane c, coalesced) once, for all 64 designs.  The
+//     non-zero counts are the set bits of a ballot, walked in ascending c with the count read from its lane into a
+//     scalar register: every lane runs the same chain of single fmas on its own design's column.
+//   * The deposits.  DIRECT adds into out[k][e]: the wave's 64 adds go to 64 tables, 64 cache lines.  INTERLEAVED
+//     adds into a chunk's scratch [n_slabs * W, 64], where they are 512 contiguous bytes, and visits_many_fold_kernel
+//     then adds the scratch into the chunk's tables through an LDS transpose and zeroes it for the next chunk.  Both
+//     are sums on the 2^-32 grid, so both give the same bits (wgrt_debug_set_reweight_layout picks; DESIGN.md 4.13 has
+//     the timings).
+//   * The weight sums stay in registers while a wave's rows share a wavelength (rows are in ray order, so they nearly
+//     always do) and go to wsums as plain 64-bit vector atomics when it changes and at the end: a few per workgroup,
+//     design and wavelength.
+// Reads: rows below n_rows, channels below C, designs below K (a lane beyond K reads zeros and deposits nothing).
+// Writes: entries below n_slabs * W (window_visit over a guarded offset) of tables k < K, hence below
+// out + K * n_slabs * W; scratch entries below n_slabs * W * 64; wsums[(k * 2 + i) * nl + l] with l < nl because the
+// row's tile index was checked against the scene.
+constexpr int kManyDesigns = 64;                 // designs per chunk: one per lane
+constexpr int kManyStride = kManyDesigns + 1;    // LDS doubles per channel
+constexpr int kManyRows = 64;                    // rows per workgroup
+constexpr size_t kManyLdsLimit = 64 * 1024;
+
+__device__ __forceinline__ void many_flush(int64_t *wsums, int64_t k, int nl, int l, unsigned long long s1,
+                                           unsigned long long s2) {
+    atomicAdd((unsigned long long *)wsums + (k * 2 + 0) * nl + l, s1);
+    atomicAdd((unsigned long long *)wsums + (k * 2 + 1) * nl + l, s2);
+}
+
+template <bool INTERLEAVED>
+__global__ __launch_bounds__(kVisitsThreads) void visits_reweight_many_kernel(
+    const uint32_t *counts, const wgrt_visit_end *ends, int64_t n_rows, int C, const double *tiles, int tile_d, int nl,
+    int nx, int ny, const WindowPlanView *plan, const double *lnscale, int K, int k_first, double *dst,
+    int64_t table_stride, int64_t *wsums) {
+    extern __shared__ double lns[];   // [C][kManyStride]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int k0 = k_first + (int)blockIdx.y * kManyDesigns;
+    const int nk = K - k0 < kManyDesigns ? K - k0 : kManyDesigns;
+    for (int i = threadIdx.x; i < kManyDesigns * C; i += kVisitsThreads) {
+        const int j = i / C, c = i - j * C;
+        lns[c * kManyStride + j] = j < nk ? lnscale[(int64_t)(k0 + j) * C + c] : 0.0;
+    }
+    __syncthreads();
+    const bool mine = lane < nk;
+    const int64_t k = k0 + lane;
+    const int64_t r0 = (int64_t)blockIdx.x * kManyRows;
+    int cur_l = -1;
+    unsigned long long s1 = 0, s2 = 0;
+    for (int i = wave; i < kManyRows; i += kVisitsThreads / 64) {
+        const int64_t r = r0 + i;   // (wave-uniform)
+        if (r >= n_rows) break;
+        const wgrt_visit_end e = load_end(ends, r);
+        const int64_t off = visit_end_offset(e, nl, nx, ny, [=](uint32_t g, int, int) {
+            return tiles + (int64_t)g * tile_d + kTileEbRange;
+        });
+        if (off < 0) continue;
+        double a = 0.0;
+        for (int cb = 0; cb < C; cb += 64) {
+            const int v = cb + lane < C ? (int)counts[r * C + cb + lane] : 0;
+            unsigned long long m = __ballot(v != 0);
+            while (m) {   // ascending c; the count from its lane, the same in every lane
+                const int b = __builtin_ctzll(m);
+                m &= m - 1;
+                const uint32_t n = (uint32_t)__builtin_amdgcn_readlane(v, b);
+                a = fma((double)n, lns[(cb + b) * kManyStride + lane], a);
+            }
+        }
+        const double q = expected_quantize(exp(a));
+        if (mine) {   // (every lane, whatever its design, has served the ballot above as a channel's lane)
+            if (INTERLEAVED)
+                window_visit(*plan, off, [=](int64_t t) { unsafeAtomicAdd(dst + t * kManyDesigns + lane, q); });
+            else
+                window_visit(*plan, off, [=](int64_t t) { unsafeAtomicAdd(dst + k * table_stride + t, q); });
+        }
+        if (wsums && mine) {
+            const int l = (int)(e.tile / ((uint32_t)nx * (uint32_t)ny));
+            if (l != cur_l) {
+                if (cur_l >= 0) many_flush(wsums, k, nl, cur_l, s1, s2);
+                cur_l = l;
+                s1 = s2 = 0;
+            }
+            s1 += (unsigned long long)visit_quanta(q * 0x1p32);
+            s2 += (unsigned long long)visit_quanta(q * q * 0x1p32);
+        }
+    }
+    if (wsums && mine && cur_l >= 0) many_flush(wsums, k, nl, cur_l, s1, s2);
+}
+
+// The interleaved form's second step: out[k0 + j][e] += scratch[e][j] for the chunk's nk designs, 64 entries per
+// workgroup through an LDS tile (reads along j, writes along e, both contiguous), and scratch is left zero.  Plain
+// adds: a call's kernels are ordered on its stream and nothing else writes the tables meanwhile.
+__global__ __launch_bounds__(kVisitsThreads) void visits_many_fold_kernel(double *scratch, int64_t n_entries, int nk,
+                                                                         double *out, int64_t table_stride) {
+    __shared__ double tile[kManyDesigns][kManyStride];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t e0 = (int64_t)blockIdx.x * 64;
+    for (int i = wave; i < 64; i += kVisitsThreads / 64) {
+        double v = 0.0;
+        if (e0 + i < n_entries) {
+            double *const p = scratch + (e0 + i) * kManyDesigns + lane;
+            v = *p;
+            if (v != 0.0) *p = 0.0;
+        }
+        tile[i][lane] = v;
+    }
+    __syncthreads();
+    if (e0 + lane >= n_entries) return;
+    for (int j = wave; j < nk; j += kVisitsThreads / 64) {
+        const double v = tile[lane][j];
+        if (v != 0.0) out[j * table_stride + e0 + lane] += v;
+    }
+}
+
+std::atomic<int> g_many_interleaved{1};   // wgrt_debug_set_reweight_layout
+
 wgrt_status reduce_args(const wgrt_scene *s, const wgrt_window_plan *plan, const uint32_t *counts,
                         const wgrt_visit_end *ends, int64_t n_rows, const void *out) {
     if (!s) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL scene");
@@ -90,6 +209,8 @@ wgrt_status reduce_args(const wgrt_scene *s, const wgrt_window_plan *plan, const
 extern "C" {
 
 int32_t wgrt_visit_channels(const wgrt_scene *s) { return s ? visit_channel_count(s->nfc, s->noc) : -1; }
+
+int32_t wgrt_visit_wavelengths(const wgrt_scene *s) { return s ? s->nl : -1; }
 
 wgrt_status wgrt_visits_sensitivity(const wgrt_scene *s, const wgrt_window_plan *plan, const uint32_t *counts,
                                     const wgrt_visit_end *ends, int64_t n_rows, double *sens, void *stream) {
@@ -120,6 +241,60 @@ wgrt_status wgrt_visits_reweight(const wgrt_scene *s, const wgrt_window_plan *pl
                        counts, ends, n_rows, visit_channel_count(s->nfc, s->noc), (const double *)s->d_tiles, s->tile_d,
                        s->nl, s->nx, s->ny, (const WindowPlanView *)plan->d_view, lnscale, out);
     HIP_TRY(hipGetLastError());
+    return WGRT_OK;
+}
+
+wgrt_status wgrt_visits_reweight_many(const wgrt_scene *s, const wgrt_window_plan *plan, const uint32_t *counts,
+                                      const wgrt_visit_end *ends, int64_t n_rows, const double *lnscale, int32_t K,
+                                      double *out, int64_t *wsums, void *stream) {
+    const wgrt_status e = reduce_args(s, plan, counts, ends, n_rows, out);
+    if (e != WGRT_OK) return e;
+    if (const char *why = visits_many_error(lnscale, K, wsums)) return fail(WGRT_ERR_INVALID_ARGUMENT, why);
+    if (n_rows == 0) return WGRT_OK;
+    const int C = visit_channel_count(s->nfc, s->noc);
+    const size_t lds = (size_t)C * kManyStride * sizeof(double);
+    if (lds > kManyLdsLimit)
+        return fail(WGRT_ERR_UNSUPPORTED, "a chunk of 64 designs x " + std::to_string(C) + " channels does not fit in LDS");
+    const int64_t blocks = (n_rows + kManyRows - 1) / kManyRows, chunks = ((int64_t)K + kManyDesigns - 1) / kManyDesigns;
+    if (blocks > 0x7fffffff) return fail(WGRT_ERR_INVALID_ARGUMENT, "too many rows for one launch");
+    if (chunks > 65535) return fail(WGRT_ERR_INVALID_ARGUMENT, "too many designs for one launch");
+    const int64_t n_entries = (int64_t)s->nl * s->nx * s->ny * plan->host.W;
+    const hipStream_t st = (hipStream_t)stream;
+    const double *const tiles = (const double *)s->d_tiles;
+    const WindowPlanView *const view = (const WindowPlanView *)plan->d_view;
+    DEVICE_SCOPE(dev_scope, s->device);
+    if (!g_many_interleaved.load(std::memory_order_relaxed)) {
+        hipLaunchKernelGGL(visits_reweight_many_kernel<false>, dim3((unsigned)blocks, (unsigned)chunks),
+                           dim3(kVisitsThreads), lds, st, counts, ends, n_rows, C, tiles, s->tile_d, s->nl, s->nx, s->ny,
+                           view, lnscale, K, 0, out, n_entries, wsums);
+        HIP_TRY(hipGetLastError());
+        return WGRT_OK;
+    }
+    // one chunk's scratch, stream-ordered: zeroed once, left zero by every fold
+    const int64_t folds = (n_entries + 63) / 64;
+    if (folds > 0x7fffffff) return fail(WGRT_ERR_INVALID_ARGUMENT, "too many table entries for one launch");
+    double *scratch = nullptr;
+    const size_t bytes = (size_t)n_entries * kManyDesigns * sizeof(double);
+    const wgrt_status m = malloc_status(hipMallocAsync((void **)&scratch, bytes, st), "hipMallocAsync(design scratch)");
+    if (m != WGRT_OK) return m;
+    hipError_t h = hipMemsetAsync(scratch, 0, bytes, st);
+    for (int64_t c = 0; c < chunks && h == hipSuccess; ++c) {
+        const int k0 = (int)(c * kManyDesigns), nk = K - k0 < kManyDesigns ? K - k0 : kManyDesigns;
+        hipLaunchKernelGGL(visits_reweight_many_kernel<true>, dim3((unsigned)blocks), dim3(kVisitsThreads), lds, st,
+                           counts, ends, n_rows, C, tiles, s->tile_d, s->nl, s->nx, s->ny, view, lnscale, K, k0, scratch,
+                           n_entries, wsums);
+        hipLaunchKernelGGL(visits_many_fold_kernel, dim3((unsigned)folds), dim3(kVisitsThreads), 0, st, scratch,
+                           n_entries, nk, out + (int64_t)k0 * n_entries, n_entries);
+        h = hipGetLastError();
+    }
+    const hipError_t f = hipFreeAsync(scratch, st);
+    HIP_TRY(h);
+    HIP_TRY(f);
+    return WGRT_OK;
+}
+
+wgrt_status wgrt_debug_set_reweight_layout(int interleaved) {
+    g_many_interleaved.store(interleaved != 0, std::memory_order_relaxed);
     return WGRT_OK;
 }
 

@@ -535,7 +535,9 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, rep
     ``visits``: a record with ``plan`` (the job's ``engine.WindowPlan``), ``fate`` (uint8 per ray), ``windows`` (a scratch
     plan and table), ``sens`` (float64 ``[C, n_slabs, W]``, added to; None: no sensitivities are wanted) and, for a what-if, ``scales`` (``{channel: s}``),
     ``table`` (float64 ``[n_slabs, W]``, added to) and ``sums`` (float64 ``[2, num_lmd]``, added to: the weights' sum and
-    sum of squares): every call first runs a fate launch with no grid on a clone of the RNG states into the scratch table,
+    sum of squares) and, for a design ensemble, ``ensemble`` (a record with ``scales``, K designs as
+    ``VisitTable.reweight_many`` takes them, ``tables`` float64 ``[K, n_slabs, W]`` and ``sums`` int64
+    ``[K, 2, num_lmd]``, both added to): every call first runs a fate launch with no grid on a clone of the RNG states into the scratch table,
     gives the rays of the ``eyebox`` class the rows 0, 1, ... (an exclusive cumsum of the mask), runs the visits launch
     from the original states (``engine.trace_fullcolor(visits=...)``) and reduces its rows into ``sens`` (and ``table``).
     Single launches only and no ``chain`` again; the tables are sums over rays, so the ranks' tables add.
@@ -562,6 +564,9 @@ def hip_tracer(scene, variant: int = 0, stats=None, windows=None, fate=None, rep
         if getattr(visits, "scales", None) is not None:
             vt.reweight(visits.plan, visits.scales, out=visits.table)
             visits.sums += vt.weight_sums(visits.scales)
+        ens = getattr(visits, "ensemble", None)
+        if ens is not None:
+            vt.reweight_many(visits.plan, ens.scales, out=ens.tables, sums=ens.sums)
 
     def select_for(rays, rng, gid):
         """The paths launch's mask (None: every ray), the rays it names counted per wavelength."""

@@ -611,6 +611,49 @@ def _lnscale(names, scales, device=None):
     return out if device is None else out.to(device)
 
 
+def _lnscale_many(names, scales) -> torch.Tensor:
+    """K designs -- a list of ``{channel name: s}`` dicts (an empty dict: every scale 1) or a ``[K, C]`` array / tensor of
+    s -- as a float64 ``[K, C]`` host tensor of ``log s``, each row through ``_lnscale`` (the same refusals)."""
+    if isinstance(scales, dict):
+        raise ValueError("scales must be a list of {channel: s} dicts or a [K, C] array, not one dict")
+    if isinstance(scales, (list, tuple)) and all(isinstance(d, dict) for d in scales):
+        rows = list(scales)
+    else:
+        a = torch.as_tensor(scales, dtype=torch.float64).detach().cpu()
+        if a.dim() != 2 or a.shape[1] != len(names):
+            raise ValueError(f"scales must be a list of dicts or have shape [K, {len(names)}], got {tuple(a.shape)}")
+        rows = list(a)
+    if not rows:
+        raise ValueError("scales must hold at least one design")
+    return torch.stack([_lnscale(names, r) for r in rows]).contiguous()
+
+
+def tolerance_scales(channels, sigma: float, n_designs: int, seed: int = 0, select=None) -> np.ndarray:
+    """The scales of a tolerance ensemble, float64 ``[n_designs, C]``: row 0 all ones (the nominal design); in the other
+    rows ``ln s_c ~ N(0, sigma^2)`` independently for every selected channel, drawn from ``np.random.default_rng(seed)``,
+    and exactly 1 for the others.  ``channels``: the names (``visit_channels``); ``select``: ``fnmatch`` patterns over them
+    (e.g. ``["r4[*].b3", "r5[*].b3"]``; None: every channel)."""
+    import fnmatch
+    channels = list(channels)
+    if not (float(sigma) > 0.0 and np.isfinite(float(sigma))):
+        raise ValueError(f"sigma must be positive and finite, got {sigma!r}")
+    if isinstance(n_designs, bool) or int(n_designs) != n_designs or int(n_designs) < 2:
+        raise ValueError(f"n_designs must be >= 2 (the nominal design and one drawn), got {n_designs!r}")
+    on = np.ones(len(channels), dtype=bool)
+    if select is not None:
+        on[:] = False
+        for pat in ([select] if isinstance(select, str) else list(select)):
+            # (brackets name a slice here, not a character class: only * and ? are wildcards)
+            hit = np.array([fnmatch.fnmatchcase(n, pat.replace("[", "[[]")) for n in channels], dtype=bool)
+            if not hit.any():
+                raise ValueError(f"the pattern {pat!r} matches no channel")
+            on |= hit
+    out = np.ones((int(n_designs), len(channels)), dtype=np.float64)
+    draws = np.random.default_rng(seed).normal(0.0, float(sigma), size=(int(n_designs) - 1, int(on.sum())))
+    out[1:, on] = np.exp(draws)
+    return out
+
+
 class VisitTable:
     """The rows of visits launches (``trace_*(visits=(visit_table, slot))``; ``wgrt_trace_visits``): ``counts``, an int32
     ``[n_rows, C]`` device tensor (the library's uint32 words) that the launches add to, and ``ends``, a uint8
@@ -621,7 +664,10 @@ class VisitTable:
     ``reweight(plan, scales, out=None)`` adds the rows re-weighted by ``prod_c s_c^N_c`` into a float64
     ``[n_slabs, W]`` table (``wgrt_visits_reweight``; ``scales``: ``{channel name: s}`` or C values): the window table
     of the design whose channels are scaled so, without a re-trace; with every scale 1, the launches' own table bit for
-    bit.  ``ess(scales)``: the effective sample size ``(sum w)^2 / sum w^2`` of those weights per wavelength (a float64
+    bit.  ``reweight_many(plan, scales, out=None, sums=None)`` does that for K designs in one pass over the rows
+    (``wgrt_visits_reweight_many``): float64 ``[K, n_slabs, W]`` tables, table k the bytes of ``reweight``'s for design
+    k, and the weights' sums as int64 quanta of 2^-32 ``[K, 2, num_lmd]`` (``ess_of_quanta``).  ``ess(scales)``: the
+    effective sample size ``(sum w)^2 / sum w^2`` of those weights per wavelength (a float64
     device tensor ``[num_lmd]``; 0 where nothing was delivered).  ``host()``: ``(counts uint32, ends)`` as numpy."""
 
     def __init__(self, scene: Scene, n_rows: int, device=None):
@@ -672,6 +718,33 @@ class VisitTable:
         n_slabs = self.scene.num_lmd * self.scene.ny * self.scene.nx
         return self._reduce(plan, _lnscale(self.channels, scales, self.device), out, (n_slabs, plan.W), stream)
 
+    def reweight_many(self, plan: WindowPlan, scales, out: torch.Tensor | None = None, sums: torch.Tensor | None = None,
+                      stream=None):
+        """``(tables, sums)`` for K designs from one pass over the rows (``wgrt_visits_reweight_many``): ``scales`` is a
+        list of ``{channel name: s}`` dicts (an empty dict: the nominal design) or a ``[K, C]`` array or tensor of s;
+        ``tables`` float64 ``[K, n_slabs, W]``, ``tables[k]`` the bytes of ``reweight(plan, scales[k])``; ``sums`` int64
+        ``[K, 2, num_lmd]``, the weights' sum and sum of squares in quanta of 2^-32 (``ess_of_quanta``).  Both are added
+        to when given."""
+        if plan.device != self.scene.device:
+            raise ValueError(f"the plan is on device {plan.device}, the scene on device {self.scene.device}")
+        ln = _lnscale_many(self.channels, scales).to(self.device)
+        K = ln.shape[0]
+        n_slabs = self.scene.num_lmd * self.scene.ny * self.scene.nx
+        for name, t, dtype, shape in (("out", out, torch.float64, (K, n_slabs, plan.W)),
+                                      ("sums", sums, torch.int64, (K, 2, self.scene.num_lmd))):
+            if t is not None:
+                _as_dev(t, dtype, name, self.device)
+                if tuple(t.shape) != shape:
+                    raise ValueError(f"{name} shape {tuple(t.shape)} != {shape}")
+        if out is None:
+            out = torch.zeros((K, n_slabs, plan.W), dtype=torch.float64, device=self.device)
+        if sums is None:
+            sums = torch.zeros((K, 2, self.scene.num_lmd), dtype=torch.int64, device=self.device)
+        check(ops().visits_reweight_many(self.scene.handle.value, plan.handle.value, self.counts, self.ends, self.n_rows,
+                                         ln, out, sums, _stream_handle(self.device, stream)),
+              "wgrt_visits_reweight_many")
+        return out, sums
+
     def weight_sums(self, scales) -> torch.Tensor:
         """Float64 ``[2, num_lmd]``: per wavelength, the sum and the sum of squares of the delivered rows' weights
         ``prod_c s_c^N_c`` (torch, from the same rows; sums of several tables add)."""
@@ -696,7 +769,19 @@ def ess_of(sums) -> torch.Tensor:
     return torch.where(s2 > 0, s1 * s1 / s2.clamp_min(1e-300), torch.zeros_like(s1))
 
 
-def _visits_host(fn, name, counts, ends, nx, ny, num_lmd, scene_ranges, plan_mask, step_y, step_x, shape, out, *more):
+def ess_of_quanta(sums):
+    """The effective sample size ``s1^2 / s2`` per design and wavelength, float64 ``[K, num_lmd]``, of
+    ``VisitTable.reweight_many``'s int64 ``[K, 2, num_lmd]`` sums (quanta of 2^-32; a tensor or an array, returned in
+    kind; 0 where nothing was delivered)."""
+    if isinstance(sums, torch.Tensor):
+        s1, s2 = sums[:, 0].double() * 2.0 ** -32, sums[:, 1].double() * 2.0 ** -32
+        return torch.where(s2 > 0, s1 * s1 / s2.clamp_min(1e-300), torch.zeros_like(s1))
+    s = np.asarray(sums).astype(np.float64) * 2.0 ** -32
+    return np.where(s[:, 1] > 0, s[:, 0] * s[:, 0] / np.maximum(s[:, 1], 1e-300), 0.0)
+
+
+def _visits_host(fn, name, counts, ends, nx, ny, num_lmd, scene_ranges, plan_mask, step_y, step_x, shape, out, *more,
+                 tail=()):
     counts = np.ascontiguousarray(counts, dtype=np.uint32)
     ends = np.ascontiguousarray(ends, dtype=VISIT_END_DTYPE)
     if counts.ndim != 2 or ends.shape != (counts.shape[0],):
@@ -710,7 +795,7 @@ def _visits_host(fn, name, counts, ends, nx, ny, num_lmd, scene_ranges, plan_mas
     elif out.dtype != np.float64 or not out.flags.c_contiguous or out.shape != shape:
         raise ValueError(f"out must be a C-contiguous float64 array of shape {shape}")
     check(fn(int(nx), int(ny), int(num_lmd), counts.shape[1], rg.ctypes.data, mask.ctypes.data, mask.shape[0],
-             int(step_y), int(step_x), counts.ctypes.data, ends.ctypes.data, counts.shape[0], *more, out.ctypes.data), name)
+             int(step_y), int(step_x), counts.ctypes.data, ends.ctypes.data, counts.shape[0], *more, out.ctypes.data, *tail), name)
     return out
 
 
@@ -741,6 +826,26 @@ def visits_reweight_host(counts, ends, lnscale, nx: int, ny: int, num_lmd: int, 
     shape = (int(num_lmd) * int(ny) * int(nx), _window_width(mask, step_y, step_x))
     return _visits_host(load().wgrt_visits_reweight_host, "wgrt_visits_reweight_host", counts, ends, nx, ny, num_lmd,
                         scene_ranges, mask, step_y, step_x, shape, out, ln.ctypes.data)
+
+
+def visits_reweight_many_host(counts, ends, lnscale, nx: int, ny: int, num_lmd: int, scene_ranges, mask, step_y: int = 8,
+                              step_x: int = 12, out=None, sums=None):
+    """``VisitTable.reweight_many`` on the host (``wgrt_visits_reweight_many_host``): ``lnscale`` float64 ``[K, C]``,
+    ``log s`` per design and channel.  Returns ``(tables, sums)``, float64 ``[K, num_lmd * ny * nx, W]`` and int64
+    ``[K, 2, num_lmd]``; both are added to when given."""
+    ln = np.ascontiguousarray(lnscale, dtype=np.float64)
+    if ln.ndim != 2 or ln.shape[0] < 1 or ln.shape[1] != np.asarray(counts).shape[1]:
+        raise ValueError("lnscale must be [K >= 1, C]: one value per design and channel")
+    K = ln.shape[0]
+    if sums is None:
+        sums = np.zeros((K, 2, int(num_lmd)), dtype=np.int64)
+    elif sums.dtype != np.int64 or not sums.flags.c_contiguous or sums.shape != (K, 2, int(num_lmd)):
+        raise ValueError(f"sums must be a C-contiguous int64 array of shape {(K, 2, int(num_lmd))}")
+    shape = (K, int(num_lmd) * int(ny) * int(nx), _window_width(mask, step_y, step_x))
+    out = _visits_host(load().wgrt_visits_reweight_many_host, "wgrt_visits_reweight_many_host", counts, ends, nx, ny,
+                       num_lmd, scene_ranges, mask, step_y, step_x, shape, out, ln.ctypes.data, K,
+                       tail=(sums.ctypes.data,))
+    return out, sums
 
 
 STOKES_SCALE = 2.0 ** 30   # quanta per unit of a normalised Stokes parameter (csrc/wgrt_stokes.h)
@@ -1415,6 +1520,6 @@ def expected_weight(e1: float, e2: float, e3: float, en1: float, en2: float, en3
     return float(load().wgrt_expected_weight_host(e1, e2, e3, en1, en2, en3, threshold))
 
 
-__all__ = ["StokesTable", "stokes_quanta", "STOKES_SCALE", "VisitTable", "visit_channels", "ess_of", "visits_sensitivity_host", "visits_reweight_host", "VISIT_END_DTYPE", "Scene", "WindowPlan", "FootprintPlan", "footprint_bin", "FOOTPRINT_CHANNELS", "PathList", "PathListOverflow", "check_paths", "paths_footprint_host", "sort_paths", "path_polylines", "path_state", "path_kind", "path_lmd", "path_tag", "PATH_DTYPE", "PATH_KINDS", "select_by_fate", "HitList", "HitListOverflow", "check_hits", "hits_grid_host", "sort_hits", "hit_inside", "hit_tag", "hit_lmn", "HIT_DTYPE", "TraceChain", "fold_replicas", "expected_weight", "MAX_REPLICAS", "fate_census", "fate_census_host", "fate_col", "loss_budget", "FATE_CLASSES", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
+__all__ = ["StokesTable", "stokes_quanta", "STOKES_SCALE", "VisitTable", "visit_channels", "ess_of", "ess_of_quanta", "tolerance_scales", "visits_sensitivity_host", "visits_reweight_host", "visits_reweight_many_host", "VISIT_END_DTYPE", "Scene", "WindowPlan", "FootprintPlan", "footprint_bin", "FOOTPRINT_CHANNELS", "PathList", "PathListOverflow", "check_paths", "paths_footprint_host", "sort_paths", "path_polylines", "path_state", "path_kind", "path_lmd", "path_tag", "PATH_DTYPE", "PATH_KINDS", "select_by_fate", "HitList", "HitListOverflow", "check_hits", "hits_grid_host", "sort_hits", "hit_inside", "hit_tag", "hit_lmn", "HIT_DTYPE", "TraceChain", "fold_replicas", "expected_weight", "MAX_REPLICAS", "fate_census", "fate_census_host", "fate_col", "loss_budget", "FATE_CLASSES", "WgrtError", "TraceStats", "STAT", "STATS_LEN", "new_stats", "check_stats", "block_runs",
            "trace_fullcolor", "trace_single", "init_rays", "schedule_by_lifetime",
            "rays_to_device", "classify_points", "shadow", "selftest_math", "RAY_COLUMNS", "_lib"]

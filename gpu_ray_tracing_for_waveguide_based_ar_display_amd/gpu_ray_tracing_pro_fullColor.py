@@ -29,7 +29,9 @@ Same flow as the reference script, on the MI355X kernel:
    records -- which way that light went (``wgrt_trace_paths``) -- and reduced to a conditional footprint on request;
    with ``sensitivity=True`` (``--sensitivity``) the branches the delivered rays took are counted per channel
    (``wgrt_trace_visits``): which grating to change; with ``what_if={channel: scale}`` (``--what-if``) the same rays,
-   re-weighted, give the figures of the scaled design without a re-trace;
+   re-weighted, give the figures of the scaled design without a re-trace; with ``designs=[...]`` (``--designs``) or
+   ``tolerance=sigma`` (``--tolerance``) the same for K listed or randomly drawn designs in one pass
+   (``wgrt_visits_reweight_many``): candidates side by side, or the band every figure lands in;
 6. the "Eyebox Center View.png" export (MAIN:199-203): the evaluated image at the first eye row,
    last eye column, as 8-bit RGB, rows flipped (``eyebox_center_view``, written without OpenCV).
 
@@ -64,7 +66,8 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
         eyebox: str = "host", keep_grid: bool = False, evaluate_on: str = "host",
         keep_image: bool = False, budget: bool = False, error_bars: int = 0, estimator: str = "analog",
         footprint=None, hits=None, paths=None, paths_capacity=None, paths_footprint=None, sensitivity=None,
-        what_if=None, polarisation: bool = False, analyser=None, analyser_frame: str = "fov") -> dict:
+        what_if=None, polarisation: bool = False, analyser=None, analyser_frame: str = "fov", designs=None,
+        tolerance=None, tolerance_designs: int = 64, tolerance_seed: int = 0, tolerance_channels=None) -> dict:
     """The reference script's job on this engine; returns its printed quantities and arrays.
     ``points``: the R/2 in-coupler origins to use (default: sampled, GRTF:12-23, seeded by
     ``point_seed``); ``png``: where to write the "Eyebox Center View" image (needs ``evaluate``).
@@ -189,6 +192,24 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
     ``error_bars``, ``estimator="expected"``, ``footprint``, ``hits`` and ``paths`` with either raise ``ValueError``
     before any GPU work.
 
+    ``designs``: a list of ``{channel name: scale}`` dicts (``{}``: the nominal design) or a ``[K, C]`` array of scales
+    (None: off): the what-if for K designs at once.  Each iteration re-weights its delivered rays for every design in one
+    pass (``VisitTable.reweight_many``, ``wgrt_visits_reweight_many``) into one float64 ``[K, n_slabs, 57]`` tensor and
+    one int64 ``[K, 2, num_lmd]`` tensor of weight sums; several GPUs sum-reduce both to rank 0.  Table k is, bit for
+    bit, the ``what_if`` table of ``designs[k]``; the designs share the sample, so their differences carry far less noise
+    than two runs'.  ``tolerance``: sigma (None: off): the same for ``tolerance_designs`` designs of
+    ``engine.tolerance_scales`` -- design 0 nominal, in the others ``ln s_c ~ N(0, sigma^2)`` per channel matching
+    ``tolerance_channels`` (``fnmatch`` patterns such as ``"r4[*].b3"``; None: every channel), from
+    ``tolerance_seed``.  The two exclude each other, need ``eyebox="windows"``, ride the visits launch of ``sensitivity``
+    and ``what_if`` (all three combine) and carry their exclusions.  The tables' bytes are computed up front and
+    printed; more than the device has free raises ``ValueError`` naming the largest K that fits.  Returned as
+    ``ensemble``: ``scales`` ``[K, C]``, ``channels``, ``table``, ``A`` ``[K, L, NY, NX]``, ``efficiency`` ``[K, L]``,
+    ``ess`` ``[K, L]`` and, with ``evaluate``, ``delta_e``, ``U_fov``, ``U_EB`` ``[K]`` (``evaluation_ensemble``); for
+    ``tolerance`` also ``summary``: per figure (``efficiency`` per wavelength, ``delta_e``, ``U_fov``, ``U_EB``) its
+    ``nominal`` value, and ``mean``, ``std``, ``p5``, ``p50``, ``p95`` over designs 1 .. K-1, and ``min_ess`` over all
+    designs.  The estimator is the what-if's, and so is its limit: an up-scaled channel is over-credited wherever a
+    state's branch efficiencies already sum to 1, so the upper tail of a tolerance band is optimistic.
+
     ``polarisation``: also the polarisation state of the delivered light (needs ``eyebox="windows"``).  The traces go as
     plain single launches that add, for every out-coupling the window table counts, the three fixed-point normalised
     Stokes parameters of the out-coupled field to int64 tables ``[3, n_slabs, 57]`` beside it (``engine.StokesTable``,
@@ -217,9 +238,11 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
     if polarisation:
         if budget or error_bars or estimator == "expected" or footprint is not None or \
                 not (hits is None or hits is False) or not (paths is None or paths is False) or \
-                not (sensitivity is None or sensitivity is False) or what_if is not None:
+                not (sensitivity is None or sensitivity is False) or what_if is not None or designs is not None or \
+                tolerance is not None:
             raise ValueError("polarisation is not combined with budget=True, error_bars, estimator='expected', footprint, "
-                             "hits, paths, sensitivity or what_if: a launch fills Stokes tables or does one of those")
+                             "hits, paths, sensitivity, what_if, designs or tolerance: a launch fills Stokes tables or "
+                             "does one of those")
         if eyebox != "windows":
             raise ValueError("polarisation fills tables beside the window table: it needs eyebox='windows'")
     top_k = 0
@@ -243,13 +266,55 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
             if not ok:
                 raise ValueError(f"what_if: {name!r}={sc_!r} is not a visit channel with a positive finite scale")
         what_if = {str(k): float(v) for k, v in what_if.items()}
-    if sensitivity is not None or what_if is not None:
+    if designs is not None and tolerance is not None:
+        raise ValueError("designs and tolerance exclude each other: an ensemble is listed or drawn, not both")
+    if designs is not None:
+        if isinstance(designs, dict) or not hasattr(designs, "__len__") or len(designs) == 0:
+            raise ValueError(f"designs must be a non-empty list of {{channel name: scale}} dicts or a [K, C] array, "
+                             f"got {designs!r}")
+        if all(isinstance(d, dict) for d in designs):
+            from .luts import channel_quad
+            for d in designs:
+                for name, sc_ in d.items():
+                    try:
+                        channel_quad(name)
+                        ok = float(sc_) > 0.0 and np.isfinite(float(sc_))
+                    except (TypeError, ValueError):
+                        ok = False
+                    if not ok:
+                        raise ValueError(f"designs: {name!r}={sc_!r} is not a visit channel with a positive finite scale")
+            designs = [{str(k): float(v) for k, v in d.items()} for d in designs]
+        else:
+            try:
+                designs = np.ascontiguousarray(designs, dtype=np.float64)
+            except (TypeError, ValueError):
+                designs = None
+            if designs is None or designs.ndim != 2 or not (np.isfinite(designs).all() and (designs > 0).all()):
+                raise ValueError("designs must be a list of {channel name: scale} dicts or a [K, C] array of positive "
+                                 "finite scales")
+    if tolerance is not None:
+        if isinstance(tolerance, bool) or not isinstance(tolerance, (int, float, np.integer, np.floating)) or \
+                not (float(tolerance) > 0.0 and np.isfinite(float(tolerance))):
+            raise ValueError(f"tolerance must be a positive finite sigma of ln(scale), got {tolerance!r}")
+        if isinstance(tolerance_designs, bool) or not isinstance(tolerance_designs, (int, np.integer)) or \
+                int(tolerance_designs) < 2:
+            raise ValueError(f"tolerance_designs must be >= 2 (the nominal design and one drawn), got "
+                             f"{tolerance_designs!r}")
+        tolerance, tolerance_designs = float(tolerance), int(tolerance_designs)
+        if tolerance_channels is not None:
+            tolerance_channels = [tolerance_channels] if isinstance(tolerance_channels, str) else list(tolerance_channels)
+            if not tolerance_channels or not all(isinstance(p, str) and p for p in tolerance_channels):
+                raise ValueError(f"tolerance_channels must be a list of channel patterns, got {tolerance_channels!r}")
+    ensemble = designs is not None or tolerance is not None
+    if sensitivity is not None or what_if is not None or ensemble:
         if budget or error_bars or estimator == "expected" or footprint is not None or \
                 not (hits is None or hits is False) or not (paths is None or paths is False):
-            raise ValueError("sensitivity / what_if are not combined with budget=True, error_bars, estimator='expected', "
-                             "footprint, hits or paths: a launch counts branch visits or does one of those")
+            raise ValueError("sensitivity / what_if / designs / tolerance are not combined with budget=True, error_bars, "
+                             "estimator='expected', footprint, hits or paths: a launch counts branch visits or does one "
+                             "of those")
         if eyebox != "windows":
-            raise ValueError("sensitivity / what_if reduce into window tables: they need eyebox='windows'")
+            raise ValueError("sensitivity / what_if / designs / tolerance reduce into window tables: they need "
+                             "eyebox='windows'")
     path_classes = None   # the fate classes of a selection (None: none, or every ray)
     if paths is None or paths is False:
         paths = None
@@ -357,7 +422,7 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
             from .engine import StokesTable
             job.stokes = StokesTable(job.scene, job.windows[0], job.dev)
         job.visits = None
-        if sensitivity is not None or what_if is not None:
+        if sensitivity is not None or what_if is not None or ensemble:
             import torch
 
             from .engine import WindowPlan, visit_channels
@@ -365,6 +430,10 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
             if what_if is not None and not set(what_if) <= set(names):
                 raise ValueError(f"what_if names no visit channel of this scene: {sorted(set(what_if) - set(names))}")
             n_slabs, W = job.windows[1].shape
+            ens = None
+            if ensemble:
+                ens = _ensemble_set_up(job, names, n_slabs, W, designs, tolerance, tolerance_designs, tolerance_seed,
+                                       tolerance_channels)
             scratch = WindowPlan(device=job.dev.index)
             job.visits = SimpleNamespace(
                 plan=job.windows[0], fate=torch.zeros(job.shard.n_rays, dtype=torch.uint8, device=job.dev),
@@ -372,7 +441,7 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
                 sens=(torch.zeros((len(names), n_slabs, W), dtype=torch.float64, device=job.dev)
                       if sensitivity is not None else None), scales=what_if,
                 table=torch.zeros((n_slabs, W), dtype=torch.float64, device=job.dev) if what_if is not None else None,
-                sums=torch.zeros((2, job.scene.num_lmd), dtype=torch.float64, device=job.dev))
+                sums=torch.zeros((2, job.scene.num_lmd), dtype=torch.float64, device=job.dev), ensemble=ens)
         try:
             kern_s = _trace(job, variant, fuse)
         finally:
@@ -404,12 +473,15 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
                 from .engine import FootprintPlan
                 pfp = FootprintPlan.for_scene(job.geom, cells=paths_footprint)
                 path_map = reduce_eyebox(job.paths.list.footprint(job.scene, pfp))
-        sens = wtable = wsums = None
+        sens = wtable = wsums = etables = esums = None
         if job.visits is not None:   # sums over rays: the ranks' tables add
             from .distributed import reduce_eyebox
             sens = reduce_eyebox(job.visits.sens) if job.visits.sens is not None else None
             if what_if is not None:
                 wtable, wsums = reduce_eyebox(job.visits.table), reduce_eyebox(job.visits.sums)
+            if ensemble:   # grid-valued doubles and integers: both add exactly
+                etables = reduce_eyebox(job.visits.ensemble.tables)
+                esums = reduce_eyebox(job.visits.ensemble.sums)
         stokes = None
         if job.stokes is not None:   # integer sums: the ranks' tables add exactly
             from .distributed import reduce_eyebox
@@ -431,6 +503,8 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
             _report_sensitivity(job, out, sens, table, top_k)
         if wtable is not None:
             _report_what_if(job, out, what_if, wtable, wsums, evaluate, evaluate_on)
+        if ensemble:
+            _report_ensemble(job, out, job.visits.ensemble, etables, esums, evaluate, evaluate_on)
         if stokes is not None:
             _report_polarisation(job, out, table, stokes, analyser, analyser_frame, evaluate, evaluate_on)
         out["post_seconds"] = time.perf_counter() - t_post
@@ -645,6 +719,97 @@ def _report_what_if(job, out: dict, scales: dict, wtable, wsums, evaluate: bool,
         job.say(f"FoV uniformity        : {w['U_fov'] * 100:8.2f} %")
         job.say(f"Eyebox uniformity     : {w['U_EB'] * 100:8.2f} %")
     out["what_if"] = w
+
+
+ENSEMBLE_CHUNK = 64   # designs per chunk of wgrt_visits_reweight_many: its scratch is [n_slabs * W, 64] float64
+
+
+def _ensemble_set_up(job, names, n_slabs: int, W: int, designs, tolerance, n_designs, seed, patterns):
+    """The ensemble's record for ``hip_tracer`` (``visits.ensemble``): ``scales`` (what ``reweight_many`` takes),
+    ``scales_array`` ``[K, C]``, ``tolerance`` (sigma or None) and the two device tensors every iteration adds to.  The
+    tables' bytes are printed and checked against the device's free memory first."""
+    import torch
+
+    from .engine import tolerance_scales
+    C = len(names)
+    if tolerance is not None:
+        scales = array = tolerance_scales(names, tolerance, n_designs, seed, patterns)
+    elif isinstance(designs, np.ndarray):
+        if designs.shape[1] != C:
+            raise ValueError(f"designs has {designs.shape[1]} scales per design, the scene {C} visit channels")
+        scales = array = designs
+    else:
+        bad = sorted(set().union(*designs) - set(names))
+        if bad:
+            raise ValueError(f"designs names no visit channel of this scene: {bad}")
+        scales, array = designs, np.ones((len(designs), C), dtype=np.float64)
+        for k, d in enumerate(designs):
+            for name, s in d.items():
+                array[k, names.index(name)] = s
+    K = array.shape[0]
+    per_design, fixed = n_slabs * W * 8, n_slabs * W * ENSEMBLE_CHUNK * 8   # a table; the reduction's scratch
+    free = int(torch.cuda.mem_get_info(job.dev)[0])
+    job.say(f"Design ensemble       : {K} designs, tables {K * per_design / 1e6:,.1f} MB "
+            f"(+ {fixed / 1e6:,.1f} MB while reducing; {free / 1e6:,.0f} MB free)")
+    if K * per_design + fixed > free:
+        fits = max((free - fixed) // per_design, 0)
+        raise ValueError(f"designs / tolerance: {K} tables of {per_design / 1e6:,.1f} MB exceed the device's free memory "
+                         f"({free / 1e6:,.0f} MB); the largest K that fits is {fits}")
+    return SimpleNamespace(scales=scales, scales_array=array, tolerance=tolerance,
+                           tables=torch.zeros((K, n_slabs, W), dtype=torch.float64, device=job.dev),
+                           sums=torch.zeros((K, 2, job.scene.num_lmd), dtype=torch.int64, device=job.dev))
+
+
+def _report_ensemble(job, out: dict, ens, tables, sums, evaluate: bool, evaluate_on: str) -> None:
+    """The ensemble's figures into ``out["ensemble"]`` and printed: one line per listed design, or, for a tolerance
+    ensemble, the band of every figure over the drawn designs."""
+    from .AR_system_evaluation_functions import evaluation_ensemble
+    from .engine import ess_of_quanta
+    shape = job.scene.eb_shape()
+    t = tables.cpu().numpy()
+    K = t.shape[0]
+    A = t[:, :, 0].reshape((K,) + tuple(shape[:-2])).astype(np.float32) / job.num_rays / job.num_iter
+    eff = np.array([[float(np.sum(A[k, l] * 3)) for l in range(A.shape[1])] for k in range(K)], dtype=np.float64)
+    ess = ess_of_quanta(sums.cpu().numpy())
+    e = dict(scales=ens.scales_array, channels=list(job.visits.channels), table=t, A=A, efficiency=eff, ess=ess,
+             sums=sums.cpu().numpy())
+    figures = {}
+    if evaluate:
+        figures = evaluation_ensemble(tables if evaluate_on == "device" else t, shape, job.R * job.num_iter, evaluate_on)
+        e.update(figures)
+    names = {0: "Blue", 1: "Green", 2: "Red"}
+    lam = [names.get(l, str(l)) for l in range(eff.shape[1])]
+    if ens.tolerance is None:
+        job.say(f"Design ensemble: {K} designs (the same rays, re-weighted)")
+        for k in range(K):
+            line = f"  design {k:3d}: " + "  ".join(f"{n} {eff[k, l] * 100:7.3f} %" for l, n in enumerate(lam))
+            if figures:
+                line += (f"  dE {figures['delta_e'][k]:6.2f}  U_fov {figures['U_fov'][k] * 100:6.2f} %"
+                         f"  U_EB {figures['U_EB'][k] * 100:6.2f} %")
+            job.say(line + f"  min ESS {ess[k].min():,.0f}")
+    else:
+        band = lambda v: dict(nominal=v[0], mean=v[1:].mean(axis=0), std=v[1:].std(axis=0),
+                              **{f"p{p}": np.percentile(v[1:], p, axis=0) for p in (5, 50, 95)})
+        s = dict(efficiency=band(eff), **{k: band(v) for k, v in figures.items()}, min_ess=float(ess.min()))
+        e["summary"] = s
+        job.say(f"Tolerance band: sigma(ln s) = {ens.tolerance:g}, {K - 1} designs drawn "
+                f"(nominal | mean +- std | 5 % / 50 % / 95 %)")
+        row = lambda name, b, f, i=(): job.say(
+            f"  {name:18s}: {b['nominal'][i] * f:8.3f} | {b['mean'][i] * f:8.3f} +- {b['std'][i] * f:7.3f} | "
+            f"{b['p5'][i] * f:8.3f} / {b['p50'][i] * f:8.3f} / {b['p95'][i] * f:8.3f}")
+        for l, n in enumerate(lam):
+            row(f"Efficiency {n} %", s["efficiency"], 100.0, l)
+        for key, name, f in (("delta_e", "Color dispersion", 1.0), ("U_fov", "FoV uniformity %", 100.0),
+                             ("U_EB", "Eyebox uniform. %", 100.0)):
+            if key in s:
+                row(name, s[key], f)
+        job.say(f"  smallest effective sample size: {s['min_ess']:,.0f}")
+    if (ens.scales_array > 1.0).any():
+        # (the what-if's limit, _report_what_if: an up-scaled channel is over-credited where a state's branch
+        # efficiencies already sum to 1, so the figures of such designs -- a band's upper tail -- are too high)
+        job.say("  note: scaled up -- unbiased only where the state's branch efficiencies still sum to <= 1; "
+                "check the scaled LUTs (luts.scale_channel) or confirm with a direct run")
+    out["ensemble"] = e
 
 
 def _report_polarisation(job, out: dict, table, stokes, analyser, frame: str, evaluate: bool, evaluate_on: str) -> None:
@@ -949,6 +1114,19 @@ def main(argv=None):
     ap.add_argument("--what-if", default="", metavar="CHANNEL=SCALE[,...]",
                     help="also the figures of the design whose channels' efficiencies are scaled so, from the same rays "
                          "re-weighted, e.g. 'r4[2].b3=1.2,r2[0].b2=0.9'; needs --eyebox windows")
+    ap.add_argument("--designs", default="", metavar="FILE.json",
+                    help="also the figures of every design of a list, from the same rays re-weighted in one pass: a JSON "
+                         "list of {CHANNEL: SCALE} objects ({}: the nominal design); needs --eyebox windows; not with "
+                         "--tolerance")
+    ap.add_argument("--tolerance", type=float, default=None, metavar="SIGMA",
+                    help="also a tolerance band: the figures of random designs whose channel efficiencies are off by "
+                         "ln s ~ N(0, SIGMA^2), from the same rays; needs --eyebox windows")
+    ap.add_argument("--tolerance-designs", type=int, default=64, metavar="K", help="designs of the band, the nominal included")
+    ap.add_argument("--tolerance-seed", type=int, default=0, metavar="S", help="seed of the band's draws")
+    ap.add_argument("--tolerance-channels", default="", metavar="PAT[,PAT...]",
+                    help="the channels that vary, as patterns over their names, e.g. 'r4[*].b3,r5[*].b3' (default: all)")
+    ap.add_argument("--ensemble-out", default="", metavar="FILE.npz",
+                    help="save the ensemble's scales, tables, weight sums and figures there (numpy)")
     ap.add_argument("--polarisation", action="store_true",
                     help="also the polarisation of the delivered light: Stokes tables beside the window table, the mean "
                          "Stokes vector and degree of polarisation per wavelength; needs --eyebox windows; not with "
@@ -1003,6 +1181,21 @@ def main(argv=None):
                 ap.error(f"--what-if takes CHANNEL=SCALE[,CHANNEL=SCALE...], got {a.what_if!r}")
     if a.sensitivity is not None and a.sensitivity < 1:
         ap.error(f"--sensitivity takes the number K >= 1 of channels to print, got {a.sensitivity}")
+    designs = None
+    if a.designs:
+        try:
+            with open(a.designs) as f:
+                designs = json.load(f)
+        except (OSError, ValueError) as e:
+            ap.error(f"--designs: cannot read {a.designs!r}: {e}")
+        if not isinstance(designs, list) or not designs or not all(isinstance(d, dict) for d in designs):
+            ap.error(f"--designs takes a JSON file holding a non-empty list of {{CHANNEL: SCALE}} objects, got {a.designs!r}")
+    if a.tolerance is not None and not (a.tolerance > 0 and np.isfinite(a.tolerance)):
+        ap.error(f"--tolerance takes a sigma > 0, got {a.tolerance}")
+    if a.tolerance_designs < 2:
+        ap.error(f"--tolerance-designs takes K >= 2 (the nominal design and one drawn), got {a.tolerance_designs}")
+    if designs is not None and a.tolerance is not None:
+        ap.error("--designs and --tolerance exclude each other")
     footprint = cells("--footprint", a.footprint)
     paths_footprint = cells("--paths-footprint", a.paths_footprint)
     res = run(a.num_fov_x, a.num_fov_y, a.rays_per_fov, a.num_iter, lut_dir=a.lut_dir, lut_seed=a.lut_seed,
@@ -1012,7 +1205,14 @@ def main(argv=None):
               footprint=footprint, hits=None if a.hits is None else (True if a.hits < 0 else a.hits),
               paths=None if not a.paths else (a.paths.split(",") if "," in a.paths else a.paths),
               paths_capacity=a.paths_capacity, paths_footprint=paths_footprint, sensitivity=a.sensitivity,
-              what_if=what_if, polarisation=a.polarisation, analyser=a.analyser, analyser_frame=a.analyser_frame)
+              what_if=what_if, polarisation=a.polarisation, analyser=a.analyser, analyser_frame=a.analyser_frame,
+              designs=designs, tolerance=a.tolerance, tolerance_designs=a.tolerance_designs,
+              tolerance_seed=a.tolerance_seed,
+              tolerance_channels=[p for p in a.tolerance_channels.split(",") if p] or None)
+    if a.ensemble_out and "ensemble" in res:   # (rank 0 has the tables)
+        e = res["ensemble"]
+        np.savez(a.ensemble_out, channels=np.array(e["channels"]),
+                 **{k: v for k, v in e.items() if isinstance(v, np.ndarray)})
     if a.polarisation_out and "stokes" in res:   # (rank 0 has the tables)
         np.save(a.polarisation_out, res["stokes"])
     if a.sensitivity_out and "sensitivity" in res:   # (rank 0 has the tables)
@@ -1028,6 +1228,10 @@ def main(argv=None):
         if "what_if" in keep:   # (its arrays stay out, as the top level's do; the ESS goes as a list)
             keep["what_if"] = {k: (v.tolist() if k == "ess" else v) for k, v in keep["what_if"].items()
                                if k == "ess" or isinstance(v, (int, float, dict, str))}
+        if "ensemble" in keep:   # (the per-design figures and the summary go as lists; the tables stay out)
+            lists = lambda d: {k: (lists(v) if isinstance(v, dict) else np.asarray(v).tolist()) for k, v in d.items()}
+            keep["ensemble"] = lists({k: v for k, v in keep["ensemble"].items()
+                                      if k in ("efficiency", "ess", "delta_e", "U_fov", "U_EB", "summary", "channels")})
         with open(a.json, "w") as f:
             json.dump(keep, f, indent=1)
     if dist.is_initialized():

@@ -775,6 +775,37 @@ wgrt_status wgrt_visits_reweight_host(int32_t nx, int32_t ny, int32_t num_lmd, i
                                       const double *lnscale, double *out);
 int32_t wgrt_visit_channel_host(int32_t n_fc_slices, int32_t n_oc_slices, int32_t state, int32_t slice, int32_t branch);
 int32_t wgrt_visit_channel_count_host(int32_t n_fc_slices, int32_t n_oc_slices);
+/* Design ensembles: K re-weighted tables from one pass over the rows (new symbols within ABI 9, looked up by name; the
+ * rule is stated once in csrc/wgrt_visits.h).
+ *   lnscale  DEVICE float64 [K, C], 8-B aligned: design k's log-scales are lnscale + k * C.  Finite values only.
+ *   out      DEVICE float64 [K, n_slabs, W], ADDED to: table k is exactly what wgrt_visits_reweight adds with
+ *            lnscale + k * C -- per delivered row the same chain of fmas in ascending c (the kernel walks the row's
+ *            non-zero counts only, which gives the same bits), the same exp, q = rint(w * 2^32) * 2^-32 deposited
+ *            through the same window membership -- so on one device table k equals the single call's bit for bit, and
+ *            with lnscale row k all zero it is the launch's window table.  A row that deposits nothing in the single
+ *            call deposits nothing for any design.
+ *   wsums    NULL, or DEVICE int64 [K, 2, num_lmd], 8-B aligned, ADDED to, in quanta of 2^-32: every depositing row
+ *            adds rint(q * 2^32) to wsums[k][0][l] and rint(q * q * 2^32) to wsums[k][1][l], l = tile / (nx * ny).  A
+ *            value that is not below 2^62 (an overflowed weight) adds 2^62 instead.  Integer adds: exact, order-free
+ *            and additive over shards at any size.  The effective sample size of design k at wavelength l is
+ *            s1^2 / s2 of the two sums.
+ * A workgroup reads a row once for a chunk of 64 designs, a lane per design.  The deposits go either straight into out
+ * or into a stream-ordered scratch [n_slabs * W, 64] (n_slabs * W * 512 bytes, allocated and freed on `stream` by the
+ * call) that a second kernel adds into the chunk's tables; both give the same bits
+ * (wgrt_debug_set_reweight_layout).  K < 1, a NULL or misaligned lnscale and a misaligned wsums are
+ * WGRT_ERR_INVALID_ARGUMENT, as is whatever wgrt_visits_reweight refuses; a scene with more than 126 channels is
+ * WGRT_ERR_UNSUPPORTED (the chunk's log-scales must fit in 64 KiB of LDS).  n_rows == 0 is WGRT_OK without a launch.
+ * Asynchronous on stream.  _host is the twin over HOST pointers through the same header, the scene and the plan stated
+ * as for wgrt_visits_reweight_host.  wgrt_visit_wavelengths is the scene's num_lmd, the last extent of wsums (-1 for a
+ * NULL scene). */
+int32_t wgrt_visit_wavelengths(const wgrt_scene *scene);
+wgrt_status wgrt_visits_reweight_many(const wgrt_scene *scene, const wgrt_window_plan *plan, const uint32_t *counts,
+                                      const wgrt_visit_end *ends, int64_t n_rows, const double *lnscale, int32_t K,
+                                      double *out, int64_t *wsums, void *stream);
+wgrt_status wgrt_visits_reweight_many_host(int32_t nx, int32_t ny, int32_t num_lmd, int32_t n_channels,
+                                           const double *scene_ranges, const float *mask, int32_t ms, int32_t step_y,
+                                           int32_t step_x, const uint32_t *counts, const wgrt_visit_end *ends,
+                                           int64_t n_rows, const double *lnscale, int32_t K, double *out, int64_t *wsums);
 
 /* Polarisation of the delivered light: Stokes window tables (new symbols within ABI 9, looked up by name; the rule is
  * stated once in csrc/wgrt_stokes.h).

@@ -190,6 +190,12 @@ wgrt_status wgrt_debug_chain_report(const wgrt_chain *chain, wgrt_chain_report *
  * give the same map. */
 wgrt_status wgrt_debug_set_footprint_aggregate(int on);
 
+/* The two forms of wgrt_visits_reweight_many's deposits in one binary (process-wide; the A/B and the tests): 1 (the
+ * default) adds a chunk of 64 designs into a scratch [n_slabs * W, 64], where a wave's 64 adds are contiguous, and
+ * folds the scratch into the tables with a second kernel; 0 adds straight into out [K, n_slabs, W], a wave's adds on 64
+ * cache lines.  Both give the same tables and weight sums. */
+wgrt_status wgrt_debug_set_reweight_layout(int interleaved);
+
 #ifdef __cplusplus
 }
 #endif
