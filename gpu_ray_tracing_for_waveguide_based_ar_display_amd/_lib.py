@@ -45,7 +45,7 @@ EXPORTED_DEBUG = ("wgrt_debug_shadow", "wgrt_debug_scene_copy", "wgrt_debug_set_
                   "wgrt_debug_set_palette_cap", "wgrt_debug_scene_palette", "wgrt_debug_expected_replays",
                   "wgrt_debug_chain_report", "wgrt_debug_set_fused_run", "wgrt_debug_fused_run",
                   "wgrt_debug_fused_items_host", "wgrt_debug_set_footprint_aggregate",
-                  "wgrt_debug_set_reweight_layout")
+                  "wgrt_debug_set_reweight_layout", "wgrt_debug_trace_kernels", "wgrt_debug_last_trace_kernel")
 
 
 class WgrtError(RuntimeError):
@@ -424,6 +424,11 @@ def load():
         L.wgrt_debug_fused_items_host.restype = st
         L.wgrt_debug_fused_items_host.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
                                                   ctypes.c_int64, _vp, _vp, _vp, _i64]
+    if hasattr(L, "wgrt_debug_trace_kernels"):   # the kernel table's readouts: new symbols within ABI 9, bound by name
+        L.wgrt_debug_trace_kernels.restype = st
+        L.wgrt_debug_trace_kernels.argtypes = [_vp, ctypes.c_int64]
+        L.wgrt_debug_last_trace_kernel.restype = st
+        L.wgrt_debug_last_trace_kernel.argtypes = [_vp, _vp]
     L.wgrt_status_string.restype = ctypes.c_char_p
     L.wgrt_status_string.argtypes = [ctypes.c_int]
     L.wgrt_last_error.restype = ctypes.c_char_p
@@ -605,6 +610,13 @@ class Scene:
               "wgrt_debug_scene_palette")
         return {"distinct_words": n.value, "byte_grid": bool(g.value), "active": bool(a.value)}
 
+    def last_trace_kernel(self) -> tuple:
+        """``wgrt_debug_last_trace_kernel``: the kernel table entry ``(mode, byte, wide, fused, single, amp)`` the scene's
+        last launch looked up (``trace_kernels``' order); all -1 after a variant 1 launch, or before any."""
+        idx = np.empty(6, np.int32)
+        check(load().wgrt_debug_last_trace_kernel(self.handle, idx.ctypes.data), "wgrt_debug_last_trace_kernel")
+        return tuple(int(v) for v in idx)
+
     def eb_shape(self):
         if self.single_lambda:   # process_rays_kernel_pro's matrix_EB [NY, NX, 80, 120]
             return (self.ny, self.nx, 80, 120)
@@ -638,6 +650,15 @@ def locator_classify_host(geom, luts, xy: np.ndarray, cell_mm: float = 0.125) ->
           "wgrt_locator_classify_host")
     return out
 
+
+
+def trace_kernels(modes: int) -> np.ndarray:
+    """``wgrt_debug_trace_kernels``: which entries of the Jones kernel table are built, as a uint8 array
+    ``[modes, 2, 2, 2, 2, 2]`` over (mode, byte locator, 64-bit cells, fused, single wavelength, AMP); needs no GPU.
+    ``modes`` must be the library's count of trace modes (any other is refused)."""
+    out = np.full(int(modes) * 32, 255, np.uint8)
+    check(load().wgrt_debug_trace_kernels(out.ctypes.data, out.size), "wgrt_debug_trace_kernels")
+    return out.reshape(int(modes), 2, 2, 2, 2, 2)
 
 
 def set_byte_locator(on: bool) -> None:

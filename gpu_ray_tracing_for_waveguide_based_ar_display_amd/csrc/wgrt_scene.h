@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <string>
@@ -43,6 +44,10 @@ struct wgrt_scene {
     // ... and the most a chained step may use (wgrt_chain_*), by [byte locator][64-bit cells]: half the resident
     // grid less a margin (query_trace_grids)
     int jones_chain_grid[2][2] = {};
+    // the kernel table's entry the last launch looked up, as the flat index of [mode][byte locator][64-bit cells]
+    // [fused][single wavelength][AMP]; -1: none yet, or a grid / exact-lane kernel (wgrt_debug_last_trace_kernel;
+    // host-side, read by nothing else)
+    std::atomic<int> last_trace_kernel{-1};
     int64_t nonunitary_blocks = 0;  // Jones blocks whose branch matrices are not scaled-unitary (their launches
                                     // run the AMP instantiations: wgrt_jones_lane.h, the amplification step)
     // The automatic issue order's statistic (wgrt_order.h): per (wavelength, FoV) tile, the traces of the

@@ -1560,6 +1560,15 @@ const void *jones_kernel(TraceMode m, bool byte, bool wide, bool fused, bool sin
     static const JonesKernels table;
     return table.k[(int)m][byte][wide][fused][single][amp];
 }
+// An entry's position in the table's order (wgrt_debug_trace_kernels, wgrt_debug_last_trace_kernel).
+int jones_kernel_index(TraceMode m, bool byte, bool wide, bool fused, bool single, bool amp) {
+    return (((((int)m * 2 + byte) * 2 + wide) * 2 + fused) * 2 + single) * 2 + amp;
+}
+// ... and back: the six indices of position i
+void jones_kernel_entry(int i, int32_t idx[6]) {
+    idx[0] = i >> 5;
+    for (int k = 1; k < 6; ++k) idx[k] = i >> (5 - k) & 1;
+}
 
 }  // namespace
 
@@ -2171,7 +2180,9 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
     hipStream_t st = (hipStream_t)stream;
     const wgrt_debug_opts *dbg = c.dbg;
     const int num_iter = c.num_iter;
+    wgrt_scene *ms = const_cast<wgrt_scene *>(s);
     if (c.variant == 1) {
+        ms->last_trace_kernel.store(-1, std::memory_order_relaxed);   // (wgrt_debug_last_trace_kernel: no table entry)
         const int64_t blocks = (A.n_rays + 255) / 256;
         if (blocks > 0x7fffffff) return fail(WGRT_ERR_INVALID_ARGUMENT, "too many rays for one launch");
         switch (c.mode) {   // (the exact lane reads a replica launch's TraceArgs::win_reps itself: the plain kernel)
@@ -2190,10 +2201,11 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
     // the table's kernel; the amplification step only for scenes that need it (wgrt_jones_lane.h, "Amplification")
     const bool amp = s->nonunitary_blocks != 0, wide = c.variant == 9;
     const void *const kernel = jones_kernel(c.mode, c.byte, wide, num_iter > 1, c.single, amp);
+    ms->last_trace_kernel.store(jones_kernel_index(c.mode, c.byte, wide, num_iter > 1, c.single, amp),
+                                std::memory_order_relaxed);   // (wgrt_debug_last_trace_kernel)
     if (!kernel)   // (a planning bug: validate_launch and plan_auto_order route every launch to a built kernel)
         return fail(WGRT_ERR_UNSUPPORTED, "no trace kernel is built for mode " + std::to_string((int)c.mode) +
                                               " with this cell width / fused / single-wavelength / AMP combination");
-    wgrt_scene *ms = const_cast<wgrt_scene *>(s);
     wgrt_scene::Scratch *sc = nullptr;
     uint32_t epoch = 0, parity = 0;
     {
@@ -2955,6 +2967,26 @@ wgrt_status wgrt_debug_set_auto_order(int on) {
 
 wgrt_status wgrt_debug_set_byte_locator(int on) {
     g_byte_locator.store(on != 0, std::memory_order_relaxed);
+    return WGRT_OK;
+}
+
+wgrt_status wgrt_debug_trace_kernels(uint8_t *built, int64_t n) {
+    if (!built || n != (int64_t)kTraceModes * 32)
+        return fail(WGRT_ERR_INVALID_ARGUMENT, "built must hold the table's " + std::to_string(kTraceModes * 32) + " entries");
+    for (int i = 0; i < kTraceModes * 32; ++i) {
+        int32_t e[6];
+        jones_kernel_entry(i, e);
+        built[i] = jones_kernel((TraceMode)e[0], e[1], e[2], e[3], e[4], e[5]) != nullptr;
+    }
+    return WGRT_OK;
+}
+
+wgrt_status wgrt_debug_last_trace_kernel(const wgrt_scene *s, int32_t idx[6]) {
+    if (!s || !idx) return fail(WGRT_ERR_INVALID_ARGUMENT, "NULL scene / idx");
+    const int i = s->last_trace_kernel.load(std::memory_order_relaxed);
+    if (i >= 0) jones_kernel_entry(i, idx);
+    else
+        for (int k = 0; k < 6; ++k) idx[k] = -1;
     return WGRT_OK;
 }
 

@@ -196,6 +196,17 @@ wgrt_status wgrt_debug_set_footprint_aggregate(int on);
  * cache lines.  Both give the same tables and weight sums. */
 wgrt_status wgrt_debug_set_reweight_layout(int interleaved);
 
+/* The Jones-vector trace kernels the library holds (csrc/wgrt_trace.hip JonesKernels; host only: no GPU, no scene): the
+ * kernel table is indexed [mode][byte locator][64-bit cells][fused][single wavelength][AMP], modes in TraceMode's order
+ * (csrc/wgrt_trace_mode.h), every other index 0 or 1.  built[i] becomes 1 where entry i, in that order, is an
+ * instantiation the library was built with, and 0 where it is not; n must be the table's modes * 32 entries. */
+wgrt_status wgrt_debug_trace_kernels(uint8_t *built, int64_t n);
+/* The table entry the scene's last launch looked its kernel up at, as the six indices above; all -1 when that launch
+ * ran a grid or exact-lane kernel (variant 1), or when the scene has launched nothing.  Recorded on the host when the
+ * launch is issued (a fused chain of variant 1 launches records each), so it says which kernel was asked for, without
+ * waiting for it. */
+wgrt_status wgrt_debug_last_trace_kernel(const wgrt_scene *scene, int32_t idx[6]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 from gpu_ray_tracing_for_waveguide_based_ar_display_amd._lib import STAT, load  # noqa: E402
+from tests import _kernel_table as KT  # noqa: E402
 from tests._fixtures import GoldenCase  # noqa: E402
 from tests.test_gpu_parity import _config  # noqa: E402
 
@@ -141,6 +142,10 @@ def test_learn_then_ordered_launch_is_exact(dev, name, variant, chunk_rays):
     run = _Run(_case(name), dev, variant)
     dbg = dict(chunk_rays=chunk_rays) if chunk_rays else None
     per0, s0 = run.launch(debug=dbg)
+    # the table entry this test owns (tests/_kernel_table.py OWNED): the learning kernel over the byte locator
+    assert run.scene.palette_info()["active"]
+    learn = (KT.MODES.index("learn"), 1, int(variant == 9), 0, 0, 0)
+    assert run.scene.last_trace_kernel() == learn and learn in KT.OWNED
     assert int(s0[STAT.replayed]) == 0   # (an abandoned ray's trace is not counted into the table)
     tail = _tile_tail(run.scene)
     np.testing.assert_array_equal(tail, _expected_tail(run, per0))
@@ -167,7 +172,11 @@ def test_learning_launch_over_the_word_locator(dev, variant):
         per, s = run.launch(n_rays=N)
     finally:
         _lib.set_byte_locator(True)
+    # the table entry this test owns (tests/_kernel_table.py OWNED): the learning kernel over the word locator
+    learn = (KT.MODES.index("learn"), 0, int(variant == 9), 0, 0, 0)
+    assert run.scene.last_trace_kernel() == learn and learn in KT.OWNED
     per1, s1 = ref.launch(n_rays=N)
+    assert ref.scene.last_trace_kernel() == (-1,) * 6   # (variant 1: no table entry)
     np.testing.assert_array_equal(per, per1)
     np.testing.assert_array_equal(run.rng.cpu().numpy(), ref.rng.cpu().numpy())
     np.testing.assert_array_equal(run.eb.cpu().numpy(), ref.eb.cpu().numpy())

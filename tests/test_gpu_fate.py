@@ -48,11 +48,15 @@ def _oracle_run(key, make, launches):
     return _oracle[key]
 
 
-def _launches(c, dev, launches, variant, with_fate, per_ray=False, windows=False, grid=True, rays=None, **kw):
+def _launches(c, dev, launches, variant, with_fate, per_ray=False, windows=False, grid=True, rays=None, scene=None,
+              **kw):
     """``launches`` single launches of case ``c``; with ``with_fate`` each into a fresh fate buffer pre-filled with
-    0xFF.  Per launch: fate (or None), rng, grid, stats, bounces, window table (host copies)."""
+    0xFF.  Per launch: fate (or None), rng, grid, stats, bounces, window table (host copies).  ``scene``: the caller's,
+    left open."""
     wl = getattr(c, "wavelength", None)
-    scene = engine.Scene.from_geometry(c.geom, c.luts, wavelength=wl)
+    own = scene is None
+    if own:
+        scene = engine.Scene.from_geometry(c.geom, c.luts, wavelength=wl)
     trace = engine.trace_single if wl is not None else engine.trace_fullcolor
     rays = engine.rays_to_device(c.rays, dev) if rays is None else rays
     rng = torch.from_numpy(c.fresh_rng().view(np.int32)).to(dev)
@@ -73,7 +77,8 @@ def _launches(c, dev, launches, variant, with_fate, per_ray=False, windows=False
                         table=table.cpu().numpy() if windows else None))
     if plan is not None:
         plan.close()
-    scene.close()
+    if own:
+        scene.close()
     return out
 
 

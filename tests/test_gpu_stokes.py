@@ -20,6 +20,7 @@ torch = pytest.importorskip("torch")
 from gpu_ray_tracing_for_waveguide_based_ar_display_amd import _lib  # noqa: E402
 from gpu_ray_tracing_for_waveguide_based_ar_display_amd._lib import STAT  # noqa: E402
 from tests import _stokes as K  # noqa: E402
+from tests import _kernel_table as KT  # noqa: E402
 from tests._fixtures import GoldenCase  # noqa: E402
 from tests.test_gpu_parity import _config  # noqa: E402
 
@@ -53,7 +54,10 @@ _cases, _checked = {}, {}
 
 def _case(name):
     if name not in _cases:
-        _cases[name] = GoldenCase(name) if name in FIXTURES else _config(**_CONFIGS[name])
+        if name in KT.CASES:   # the kernel table's four cases (tests/_kernel_table.py), shared by every sink module
+            _cases[name] = KT.case(name)
+        else:
+            _cases[name] = GoldenCase(name) if name in FIXTURES else _config(**_CONFIGS[name])
     return _cases[name]
 
 
