@@ -44,7 +44,8 @@ EXPORTED_DEBUG = ("wgrt_debug_shadow", "wgrt_debug_scene_copy", "wgrt_debug_set_
                   "wgrt_debug_chain_plan", "wgrt_debug_chain_set_serial", "wgrt_debug_set_byte_locator",
                   "wgrt_debug_set_palette_cap", "wgrt_debug_scene_palette", "wgrt_debug_expected_replays",
                   "wgrt_debug_chain_report", "wgrt_debug_set_fused_run", "wgrt_debug_fused_run",
-                  "wgrt_debug_fused_items_host", "wgrt_debug_set_footprint_aggregate",
+                  "wgrt_debug_fused_items_host", "wgrt_debug_set_fused_taper", "wgrt_debug_fused_taper",
+                  "wgrt_debug_fused_partition_host", "wgrt_debug_set_footprint_aggregate",
                   "wgrt_debug_set_reweight_layout", "wgrt_debug_trace_kernels", "wgrt_debug_last_trace_kernel")
 
 
@@ -424,6 +425,14 @@ def load():
         L.wgrt_debug_fused_items_host.restype = st
         L.wgrt_debug_fused_items_host.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
                                                   ctypes.c_int64, _vp, _vp, _vp, _i64]
+    if hasattr(L, "wgrt_debug_set_fused_taper"):   # fused launches' taper: new symbols within ABI 9, bound by name
+        L.wgrt_debug_set_fused_taper.restype = st
+        L.wgrt_debug_set_fused_taper.argtypes = [ctypes.c_int]
+        L.wgrt_debug_fused_taper.restype = st
+        L.wgrt_debug_fused_taper.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        L.wgrt_debug_fused_partition_host.restype = st
+        L.wgrt_debug_fused_partition_host.argtypes = [ctypes.c_int64] + [ctypes.c_int] * 4 + [ctypes.c_int64] * 2 + \
+            [ctypes.POINTER(ctypes.c_int)] + [_vp] * 6 + [_i64]
     if hasattr(L, "wgrt_debug_trace_kernels"):   # the kernel table's readouts: new symbols within ABI 9, bound by name
         L.wgrt_debug_trace_kernels.restype = st
         L.wgrt_debug_trace_kernels.argtypes = [_vp, ctypes.c_int64]
@@ -703,6 +712,40 @@ def fused_items_host(n_chunks: int, num_iter: int, run: int, head: int):
           "wgrt_debug_fused_items_host")
     assert n.value < cap, "the head's queue ends before the buffer does"
     return chunk[:n.value], k0[:n.value], k1[:n.value]
+
+
+def set_fused_taper(t0: int = -1) -> None:
+    """``wgrt_debug_set_fused_taper``: the taper of fused launches, process-wide (A/B, tests): -1 the library's rule,
+    0 never, a power of two that first tail length (the launch's last runs are t0, t0 / 2, ..., 2, 1 traces)."""
+    check(load().wgrt_debug_set_fused_taper(int(t0)), "wgrt_debug_set_fused_taper")
+
+
+def fused_taper(num_iter: int, n_rays: int, handoff_bound: bool = False) -> int:
+    """``wgrt_debug_fused_taper``: the first tail length a fused launch of ``num_iter`` traces of ``n_rays`` rays runs
+    with now (0: none)."""
+    t0 = ctypes.c_int()
+    check(load().wgrt_debug_fused_taper(int(num_iter), int(n_rays), 1 if handoff_bound else 0, ctypes.byref(t0)),
+          "wgrt_debug_fused_taper")
+    return t0.value
+
+
+def fused_partition_host(n_chunks: int, num_iter: int, run: int, t0: int, head: int = 0, items: bool = True) -> dict:
+    """``wgrt_debug_fused_partition_host``: the run partition of a fused launch and ``head``'s work items under it, from
+    the code the kernels compile (no GPU needed): ``run_first`` (per run), ``trace_first``, ``trace_end`` (per
+    trace) and, with ``items``, the ``chunk``, ``first_trace``, ``end_trace`` arrays of every item, in order."""
+    n_it = int(num_iter)
+    cap = (int(n_chunks) + 1) * n_it + 1 if items else 0
+    n_runs = ctypes.c_int()
+    rf, tf, te = (np.zeros(n_it, np.int32) for _ in range(3))
+    chunk, k0, k1 = np.zeros(cap, np.int64), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+    n = ctypes.c_int64()
+    check(load().wgrt_debug_fused_partition_host(int(n_chunks), n_it, int(run), int(t0), int(head), 0, cap,
+                                                 ctypes.byref(n_runs), rf.ctypes.data, tf.ctypes.data, te.ctypes.data,
+                                                 chunk.ctypes.data, k0.ctypes.data, k1.ctypes.data,
+                                                 ctypes.byref(n)), "wgrt_debug_fused_partition_host")
+    assert not items or n.value < cap, "the head's queue ends before the buffer does"
+    return {"run_first": rf[:n_runs.value], "trace_first": tf, "trace_end": te,
+            "chunk": chunk[:n.value], "first_trace": k0[:n.value], "end_trace": k1[:n.value]}
 
 
 def set_palette_cap(cap: int = 256) -> None:

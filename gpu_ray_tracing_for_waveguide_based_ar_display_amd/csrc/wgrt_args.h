@@ -127,9 +127,11 @@ struct TraceArgs {
     int64_t win_rep_stride;
     int32_t win_reps;
     // fused launches: the run length, the consecutive traces of a ray one work item covers and one lane keeps the
-    // ray for (wgrt_items.h; a power of two, 1: an item per trace).  In the word that padded the struct, so every
-    // other field and the kernel parameters behind it keep their places in the kernarg segment.
-    int32_t fused_run;
+    // ray for (wgrt_items.h; a power of two, 1: an item per trace), and the first tail length of the launch's taper
+    // (a power of two below the run, 0: none) -- together the launch's run partition.  Both in the word that padded
+    // the struct, so every other field and the kernel parameters behind it keep their places in the kernarg segment.
+    int16_t fused_run;
+    int16_t fused_t0;
     // footprint maps (wgrt_trace_footprint; wgrt_footprint.h): with fp_map, every counted draw of the bounce loop adds
     // to the int64 map [nl, 9, fp.ny_cells, fp.nx_cells] under the plan fp (by value).  fp_seen: one word per
     // replay-list entry of the launch scratch, the draws the Jones-vector lane had counted when it abandoned the

@@ -610,12 +610,22 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
     // ended the launch 60 us after the first (striping: -6 % per single launch on C3) -- while
     // a stripe's rays still share their tiles in that die's L2.
     const int64_t ns = (n_chunks + kStripe - 1) / kStripe, last = n_chunks - (ns - 1) * kStripe;
-    // (wgrt_items.h: the mapping, shared with the host.)  FUSED: an item is a run of A.fused_run consecutive traces
-    // of its chunk's rays, k the run's first trace
+    // (wgrt_items.h: the mapping, shared with the host.)  FUSED: an item is a run of consecutive traces of its
+    // chunk's rays, k the run's first trace; the runs are the partition of [0, n_iter) that (n_iter, run, t0) fix --
+    // runs of A.fused_run, and with a taper (t0 > 0) shorter ones at the launch's end.  Only the dequeue asks the
+    // partition's functions: it packs the run's bounds into the lanes' trace number (the run word), and every site
+    // below that asks where a run ends or began unpacks that word.
     const uint32_t run = FUSED ? (uint32_t)A.fused_run : 1u;
-    const int64_t n_runs = FUSED ? (n_iter + run - 1) / run : 1;
+    const uint32_t t0 = FUSED ? (uint32_t)A.fused_t0 : 0u;
+    const int64_t n_runs = FUSED ? (int64_t)part_runs((uint32_t)n_iter, run, t0) : 1;
     auto decode = [&](int x, int64_t q, int64_t &c, uint32_t &k) -> bool {
-        return item_decode<FUSED>(ns, last, n_runs, run, x, q, c, k);
+        if constexpr (FUSED) {
+            // (the lanes that take the item's rays carry its run as a run word: the one place a boundary is derived)
+            const bool got = item_decode<true>(ns, last, n_runs, (uint32_t)n_iter, run, t0, x, q, c, k);
+            if (got) k = run_word(k, run_end(k, (uint32_t)n_iter, run, t0));
+            return got;
+        }
+        else return item_decode<false>(ns, last, n_runs, 1u, run, 0u, x, q, c, k);
     };
     // this wave's two LDS buffers of staged ray columns (wgrt_jones_lane.h stage_chunk): a refill takes
     // rays of at most two chunks, the one being used up and the next
@@ -646,17 +656,19 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
     // skipped (bad ray / ray already handed to the replay)
     auto start = [&]() {
         uint64_t w = 0;
+        uint32_t lk = L.k;   // the trace; FUSED: L.k is the lane's run word (wgrt_items.h)
+        if constexpr (FUSED) lk = word_trace(L.k);
         const uint32_t oc = L.i - sbase;
         const bool in_cur = oc < 64u;
         const bool ok = lane_load_staged(sbufs + (in_cur ? sb : sb ^ 1) * (kStageCols * 64),
                                          (int)(in_cur ? oc : L.i - sbase_prev), L.i, L,
-                                         (CHAIN || (FUSED && L.k > 0)) ? KA(rng64) + L.i : nullptr, &w);
+                                         (CHAIN || (FUSED && lk > 0)) ? KA(rng64) + L.i : nullptr, &w);
         waiting = false;
         active = false;
         if (__builtin_expect(!ok, 0)) {
             // FUSED: once per trace the item covers (a bad ray has no granule: nothing is handed on)
             ++tot_bad;
-            if constexpr (FUSED) tot_bad += run_end(L.k, run, (uint32_t)n_iter) - L.k - 1u;
+            if constexpr (FUSED) tot_bad += word_end(L.k) - lk - 1u;
             if (FATE) KA(fate)[L.i] = 0;   // no trace
             return;
         }
@@ -666,9 +678,9 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             if (run > 1u)
                 keep_slot(sbufs + (in_cur ? sb : sb ^ 1) * (kStageCols * 64), (int)(in_cur ? oc : L.i - sbase_prev),
                           rslot_of());
-        if (FUSED && L.k > 0) {
+        if (FUSED && lk > 0) {
             const uint32_t tag = (uint32_t)w;
-            if (tag == iter_tag(A.iter_epoch, L.k, false)) {
+            if (tag == iter_tag(A.iter_epoch, lk, false)) {
                 L.r.s = (uint32_t)(w >> 32);
                 if constexpr (FUSED) rslot_of()[kRunS0 * 64] = L.r.s;
             } else if ((tag >> 8) == ((A.iter_epoch << 1) | 1u)) {
@@ -736,13 +748,15 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             if (st) atomicAdd((unsigned long long *)&st->bounces, (unsigned long long)tot_b);
             tot_b = 0;
         }
-        if (FUSED && (int64_t)L.k + 1 < n_iter) {
-            const uint64_t hand = ((uint64_t)L.r.s << 32) | iter_tag(A.iter_epoch, L.k + 1, false);
-            // (only a run's last trace comes here: L.k + 1 is the next run's first trace)
-            uint32_t k0 = L.k, s_k0 = L.s0;
+        uint32_t lk = L.k;   // the trace; FUSED: L.k is the lane's run word
+        if constexpr (FUSED) lk = word_trace(L.k);
+        if (FUSED && (int64_t)lk + 1 < n_iter) {
+            const uint64_t hand = ((uint64_t)L.r.s << 32) | iter_tag(A.iter_epoch, lk + 1, false);
+            // (only a run's last trace comes here: lk + 1 is the next run's first trace)
+            uint32_t k0 = lk, s_k0 = L.s0;
             if constexpr (FUSED) {   // (compile-time, like every use of the run's state in these lambdas: a single
                                      // launch's closures capture what the parent's did)
-                k0 = L.k & ~(run - 1u);
+                k0 = word_first(L.k);
                 if (k0 > 0) s_k0 = rslot_of()[kRunS0 * 64];
             }
             if (k0 > 0) {
@@ -910,7 +924,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             if (__builtin_expect(next == kUncertain, 0)) {
                 // abandoned with no side effect; epilogue_kernel re-traces it from this iteration on,
                 // so later iterations skip the ray
-                __hip_atomic_store(KA(rng64) + L.i, ((uint64_t)L.s0 << 32) | iter_tag(A.iter_epoch, L.k, true),
+                __hip_atomic_store(KA(rng64) + L.i, ((uint64_t)L.s0 << 32) | iter_tag(A.iter_epoch, word_trace(L.k), true),
                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 record_abandoned<M>(K, L.i, 0u);
                 active = false;
@@ -918,7 +932,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
                 // inside a run the ray starts its next trace on this lane, at the next pass's restart site; a run's
                 // last trace publishes at once (the hand-off would wait a pass)
                 if constexpr (FUSED) {
-                    if (L.k + 1u < run_end(L.k, run, (uint32_t)n_iter)) blk = kAgain, active = false;
+                    if (word_trace(L.k) + 1u < word_end(L.k)) blk = kAgain, active = false;
                     else retire();
                 } else {
                     retire();
@@ -1039,8 +1053,10 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             entry = false;
             if (!FUSED) fin |= blk == kDie;
             else if (blk == kDie) {
-                if (L.k + 1u < run_end(L.k, run, (uint32_t)n_iter)) blk = kAgain, active = false;
-                else retire();
+                if constexpr (FUSED) {
+                    if (word_trace(L.k) + 1u < word_end(L.k)) blk = kAgain, active = false;
+                    else retire();
+                }
             }
         }
         if (FUSED && blk == kAgain) {
@@ -1054,7 +1070,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
                 if (st) atomicAdd((unsigned long long *)&st->bounces, (unsigned long long)tot_b);
                 tot_b = 0;
             }
-            ++L.k;
+            ++L.k;   // (the run word's low byte: a trace inside a run is below 255)
             lane_restart(rslot_of(), L);
             L.s0 = L.r.s;
             active = true;
@@ -1072,7 +1088,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
             // start() that found it not ready
             const uint64_t w = __hip_atomic_load(KA(rng64) + L.i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const uint32_t tag = (uint32_t)w;
-            if (tag == iter_tag(A.iter_epoch, L.k, false)) {
+            if (tag == iter_tag(A.iter_epoch, word_trace(L.k), false)) {
                 L.r.s = (uint32_t)(w >> 32);
                 L.s0 = L.r.s;
                 rslot_of()[kRunS0 * 64] = L.r.s;
@@ -1092,7 +1108,7 @@ __device__ __forceinline__ void jones_body(const TraceArgs &A, const KArgs &K, c
                 // value just polled: a hand-off that arrived since is taken by the next pass's poll instead
                 uint64_t seen = w;
                 if (__hip_atomic_compare_exchange_strong(KA(rng64) + L.i, &seen,
-                                                         (uint64_t)iter_tag(A.iter_epoch, L.k, true), __ATOMIC_RELAXED,
+                                                         (uint64_t)iter_tag(A.iter_epoch, word_trace(L.k), true), __ATOMIC_RELAXED,
                                                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
                     waiting = false;
                     ++tot_giveup;
@@ -1907,6 +1923,33 @@ int fused_run_for(int num_iter, const wgrt_debug_opts *dbg) {
     return run;
 }
 
+// wgrt_debug_set_fused_taper: -1 the rule below, 0 never, a power of two: that first tail length.
+std::atomic<int> g_fused_taper{-1};
+
+// The first tail length t0 of a fused launch of num_iter traces in runs of `run` (wgrt_items.h: the launch's last
+// 2 t0 - 1 traces are runs of t0, ..., 2, 1; TraceArgs::fused_t0).  The rule is what the same-binary sweep left
+// (profiles/fused_taper_sweep.jsonl): a launch whose run length is automatic tapers from half its
+// run, t0 = run / 2, where that was measured faster and nowhere else --
+//   * runs of 8 or more (num_iter >= 32): at 8 and 20 traces (runs of 2 and 4) the taper read -1.0 to +0.3 %;
+//   * batches of kTaperMinChunks to kTaperMaxChunks chunks: at 39 traces C3 (21,168 chunks) gained 1.2-1.6 %, C2
+//     and the eighth C3 shard (2,646) lost 2.4-3.3 % -- a level of so few items has no bulk for the level before
+//     to drain under, and pays its hand-offs -- and C4 (84,672), whose drain is a small share of a launch four
+//     times as long, read -0.1 to -0.3 %.  The bounds are the geometric means between the measured sizes.
+// An explicit run length means uniform runs, as it always has.  An explicit taper wins over both, cut to below the
+// run (a partition needs t0 < run).
+constexpr int kTaperMinRun = 8;
+constexpr int64_t kTaperMinChunks = 7500, kTaperMaxChunks = 42000;
+int fused_taper_for(int64_t n_chunks, int run) {
+    const int set = g_fused_taper.load(std::memory_order_relaxed);
+    int t0 = 0;
+    if (set > 0) t0 = set;
+    else if (set < 0 && g_fused_run.load(std::memory_order_relaxed) == 0 && run >= kTaperMinRun &&
+             n_chunks >= kTaperMinChunks && n_chunks <= kTaperMaxChunks)
+        t0 = run / 2;
+    while (t0 >= run) t0 /= 2;
+    return t0;
+}
+
 // wgrt_debug_set_auto_order: the automatic issue order (and its learning launches) on / off, process-wide.
 std::atomic<int> g_auto_order{1};
 
@@ -2144,6 +2187,7 @@ TraceArgs fill_args(const wgrt_scene *s, const wgrt_rays *rays, int64_t n_rays, 
     A.timeline_waves = c.mode == TraceMode::kTimeline ? dbg->timeline_waves : 0;
     A.n_iter = 1;
     A.fused_run = 1;
+    A.fused_t0 = 0;
     return A;
 }
 
@@ -2216,7 +2260,8 @@ wgrt_status dispatch(const wgrt_scene *s, TraceArgs &A, int64_t grid, int item, 
     }
     if (num_iter > 1) {
         A.n_iter = num_iter;
-        A.fused_run = fused_run_for(num_iter, dbg);
+        A.fused_run = (int16_t)fused_run_for(num_iter, dbg);
+        A.fused_t0 = (int16_t)fused_taper_for((A.n_rays + kChunk - 1) / kChunk, A.fused_run);
         A.rng64 = sc->rng64;
         A.iter_epoch = epoch;
         A.handoff_wait_ticks = (dbg && dbg->handoff_wait_ticks) ? dbg->handoff_wait_ticks
@@ -3016,9 +3061,56 @@ wgrt_status wgrt_debug_fused_items_host(int64_t n_chunks, int num_iter, int run,
     int64_t k = 0;
     for (; k < n; ++k) {
         uint32_t k0 = 0;
-        if (!item_decode<true>(ns, last, n_runs, (uint32_t)run, head, q0 + k, chunk[k], k0)) break;
+        if (!item_decode<true>(ns, last, n_runs, (uint32_t)num_iter, (uint32_t)run, 0u, head, q0 + k, chunk[k], k0)) break;
         first_trace[k] = (int32_t)k0;
-        end_trace[k] = (int32_t)run_end(k0, (uint32_t)run, (uint32_t)num_iter);
+        end_trace[k] = (int32_t)run_end(k0, (uint32_t)num_iter, (uint32_t)run, 0u);
+    }
+    *count = k;
+    return WGRT_OK;
+}
+
+wgrt_status wgrt_debug_set_fused_taper(int t0) {
+    if (t0 < -1 || t0 >= kMaxFusedRun || (t0 > 0 && (t0 & (t0 - 1)) != 0))
+        return fail(WGRT_ERR_INVALID_ARGUMENT, "the taper is -1 (the rule), 0 (none) or a power of two below " +
+                                                   std::to_string(kMaxFusedRun));
+    g_fused_taper.store(t0, std::memory_order_relaxed);
+    return WGRT_OK;
+}
+
+wgrt_status wgrt_debug_fused_taper(int num_iter, int64_t n_rays, int handoff_bound, int *t0) {
+    if (num_iter < 1 || n_rays < 0 || !t0) return fail(WGRT_ERR_INVALID_ARGUMENT, "need num_iter >= 1, n_rays >= 0 and t0");
+    wgrt_debug_opts d{};
+    d.handoff_wait_ticks = handoff_bound ? 1u : 0u;
+    *t0 = num_iter > 1 ? fused_taper_for((n_rays + kChunk - 1) / kChunk, fused_run_for(num_iter, &d)) : 0;
+    return WGRT_OK;
+}
+
+wgrt_status wgrt_debug_fused_partition_host(int64_t n_chunks, int num_iter, int run, int t0, int head, int64_t q0,
+                                            int64_t n, int32_t *n_runs, int32_t *run_first_trace, int32_t *trace_first,
+                                            int32_t *trace_end, int64_t *chunk, int32_t *first_trace,
+                                            int32_t *end_trace, int64_t *count) {
+    if (n_chunks < 1 || num_iter < 1 || num_iter > 255 || run < 1 || run > kMaxFusedRun || (run & (run - 1)) != 0 ||
+        t0 < 0 || t0 >= run || (t0 & (t0 - 1)) != 0 || head < 0 || head >= kItemHeads || q0 < 0 || n < 0 || !n_runs ||
+        !run_first_trace || !trace_first || !trace_end || !count ||
+        (n > 0 && (!chunk || !first_trace || !end_trace)))
+        return fail(WGRT_ERR_INVALID_ARGUMENT, "bad partition query");
+    const uint32_t ni = (uint32_t)num_iter, S = (uint32_t)run, t = (uint32_t)t0;
+    const uint32_t nr = part_runs(ni, S, t);
+    *n_runs = (int32_t)nr;
+    for (uint32_t r = 0; r < nr && r < ni; ++r) run_first_trace[r] = (int32_t)part_run_first(r, ni, S, t);
+    for (uint32_t k = 0; k < ni; ++k) {
+        uint32_t f = 0, e = 0;
+        part_span(k, ni, S, t, f, e);
+        trace_first[k] = (int32_t)f;
+        trace_end[k] = (int32_t)e;
+    }
+    const int64_t ns = (n_chunks + kItemStripe - 1) / kItemStripe, last = n_chunks - (ns - 1) * kItemStripe;
+    int64_t k = 0;
+    for (; k < n; ++k) {
+        uint32_t k0 = 0;
+        if (!item_decode<true>(ns, last, (int64_t)nr, ni, S, t, head, q0 + k, chunk[k], k0)) break;
+        first_trace[k] = (int32_t)k0;
+        end_trace[k] = (int32_t)run_end(k0, ni, S, t);
     }
     *count = k;
     return WGRT_OK;

@@ -114,6 +114,29 @@ wgrt_status wgrt_debug_fused_run(int num_iter, int handoff_bound, int *run);
  * positions before the head's queue ends (<= n). */
 wgrt_status wgrt_debug_fused_items_host(int64_t n_chunks, int num_iter, int run, int head, int64_t q0, int64_t n,
                                         int64_t *chunk, int32_t *first_trace, int32_t *end_trace, int64_t *count);
+/* The taper of fused launches (csrc/wgrt_items.h): with a first tail length t0 -- a power of two below the run length
+ * -- the launch's last 2 t0 - 1 traces are runs of t0, t0 / 2, ..., 2, 1 traces, and the runs before them are aligned
+ * from there backwards, so the launch drains like a single trace.  A scheduling detail like the run length: results
+ * do not depend on it.  Process-wide, for the same-binary A/B and the tests: -1 (the default) is the library's
+ * rule -- a launch whose run length is automatic tapers from half its run where that was measured faster (runs of 8
+ * or more, batches of 7,500 to 42,000 64-ray chunks), an explicit run length
+ * (wgrt_debug_set_fused_run) means uniform runs; 0 never tapers; a power of two is that t0 for every fused launch,
+ * also beside an explicit run length (halved until it is below the launch's run).  Anything else is
+ * WGRT_ERR_INVALID_ARGUMENT. */
+wgrt_status wgrt_debug_set_fused_taper(int t0);
+/* The first tail length a fused launch of num_iter traces of n_rays rays runs with now (0: no taper; handoff_bound
+ * as above). */
+wgrt_status wgrt_debug_fused_taper(int num_iter, int64_t n_rays, int handoff_bound, int *t0);
+/* The run partition of a fused launch and its work items under it, from the code the kernels compile (needs no GPU):
+ * num_iter (1 .. 255) traces in runs of `run` with first tail length t0 (0, or a power of two below run).
+ * *n_runs is the number of runs and run_first_trace[r] the first trace of run r, filled for r < *n_runs only;
+ * trace_first[k] and trace_end[k] (exclusive) are the run that holds trace k, as the dequeue derives it.  The
+ * caller gives all three arrays num_iter entries (a launch has at most num_iter runs).  The item arrays are
+ * wgrt_debug_fused_items_host's, under this partition. */
+wgrt_status wgrt_debug_fused_partition_host(int64_t n_chunks, int num_iter, int run, int t0, int head, int64_t q0,
+                                            int64_t n, int32_t *n_runs, int32_t *run_first_trace, int32_t *trace_first,
+                                            int32_t *trace_end, int64_t *chunk, int32_t *first_trace,
+                                            int32_t *end_trace, int64_t *count);
 /* The most distinct cell words a scene created from now on may have and still get a byte grid (0 .. 256,
  * larger values mean 256; default 256): a test forces the word-form fallback with it. */
 wgrt_status wgrt_debug_set_palette_cap(int cap);

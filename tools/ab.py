@@ -35,6 +35,9 @@ if "byte" in _sw:
 if "run" in _sw:   # %run=0|1|2|4|...: the run length of fused launches (wgrt_debug_set_fused_run)
     from gpu_ray_tracing_for_waveguide_based_ar_display_amd import _lib
     _lib.set_fused_run(int(_sw["run"]))
+if "taper" in _sw:   # %taper=-1|0|1|2|...: the first tail length of fused launches (wgrt_debug_set_fused_taper)
+    from gpu_ray_tracing_for_waveguide_based_ar_display_amd import _lib
+    _lib.set_fused_taper(int(_sw["taper"]))
 sc = Scene.from_geometry(g, L, **json.loads(os.environ.get("AB_SCENE") or "{}"))
 lk = json.loads(os.environ.get("AB_LAUNCH") or "{}")
 _dbg = {k[4:]: lk.pop(k) for k in [k for k in lk if k.startswith("dbg_")]}   # +dbg_<field>=v: wgrt_debug_opts

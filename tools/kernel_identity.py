@@ -15,14 +15,15 @@ import re
 import subprocess
 import sys
 
-MODES = ["plain", "tl", "learn", "chain", "fate", "reps", "ev", "fp"]   # wgrt::TraceMode's order
+MODES = ["plain", "tl", "learn", "chain", "fate", "reps", "ev", "fp", "hits", "paths", "visits",
+         "stokes"]   # wgrt::TraceMode's order
 CELL = {"unsigned int": 32, "unsigned long": 64}
 
 
 def key_of(name, sym):
     """The instantiation a demangled kernel name stands for."""
     b = lambda s: s.strip() == "true"
-    m = re.search(r"trace_jones_(mode|learn)_kernel<wgrt::(Byte)?LocatorT<([^>]*)> ?(?:, \(wgrt::TraceMode\)(\d), (\w+), (\w+), (\w+))?>", name)
+    m = re.search(r"trace_jones_(mode|learn)_kernel<wgrt::(Byte)?LocatorT<([^>]*)> ?(?:, \(wgrt::TraceMode\)(\d+), (\w+), (\w+), (\w+))?>", name)
     if m:   # the mode as a template argument
         mode = MODES[int(m.group(4))] if m.group(1) == "mode" else "learn"
         return (mode, bool(m.group(2)), CELL[m.group(3).strip()], *[b(m.group(k) or "false") for k in (5, 6, 7)])

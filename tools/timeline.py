@@ -4,8 +4,9 @@
 Runs the bench workload (C3 by default), records per wave: start, queue-exhausted and end
 times, passes and lane-passes, and prints a summary: launch span, when the work queue ran dry,
 the drain (tail) after it, lane occupancy before and after, per-XCD end times.
-Usage: python tools/timeline.py [--config C3] [--num-iter 1] [--variant 0] [--shard N] [--run S] [--out FILE]
+Usage: python tools/timeline.py [--config C3] [--num-iter 1] [--variant 0] [--shard N] [--run S] [--taper T] [--out FILE]
 --run S: the run length of a fused launch (wgrt_debug_set_fused_run; default: the library's rule).
+--taper T: the first tail length of a fused launch (wgrt_debug_set_fused_taper; 0: none; default: the library's rule).
 --shard N: rank 0's interleaved FoV x wavelength shard of N (distributed.make_shard), i.e. what one GPU
 of the N-GPU strong-scaling run traces.  Single traces use the product's grid rule (wgrt_launch_opts
 grid_sqrt_k: ceil(6.5 sqrt(work items)) workgroups), like the launches the bench times.
@@ -34,6 +35,7 @@ def main():
                     help="chunk issue order: ascending, or long-lived tiles first (from a previous launch)")
     ap.add_argument("--shard", type=int, default=1, help="trace rank 0's interleaved shard of N ranks")
     ap.add_argument("--run", type=int, default=None, help="run length of fused launches (wgrt_debug_set_fused_run)")
+    ap.add_argument("--taper", type=int, default=None, help="first tail length (wgrt_debug_set_fused_taper; 0: none)")
     a = ap.parse_args()
     import torch
     from gpu_ray_tracing_for_waveguide_based_ar_display_amd.configs import CONFIGS, build_inputs
@@ -47,6 +49,9 @@ def main():
     if a.run is not None:
         from gpu_ray_tracing_for_waveguide_based_ar_display_amd import _lib
         _lib.set_fused_run(a.run)
+    if a.taper is not None:
+        from gpu_ray_tracing_for_waveguide_based_ar_display_amd import _lib
+        _lib.set_fused_taper(a.taper)
     scene = Scene.from_geometry(geom, luts)
     shard = make_shard(nx, ny, len(lam), R, a.shard, 0)
     rays, rng = hip_shard_builder(pts, nx, ny, lam, R, dev)(shard)
@@ -82,6 +87,8 @@ def main():
              "start_us": [float(np.percentile(us(start), q)) for q in (0, 50, 100)],
              "exhausted_us": [float(np.percentile(us(exh), q)) for q in (0, 10, 50, 90, 100)],
              "end_us": [float(np.percentile(us(end), q)) for q in (0, 10, 50, 90, 99, 100)],
+             # the launch's end: how long the last wave ends after the median wave's queue ran dry
+             "end_after_median_dry_us": float(us(end).max() - np.percentile(us(exh), 50)),
              "passes_per_wave": [float(np.percentile(passes, q)) for q in (0, 50, 100)],
              "mean_active_lanes_per_pass": float(lanes.sum() / max(passes.sum(), 1)),
              "bulk_us_per_pass": float(np.median(us(exh) / np.maximum(p_exh, 1))),
@@ -111,7 +118,7 @@ def main():
             from gpu_ray_tracing_for_waveguide_based_ar_display_amd._lib import loaded_path
             with open(loaded_path(), "rb") as lf:
                 sha = hashlib.sha256(lf.read()).hexdigest()[:16]
-            json.dump({"config": a.config, "num_iter": a.num_iter, "shard_of": a.shard, "fused_run": a.run, "lib_sha16": sha,
+            json.dump({"config": a.config, "num_iter": a.num_iter, "shard_of": a.shard, "fused_run": a.run, "fused_taper": a.taper, "lib_sha16": sha,
                        "runs": res}, f, indent=1)
 
 
