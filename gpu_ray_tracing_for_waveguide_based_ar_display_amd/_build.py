@@ -17,9 +17,10 @@ LIB = os.path.join(PKG, "libwgrt.so")
 OPS_LIB = os.path.join(PKG, "_wgrt_torch.so")
 OPS_SOURCE = "wgrt_torch.cpp"
 SOURCES = ["wgrt_trace.hip", "wgrt_scene.hip", "wgrt_rays.hip", "wgrt_shadow.hip", "wgrt_eyebox.hip", "wgrt_fate.hip",
-           "wgrt_hits.hip", "wgrt_paths.hip", "wgrt_visits.hip",
+           "wgrt_hits.hip", "wgrt_paths.hip", "wgrt_visits.hip", "wgrt_sources.hip",
            "wgrt_scene_build.cpp", "wgrt_eyebox_host.cpp", "wgrt_fate_host.cpp",
-           "wgrt_footprint_host.cpp", "wgrt_hits_host.cpp", "wgrt_paths_host.cpp", "wgrt_visits_host.cpp"]
+           "wgrt_footprint_host.cpp", "wgrt_hits_host.cpp", "wgrt_paths_host.cpp", "wgrt_visits_host.cpp",
+           "wgrt_sources_host.cpp"]
 ARCH = os.environ.get("WGRT_OFFLOAD_ARCH", "gfx950")
 
 # -ffp-contract=off: the reference never fuses a*b+c (Python float semantics); keeping

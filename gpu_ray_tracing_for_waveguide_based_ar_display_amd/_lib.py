@@ -38,7 +38,8 @@ EXPORTED = ("wgrt_scene_create", "wgrt_scene_create_ex", "wgrt_scene_destroy", "
             "wgrt_visits_sensitivity", "wgrt_visits_reweight", "wgrt_visits_sensitivity_host",
             "wgrt_visits_reweight_host", "wgrt_visit_channel_host", "wgrt_visit_channel_count_host",
             "wgrt_trace_stokes", "wgrt_stokes_quanta_host", "wgrt_visits_reweight_many",
-            "wgrt_visits_reweight_many_host", "wgrt_visit_wavelengths")
+            "wgrt_visits_reweight_many_host", "wgrt_visit_wavelengths", "wgrt_hits_source_counts",
+            "wgrt_hits_source_counts_host", "wgrt_hits_reweight_sources", "wgrt_hits_reweight_sources_host")
 EXPORTED_DEBUG = ("wgrt_debug_shadow", "wgrt_debug_scene_copy", "wgrt_debug_set_auto_order",
                   "wgrt_debug_get_auto_order", "wgrt_debug_get_tile_tail", "wgrt_debug_order_host",
                   "wgrt_debug_chain_plan", "wgrt_debug_chain_set_serial", "wgrt_debug_set_byte_locator",
@@ -401,6 +402,17 @@ def load():
         L.wgrt_visit_wavelengths.argtypes = [_vp]
         L.wgrt_debug_set_reweight_layout.restype = st
         L.wgrt_debug_set_reweight_layout.argtypes = [ctypes.c_int]
+    if hasattr(L, "wgrt_hits_reweight_sources"):   # source what-ifs: new symbols within ABI 9, by name
+        i32, i64 = ctypes.c_int32, ctypes.c_int64
+        L.wgrt_hits_source_counts.restype = st
+        L.wgrt_hits_source_counts.argtypes = [_vp, _vp, i64, i64, _vp, _vp]
+        L.wgrt_hits_source_counts_host.restype = st
+        L.wgrt_hits_source_counts_host.argtypes = [i32, i32, i32, _vp, i64, i64, _vp]
+        L.wgrt_hits_reweight_sources.restype = st
+        L.wgrt_hits_reweight_sources.argtypes = [_vp, _vp, _vp, i64, _vp, i64, i32, _vp, _vp, _vp]
+        L.wgrt_hits_reweight_sources_host.restype = st
+        L.wgrt_hits_reweight_sources_host.argtypes = [i32, i32, i32, _vp, _vp, i32, i32, i32, _vp, i64, _vp, i64, i32, _vp,
+                                                      _vp]
     if hasattr(L, "wgrt_trace_stokes"):   # the Stokes window tables: new symbols within ABI 9, by name
         L.wgrt_trace_stokes.restype = st
         L.wgrt_trace_stokes.argtypes = L.wgrt_trace_opts.argtypes + [_vp, _vp, _vp]

@@ -21,6 +21,7 @@
 
 #include "../../include/wgrt.h"
 #include "../../include/wgrt_debug.h"
+#include "wgrt_many_fold.h"
 #include "wgrt_scene.h"
 #include "wgrt_visits.h"
 
@@ -87,9 +88,9 @@ __global__ __launch_bounds__(kVisitsThreads) void visits_reweight_kernel(const u
 //     scalar register: every lane runs the same chain of single fmas on its own design's column.
 //   * The deposits.  DIRECT adds into out[k][e]: the wave's 64 adds go to 64 tables, 64 cache lines.  INTERLEAVED
 //     adds into a chunk's scratch [n_slabs * W, 64], where they are 512 contiguous bytes, and visits_many_fold_kernel
-//     then adds the scratch into the chunk's tables through an LDS transpose and zeroes it for the next chunk.  Both
-//     are sums on the 2^-32 grid, so both give the same bits (wgrt_debug_set_reweight_layout picks; DESIGN.md 4.13 has
-//     the timings).
+//     (wgrt_many_fold.h) then adds the scratch into the chunk's tables through an LDS transpose and zeroes it for the
+//     next chunk.  Both are sums on the 2^-32 grid, so both give the same bits (wgrt_debug_set_reweight_layout picks;
+//     DESIGN.md 4.13 has the timings).
 //   * The weight sums stay in registers while a wave's rows share a wavelength (rows are in ray order, so they nearly
 //     always do) and go to wsums as plain 64-bit vector atomics when it changes and at the end: a few per workgroup,
 //     design and wavelength.
@@ -97,9 +98,7 @@ __global__ __launch_bounds__(kVisitsThreads) void visits_reweight_kernel(const u
 // Writes: entries below n_slabs * W (window_visit over a guarded offset) of tables k < K, hence below
 // out + K * n_slabs * W; scratch entries below n_slabs * W * 64; wsums[(k * 2 + i) * nl + l] with l < nl because the
 // row's tile index was checked against the scene.
-constexpr int kManyDesigns = 64;                 // designs per chunk: one per lane
-constexpr int kManyStride = kManyDesigns + 1;    // LDS doubles per channel
-constexpr int kManyRows = 64;                    // rows per workgroup
+// (kManyDesigns, kManyStride, kManyRows and the fold kernel: wgrt_many_fold.h, shared with wgrt_sources.hip)
 constexpr size_t kManyLdsLimit = 64 * 1024;
 
 __device__ __forceinline__ void many_flush(int64_t *wsums, int64_t k, int nl, int l, unsigned long long s1,
@@ -165,31 +164,6 @@ __global__ __launch_bounds__(kVisitsThreads) void visits_reweight_many_kernel(
         }
     }
     if (wsums && mine && cur_l >= 0) many_flush(wsums, k, nl, cur_l, s1, s2);
-}
-
-// The interleaved form's second step: out[k0 + j][e] += scratch[e][j] for the chunk's nk designs, 64 entries per
-// workgroup through an LDS tile (reads along j, writes along e, both contiguous), and scratch is left zero.  Plain
-// adds: a call's kernels are ordered on its stream and nothing else writes the tables meanwhile.
-__global__ __launch_bounds__(kVisitsThreads) void visits_many_fold_kernel(double *scratch, int64_t n_entries, int nk,
-                                                                         double *out, int64_t table_stride) {
-    __shared__ double tile[kManyDesigns][kManyStride];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t e0 = (int64_t)blockIdx.x * 64;
-    for (int i = wave; i < 64; i += kVisitsThreads / 64) {
-        double v = 0.0;
-        if (e0 + i < n_entries) {
-            double *const p = scratch + (e0 + i) * kManyDesigns + lane;
-            v = *p;
-            if (v != 0.0) *p = 0.0;
-        }
-        tile[i][lane] = v;
-    }
-    __syncthreads();
-    if (e0 + lane >= n_entries) return;
-    for (int j = wave; j < nk; j += kVisitsThreads / 64) {
-        const double v = tile[lane][j];
-        if (v != 0.0) out[j * table_stride + e0 + lane] += v;
-    }
 }
 
 std::atomic<int> g_many_interleaved{1};   // wgrt_debug_set_reweight_layout
@@ -283,7 +257,7 @@ wgrt_status wgrt_visits_reweight_many(const wgrt_scene *s, const wgrt_window_pla
         hipLaunchKernelGGL(visits_reweight_many_kernel<true>, dim3((unsigned)blocks), dim3(kVisitsThreads), lds, st,
                            counts, ends, n_rows, C, tiles, s->tile_d, s->nl, s->nx, s->ny, view, lnscale, K, k0, scratch,
                            n_entries, wsums);
-        hipLaunchKernelGGL(visits_many_fold_kernel, dim3((unsigned)folds), dim3(kVisitsThreads), 0, st, scratch,
+        hipLaunchKernelGGL(visits_many_fold_kernel, dim3((unsigned)folds), dim3(kManyThreads), 0, st, scratch,
                            n_entries, nk, out + (int64_t)k0 * n_entries, n_entries);
         h = hipGetLastError();
     }

@@ -415,6 +415,252 @@ class HitList(_RecordList):
               "wgrt_hits_grid")
         return out
 
+    def _for_scene(self, scene: Scene) -> int:
+        """The stored record count for a reduction that needs the whole list: raises ``HitListOverflow`` for a list that
+        counted more than it stores (a re-weighted table of a truncated list is silently wrong).  Synchronises."""
+        if torch.device("cuda", scene.device) != self.device:
+            raise ValueError(f"the hit list is on {self.device}, the scene on device {scene.device}")
+        self.check_overflow()
+        return self.stored()
+
+    def source_counts(self, scene: Scene, R: int, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """The stored records counted per entry class on the device (``wgrt_hits_source_counts``): int64
+        ``[num_lmd, 2, R]``, ``[l, 0, r]`` the out-couplings at wavelength ``l`` of the rays with block index
+        ``r = gid mod R`` inside their FoV's eyebox rectangle, ``[l, 1, r]`` those beside it.  ``R``: rays per FoV x
+        wavelength block.  Adds into ``out`` when given.  Raises ``HitListOverflow`` for a list that overflowed."""
+        R = int(R)
+        if R < 1:
+            raise ValueError("R must be >= 1 rays per block")
+        n = self._for_scene(scene)
+        shape = (scene.num_lmd, 2, R)
+        if out is None:
+            out = torch.zeros(shape, dtype=torch.int64, device=self.device)
+        else:
+            _as_dev(out, torch.int64, "out", self.device)
+            if tuple(out.shape) != shape:
+                raise ValueError(f"out shape {tuple(out.shape)} != {shape}")
+        check(load().wgrt_hits_source_counts(scene.handle, self.buffer.data_ptr(), n, R, out.data_ptr(),
+                                             ctypes.c_void_p(_stream_handle(self.device, stream))),
+              "wgrt_hits_source_counts")
+        return out
+
+    def reweight_sources(self, scene: Scene, plan: WindowPlan, weights, out: torch.Tensor | None = None,
+                         sums: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """The window tables of K projector pupils from the stored records, without a re-trace
+        (``wgrt_hits_reweight_sources``): ``weights`` float64 ``[K, R]`` (an array or a tensor; ``source_weights`` makes
+        them), ``weights[k, r]`` the relative radiance of entry class ``r = gid mod R`` in source k, finite and in
+        ``[0, 1024]``.  Returns float64 ``[K, n_slabs, W]``: table k is the table the launches would have left had every
+        ray of class r carried ``weights[k, r]``; a row of ones gives their window table bit for bit.  ``sums``: int64
+        ``[K, 2, num_lmd]``, the weights' sum and sum of squares over the depositing records in quanta of 2^-32
+        (``ess_of_quanta``).  ``out`` and ``sums`` are added to when given.  Raises ``HitListOverflow`` for a list
+        that overflowed."""
+        if plan.device != scene.device:
+            raise ValueError(f"the plan is on device {plan.device}, the scene on device {scene.device}")
+        n = self._for_scene(scene)
+        w = weights if isinstance(weights, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float64))
+        if w.dim() != 2 or w.shape[0] < 1 or w.shape[1] < 1 or w.dtype != torch.float64:
+            raise ValueError("weights must be float64 [K >= 1, R >= 1]: one value per source and entry class")
+        w = w.to(self.device).contiguous()
+        if not bool((torch.isfinite(w) & (w >= 0) & (w <= SOURCE_MAX_WEIGHT)).all()):
+            raise ValueError(f"weights must be finite and in [0, {SOURCE_MAX_WEIGHT:g}]")
+        K, R = int(w.shape[0]), int(w.shape[1])
+        n_slabs = scene.num_lmd * scene.ny * scene.nx
+        for name, t, dtype, shape in (("out", out, torch.float64, (K, n_slabs, plan.W)),
+                                      ("sums", sums, torch.int64, (K, 2, scene.num_lmd))):
+            if t is not None:
+                _as_dev(t, dtype, name, self.device)
+                if tuple(t.shape) != shape:
+                    raise ValueError(f"{name} shape {tuple(t.shape)} != {shape}")
+        if out is None:
+            out = torch.zeros((K, n_slabs, plan.W), dtype=torch.float64, device=self.device)
+        check(load().wgrt_hits_reweight_sources(scene.handle, plan.handle, self.buffer.data_ptr(), n, w.data_ptr(), R, K,
+                                                out.data_ptr(), sums.data_ptr() if sums is not None else None,
+                                                ctypes.c_void_p(_stream_handle(self.device, stream))),
+              "wgrt_hits_reweight_sources")
+        return out
+
+
+SOURCE_MAX_WEIGHT = 1024.0   # csrc/wgrt_sources.h
+
+
+def hits_source_counts_host(records, nx: int, ny: int, num_lmd: int, R: int, out=None) -> np.ndarray:
+    """``HitList.source_counts`` on the host (``wgrt_hits_source_counts_host``; numpy arrays, no GPU needed): int64
+    ``[num_lmd, 2, R]``.  Adds into ``out`` when given."""
+    rec = np.ascontiguousarray(records, dtype=HIT_DTYPE)
+    shape = (int(num_lmd), 2, int(R))
+    if int(R) < 1:
+        raise ValueError("R must be >= 1 rays per block")
+    if out is None:
+        out = np.zeros(shape, dtype=np.int64)
+    elif out.dtype != np.int64 or not out.flags.c_contiguous or out.shape != shape:
+        raise ValueError(f"out must be a C-contiguous int64 array of shape {shape}")
+    check(load().wgrt_hits_source_counts_host(int(nx), int(ny), int(num_lmd), rec.ctypes.data, rec.shape[0], int(R),
+                                              out.ctypes.data), "wgrt_hits_source_counts_host")
+    return out
+
+
+def hits_reweight_sources_host(records, weights, nx: int, ny: int, num_lmd: int, scene_ranges, mask=None, step_y: int = 8,
+                               step_x: int = 12, out=None, sums=None):
+    """``HitList.reweight_sources`` on the host (``wgrt_hits_reweight_sources_host``; numpy arrays, no GPU needed)
+    through the same rule and with the same bits: ``records`` a ``HIT_DTYPE`` array, ``weights`` float64 ``[K, R]``,
+    ``scene_ranges`` the scene's ``eff_reg_FOV_range`` ``[nx, ny, 4]``, ``mask`` the plan's binary pupil mask (default
+    ``pupil_mask()``).  Returns ``(tables, sums)``, float64 ``[K, num_lmd * ny * nx, W]`` and int64
+    ``[K, 2, num_lmd]``; both are added to when given."""
+    from .AR_system_evaluation_functions import _square_mask
+    rec = np.ascontiguousarray(records, dtype=HIT_DTYPE)
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.ndim != 2 or w.shape[0] < 1 or w.shape[1] < 1:
+        raise ValueError("weights must be [K >= 1, R >= 1]: one value per source and entry class")
+    rg = np.ascontiguousarray(scene_ranges, dtype=np.float64)
+    if rg.shape != (int(nx), int(ny), 4):
+        raise ValueError(f"scene_ranges must have shape {(int(nx), int(ny), 4)}")
+    m = _square_mask(mask)
+    K, R = w.shape
+    shape = (K, int(num_lmd) * int(ny) * int(nx), _window_width(m, step_y, step_x))
+    if out is None:
+        out = np.zeros(shape, dtype=np.float64)
+    elif out.dtype != np.float64 or not out.flags.c_contiguous or out.shape != shape:
+        raise ValueError(f"out must be a C-contiguous float64 array of shape {shape}")
+    if sums is None:
+        sums = np.zeros((K, 2, int(num_lmd)), dtype=np.int64)
+    elif sums.dtype != np.int64 or not sums.flags.c_contiguous or sums.shape != (K, 2, int(num_lmd)):
+        raise ValueError(f"sums must be a C-contiguous int64 array of shape {(K, 2, int(num_lmd))}")
+    check(load().wgrt_hits_reweight_sources_host(int(nx), int(ny), int(num_lmd), rg.ctypes.data, m.ctypes.data, m.shape[0],
+                                                 int(step_y), int(step_x), rec.ctypes.data, rec.shape[0], w.ctypes.data,
+                                                 R, K, out.ctypes.data, sums.ctypes.data),
+          "wgrt_hits_reweight_sources_host")
+    return out, sums
+
+
+SOURCE_KEYS = ("centre", "diameter", "sigma", "te", "tm", "weights")
+
+
+def check_sources(sources, R: int) -> list:
+    """What ``source_weights`` can check without the entry points: ``sources`` as a list of dicts (a ``[K, R]`` array
+    becomes K dicts of explicit ``weights``), or ``ValueError`` naming the source -- an unknown key, ``weights`` beside
+    another key or of another length than R, a weight, ``te`` or ``tm`` that is negative or not finite, a ``diameter``
+    or ``sigma`` that is not positive and finite, a ``centre`` that is not a finite ``[x, y]``."""
+    R = int(R)
+    if R < 2 or R % 2:
+        raise ValueError(f"sources need an even number R >= 2 of rays per block (half TE, half TM), got {R}")
+    if isinstance(sources, (dict, str)) or not hasattr(sources, "__len__") or len(sources) == 0:
+        raise ValueError(f"sources must be a non-empty list of dicts or a [K, R] array, got {sources!r}")
+    if not all(isinstance(s, dict) for s in sources):
+        try:
+            arr = np.asarray(sources, dtype=np.float64)
+        except (TypeError, ValueError):
+            arr = None
+        if arr is None or arr.ndim != 2 or arr.shape[1] != R:
+            raise ValueError(f"sources must be a list of dicts or a [K, {R}] array of weights")
+        sources = [{"weights": row} for row in arr]
+    out = []
+    for k, s in enumerate(sources):
+        unknown = sorted(str(key) for key in set(s) - set(SOURCE_KEYS))
+        if unknown:
+            raise ValueError(f"source {k}: unknown key(s) {unknown}; the keys are {list(SOURCE_KEYS)}")
+        try:
+            if "weights" in s:
+                if len(s) > 1:
+                    raise ValueError(f"source {k}: 'weights' excludes the other keys")
+                w = np.array(s["weights"], dtype=np.float64)
+                if w.shape != (R,):
+                    raise ValueError(f"source {k}: weights must hold {R} values, got shape {w.shape}")
+                if not (np.isfinite(w).all() and (w >= 0).all()):
+                    raise ValueError(f"source {k}: a weight is negative or not finite")
+                out.append({"weights": w})
+                continue
+            d = {}
+            if "centre" in s:
+                c = np.asarray(s["centre"], dtype=np.float64)
+                if c.shape != (2,) or not np.isfinite(c).all():
+                    raise ValueError(f"source {k}: centre must be a finite [x, y], got {s['centre']!r}")
+                d["centre"] = [float(c[0]), float(c[1])]
+            for key in ("diameter", "sigma"):
+                if key in s:
+                    if isinstance(s[key], bool) or not (np.isfinite(float(s[key])) and float(s[key]) > 0):
+                        raise ValueError(f"source {k}: {key} must be positive and finite, got {s[key]!r}")
+                    d[key] = float(s[key])
+            for key in ("te", "tm"):
+                if key in s:
+                    if isinstance(s[key], bool) or not (np.isfinite(float(s[key])) and float(s[key]) >= 0):
+                        raise ValueError(f"source {k}: the factor {key} must be non-negative and finite, got {s[key]!r}")
+                    d[key] = float(s[key])
+            out.append(d)
+        except TypeError as e:
+            raise ValueError(f"source {k}: {e}") from e
+    return out
+
+
+def source_weights(points, R: int, sources) -> np.ndarray:
+    """The weights of K projector pupils for ``HitList.reweight_sources``: float64 ``[K, R]``.  ``points``: the entry
+    points ``[R / 2, 2]`` the rays were built from (entry class r starts at ``points[r mod (R / 2)]`` and is TE for
+    ``r < R / 2``, TM otherwise).  ``sources``: a list of dicts, or a ``[K, R]`` array of explicit weights.  ``{}`` is the
+    nominal source, the uniformly filled in-coupler with half the rays TE and half TM.  Keys: ``centre`` ``[x, y]``
+    (default: the centroid of ``points``); ``diameter``, a hard circular stop about the centre (weight 0 outside);
+    ``sigma``, a Gaussian apodisation ``exp(-d^2 / (2 sigma^2))`` of the distance d from the centre; ``te`` / ``tm``,
+    non-negative factors on the two halves (default 1 and 1); ``weights``, an explicit ``[R]`` array, which excludes
+    the other keys.  Every row is scaled to mean 1 over its R classes, so the tables' divisor stays ``R * num_iter`` and
+    efficiencies are per unit of projector power.  An unknown key, a negative or non-finite value, a source of zero total
+    weight or a weight above 1024 after scaling raises ``ValueError`` naming the source."""
+    R = int(R)
+    sources = check_sources(sources, R)
+    pts = np.asarray(points, dtype=np.float64)
+    if pts.ndim != 2 or pts.shape != (R // 2, 2) or not np.isfinite(pts).all():
+        raise ValueError(f"points must be a finite [R / 2, 2] array, got shape {pts.shape} for R = {R}")
+    out = np.empty((len(sources), R), dtype=np.float64)
+    for k, s in enumerate(sources):
+        if "weights" in s:
+            w = np.array(s["weights"], dtype=np.float64)
+        else:
+            centre = np.asarray(s.get("centre", pts.mean(axis=0)), dtype=np.float64)
+            d2 = ((pts - centre) ** 2).sum(axis=1)
+            w = np.ones(R // 2, dtype=np.float64)
+            if "diameter" in s:
+                w = np.where(d2 <= (float(s["diameter"]) / 2) ** 2, w, 0.0)
+            if "sigma" in s:
+                w = w * np.exp(-d2 / (2 * float(s["sigma"]) ** 2))
+            w = np.concatenate([float(s.get("te", 1.0)) * w, float(s.get("tm", 1.0)) * w])
+        total = w.sum()
+        if not total > 0:
+            raise ValueError(f"source {k}: the source has zero total weight (nothing is emitted)")
+        w = w * (R / total)
+        if w.max() > SOURCE_MAX_WEIGHT:
+            raise ValueError(f"source {k}: a weight is {w.max():g} after scaling to mean 1, above {SOURCE_MAX_WEIGHT:g}: "
+                             f"the source keeps too small a part of the {R} entry classes")
+        out[k] = w
+    return out
+
+
+def source_map(points, counts, H: int, W: int):
+    """The entrance-pupil map on the host: ``(delivered, launched)``.  ``delivered`` int64 ``[num_lmd, 2, H, W]``: per
+    wavelength and input polarisation (0 TE, 1 TM), the out-couplings inside the eyebox (``counts[:, 0]`` of
+    ``HitList.source_counts``, int64 ``[num_lmd, 2, R]``) of the rays that entered in each cell; ``launched`` int64
+    ``[H, W]``: the entry points per cell (each launches one ray per FoV, wavelength, polarisation and iteration).  The
+    cells cover the bounding box of ``points`` ``[R / 2, 2]``, ``FootprintPlan``'s rule ``ix = floor((x - x0) / cell_x)``,
+    ``iy = floor((y - y0) / cell_y)``, with the box's upper edges counted into the last cell, so that nothing is dropped."""
+    pts = np.asarray(points, dtype=np.float64)
+    c = np.asarray(counts.cpu() if hasattr(counts, "cpu") else counts)
+    H, W = int(H), int(W)
+    if not (1 <= H <= 4096 and 1 <= W <= 4096):
+        raise ValueError("H and W must be 1 .. 4096")
+    if pts.ndim != 2 or pts.shape[1] != 2 or pts.shape[0] < 1 or not np.isfinite(pts).all():
+        raise ValueError("points must be a finite [R / 2, 2] array")
+    P = pts.shape[0]
+    if c.ndim != 3 or c.shape[1] != 2 or c.shape[2] != 2 * P:
+        raise ValueError(f"counts must be [num_lmd, 2, {2 * P}], got shape {c.shape}")
+    (x0, y0), (x1, y1) = pts.min(axis=0), pts.max(axis=0)
+    cx, cy = (x1 - x0) / W or 1.0, (y1 - y0) / H or 1.0
+    ix = np.minimum(np.floor((pts[:, 0] - x0) / cx).astype(np.int64), W - 1)
+    iy = np.minimum(np.floor((pts[:, 1] - y0) / cy).astype(np.int64), H - 1)
+    cell = iy * W + ix
+    launched = np.bincount(cell, minlength=H * W).astype(np.int64).reshape(H, W)
+    inside = c[:, 0].astype(np.int64).reshape(c.shape[0], 2, P)          # [l, TE / TM, point]
+    delivered = np.zeros((c.shape[0], 2, H * W), dtype=np.int64)
+    for l in range(c.shape[0]):
+        for p in range(2):
+            np.add.at(delivered[l, p], cell, inside[l, p])
+    return delivered.reshape(c.shape[0], 2, H, W), launched
+
 
 def check_hits(hit_list: HitList) -> None:
     """Raise ``HitListOverflow`` if the list counted more out-couplings than it stores.  Synchronises."""

@@ -31,7 +31,9 @@ Same flow as the reference script, on the MI355X kernel:
    (``wgrt_trace_visits``): which grating to change; with ``what_if={channel: scale}`` (``--what-if``) the same rays,
    re-weighted, give the figures of the scaled design without a re-trace; with ``designs=[...]`` (``--designs``) or
    ``tolerance=sigma`` (``--tolerance``) the same for K listed or randomly drawn designs in one pass
-   (``wgrt_visits_reweight_many``): candidates side by side, or the band every figure lands in;
+   (``wgrt_visits_reweight_many``): candidates side by side, or the band every figure lands in; with
+   ``sources=[...]`` (``--sources``) the hit list, re-weighted by each ray's entry class, gives the figures of K
+   projector pupils -- smaller, decentred, apodised, TE or TM -- from the one trace (``wgrt_hits_reweight_sources``);
 6. the "Eyebox Center View.png" export (MAIN:199-203): the evaluated image at the first eye row,
    last eye column, as 8-bit RGB, rows flipped (``eyebox_center_view``, written without OpenCV).
 
@@ -67,7 +69,8 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
         keep_image: bool = False, budget: bool = False, error_bars: int = 0, estimator: str = "analog",
         footprint=None, hits=None, paths=None, paths_capacity=None, paths_footprint=None, sensitivity=None,
         what_if=None, polarisation: bool = False, analyser=None, analyser_frame: str = "fov", designs=None,
-        tolerance=None, tolerance_designs: int = 64, tolerance_seed: int = 0, tolerance_channels=None) -> dict:
+        tolerance=None, tolerance_designs: int = 64, tolerance_seed: int = 0, tolerance_channels=None,
+        sources=None, source_counts: bool = False, source_map=None) -> dict:
     """The reference script's job on this engine; returns its printed quantities and arrays.
     ``points``: the R/2 in-coupler origins to use (default: sampled, GRTF:12-23, seeded by
     ``point_seed``); ``png``: where to write the "Eyebox Center View" image (needs ``evaluate``).
@@ -225,7 +228,50 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
     analyser, ``analysed`` (``theta_deg``, ``frame``, ``table``, ``A``, ``efficiency`` and, with ``evaluate``,
     ``delta_e``, ``U_fov``, ``U_EB``).  Everything returned before is bit-identical with and without it.  ``budget=True``,
     ``error_bars``, ``estimator="expected"``, ``footprint``, ``hits``, ``paths``, ``sensitivity`` and ``what_if`` with it
-    raise ``ValueError`` before any GPU work."""
+    raise ``ValueError`` before any GPU work.
+
+    ``sources``: a list of source dicts (``engine.source_weights``: ``{}`` the nominal source; ``centre``, ``diameter``,
+    ``sigma``, ``te``, ``tm`` or explicit ``weights``) or a ``[K, R]`` array of weights (None: off): the figures of K
+    projector pupils from the one trace.  A ray's entry point and input polarisation are a function of its global id, so
+    each rank re-weights its own hit list on the device after the traces (``HitList.reweight_sources``,
+    ``wgrt_hits_reweight_sources``): every out-coupling deposits its entry class's weight instead of 1.  This is exact,
+    not an approximation, and the sources share the rays, so their differences carry far less noise than two runs'.  It
+    implies ``hits=True`` when ``hits`` is not given, needs ``eyebox="windows"`` and combines and excludes exactly as
+    ``hits`` does.  The tables' bytes are computed up front and printed; more than the device has free raises
+    ``ValueError`` naming the largest K that fits.  The tables and the integer weight sums of several GPUs are
+    sum-reduced to rank 0.  Printed: one line per source with the efficiencies, the three figures and the smallest
+    effective sample size.  Returned as ``sources``: ``weights`` ``[K, R]``, ``table`` ``[K, n_slabs, 57]``, ``A``,
+    ``efficiency`` ``[K, L]``, ``sums``, ``ess`` ``[K, L]`` and, with ``evaluate``, ``delta_e``, ``U_fov``, ``U_EB``
+    ``[K]``; source ``{}`` has the job's own table and figures bit for bit.  Every row of weights has mean 1, so the
+    efficiencies are per unit of projector power.  A stop that keeps a fraction of the entry points keeps that fraction
+    of the rays: judge a source with its effective sample size beside it.
+
+    ``source_counts=True`` (needs ``hits``): also the hit list counted per entry class on the device
+    (``HitList.source_counts``), returned as ``source_counts`` (int64 ``[num_lmd, 2, R]``: inside / beside the eyebox),
+    and printed per wavelength: the delivered efficiency of the TE half and of the TM half of the input.
+    ``source_map=(H, W)``: also the entrance-pupil map ``engine.source_map`` of those counts, returned as
+    ``source_map`` (``delivered`` ``[num_lmd, 2, H, W]``, ``launched`` ``[H, W]``)."""
+    if sources is not None:
+        from .engine import check_sources
+        sources = check_sources(sources, int(num_rays_per_FoV))
+        if eyebox != "windows":
+            raise ValueError("sources re-weights the hit list into window tables: it needs eyebox='windows'")
+        if hits is None or hits is False:
+            hits = True
+    if source_map is not None:
+        if len(tuple(source_map)) != 2 or not all(1 <= int(v) <= 4096 for v in source_map):
+            raise ValueError(f"source_map must be (H, W) cells, each 1 .. 4096, got {source_map!r}")
+        source_map = (int(source_map[0]), int(source_map[1]))
+        if not source_counts:
+            raise ValueError("source_map is a map of the source counts: it needs source_counts=True")
+    if source_counts:
+        if hits is None or hits is False:
+            raise ValueError("source_counts counts the hit list per entry class: it needs hits")
+        if int(num_rays_per_FoV) % 2:
+            raise ValueError("source_counts needs an even num_rays_per_FoV: half the entry classes are TE, half TM")
+    if sources is not None and points is not None:   # the whole check before any GPU work where the origins are given
+        from .engine import source_weights
+        source_weights(points, int(num_rays_per_FoV), sources)
     if analyser_frame not in ("fov", "lab"):
         raise ValueError(f"analyser_frame must be 'fov' or 'lab', got {analyser_frame!r}")
     if analyser is not None:
@@ -399,6 +445,7 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
             from .engine import HitList
             cap = -(-job.shard.n_rays * int(num_iter) // 8) if hits is True else int(hits)
             job.hits = HitList(cap, job.dev)
+        src = _sources_set_up(job, sources) if sources is not None else None
         job.paths = None
         if paths is not None:
             import torch
@@ -464,6 +511,14 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
             from .distributed import reduce_eyebox
             fmap = reduce_eyebox(job.footprint[1])
         records = _gather_hits(job) if job.hits is not None else None
+        stables = ssums = scounts = None
+        if src is not None:   # every rank re-weights its own list; grid-valued doubles and integers: both add exactly
+            from .distributed import reduce_eyebox
+            job.hits.reweight_sources(job.scene, job.windows[0], src.weights_dev, out=src.tables, sums=src.sums)
+            stables, ssums = reduce_eyebox(src.tables), reduce_eyebox(src.sums)
+        if source_counts:     # integer counts: the ranks' add exactly
+            from .distributed import reduce_eyebox
+            scounts = reduce_eyebox(job.hits.source_counts(job.scene, job.R))
         path_records = path_map = path_sel = None
         if job.paths is not None:
             from .distributed import reduce_eyebox
@@ -507,6 +562,10 @@ def run(num_FOV_x: int = 100, num_FOV_y: int = 75, num_rays_per_FoV: int = 5000,
             _report_ensemble(job, out, job.visits.ensemble, etables, esums, evaluate, evaluate_on)
         if stokes is not None:
             _report_polarisation(job, out, table, stokes, analyser, analyser_frame, evaluate, evaluate_on)
+        if scounts is not None:
+            _report_source_counts(job, out, scounts, source_map)
+        if stables is not None:
+            _report_sources(job, out, src, stables, ssums, evaluate, evaluate_on)
         out["post_seconds"] = time.perf_counter() - t_post
         job.say(f"Post-processing time  : {out['post_seconds']:.4f} s  (eyebox reduced "
                 f"{'by the trace' if eyebox == 'windows' else 'on the ' + eyebox})")
@@ -569,7 +628,7 @@ def _set_up(nx, ny, R, num_iter, lambdas, lut_dir, lut_seed, lut_profile, point_
                                   dev=dev, say=say, scene=scene, shards=shards, shard=shards[rank], rays=rays, rng=rng,
                                   eb=eb, windows=(plan, plan.new_table(scene, replicas=replicas)) if windows else None,
                                   stats=new_stats(dev), num_rays=num_rays, fate=fate, census=census,
-                                  replicas=replicas, geom=geom)
+                                  replicas=replicas, geom=geom, points=points)
         finally:
             if plan is not None:
                 plan.close()
@@ -810,6 +869,80 @@ def _report_ensemble(job, out: dict, ens, tables, sums, evaluate: bool, evaluate
         job.say("  note: scaled up -- unbiased only where the state's branch efficiencies still sum to <= 1; "
                 "check the scaled LUTs (luts.scale_channel) or confirm with a direct run")
     out["ensemble"] = e
+
+
+def _sources_set_up(job, sources):
+    """The sources' record: ``weights`` float64 ``[K, R]`` (``engine.source_weights`` over the job's origins), their
+    device copy, and the two device tensors the re-weighting adds to.  The tables' bytes are printed and checked against
+    the device's free memory first."""
+    import torch
+
+    from .engine import source_weights
+    weights = source_weights(job.points, job.R, sources)
+    K = weights.shape[0]
+    n_slabs, W = job.windows[1].shape
+    # a table; the re-weighting's chunk scratch, the weights [K, R] and their transposed copy [R, 64 * chunks]
+    per_source = n_slabs * W * 8
+    fixed = lambda k: n_slabs * W * ENSEMBLE_CHUNK * 8 + job.R * (k + -(-k // ENSEMBLE_CHUNK) * ENSEMBLE_CHUNK) * 8
+    free = int(torch.cuda.mem_get_info(job.dev)[0])
+    job.say(f"Source what-ifs       : {K} sources, tables {K * per_source / 1e6:,.1f} MB "
+            f"(+ {fixed(K) / 1e6:,.1f} MB while re-weighting; {free / 1e6:,.0f} MB free)")
+    if K * per_source + fixed(K) > free:
+        fits = K
+        while fits > 0 and fits * per_source + fixed(fits) > free:
+            fits -= 1
+        raise ValueError(f"sources: {K} tables of {per_source / 1e6:,.1f} MB exceed the device's free memory "
+                         f"({free / 1e6:,.0f} MB); the largest K that fits is {fits}")
+    return SimpleNamespace(weights=weights, weights_dev=torch.from_numpy(weights).to(job.dev),
+                           tables=torch.zeros((K, n_slabs, W), dtype=torch.float64, device=job.dev),
+                           sums=torch.zeros((K, 2, job.scene.num_lmd), dtype=torch.int64, device=job.dev))
+
+
+def _report_sources(job, out: dict, src, tables, sums, evaluate: bool, evaluate_on: str) -> None:
+    """The sources' figures into ``out["sources"]`` and printed, one line per source (as ``_report_ensemble``'s)."""
+    from .AR_system_evaluation_functions import evaluation_ensemble
+    from .engine import ess_of_quanta
+    shape = job.scene.eb_shape()
+    t = tables.cpu().numpy()
+    K = t.shape[0]
+    A = t[:, :, 0].reshape((K,) + tuple(shape[:-2])).astype(np.float32) / job.num_rays / job.num_iter
+    eff = np.array([[float(np.sum(A[k, l] * 3)) for l in range(A.shape[1])] for k in range(K)], dtype=np.float64)
+    ess = ess_of_quanta(sums.cpu().numpy())
+    s = dict(weights=src.weights, table=t, A=A, efficiency=eff, ess=ess, sums=sums.cpu().numpy())
+    figures = {}
+    if evaluate:
+        figures = evaluation_ensemble(tables if evaluate_on == "device" else t, shape, job.R * job.num_iter, evaluate_on)
+        s.update(figures)
+    names = {0: "Blue", 1: "Green", 2: "Red"}
+    lam = [names.get(l, str(l)) for l in range(eff.shape[1])]
+    job.say(f"Source what-ifs: {K} sources (the same rays, re-weighted by entry class; per unit of projector power)")
+    for k in range(K):
+        line = f"  source {k:3d}: " + "  ".join(f"{n} {eff[k, l] * 100:7.3f} %" for l, n in enumerate(lam))
+        if figures:
+            line += (f"  dE {figures['delta_e'][k]:6.2f}  U_fov {figures['U_fov'][k] * 100:6.2f} %"
+                     f"  U_EB {figures['U_EB'][k] * 100:6.2f} %")
+        job.say(line + f"  min ESS {ess[k].min():,.0f}")
+    out["sources"] = s
+
+
+def _report_source_counts(job, out: dict, counts, cells) -> None:
+    """The per-class counts into ``out["source_counts"]``, per wavelength the delivered efficiency of the TE half and of
+    the TM half of the input printed, and, with ``cells = (H, W)``, the entrance-pupil map into ``out["source_map"]``."""
+    c = counts.cpu().numpy()
+    out["source_counts"] = c
+    half = job.R // 2
+    launched = job.nx * job.ny * half * job.num_iter                   # rays of one polarisation at one wavelength
+    names = {0: "Blue", 1: "Green", 2: "Red"}
+    used = int((c[:, 0, :half].sum(axis=0) + c[:, 0, half:].sum(axis=0) > 0).sum())
+    job.say(f"Delivered light by input polarisation ({used:,} of {half:,} entry points delivered any)")
+    job.say(f"  {'':10s}{'TE half':>12s}{'TM half':>12s}")
+    for l in range(c.shape[0]):
+        te, tm = int(c[l, 0, :half].sum()), int(c[l, 0, half:].sum())
+        job.say(f"  {names.get(l, str(l)):10s}{te / launched * 100:11.3f}%{tm / launched * 100:11.3f}%")
+    if cells is not None:
+        from .engine import source_map
+        delivered, per_cell = source_map(job.points, c, *cells)
+        out["source_map"] = dict(delivered=delivered, launched=per_cell)
 
 
 def _report_polarisation(job, out: dict, table, stokes, analyser, frame: str, evaluate: bool, evaluate_on: str) -> None:
@@ -1127,6 +1260,18 @@ def main(argv=None):
                     help="the channels that vary, as patterns over their names, e.g. 'r4[*].b3,r5[*].b3' (default: all)")
     ap.add_argument("--ensemble-out", default="", metavar="FILE.npz",
                     help="save the ensemble's scales, tables, weight sums and figures there (numpy)")
+    ap.add_argument("--sources", default="", metavar="FILE.json",
+                    help="also the figures of every projector pupil of a list, from the one trace's hit list re-weighted "
+                         "by entry class: a JSON list of objects with the keys centre [x, y], diameter, sigma, te, tm or "
+                         "weights ({}: the nominal source); needs --eyebox windows; implies --hits")
+    ap.add_argument("--sources-out", default="", metavar="FILE.npz",
+                    help="save the sources' weights, tables, weight sums and figures there (numpy)")
+    ap.add_argument("--source-counts", action="store_true",
+                    help="with --hits: also count the out-couplings per entry class and print, per wavelength, the "
+                         "delivered efficiency of the TE half and of the TM half of the input")
+    ap.add_argument("--source-map", default="", metavar="HxW",
+                    help="with --source-counts: also the entrance-pupil map of H x W cells, delivered and launched")
+    ap.add_argument("--source-map-out", default="", metavar="FILE.npz", help="save the entrance-pupil map there (numpy)")
     ap.add_argument("--polarisation", action="store_true",
                     help="also the polarisation of the delivered light: Stokes tables beside the window table, the mean "
                          "Stokes vector and degree of polarisation per wavelength; needs --eyebox windows; not with "
@@ -1196,6 +1341,19 @@ def main(argv=None):
         ap.error(f"--tolerance-designs takes K >= 2 (the nominal design and one drawn), got {a.tolerance_designs}")
     if designs is not None and a.tolerance is not None:
         ap.error("--designs and --tolerance exclude each other")
+    sources = None
+    if a.sources:
+        try:
+            with open(a.sources) as f:
+                sources = json.load(f)
+        except (OSError, ValueError) as e:
+            ap.error(f"--sources: cannot read {a.sources!r}: {e}")
+        if not isinstance(sources, list) or not sources or not all(isinstance(d, dict) for d in sources):
+            ap.error(f"--sources takes a JSON file holding a non-empty list of source objects, got {a.sources!r}")
+    if a.source_map and not a.source_counts:
+        ap.error("--source-map needs --source-counts")
+    if a.source_counts and a.hits is None and sources is None:
+        ap.error("--source-counts needs --hits")
     footprint = cells("--footprint", a.footprint)
     paths_footprint = cells("--paths-footprint", a.paths_footprint)
     res = run(a.num_fov_x, a.num_fov_y, a.rays_per_fov, a.num_iter, lut_dir=a.lut_dir, lut_seed=a.lut_seed,
@@ -1208,7 +1366,12 @@ def main(argv=None):
               what_if=what_if, polarisation=a.polarisation, analyser=a.analyser, analyser_frame=a.analyser_frame,
               designs=designs, tolerance=a.tolerance, tolerance_designs=a.tolerance_designs,
               tolerance_seed=a.tolerance_seed,
-              tolerance_channels=[p for p in a.tolerance_channels.split(",") if p] or None)
+              tolerance_channels=[p for p in a.tolerance_channels.split(",") if p] or None,
+              sources=sources, source_counts=a.source_counts, source_map=cells("--source-map", a.source_map))
+    if a.sources_out and "sources" in res:   # (rank 0 has the tables)
+        np.savez(a.sources_out, **{k: v for k, v in res["sources"].items() if isinstance(v, np.ndarray)})
+    if a.source_map_out and "source_map" in res:
+        np.savez(a.source_map_out, counts=res["source_counts"], **res["source_map"])
     if a.ensemble_out and "ensemble" in res:   # (rank 0 has the tables)
         e = res["ensemble"]
         np.savez(a.ensemble_out, channels=np.array(e["channels"]),
@@ -1232,6 +1395,10 @@ def main(argv=None):
             lists = lambda d: {k: (lists(v) if isinstance(v, dict) else np.asarray(v).tolist()) for k, v in d.items()}
             keep["ensemble"] = lists({k: v for k, v in keep["ensemble"].items()
                                       if k in ("efficiency", "ess", "delta_e", "U_fov", "U_EB", "summary", "channels")})
+        if "sources" in keep:   # (the per-source figures go as lists; the weights and the tables stay out)
+            keep["sources"] = {k: np.asarray(v).tolist() for k, v in keep["sources"].items()
+                               if k in ("efficiency", "ess", "delta_e", "U_fov", "U_EB")}
+        keep.pop("source_map", None)
         with open(a.json, "w") as f:
             json.dump(keep, f, indent=1)
     if dist.is_initialized():

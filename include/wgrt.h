@@ -646,6 +646,54 @@ wgrt_status wgrt_hits_grid(const wgrt_scene *scene, const wgrt_hit *hits, int64_
 wgrt_status wgrt_hits_grid_host(int32_t nx, int32_t ny, int32_t num_lmd, const double *scene_ranges, const wgrt_hit *hits,
                                 int64_t n, const double *ranges, int32_t H, int32_t W, float *grid);
 
+/* Source what-ifs: a hit list re-weighted for K projector pupils, and counted per entry class (new symbols within ABI 9,
+ * looked up by name; the rule is stated once in csrc/wgrt_sources.h).
+ *
+ * A ray's entry point and input polarisation are a pure function of its global id: with R rays per FoV x wavelength
+ * block, ray gid has the block index r = gid mod R, starts at points[r mod (R / 2)] and is TE for r < R / 2, TM
+ * otherwise (wgrt_rays_init).  Rays are independent, so a source that emits class r with relative radiance w[r] delivers
+ * exactly the table in which every out-coupling deposits w[gid mod R] instead of 1.  A record with gid < 0 is dropped.
+ *
+ * wgrt_hits_source_counts: counts is DEVICE int64 [num_lmd, 2, R], 8-B aligned, ADDED to.  A record whose tile is below
+ * num_lmd * nx * ny adds 1 to counts[l][0][gid mod R] when its flag bit 0 is set (inside its FoV's eyebox rectangle) and
+ * to counts[l][1][gid mod R] when it is clear (beside it), l = tile / (nx * ny): the flag decides, not whether the
+ * aliased grid offset was stored.  One thread per record, 64-bit integer atomics: the same bits for any record order.
+ * R < 1, n < 0, a NULL or misaligned pointer are WGRT_ERR_INVALID_ARGUMENT; n == 0 is WGRT_OK without a launch.
+ *
+ * wgrt_hits_reweight_sources:
+ *   weights  DEVICE float64 [K, R], 8-B aligned: source k emits class r with relative radiance weights[k][r].  Finite
+ *            and 0 <= w <= 1024; the device entry point does not look (the host twin and the Python layer do): a
+ *            weight outside gives a table without meaning, never a write out of bounds.
+ *   out      DEVICE float64 [K, n_slabs, W], ADDED to: a record that counts -- flag bit 0 set, tile below
+ *            num_lmd * nx * ny, gid >= 0 -- deposits q = rint(w * 2^32) * 2^-32, w = weights[k][gid mod R], into table k
+ *            at the entries wgrt_trace_windows adds 1 to for that out-coupling: its bin is the trace's own (the scene's
+ *            range, 80 x 120, the aliasing and the [0, total) guard of wgrt_hits_grid at ranges == NULL), its slab comes
+ *            from the offset.  Sums on the 2^-32 grid are exact and order-free while an entry stays below 2^21, and a
+ *            weight of 1 deposits exactly 1.0: a row of ones gives the launches' window table bit for bit.  q == 0
+ *            deposits nothing.
+ *   wsums    NULL, or DEVICE int64 [K, 2, num_lmd], 8-B aligned, ADDED to, as wgrt_visits_reweight_many keeps them:
+ *            every depositing record adds rint(q * 2^32) to wsums[k][0][l] and rint(q * q * 2^32) to wsums[k][1][l].
+ * A workgroup reads a record once for a chunk of 64 sources, a lane per source.  The call allocates and frees on `stream`
+ * the quantised, transposed weights [R, 64 * ceil(K / 64)] (float64) and one chunk's deposits [n_slabs * W, 64], which a
+ * second kernel adds into the chunk's tables.  A plan on another device than the scene, K < 1, R < 1, n < 0, a NULL or
+ * misaligned pointer, more than 2^31 * 64 records or 65535 chunks are WGRT_ERR_INVALID_ARGUMENT.  n == 0 is WGRT_OK
+ * without a launch.  Asynchronous on stream.
+ * The _host twins run the same rule over HOST pointers (no GPU needed) and give the same bits: the scene is stated by
+ * nx, ny, num_lmd and scene_ranges (HOST float64 [nx, ny, 4], eff_reg_FOV_range), the plan by its mask, as
+ * wgrt_visits_reweight_many_host states them.  wgrt_hits_reweight_sources_host also refuses a weight that is not finite
+ * or outside [0, 1024]. */
+wgrt_status wgrt_hits_source_counts(const wgrt_scene *scene, const wgrt_hit *hits, int64_t n, int64_t R, int64_t *counts,
+                                    void *stream);
+wgrt_status wgrt_hits_source_counts_host(int32_t nx, int32_t ny, int32_t num_lmd, const wgrt_hit *hits, int64_t n,
+                                         int64_t R, int64_t *counts);
+wgrt_status wgrt_hits_reweight_sources(const wgrt_scene *scene, const wgrt_window_plan *plan, const wgrt_hit *hits,
+                                       int64_t n, const double *weights, int64_t R, int32_t K, double *out,
+                                       int64_t *wsums, void *stream);
+wgrt_status wgrt_hits_reweight_sources_host(int32_t nx, int32_t ny, int32_t num_lmd, const double *scene_ranges,
+                                            const float *mask, int32_t ms, int32_t step_y, int32_t step_x,
+                                            const wgrt_hit *hits, int64_t n, const double *weights, int64_t R, int32_t K,
+                                            double *out, int64_t *wsums);
+
 /* Ray paths: every draw of selected rays as a record, and a path list reduced to a footprint map (new symbols within
  * ABI 9, looked up by name; the rule is stated once in csrc/wgrt_paths.h).
  *
