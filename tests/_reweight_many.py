@@ -6,15 +6,17 @@ from tests import _visits as V
 
 
 def crafted_rows(c, n_rows=37, seed=7, num_lmd=3):
-    """``(counts uint32 [n_rows, 70], ends [n_rows], deposits bool [n_rows])``: counts 70 % zeros and the rest 1 .. 3, row
-    0 all zero and row 1 (when there is one) holding a count of 40; ends drawn inside each row's FoV's range; about one
-    row in six not delivered (flags 2 or 0) and about one in nine with a tile index at or beyond the scene's count."""
+    """``(counts uint32 [n_rows, C], ends [n_rows], deposits bool [n_rows])``, C the channel count of the case's geometry
+    (70 on the default design): counts 70 % zeros and the rest 1 .. 3, row 0 all zero and row 1 (when there is one)
+    holding a count of 40 (in channel 17, or the last one of a narrower table); ends drawn inside each row's FoV's
+    range; about one row in six not delivered (flags 2 or 0) and about one in nine with a tile index at or beyond the
+    scene's count."""
     rng = np.random.default_rng(seed)
     C = 6 + 4 * c.geom.num_fc_slices + 6 * c.geom.num_oc_slices
     counts = np.where(rng.random((n_rows, C)) < 0.7, 0, rng.integers(1, 4, (n_rows, C))).astype(np.uint32)
     counts[0] = 0
     if n_rows > 1:
-        counts[1, 17] = 40
+        counts[1, min(17, C - 1)] = 40
     rg = c.geom.eff_reg_FOV_range
     n_tiles = num_lmd * c.nx * c.ny
     ends = np.zeros(n_rows, V.DTYPE)

@@ -57,20 +57,11 @@ def n_channels(nfc, noc):
     return int(lib().wgrt_oracle_visit_channels(nfc, noc))
 
 
-def config(nx, ny, lambdas, R, seed=0, profile="default", point_seed=1):
-    """A full-colour job on the design geometry (the shapes of ``tests/test_gpu_paths.py``), without torch."""
-    from types import SimpleNamespace
-
-    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.couplers_coor import design_geometry
-    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.luts import synthetic_luts
-    from gpu_ray_tracing_for_waveguide_based_ar_display_amd.rays import build_rays, generate_points_in_polygon, rng_seeds
-    geom = design_geometry(nx, ny)
-    pts = generate_points_in_polygon(geom.IC, R // 2, rng=np.random.default_rng(point_seed))
-    rays = build_rays(pts, nx, ny, lambdas, R)
-    N = rays["x"].shape[0]
-    return SimpleNamespace(geom=geom, luts=synthetic_luts(geom, seed=seed, profile=profile), rays=rays, N=N, R=R, nx=nx,
-                           ny=ny, lambdas=list(lambdas), wavelength=None, fresh_rng=lambda: rng_seeds(N),
-                           eb_shape=lambda: (3, ny, nx, EB_NY, EB_NX))
+def config(nx, ny, lambdas, R, seed=0, profile="default", point_seed=1, design="D16"):
+    """A full-colour job on the design geometry (the shapes of ``tests/test_gpu_paths.py``), without torch: the one
+    statement of it is ``tests/_designs.config``; ``design`` names another waveguide design."""
+    from tests import _designs
+    return _designs.config(design, nx, ny, lambdas, R, seed=seed, profile=profile, point_seed=point_seed)
 
 
 def checker(sc: oracle.OracleScene, rays: dict, rng: np.ndarray, launches: int = 1, gid_offset: int = 0,

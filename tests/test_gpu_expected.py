@@ -58,7 +58,7 @@ def _case(name):
             _cases[name] = SimpleNamespace(geom=c.geom, luts=crafted_luts(c.luts, kind), rays=c.rays, N=c.N,
                                            fresh_rng=c.fresh_rng, eb_shape=c.eb_shape,
                                            wavelength=getattr(c, "wavelength", None))
-        elif name in KT.CASES:   # the kernel table's four cases (tests/_kernel_table.py), shared by every sink module
+        elif KT.is_case(name):   # the kernel table's four cases (tests/_kernel_table.py), shared by every sink module
             _cases[name] = KT.case(name)
         else:
             _cases[name] = GoldenCase(name) if name in FIXTURES else _config(**_CONFIGS[name])

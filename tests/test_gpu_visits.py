@@ -49,7 +49,7 @@ _cases, _checked = {}, {}
 
 def _case(name):
     if name not in _cases:
-        if name in KT.CASES:   # the kernel table's four cases (tests/_kernel_table.py), shared by every sink module
+        if KT.is_case(name):   # the kernel table's four cases (tests/_kernel_table.py), shared by every sink module
             _cases[name] = KT.case(name)
         else:
             _cases[name] = GoldenCase(name) if name in FIXTURES else _config(**_CONFIGS[name])

@@ -119,7 +119,8 @@ def test_host_twins_equal_the_numpy_restatement():
     np.testing.assert_array_equal(got, sens)
     assert got[:, :, 0].sum() == counts[delivered].sum() > 0
     # the deposits of every delivered ray: its one out-coupling; its one in-coupling
-    names = visit_channels((7, 6))
+    names = visit_channels((c.geom.num_fc_slices, c.geom.num_oc_slices))
+    assert len(names) == counts.shape[1] == 70
     b3 = [k for k, n in enumerate(names) if n.endswith(".b3")]
     np.testing.assert_array_equal(got[b3].sum(axis=0), dep.astype(np.float64))
     np.testing.assert_array_equal(got[0] + got[1], dep.astype(np.float64))
